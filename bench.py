@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json's metric on BASELINE.json's configs.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg3|cfg4|cfg5]
+    python bench.py --gpus N --steps K --warmup W [--config cfg3|cfg4|cfg5] [--full] [--dump-outputs DIR]
     (N>1: started bare it launches `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...` itself, as a
      child process, and relays rank 0's JSON line; started under torch.distributed.run it is one of the ranks)
 
@@ -9,8 +9,8 @@
     N = 1: a step is ONE kernel launch writing one frame (the hot path, main.js:184-199 + :216-451, through the C ABI's
     rt_render_tiles_device).  N > 1: a step is ONE frame, row-tiled over the N ranks and whole on rank 0 after one collective /
     barrier - north_star's form, strong scaling: `value`, with `efficiency_vs_n1` and `predicted` (what the links allow, stated
-    per N).  The batch form (N frames per step, frame f whole on rank f, every directed link in use; weak scaling) is measured
-    in the same run and rides in the line as `batch_mode`.
+    per N, with --full).  With --full the batch form (N frames per step, frame f whole on rank f, every directed link in use;
+    weak scaling) is measured in the same run and rides in the line as `batch_mode`.
 --config cfg4: BASELINE configs[3] — ONE 7680x4320 H8 frame per step, row-tiled over the N ranks and whole on rank 0 after
     one collective / barrier (strong scaling: the frame is fixed, per-GPU work shrinks with N).
 --config cfg5: BASELINE configs[4] — ONE 16384x16384 frame, 2x2 supersample, 64 spheres, depth 5, the same way.
@@ -38,7 +38,14 @@ The scene is resident in HBM before the timed region and the frames stay in HBM 
 Before the W warm-up steps the GPU is brought to steady clocks: trains of launches until two consecutive trains agree within
 1 % (at least 50 ms), so a short timed region (the driver's --steps 20) measures the steady-state kernel.
 
-Rank 0 prints ONE JSON line.  `roofline` prices the trace kernel against the HBM-store roofline the metric names (4 algorithmic
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set-up, steady clocks, the W warm-up steps and the
+K timed steps; its line holds `value` (Mpixel/s over the timed steps), `ms_per_step` and how the frames were made (`config`).
+--dump-outputs DIR then writes the frame of the last timed step (see dump_outputs).
+
+--full adds everything else, after the timed steps: the kernel's own time on a train of launches, a parity check of the frames
+against the reference's rows, work counters, the store fill, the cold-frame / moving-camera legs, the reference's own scene, the
+CPU baseline, and at N>1 the one-GPU reference (`efficiency_vs_n1`) and the per-N expectation; a frame that differs from the
+reference's rows by more than 1 LSB then fails the run.  `roofline` prices the trace kernel against the HBM-store roofline the metric names (4 algorithmic
 bytes per pixel); `roofline.traffic` and `fp64_valu.measured` come from rocprofv3 PMC passes over a short child run of this
 same command (N=1; --no-pmc or a missing rocprofv3 fall back to the committed profile and say so).  The path is FP64-VALU bound,
 so `fp64_valu` prices it against that bound: `measured` from the SQ_INSTS_VALU_*_F64 counters, `model` from the reference's
@@ -67,6 +74,21 @@ CONFIGS = {   # name: (scene, width, height, one frame per step shared by all ra
     "cfg4": ("h8", 7680, 4320, True),
     "cfg5": ("lcg64", 16384, 16384, True),
 }
+DUMP_MAX_PIXELS = 1 << 21    # --dump-outputs: 32 MiB of float32 RGBA + 16 MiB of float64 pixel indices at most
+
+
+def dump_outputs(out_dir, rgba):
+    """--dump-outputs: the (h, w, 4) RGBA8 frame as float32 pixels and their flat indices; a frame of more than DUMP_MAX_PIXELS
+    pixels gives the same seeded sample of pixels on every run."""
+    import numpy as np
+    px = rgba.reshape(-1, 4)
+    if len(px) <= DUMP_MAX_PIXELS:
+        idx = np.arange(len(px))
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(len(px), DUMP_MAX_PIXELS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame_rgba.npy"), px[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
 
 
 def cpu_baseline(scene_name, w, h):
@@ -422,7 +444,7 @@ def predicted_single_frame(n, w, h, kernel_ms_n1, bytes_per_pixel, sky_fraction)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)     # 0.25 s timed at N=1: start-up and the final sync (~0.8 ms) no longer show
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 2000 for cfg3, 400 for cfg4, 20 for cfg5)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="cfg3", help="which BASELINE config (default: the headline, configs[2])")
     ap.add_argument("--scene", default=None)
@@ -432,12 +454,23 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (traffic / measured FP64 come from profiles/ then)")
     ap.add_argument("--no-cold", action="store_true", help="skip the cold-frame and moving-camera measurements (N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else: parity against the reference's rows, the kernel's own "
+                         "time, work counters, roofline and rocprofv3 counter passes, the store fill, the cold-frame / moving-camera and "
+                         "reference-scene legs, the CPU baseline; at N>1 the one-GPU reference, the batch form and the per-N expectation")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame of the last step as DIR/frame_rgba.npy (float32, pixels x RGBA) and "
+                         "DIR/frame_pixel_index.npy (float64, y * width + x); frames of more than %d pixels give a fixed, seeded "
+                         "sample of that many pixels" % DUMP_MAX_PIXELS)
     args = ap.parse_args()
     cfg_scene, cfg_w, cfg_h, single = CONFIGS[args.config]
     scene_name = args.scene or cfg_scene
     w, h = args.width or cfg_w, args.height or cfg_h
-    if args.config != "cfg3" and "--steps" not in sys.argv:
-        args.steps = 400 if args.config == "cfg4" else 20
+    if args.steps is None:
+        # 0.25 s timed at N=1 for the headline: start-up and the final sync (~0.8 ms) no longer show
+        args.steps = {"cfg3": 2000, "cfg4": 400, "cfg5": 20}[args.config]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # `python3 bench.py --gpus N` with N > 1 and no rank environment: start the N ranks ourselves.  A CHILD process (never an exec),
     # started before anything here has touched the GPU; its one JSON line is relayed, its exit code is ours.
@@ -490,9 +523,10 @@ def main():
         else:
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 
-    def run(single):
+    def run(single, dump_to=None):
         """One measurement: batch mode (single = False: N frames per step, frame f whole on rank f) or single-frame mode (True: ONE frame
-        per step, row-tiled over the ranks, whole on rank 0).  Returns (the JSON object on rank 0, parity_ok, max_lsb)."""
+        per step, row-tiled over the ranks, whole on rank 0).  dump_to: the directory for the last timed step's frame (--dump-outputs).
+        Returns (the JSON object on rank 0, parity_ok, max_lsb)."""
         result = None
         scene = rt_host.load_scene(scene_name)
         ss = scene.get("supersample", 1)
@@ -569,10 +603,12 @@ def main():
             blob = rt_host.flatten_scene(scene)
             return rows, np.frombuffer(ou.c_oracle_rows(blob, w, h, rows), dtype=np.uint8), "oracle/rt_oracle.c rows %s" % rows
 
-        check_rows, check_bytes, check_source = reference_rows()
+        check = {}                                                     # (rows, bytes, source), made on first use
 
         def worst_lsb(host_frame):
-            return int(ou.max_lsb(np.ascontiguousarray(host_frame[check_rows]).reshape(-1), check_bytes)[0])
+            if not check:
+                check["rows"], check["bytes"], check["source"] = reference_rows()
+            return int(ou.max_lsb(np.ascontiguousarray(host_frame[check["rows"]]).reshape(-1), check["bytes"])[0])
 
         p2p_note = None
         my_buf, peer_buf = None, {}
@@ -764,7 +800,7 @@ def main():
 
         # What ONE of these GPUs does with the same frame on its own (rank 0, the others wait): the reference of efficiency_vs_n1
         n1_mpix = None
-        if world > 1:
+        if world > 1 and args.full:
             if rank == 0:
                 tmp = frame if (i_own and frames.shape[1] == h) else torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
                 k1 = max(10, min(400, int(0.05 / max(1e-6, w * h / 1e11))))
@@ -845,8 +881,80 @@ def main():
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+        total_pixels = w * h * frames_per_step * args.steps
+        value = total_pixels / elapsed / 1e6
+
+        def reassembled(j):
+            if not mode["p2p"]:
+                return frames[j].cpu().numpy()
+            host = np.empty((h, w, 4), dtype=np.uint8)
+            if lib.rt_copy_to_host(dev_index, host.ctypes.data, my_buf + (group["last_slot"] * every + j) * frame_bytes, frame_bytes) != 0:
+                raise SystemExit("bench.py: rt_copy_to_host: " + lib.rt_last_error().decode())
+            return host
+
+        if dump_to and rank == 0:
+            # the frame of the last timed step, as the timed path left it (rank 0 owns a frame in every mode)
+            last = args.steps - 1
+            if not multi:
+                host = (frame_b if (two_streams and (last & 1)) else frame).cpu().numpy()
+            else:
+                host = reassembled(last % every)
+            dump_outputs(dump_to, host)
+            del host
 
         channels = 4 if (not multi or mode["p2p"]) else a2a_channels          # bytes per pixel the chosen plan's launches store
+
+        def headline():
+            """The result line as a plain run prints it: the timed steps' rate and how the frames were made."""
+            if not multi:
+                how = "one launch per frame" + ("; consecutive frames alternate between two HIP streams and two frame buffers" if two_streams else "")
+            elif mode["p2p"]:
+                how = ("a step = %s: interleaved %d-row tiles over %d ranks, one launch per rank whose stores go straight into the "
+                       "frame buffer of the rank that owns each frame (peer-mapped over xGMI, RGBA8, rows in place): no data collective, no "
+                       "de-interleave; one all_reduce per %d steps is the barrier"
+                       % ("ONE frame, whole on rank 0" if single else "a batch of %d frames" % world, TILE_ROWS, world, every))
+            else:
+                how = ("a step = %s: interleaved %d-row tiles over %d ranks, one launch per rank, ONE %s (RCCL over xGMI) "
+                       "reassembles %s (bands travel as %s), de-interleave to RGBA8 in HBM; the bands of %d consecutive steps share one "
+                       "collective, which overlaps the renders of the next %d steps"
+                       % ("ONE frame" if single else "a batch of %d frames" % world, TILE_ROWS, world, "gather to rank 0" if single else "all-to-all",
+                          "the frame on rank 0" if single else "frame f on rank f", "RGB24, alpha restored on arrival" if channels == 3 else "RGBA8", every, every))
+            out = {
+                "metric": "Mpixel/s", "value": round(value, 2), "unit": "Mpixel/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong" if (single and multi) else "weak",
+                "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+                "config": {"workload": "%s: %s scene (%d spheres, %d lights, depth %d, supersample %d) at %dx%d; SCENE, CAMERA AND LAUNCH TABLE RESIDENT (a static frame rendered again and again: "
+                                       "cold_frame / new_camera_every_step are the other cases); %s" % (
+                    args.config if (scene_name, w, h) == CONFIGS[args.config][:3] else "custom", scene_name, len(scene["objects"]), len(scene["lights"]),
+                    scene["segs"], ss, w, h, how),
+                    "kernel": "strict (no FMA)" if args.strict_fp else "fma", "frames_per_step": frames_per_step,
+                    "pixels_per_gpu_per_step": (w * h * frames_per_step) // world if multi else w * h,
+                    "steady_state_warmup": settle,
+                    **({"REHEARSAL": "all ranks on one GPU, gloo through host memory - not a measurement"} if rehearse else {}),
+                    **({"FORCED_EXCHANGE": "the N>1 plan run by ONE rank (1-rank RCCL collective = self copy): the plan's own overhead, not the headline"} if force else {})},
+            }
+            if p2p_note:
+                out["config"]["plan_note"] = p2p_note
+            if calibration:
+                out["config"]["plan_calibration_ms_per_step"] = calibration
+            return out
+
+        def close():
+            renderer.close()
+            if p2p:
+                fence()
+                for g, q in peer_buf.items():
+                    if g != rank:
+                        lib.rt_ipc_close(dev_index, q)
+                fence()
+                if my_buf:
+                    lib.rt_free_device(dev_index, my_buf)
+
+        if not args.full:                  # a plain run: the headline and nothing else
+            result = headline() if rank == 0 else None
+            close()
+            return result, True, 0
+
         # ---- dominant kernel: average launch duration, HIP events on the launch stream.  At N=1 the timed region IS a train of
         #      these launches on this stream, so two events around a train of them give the average over every launch (what
         #      rocprofv3's per-kernel average of the same command shows); at N>1 the region also waits for slots, so the kernel is
@@ -876,14 +984,6 @@ def main():
         drain()
         fence()
 
-        def reassembled(j):
-            if not mode["p2p"]:
-                return frames[j].cpu().numpy()
-            host = np.empty((h, w, 4), dtype=np.uint8)
-            if lib.rt_copy_to_host(dev_index, host.ctypes.data, my_buf + (group["last_slot"] * every + j) * frame_bytes, frame_bytes) != 0:
-                raise SystemExit("bench.py: rt_copy_to_host: " + lib.rt_last_error().decode())
-            return host
-
         max_lsb = 0
         if i_own:
             for j in range(every):
@@ -902,8 +1002,6 @@ def main():
             cnt_frame = frame if i_own and frames.shape[1] == h else torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
             st = renderer.render_tiles(w, h, cnt_frame.data_ptr(), whole, stream=stream, flags=flags | rt_host.RT_FLAG_COUNT, want_stats=True)
             rays_pp, shadow_pp, tests_pp = st.rays / st.pixels, st.shadow_rays / st.pixels, st.sphere_tests / st.pixels
-            total_pixels = w * h * frames_per_step * args.steps
-            value = total_pixels / elapsed / 1e6
             flops_pp = 15.0 * tests_pp + 120.0 * rays_pp + 60.0 * shadow_pp        # SURVEY §8(d) algorithmic FP64 flop model
             algo_bytes = float(channels) * launch_pixels        # what one launch stores: RGBA8, or RGB24 bands at N>1
             if compact and single and not mode["p2p"]:
@@ -952,19 +1050,6 @@ def main():
                             fp64_measured = dict(tj[key]["fp64"], achieved=round(fl / (kernel_ms * 1e-3) / 1e12, 3),
                                                  frac=round(fl / (kernel_ms * 1e-3) / 1e12 / FP64_VALU_PEAK_TF, 4),
                                                  note="counters REPLAYED from profiles/traffic.json, this run's kernel_ms")
-            if not multi:
-                how = "one launch per frame" + ("; consecutive frames alternate between two HIP streams and two frame buffers" if two_streams else "")
-            elif mode["p2p"]:
-                how = ("a step = %s: interleaved %d-row tiles over %d ranks, one launch per rank whose stores go straight into the "
-                       "frame buffer of the rank that owns each frame (peer-mapped over xGMI, RGBA8, rows in place): no data collective, no "
-                       "de-interleave; one all_reduce per %d steps is the barrier"
-                       % ("ONE frame, whole on rank 0" if single else "a batch of %d frames" % world, TILE_ROWS, world, every))
-            else:
-                how = ("a step = %s: interleaved %d-row tiles over %d ranks, one launch per rank, ONE %s (RCCL over xGMI) "
-                       "reassembles %s (bands travel as %s), de-interleave to RGBA8 in HBM; the bands of %d consecutive steps share one "
-                       "collective, which overlaps the renders of the next %d steps"
-                       % ("ONE frame" if single else "a batch of %d frames" % world, TILE_ROWS, world, "gather to rank 0" if single else "all-to-all",
-                          "the frame on rank 0" if single else "frame f on rank f", "RGB24, alpha restored on arrival" if channels == 3 else "RGBA8", every, every))
             # the store roofline as this box delivers it (quote a measured fill next to the nominal peak): a 2 GiB
             # torch fill, best of 5, on the launch stream
             fill_gbs = None
@@ -985,22 +1070,11 @@ def main():
                 except Exception:      # noqa: BLE001  (a small box: the nominal peak stands alone)
                     fill_gbs = None
             model_tf = flops_pp * launch_pixels / (kernel_ms * 1e-3) / 1e12
-            out = {
-                "metric": "Mpixel/s", "value": round(value, 2), "unit": "Mpixel/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong" if (single and multi) else "weak",
-                "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-                "config": {"workload": "%s: %s scene (%d spheres, %d lights, depth %d, supersample %d) at %dx%d; SCENE, CAMERA AND LAUNCH TABLE RESIDENT (a static frame rendered again and again: "
-                                       "cold_frame / new_camera_every_step are the other cases); %s" % (
-                    args.config if (scene_name, w, h) == CONFIGS[args.config][:3] else "custom", scene_name, len(scene["objects"]), len(scene["lights"]),
-                    scene["segs"], ss, w, h, how),
-                    "kernel": "strict (no FMA)" if args.strict_fp else "fma", "frames_per_step": frames_per_step,
-                    "pixels_per_gpu_per_step": (w * h * frames_per_step) // world if multi else w * h,
-                    "steady_state_warmup": settle,
-                    **({"REHEARSAL": "all ranks on one GPU, gloo through host memory - not a measurement"} if rehearse else {}),
-                    **({"FORCED_EXCHANGE": "the N>1 plan run by ONE rank (1-rank RCCL collective = self copy): the plan's own overhead, not the headline"} if force else {})},
+            out = headline()
+            out.update({
                 "mray_per_s": round(value * rays_pp, 2), "mshadow_per_s": round(value * shadow_pp, 2),
                 "rays_per_pixel": round(rays_pp, 4), "shadow_rays_per_pixel": round(shadow_pp, 4), "sphere_tests_per_pixel": round(tests_pp, 3),
-                "max_lsb_vs_reference_rows": max_lsb, "parity_ok": parity_ok, "parity_checked_against": check_source,
+                "max_lsb_vs_reference_rows": max_lsb, "parity_ok": parity_ok, "parity_checked_against": check["source"],
                 "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
                              "traffic": traffic, "traffic_source": traffic_src, "kernel": "rt_trace", "kernel_ms": round(kernel_ms, 4),
                              "algorithmic_bytes_per_launch": algo_bytes,
@@ -1013,14 +1087,10 @@ def main():
                                                               "this kernel's pixel rate; the product kernel does not execute those operations (anchored tests are 4, not 10; sky workgroups, "
                                                               "most floor blocks' shadow scans and the culled tests are never executed) - `measured` is what it executes"},
                               "kernel_mpixel_per_s": round(launch_pixels / (kernel_ms * 1e-3) / 1e6, 1)},
-            }
+            })
             if n1_mpix:
                 out["n1_reference"] = {"mpixel_per_s": round(n1_mpix, 2), "note": "rank 0 alone, the same %dx%d frame, launches back to back, frame in HBM, measured in this run" % (w, h)}
                 out["efficiency_vs_n1"] = round(value / (world * n1_mpix), 4)
-            if p2p_note:
-                out["config"]["plan_note"] = p2p_note
-            if calibration:
-                out["config"]["plan_calibration_ms_per_step"] = calibration
             if multi and mode["p2p"]:
                 sender = rank if any(g != rank for g in owners) else min(world - 1, 1)       # (single-frame mode: rank 0 owns, rank 1 sends)
                 remote_px = sum(1 for g in owners if g != sender) * plan.pixels_of(sender)
@@ -1072,15 +1142,7 @@ def main():
                     out["cpu_baseline"] = {"value": None, "unit": "Mpixel/s", "cores": 1, "kind": "port", "sample": "failed: %s" % e}
             result = out
 
-        renderer.close()
-        if p2p:
-            fence()
-            for g, q in peer_buf.items():
-                if g != rank:
-                    lib.rt_ipc_close(dev_index, q)
-            fence()
-            if my_buf:
-                lib.rt_free_device(dev_index, my_buf)
+        close()
         return result, parity_ok, max_lsb
 
 
@@ -1088,9 +1150,9 @@ def main():
     # after one collective / barrier (strong scaling: the frame is fixed).  The batch form - N frames per step, frame f whole on rank f,
     # every directed link in use - is measured first and rides in the same JSON line as `batch_mode` (weak scaling; never the headline).
     batch = None
-    if world > 1 and args.config == "cfg3" and not single and os.environ.get("RT_BENCH_NO_BATCH") != "1":
+    if args.full and world > 1 and args.config == "cfg3" and not single and os.environ.get("RT_BENCH_NO_BATCH") != "1":
         batch = run(False)
-    out, parity_ok, max_lsb = run(True if (world > 1 and args.config == "cfg3") else single)
+    out, parity_ok, max_lsb = run(True if (world > 1 and args.config == "cfg3") else single, dump_to=args.dump_outputs)
     if batch is not None:
         out_b, ok_b, lsb_b = batch
         parity_ok, max_lsb = parity_ok and ok_b, max(max_lsb, lsb_b)

@@ -24,17 +24,17 @@ step_tests() {              # the whole -m gpu suite, one process
 step_tests_k() {            # K="expr": a slice of the suite
   timeout -k 10 600 python -m pytest tests -x -q -m gpu -k "$K" > ${O}_gpu_tests_k.log 2>&1; rc=$?; tail -15 ${O}_gpu_tests_k.log | cut -c1-400; return $rc
 }
-step_bench() {              # the default line and the driver's form
-  timeout -k 10 500 python bench.py > ${O}_bench_n1.json 2>${O}_bench_n1.err; rc=$?; cut -c1-400 ${O}_bench_n1.json; [ $rc = 0 ] || { tail -5 ${O}_bench_n1.err; return $rc; }
+step_bench() {              # the full default line and the driver's (plain) form
+  timeout -k 10 500 python bench.py --full > ${O}_bench_n1.json 2>${O}_bench_n1.err; rc=$?; cut -c1-400 ${O}_bench_n1.json; [ $rc = 0 ] || { tail -5 ${O}_bench_n1.err; return $rc; }
   timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > ${O}_bench_n1_driver_form.json 2>${O}_bench_n1_driver_form.err; rc=$?; cut -c1-300 ${O}_bench_n1_driver_form.json; return $rc
 }
 step_bench_more() {         # the other configs and the reference's own scene on one GPU
-  timeout -k 10 200 python bench.py --config cfg4 --no-cpu-baseline > ${O}_bench_cfg4_n1.json 2>${O}_bench_cfg4_n1.err; cut -c1-300 ${O}_bench_cfg4_n1.json
-  timeout -k 10 300 python bench.py --config cfg5 --no-cpu-baseline > ${O}_bench_cfg5_n1.json 2>${O}_bench_cfg5_n1.err; cut -c1-300 ${O}_bench_cfg5_n1.json
-  timeout -k 10 200 python bench.py --scene default14 --no-cpu-baseline > ${O}_bench_default14_n1.json 2>${O}_bench_default14_n1.err; cut -c1-300 ${O}_bench_default14_n1.json
+  timeout -k 10 200 python bench.py --config cfg4 --full --no-cpu-baseline > ${O}_bench_cfg4_n1.json 2>${O}_bench_cfg4_n1.err; cut -c1-300 ${O}_bench_cfg4_n1.json
+  timeout -k 10 300 python bench.py --config cfg5 --full --no-cpu-baseline > ${O}_bench_cfg5_n1.json 2>${O}_bench_cfg5_n1.err; cut -c1-300 ${O}_bench_cfg5_n1.json
+  timeout -k 10 200 python bench.py --scene default14 --full --no-cpu-baseline > ${O}_bench_default14_n1.json 2>${O}_bench_default14_n1.err; cut -c1-300 ${O}_bench_default14_n1.json
 }
 step_rehearse() {           # `bench.py --gpus 2` started bare (the driver's command), two ranks on the one GPU
-  RT_BENCH_REHEARSE=1 timeout -k 10 600 python bench.py --gpus 2 --steps 20 --warmup 5 > ${O}_rehearsal_n2_bare.json 2>${O}_rehearsal_n2_bare.err; rc=$?
+  RT_BENCH_REHEARSE=1 timeout -k 10 600 python bench.py --gpus 2 --steps 20 --warmup 5 --full > ${O}_rehearsal_n2_bare.json 2>${O}_rehearsal_n2_bare.err; rc=$?
   cut -c1-600 ${O}_rehearsal_n2_bare.json; [ $rc = 0 ] || tail -20 ${O}_rehearsal_n2_bare.err; return $rc
 }
 step_profile() {            # PROFILE_TAG=<name> PROFILE_ARGS="<bench.py arguments>": rocprofv3 trace + counter passes (run_profile.sh)

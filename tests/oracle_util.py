@@ -35,6 +35,12 @@ def golden_frame(entry):
     return np.fromfile(os.path.join(GOLDEN, entry["file"]), dtype=np.uint8)
 
 
+def reference_results():
+    """SHA-256 of frames the reference itself rendered (tests/golden/reference_results.json, oracle/record_reference_results.py)."""
+    with open(os.path.join(GOLDEN, "reference_results.json")) as f:
+        return json.load(f)
+
+
 def c_oracle():
     global _c
     if _c is None:

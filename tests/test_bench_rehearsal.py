@@ -27,7 +27,7 @@ def free_port():
 def run_bench(world, extra_args=(), bare=False, **env_extra):
     env = dict(os.environ, RT_BENCH_REHEARSE="1", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.update(env_extra)
-    tail = [os.path.join(ou.ROOT, "bench.py"), "--gpus", str(world), "--steps", "10", "--warmup", "2", *extra_args]
+    tail = [os.path.join(ou.ROOT, "bench.py"), "--gpus", str(world), "--steps", "10", "--warmup", "2", "--full", *extra_args]
     if bare:       # the way the driver starts it: no launcher, no rank environment - bench.py starts its ranks itself (a child process)
         for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
             env.pop(k, None)

@@ -2,8 +2,8 @@
 
   * restate.js (JS)  == golden frames produced by /root/reference/main.js   BIT-EXACT (sha256)
   * rt_oracle.c (C)  vs the same golden frames                               <= 1 LSB / channel
-  * with /root/reference present (build container): re-run the reference itself and compare again,
-    so stale fixtures cannot hide a regression.
+  * restate.js (JS)  == frames the reference rendered at other sizes and on random scenes, recorded as SHA-256
+    (tests/golden/reference_results.json, oracle/record_reference_results.py), so stale golden frames cannot hide a regression.
 """
 import hashlib
 
@@ -15,8 +15,8 @@ import rt_host
 
 M = ou.manifest()
 FRAMES = {f["name"]: f for f in M["frames"]}
+REF = ou.reference_results()
 needs_node = pytest.mark.skipif(ou.node_path() is None, reason="node not installed")
-needs_ref = pytest.mark.skipif(not ou.have_reference(), reason="/root/reference not present (GPU box)")
 
 
 def sha(b):
@@ -87,35 +87,33 @@ def test_work_counters_match_survey(built):
     assert abs(r["rays"] / px - 1.127) < 0.01 and abs(r["sphereTests"] / px - 15.64) < 0.1
 
 
-# ---------------------------------------------------------------- against the live reference (build container)
-@needs_ref
-@pytest.mark.reference
+# ---------------------------------------------------------------- against the reference's recorded frames
 def test_reference_main_still_produces_the_golden_frame():
+    """The reference's own main() at 64x48 as recorded by oracle/record_reference_results.py is the golden frame, byte for byte."""
     f = FRAMES["default14_main_64x48"]
-    assert ou.node_cli("main", f["w"], f["h"])["sha256"] == f["sha256"]
+    rec = {(m["w"], m["h"]): m["sha256"] for m in REF["main"]}
+    assert rec[(f["w"], f["h"])] == f["sha256"] == sha(ou.golden_frame(f))
 
 
-@needs_ref
-@pytest.mark.reference
-@pytest.mark.parametrize("scene,w,h", [("cfg1", 96, 96), ("cfg2", 160, 90), ("h8", 200, 112), ("h8_d8", 120, 68),
-                                       ("default14", 128, 72), ("lcg64", 48, 48), ("lcg64_ss1", 64, 64)])
-def test_restatement_bit_exact_vs_live_reference(scene, w, h):
-    # sizes differ from the committed fixtures on purpose
-    a = ou.node_cli("reference", ou.scene_json(scene), w, h)
-    b = ou.node_cli("restate", ou.scene_json(scene), w, h)
-    assert a["sha256"] == b["sha256"]
-
-
-@needs_ref
 @needs_node
-@pytest.mark.reference
+@pytest.mark.parametrize("scene,w,h", [(r["scene"], r["w"], r["h"]) for r in REF["scenes"]])
+def test_restatement_bit_exact_vs_live_reference(scene, w, h):
+    # sizes differ from the committed fixtures on purpose; the reference's frames are recorded as SHA-256
+    want = next(r["sha256"] for r in REF["scenes"] if (r["scene"], r["w"], r["h"]) == (scene, w, h))
+    assert ou.node_cli("restate", ou.scene_json(scene), w, h)["sha256"] == want
+
+
+@needs_node
 def test_restatements_vs_live_reference_on_random_scenes(built):
     """A slice of tests/soak_oracle_vs_reference.py (600 scenes by hand: profiles/r01_soak_oracle_vs_reference.json):
     random scenes far from the fixtures - sphere counts, samplers, transparent occluders, lights inside spheres, arbitrary
-    cameras, fov, depth, supersampling - through the reference's own intersectWorld; the JS restatement must be
-    bit-identical, the C restatement within 1 LSB with no flipped pixel."""
+    cameras, fov, depth, supersampling - rendered by the reference's own intersectWorld and recorded as SHA-256
+    (tests/golden/reference_results.json); the JS restatement must be bit-identical, the C restatement within 1 LSB with
+    no flipped pixel."""
     import soak_oracle_vs_reference as sr
-    res = sr.run(10, 1000, verbose=False)
+    rs = REF["random_scenes"]
+    recorded = {r["seed"]: r["sha256"] for r in rs["frames"]}
+    res = sr.run(10, rs["first"], verbose=False, recorded=recorded)
     assert res["scenes"] == 10 and res["restate_mismatch"] == []
     assert res["c_flipped_pixels"] == 0
 
