@@ -747,6 +747,17 @@ extern "C" int rt_scene_set_camera(rt_scene_dev *s, const double origin[3], cons
   return RT_OK;
 }
 
+// The stars seed (include/rt_hip.h: RT_SAMPLER_STARS) is host state: render_batch_impl copies it into each launch record, so frames
+// already enqueued keep theirs.  Nothing on the device depends on it - a stars sky is never a constant background, so no launch
+// table or sky block changes.
+extern "C" int rt_scene_set_stars_seed(rt_scene_dev *s, uint32_t seed) {
+  if (!s) return fail(RT_ERR_INVALID, "rt_scene_set_stars_seed: NULL scene");
+  std::lock_guard<std::mutex> lk(s->launch_mu);
+  s->hd.stars_seed = seed;
+  memcpy(s->host_blob.data() + offsetof(rt_scene_header, stars_seed), &seed, sizeof seed);
+  return RT_OK;
+}
+
 // ------------------------------------------------------------------------------------ launch
 extern "C" int rt_render_tiles_device(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, void *d_out, void *hip_stream,
                                       uint32_t flags, rt_stats *stats) {
@@ -1155,9 +1166,11 @@ int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *t
   device_state &D = G.dev[s->device];
   hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : D.stream;
   const auto t_begin = std::chrono::steady_clock::now();
+  uint32_t stars_seed;
   {
     // which streams the scene's launches run on (rt_scene_set_camera, dispatch_order), and: behind the last write of the camera block
     std::lock_guard<std::mutex> lk(s->launch_mu);
+    stars_seed = s->hd.stars_seed;                     // (rt_scene_set_stars_seed: this launch's, whatever the next call sets)
     if ((rc = behind_the_camera(s, stream))) return rc;
     if (s->any_launch && s->last_stream != stream) s->several_streams = true;
     s->last_stream = stream; s->any_launch = true; s->launched_since_move = true;
@@ -1242,6 +1255,8 @@ int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *t
 #endif
   L.mark_flags = (RT_TEST_ENV("RT_MARK_ALL") ? RT_MARK_ALL : 0u) | (no_fixup ? RT_MARK_NEVER : 0u) | (RT_TEST_ENV("RT_TEST_MARK_STRIPES") ? RT_MARK_ZERO : 0u) | (s->unit_weights ? RT_MARK_WEIGHT : 0u);
   L.marks_cap = RT_MARKS_CAP;
+  L.stars_seed = stars_seed;
+  L.stars_step = (flags & RT_FLAG_STARS_PER_FRAME) ? 1u : 0u;
   L.textures = s->d_texdesc;
   L.texel_base = db;
   L.out = (uint32_t *)d_out;
@@ -1799,14 +1814,18 @@ int ensure_rccl(int ndev) {
 int scene_for(int device, const void *blob, size_t bytes, rt_scene_dev **out) {
   device_state &D = G.dev[device];
   if (D.cached_scene && D.cached_blob.size() == bytes && memcmp(D.cached_blob.data(), blob, bytes) == 0) { *out = D.cached_scene; return RT_OK; }
-  // the same scene from another camera (an animation: lookAt per frame, main.js:92-100): the resident scene moves its camera
+  // the same scene from another camera and / or with another stars seed (an animation: lookAt per frame, main.js:92-100, and a new sky
+  // per redraw, main.js:135-139, 180): the resident scene moves its camera and takes the seed
   if (D.cached_scene && D.cached_blob.size() == bytes) {
     const size_t c0 = offsetof(rt_scene_header, cam_origin), c1 = c0 + 12 * sizeof(double);
+    const size_t s0 = offsetof(rt_scene_header, stars_seed), s1 = s0 + sizeof(uint32_t);
+    static_assert(c1 <= s0, "the camera lies in front of the stars seed in rt_scene_header");
     const uint8_t *a = D.cached_blob.data(), *b = (const uint8_t *)blob;
-    if (memcmp(a, b, c0) == 0 && memcmp(a + c1, b + c1, bytes - c1) == 0) {
+    if (memcmp(a, b, c0) == 0 && memcmp(a + c1, b + c1, s0 - c1) == 0 && memcmp(a + s1, b + s1, bytes - s1) == 0) {
       const rt_scene_header *nh = (const rt_scene_header *)blob;
-      if (rt_scene_set_camera(D.cached_scene, nh->cam_origin, nh->cam_axis_x, nh->cam_axis_y, nh->cam_axis_z, nullptr) == RT_OK) {
-        memcpy(D.cached_blob.data() + c0, b + c0, c1 - c0);
+      if (rt_scene_set_camera(D.cached_scene, nh->cam_origin, nh->cam_axis_x, nh->cam_axis_y, nh->cam_axis_z, nullptr) == RT_OK &&
+          rt_scene_set_stars_seed(D.cached_scene, nh->stars_seed) == RT_OK) {
+        memcpy(D.cached_blob.data() + c0, b + c0, s1 - c0);      // (what lies between the two is equal)
         *out = D.cached_scene;
         return RT_OK;
       }

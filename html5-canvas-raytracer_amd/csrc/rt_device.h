@@ -114,7 +114,9 @@ struct rt_launch {
   uint32_t marks_cap;                // entries the list holds; beyond it only the count grows and rt_retrace traces every sample
   double flag_tol;                   // tolerance of the boundary test: RT_FLAG_T1 x the largest sampler frequency of the scene
   uint32_t mark_flags;               // RT_MARK_* (below)
-  uint32_t mark_pad;
+  // Stars sampler (read only inside its branch, from the kernarg segment): frame f of the launch hashes with seed stars_seed + stars_step * f
+  uint32_t stars_seed;               // rt_scene_header.stars_seed as the scene held it when this launch was issued
+  uint32_t stars_step;               // 1 with RT_FLAG_STARS_PER_FRAME, else 0
   // rt_retrace only
   unsigned long long *marks_known;   // pinned host word that receives known_tag << 32 | count + 1, or NULL
   uint32_t known_tag;                // (the camera generation the frame is rendered with)

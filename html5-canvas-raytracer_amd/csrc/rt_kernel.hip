@@ -350,14 +350,15 @@ __device__ __forceinline__ double min1(double x) { return (x > 1.0) ? 1.0 : x; }
 __device__ __forceinline__ double maxa(double a, double x) { return (x < a) ? a : x; }
 
 // Counter-based stand-in for Math.random() in the stars sampler (main.js:135-139): lowbias32 twice over the sample's
-// index in the frame and the node's position in the ray tree (root 1, reflect child 2p, refract child 2p+1).
-// Identical in oracle/restate.js and oracle/rt_oracle.c.
+// index in the frame and the node's position in the ray tree (root 1, reflect child 2p, refract child 2p+1), with the
+// index's high word XORed by mix = lowbias32(seed) (include/rt_hip.h: RT_SAMPLER_STARS).  lowbias32(0) == 0: at seed 0
+// identical to oracle/restate.js and oracle/rt_oracle.c, which know no seed.
 __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
   return x;
 }
-__device__ __forceinline__ double star_uniform(uint32_t pix_lo, uint32_t pix_hi, uint32_t path) {
-  return (double)lowbias32(pix_lo ^ lowbias32(path + 0x9e3779b9u * (pix_hi + 1u))) * (1.0 / 4294967296.0);
+__device__ __forceinline__ double star_uniform(uint32_t pix_lo, uint32_t pix_hi, uint32_t path, uint32_t mix) {
+  return (double)lowbias32(pix_lo ^ lowbias32(path + 0x9e3779b9u * ((pix_hi ^ mix) + 1u))) * (1.0 / 4294967296.0);
 }
 
 // ECMAScript ToInt32(x) & 1   (main.js:129-130)
@@ -525,15 +526,16 @@ __device__ __forceinline__ rt_geom_pair rt_load_geom_pair32(geom_kptr tab, uint3
   return rt_geom_pair{rt_geom{v[0], v[1], v[2], v[3]}, rt_geom{v[4], v[5], v[6], v[7]}};
 }
 
-#if !RT_STRICT
 // The launch record as the COLD paths read it: straight from the kernarg segment at the point of use (the kernel's only argument lies
 // at its start), behind an opaque copy of the pointer, so that a field only the rare paths need is not loaded at kernel entry and
-// held in scalar registers across the whole trace (the kernel has none to spare).
+// held in scalar registers across the whole trace (the kernel has none to spare).  (Every kernel of this file that traces - rt_trace,
+// rt_retrace - takes the launch record as its only argument.)
 __device__ __forceinline__ const rt_launch __attribute__((address_space(4))) *rt_cold_args() {
   const rt_launch __attribute__((address_space(4))) *K = (const rt_launch __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(K));
   return K;
 }
+#if !RT_STRICT
 // Append this work-item's sample to the launch's mark list (the cold end of the samplers' boundary test, a handful of samples per frame): entry = sample x |
 // sample y << 20 | frame of the batch << 40; the counter of THIS launch is marks[marks_slot] (rt_api.hip alternates two, so that
 // rt_retrace can clear the next launch's while it reads its own); beyond the list's capacity only the count grows and rt_retrace
@@ -563,7 +565,7 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
                                             [[maybe_unused]] double blk_x0, [[maybe_unused]] double blk_x1, [[maybe_unused]] double blk_y0,
                                             [[maybe_unused]] double blk_y1, v3 p, v3 d, double rgb[3], uint32_t cnt[3],
                                             [[maybe_unused]] bool is_probe, [[maybe_unused]] uint32_t cand_host,
-                                            [[maybe_unused]] uint32_t own_sx = 0u, [[maybe_unused]] uint32_t own_sy = 0u) {
+                                            [[maybe_unused]] uint32_t own_sx = 0u, [[maybe_unused]] uint32_t own_sy = 0u, [[maybe_unused]] uint32_t own_f = 0u) {
 #ifdef RT_TESTING
   uint32_t probe_n = 0;                                  // test build: nodes of this sample's ray tree recorded so far
   double probe_li = 0.0;
@@ -960,8 +962,9 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
         } else if (kind == RT_SAMPLER_STARS) {
           // the sample's index in the FRAME (not in this call's tiles), recomputed from the work-item id so that it
           // costs no register outside this branch; `path` is the node's position in the ray tree
-          uint32_t sx = own_sx, sy = own_sy;         // rt_retrace hands the sample over
+          uint32_t sx = own_sx, sy = own_sy, f = own_f;   // rt_retrace hands the sample and its frame over
           if constexpr (!ITEM) {
+            f = blockIdx.z;                          // the frame of the batch
             uint32_t t3 = threadIdx.x;
             asm volatile("" : "+v"(t3));
             const rt_pixel P = rt_pixel_of<SS2, W1>(L, t3);
@@ -969,7 +972,10 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
           }
           const unsigned long long pix = (unsigned long long)sy * (SS2 ? 2u * L.w : L.w) + sx;
           const uint32_t path = REFRACT ? tree_path : (1u << RT_LVL(level));
-          double c = star_uniform((uint32_t)pix, (uint32_t)(pix >> 32), path);
+          // the seed of this frame, read here from the kernarg segment: no other path holds it in a register
+          const rt_launch __attribute__((address_space(4))) *K = rt_cold_args();
+          const uint32_t mix = lowbias32(K->stars_seed + K->stars_step * f);
+          double c = star_uniform((uint32_t)pix, (uint32_t)(pix >> 32), path, mix);
           c = (c >= m.c[6]) ? 0.0 : c * m.c[7];     // main.js:137-138
           col[0] = col[1] = col[2] = c;
         } else { col[0] = m.c[0]; col[1] = m.c[1]; col[2] = m.c[2]; }
@@ -1745,7 +1751,7 @@ __global__ void __launch_bounds__(RT_WG_THREADS) rt_retrace(const rt_launch L) {
       const v3 ray = unit(mk(target.x - o.x, target.y - o.y, target.z - o.z), &rl);
       double rgb[3];
       uint32_t cnt[3] = {0u, 0u, 0u};
-      trace_pixel<REFRACT, false, false, SS2, true>(L, mtl, tex, nullptr, nullptr, rt_geom{0.0, 0.0, 0.0, 0.0}, 0u, 0.0, 0.0, 0.0, 0.0, o, ray, rgb, cnt, false, 0u, sx, sy);
+      trace_pixel<REFRACT, false, false, SS2, true>(L, mtl, tex, nullptr, nullptr, rt_geom{0.0, 0.0, 0.0, 0.0}, 0u, 0.0, 0.0, 0.0, 0.0, o, ray, rgb, cnt, false, 0u, sx, sy, f);
       sum[0] += to_byte(rgb[0]); sum[1] += to_byte(rgb[1]); sum[2] += to_byte(rgb[2]);
     }
     if (SS2) {

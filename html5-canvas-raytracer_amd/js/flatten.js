@@ -32,7 +32,7 @@ function flattenScene(scene) {
   u32(RT_SCENE_MAGIC); u32(RT_ABI_VERSION); u64(total);
   vec(scene.camera.origin, 3); vec(scene.camera.axisX, 3); vec(scene.camera.axisY, 3); vec(scene.camera.axisZ, 3);
   f64(scene.fovDeg); f64(scene.light_intensity); f64(scene.epsilon); vec(scene.miss_color || [1, 0, 0], 3);
-  u32(scene.segs); u32(scene.supersample || 1); u32(nObj); u32(nLight); u32(nTex); u32(0);
+  u32(scene.segs); u32(scene.supersample || 1); u32(nObj); u32(nLight); u32(nTex); u32(scene.starsSeed || 0);
   u64(objectsOff); u64(lightsOff); u64(texOff);
   if (o !== HEADER_BYTES) throw new Error('flatten: header size drifted');
 
@@ -65,12 +65,12 @@ function sceneToJSON(scene, name, dir) {
     if (dir) fs.writeFileSync(path.join(dir, file), Buffer.from(t.texels));
     return {width: t.width, height: t.height, file};
   });
-  return JSON.stringify({
+  return JSON.stringify(Object.assign({
     name, camera: scene.camera, fovDeg: scene.fovDeg, segs: scene.segs, supersample: scene.supersample || 1,
     light_intensity: scene.light_intensity, epsilon: scene.epsilon, lights: scene.lights,
     objects: scene.objects.map((ob) => ({origin: ob.origin, r2: ob.r2, mtl: ob.mtl})),
     textures,
-  }, null, 1);
+  }, scene.starsSeed ? {starsSeed: scene.starsSeed} : {}), null, 1);     // (seed 0 is the key's absence: scene files stay as they were)
 }
 
 function sceneFromJSON(text, dir) {
@@ -81,7 +81,7 @@ function sceneFromJSON(text, dir) {
   });
   return S.createScene({
     camera: j.camera, fovDeg: j.fovDeg, segs: j.segs, supersample: j.supersample, light_intensity: j.light_intensity,
-    epsilon: j.epsilon, lights: j.lights, textures,
+    epsilon: j.epsilon, lights: j.lights, textures, starsSeed: j.starsSeed,
     objects: j.objects.map((ob) => ({origin: ob.origin, r2: ob.r2, mtl: ob.mtl})),
   });
 }

@@ -15,7 +15,8 @@
 //   kind 1 'texture'  nearest-texel lookup at hit.u,hit.v       (:143-145, :343-351)
 //   kind 2 'checker'  sphere checker on its own u,v             (:126-133)
 //   kind 3 'stars'    night stars :135-139 with Math.random() replaced by a counter-based hash of (sample index,
-//                     position in the ray tree): deterministic, NOT comparable with the random reference
+//                     position in the ray tree, scene.starsSeed): deterministic, NOT comparable with the random reference;
+//                     the reference draws a new sky per redraw (:180) - set a new scene.starsSeed per frame for that
 
 const {readPNG} = require('./png.js');
 
@@ -123,6 +124,7 @@ function createScene(opts) {
     textures: opts.textures || [],
     epsilon: opts.epsilon === undefined ? 0.001 : opts.epsilon,                 // main.js:430-436
     supersample: opts.supersample || 1,                                         // 1, or k = 2 (cfg5), 3, 4: k x k box of the kw x kh frame
+    starsSeed: opts.starsSeed === undefined ? 0 : opts.starsSeed,               // the stars sampler's seed: a new one per redraw is main.js:180's new sky
   };
   validateScene(scene);
   return scene;
@@ -137,6 +139,7 @@ function validateScene(scene) {
   if (!c || !isVec(c.origin, 3) || !isVec(c.axisX, 3) || !isVec(c.axisY, 3) || !isVec(c.axisZ, 3)) throw new Error('scene.camera must hold origin/axisX/axisY/axisZ 3-vectors');
   if (!Number.isInteger(scene.segs) || scene.segs < 0 || scene.segs > 16) throw new Error('scene.segs must be an integer in [0,16]');
   if (![1, 2, 3, 4].includes(scene.supersample)) throw new Error('scene.supersample must be 1, 2, 3 or 4');
+  if (scene.starsSeed !== undefined && !(Number.isInteger(scene.starsSeed) && scene.starsSeed >= 0 && scene.starsSeed < 4294967296)) throw new Error('scene.starsSeed must be an integer in [0, 2^32)');
   if (!Array.isArray(scene.objects) || scene.objects.length < 1 || scene.objects.length > 256) throw new Error('scene.objects must hold 1..256 spheres');
   if (!Array.isArray(scene.lights) || scene.lights.length > 16) throw new Error('scene.lights must hold 0..16 lights');
   scene.lights.forEach((l) => { if (!isVec(l, 3)) throw new Error('light must be a 3-vector'); });

@@ -8,6 +8,9 @@
 //   GET /                               the page
 //   GET /frame?scene=h8&w=1280&h=720    raw RGBA8, w*h*4 bytes (ImageData.data layout);
 //                                       headers X-Width, X-Height, X-Kernel-Ms, X-Total-Ms, X-Build, X-Report ('build #741.r4 (12ms)')
+//   GET /frame?...&seed=N               the same with the stars sampler's seed N (an integer in [0, 2^32); default 0): the
+//                                       reference draws a new night sky per redraw (main.js:135-139, 180), a page that wants
+//                                       that asks for a new seed per frame
 //   GET /frame?...&progressive=8        the same bytes as a CHUNKED response, one chunk per row band as it leaves the
 //                                       GPU (renderProgressive): the page paints top to bottom like the reference's
 //                                       scanline loop (main.js:183-201)
@@ -33,10 +36,12 @@ const PAGE = `<!DOCTYPE html>
   const canvas = document.getElementById('canvasID');
   canvas.width = document.body.clientWidth; canvas.height = document.body.clientHeight;
   const ctx = canvas.getContext('2d');
-  const scene = new URLSearchParams(location.search).get('scene') || 'default14_stars';
+  const q = new URLSearchParams(location.search);
+  const scene = q.get('scene') || 'default14_stars';
+  const seed = q.get('seed');
   const t0 = Date.now();
   const w = canvas.width, h = canvas.height;
-  const r = await fetch('/frame?scene=' + scene + '&w=' + w + '&h=' + h + '&progressive=8');
+  const r = await fetch('/frame?scene=' + scene + '&w=' + w + '&h=' + h + '&progressive=8' + (seed !== null ? '&seed=' + encodeURIComponent(seed) : ''));
   if (!r.ok) { ctx.fillStyle = '#f44'; ctx.font = '16px monospace'; ctx.fillText((await r.json()).error, 8, 24); return; }
   // paint whole rows as the chunks arrive (the reference paints one scanline per macrotask)
   const data = new Uint8ClampedArray(w * h * 4);
@@ -94,6 +99,12 @@ function createServer(opts) {
       if (!(w > 0 && h > 0 && w <= 65536 && h <= 65536 && w * h <= maxPixels)) return sendJSON(res, 400, {error: 'w and h must be positive integers within the frame limit'});
       let scene;
       try { scene = loadNamedScene(String(u.query.scene || 'default14_stars')); } catch (e) { return sendJSON(res, e.status || 500, {error: e.message}); }
+      if (u.query.seed !== undefined) {
+        // per request: a shallow copy with its own seed, the cached scene stays as it is (flattenScene reads it per render)
+        const seed = /^[0-9]{1,10}$/.test(String(u.query.seed)) ? Number(u.query.seed) : -1;
+        if (!(seed >= 0 && seed < 4294967296)) return sendJSON(res, 400, {error: 'seed must be an integer in [0, 2^32)'});
+        scene = Object.assign({}, scene, {starsSeed: seed});
+      }
       const bands = parseInt(u.query.progressive || '0', 10);
       if (bands > 0) {
         // chunked: each band is written as soon as it is in the pinned frame; headers cannot carry the timings any more

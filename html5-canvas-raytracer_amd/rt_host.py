@@ -34,6 +34,7 @@ RT_FLAG_RGB24 = 4        # device entry points: 3 bytes per pixel, the constant 
 RT_FLAG_NO_SKY = 8       # blocks that can only show the constant background are not stored (the frame's owner stores them: RT_FLAG_SKY_ONLY)
 RT_FLAG_SKY_ONLY = 16
 RT_FLAG_COMPACT = 32     # with RT_FLAG_RGB24 | RT_FLAG_NO_SKY: a compact band (the stored blocks back to back, for a collective)
+RT_FLAG_STARS_PER_FRAME = 64   # batches: frame f draws its stars with seed starsSeed + f (mod 2^32); without it every frame is the same
 
 
 # --------------------------------------------------------------------------- scenes
@@ -70,6 +71,9 @@ def validate_scene(scene):
         raise ValueError("scene.objects must hold 1..256 spheres")
     if len(scene["lights"]) > 16:
         raise ValueError("scene.lights must hold 0..16 lights")
+    seed = scene.get("starsSeed", 0)
+    if not (isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < 2 ** 32):
+        raise ValueError("scene.starsSeed must be an integer in [0, 2^32)")
     for i, o in enumerate(scene["objects"]):
         s = o["mtl"]["sampler"]
         if s["kind"] not in (SAMPLER_COLOR, SAMPLER_TEXTURE, SAMPLER_CHECKER, SAMPLER_STARS):
@@ -98,7 +102,7 @@ def flatten_scene(scene):
         *cam["origin"], *cam["axisX"], *cam["axisY"], *cam["axisZ"],
         float(scene.get("fovDeg", 60)), float(scene.get("light_intensity", 50)), float(scene.get("epsilon", 0.001)),
         *[float(x) for x in scene.get("miss_color", [1, 0, 0])],
-        scene["segs"], scene.get("supersample", 1), len(objs), len(lights), len(texs), 0,
+        scene["segs"], scene.get("supersample", 1), len(objs), len(lights), len(texs), scene.get("starsSeed", 0),
         objects_off, lights_off, tex_off)
     assert len(hdr) == HEADER_BYTES
     out[0:HEADER_BYTES] = hdr
@@ -156,6 +160,7 @@ ABI = {
     "rt_scene_upload": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "rt_scene_free": (None, [C.c_void_p]),
     "rt_scene_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
+    "rt_scene_set_stars_seed": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rt_render_tiles_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtTiles), C.c_void_p, C.c_void_p,
                                          C.c_uint32, C.POINTER(RtStats)]),
     "rt_render_batch_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtTiles), C.c_uint32, C.c_void_p, C.c_uint64,
@@ -238,6 +243,13 @@ class Renderer:
         asynchronous copy; the next render rebuilds what depends on it on the GPU."""
         v = [(C.c_double * 3)(*camera[k]) for k in ("origin", "axisX", "axisY", "axisZ")]
         _check(self.lib, self.lib.rt_scene_set_camera(self.handle, v[0], v[1], v[2], v[3], C.c_void_p(stream or 0)), "rt_scene_set_camera")
+
+    def set_stars_seed(self, seed):
+        """Seed of the stars sampler's hash for the scene's later renders (the reference's new Math.random() draws per redraw,
+        main.js:135-139, 180).  Host state only: renders already enqueued keep the seed they were launched with."""
+        if not (isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < 2 ** 32):
+            raise ValueError("stars seed must be an integer in [0, 2^32)")
+        _check(self.lib, self.lib.rt_scene_set_stars_seed(self.handle, seed), "rt_scene_set_stars_seed")
 
     def render_tiles(self, w, h, d_out, tiles=None, stream=None, flags=0, want_stats=False):
         t = tiles if isinstance(tiles, RtTiles) else RtTiles(*(tiles or (h, 0, 1, 1)))

@@ -58,9 +58,18 @@ enum {
   RT_SAMPLER_TEXTURE = 1, /* main.js:143-145   sampleTexture(tex, hit.u, hit.v)   */
   RT_SAMPLER_CHECKER = 2, /* main.js:126-133   sphere checker on its own u,v      */
   RT_SAMPLER_STARS = 3    /* main.js:135-139   night stars, with Math.random() replaced by a counter-based hash of
-                           *                    (sample index in the frame, position in the ray tree): deterministic, the same
+                           *                    (sample index in the frame, position in the ray tree, seed): deterministic, the same
                            *                    on every implementation here, NOT comparable with the (random) reference.
-                           *                    checker_freq[0] = threshold (0.001), checker_freq[1] = scale (1000). */
+                           *                    checker_freq[0] = threshold (0.001), checker_freq[1] = scale (1000).
+                           *                    With pix = sample y * sample-grid width + sample x (64 bits; pix_lo, pix_hi its
+                           *                    words), path = the node's place in the ray tree (root 1, reflect child 2p, refract
+                           *                    child 2p + 1) and seed = rt_scene_header.stars_seed (+ frame, RT_FLAG_STARS_PER_FRAME):
+                           *                      mix = lowbias32(seed)                        (lowbias32(0) == 0)
+                           *                      u   = lowbias32(pix_lo ^ lowbias32(path + 0x9e3779b9 * ((pix_hi ^ mix) + 1))) / 2^32
+                           *                    (32-bit unsigned arithmetic; lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15;
+                           *                    x *= 0x846ca68b; x ^= x >> 16), and the sample's grey is u * scale where u < threshold,
+                           *                    else 0.  Seed 0 is the hash of ABI 2 before the seed existed, bit for bit.  The
+                           *                    reference draws a new sky per redraw (main.js:180); a new seed per frame does that. */
 };
 
 /* One sphere + its material: createSphere (main.js:408-418) + createMaterial (:397-406).
@@ -105,7 +114,8 @@ typedef struct rt_scene_header {
   uint32_t n_objects;      /* objs.length, already in the reference's sorted order (main.js:159-163) */
   uint32_t n_lights;       /* lights.length main.js:283 */
   uint32_t n_textures;
-  uint32_t reserved0;
+  uint32_t stars_seed;     /* seed of the stars sampler's hash (RT_SAMPLER_STARS above); any value; 0 = the sky every host drew before
+                            * the field existed.  Replaces the per-redraw Math.random() stream of main.js:135-139, 180. */
   uint64_t objects_offset;  /* rt_sphere[n_objects] */
   uint64_t lights_offset;   /* double[3*n_lights] */
   uint64_t textures_offset; /* rt_texture_desc[n_textures] */
@@ -153,12 +163,15 @@ enum {
                              * from its own table: the two kinds of call together store every pixel once, and about half of the
                              * headline's pixels never cross a link.  Scenes without a constant background: RT_FLAG_NO_SKY leaves nothing
                              * out and RT_FLAG_SKY_ONLY stores nothing.  Not with RT_FLAG_COUNT. */
-  RT_FLAG_COMPACT = 32      /* rt_render_batch_device with RT_FLAG_RGB24 | RT_FLAG_NO_SKY: a COMPACT band for a collective - the blocks that
+  RT_FLAG_COMPACT = 32,     /* rt_render_batch_device with RT_FLAG_RGB24 | RT_FLAG_NO_SKY: a COMPACT band for a collective - the blocks that
                              * are stored at all (everything but the sky) back to back, block b of the launch (32 pixels x 8 rows, x 2
                              * rows with supersample 2; RGB24, row by row: 768 / 192 bytes) at d_out + b * block_bytes, dearest block
                              * first.  rt_compact_count says how many there are; the receiver, which holds the same scene with the same
                              * camera, puts them back with rt_compact_expand_device and fills the sky itself (RT_FLAG_SKY_ONLY).  Not
                              * for scenes the strict kernel renders (RT_ERR_UNSUPPORTED: send plain bands), not with RT_FLAG_COUNT. */
+  RT_FLAG_STARS_PER_FRAME = 64  /* rt_render_batch_device / rt_render_scatter_device: frame f of the batch draws its stars with seed
+                                 * stars_seed + f (mod 2^32) - N different night skies, as N redraws of the reference give.  Without it
+                                 * every frame of a batch is the same picture.  A no-op for one frame. */
 };
 
 typedef struct rt_scene_dev rt_scene_dev; /* opaque: a scene resident in one GPU's HBM */
@@ -219,6 +232,12 @@ void rt_scene_free(rt_scene_dev *scene);
 int rt_scene_set_camera(rt_scene_dev *scene, const double origin[3], const double axis_x[3], const double axis_y[3], const double axis_z[3],
                         void *hip_stream);
 
+/* Set the stars seed of a resident scene (rt_scene_header.stars_seed; the reference's fresh Math.random() draws per redraw, main.js:180).
+ * Host state only: it is copied into each later render's launch parameters - frames already enqueued keep the seed they were launched
+ * with, nothing is uploaded and no launch table is rebuilt (a stars sky is never a constant background).  Thread rules as for
+ * rt_scene_set_camera.  Any value is valid. */
+int rt_scene_set_stars_seed(rt_scene_dev *scene, uint32_t seed);
+
 /* Render tiles of the w x h frame into DEVICE memory `d_out_rgba` (at least
  * n_tiles*tile_rows*w*4 bytes) on `hip_stream` (a hipStream_t; NULL = the library's own
  * stream for that device).  Asynchronous unless `stats` is non-NULL (then it waits and
@@ -227,8 +246,8 @@ int rt_render_tiles_device(rt_scene_dev *scene, uint32_t w, uint32_t h, const rt
                            void *d_out_rgba, void *hip_stream, uint32_t flags, rt_stats *stats);
 
 /* The same for a BATCH of n_frames frames in one launch (grid z = frame): frame f's tiles go to
- * d_out_rgba + f*frame_stride_bytes.  All frames use `scene` (synthetic batches; a real animation uploads one
- * scene per frame and calls rt_render_tiles_device per frame).  Used by the multi-GPU plan, where a step
+ * d_out_rgba + f*frame_stride_bytes.  All frames use `scene` and its camera (synthetic batches; a real animation moves the
+ * camera per frame and calls rt_render_tiles_device per frame); with RT_FLAG_STARS_PER_FRAME frame f has a sky of its own.  Used by the multi-GPU plan, where a step
  * renders this rank's row tiles of N frames and one all-to-all reassembles frame f on rank f. */
 int rt_render_batch_device(rt_scene_dev *scene, uint32_t w, uint32_t h, const rt_tiles *tiles, uint32_t n_frames,
                            void *d_out_rgba, uint64_t frame_stride_bytes, void *hip_stream, uint32_t flags, rt_stats *stats);
@@ -253,8 +272,9 @@ int rt_ipc_close(int device, void *d_ptr);
  * and the GPU's own stores reach directly).  One GPU: frames of 8 MiB and more are rendered as 4 row bands whose copy-out overlaps
  * the next band's render; into smaller pinned frames the trace kernel stores directly, over PCIe.  Either way the call takes about
  * max(kernel, frame bytes / PCIe rate).  With more than one GPU in use the frame is sharded by interleaved row tiles and put
- * together on GPU 0 (peer stores, or one RCCL gather) before the copy-out.  Replaces redraw()/spanish() + ImageData
- * (main.js:83,180-201). */
+ * together on GPU 0 (peer stores, or one RCCL gather) before the copy-out.  The scene stays resident between calls: a blob that
+ * differs from the previous call's only in the camera and / or stars_seed is not uploaded again (the resident scene moves its camera,
+ * rt_scene_set_camera, and takes the seed, rt_scene_set_stars_seed).  Replaces redraw()/spanish() + ImageData (main.js:83,180-201). */
 int rt_render(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h,
               uint8_t *out_rgba, uint32_t flags, rt_stats *stats);
 
