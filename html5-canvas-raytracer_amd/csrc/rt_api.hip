@@ -24,6 +24,7 @@
 #include "rt_device.h"
 #include "rt_tables.h"
 #include "rt_tables_gpu.h"
+#include "rt_hits.h"
 
 extern "C" int rt_launch_trace_fast(const rt_launch *, int, int, int, unsigned, hipStream_t);
 extern "C" int rt_launch_trace_strict(const rt_launch *, int, int, int, unsigned, hipStream_t);
@@ -1896,6 +1897,154 @@ extern "C" int rt_render_progressive(const void *blob, size_t bytes, uint32_t w,
   if (n_bands == 0 || n_bands > 64u) return fail(RT_ERR_INVALID, "n_bands %u not in 1..64", n_bands);
   if (!on_band) return fail(RT_ERR_INVALID, "on_band is NULL");
   return render_to_host(blob, bytes, w, h, out_rgba, flags, stats, n_bands, on_band, user);
+}
+
+// ------------------------------------------------------------------------------------ primary hits (rt_hits.hip)
+// What is under a sample: the hit kernels read the uploaded blob (camera-independent, never written after the upload) and take the
+// camera from the scene's host state at the call, so they need nothing of the camera pipeline (rt_scene_set_camera's blocks, tables
+// and events) and leave the colour path's launch bookkeeping alone.
+namespace {
+int hits_frame_check(uint32_t w, uint32_t h, uint32_t k, const char *what) {
+  if (w == 0 || h == 0 || w > 65536 || h > 65536) return fail(RT_ERR_INVALID, "%s: frame size %ux%u not in 1..65536", what, w, h);
+  if ((uint64_t)k * w * k * h >= (1ull << 32)) return fail(RT_ERR_INVALID, "%s: a sample grid of %ux%u exceeds 2^32 - 1 samples", what, k * w, k * h);
+  return RT_OK;
+}
+
+int pick_points_check(uint32_t w, uint32_t h, uint32_t k, uint32_t n, const uint32_t *xy, const void *out, const char *what) {
+  if (!xy || !out) return fail(RT_ERR_INVALID, "%s: NULL points or output", what);
+  if (n == 0 || n > 65536u) return fail(RT_ERR_INVALID, "%s: n %u not in 1..65536", what, n);
+  int rc = hits_frame_check(w, h, k, what);
+  if (rc) return rc;
+  for (uint32_t j = 0; j < n; j++)
+    if (xy[2 * j] >= k * w || xy[2 * j + 1] >= k * h)
+      return fail(RT_ERR_INVALID, "%s: point %u (%u, %u) lies outside the %ux%u sample grid", what, j, xy[2 * j], xy[2 * j + 1], k * w, k * h);
+  return RT_OK;
+}
+
+// the launch record's scene part: blob-order spheres, the CURRENT camera, the projection of the k w x k h sample grid
+void hits_bind(rt_scene_dev *s, uint32_t w, uint32_t h, rt_hits_launch &L) {
+  memset(&L, 0, sizeof L);
+  std::lock_guard<std::mutex> lk(s->launch_mu);
+  const rt_scene_header &hd = s->hd;
+  L.objects = (const rt_sphere *)((const uint8_t *)s->d_blob + hd.objects_offset);
+  memcpy(L.cam, hd.cam_origin, 12 * sizeof(double));   // origin, axisX, axisY, axisZ are contiguous
+  L.k = hd.supersample;
+  L.sw = L.k * w; L.sh = L.k * h;
+  // main.js:102-105 for the sample grid, in binary64 on the host (the expressions of render_batch_impl: the same bits)
+  const double projA = hd.fov_deg * M_PI / 180.0;
+  L.proj_w = (double)L.sw / 2.0; L.proj_h = (double)L.sh / 2.0; L.proj_d = L.proj_w / tan(projA / 2.0);
+  L.epsilon = hd.epsilon;
+  L.n_objects = hd.n_objects;
+}
+}  // namespace
+
+extern "C" int rt_render_hits_device(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, const rt_hit_buffers *b, void *hip_stream,
+                                     rt_stats *stats) {
+  if (!s) return fail(RT_ERR_STATE, "rt_render_hits_device: NULL scene handle");
+  if (!tiles || !b) return fail(RT_ERR_INVALID, "rt_render_hits_device: NULL tiles or buffers");
+  int rc = hits_frame_check(w, h, s->hd.supersample, "rt_render_hits_device");
+  if (rc) return rc;
+  if (tiles->tile_rows == 0 || tiles->tile_stride == 0 || tiles->n_tiles == 0) return fail(RT_ERR_INVALID, "rt_render_hits_device: empty tile set");
+  if ((uint64_t)tiles->n_tiles * tiles->tile_rows > (1ull << 24)) return fail(RT_ERR_INVALID, "rt_render_hits_device: too many rows in one call");
+  if (((uintptr_t)b->id & 3u) || ((uintptr_t)b->depth & 7u) || ((uintptr_t)b->normal & 3u))
+    return fail(RT_ERR_INVALID, "rt_render_hits_device: misaligned buffer (id and normal need 4 bytes, depth 8)");
+  if ((rc = ensure_device(s->device))) return rc;
+  device_state &D = G.dev[s->device];
+  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : D.stream;
+  const auto t_begin = std::chrono::steady_clock::now();
+  rt_hits_launch L;
+  hits_bind(s, w, h, L);
+  L.id = b->id; L.depth = b->depth; L.normal = b->normal;
+  L.tile_rows = tiles->tile_rows; L.tile_first = tiles->tile_first; L.tile_stride = tiles->tile_stride;
+  L.band_rows = tiles->n_tiles * L.k * tiles->tile_rows;
+  struct event_pair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~event_pair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  } ev;
+  if (stats) { HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b)); HIP_TRY(hipEventRecord(ev.a, stream)); }
+  if (L.id || L.depth || L.normal) {
+    const int e = rt_launch_hits(&L, stream);
+    if (e != 0) return fail(RT_ERR_DEVICE, "hits kernel launch: %s", hipGetErrorString((hipError_t)e));
+  }
+  if (stats) {
+    HIP_TRY(hipEventRecord(ev.b, stream));
+    HIP_TRY(hipEventSynchronize(ev.b));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = ms;
+    uint64_t px = 0;
+    for (uint32_t i = 0; i < tiles->n_tiles; i++) {
+      const uint64_t r0 = (uint64_t)(tiles->tile_first + (uint64_t)i * tiles->tile_stride) * tiles->tile_rows;
+      if (r0 < h) px += ((r0 + tiles->tile_rows <= h) ? tiles->tile_rows : (h - r0)) * (uint64_t)w;
+    }
+    stats->pixels = px;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
+}
+
+extern "C" int rt_scene_pick(rt_scene_dev *s, uint32_t w, uint32_t h, uint32_t n, const uint32_t *xy, rt_hit *out) {
+  if (!s) return fail(RT_ERR_STATE, "rt_scene_pick: NULL scene handle");
+  int rc = pick_points_check(w, h, s->hd.supersample, n, xy, out, "rt_scene_pick");
+  if (rc) return rc;
+  if ((rc = ensure_device(s->device))) return rc;
+  device_state &D = G.dev[s->device];
+  rt_hits_launch L;
+  hits_bind(s, w, h, L);
+  L.n_points = n;
+  struct device_mem { void *p = nullptr; ~device_mem() { if (p) (void)hipFree(p); } } mem;
+  HIP_TRY(hipMalloc(&mem.p, (size_t)n * (sizeof(rt_hit) + 2u * sizeof(uint32_t))));
+  L.hits = (rt_hit *)mem.p;
+  L.points = (const uint32_t *)((uint8_t *)mem.p + (size_t)n * sizeof(rt_hit));
+  HIP_TRY(hipMemcpyAsync((void *)L.points, xy, (size_t)n * 2u * sizeof(uint32_t), hipMemcpyHostToDevice, D.stream));
+  const int e = rt_launch_pick(&L, D.stream);
+  if (e != 0) return fail(RT_ERR_DEVICE, "pick kernel launch: %s", hipGetErrorString((hipError_t)e));
+  HIP_TRY(hipMemcpyAsync(out, L.hits, (size_t)n * sizeof(rt_hit), hipMemcpyDeviceToHost, D.stream));
+  HIP_TRY(hipStreamSynchronize(D.stream));
+  return RT_OK;
+}
+
+extern "C" int rt_render_hits(const void *blob, size_t bytes, uint32_t w, uint32_t h, const rt_hit_buffers *hb, rt_stats *stats) {
+  if (!hb) return fail(RT_ERR_INVALID, "rt_render_hits: NULL buffers");
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  const uint32_t k = ((const rt_scene_header *)blob)->supersample;
+  if ((rc = hits_frame_check(w, h, k, "rt_render_hits"))) return rc;
+  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
+  std::lock_guard<std::mutex> lk(G.mu);
+  const auto t_begin = std::chrono::steady_clock::now();
+  rt_scene_dev *s = nullptr;
+  if ((rc = scene_for(0, blob, bytes, &s))) return rc;
+  if ((rc = ensure_device(0))) return rc;
+  device_state &D = G.dev[0];
+  const size_t samples = (size_t)k * w * k * h;
+  struct device_bufs { void *p[3] = {nullptr, nullptr, nullptr}; ~device_bufs() { for (void *q : p) if (q) (void)hipFree(q); } } mem;
+  const size_t each[3] = {sizeof(int32_t), sizeof(double), 3u * sizeof(float)};
+  void *const host[3] = {hb->id, hb->depth, hb->normal};
+  for (int i = 0; i < 3; i++) if (host[i]) HIP_TRY(hipMalloc(&mem.p[i], samples * each[i]));
+  const rt_hit_buffers db = {(int32_t *)mem.p[0], (double *)mem.p[1], (float *)mem.p[2]};
+  const rt_tiles whole = {h, 0u, 1u, 1u};
+  rt_stats st;
+  if ((rc = rt_render_hits_device(s, w, h, &whole, &db, D.stream, &st))) return rc;
+  for (int i = 0; i < 3; i++) if (host[i]) HIP_TRY(hipMemcpyAsync(host[i], mem.p[i], samples * each[i], hipMemcpyDeviceToHost, D.stream));
+  HIP_TRY(hipStreamSynchronize(D.stream));
+  if (stats) {
+    *stats = st;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
+}
+
+extern "C" int rt_pick(const void *blob, size_t bytes, uint32_t w, uint32_t h, uint32_t n, const uint32_t *xy, rt_hit *out) {
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  if ((rc = pick_points_check(w, h, ((const rt_scene_header *)blob)->supersample, n, xy, out, "rt_pick"))) return rc;
+  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
+  std::lock_guard<std::mutex> lk(G.mu);
+  rt_scene_dev *s = nullptr;
+  if ((rc = scene_for(0, blob, bytes, &s))) return rc;
+  return rt_scene_pick(s, w, h, n, xy, out);
 }
 
 namespace {

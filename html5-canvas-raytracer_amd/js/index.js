@@ -62,10 +62,34 @@ function renderProgressive(width, height, sceneObj, opts) {
   return r.promise.then((stats) => { r.data.stats = stats; return r.data; });
 }
 
+// What is under the samples (main.js:216-231, 440-449, which the reference computes per ray and drops after shading): the primary
+// hit of every sample of the frame's sample grid (k*width x k*height when the scene supersamples by k), row-major:
+//   id      Int32Array, the index into scene.objects | inside << 16, or -1 where the ray meets nothing (main.js:231)
+//   depth   Float64Array, hit.t (Infinity on a miss)                  opts.depth === false: not computed (null)
+//   normal  Float32Array, 3 per sample, hit.n (0,0,0 on a miss)        opts.normal === false: not computed (null)
+function renderHits(width, height, sceneObj, opts) {
+  if (!inited) init(opts && opts.maxDevices);
+  return native().renderHits(flattenScene(sceneObj), width, height, !(opts && opts.depth === false), !(opts && opts.normal === false));
+}
+
+// Pixel picking: what is under output pixel (x, y) - clicking on the canvas.  The pixel's sample is the centre one of its k x k block,
+// (k*x + floor(k/2), k*y + floor(k/2)).  Returns {index, object: scene.objects[index], inside, t, point, normal, u, v} (hit.u / hit.v
+// of main.js:446-447), or null when the ray meets nothing.  Throws for a pixel outside the frame.
+function pick(width, height, sceneObj, x, y) {
+  if (!(Number.isInteger(x) && Number.isInteger(y) && x >= 0 && y >= 0 && x < width && y < height)) {
+    throw new RangeError('pick: (' + x + ', ' + y + ') is not a pixel of the ' + width + 'x' + height + ' frame');
+  }
+  if (!inited) init();
+  const k = sceneObj.supersample || 1, c = Math.floor(k / 2);
+  const r = native().pick(flattenScene(sceneObj), width, height, k * x + c, k * y + c);
+  if (r) r.object = sceneObj.objects[r.index];
+  return r;
+}
+
 // `const build = '741'` (main.js:3) + this library's revision; every render's `.stats` also carries `.build` and `.report`, the
 // reference's end-of-frame string 'build #<id> (<elapsed>ms)' (main.js:204-205) for that render.
 function buildId() { return native().buildId(); }
 
 function shutdown() { if (addon) addon.shutdown(); inited = false; }
 
-module.exports = Object.assign({render, renderAsync, renderProgressive, init, shutdown, buildId, flattenScene, scenes, native}, scene);
+module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, init, shutdown, buildId, flattenScene, scenes, native}, scene);

@@ -14,6 +14,9 @@
 //   GET /frame?...&progressive=8        the same bytes as a CHUNKED response, one chunk per row band as it leaves the
 //                                       GPU (renderProgressive): the page paints top to bottom like the reference's
 //                                       scanline loop (main.js:183-201)
+//   GET /pick?scene=h8&w=1280&h=720&x=640&y=360[&seed=N]
+//                                       what is under output pixel (x, y) (RT.pick): JSON {index, inside, t, point, normal, u, v},
+//                                       or null where the ray meets nothing; x, y outside the frame: 400
 //   GET /scenes                         JSON list of scene names
 // Errors (no GPU, bad scene, bad size) are JSON with status 4xx/5xx; never a CPU-rendered frame.
 //
@@ -59,6 +62,17 @@ const PAGE = `<!DOCTYPE html>
   const message = 'build #' + (r.headers.get('X-Build') || '?') + ' (' + (Date.now() - t0) + 'ms)';
   ctx.font = '16px monospace'; ctx.textAlign = 'left'; ctx.textBaseline = 'top'; ctx.fillStyle = '#ffffff';
   ctx.fillText(message, 0, 0);
+  // a click asks what is under that pixel (GET /pick) and shows the sphere's index and distance beside the cursor
+  canvas.addEventListener('click', async (ev) => {
+    const pr = await fetch('/pick?scene=' + scene + '&w=' + w + '&h=' + h + '&x=' + Math.floor(ev.offsetX) + '&y=' + Math.floor(ev.offsetY) +
+      (seed !== null ? '&seed=' + encodeURIComponent(seed) : ''));
+    const hit = await pr.json();
+    const text = !pr.ok ? hit.error : hit === null ? 'nothing' : 'object #' + hit.index + '  t = ' + hit.t.toFixed(4);
+    ctx.font = '16px monospace'; ctx.textAlign = 'left'; ctx.textBaseline = 'top';
+    const tw = ctx.measureText(text).width;
+    ctx.fillStyle = '#000000'; ctx.fillRect(ev.offsetX + 8, ev.offsetY + 8, tw + 8, 20);
+    ctx.fillStyle = '#ffffff'; ctx.fillText(text, ev.offsetX + 12, ev.offsetY + 10);
+  });
 })();
 </script></body></html>`;
 
@@ -94,7 +108,7 @@ function createServer(opts) {
       return res.end(PAGE);
     }
     if (u.pathname === '/scenes') return sendJSON(res, 200, {scenes: listScenes()});
-    if (u.pathname === '/frame') {
+    if (u.pathname === '/frame' || u.pathname === '/pick') {
       const w = parseInt(u.query.w, 10), h = parseInt(u.query.h, 10);
       if (!(w > 0 && h > 0 && w <= 65536 && h <= 65536 && w * h <= maxPixels)) return sendJSON(res, 400, {error: 'w and h must be positive integers within the frame limit'});
       let scene;
@@ -104,6 +118,14 @@ function createServer(opts) {
         const seed = /^[0-9]{1,10}$/.test(String(u.query.seed)) ? Number(u.query.seed) : -1;
         if (!(seed >= 0 && seed < 4294967296)) return sendJSON(res, 400, {error: 'seed must be an integer in [0, 2^32)'});
         scene = Object.assign({}, scene, {starsSeed: seed});
+      }
+      if (u.pathname === '/pick') {
+        const x = /^[0-9]{1,5}$/.test(String(u.query.x)) ? Number(u.query.x) : -1, y = /^[0-9]{1,5}$/.test(String(u.query.y)) ? Number(u.query.y) : -1;
+        if (!(x >= 0 && y >= 0 && x < w && y < h)) return sendJSON(res, 400, {error: 'x and y must be integers inside the w x h frame'});
+        let hit;
+        try { hit = RT.pick(w, h, scene, x, y); } catch (e) { return sendJSON(res, 503, {error: e.message}); }
+        if (hit) delete hit.object;                  // (the scene's own record: the page knows it by its index)
+        return sendJSON(res, 200, hit);
       }
       const bands = parseInt(u.query.progressive || '0', 10);
       if (bands > 0) {

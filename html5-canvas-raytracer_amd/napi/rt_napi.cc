@@ -8,6 +8,9 @@
 //           renderAsync(blob, w, h, flags) -> Promise of the same        shutdown()      abiVersion()
 //           renderProgressive(blob, w, h, flags, bands, onBand(firstRow, nRows)) -> {data, promise}: `data` is the frame
 //           being filled; onBand fires on the main thread as each row band lands in it; the promise resolves to the stats
+//           renderHits(blob, w, h, wantDepth, wantNormal) -> {id: Int32Array, depth: Float64Array | null, normal: Float32Array | null}
+//           pick(blob, w, h, sx, sy) -> {index, inside, t, point, normal, u, v} or null (a miss); sx, sy in sample-grid coordinates
+//           (these two are not enumerable: the enumerable surface is the frame API)
 // Every failure of the library becomes a thrown JS Error carrying rt_last_error().
 //
 // Build: g++ -shared -fPIC -I/usr/include/node rt_napi.cc -L../csrc -lrt_hip  (napi/Makefile; no node-gyp).
@@ -327,6 +330,85 @@ napi_value Validate(napi_env env, napi_callback_info info) {
   return v;
 }
 
+// renderHits(blob, w, h, wantDepth, wantNormal): the primary hit of every sample (rt_render_hits) into typed arrays the JS heap owns
+napi_value RenderHits(napi_env env, napi_callback_info info) {
+  args a;
+  if (!parse(env, info, &a, false)) return nullptr;
+  size_t argc = 5;
+  napi_value argv[5];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  bool want_depth = true, want_normal = true;
+  if (argc >= 4) napi_get_value_bool(env, argv[3], &want_depth);
+  if (argc >= 5) napi_get_value_bool(env, argv[4], &want_normal);
+  // the sample grid's size comes from the blob: a malformed one is refused before anything is allocated
+  const int vrc = rt_scene_validate(a.blob, a.bytes);
+  const uint32_t k = vrc == RT_OK ? ((const rt_scene_header *)a.blob)->supersample : 1u;
+  const size_t n = (size_t)k * a.w * k * a.h;
+  napi_value ab_id = nullptr, ab_depth = nullptr, ab_normal = nullptr, res, v;
+  void *p_id = nullptr, *p_depth = nullptr, *p_normal = nullptr;
+  const bool ok = vrc == RT_OK && a.w <= 65536u && a.h <= 65536u && n < (1ull << 32) &&
+                  napi_create_arraybuffer(env, n * 4u, &p_id, &ab_id) == napi_ok &&
+                  (!want_depth || napi_create_arraybuffer(env, n * 8u, &p_depth, &ab_depth) == napi_ok) &&
+                  (!want_normal || napi_create_arraybuffer(env, n * 12u, &p_normal, &ab_normal) == napi_ok);
+  if (!ok) {
+    if (a.owned) free(a.blob);
+    if (vrc != RT_OK) return throw_rt(env, "rt_render_hits", vrc);
+    napi_throw_error(env, nullptr, "renderHits: the frame is too large or its output arrays cannot be allocated");
+    return nullptr;
+  }
+  const rt_hit_buffers b = {(int32_t *)p_id, (double *)p_depth, (float *)p_normal};
+  a.rc = rt_render_hits(a.blob, a.bytes, a.w, a.h, &b, &a.st);
+  if (a.owned) free(a.blob);
+  if (a.rc != RT_OK) return throw_rt(env, "rt_render_hits", a.rc);
+  NAPI_TRY(napi_create_object(env, &res));
+  NAPI_TRY(napi_create_typedarray(env, napi_int32_array, n, ab_id, 0, &v)); napi_set_named_property(env, res, "id", v);
+  if (want_depth) { NAPI_TRY(napi_create_typedarray(env, napi_float64_array, n, ab_depth, 0, &v)); } else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "depth", v);
+  if (want_normal) { NAPI_TRY(napi_create_typedarray(env, napi_float32_array, 3 * n, ab_normal, 0, &v)); } else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "normal", v);
+  napi_create_uint32(env, k * a.w, &v); napi_set_named_property(env, res, "width", v);
+  napi_create_uint32(env, k * a.h, &v); napi_set_named_property(env, res, "height", v);
+  napi_create_double(env, a.st.kernel_ms, &v); napi_set_named_property(env, res, "kernel_ms", v);
+  return res;
+}
+
+napi_value doubles(napi_env env, const double *x, int n) {
+  napi_value arr, v;
+  napi_create_array_with_length(env, n, &arr);
+  for (int i = 0; i < n; i++) { napi_create_double(env, x[i], &v); napi_set_element(env, arr, i, v); }
+  return arr;
+}
+
+// pick(blob, w, h, sx, sy): one sample's hit record (rt_pick), or null on a miss
+napi_value Pick(napi_env env, napi_callback_info info) {
+  args a;
+  if (!parse(env, info, &a, false)) return nullptr;
+  size_t argc = 5;
+  napi_value argv[5];
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  uint32_t xy[2];
+  if (argc < 5 || napi_get_value_uint32(env, argv[3], &xy[0]) != napi_ok || napi_get_value_uint32(env, argv[4], &xy[1]) != napi_ok) {
+    if (a.owned) free(a.blob);
+    napi_throw_type_error(env, nullptr, "pick(blob, width, height, sx, sy): sx, sy must be non-negative integers");
+    return nullptr;
+  }
+  rt_hit r;
+  a.rc = rt_pick(a.blob, a.bytes, a.w, a.h, 1u, xy, &r);
+  if (a.owned) free(a.blob);
+  if (a.rc != RT_OK) return throw_rt(env, "rt_pick", a.rc);
+  napi_value res, v;
+  if (r.object < 0) { napi_get_null(env, &res); return res; }
+  NAPI_TRY(napi_create_object(env, &res));
+  napi_create_int32(env, r.object, &v); napi_set_named_property(env, res, "index", v);
+  napi_get_boolean(env, r.inside != 0, &v); napi_set_named_property(env, res, "inside", v);
+  napi_create_double(env, r.t, &v); napi_set_named_property(env, res, "t", v);
+  napi_set_named_property(env, res, "point", doubles(env, r.point, 3));
+  napi_set_named_property(env, res, "normal", doubles(env, r.normal, 3));
+  napi_create_double(env, r.u, &v); napi_set_named_property(env, res, "u", v);
+  napi_create_double(env, r.v, &v); napi_set_named_property(env, res, "v", v);
+  return res;
+}
+
 napi_value Module(napi_env env, napi_value exports) {
   const napi_property_descriptor props[] = {
       {"init", nullptr, Init, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
@@ -337,6 +419,8 @@ napi_value Module(napi_env env, napi_value exports) {
       {"shutdown", nullptr, Shutdown, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"abiVersion", nullptr, AbiVersion, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"buildId", nullptr, BuildId, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"renderHits", nullptr, RenderHits, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"pick", nullptr, Pick, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

@@ -143,6 +143,16 @@ class RtStats(C.Structure):
                 ("shadow_rays", C.c_uint64), ("sphere_tests", C.c_uint64), ("exact_samples", C.c_uint64)]
 
 
+class RtHit(C.Structure):
+    """A primary hit (include/rt_hip.h rt_hit, 80 bytes): main.js:440-449's hit_i, inside flag, t, p, n, u, v."""
+    _fields_ = [("object", C.c_int32), ("inside", C.c_int32), ("t", C.c_double), ("point", C.c_double * 3), ("normal", C.c_double * 3),
+                ("u", C.c_double), ("v", C.c_double)]
+
+
+class RtHitBuffers(C.Structure):
+    _fields_ = [("id", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p)]
+
+
 # every symbol include/rt_hip.h declares: (restype, argtypes)
 ABI = {
     "rt_init": (C.c_int, [C.c_int]),
@@ -186,6 +196,11 @@ ABI = {
     "rt_compact_expand_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_deinterleave_rgb24_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.c_uint64, C.c_void_p]),
+    "rt_render_hits_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtTiles), C.POINTER(RtHitBuffers), C.c_void_p,
+                                        C.POINTER(RtStats)]),
+    "rt_scene_pick": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(RtHit)]),
+    "rt_render_hits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(RtHitBuffers), C.POINTER(RtStats)]),
+    "rt_pick": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(RtHit)]),
 }
 
 
@@ -291,6 +306,23 @@ class Renderer:
         t = tiles if isinstance(tiles, RtTiles) else RtTiles(*tiles)
         _check(self.lib, self.lib.rt_compact_expand_device(self.handle, w, h, C.byref(t), C.c_void_p(d_compact), C.c_void_p(d_frame), C.c_void_p(stream or 0)), "rt_compact_expand_device")
 
+    def render_hits(self, w, h, id_ptr, depth_ptr, normal_ptr, tiles=None, stream=None, want_stats=False):
+        """Primary hits of `tiles` (output rows) into DEVICE buffers (0 / None = not wanted): per sample int32 id (sphere index |
+        inside << 16, -1 = miss), float64 depth, 3 x float32 normal; tile slot i holds its k*tile_rows sample rows of k*w samples."""
+        t = tiles if isinstance(tiles, RtTiles) else RtTiles(*(tiles or (h, 0, 1, 1)))
+        bufs = RtHitBuffers(id_ptr or None, depth_ptr or None, normal_ptr or None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_render_hits_device(self.handle, w, h, C.byref(t), C.byref(bufs), C.c_void_p(stream or 0),
+                                            C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_render_hits_device")
+        return st
+
+    def pick(self, w, h, points):
+        """Hit records of sample points [(x, y), ...] (sample-grid coordinates), with the scene's current camera: a list of dicts
+        (_hit_dict), None for a miss."""
+        n, xy = _points_array(points)
+        return _pick_call(self.lib, lambda n, xy, out: self.lib.rt_scene_pick(self.handle, w, h, n, xy, out), n, xy, "rt_scene_pick")
+
     def close(self):
         if self.handle:
             self.lib.rt_scene_free(self.handle)
@@ -335,3 +367,55 @@ def render(width, height, scene, flags=0, lib=None, max_devices=1):
         return C.string_at(p, n), st
     finally:
         lib.rt_free_pinned(p)
+
+
+def _init_once(lib):
+    if lib.rt_device_count() < 0:                     # not initialised yet: one GPU, as render() (an earlier rt_init's choice stands)
+        _check(lib, lib.rt_init(1), "rt_init")
+
+
+def _hit_dict(r):
+    if r.object < 0:
+        return None
+    return {"object": r.object, "inside": bool(r.inside), "t": r.t, "point": list(r.point), "normal": list(r.normal), "u": r.u, "v": r.v}
+
+
+def _points_array(points):
+    pts = [(int(x), int(y)) for x, y in points]
+    if not all(0 <= c < 2 ** 32 for p in pts for c in p):
+        raise ValueError("sample coordinates must be integers in [0, 2^32)")
+    return len(pts), (C.c_uint32 * (2 * len(pts)))(*[c for p in pts for c in p])
+
+
+def _pick_call(lib, call, n, xy, what):
+    if n == 0:
+        return []
+    out = (RtHit * n)()
+    _check(lib, call(n, xy, out), what)
+    return [_hit_dict(r) for r in out]
+
+
+def hits(width, height, scene, lib=None):
+    """hits(width,height,scene) -> {"id": int32 (kh, kw), "depth": float64 (kh, kw), "normal": float32 (kh, kw, 3)}: the primary hit of
+    every sample (k = the scene's supersample factor), rendered on GPU 0 with rt_render's resident scene."""
+    import numpy as np
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    k = struct.unpack_from("<I", blob, 164)[0]          # rt_scene_header.supersample
+    _init_once(lib)
+    out = {"id": np.empty((k * height, k * width), np.int32), "depth": np.empty((k * height, k * width), np.float64),
+           "normal": np.empty((k * height, k * width, 3), np.float32)}
+    bufs = RtHitBuffers(out["id"].ctypes.data, out["depth"].ctypes.data, out["normal"].ctypes.data)
+    buf = C.create_string_buffer(blob, len(blob))
+    _check(lib, lib.rt_render_hits(buf, len(blob), width, height, C.byref(bufs), None), "rt_render_hits")
+    return out
+
+
+def pick(width, height, scene, points, lib=None):
+    """pick(width,height,scene,points) -> [hit dict or None per (x, y) sample point] on GPU 0 with rt_render's resident scene."""
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    n, xy = _points_array(points)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    return _pick_call(lib, lambda n, xy, out: lib.rt_pick(buf, len(blob), width, height, n, xy, out), n, xy, "rt_pick")

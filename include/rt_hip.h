@@ -332,6 +332,56 @@ int rt_compact_count(rt_scene_dev *scene, uint32_t w, uint32_t h, const rt_tiles
  * `d_frame` (w x h, alpha 255).  The sky blocks are not part of the band: the frame's owner stores them with RT_FLAG_SKY_ONLY. */
 int rt_compact_expand_device(rt_scene_dev *scene, uint32_t w, uint32_t h, const rt_tiles *tiles, const void *d_compact, void *d_frame, void *hip_stream);
 
+/* What is under a sample: primary hits.  The reference computes, per ray, the closest sphere and where and how it is met
+ * (main.js:216-231, 440-449: hit_i, hit.t, hit.p, hit.n, the inside flag behind hit.l, hit.u / hit.v) and throws it away after
+ * shading; these entry points return it - for picking (clicking on the canvas), depth compositing and object-id / normal views.
+ *
+ * For each sample of the sample grid (k w x k h when the scene supersamples by k, else w x h) the primary ray of main.js:184-193
+ * (the reference's operation order, dist indexed by component: quirk q1) and then:
+ *   id      the closest hit over the spheres in BLOB order (the host's sorted `objects`, main.js:159-163), strict <, first wins
+ *           (main.js:223-231): the reference's hit_i, | inside << 16 with inside = (t0 < eps || t1 < eps) of main.js:445; -1 on a
+ *           miss (main.js:231).  (Not the colour kernels' internal loop order, which moves an enclosing sphere last.)
+ *   depth   hit.t as binary64; +Infinity on a miss.
+ *   normal  hit.n = (hit.p - origin) * (1 / |hit.p - origin|) (quirk q7), as 3 float32 each rounded to nearest from binary64;
+ *           0, 0, 0 on a miss.
+ *   pick    (single samples, binary64 throughout) object, inside, t, point = hit.p, normal = hit.n, and u, v of main.js:446-447:
+ *           atan2(-n[2], -n[0]) / pi / 2 + 0.5 and asin(-n[1]) / (pi / 2) / 2 + 0.5 - two successive divisions each (q6), with
+ *           fdlibm's atan2 / asin as the JS engines have them.  A miss: object -1, inside 0, t +Infinity, everything else 0.
+ * The arithmetic is the strict one (no FMA contraction; the reference's own discriminant r2 - d2), so t, p and n are the bits
+ * of the reference's expressions.  The primary ray is traced whatever the scene's depth (segs). */
+typedef struct rt_hit {
+  int32_t object;     /* hit_i (blob order), or -1 */
+  int32_t inside;     /* 1: the ray starts inside the sphere (main.js:445) */
+  double t;
+  double point[3];
+  double normal[3];
+  double u, v;
+} rt_hit;             /* 80 bytes */
+
+typedef struct rt_hit_buffers {
+  int32_t *id;        /* one per sample, or NULL */
+  double *depth;      /* one per sample, or NULL */
+  float *normal;      /* three per sample, or NULL */
+} rt_hit_buffers;
+
+/* The primary hits of `tiles` (in OUTPUT rows, as rt_render_tiles_device) into DEVICE buffers: tile slot i holds its k*tile_rows
+ * sample rows of k*w samples one after another (rows past the frame's last are not written).  Any buffer may be NULL and is then
+ * not touched; id and normal must be 4-byte aligned, depth 8-byte aligned.  Uses the scene's CURRENT camera (the latest
+ * rt_scene_set_camera).  Stream and thread rules as rt_render_tiles_device: asynchronous on `hip_stream` (NULL = the library's
+ * stream for the scene's device) unless `stats` is non-NULL (then it waits and fills kernel_ms, total_ms and pixels). */
+int rt_render_hits_device(rt_scene_dev *scene, uint32_t w, uint32_t h, const rt_tiles *tiles,
+                          const rt_hit_buffers *d_bufs, void *hip_stream, rt_stats *stats);
+
+/* The hit records of n (1..65536) samples, sample_xy = {x0, y0, x1, y1, ...} in sample-grid coordinates (x < k*w, y < k*h), into
+ * the HOST array out[n], with the scene's current camera.  Synchronous. */
+int rt_scene_pick(rt_scene_dev *scene, uint32_t w, uint32_t h, uint32_t n, const uint32_t *sample_xy, rt_hit *out);
+
+/* The host forms: rt_render's resident scene (a blob that differs from the resident one only in the camera and / or stars_seed is
+ * not uploaded again: the resident scene moves its camera), outputs in HOST memory.  rt_render_hits fills the whole frame's
+ * (k*w x k*h samples) non-NULL buffers of host_bufs; rt_pick is rt_scene_pick on that scene.  Both synchronous, on GPU 0. */
+int rt_render_hits(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h, const rt_hit_buffers *host_bufs, rt_stats *stats);
+int rt_pick(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h, uint32_t n, const uint32_t *sample_xy, rt_hit *out);
+
 #ifdef __cplusplus
 }
 #endif
