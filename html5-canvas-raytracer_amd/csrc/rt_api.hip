@@ -1,5 +1,5 @@
-// rt_api.hip — the C ABI of include/rt_hip.h: scene validation/upload, the host-built tables (cull rectangles, shadow
-// grids, bounce table, launch table), launches, pinned framebuffers, and the single-process multi-GPU frame (interleaved
+// rt_api.hip — the C ABI of include/rt_hip.h: scene validation/upload, camera and object moves of a resident scene, the host-built
+// tables (cull rectangles, shadow grids, bounce table, launch table), launches, pinned framebuffers, and the single-process multi-GPU frame (interleaved
 // row tiles stored straight into GPU 0's frame over xGMI; fallback: RGB24 bands + one RCCL gather + de-interleave).
 //
 // Host-side counterpart of the reference's driver code: main() sets up what a frame needs
@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <mutex>
@@ -25,6 +26,7 @@
 #include "rt_tables.h"
 #include "rt_tables_gpu.h"
 #include "rt_hits.h"
+#include "rt_objects_gpu.h"
 
 extern "C" int rt_launch_trace_fast(const rt_launch *, int, int, int, unsigned, hipStream_t);
 extern "C" int rt_launch_trace_strict(const rt_launch *, int, int, int, unsigned, hipStream_t);
@@ -179,13 +181,26 @@ struct rt_scene_dev {
   // when the camera moves (rt_scene_set_camera).
   uint8_t *arena = nullptr;
   size_t arena_bytes = 0;
-  void *d_blob;                  // the uploaded scene blob
+  void *d_blob;                  // the uploaded scene blob (its texels and lights; its sphere records are the OBJECT BLOCK's)
   rt_texture_desc *d_texdesc;    // RT_MAX_TEXTURES descriptors (zero padded)
-  rt_geom *d_geom;               // camera-independent geometry tables, per ordering [plain N | anchored at light k: NL x N]
-  rt_sphere *d_objects_b;        // object records with the enclosing sphere moved last (ordering B); NULL if none
-  uint64_t *d_shadow_grid;       // light grids for the product kernel's loop order, or NULL (few spheres)
-  uint64_t *d_bounce_table;      // bounce table for the same order, or NULL (few spheres, or depth < 2)
-  uint8_t *d_lds_image;          // many spheres: per ordering [materials (rt_mtl) | 16 texture descriptors], the LDS image (few spheres: it holds the cull rectangles and lives in the camera block)
+  double *d_cones;               // the bounce table's cell cones (rt_tables.cpp: bounce_cell_cones), or NULL (no bounce table)
+  // The OBJECT BLOCK: what depends on the spheres but not on the camera, at offsets o_* inside it:
+  //   o_objs     the sphere records in blob order (1/r in `reserved`)
+  //   o_geom     camera-independent geometry tables, per ordering [plain N | anchored at light k: NL x N]
+  //   o_objs_b   object records with the enclosing sphere moved last (ordering B); none without one
+  //   o_img      many spheres: per ordering [materials (rt_mtl) | 16 texture descriptors], the LDS image (few spheres: it holds the
+  //              cull rectangles and lives in the camera block)
+  //   o_sg       light grids for the product kernel's loop order (has_sg: more than RT_SGRID_MIN_LOOP loop spheres)
+  //   o_bt       bounce table for the same order (has_bt: more than RT_BTABLE_MIN_LOOP loop spheres and depth >= 2)
+  // Everything up to the shadow grids' masks (obj_host_bytes) is written by the host; the masks and the bounce table are built from it
+  // (rt_objects_gpu.hip after a move; rt_tables.cpp at upload).  TWO blocks, like the camera blocks: generation g reads block g & 1,
+  // so that rt_scene_set_objects can write the next one while launches with the current spheres are still running.
+  uint8_t *d_obj_buf[2];
+  size_t obj_bytes, obj_host_bytes;
+  size_t o_objs, o_geom, o_objs_b, o_img, o_sg, o_bt, sg_bytes, bt_bytes;
+  bool has_sg, has_bt;
+  uint64_t obj_version = 0;      // bumped by every object move; slot_version[b]: the version object block b holds
+  uint64_t slot_version[2] = {0, 0};
   // The camera block: per ordering [anchored at the camera N | cull rectangles N], then (few spheres) the LDS images.  TWO of them:
   // camera generation g lives in block g & 1, so that the block of the NEXT camera can be written - on the scene's own side stream,
   // by rt_scene_set_camera - while launches with the current one are still running.
@@ -310,6 +325,18 @@ extern "C" int rt_device_count(void) {
 }
 
 // ------------------------------------------------------------------------------------ validation (host logic only)
+namespace {
+// one sphere record of a scene with `n_textures` textures (rt_scene_validate, rt_scene_set_objects)
+int check_sphere(const rt_sphere &o, uint32_t i, uint32_t n_textures) {
+  const int k = o.sampler_kind;
+  if (k != RT_SAMPLER_COLOR && k != RT_SAMPLER_TEXTURE && k != RT_SAMPLER_CHECKER && k != RT_SAMPLER_STARS)
+    return fail(RT_ERR_UNSUPPORTED, "object %u: sampler kind %d is not supported (0 colour, 1 texture, 2 checker, 3 hashed stars)", i, k);
+  if (k == RT_SAMPLER_TEXTURE && (o.texture < 0 || (uint32_t)o.texture >= n_textures))
+    return fail(RT_ERR_INVALID, "object %u: texture index %d out of range", i, o.texture);
+  return RT_OK;
+}
+}  // namespace
+
 extern "C" int rt_scene_validate(const void *blob, size_t bytes) {
   if (!blob || bytes < sizeof(rt_scene_header)) return fail(RT_ERR_INVALID, "scene blob shorter than its header");
   if (((uintptr_t)blob & 7u) != 0) return fail(RT_ERR_INVALID, "scene blob must be 8-byte aligned");
@@ -335,13 +362,8 @@ extern "C" int rt_scene_validate(const void *blob, size_t bytes) {
       return fail(RT_ERR_INVALID, "texture %u: texels out of bounds", t);
   }
   const rt_sphere *ob = (const rt_sphere *)(base + hd->objects_offset);
-  for (uint32_t i = 0; i < hd->n_objects; i++) {
-    const int k = ob[i].sampler_kind;
-    if (k != RT_SAMPLER_COLOR && k != RT_SAMPLER_TEXTURE && k != RT_SAMPLER_CHECKER && k != RT_SAMPLER_STARS)
-      return fail(RT_ERR_UNSUPPORTED, "object %u: sampler kind %d is not supported (0 colour, 1 texture, 2 checker, 3 hashed stars)", i, k);
-    if (k == RT_SAMPLER_TEXTURE && (ob[i].texture < 0 || (uint32_t)ob[i].texture >= hd->n_textures))
-      return fail(RT_ERR_INVALID, "object %u: texture index %d out of range", i, ob[i].texture);
-  }
+  for (uint32_t i = 0; i < hd->n_objects; i++)
+    if (int rc = check_sphere(ob[i], i, hd->n_textures)) return rc;
   return RT_OK;
 }
 
@@ -391,7 +413,8 @@ void free_order_entry(rt_scene_dev::order_entry &e) {
   e.built = nullptr;
 }
 inline uint8_t *cam_block(const rt_scene_dev *s) { return s->d_cam_buf[s->cam_gen & 1u]; }
-inline uint8_t *lds_image_of(const rt_scene_dev *s) { return s->cull_in_lds ? cam_block(s) + s->cam_lds_offset : s->d_lds_image; }
+inline uint8_t *obj_block(const rt_scene_dev *s) { return s->d_obj_buf[s->cam_gen & 1u]; }
+inline uint8_t *lds_image_of(const rt_scene_dev *s) { return s->cull_in_lds ? cam_block(s) + s->cam_lds_offset : obj_block(s) + s->o_img; }
 
 // [materials (rt_mtl) | 16 texture descriptors | cull rectangles (few spheres)] of ordering `ord`: the workgroup's LDS image
 void fill_lds_image(const rt_scene_dev *s, uint8_t *dst, int ord) {
@@ -451,28 +474,14 @@ void camera_decisions(rt_scene_dev *s) {
   scene_tile_weights(hd, ob, &s->host_cull, &s->tile_weight);
 }
 
-// a staging slot of `bytes` (<= stage_bytes), free to be written: its previous copy has been read
-uint8_t *acquire_stage(rt_scene_dev *s, rt_scene_dev::stage_slot **slot) {
-  rt_scene_dev::stage_slot &g = s->stages[s->stage_next++ & 15u];
-  if (g.used) (void)hipEventSynchronize(g.done);
-  g.used = true;
-  *slot = &g;
-  return g.h;
-}
-}  // namespace
-
-extern "C" int rt_scene_upload(int device, const void *blob, size_t bytes, rt_scene_dev **out) {
-  if (!out) return fail(RT_ERR_INVALID, "out handle is NULL");
-  *out = nullptr;
-  int rc = rt_scene_validate(blob, bytes);
-  if (rc) return rc;
-  if ((rc = ensure_device(device))) return rc;
-  const rt_scene_header *hd = (const rt_scene_header *)blob;
-  rt_scene_dev *s = new rt_scene_dev();
-  s->device = device; s->hd = *hd; s->d_blob = nullptr; s->d_texdesc = nullptr; s->d_geom = nullptr; s->d_objects_b = nullptr; s->d_lds_image = nullptr; s->d_shadow_grid = nullptr; s->d_bounce_table = nullptr;
-  s->d_cam_buf[0] = s->d_cam_buf[1] = nullptr;
-  const uint8_t *base = (const uint8_t *)blob;
-  const rt_sphere *ob = (const rt_sphere *)(base + hd->objects_offset);
+// What of a resident scene depends on its spheres and is decided on the host - in ONE place, for rt_scene_upload and
+// rt_scene_set_objects alike: the device copy of the records (host_blob's, with 1/r in `reserved`), ordering B, the kernel
+// variant, the strict-kernel coincidences, the samplers' boundary tolerance, the mark weight rule and the enclosing sphere's
+// background.  Reads host_objects (the records as given); `enclosing` is decided already.
+void object_decisions(rt_scene_dev *s) {
+  const rt_scene_header *hd = &s->hd;
+  const uint8_t *base = s->host_blob.data();
+  const rt_sphere *ob = s->host_objects.data();
   s->refract = false;
   for (uint32_t i = 0; i < hd->n_objects; i++) if (ob[i].albedo[4] > 0.0) s->refract = true;
   // Scenes whose picture hinges on exact coincidences are rendered by the strict kernel throughout (the product kernel's
@@ -487,9 +496,8 @@ extern "C" int rt_scene_upload(int device, const void *blob, size_t bytes, rt_sc
   s->needs_strict_scene = false;
   for (uint32_t i = 0; i < hd->n_objects; i++) {
     if (!(ob[i].r2 > 0.0) || !std::isfinite(ob[i].r2)) s->needs_strict_scene = true;
-    const double *lt = (const double *)(base + hd->lights_offset);
     for (uint32_t k = 0; k < hd->n_lights; k++) {
-      const double x = lt[3 * k] - ob[i].origin[0], y = lt[3 * k + 1] - ob[i].origin[1], z = lt[3 * k + 2] - ob[i].origin[2];
+      const double x = s->lights[k][0] - ob[i].origin[0], y = s->lights[k][1] - ob[i].origin[1], z = s->lights[k][2] - ob[i].origin[2];
       if (fabs((x * x + y * y + z * z) - ob[i].r2) <= 1e-9 * fmax(ob[i].r2, 1.0)) s->needs_strict_scene = true;
     }
   }
@@ -523,12 +531,6 @@ extern "C" int rt_scene_upload(int device, const void *blob, size_t bytes, rt_sc
       if (ob[i].sampler_kind == RT_SAMPLER_CHECKER) for (int c = 0; c < 6; c++) if (!(ob[i].checker_color[c / 3][c % 3] >= 0.0 && ob[i].checker_color[c / 3][c % 3] <= 1.0)) s->unit_weights = false;
     }
   }
-  memset(s->lights, 0, sizeof s->lights);
-  if (hd->n_lights) memcpy(s->lights, base + hd->lights_offset, hd->n_lights * 24u);
-  rt_texture_desc (&descs)[RT_MAX_TEXTURES] = s->descs;
-  memset(descs, 0, sizeof descs);
-  if (hd->n_textures) memcpy(descs, base + hd->textures_offset, hd->n_textures * sizeof(rt_texture_desc));
-  s->enclosing = enclosing_sphere(hd, ob, s->lights);     // (rt_tables.cpp)
   s->enclosing_flat = false;
   if (s->enclosing != ~0u) {
     const rt_sphere &sk = ob[s->enclosing];
@@ -547,88 +549,160 @@ extern "C" int rt_scene_upload(int device, const void *blob, size_t bytes, rt_sc
       s->sky_rgb[c] = (m1 < amb) ? (double)amb : m1;                    // Math.max(amb, .) as the kernel's maxa() evaluates it
     }
   }
-  s->host_objects.assign(ob, ob + hd->n_objects);
-  // device copy of the blob: the `reserved` slot of each sphere record carries 1/r for the product kernel
-  s->host_blob.assign((const uint8_t *)blob, (const uint8_t *)blob + bytes);
-  {
-    rt_sphere *pob = (rt_sphere *)(s->host_blob.data() + hd->objects_offset);
-    for (uint32_t i = 0; i < hd->n_objects; i++) pob[i].reserved = 1.0 / sqrt(pob[i].r2);
-  }
-  camera_decisions(s);
+  // device copy of the records: the `reserved` slot of each sphere record carries 1/r for the product kernel
+  rt_sphere *pob = (rt_sphere *)(s->host_blob.data() + hd->objects_offset);
+  memcpy(pob, ob, (size_t)hd->n_objects * sizeof(rt_sphere));
+  for (uint32_t i = 0; i < hd->n_objects; i++) pob[i].reserved = 1.0 / sqrt(pob[i].r2);
   // Two orderings of the spheres.  A = the scene's own order (strict kernels, counting variant).  B = the enclosing sphere moved to
   // the end, so that the product kernel's loops run over [0, N-1) and never test it.
-  const uint32_t NO = hd->n_objects, NL = hd->n_lights;
-  s->has_b = s->enclosing != ~0u;
-  const bool has_b = s->has_b;
-  const int n_ord = has_b ? 2 : 1;
-  const rt_sphere *pob_a = (const rt_sphere *)(s->host_blob.data() + hd->objects_offset);
   s->host_objects_b.clear();
-  if (has_b) {
-    for (uint32_t i = 0; i < NO; i++) if (i != s->enclosing) s->host_objects_b.push_back(pob_a[i]);
-    s->host_objects_b.push_back(pob_a[s->enclosing]);
+  if (s->enclosing != ~0u) {
+    for (uint32_t i = 0; i < hd->n_objects; i++) if (i != s->enclosing) s->host_objects_b.push_back(pob[i]);
+    s->host_objects_b.push_back(pob[s->enclosing]);
   }
-  const uint32_t n_loop_b = has_b ? NO - 1 : NO;       // spheres in the product kernel's loops
-  static const uint32_t sgrid_min = RT_TEST_ENV("RT_SGRID_MIN") ? (uint32_t)atoi(RT_TEST_ENV("RT_SGRID_MIN")) : RT_SGRID_MIN_LOOP;     // A/B switches (test build)
-  static const uint32_t btable_min = RT_TEST_ENV("RT_BTABLE_MIN") ? (uint32_t)atoi(RT_TEST_ENV("RT_BTABLE_MIN")) : RT_BTABLE_MIN_LOOP;
-  const bool want_shadow_grid = n_loop_b > sgrid_min && NL > 0;
-  const bool want_bounce_table = n_loop_b > btable_min && hd->segs > 1;      // rays bounce at all only from depth 2 on
-  // few spheres: the cull rectangles ride in the LDS image; scenes that get a shadow grid or a bounce table run the many-sphere
-  // kernel variant, which fetches them per lane (rt_kernel.hip: 64 spheres + the fold state then fit 32 KB of LDS, five workgroups
-  // per CU instead of four)
-  s->cull_in_lds = !(want_shadow_grid || want_bounce_table);
-  s->lds_image_bytes = (size_t)NO * (sizeof(rt_mtl) + (s->cull_in_lds ? sizeof(rt_geom) : 0u)) + sizeof descs;
-  s->lds_bytes = (unsigned)s->lds_image_bytes;
-  std::vector<uint64_t> sg, bt;
-  if (want_shadow_grid) sg = build_shadow_grid(has_b ? s->host_objects_b.data() : pob_a, n_loop_b, NL, s->lights);
-  if (want_bounce_table) bt = build_bounce_table(has_b ? s->host_objects_b.data() : pob_a, NO, n_loop_b);
-  // ---- the arena's layout (every part 256-byte aligned) ----
-  auto up = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
-  size_t at = 0;
-  const size_t off_blob = at; at = up(at + bytes);
-  const size_t off_tex = at; at = up(at + sizeof descs);
+}
+
+// The host-written part of an object block (rt_scene_dev: obj_host_bytes of host memory at `dst`): the records, the geometry tables,
+// ordering B, the LDS images of many-sphere scenes and the shadow grids' headers.  The masks and the bounce table behind it are built
+// from these (rt_scene_upload: rt_tables.cpp on the host; rt_scene_set_objects: rt_objects_gpu.hip).
+void fill_object_block(const rt_scene_dev *s, uint8_t *dst) {
+  const rt_scene_header *hd = &s->hd;
+  const uint32_t NO = hd->n_objects, NL = hd->n_lights;
+  const int n_ord = s->has_b ? 2 : 1;
+  memset(dst, 0, s->obj_host_bytes);
+  const rt_sphere *pob_a = (const rt_sphere *)(s->host_blob.data() + hd->objects_offset);
+  memcpy(dst + s->o_objs, pob_a, (size_t)NO * sizeof(rt_sphere));
   const size_t geom_per_order = (size_t)NO * (1 + NL);                 // [plain N | anchored at light k: NL x N]
-  const size_t off_geom = at; at = up(at + (geom_per_order * n_ord + 1) * sizeof(rt_geom));   // + one record of padding: the kernel's scans fetch a light's first two records at once, also when it has one
-  const size_t off_objs_b = at; at = up(at + (has_b ? NO * sizeof(rt_sphere) : 0));
-  const size_t off_img = at; at = up(at + (s->cull_in_lds ? 0 : s->lds_image_bytes * n_ord + 4096u));   // the many-sphere kernel reads whole 4 KB pieces (rt_kernel.hip staging)
-  const size_t off_sg = at; at = up(at + sg.size() * sizeof(uint64_t));
-  const size_t off_bt = at; at = up(at + bt.size() * sizeof(uint64_t));
-  s->cam_lds_offset = up((size_t)n_ord * 2u * NO * sizeof(rt_geom));
-  s->cam_bytes_used = s->cam_lds_offset + (s->cull_in_lds ? s->lds_image_bytes * n_ord : 0);
-  s->cam_bytes = s->cam_bytes_used + (s->cull_in_lds ? 4096u : 0);
-  const size_t off_cam0 = at; at = up(at + s->cam_bytes);
-  const size_t off_cam1 = at; at = up(at + s->cam_bytes);
-  s->arena_bytes = at;
-  std::vector<uint8_t> host(at, 0);
-  memcpy(host.data() + off_blob, s->host_blob.data(), bytes);
-  memcpy(host.data() + off_tex, descs, sizeof descs);
   auto anchored = [&](const rt_sphere &o, const double a[3]) {
     const double lx = o.origin[0] - a[0], ly = o.origin[1] - a[1], lz = o.origin[2] - a[2];
     return rt_geom{lx, ly, lz, (lx * lx + ly * ly + lz * lz) - o.r2};
   };
   for (int ord = 0; ord < n_ord; ord++) {
     const rt_sphere *src = ord ? s->host_objects_b.data() : pob_a;
-    rt_geom *dst = (rt_geom *)(host.data() + off_geom) + ord * geom_per_order;
+    rt_geom *g = (rt_geom *)(dst + s->o_geom) + ord * geom_per_order;
     for (uint32_t i = 0; i < NO; i++) {
-      dst[i] = rt_geom{src[i].origin[0], src[i].origin[1], src[i].origin[2], src[i].r2};
-      for (uint32_t k = 0; k < NL; k++) dst[(size_t)NO * (1 + k) + i] = anchored(src[i], s->lights[k]);
+      g[i] = rt_geom{src[i].origin[0], src[i].origin[1], src[i].origin[2], src[i].r2};
+      for (uint32_t k = 0; k < NL; k++) g[(size_t)NO * (1 + k) + i] = anchored(src[i], s->lights[k]);
     }
   }
-  ((rt_geom *)(host.data() + off_geom))[geom_per_order * n_ord] = rt_geom{0.0, 0.0, 0.0, -1.0};
-  if (has_b) memcpy(host.data() + off_objs_b, s->host_objects_b.data(), NO * sizeof(rt_sphere));
-  if (!sg.empty()) memcpy(host.data() + off_sg, sg.data(), sg.size() * sizeof(uint64_t));
-  if (!bt.empty()) memcpy(host.data() + off_bt, bt.data(), bt.size() * sizeof(uint64_t));
-  // the LDS images' camera-independent part: [materials | texture descriptors] (fill_camera_block below writes them again, with
-  // their cull rectangles, when they live in the camera block)
-  if (!s->cull_in_lds) for (int ord = 0; ord < n_ord; ord++) fill_lds_image(s, host.data() + off_img + ord * s->lds_image_bytes, ord);
+  ((rt_geom *)(dst + s->o_geom))[geom_per_order * n_ord] = rt_geom{0.0, 0.0, 0.0, -1.0};   // one record of padding: the kernel's scans fetch a light's first two records at once, also when it has one
+  if (s->has_b) memcpy(dst + s->o_objs_b, s->host_objects_b.data(), (size_t)NO * sizeof(rt_sphere));
+  // the LDS images' camera-independent part: [materials | texture descriptors] (fill_camera_block writes them, with their cull
+  // rectangles, when they live in the camera block)
+  if (!s->cull_in_lds) for (int ord = 0; ord < n_ord; ord++) fill_lds_image(s, dst + s->o_img + ord * s->lds_image_bytes, ord);
+  if (s->has_sg) {
+    const rt_sphere *loop = s->has_b ? s->host_objects_b.data() : pob_a;
+    for (uint32_t k = 0; k < NL; k++) shadow_grid_frame(loop, s->has_b ? NO - 1u : NO, s->lights[k], (double *)(dst + s->o_sg) + 16u * k);
+  }
+}
+
+// a staging slot of `bytes` (<= stage_bytes), free to be written: its previous copy has been read
+uint8_t *acquire_stage(rt_scene_dev *s, rt_scene_dev::stage_slot **slot) {
+  rt_scene_dev::stage_slot &g = s->stages[s->stage_next++ & 15u];
+  if (g.used) (void)hipEventSynchronize(g.done);
+  g.used = true;
+  *slot = &g;
+  return g.h;
+}
+
+std::atomic<int> g_uploads{0};       // rt_scene_upload calls (test build: rt_test_upload_count)
+constexpr size_t up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
+}  // namespace
+
+#ifdef RT_TESTING
+extern "C" int rt_test_upload_count(void) { return g_uploads.load(); }
+#endif
+
+extern "C" int rt_scene_upload(int device, const void *blob, size_t bytes, rt_scene_dev **out) {
+  if (!out) return fail(RT_ERR_INVALID, "out handle is NULL");
+  *out = nullptr;
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  if ((rc = ensure_device(device))) return rc;
+  g_uploads++;
+  const rt_scene_header *hd = (const rt_scene_header *)blob;
+  rt_scene_dev *s = new rt_scene_dev();
+  s->device = device; s->hd = *hd; s->d_blob = nullptr; s->d_texdesc = nullptr; s->d_cones = nullptr;
+  s->d_cam_buf[0] = s->d_cam_buf[1] = nullptr; s->d_obj_buf[0] = s->d_obj_buf[1] = nullptr;
+  const uint8_t *base = (const uint8_t *)blob;
+  const rt_sphere *ob = (const rt_sphere *)(base + hd->objects_offset);
+  memset(s->lights, 0, sizeof s->lights);
+  if (hd->n_lights) memcpy(s->lights, base + hd->lights_offset, hd->n_lights * 24u);
+  rt_texture_desc (&descs)[RT_MAX_TEXTURES] = s->descs;
+  memset(descs, 0, sizeof descs);
+  if (hd->n_textures) memcpy(descs, base + hd->textures_offset, hd->n_textures * sizeof(rt_texture_desc));
+  s->enclosing = enclosing_sphere(hd, ob, s->lights);     // (rt_tables.cpp)
+  s->host_objects.assign(ob, ob + hd->n_objects);
+  s->host_blob.assign((const uint8_t *)blob, (const uint8_t *)blob + bytes);
+  object_decisions(s);
+  camera_decisions(s);
+  const uint32_t NO = hd->n_objects, NL = hd->n_lights;
+  s->has_b = s->enclosing != ~0u;
+  const bool has_b = s->has_b;
+  const int n_ord = has_b ? 2 : 1;
+  const rt_sphere *pob_a = (const rt_sphere *)(s->host_blob.data() + hd->objects_offset);
+  const uint32_t n_loop_b = has_b ? NO - 1 : NO;       // spheres in the product kernel's loops
+  static const uint32_t sgrid_min = RT_TEST_ENV("RT_SGRID_MIN") ? (uint32_t)atoi(RT_TEST_ENV("RT_SGRID_MIN")) : RT_SGRID_MIN_LOOP;     // A/B switches (test build)
+  static const uint32_t btable_min = RT_TEST_ENV("RT_BTABLE_MIN") ? (uint32_t)atoi(RT_TEST_ENV("RT_BTABLE_MIN")) : RT_BTABLE_MIN_LOOP;
+  s->has_sg = n_loop_b > sgrid_min && NL > 0;
+  s->has_bt = n_loop_b > btable_min && hd->segs > 1;      // rays bounce at all only from depth 2 on
+  // few spheres: the cull rectangles ride in the LDS image; scenes that get a shadow grid or a bounce table run the many-sphere
+  // kernel variant, which fetches them per lane (rt_kernel.hip: 64 spheres + the fold state then fit 32 KB of LDS, five workgroups
+  // per CU instead of four)
+  s->cull_in_lds = !(s->has_sg || s->has_bt);
+  s->lds_image_bytes = (size_t)NO * (sizeof(rt_mtl) + (s->cull_in_lds ? sizeof(rt_geom) : 0u)) + sizeof descs;
+  s->lds_bytes = (unsigned)s->lds_image_bytes;
+  const size_t sg_words = s->has_sg ? (size_t)NL * 16u + (size_t)NL * (RT_SGRID * RT_SGRID + 1u) * ((n_loop_b + 63u) / 64u) : 0u;
+  const size_t bt_words = s->has_bt ? (size_t)NO * RT_BCELLS * ((n_loop_b + 63u) / 64u) : 0u;
+  // ---- an object block's layout (every part 256-byte aligned) ----
+  size_t ot = 0;
+  s->o_objs = ot; ot = up256(ot + (size_t)NO * sizeof(rt_sphere));
+  s->o_geom = ot; ot = up256(ot + ((size_t)NO * (1 + NL) * n_ord + 1) * sizeof(rt_geom));
+  s->o_objs_b = ot; ot = up256(ot + (has_b ? NO * sizeof(rt_sphere) : 0));
+  s->o_img = ot; ot = up256(ot + (s->cull_in_lds ? 0 : s->lds_image_bytes * n_ord + 4096u));   // the many-sphere kernel reads whole 4 KB pieces (rt_kernel.hip staging)
+  s->o_sg = ot; ot = up256(ot + sg_words * sizeof(uint64_t));
+  s->obj_host_bytes = s->o_sg + (s->has_sg ? (size_t)NL * 16u * sizeof(double) : 0u);
+  s->o_bt = ot; ot = up256(ot + bt_words * sizeof(uint64_t));
+  s->obj_bytes = ot;
+  s->sg_bytes = sg_words * sizeof(uint64_t); s->bt_bytes = bt_words * sizeof(uint64_t);
+  // ---- the arena's layout ----
+  size_t at = 0;
+  const size_t off_blob = at; at = up256(at + bytes);
+  const size_t off_tex = at; at = up256(at + sizeof descs);
+  const size_t off_cones = at; at = up256(at + (s->has_bt ? 5u * RT_BCELLS * sizeof(double) : 0u));
+  const size_t off_obj0 = at; at = up256(at + s->obj_bytes);
+  const size_t off_obj1 = at; at = up256(at + s->obj_bytes);
+  s->cam_lds_offset = up256((size_t)n_ord * 2u * NO * sizeof(rt_geom));
+  s->cam_bytes_used = s->cam_lds_offset + (s->cull_in_lds ? s->lds_image_bytes * n_ord : 0);
+  s->cam_bytes = s->cam_bytes_used + (s->cull_in_lds ? 4096u : 0);
+  const size_t off_cam0 = at; at = up256(at + s->cam_bytes);
+  const size_t off_cam1 = at; at = up256(at + s->cam_bytes);
+  s->arena_bytes = at;
+  std::vector<uint8_t> host(at, 0);
+  memcpy(host.data() + off_blob, s->host_blob.data(), bytes);
+  memcpy(host.data() + off_tex, descs, sizeof descs);
+  if (s->has_bt) { const std::vector<double> cones = bounce_cell_cones(); memcpy(host.data() + off_cones, cones.data(), cones.size() * sizeof(double)); }
+  fill_object_block(s, host.data() + off_obj0);
+  if (s->has_sg) {
+    const std::vector<uint64_t> sg = build_shadow_grid(has_b ? s->host_objects_b.data() : pob_a, n_loop_b, NL, s->lights);
+    memcpy(host.data() + off_obj0 + s->o_sg, sg.data(), sg.size() * sizeof(uint64_t));
+  }
+  if (s->has_bt) {
+    const std::vector<uint64_t> bt = build_bounce_table(has_b ? s->host_objects_b.data() : pob_a, NO, n_loop_b);
+    memcpy(host.data() + off_obj0 + s->o_bt, bt.data(), bt.size() * sizeof(uint64_t));
+  }
+  memcpy(host.data() + off_obj1, host.data() + off_obj0, s->obj_bytes);
   fill_camera_block(s, host.data() + off_cam0);
   memcpy(host.data() + off_cam1, host.data() + off_cam0, s->cam_bytes_used);
   // ---- one allocation, one copy ----
   hipError_t e = hipMalloc((void **)&s->arena, s->arena_bytes);
   if (e == hipSuccess) e = hipMemcpy(s->arena, host.data(), s->arena_bytes, hipMemcpyHostToDevice);
-  // pinned staging for what follows a camera move
+  // pinned staging for what follows a camera move (the camera block) or an object move (the camera block, then the host-written
+  // part of the object block)
   {
     const size_t table_dyn = 512u + (size_t)NO * (sizeof(rt_ball) + sizeof(rt_cost_rect));      // a launch table's parameters, cone-test spheres and cost rectangles
-    s->stage_bytes = up(s->cam_bytes > table_dyn ? s->cam_bytes : table_dyn);
+    const size_t move = up256(s->cam_bytes) + s->obj_host_bytes;
+    s->stage_bytes = up256(move > table_dyn ? move : table_dyn);
     if (e == hipSuccess) e = hipHostMalloc((void **)&s->stage_pool, s->stage_bytes * 16u, hipHostMallocDefault);
     for (size_t i = 0; i < 16u; i++) {
       s->stages[i].h = s->stage_pool ? s->stage_pool + i * s->stage_bytes : nullptr;
@@ -642,12 +716,9 @@ extern "C" int rt_scene_upload(int device, const void *blob, size_t bytes, rt_sc
   }
   s->d_blob = s->arena + off_blob;
   s->d_texdesc = (rt_texture_desc *)(s->arena + off_tex);
-  s->d_geom = (rt_geom *)(s->arena + off_geom);
-  s->d_objects_b = has_b ? (rt_sphere *)(s->arena + off_objs_b) : nullptr;
-  s->d_shadow_grid = sg.empty() ? nullptr : (uint64_t *)(s->arena + off_sg);
-  s->d_bounce_table = bt.empty() ? nullptr : (uint64_t *)(s->arena + off_bt);
+  s->d_cones = s->has_bt ? (double *)(s->arena + off_cones) : nullptr;
+  s->d_obj_buf[0] = s->arena + off_obj0; s->d_obj_buf[1] = s->arena + off_obj1;
   s->d_cam_buf[0] = s->arena + off_cam0; s->d_cam_buf[1] = s->arena + off_cam1;
-  s->d_lds_image = s->cull_in_lds ? nullptr : s->arena + off_img;
   *out = s;
   return RT_OK;
 }
@@ -680,47 +751,61 @@ bool build_table(rt_scene_dev *s, int found, const rt_tiles *tiles, uint32_t til
                  rt_scene_dev::stage_slot *cam);
 }  // namespace
 
-extern "C" int rt_scene_set_camera(rt_scene_dev *s, const double origin[3], const double axis_x[3], const double axis_y[3], const double axis_z[3], void *hip_stream) {
-  if (!s || !origin || !axis_x || !axis_y || !axis_z) return fail(RT_ERR_INVALID, "rt_scene_set_camera: NULL argument");
-  int rc = ensure_device(s->device);
-  if (rc) return rc;
-  (void)hip_stream;                                  // (kept in the signature: the copy and the rebuilds run on the scene's own side stream)
-  std::lock_guard<std::mutex> lk(s->launch_mu);
-  rt_scene_header nh = s->hd;
-  memcpy(nh.cam_origin, origin, 24); memcpy(nh.cam_axis_x, axis_x, 24); memcpy(nh.cam_axis_y, axis_y, 24); memcpy(nh.cam_axis_z, axis_z, 24);
-  if (memcmp(&nh, &s->hd, sizeof nh) == 0) return RT_OK;
-  // the two orderings of the scene's tables are built around the sphere that encloses everything INCLUDING the camera
-  if (enclosing_sphere(&nh, s->host_objects.data(), s->lights) != s->enclosing)
-    return fail(RT_ERR_UNSUPPORTED, "rt_scene_set_camera: the camera crossed the enclosing sphere (the scene's tables are laid out around it): upload the scene again");
-  if (!s->side) {
-    // HIGH priority: its few hundred waves are launched INTO a chip the previous frame's trace keeps full; at normal priority the
-    // table build's workgroups waited for slots and took 77 us instead of 20 (profiles/r04_ab_log.md)
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    HIP_TRY(hipStreamCreateWithPriority(&s->side, hipStreamNonBlocking, prio_hi));
-    for (int b = 0; b < 2; b++) { HIP_TRY(hipEventCreateWithFlags(&s->old_done[b], hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s->prep_done[b], hipEventDisableTiming)); }
-  }
+namespace {
+// the scene's side stream (HIGH priority: its few hundred waves are launched INTO a chip the previous frame's trace keeps full; at
+// normal priority the table build's workgroups waited for slots and took 77 us instead of 20, profiles/r04_ab_log.md) and its events
+int ensure_side(rt_scene_dev *s) {
+  if (s->side) return RT_OK;
+  int prio_lo = 0, prio_hi = 0;
+  (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+  HIP_TRY(hipStreamCreateWithPriority(&s->side, hipStreamNonBlocking, prio_hi));
+  for (int b = 0; b < 2; b++) { HIP_TRY(hipEventCreateWithFlags(&s->old_done[b], hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s->prep_done[b], hipEventDisableTiming)); }
+  return RT_OK;
+}
+
+// The host state of the scene has just changed - its camera (rt_scene_set_camera) or its spheres (rt_scene_set_objects,
+// `objects_moved`), host decisions included - and generation old_gen + 1 begins: on the side stream, behind the launches that read
+// its blocks last (generation old_gen - 1), the camera block is copied and the object block brought up to date (a move: the staged
+// host part, then the masks and the bounce table on the GPU; a camera move after an object move: a copy of the other block), and
+// the launch tables the previous generation's frames used are rebuilt.  Everything keyed to the generation - launch tables, mark
+// counts, camera_uses - is stale from here on.  launch_mu held.
+int next_generation(rt_scene_dev *s, uint64_t old_gen, bool objects_moved) {
   // launches of this scene in flight on SEVERAL caller streams: no single event covers them (rare: drain the device)
   if (s->any_launch && s->several_streams) { HIP_TRY(hipDeviceSynchronize()); s->any_launch = false; s->several_streams = false; s->launched_since_move = false; s->old_done_valid[0] = s->old_done_valid[1] = false; }
-  const uint64_t old_gen = s->cam_gen;
-  s->hd = nh;
-  memcpy(s->host_blob.data(), &nh, sizeof nh);
-  camera_decisions(s);
   const uint64_t G = ++s->cam_gen;
   const uint32_t b = (uint32_t)(G & 1u);
   s->renders_with_camera = 0;
-  // every launch so far (generations < G) precedes this event on the caller's stream; the move to G + 1 will write block / tables
+  // every launch so far (generations < G) precedes this event on the caller's stream; the move to G + 1 will write blocks / tables
   // (G + 1) & 1 - the ones generation G - 1 used - only behind it.  (No launch since the last move: the older record still covers them.)
   if (s->launched_since_move && s->any_launch) { HIP_TRY(hipEventRecord(s->old_done[(G - 1u) & 1u], s->last_stream)); s->old_done_valid[(G - 1u) & 1u] = true; }
   s->launched_since_move = false;
-  // block and tables b were last read by generation G - 2
+  // blocks and tables b were last read by generation G - 2
   if (s->old_done_valid[b]) HIP_TRY(hipStreamWaitEvent(s->side, s->old_done[b], 0));
   rt_scene_dev::stage_slot *slot = nullptr;
   uint8_t *st = acquire_stage(s, &slot);
   fill_camera_block(s, st);
-  // the tables the previous camera's frames used are rebuilt now, on the side stream, beside those frames' launches: the next render
-  // of such a frame finds its table (up to four; others are built by the launch that needs them, on its stream).  Many-sphere scenes:
-  // the first frame from a camera takes the table without shadow masks (rt_render_batch: masks_pay).
+  if (objects_moved) s->obj_version++;
+  if (s->slot_version[b] != s->obj_version) {
+    uint8_t *blk = s->d_obj_buf[b];
+    hipError_t e = hipSuccess;
+    if (objects_moved) {
+      uint8_t *so = st + up256(s->cam_bytes);
+      fill_object_block(s, so);
+      const uint32_t NO = s->hd.n_objects, n_loop = s->has_b ? NO - 1u : NO;
+      const rt_sphere *loop = (const rt_sphere *)(blk + (s->has_b ? s->o_objs_b : s->o_objs));
+      e = (hipError_t)rt_launch_objects_copy(blk, so, s->obj_host_bytes, s->side);
+      if (e == hipSuccess && s->has_sg)
+        e = (hipError_t)rt_launch_sgrid_build(loop, n_loop, s->hd.n_lights, (const double *)((const uint8_t *)s->d_blob + s->hd.lights_offset), (uint64_t *)(blk + s->o_sg), s->side);
+      if (e == hipSuccess && s->has_bt) e = (hipError_t)rt_launch_bounce_build(loop, NO, n_loop, s->d_cones, (uint64_t *)(blk + s->o_bt), s->side);
+    } else {
+      e = hipMemcpyAsync(blk, s->d_obj_buf[b ^ 1u], s->obj_bytes, hipMemcpyDeviceToDevice, s->side);
+    }
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "object block: %s", hipGetErrorString(e));
+    s->slot_version[b] = s->obj_version;
+  }
+  // the tables the previous generation's frames used are rebuilt now, on the side stream, beside those frames' launches: the next
+  // render of such a frame finds its table (up to four; others are built by the launch that needs them, on its stream).  Many-sphere
+  // scenes: the first frame from a camera takes the table without shadow masks (rt_render_batch: masks_pay).
   const uint32_t n_loop = s->hd.n_objects - (s->enclosing != ~0u ? 1u : 0u);
   int built = 0;
   bool cam_sent = false;
@@ -746,6 +831,59 @@ extern "C" int rt_scene_set_camera(rt_scene_dev *s, const double origin[3], cons
   s->prep_valid[b] = true;
   s->prep_waited.clear();
   return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_scene_set_camera(rt_scene_dev *s, const double origin[3], const double axis_x[3], const double axis_y[3], const double axis_z[3], void *hip_stream) {
+  if (!s || !origin || !axis_x || !axis_y || !axis_z) return fail(RT_ERR_INVALID, "rt_scene_set_camera: NULL argument");
+  int rc = ensure_device(s->device);
+  if (rc) return rc;
+  (void)hip_stream;                                  // (kept in the signature: the copy and the rebuilds run on the scene's own side stream)
+  std::lock_guard<std::mutex> lk(s->launch_mu);
+  rt_scene_header nh = s->hd;
+  memcpy(nh.cam_origin, origin, 24); memcpy(nh.cam_axis_x, axis_x, 24); memcpy(nh.cam_axis_y, axis_y, 24); memcpy(nh.cam_axis_z, axis_z, 24);
+  if (memcmp(&nh, &s->hd, sizeof nh) == 0) return RT_OK;
+  // the two orderings of the scene's tables are built around the sphere that encloses everything INCLUDING the camera
+  if (enclosing_sphere(&nh, s->host_objects.data(), s->lights) != s->enclosing)
+    return fail(RT_ERR_UNSUPPORTED, "rt_scene_set_camera: the camera crossed the enclosing sphere (the scene's tables are laid out around it): upload the scene again");
+  if ((rc = ensure_side(s))) return rc;
+  const uint64_t old_gen = s->cam_gen;
+  s->hd = nh;
+  memcpy(s->host_blob.data(), &nh, sizeof nh);
+  camera_decisions(s);
+  return next_generation(s, old_gen, false);
+}
+
+// The spheres of a resident scene move or change their material (the reference's objects are plain arrays a page may change between
+// two redraws, main.js:180-201).  What depends on them - the object block, the camera block, the launch tables, the host decisions -
+// follows through the same generation pipeline as a camera move (next_generation): frames already enqueued keep the old spheres, the
+// next launch of the scene on any stream waits (by event) for the new ones.
+extern "C" int rt_scene_set_objects(rt_scene_dev *s, uint32_t first, uint32_t count, const rt_sphere *records, void *hip_stream) {
+  if (!s) return fail(RT_ERR_INVALID, "rt_scene_set_objects: NULL scene");
+  (void)hip_stream;                                  // (as rt_scene_set_camera: the copy and the builds run on the scene's side stream)
+  const uint32_t NO = s->hd.n_objects;
+  if (first > NO || count > NO - first) return fail(RT_ERR_INVALID, "rt_scene_set_objects: spheres [%u, %u + %u) outside [0, %u)", first, first, count, NO);
+  if (count && !records) return fail(RT_ERR_INVALID, "rt_scene_set_objects: NULL records");
+  for (uint32_t i = 0; i < count; i++)
+    if (check_sphere(records[i], first + i, s->hd.n_textures) != RT_OK) { const std::string why = g_err; return fail(RT_ERR_INVALID, "rt_scene_set_objects: %s", why.c_str()); }
+  int rc = ensure_device(s->device);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(s->launch_mu);
+  std::vector<rt_sphere> next(s->host_objects);
+  for (uint32_t i = 0; i < count; i++) {
+    rt_sphere r = records[i];
+    r.reserved = next[first + i].reserved;           // (the device copy's 1/r: derived, whatever the caller's record holds)
+    next[first + i] = r;
+  }
+  if (memcmp(next.data(), s->host_objects.data(), (size_t)NO * sizeof(rt_sphere)) == 0) return RT_OK;
+  if (enclosing_sphere(&s->hd, next.data(), s->lights) != s->enclosing)
+    return fail(RT_ERR_UNSUPPORTED, "rt_scene_set_objects: the edit changes the sphere that encloses everything (the scene's tables are laid out around it): upload the scene again");
+  if ((rc = ensure_side(s))) return rc;
+  const uint64_t old_gen = s->cam_gen;
+  s->host_objects.swap(next);
+  object_decisions(s);
+  camera_decisions(s);
+  return next_generation(s, old_gen, true);
 }
 
 // The stars seed (include/rt_hip.h: RT_SAMPLER_STARS) is host state: render_batch_impl copies it into each launch record, so frames
@@ -972,6 +1110,35 @@ int dispatch_order(rt_scene_dev *s, uint32_t w, uint32_t h, uint32_t ss, const r
 }  // namespace
 
 #ifdef RT_TESTING
+// Test build only: a sphere-dependent region of the scene's CURRENT generation, read back (the device is drained first).  part: 0 the
+// records in blob order (1/r in `reserved`), 1 the geometry tables, 2 ordering B, 3 the LDS images, 4 the shadow grids, 5 the bounce
+// table, 6 the camera block.  Returns the region's size in bytes (0: the scene has no such region), copied to `out` when `bytes`
+// holds it; < 0: an RT_ERR_* code.
+extern "C" long long rt_test_scene_state(rt_scene_dev *s, int part, void *out, size_t bytes) {
+  if (!s) return fail(RT_ERR_INVALID, "rt_test_scene_state: NULL scene");
+  if (int rc = ensure_device(s->device)) return rc;
+  std::lock_guard<std::mutex> lk(s->launch_mu);
+  const uint32_t NO = s->hd.n_objects, NL = s->hd.n_lights;
+  const int n_ord = s->has_b ? 2 : 1;
+  const uint8_t *src = nullptr;
+  size_t n = 0;
+  switch (part) {
+    case 0: src = obj_block(s) + s->o_objs; n = (size_t)NO * sizeof(rt_sphere); break;
+    case 1: src = obj_block(s) + s->o_geom; n = ((size_t)NO * (1 + NL) * n_ord + 1) * sizeof(rt_geom); break;
+    case 2: src = obj_block(s) + s->o_objs_b; n = s->has_b ? (size_t)NO * sizeof(rt_sphere) : 0u; break;
+    case 3: src = lds_image_of(s); n = s->lds_image_bytes * n_ord; break;
+    case 4: src = obj_block(s) + s->o_sg; n = s->sg_bytes; break;
+    case 5: src = obj_block(s) + s->o_bt; n = s->bt_bytes; break;
+    case 6: src = cam_block(s); n = s->cam_bytes_used; break;
+    default: return fail(RT_ERR_INVALID, "rt_test_scene_state: part %d not in 0..6", part);
+  }
+  if (out && n && bytes >= n) {
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, src, n, hipMemcpyDeviceToHost));
+  }
+  return (long long)n;
+}
+
 // Test build only: the launch table as the library builds it ON THE GPU for `tiles` of the w x h frame of a resident scene (its
 // current camera), read back: same arguments and layout as the host-logic probe rt_scene_launch_table below, whose table (the host
 // build of the same rt_block.h) it must equal word for word.
@@ -1205,17 +1372,18 @@ int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *t
   // order so that they stay literal / count what the reference counts
   auto bind_kernel = [&](rt_launch &K, bool strict) {
     const bool plain = strict || count;
-    const bool order_b = s->d_objects_b && !plain;
-    const rt_geom *gt = s->d_geom + (order_b ? (size_t)hd.n_objects * (1 + hd.n_lights) : 0);      // [plain N | anchored at light k: NL x N]
+    const bool order_b = s->has_b && !plain;
+    const uint8_t *ob = obj_block(s);                 // this generation's spheres
+    const rt_geom *gt = (const rt_geom *)(ob + s->o_geom) + (order_b ? (size_t)hd.n_objects * (1 + hd.n_lights) : 0);      // [plain N | anchored at light k: NL x N]
     const rt_geom *gc = (const rt_geom *)cam_block(s) + (order_b ? 2 * (size_t)hd.n_objects : 0);     // this camera's block: [anchored at the camera N | cull rectangles N]
-    K.objects = order_b ? s->d_objects_b : (const rt_sphere *)(db + hd.objects_offset);
+    K.objects = (const rt_sphere *)(ob + (order_b ? s->o_objs_b : s->o_objs));
     K.geom = gt;
     K.geom_cam = gc;
     K.cull = gc + hd.n_objects;
     K.geom_light = gt + hd.n_objects;
     K.lds_image = lds_image_of(s) + (order_b ? s->lds_image_bytes : 0);
-    K.shadow_grid = (!plain && !no_grid) ? s->d_shadow_grid : nullptr;
-    K.bounce_table = (!plain && !no_bounce) ? s->d_bounce_table : nullptr;
+    K.shadow_grid = (!plain && !no_grid && s->has_sg) ? ob + s->o_sg : nullptr;
+    K.bounce_table = (!plain && !no_bounce && s->has_bt) ? ob + s->o_bt : nullptr;
     K.n_loop = order_b ? hd.n_objects - 1 : hd.n_objects;
     K.enclosing = order_b ? hd.n_objects - 1 : ~0u;
     K.enclosing_flat = (order_b && s->enclosing_flat) ? 1u : 0u;
@@ -1815,18 +1983,27 @@ int ensure_rccl(int ndev) {
 int scene_for(int device, const void *blob, size_t bytes, rt_scene_dev **out) {
   device_state &D = G.dev[device];
   if (D.cached_scene && D.cached_blob.size() == bytes && memcmp(D.cached_blob.data(), blob, bytes) == 0) { *out = D.cached_scene; return RT_OK; }
-  // the same scene from another camera and / or with another stars seed (an animation: lookAt per frame, main.js:92-100, and a new sky
-  // per redraw, main.js:135-139, 180): the resident scene moves its camera and takes the seed
+  // the same scene from another camera, with another stars seed and / or with moved or restyled spheres (an animation: lookAt per
+  // frame, main.js:92-100, a new sky per redraw, main.js:135-139, 180, objects a page changes between redraws): the resident scene
+  // takes the spheres of the smallest range that covers the differences, then the camera, then the seed
   if (D.cached_scene && D.cached_blob.size() == bytes) {
     const size_t c0 = offsetof(rt_scene_header, cam_origin), c1 = c0 + 12 * sizeof(double);
     const size_t s0 = offsetof(rt_scene_header, stars_seed), s1 = s0 + sizeof(uint32_t);
     static_assert(c1 <= s0, "the camera lies in front of the stars seed in rt_scene_header");
     const uint8_t *a = D.cached_blob.data(), *b = (const uint8_t *)blob;
-    if (memcmp(a, b, c0) == 0 && memcmp(a + c1, b + c1, s0 - c1) == 0 && memcmp(a + s1, b + s1, bytes - s1) == 0) {
-      const rt_scene_header *nh = (const rt_scene_header *)blob;
-      if (rt_scene_set_camera(D.cached_scene, nh->cam_origin, nh->cam_axis_x, nh->cam_axis_y, nh->cam_axis_z, nullptr) == RT_OK &&
+    const rt_scene_header *nh = (const rt_scene_header *)blob;
+    const size_t o0 = nh->objects_offset, o1 = o0 + (size_t)nh->n_objects * sizeof(rt_sphere);
+    // the header's other fields equal (the object table's place and size included), then everything outside the object table
+    if (memcmp(a, b, c0) == 0 && memcmp(a + c1, b + c1, s0 - c1) == 0 && memcmp(a + s1, b + s1, sizeof(rt_scene_header) - s1) == 0 &&
+        memcmp(a + sizeof(rt_scene_header), b + sizeof(rt_scene_header), o0 - sizeof(rt_scene_header)) == 0 && memcmp(a + o1, b + o1, bytes - o1) == 0) {
+      const rt_sphere *na = (const rt_sphere *)(a + o0), *nb = (const rt_sphere *)(b + o0);
+      uint32_t first = nh->n_objects, last = 0;
+      for (uint32_t i = 0; i < nh->n_objects; i++)
+        if (memcmp(&na[i], &nb[i], sizeof(rt_sphere)) != 0) { if (first == nh->n_objects) first = i; last = i + 1; }
+      if ((first == nh->n_objects || rt_scene_set_objects(D.cached_scene, first, last - first, nb + first, nullptr) == RT_OK) &&
+          rt_scene_set_camera(D.cached_scene, nh->cam_origin, nh->cam_axis_x, nh->cam_axis_y, nh->cam_axis_z, nullptr) == RT_OK &&
           rt_scene_set_stars_seed(D.cached_scene, nh->stars_seed) == RT_OK) {
-        memcpy(D.cached_blob.data() + c0, b + c0, s1 - c0);      // (what lies between the two is equal)
+        memcpy(D.cached_blob.data(), b, bytes);
         *out = D.cached_scene;
         return RT_OK;
       }
@@ -1900,9 +2077,9 @@ extern "C" int rt_render_progressive(const void *blob, size_t bytes, uint32_t w,
 }
 
 // ------------------------------------------------------------------------------------ primary hits (rt_hits.hip)
-// What is under a sample: the hit kernels read the uploaded blob (camera-independent, never written after the upload) and take the
-// camera from the scene's host state at the call, so they need nothing of the camera pipeline (rt_scene_set_camera's blocks, tables
-// and events) and leave the colour path's launch bookkeeping alone.
+// What is under a sample: the hit kernels read the sphere records of the scene's current generation (its object block: an object move
+// writes the other one, rt_scene_set_objects) and take the camera from the scene's host state at the call.  So they come behind the
+// generation's preparation on the side stream, like a colour launch, and count as launches of the scene for the next move's events.
 namespace {
 int hits_frame_check(uint32_t w, uint32_t h, uint32_t k, const char *what) {
   if (w == 0 || h == 0 || w > 65536 || h > 65536) return fail(RT_ERR_INVALID, "%s: frame size %ux%u not in 1..65536", what, w, h);
@@ -1922,11 +2099,14 @@ int pick_points_check(uint32_t w, uint32_t h, uint32_t k, uint32_t n, const uint
 }
 
 // the launch record's scene part: blob-order spheres, the CURRENT camera, the projection of the k w x k h sample grid
-void hits_bind(rt_scene_dev *s, uint32_t w, uint32_t h, rt_hits_launch &L) {
+int hits_bind(rt_scene_dev *s, uint32_t w, uint32_t h, rt_hits_launch &L, hipStream_t stream) {
   memset(&L, 0, sizeof L);
   std::lock_guard<std::mutex> lk(s->launch_mu);
+  if (int rc = behind_the_camera(s, stream)) return rc;
+  if (s->any_launch && s->last_stream != stream) s->several_streams = true;
+  s->last_stream = stream; s->any_launch = true; s->launched_since_move = true;
   const rt_scene_header &hd = s->hd;
-  L.objects = (const rt_sphere *)((const uint8_t *)s->d_blob + hd.objects_offset);
+  L.objects = (const rt_sphere *)(obj_block(s) + s->o_objs);
   memcpy(L.cam, hd.cam_origin, 12 * sizeof(double));   // origin, axisX, axisY, axisZ are contiguous
   L.k = hd.supersample;
   L.sw = L.k * w; L.sh = L.k * h;
@@ -1935,6 +2115,7 @@ void hits_bind(rt_scene_dev *s, uint32_t w, uint32_t h, rt_hits_launch &L) {
   L.proj_w = (double)L.sw / 2.0; L.proj_h = (double)L.sh / 2.0; L.proj_d = L.proj_w / tan(projA / 2.0);
   L.epsilon = hd.epsilon;
   L.n_objects = hd.n_objects;
+  return RT_OK;
 }
 }  // namespace
 
@@ -1953,7 +2134,7 @@ extern "C" int rt_render_hits_device(rt_scene_dev *s, uint32_t w, uint32_t h, co
   hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : D.stream;
   const auto t_begin = std::chrono::steady_clock::now();
   rt_hits_launch L;
-  hits_bind(s, w, h, L);
+  if ((rc = hits_bind(s, w, h, L, stream))) return rc;
   L.id = b->id; L.depth = b->depth; L.normal = b->normal;
   L.tile_rows = tiles->tile_rows; L.tile_first = tiles->tile_first; L.tile_stride = tiles->tile_stride;
   L.band_rows = tiles->n_tiles * L.k * tiles->tile_rows;
@@ -1991,7 +2172,7 @@ extern "C" int rt_scene_pick(rt_scene_dev *s, uint32_t w, uint32_t h, uint32_t n
   if ((rc = ensure_device(s->device))) return rc;
   device_state &D = G.dev[s->device];
   rt_hits_launch L;
-  hits_bind(s, w, h, L);
+  if ((rc = hits_bind(s, w, h, L, D.stream))) return rc;
   L.n_points = n;
   struct device_mem { void *p = nullptr; ~device_mem() { if (p) (void)hipFree(p); } } mem;
   HIP_TRY(hipMalloc(&mem.p, (size_t)n * (sizeof(rt_hit) + 2u * sizeof(uint32_t))));

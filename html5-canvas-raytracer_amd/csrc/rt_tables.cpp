@@ -11,6 +11,7 @@
 
 #include <string.h>
 
+#include "rt_objects.h"
 #include "rt_tables.h"
 
 namespace rt_tables {
@@ -23,19 +24,7 @@ namespace rt_tables {
 // centre is within R of it:  (C0*s2 - C2*s0*xi)^2 <= R^2 (s2^2 + s0^2 xi^2),  a quadratic in xi whose root
 // interval bounds every pixel column whose LINE meets the sphere (a superset of the columns whose ray hits
 // it).  Same for rows with (C1, s1).  Unbounded or doubtful cases return the whole axis.
-static void axis_bounds(double c_axis, double c_z, double s_axis, double s_z, double r2, double *lo, double *hi) {
-  *lo = -INFINITY; *hi = INFINITY;
-  const double A = s_axis * s_axis * (c_z * c_z - r2);
-  const double B = -2.0 * c_axis * c_z * s_axis * s_z;
-  const double Cq = s_z * s_z * (c_axis * c_axis - r2);
-  const double disc = B * B - 4.0 * A * Cq;
-  if (!(A > 1e-12 * s_axis * s_axis * (c_z * c_z + r2)) || !(disc >= 0.0)) return;   // image unbounded along this axis (or degenerate)
-  const double sq = sqrt(disc);
-  const double x1 = (-B - sq) / (2.0 * A), x2 = (-B + sq) / (2.0 * A);
-  if (!(x1 <= x2) || !std::isfinite(x1) || !std::isfinite(x2)) return;
-  *lo = x1 - 1e-7 * (1.0 + fabs(x1));                 // margins far above rounding, far below a pixel (1/D >= 1.5e-5)
-  *hi = x2 + 1e-7 * (1.0 + fabs(x2));
-}
+// (rt_objects.h: rt_axis_bounds)
 
 rt_geom cull_rect(const rt_scene_header *hd, const rt_sphere &o) {
   rt_geom r = {-INFINITY, INFINITY, -INFINITY, INFINITY};          // {x_lo, x_hi, y_lo, y_hi}
@@ -44,8 +33,8 @@ rt_geom cull_rect(const rt_scene_header *hd, const rt_sphere &o) {
                        hd->cam_axis_x[2] + hd->cam_axis_y[2] + hd->cam_axis_z[2]};
   const double k = (c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) - o.r2;
   if (!(k > 1e-9 * o.r2) || !(o.r2 > 0.0)) return r;              // camera inside / on / near the sphere: no bound
-  axis_bounds(c[0], c[2], s[0], s[2], o.r2, &r.ox, &r.oy);
-  axis_bounds(c[1], c[2], s[1], s[2], o.r2, &r.oz, &r.r2);
+  rt_axis_bounds(c[0], c[2], s[0], s[2], o.r2, &r.ox, &r.oy);
+  rt_axis_bounds(c[1], c[2], s[1], s[2], o.r2, &r.oz, &r.r2);
   return r;
 }
 
@@ -70,65 +59,57 @@ uint32_t enclosing_sphere(const rt_scene_header *hd, const rt_sphere *ob, const 
 // 1/cell_h, pad[3]}, then per light (RT_SGRID*RT_SGRID + 1) cells of `words` uint64 each: bit j of a cell = sphere j
 // (loop order) may block a shadow ray whose hit point projects into that cell; the last cell holds every sphere and
 // serves hit points behind the light's frame plane.  Border cells stand for the half-lines beyond the grid.
+// The frame of light k (its header: the first 13 doubles), from the spheres in loop order.  The centroid is a sequential sum in loop
+// order: this stays on the host (rt_objects_gpu.hip fills the masks from it).
+void shadow_grid_frame(const rt_sphere *objs, uint32_t n_loop, const double Lp[3], double hk[16]) {
+  const uint32_t G = RT_SGRID;
+  // frame: z' looks from the light at the centroid of the sphere centres
+  double cz[3] = {0, 0, 0};
+  for (uint32_t j = 0; j < n_loop; j++) for (int c = 0; c < 3; c++) cz[c] += (objs[j].origin[c] - Lp[c]) / n_loop;
+  double len = sqrt(cz[0] * cz[0] + cz[1] * cz[1] + cz[2] * cz[2]);
+  double z[3] = {0, -1, 0};
+  if (len > 1e-9 && std::isfinite(len)) for (int c = 0; c < 3; c++) z[c] = cz[c] / len;
+  const double up[3] = {fabs(z[1]) < 0.9 ? 0.0 : 1.0, fabs(z[1]) < 0.9 ? 1.0 : 0.0, 0.0};
+  double x[3] = {up[1] * z[2] - up[2] * z[1], up[2] * z[0] - up[0] * z[2], up[0] * z[1] - up[1] * z[0]};
+  len = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+  for (int c = 0; c < 3; c++) x[c] /= len;
+  const double y[3] = {z[1] * x[2] - z[2] * x[1], z[2] * x[0] - z[0] * x[2], z[0] * x[1] - z[1] * x[0]};
+  memset(hk, 0, 16 * sizeof(double));
+  for (int c = 0; c < 3; c++) { hk[c] = x[c]; hk[3 + c] = y[c]; hk[6 + c] = z[c]; }
+  // the grid spans the spheres' rectangles in (x'/z', y'/z')
+  double gx0 = INFINITY, gx1 = -INFINITY, gy0 = INFINITY, gy1 = -INFINITY;
+  for (uint32_t j = 0; j < n_loop; j++) {
+    rt_geom q;
+    if (rt_shadow_rect(hk, Lp, objs[j].origin, objs[j].r2, &q)) continue;
+    if (std::isfinite(q.ox)) gx0 = fmin(gx0, q.ox);
+    if (std::isfinite(q.oy)) gx1 = fmax(gx1, q.oy);
+    if (std::isfinite(q.oz)) gy0 = fmin(gy0, q.oz);
+    if (std::isfinite(q.r2)) gy1 = fmax(gy1, q.r2);
+  }
+  if (!(gx0 < gx1)) { gx0 = -1.0; gx1 = 1.0; }
+  if (!(gy0 < gy1)) { gy0 = -1.0; gy1 = 1.0; }
+  gx0 = fmax(gx0, -8.0); gx1 = fmin(gx1, 8.0); gy0 = fmax(gy0, -8.0); gy1 = fmin(gy1, 8.0);
+  if (!(gx0 < gx1)) { gx0 = -8.0; gx1 = 8.0; }
+  if (!(gy0 < gy1)) { gy0 = -8.0; gy1 = 8.0; }
+  hk[9] = gx0; hk[10] = gy0; hk[11] = G / (gx1 - gx0); hk[12] = G / (gy1 - gy0);
+}
+
 std::vector<uint64_t> build_shadow_grid(const rt_sphere *objs, uint32_t n_loop, uint32_t n_lights, const double lights[][3]) {
   const uint32_t G = RT_SGRID, words = (n_loop + 63u) / 64u, cells = G * G + 1u;
   std::vector<uint64_t> buf((size_t)n_lights * 16u + (size_t)n_lights * cells * words, 0ull);
   double *hdr = (double *)buf.data();
   uint64_t *masks = buf.data() + (size_t)n_lights * 16u;
   for (uint32_t k = 0; k < n_lights; k++) {
-    const double *Lp = lights[k];
-    // frame: z' looks from the light at the centroid of the sphere centres
-    double cz[3] = {0, 0, 0};
-    for (uint32_t j = 0; j < n_loop; j++) for (int c = 0; c < 3; c++) cz[c] += (objs[j].origin[c] - Lp[c]) / n_loop;
-    double len = sqrt(cz[0] * cz[0] + cz[1] * cz[1] + cz[2] * cz[2]);
-    double z[3] = {0, -1, 0};
-    if (len > 1e-9 && std::isfinite(len)) for (int c = 0; c < 3; c++) z[c] = cz[c] / len;
-    const double up[3] = {fabs(z[1]) < 0.9 ? 0.0 : 1.0, fabs(z[1]) < 0.9 ? 1.0 : 0.0, 0.0};
-    double x[3] = {up[1] * z[2] - up[2] * z[1], up[2] * z[0] - up[0] * z[2], up[0] * z[1] - up[1] * z[0]};
-    len = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-    for (int c = 0; c < 3; c++) x[c] /= len;
-    const double y[3] = {z[1] * x[2] - z[2] * x[1], z[2] * x[0] - z[0] * x[2], z[0] * x[1] - z[1] * x[0]};
-    // per-sphere rectangles in (x'/z', y'/z')
-    std::vector<rt_geom> rect(n_loop);
-    std::vector<char> skip(n_loop, 0);
-    double gx0 = INFINITY, gx1 = -INFINITY, gy0 = INFINITY, gy1 = -INFINITY;
-    for (uint32_t j = 0; j < n_loop; j++) {
-      const double c[3] = {objs[j].origin[0] - Lp[0], objs[j].origin[1] - Lp[1], objs[j].origin[2] - Lp[2]};
-      const double cx = x[0] * c[0] + x[1] * c[1] + x[2] * c[2], cy = y[0] * c[0] + y[1] * c[1] + y[2] * c[2], cq = z[0] * c[0] + z[1] * c[1] + z[2] * c[2];
-      const double r2 = objs[j].r2, r = sqrt(r2);
-      rt_geom q = {-INFINITY, INFINITY, -INFINITY, INFINITY};
-      if (cq + r * (1.0 + 1e-9) + 1e-9 < 0.0) { skip[j] = 1; rect[j] = q; continue; }   // wholly behind the light: cannot lie between it and a point in front
-      const double kk = (cx * cx + cy * cy + cq * cq) - r2;
-      if (kk > 1e-9 * r2 && r2 > 0.0) {
-        axis_bounds(cx, cq, 1.0, 1.0, r2, &q.ox, &q.oy);
-        axis_bounds(cy, cq, 1.0, 1.0, r2, &q.oz, &q.r2);
-      }
-      rect[j] = q;
-      if (std::isfinite(q.ox)) gx0 = fmin(gx0, q.ox);
-      if (std::isfinite(q.oy)) gx1 = fmax(gx1, q.oy);
-      if (std::isfinite(q.oz)) gy0 = fmin(gy0, q.oz);
-      if (std::isfinite(q.r2)) gy1 = fmax(gy1, q.r2);
-    }
-    if (!(gx0 < gx1)) { gx0 = -1.0; gx1 = 1.0; }
-    if (!(gy0 < gy1)) { gy0 = -1.0; gy1 = 1.0; }
-    gx0 = fmax(gx0, -8.0); gx1 = fmin(gx1, 8.0); gy0 = fmax(gy0, -8.0); gy1 = fmin(gy1, 8.0);
-    if (!(gx0 < gx1)) { gx0 = -8.0; gx1 = 8.0; }
-    if (!(gy0 < gy1)) { gy0 = -8.0; gy1 = 8.0; }
-    const double inv_cw = G / (gx1 - gx0), inv_ch = G / (gy1 - gy0);
     double *hk = hdr + 16u * k;
-    for (int c = 0; c < 3; c++) { hk[c] = x[c]; hk[3 + c] = y[c]; hk[6 + c] = z[c]; }
-    hk[9] = gx0; hk[10] = gy0; hk[11] = inv_cw; hk[12] = inv_ch;
-    auto cell_of = [&](double v, double g0, double inv) -> uint32_t {     // the kernel's own mapping
-      const double f = fmin(fmax((v - g0) * inv, 0.0), (double)(G - 1));
-      return (uint32_t)f;
-    };
+    shadow_grid_frame(objs, n_loop, lights[k], hk);
     uint64_t *mk = masks + (size_t)k * cells * words;
     for (uint32_t j = 0; j < n_loop; j++) {
       mk[(size_t)(G * G) * words + (j >> 6)] |= 1ull << (j & 63u);                    // the "every sphere" cell
-      if (skip[j]) continue;
-      const uint32_t ix0 = cell_of(rect[j].ox, gx0, inv_cw), ix1 = cell_of(rect[j].oy, gx0, inv_cw);
-      const uint32_t iy0 = cell_of(rect[j].oz, gy0, inv_ch), iy1 = cell_of(rect[j].r2, gy0, inv_ch);
-      for (uint32_t iy = iy0; iy <= iy1; iy++) for (uint32_t ix = ix0; ix <= ix1; ix++) mk[((size_t)iy * G + ix) * words + (j >> 6)] |= 1ull << (j & 63u);
+      rt_geom q;
+      if (rt_shadow_rect(hk, lights[k], objs[j].origin, objs[j].r2, &q)) continue;
+      const uint32_t span = rt_sgrid_span(q, hk);
+      for (uint32_t iy = (span >> 16) & 255u; iy <= (span >> 24); iy++)
+        for (uint32_t ix = span & 255u; ix <= ((span >> 8) & 255u); ix++) mk[((size_t)iy * G + ix) * words + (j >> 6)] |= 1ull << (j & 63u);
     }
   }
   return buf;
@@ -147,12 +128,11 @@ std::vector<uint64_t> build_shadow_grid(const rt_sphere *objs, uint32_t n_loop, 
 // on the sphere only up to an ulp, its cell index comes from a 2^-24 reciprocal - cannot put a ray outside the set its
 // entry describes.  The table only prunes the candidates of the closest-hit search; the tests themselves are unchanged.
 // Layout: [n_objects][RT_BCELLS][words] uint64, bit j = loop sphere j (device order).
-std::vector<uint64_t> build_bounce_table(const rt_sphere *objs, uint32_t n_objects, uint32_t n_loop) {
-  const uint32_t K = RT_BGRID, cells = RT_BCELLS, words = (n_loop + 63u) / 64u;
-  std::vector<uint64_t> tab((size_t)n_objects * cells * words, 0ull);
+std::vector<double> bounce_cell_cones() {
+  const uint32_t K = RT_BGRID, cells = RT_BCELLS;
   // cell cones: centre direction, cos/sin of the half-angle (the kernel's mapping: face = 2*major axis + (negative), u/v =
   // the other two axes in x,y,z order, a = u/|major|, b = v/|major| in [-1,1], cell = floor((a+1)K/2))
-  std::vector<double> cdir(3u * cells), ccos(cells), csin(cells);
+  std::vector<double> cones(5u * cells);
   for (uint32_t f = 0; f < 6; f++) {
     const int m = (int)(f >> 1), ua = (m == 0) ? 1 : 0, va = (m == 2) ? 1 : 2;
     const double sgn = (f & 1u) ? -1.0 : 1.0;
@@ -171,39 +151,26 @@ std::vector<uint64_t> build_bounce_table(const rt_sphere *objs, uint32_t n_objec
         worst = fmin(worst, (v[0] * ctr[0] + v[1] * ctr[1] + v[2] * ctr[2]) / vl);
       }
       const double half = acos(fmax(-1.0, fmin(1.0, worst))) + 1e-6;
-      for (int k = 0; k < 3; k++) cdir[3u * c + k] = ctr[k];
-      ccos[c] = cos(half); csin[c] = sin(half);
+      for (int k = 0; k < 3; k++) cones[k * cells + c] = ctr[k];
+      cones[3u * cells + c] = cos(half); cones[4u * cells + c] = sin(half);
     }
   }
-  // per (i, j): one branch-free pass over the cells (structure-of-arrays, no division: both sides scaled by |D|)
-  std::vector<double> cx(cells), cy(cells), cz(cells);
-  for (uint32_t c = 0; c < cells; c++) { cx[c] = cdir[3u * c]; cy[c] = cdir[3u * c + 1]; cz[c] = cdir[3u * c + 2]; }
-  std::vector<uint8_t> hit(cells);
+  return cones;
+}
+
+std::vector<uint64_t> build_bounce_table(const rt_sphere *objs, uint32_t n_objects, uint32_t n_loop) {
+  const uint32_t cells = RT_BCELLS, words = (n_loop + 63u) / 64u;
+  std::vector<uint64_t> tab((size_t)n_objects * cells * words, 0ull);
+  const std::vector<double> cones = bounce_cell_cones();
   for (uint32_t i = 0; i < n_objects; i++) {
     const double ri = sqrt(objs[i].r2);
     uint64_t *row = tab.data() + (size_t)i * cells * words;
-    // rays leave a sphere only if it reflects or refracts (albedo[3] > 0 or albedo[4] > 0, main.js:233,246): the rows of
-    // the others are never read
-    if (!(objs[i].albedo[3] > 0.0) && !(objs[i].albedo[4] > 0.0)) continue;
+    if (!rt_bounce_row_used(objs[i])) continue;            // the rows of the others are never read
     for (uint32_t j = 0; j < n_loop; j++) {
-      const double D0 = objs[j].origin[0] - objs[i].origin[0], D1 = objs[j].origin[1] - objs[i].origin[1], D2 = objs[j].origin[2] - objs[i].origin[2];
-      const double Ld = sqrt(D0 * D0 + D1 * D1 + D2 * D2);
-      const double R = (ri + sqrt(objs[j].r2)) * (1.0 + 1e-9);
+      const rt_bounce_pair p = rt_bounce_pair_of(objs[i], ri, objs[j]);
       const uint64_t bit = 1ull << (j & 63u);
       const size_t wj = j >> 6;
-      const bool everywhere = !(R < Ld * (1.0 - 1e-9)) || !std::isfinite(R) || !std::isfinite(Ld);   // overlapping / containing / degenerate: all cells
-      if (everywhere) {
-        for (uint32_t c = 0; c < cells; c++) row[(size_t)c * words + wj] |= bit;
-        continue;
-      }
-      const double sa = R / Ld, ca = sqrt(fmax(0.0, 1.0 - sa * sa));
-      // angle(centre, D) <= alpha + half  <=>  cos(angle) >= cos(alpha + half); alpha, half in (0, pi/2), so the sum is < pi
-      for (uint32_t c = 0; c < cells; c++) {
-        const double dotp = cx[c] * D0 + cy[c] * D1 + cz[c] * D2;                       // |D| cos(angle)
-        const double cos_sum = ca * ccos[c] - sa * csin[c], sin_sum = sa * ccos[c] + ca * csin[c];
-        hit[c] = (uint8_t)((sin_sum <= 0.0) | (dotp >= Ld * (cos_sum - 1e-12)));
-      }
-      for (uint32_t c = 0; c < cells; c++) if (hit[c]) row[(size_t)c * words + wj] |= bit;
+      for (uint32_t c = 0; c < cells; c++) if (rt_bounce_cell_hit(p, cones.data(), c)) row[(size_t)c * words + wj] |= bit;
     }
   }
   return tab;

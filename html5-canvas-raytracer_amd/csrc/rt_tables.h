@@ -20,6 +20,12 @@ uint32_t enclosing_sphere(const rt_scene_header *hd, const rt_sphere *ob, const 
 // per-light grids of sphere bit sets for the shadow scans of many-sphere scenes (layout: rt_tables.cpp)
 std::vector<uint64_t> build_shadow_grid(const rt_sphere *objs, uint32_t n_loop, uint32_t n_lights, const double lights[][3]);
 
+// the frame header (16 doubles) of one light's shadow grid
+void shadow_grid_frame(const rt_sphere *objs, uint32_t n_loop, const double Lp[3], double hk[16]);
+
+// the bounce table's cell cones, [cx | cy | cz | cos | sin] x RT_BCELLS (rt_objects.h)
+std::vector<double> bounce_cell_cones();
+
 // per (sphere, cube-map direction cell) bit sets of the spheres a ray leaving that sphere in that direction can meet
 std::vector<uint64_t> build_bounce_table(const rt_sphere *objs, uint32_t n_objects, uint32_t n_loop);
 

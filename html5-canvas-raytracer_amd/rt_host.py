@@ -82,6 +82,28 @@ def validate_scene(scene):
             raise ValueError("object %d: texture index out of range" % i)
 
 
+def _sphere_record(ob):
+    m = ob["mtl"]
+    s = m["sampler"]
+    if s["kind"] == SAMPLER_CHECKER:
+        ck = [s["freqU"], s["freqV"], *s["colors"][0], *s["colors"][1]]
+    elif s["kind"] == SAMPLER_STARS:
+        ck = [s["threshold"], s["scale"], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]
+    else:
+        ck = [0.0] * 8
+    rec = struct.pack("<22d2id", *ob["origin"], ob["r2"], *m["color"], m["specular_exponent"],
+                      *m["albedo"], m["refract_index"], *[float(x) for x in ck],
+                      s["kind"], s["texture"] if s["kind"] == SAMPLER_TEXTURE else -1, 0.0)
+    assert len(rec) == SPHERE_BYTES
+    return rec
+
+
+def sphere_records(objects):
+    """scene-dict objects -> their rt_sphere records (bytes, SPHERE_BYTES each), packed exactly as flatten_scene packs them: what
+    rt_scene_set_objects / Renderer.set_objects take."""
+    return b"".join(_sphere_record(ob) for ob in objects)
+
+
 def flatten_scene(scene):
     """scene dict -> pointer-free blob (bytes), byte-identical to js/flatten.js flattenScene."""
     validate_scene(scene)
@@ -107,21 +129,8 @@ def flatten_scene(scene):
     assert len(hdr) == HEADER_BYTES
     out[0:HEADER_BYTES] = hdr
     o = objects_off
-    for ob in objs:
-        m = ob["mtl"]
-        s = m["sampler"]
-        if s["kind"] == SAMPLER_CHECKER:
-            ck = [s["freqU"], s["freqV"], *s["colors"][0], *s["colors"][1]]
-        elif s["kind"] == SAMPLER_STARS:
-            ck = [s["threshold"], s["scale"], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]
-        else:
-            ck = [0.0] * 8
-        rec = struct.pack("<22d2id", *ob["origin"], ob["r2"], *m["color"], m["specular_exponent"],
-                          *m["albedo"], m["refract_index"], *[float(x) for x in ck],
-                          s["kind"], s["texture"] if s["kind"] == SAMPLER_TEXTURE else -1, 0.0)
-        assert len(rec) == SPHERE_BYTES
-        out[o:o + SPHERE_BYTES] = rec
-        o += SPHERE_BYTES
+    out[o:o + len(objs) * SPHERE_BYTES] = sphere_records(objs)
+    o += len(objs) * SPHERE_BYTES
     for l in lights:
         out[o:o + 24] = struct.pack("<3d", *l)
         o += 24
@@ -171,6 +180,7 @@ ABI = {
     "rt_scene_free": (None, [C.c_void_p]),
     "rt_scene_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "rt_scene_set_stars_seed": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_scene_set_objects": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_render_tiles_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtTiles), C.c_void_p, C.c_void_p,
                                          C.c_uint32, C.POINTER(RtStats)]),
     "rt_render_batch_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtTiles), C.c_uint32, C.c_void_p, C.c_uint64,
@@ -265,6 +275,17 @@ class Renderer:
         if not (isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < 2 ** 32):
             raise ValueError("stars seed must be an integer in [0, 2^32)")
         _check(self.lib, self.lib.rt_scene_set_stars_seed(self.handle, seed), "rt_scene_set_stars_seed")
+
+    def set_objects(self, objects, first=0, stream=None):
+        """Replace spheres [first, first + len(objects)) of the resident scene (scene-dict objects, or their packed records from
+        sphere_records): asynchronous, like a camera move; the next render sees them.  RtError (RT_ERR_UNSUPPORTED) when the edit
+        changes the sphere that encloses everything: upload the scene again."""
+        recs = bytes(objects) if isinstance(objects, (bytes, bytearray)) else sphere_records(objects)
+        if len(recs) % SPHERE_BYTES:
+            raise ValueError("sphere records are %d bytes each" % SPHERE_BYTES)
+        buf = C.create_string_buffer(recs, max(len(recs), 1))
+        _check(self.lib, self.lib.rt_scene_set_objects(self.handle, first, len(recs) // SPHERE_BYTES, buf, C.c_void_p(stream or 0)),
+               "rt_scene_set_objects")
 
     def render_tiles(self, w, h, d_out, tiles=None, stream=None, flags=0, want_stats=False):
         t = tiles if isinstance(tiles, RtTiles) else RtTiles(*(tiles or (h, 0, 1, 1)))

@@ -238,6 +238,17 @@ int rt_scene_set_camera(rt_scene_dev *scene, const double origin[3], const doubl
  * rt_scene_set_camera.  Any value is valid. */
 int rt_scene_set_stars_seed(rt_scene_dev *scene, uint32_t seed);
 
+/* Replace the sphere records [first, first + count) of a resident scene, in blob order (the reference's objects are plain arrays a
+ * page may change between redraws, main.js:180-201): every field of a record may change - origin, r2, material, sampler, texture
+ * index; n_objects, lights, textures, camera and seed stay.  Blob order stays the semantics (closest hit: strict <, the first wins).
+ * Records are checked by rt_scene_validate's rules; a bad record or a range outside [0, n_objects) is RT_ERR_INVALID and leaves the
+ * scene as it was.  Records equal to the current ones change nothing.  Asynchronous, like a camera move: what depends on the spheres
+ * (records, geometry tables, LDS images, shadow grids, bounce table) exists twice, the move writes the next copy on the library's
+ * own stream - the tables of many-sphere scenes are rebuilt ON THE GPU - beside frames still rendering with the old spheres, and
+ * the next render of the scene on any stream waits for it by event.  An edit that changes the sphere that encloses everything (a
+ * skybox) is RT_ERR_UNSUPPORTED: upload the scene again.  `hip_stream` and thread rules as for rt_scene_set_camera. */
+int rt_scene_set_objects(rt_scene_dev *scene, uint32_t first, uint32_t count, const rt_sphere *records, void *hip_stream);
+
 /* Render tiles of the w x h frame into DEVICE memory `d_out_rgba` (at least
  * n_tiles*tile_rows*w*4 bytes) on `hip_stream` (a hipStream_t; NULL = the library's own
  * stream for that device).  Asynchronous unless `stats` is non-NULL (then it waits and
@@ -273,8 +284,9 @@ int rt_ipc_close(int device, void *d_ptr);
  * the next band's render; into smaller pinned frames the trace kernel stores directly, over PCIe.  Either way the call takes about
  * max(kernel, frame bytes / PCIe rate).  With more than one GPU in use the frame is sharded by interleaved row tiles and put
  * together on GPU 0 (peer stores, or one RCCL gather) before the copy-out.  The scene stays resident between calls: a blob that
- * differs from the previous call's only in the camera and / or stars_seed is not uploaded again (the resident scene moves its camera,
- * rt_scene_set_camera, and takes the seed, rt_scene_set_stars_seed).  Replaces redraw()/spanish() + ImageData (main.js:83,180-201). */
+ * differs from the previous call's only in the camera, stars_seed and / or sphere records is not uploaded again (the resident scene
+ * takes the spheres of the smallest range that covers the differences, rt_scene_set_objects, then moves its camera,
+ * rt_scene_set_camera, and takes the seed, rt_scene_set_stars_seed; an edit either call refuses with RT_ERR_UNSUPPORTED is uploaded).  Replaces redraw()/spanish() + ImageData (main.js:83,180-201). */
 int rt_render(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h,
               uint8_t *out_rgba, uint32_t flags, rt_stats *stats);
 
