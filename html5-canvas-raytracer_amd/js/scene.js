@@ -143,8 +143,10 @@ function validateScene(scene) {
   if (!Array.isArray(scene.objects) || scene.objects.length < 1 || scene.objects.length > 256) throw new Error('scene.objects must hold 1..256 spheres');
   if (!Array.isArray(scene.lights) || scene.lights.length > 16) throw new Error('scene.lights must hold 0..16 lights');
   scene.lights.forEach((l) => { if (!isVec(l, 3)) throw new Error('light must be a 3-vector'); });
+  if (!Array.isArray(scene.textures) || scene.textures.length > 16) throw new Error('scene.textures must hold 0..16 textures');
   scene.textures.forEach((t, i) => {
     if (!(t.width > 0 && t.height > 0) || t.texels.length !== t.width * t.height * 4) throw new Error('texture ' + i + ' is not loaded RGBA8');
+    if (!(Number.isInteger(t.width) && Number.isInteger(t.height) && t.width <= 16384 && t.height <= 16384)) throw new Error('texture ' + i + ': width and height must be in 1..16384');
   });
   scene.objects.forEach((o, i) => {
     if (!isVec(o.origin, 3) || typeof o.r2 !== 'number') throw new Error('object ' + i + ': origin/r2');

@@ -71,6 +71,11 @@ def validate_scene(scene):
         raise ValueError("scene.objects must hold 1..256 spheres")
     if len(scene["lights"]) > 16:
         raise ValueError("scene.lights must hold 0..16 lights")
+    if len(scene["textures"]) > 16:
+        raise ValueError("scene.textures must hold 0..16 textures")
+    for i, t in enumerate(scene["textures"]):
+        if not (1 <= t["width"] <= 16384 and 1 <= t["height"] <= 16384):
+            raise ValueError("texture %d: width and height must be in 1..16384" % i)
     seed = scene.get("starsSeed", 0)
     if not (isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < 2 ** 32):
         raise ValueError("scene.starsSeed must be an integer in [0, 2^32)")

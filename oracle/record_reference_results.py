@@ -6,8 +6,8 @@ present (like oracle/make_golden.js):
     python oracle/record_reference_results.py
 
 Writes tests/golden/reference_results.json, data only: the SHA-256 of frames rendered by the reference - its own main(), its
-intersectWorld on scenes of our schema at sizes that differ from the golden frames, and the random scenes of
-tests/soak_oracle_vs_reference.py.
+intersectWorld on scenes of our schema at sizes that differ from the golden frames, the random scenes of
+tests/soak_oracle_vs_reference.py, and the scenes of tests/texture_util.py that carry sixteen textures of odd shapes (1x1 ... 16384x2).
 """
 import json
 import os
@@ -19,6 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "html5-canvas-raytracer_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle_util as ou  # noqa: E402
 import soak_oracle_vs_reference as sr  # noqa: E402
+import texture_util as tu  # noqa: E402
 
 MAIN_SIZES = [(64, 48)]
 SCENES = [("cfg1", 96, 96), ("cfg2", 160, 90), ("h8", 200, 112), ("h8_d8", 120, 68), ("default14", 128, 72), ("lcg64", 48, 48),
@@ -30,7 +31,8 @@ def main():
     if not ou.have_reference():
         raise SystemExit("record_reference_results.py: the reference (or node) is not here")
     out = {"generator": "oracle/record_reference_results.py", "reference": ou.manifest()["reference"],
-           "main": [], "scenes": [], "random_scenes": {"first": RANDOM_FIRST, "frames": []}}
+           "main": [], "scenes": [], "random_scenes": {"first": RANDOM_FIRST, "frames": []},
+           "texture_scenes": []}
     for w, h in MAIN_SIZES:
         out["main"].append({"w": w, "h": h, "sha256": ou.node_cli("main", w, h)["sha256"]})
     for scene, w, h in SCENES:
@@ -42,11 +44,17 @@ def main():
             with open(p, "w") as f:
                 f.write(sr.to_json(scene))
             out["random_scenes"]["frames"].append({"seed": seed, "w": w, "h": h, "sha256": ou.node_cli("reference", p, w, h)["sha256"]})
+        for name, _, _, _ in tu.ORACLE_SCENES:
+            scene, w, h = tu.oracle_scene(name)
+            with open(p, "w") as f:
+                f.write(sr.to_json(scene))
+            out["texture_scenes"].append({"scene": name, "w": w, "h": h, "sha256": ou.node_cli("reference", p, w, h)["sha256"]})
     path = os.path.join(ou.GOLDEN, "reference_results.json")
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
-    print("wrote %s: %d main(), %d scenes, %d random scenes" % (path, len(out["main"]), len(out["scenes"]), len(out["random_scenes"]["frames"])))
+    print("wrote %s: %d main(), %d scenes, %d random scenes, %d texture scenes" % (path, len(out["main"]), len(out["scenes"]),
+                                                                                len(out["random_scenes"]["frames"]), len(out["texture_scenes"])))
 
 
 if __name__ == "__main__":

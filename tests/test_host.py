@@ -710,3 +710,58 @@ def test_dispatch_ranking_sees_what_a_blocks_mirrors_show(built):
     assert max(chrome) < 2500, chrome                                                                         # (round 3: 6 977 .. 7 052)
     floor = [rank[(tx, 2000)] for tx in range(40, 80)]                                                        # plain floor: far behind both
     assert min(floor) > max(chrome)
+
+
+# the texture rules of rt_scene_validate (at most RT_MAX_TEXTURES textures, each 1..16384 texels wide and high): (texture shapes, valid)
+TEXTURE_SETS = [
+    ([], True),
+    ([(1, 1)], True),
+    ([(1, 1)] * 16, True),
+    ([(16384, 1), (1, 16384), (3, 7)], True),
+    ([(16384, 2), (2, 16384)], True),
+    ([(1, 1)] * 17, False),
+    ([(16385, 1)], False),
+    ([(1, 16385)], False),
+    ([(1, 1), (0, 4)], False),
+    ([(4, 0)], False),
+]
+
+
+@needs_node
+def test_the_three_validators_agree_on_texture_sets(built, tmp_path, monkeypatch):
+    """rt_scene_validate (C), rt_host.validate_scene and js/scene.js validateScene state the same rules: each texture set gets the
+    same verdict from all three (lcg64's spheres draw no texture, so only the texture table decides)."""
+    lib = rt_host.load_library()
+    base = rt_host.load_scene("lcg64")
+
+    def scene_with(shapes):
+        return dict(base, textures=[{"width": w, "height": h, "texels": bytes(w * h * 4)} for w, h in shapes])
+
+    def python_ok(shapes):
+        try:
+            rt_host.validate_scene(scene_with(shapes))
+            return True
+        except ValueError:
+            return False
+
+    def c_ok(shapes):
+        with monkeypatch.context() as m:
+            m.setattr(rt_host, "validate_scene", lambda s: None)          # the blob as a caller of the C ABI may hand it over
+            blob = rt_host.flatten_scene(scene_with(shapes))
+        return lib.rt_scene_validate(C.create_string_buffer(blob, len(blob)), len(blob)) == 0
+
+    cases = tmp_path / "cases.json"
+    cases.write_text(json.dumps([shapes for shapes, _ in TEXTURE_SETS]))
+    js = """
+const S = require('%(pkg)s/js/scene.js'); const F = require('%(pkg)s/js/flatten.js'); const fs = require('fs');
+const base = F.sceneFromJSON(fs.readFileSync('%(pkg)s/scenes/lcg64.json', 'utf8'), '%(pkg)s/scenes');
+const out = JSON.parse(fs.readFileSync(process.argv[1], 'utf8')).map((shapes) => {
+  const sc = Object.assign({}, base, {textures: shapes.map(([w, h]) => ({width: w, height: h, texels: new Uint8Array(w * h * 4), loaded: true}))});
+  try { S.validateScene(sc); return true; } catch (e) { return false; }
+});
+console.log(JSON.stringify(out));
+""" % {"pkg": os.path.join(ROOT, "html5-canvas-raytracer_amd")}
+    js_ok = json.loads(subprocess.check_output([ou.node_path(), "-e", js, str(cases)], text=True))
+    for (shapes, want), j in zip(TEXTURE_SETS, js_ok):
+        label = shapes[:3] + (["... %d in all" % len(shapes)] if len(shapes) > 3 else [])
+        assert (c_ok(shapes), python_ok(shapes), j) == (want, want, want), label

@@ -118,6 +118,27 @@ def test_restatements_vs_live_reference_on_random_scenes(built):
     assert res["c_flipped_pixels"] == 0
 
 
+@needs_node
+@pytest.mark.parametrize("name", [r["scene"] for r in REF["texture_scenes"]])
+def test_restatements_vs_live_reference_on_odd_texture_shapes(name, built, tmp_path):
+    """Sixteen generated textures of odd shapes (tests/texture_util.py: 1x1, 3x7, 1x9, 9x1, 16384x2, 2x16384, ...) on h8's spheres,
+    rendered by the reference itself and recorded as SHA-256: the JS restatement must be bit-identical, the C restatement within
+    1 LSB with no flipped pixel.  This pins the `ceil(u * w) - 1` texel edges (main.js) at a width or height of 1 and at 16384."""
+    import soak_oracle_vs_reference as sr
+    import texture_util as tu
+    rec = next(r for r in REF["texture_scenes"] if r["scene"] == name)
+    scene, w, h = tu.oracle_scene(name)
+    assert (w, h) == (rec["w"], rec["h"])
+    p, out = tmp_path / "s.json", tmp_path / "s.rgba"
+    p.write_text(sr.to_json(scene))
+    assert ou.node_cli("restate", p, w, h, "--out", out)["sha256"] == rec["sha256"]
+    ref = np.fromfile(out, dtype=np.uint8)
+    assert len(np.unique(ref.reshape(-1, 4), axis=0)) > 500                  # (the textures show: hundreds of distinct colours)
+    c = np.frombuffer(ou.c_oracle_render(rt_host.flatten_scene(scene), w, h), dtype=np.uint8)
+    d = np.abs(c.reshape(-1, 4).astype(np.int16) - ref.reshape(-1, 4).astype(np.int16))
+    assert int(d.max()) <= 1 and float((d > 0).mean()) < 0.01, (name, int(d.max()))
+
+
 # ---------------------------------------------------------------- hashed stars sampler (kind 3)
 @needs_node
 def test_stars_sampler_js_and_c_restatements_agree(built, tmp_path):
