@@ -1,0 +1,283 @@
+// rt_api_internal.h — what the host units of the C ABI share: errors and test switches, the library and device state, the resident
+// scene (rt_scene_dev) and the few functions that cross units.  Not part of the ABI.
+//   rt_api.hip     lifetime, errors, device state, the scratch guard, the host-logic probes, memory helpers, IPC
+//   rt_scene.hip   upload and moves of a resident scene (the generation pipeline), its launch decisions and launch tables
+//   rt_launch.hip  the launches: colour (product / strict / retrace), supersampling, compact bands, primary hits and picking
+//   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick
+#ifndef RT_API_INTERNAL_H
+#define RT_API_INTERNAL_H
+
+#include <hip/hip_runtime.h>
+#include <dlfcn.h>
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "rt_device.h"
+#include "rt_tables.h"
+#include "rt_tables_gpu.h"
+#include "rt_hits.h"
+#include "rt_objects_gpu.h"
+
+extern "C" int rt_launch_trace_fast(const rt_launch *, int, int, int, unsigned, hipStream_t);
+extern "C" int rt_launch_trace_strict(const rt_launch *, int, int, int, unsigned, hipStream_t);
+extern "C" int rt_launch_retrace(const rt_launch *, int, int, unsigned, hipStream_t);
+extern "C" int rt_scratch_trace_fast(int, int, int, int, int, size_t *);
+extern "C" int rt_scratch_trace_strict(int, int, int, int, int, size_t *);
+extern "C" int rt_scratch_retrace(int, int, size_t *);
+
+using namespace rt_tables;   // the host-built tables (pure host logic, rt_tables.cpp)
+
+namespace rt_api {
+
+extern thread_local char g_err[512];
+
+// A/B and test switches exist only in the TEST build of this library (csrc/Makefile: librt_hip_test.so, -DRT_TESTING,
+// selected by the tests with RT_HIP_LIB).  The product library reads no environment variable on the render path.
+#ifdef RT_TESTING
+#define RT_TEST_ENV(name) getenv(name)
+#else
+#define RT_TEST_ENV(name) ((const char *)nullptr)
+#endif
+
+int fail(int code, const char *fmt, ...);
+#define HIP_TRY(expr)                                                                             \
+  do {                                                                                            \
+    hipError_t e_ = (expr);                                                                       \
+    if (e_ != hipSuccess) return fail(RT_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_));     \
+  } while (0)
+
+struct device_state {
+  int hip_id = -1;
+  hipStream_t stream = nullptr;          // created on first use
+  hipStream_t copy_stream = nullptr;     // rt_render: PCIe copy-out overlapped with rendering
+  unsigned long long *d_counters = nullptr;
+  void *d_frame = nullptr;               // rt_render scratch: this device's tiles (or the whole frame)
+  size_t frame_bytes = 0;
+  void *d_gather = nullptr;              // device 0 only: gather target (fallback plan of rt_render on several GPUs)
+  size_t gather_bytes = 0;
+  int peer_to_root = 0;                  // rt_render on several GPUs: 1 = this device may store into device 0's memory, -1 = it may not, 0 = not asked yet
+  // rt_render: the scene of the previous call stays resident; a call with the same blob (byte for byte) reuses it
+  // (upload + table builds cost 0.1 ms for 8 spheres and 1.8 ms for 64, against a 0.7 ms frame)
+  struct rt_scene_dev *cached_scene = nullptr;
+  std::vector<uint8_t> cached_blob;
+  // scratch_guard: wave slots of the device (CUs x waves per CU) and, per stream, the largest per-lane scratch figure whose reservation
+  // has been held against the free device memory
+  size_t wave_slots = 0;
+  struct scratch_seen { hipStream_t stream; size_t per_lane; };
+  std::vector<scratch_seen> scratch_checked;
+};
+
+struct lib_state {
+  bool inited = false;
+  std::vector<device_state> dev;
+  std::mutex mu;
+  std::mutex dev_mu;                     // lazy per-device stream creation (ensure_device may run inside rt_render, which holds `mu`)
+  // RCCL, resolved lazily with dlopen so that single-GPU users never load it
+  void *rccl = nullptr;
+  void *comms[16] = {nullptr};
+  bool comms_ready = false;
+  // RT_EMULATE_DEVICES=N (test aid for 1-GPU boxes): rt_init reports N devices that all map to HIP device 0, and
+  // rt_render's gather becomes device-to-device copies instead of ncclGather (RCCL refuses two ranks on one GPU).
+  // Everything else of the multi-GPU frame - tile plan, per-device scenes and streams, RGB24 bands, de-interleave -
+  // runs as on a real node.
+  bool emulated = false;
+  bool all_visible = false;
+};
+extern lib_state G;
+
+int ensure_device(int d);
+int scratch_guard(device_state &D, hipStream_t stream, size_t per_lane, uint64_t waves_in_grid, const char *what);
+int kernel_scratch(bool strict, bool retrace, int refract, int count, int ss2, int grid_variant, size_t *out, bool one_wave = false);
+int guard_kernel_scratch(device_state &D, hipStream_t stream, bool strict, bool retrace, int refract, int count, int ss2, int grid_variant, bool one_wave,
+                         uint64_t waves_in_grid, const char *what);
+int check_frame(const char *what, uint32_t w, uint32_t h, const rt_tiles *tiles, uint32_t flags);
+uint64_t tile_set_pixels(uint32_t w, uint32_t h, const rt_tiles *tiles);
+
+// The sample grid of a launch over a w x h frame at supersample ss (1 or 2; the hit kernels: 1..4): workgroups per tile row, rows
+// per workgroup, row blocks per tile, and the projection constants (main.js:102-105) in binary64 on the host.
+struct launch_geom { uint32_t tiles_x, rows_per_wg, rb_per_tile; double proj_w, proj_h, proj_d; };
+launch_geom launch_geometry(double fov_deg, uint32_t w, uint32_t h, uint32_t ss, uint32_t tile_rows);
+
+// GPU time between start() and stop() on a stream; the events are released on every way out
+struct event_timer {
+  hipEvent_t a = nullptr, b = nullptr;
+  event_timer() = default;
+  event_timer(const event_timer &) = delete;
+  ~event_timer() { release(); }
+  void release() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); a = b = nullptr; }
+  hipError_t start(hipStream_t stream) {
+    hipError_t e = hipEventCreate(&a);
+    if (e == hipSuccess) e = hipEventCreate(&b);
+    if (e == hipSuccess) e = hipEventRecord(a, stream);
+    return e;
+  }
+  hipError_t stop(hipStream_t stream) { return hipEventRecord(b, stream); }
+  hipError_t elapsed(float *ms) const { return hipEventElapsedTime(ms, a, b); }
+};
+
+}  // namespace rt_api
+
+using namespace rt_api;
+
+// One kind of frame: size, sample grid (1 or 2), tile set and sky part (0 everything, 1 RT_FLAG_NO_SKY, 2 RT_FLAG_SKY_ONLY).  A scene
+// keeps a launch table and a use count per kind.
+struct frame_kind {
+  uint32_t w, h, ss;
+  rt_tiles tiles;
+  uint32_t part;
+  bool operator==(const frame_kind &o) const {
+    return w == o.w && h == o.h && ss == o.ss && tiles.tile_rows == o.tiles.tile_rows && tiles.tile_first == o.tiles.tile_first &&
+           tiles.tile_stride == o.tiles.tile_stride && tiles.n_tiles == o.tiles.n_tiles && part == o.part;
+  }
+};
+
+struct rt_scene_dev {
+  int device;
+  // Everything the scene keeps in HBM is ONE allocation (`arena`), filled by one copy at upload; the pointers below point into it.
+  // Its last part is the CAMERA BLOCK - what depends on the camera: per ordering the camera-anchored geometry and the cull
+  // rectangles, and (few spheres) the LDS images, whose tails are the cull rectangles - rewritten with one small asynchronous copy
+  // when the camera moves (rt_scene_set_camera).
+  uint8_t *arena = nullptr;
+  size_t arena_bytes = 0;
+  void *d_blob;                  // the uploaded scene blob (its texels and lights; its sphere records are the OBJECT BLOCK's)
+  rt_texture_desc *d_texdesc;    // RT_MAX_TEXTURES descriptors (zero padded)
+  double *d_cones;               // the bounce table's cell cones (rt_tables.cpp: bounce_cell_cones), or NULL (no bounce table)
+  // The OBJECT BLOCK: what depends on the spheres but not on the camera, at offsets o_* inside it:
+  //   o_objs     the sphere records in blob order (1/r in `reserved`)
+  //   o_geom     camera-independent geometry tables, per ordering [plain N | anchored at light k: NL x N]
+  //   o_objs_b   object records with the enclosing sphere moved last (ordering B); none without one
+  //   o_img      many spheres: per ordering [materials (rt_mtl) | 16 texture descriptors], the LDS image (few spheres: it holds the
+  //              cull rectangles and lives in the camera block)
+  //   o_sg       light grids for the product kernel's loop order (has_sg: more than RT_SGRID_MIN_LOOP loop spheres)
+  //   o_bt       bounce table for the same order (has_bt: more than RT_BTABLE_MIN_LOOP loop spheres and depth >= 2)
+  // Everything up to the shadow grids' masks (obj_host_bytes) is written by the host; the masks and the bounce table are built from it
+  // (rt_objects_gpu.hip after a move; rt_tables.cpp at upload).  TWO blocks, like the camera blocks: generation g reads block g & 1,
+  // so that rt_scene_set_objects can write the next one while launches with the current spheres are still running.
+  uint8_t *d_obj_buf[2];
+  size_t obj_bytes, obj_host_bytes;
+  size_t o_objs, o_geom, o_objs_b, o_img, o_sg, o_bt, sg_bytes, bt_bytes;
+  bool has_sg, has_bt;
+  uint64_t obj_version = 0;      // bumped by every object move; slot_version[b]: the version object block b holds
+  uint64_t slot_version[2] = {0, 0};
+  // The camera block: per ordering [anchored at the camera N | cull rectangles N], then (few spheres) the LDS images.  TWO of them:
+  // camera generation g lives in block g & 1, so that the block of the NEXT camera can be written - on the scene's own side stream,
+  // by rt_scene_set_camera - while launches with the current one are still running.
+  uint8_t *d_cam_buf[2];
+  size_t cam_lds_offset;         // of the LDS images inside a camera block
+  size_t cam_bytes;              // (with the padding the many-sphere staging may read over)
+  size_t cam_bytes_used;         // what a camera move has to copy
+  bool has_b;                    // two orderings (an enclosing sphere)
+  bool cull_in_lds;
+  size_t lds_image_bytes;        // of one ordering
+  uint64_t cam_gen = 1;          // bumped when the camera moves: launch tables and mark counts of an older camera are stale
+  // product launches per frame kind since the camera last moved: many-sphere scenes get their shadow masks with the SECOND frame of a kind
+  struct camera_use { frame_kind kind; uint64_t cam_gen; uint32_t uses; };
+  std::vector<camera_use> camera_uses;
+  hipStream_t last_stream = nullptr;     // the stream of the scene's last launch; several: launches of this scene are in flight on more than one
+  bool any_launch = false, several_streams = false, launched_since_move = false;
+  // The camera pipeline (rt_scene_set_camera).  `side`: a stream of the scene's own, on which a move's camera block is copied and the
+  // launch tables of the frame sizes in use are rebuilt - beside the previous camera's launches, which run on the caller's stream.
+  //   old_done[x]   recorded on the caller's stream at the move to generation g (x = (g - 1) & 1): every launch with generations < g
+  //                 precedes it.  The move to g + 1 writes block / tables (g + 1) & 1 = x only behind it.
+  //   prep_done[b]  recorded on `side` behind the copy and the builds of generation g (b = g & 1): the first launch of generation g
+  //                 on a stream waits for it (prep_waited: which streams already do).
+  hipStream_t side = nullptr;
+  hipEvent_t old_done[2] = {nullptr, nullptr}, prep_done[2] = {nullptr, nullptr};
+  bool old_done_valid[2] = {false, false}, prep_valid[2] = {false, false};
+  struct waited_on { hipStream_t stream; uint64_t gen; };
+  std::vector<waited_on> prep_waited;
+  // pinned staging for the small copies that follow a camera move (the camera block; a launch table's parameters): a ring of slots,
+  // each guarded by an event recorded behind the copy that read it
+  struct stage_slot { uint8_t *h = nullptr; hipEvent_t done = nullptr; bool used = false; };
+  stage_slot stages[16];                 // (16: the host may run eight frames ahead of the GPU in an animation; one pinned allocation behind them)
+  uint8_t *stage_pool = nullptr;
+  size_t stage_bytes = 0;
+  uint32_t stage_next = 0;
+  std::vector<uint8_t> host_blob;        // the scene as uploaded (patched: 1/r per sphere), for rebuilding the camera block
+  std::vector<rt_sphere> host_objects_b; // ordering B of its sphere records
+  rt_scene_header hd;            // host copy
+  bool refract;                  // any albedo[4] > 0  -> general (binary-tree) kernel variant
+  unsigned lds_bytes;
+  double lights[RT_MAX_LIGHTS][3];   // host copy: lights travel in the kernarg segment
+  uint32_t enclosing;            // sphere that strictly contains everything else (a skybox), or ~0u
+  bool enclosing_flat;           // ... and it has no lighting, no children and a sampler that ignores the hit point (colour / stars)
+  bool sky_const;                // ... a plain colour: the pixel of a ray that meets nothing else is the constant sky_rgb
+  double sky_rgb[3];
+  // cost-ordered dispatch (dispatch_order below): per sphere its screen rectangle (X/D, Y/D bounds, scene order) and a weight,
+  // and the order tables built so far, one per (frame size, tile set), kept on the device
+  std::vector<rt_sphere> host_objects;   // the scene's sphere records (scene order), for the launch table's sky marking
+  std::vector<rt_geom> host_cull;
+  std::vector<uint32_t> tile_weight;
+  // One launch table per (frame size, tile set, flags), built on the GPU (rt_tables_gpu.hip) on the stream of the launch that needs
+  // it first and again when the camera has moved since (cam_gen).  `Tb` = its device memory; `d_blockb` = ONE allocation
+  // behind all of T's arrays; `n_blocks` workgroups are launched until the host has seen the number of entries the build published
+  // (`known`: generation << 32 | entries + 1, a pinned host word), from then on exactly that many.
+  struct order_entry {
+    frame_kind kind; int ranked; bool sky, masks, cands;     // ranked: 0 grid order, 1 ranked when large enough, 2 always (a compact band's launch)
+    uint64_t cam_gen; uint32_t n_blocks; volatile unsigned long long *known; hipStream_t built_on; hipEvent_t built;
+    bool shared;                   // launched with on a stream other than the one it was built on
+    // two tables, like the camera blocks: generation g's is Tb[g & 1] (the next camera's is built while this one's is still read)
+    rt_table_dev Tb[2]; uint8_t *d_blockb[2]; size_t hist_wordsb[2];
+    uint32_t cost_bins;            // of the current build (rt_retrace of a compact launch)
+    uint64_t used_gen;             // the last camera generation a launch used it with: a move rebuilds the tables in use ahead of the next render
+  };
+  std::vector<order_entry> orders;
+  uint32_t order_evict = 0;
+  rt_texture_desc descs[RT_MAX_TEXTURES];
+  // Marked samples (rt_device.h, rt_kernel.hip: rt_retrace).  One state per (launch table, stream): the device list the product
+  // launch appends to and rt_retrace reads, which of its two counters the next launch uses, and a pinned host word in which
+  // rt_retrace publishes how many samples a frame of this scene, camera, size and tile set marks - the same every time, so once it
+  // says "none" (and the sample grid has no odd centre) the second launch is skipped.  Launches that share a state share a
+  // stream, i.e. they are ordered; mark_mu makes a launch pair one step for the threads of this process.
+  struct mark_state { uint32_t order_index; hipStream_t stream; uint32_t *d_marks; volatile unsigned long long *h_known; uint32_t slot; };   // *h_known: camera generation << 32 | marks + 1
+  std::vector<mark_state> mark_states;
+  unsigned long long *h_known_pool = nullptr;      // 2 x RT_KNOWN_WORDS pinned words: the mark states', then the launch tables'
+  std::mutex launch_mu;          // a product launch - its table (found or built), the trace launch, rt_retrace - is one step for the threads of this process
+  bool needs_strict;             // the scene sits on an exact coincidence (below): every launch uses the strict kernel
+  bool needs_strict_scene;       // ... whatever the camera (a light on a surface, a sphere without a radius, exotic checker frequencies)
+  bool unit_weights;             // every albedo and colour in [0, 1] (RT_MARK_WEIGHT)
+  double flag_tol;               // RT_FLAG_T1 x the largest sampler frequency of the scene (texture width / height, checker frequencies): rt_device.h
+};
+
+namespace rt_api {
+constexpr size_t RT_KNOWN_WORDS = 256;
+inline uint8_t *cam_block(const rt_scene_dev *s) { return s->d_cam_buf[s->cam_gen & 1u]; }
+inline uint8_t *obj_block(const rt_scene_dev *s) { return s->d_obj_buf[s->cam_gen & 1u]; }
+inline uint8_t *lds_image_of(const rt_scene_dev *s) { return s->cull_in_lds ? cam_block(s) + s->cam_lds_offset : obj_block(s) + s->o_img; }
+
+// rt_api.hip
+int check_sphere(const rt_sphere &o, uint32_t i, uint32_t n_textures);
+
+// rt_scene.hip: the launch decisions of a resident scene, its launch tables
+void note_launch(rt_scene_dev *s, hipStream_t stream);
+bool strict_scene(const rt_scene_dev *s);
+bool sky_fast(const rt_scene_dev *s);
+bool masks_pay(const rt_scene_dev *s, uint32_t uses_before);
+uint32_t sky_part_of(uint32_t flags);
+struct table_choice { int ranked; bool mark_sky, shadow_masks, name_candidates; };
+table_choice choose_table(const rt_scene_dev *s, uint32_t flags, uint32_t uses_before);
+uint32_t count_use(rt_scene_dev *s, const frame_kind &kind);
+volatile unsigned long long *known_word(rt_scene_dev *s, size_t index);
+uint32_t known_value(const volatile unsigned long long *p, uint64_t gen);
+int behind_the_camera(rt_scene_dev *s, hipStream_t stream);
+int dispatch_order(rt_scene_dev *s, const frame_kind &kind, const table_choice &c, hipStream_t stream);
+
+// rt_launch.hip: argument checks of the hit entry points
+int hits_frame_check(uint32_t w, uint32_t h, uint32_t k, const char *what);
+int pick_points_check(uint32_t w, uint32_t h, uint32_t k, uint32_t n, const uint32_t *xy, const void *out, const char *what);
+
+// rt_frame.hip: RCCL's communicators are destroyed (rt_shutdown)
+void release_rccl();
+}  // namespace rt_api
+
+#endif

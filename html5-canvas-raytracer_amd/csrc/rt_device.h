@@ -96,7 +96,7 @@ struct rt_launch {
   uint32_t scatter;                  // rt_render_scatter_device: frame f goes to out_frames[f] (possibly another GPU's memory,
                                      // peer-mapped), its rows in FRAME order; `out` and frame_stride are unused
   uint32_t *out_frames[RT_MAX_SCATTER];
-  // Launch table of the product kernel (rt_api.hip: dispatch_order): workgroup b of the flat grid renders the tile described by
+  // Launch table of the product kernel (rt_scene.hip: dispatch_order): workgroup b of the flat grid renders the tile described by
   // entry b = {tile_x | rows_valid << 11 | first frame row << 15, first row in the output band}; the table build (rt_tables_gpu.hip) lists the tiles
   // dearest first, so that a launch ends on cheap tiles.  The strict kernel runs on the plain 2-D grid and ignores it.
   const uint32_t *order;             // the entries; the four words in front of them are the table's header {entries, ceil(entries / 8), 0, 0}
@@ -106,7 +106,7 @@ struct rt_launch {
   uint32_t grid_x, grid_y;           // host side only: the product launch's flat grid (one workgroup per table entry; 0 = the plain 2-D grid)
   // Samples on exact coincidences.  A sample whose outcome in the reference hinges on the last bit of the reference's own
   // arithmetic is traced a second time with the reference's own operation sequence by the strict build's list-driven kernel
-  // (rt_kernel.hip: rt_retrace; rt_api.hip launches it after the product launch): the samples the product kernel MARKED - a sampler
+  // (rt_kernel.hip: rt_retrace; rt_launch.hip launches it after the product launch): the samples the product kernel MARKED - a sampler
   // coordinate within rounding of a texel / checker boundary (main.js:129-130, 344-347) - and the centre row / column of an odd
   // sample grid (a primary ray with an exactly-zero component, main.js:186).
   uint32_t *marks;                   // words 0, 1: the mark counters of alternate launches; words 4...: entries of 8 bytes (sample x | y << 20 | frame << 40)

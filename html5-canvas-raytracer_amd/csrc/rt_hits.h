@@ -1,4 +1,4 @@
-// Launch record of the primary-hit kernels (rt_hits.hip), shared with their host side (rt_api.hip).  Not part of the ABI.
+// Launch record of the primary-hit kernels (rt_hits.hip), shared with their host side (rt_launch.hip).  Not part of the ABI.
 #ifndef RT_HITS_H
 #define RT_HITS_H
 

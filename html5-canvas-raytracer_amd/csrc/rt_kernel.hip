@@ -18,7 +18,7 @@
 //     128-byte framebuffer lines, each line written by exactly one workgroup (no cross-XCD sharing);
 //     product kernel: a FLAT grid whose workgroups look their tile up in a launch table built on the GPU (one
 //     s_load_dwordx4: no tile arithmetic, no division) that lists the tiles dearest first, so a launch ends
-//     on cheap sky tiles (rt_api.hip: dispatch_order); strict kernel: the plain 2-D grid;
+//     on cheap sky tiles (rt_scene.hip: dispatch_order); strict kernel: the plain 2-D grid;
 //   * everything wave-uniform — camera, lights, loop bounds (kernarg) and the sphere tables walked by
 //     the uniform object loops (typed address_space(4)) — is read with SCALAR loads into SGPRs: the
 //     intersection loops issue no vector memory and no LDS instruction;
@@ -43,7 +43,7 @@
 // odd sample grid) that stay in a coordinate plane through sphere centres - can only be reproduced by the reference's own
 // operation sequence.  The product kernels MARK the former while tracing (a list in HBM); the strict build has a second,
 // list-driven kernel (rt_retrace) that traces the marked samples and the centre row / column again and stores over them
-// (rt_api.hip: render_batch_impl launches it unless it KNOWS that a frame of this scene, camera, size and tile set has neither).
+// (rt_launch.hip: render_batch_impl launches it unless it KNOWS that a frame of this scene, camera, size and tile set has neither).
 // Scenes that sit on a coincidence as a whole (a light exactly on a surface, a camera with a zero axis sum:
 // rt_scene_dev::needs_strict) take the strict kernels throughout.
 
@@ -456,7 +456,7 @@ __device__ __forceinline__ const rt_launch __attribute__((address_space(4))) *rt
 }
 #if !RT_STRICT
 // Append this work-item's sample to the launch's mark list (the cold end of the samplers' boundary test, a handful of samples per frame): entry = sample x |
-// sample y << 20 | frame of the batch << 40; the counter of THIS launch is marks[marks_slot] (rt_api.hip alternates two, so that
+// sample y << 20 | frame of the batch << 40; the counter of THIS launch is marks[marks_slot] (rt_launch.hip alternates two, so that
 // rt_retrace can clear the next launch's while it reads its own); beyond the list's capacity only the count grows and rt_retrace
 // traces every sample of the launch.
 template <bool SS2>
@@ -737,7 +737,7 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
 #if defined(RT_TESTING) && defined(RT_ABLATE_SHADE)
       if (true) { ret[0] = ht; ret[1] = (double)hcode; ret[2] = 0.0; } else
 #endif
-      if (hcode < 0) {                                // main.js:231 (with a flat sky of constant colour: that sky's pixel term, see rt_api.hip bind_kernel)
+      if (hcode < 0) {                                // main.js:231 (with a flat sky of constant colour: that sky's pixel term, see rt_launch.hip bind_kernel)
 #if RT_STRICT
         ret[0] = L.miss_color[0]; ret[1] = L.miss_color[1]; ret[2] = L.miss_color[2];
 #else
@@ -813,11 +813,11 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
         // part, and this kernel's u, v differ from the reference's in their last bits (its hit point and normal do).  A sample with a
         // coordinate within L.flag_tol (RT_FLAG_T1 x the scene's largest sampler frequency: 1e-9 for the reference's checker) of an
         // integer is decided in the reference by the last bits of ITS arithmetic: it is appended to the launch's mark list and
-        // traced again, operation for operation, by the strict build's rt_retrace (rt_api.hip).  The test on the hot path is integer work on the bits of x + 1.5 * 2^32, a sum whose ulp
+        // traced again, operation for operation, by the strict build's rt_retrace (rt_launch.hip).  The test on the hot path is integer work on the bits of x + 1.5 * 2^32, a sum whose ulp
         // is 2^-20: its mantissa holds floor(x) (from bit 20 up) - the texel index, the checker parity - and 20 fraction bits;
         // "fraction within 2^-20 of 0 or 1" (6e-6 of the hits) sends the sample to the precise test, which also takes floor(x)
         // again (the sum rounds a fraction above 1 - 2^-21 up).  (Checker frequencies outside [0, 2^31), where the sum does not hold
-        // ToInt32's parity, make the scene a strict-kernel scene: rt_api.hip.)
+        // ToInt32's parity, make the scene a strict-kernel scene: rt_scene.hip.)
         // RT_XY_INDEX: iu, iv = floor(xu), floor(xv) and the boundary mark
 #define RT_XY_INDEX(XU, XV, FU, FV)                                                                                \
           const unsigned long long su = __builtin_bit_cast(unsigned long long, (XU) + 6442450944.0), sv = __builtin_bit_cast(unsigned long long, (XV) + 6442450944.0);   \
@@ -1606,7 +1606,7 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
 // materials read from HBM, no wave-wide step (a wave's lanes hold unrelated samples) - and stored where the product launch
 // stored it (band, RGB24 band, or its row of the frame in scatter mode).  With supersample 2 the pixel's four samples are all
 // traced (the product launch kept only their average).  A grid-stride loop: the number of items is only known on the device.
-// Work-item 0 clears the NEXT launch's counter and publishes this launch's count to the host (rt_api.hip skips this launch from
+// Work-item 0 clears the NEXT launch's counter and publishes this launch's count to the host (rt_launch.hip skips this launch from
 // then on if a frame of this scene, camera, size and tile set has no item at all).
 template <bool REFRACT, bool SS2>
 __global__ void __launch_bounds__(RT_WG_THREADS) rt_retrace(const rt_launch L) {

@@ -1,0 +1,652 @@
+// rt_launch.hip — the launches of a resident scene (include/rt_hip.h: rt_render_*_device): the product launch with its launch table
+// and the list-driven strict launch behind it (rt_retrace), the strict kernel, 3x3 / 4x4 supersampling with a box filter, compact
+// bands, primary hits and picking, and the test build's per-sample probe.
+
+#include "rt_api_internal.h"
+
+// ------------------------------------------------------------------------------------ launch
+extern "C" int rt_render_tiles_device(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, void *d_out, void *hip_stream,
+                                      uint32_t flags, rt_stats *stats) {
+  return rt_render_batch_device(s, w, h, tiles, 1u, d_out, 0u, hip_stream, flags, stats);
+}
+
+namespace {
+int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, uint32_t n_frames, void *d_out, uint64_t frame_stride_bytes,
+                      void *const *d_frames, void *hip_stream, uint32_t flags, rt_stats *stats, uint32_t ss_override = 0u);
+#ifdef RT_TESTING
+thread_local struct { double *d_buf; uint32_t x, y; } g_probe = {nullptr, 0u, 0u};
+#endif
+}  // namespace
+
+#ifdef RT_TESTING
+// Test build only: the ray tree of ONE sample (sample-grid coordinates sx, sy) as RT_PROBE_NODES records of RT_PROBE_WORDS
+// doubles {path, hcode, t, hit point, normal, direction, sampled colour, diffuse, specular, segs left, light intensity after
+// the scans, ray origin, children mask, valid}; the row that holds the sample is rendered into scratch memory.
+extern "C" int rt_test_probe(rt_scene_dev *s, uint32_t w, uint32_t h, uint32_t sx, uint32_t sy, uint32_t flags, double *out_records) {
+  if (!s || !out_records) return fail(RT_ERR_INVALID, "rt_test_probe: NULL argument");
+  int rc = ensure_device(s->device);
+  if (rc) return rc;
+  const size_t bytes = (size_t)RT_PROBE_NODES * RT_PROBE_WORDS * sizeof(double);
+  double *d_probe = nullptr;
+  void *d_row = nullptr;
+  HIP_TRY(hipMalloc((void **)&d_probe, bytes));
+  hipError_t e = hipMemset(d_probe, 0, bytes);
+  if (e == hipSuccess) e = hipMalloc(&d_row, (size_t)w * 4u);
+  if (e != hipSuccess) { (void)hipFree(d_probe); return fail(RT_ERR_DEVICE, "rt_test_probe: %s", hipGetErrorString(e)); }
+  const uint32_t ss = s->hd.supersample;
+  rt_tiles t = {1u, sy / ss, 1u, 1u};
+  rt_stats st;
+  g_probe.d_buf = d_probe; g_probe.x = sx; g_probe.y = sy;
+  rc = rt_render_tiles_device(s, w, h, &t, d_row, nullptr, flags & ~(uint32_t)RT_FLAG_RGB24, &st);
+  g_probe.d_buf = nullptr;
+  if (!rc) { e = hipMemcpy(out_records, d_probe, bytes, hipMemcpyDeviceToHost); if (e != hipSuccess) rc = fail(RT_ERR_DEVICE, "rt_test_probe: %s", hipGetErrorString(e)); }
+  (void)hipFree(d_probe); (void)hipFree(d_row);
+  return rc;
+}
+#endif
+
+extern "C" int rt_render_batch_device(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, uint32_t n_frames, void *d_out,
+                                      uint64_t frame_stride_bytes, void *hip_stream, uint32_t flags, rt_stats *stats) {
+  if (!d_out) return fail(RT_ERR_INVALID, "NULL scene, tiles or output");
+  return render_batch_impl(s, w, h, tiles, n_frames, d_out, frame_stride_bytes, nullptr, hip_stream, flags, stats);
+}
+
+extern "C" int rt_render_scatter_device(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, uint32_t n_frames, void *const *d_frames,
+                                        void *hip_stream, uint32_t flags, rt_stats *stats) {
+  if (!d_frames) return fail(RT_ERR_INVALID, "NULL frame pointer array");
+  if (n_frames == 0 || n_frames > RT_MAX_SCATTER) return fail(RT_ERR_INVALID, "scatter: n_frames %u not in 1..%u", n_frames, RT_MAX_SCATTER);
+  if (flags & RT_FLAG_RGB24) return fail(RT_ERR_INVALID, "scatter writes whole RGBA8 frames: RT_FLAG_RGB24 does not apply");
+  for (uint32_t f = 0; f < n_frames; f++) if (!d_frames[f] || ((uintptr_t)d_frames[f] & 3u)) return fail(RT_ERR_INVALID, "scatter: frame pointer %u is NULL or unaligned", f);
+  return render_batch_impl(s, w, h, tiles, n_frames, nullptr, 0u, d_frames, hip_stream, flags, stats);
+}
+
+namespace {
+// k x k box filter of the two-pass supersampling (k = 3, 4): `src` holds the rendered SAMPLES of this call's tiles as a band
+// (rows of k*w RGBA8 samples, k sample rows per output row, tiles contiguous), the output pixel is (sum + k*k/2) / (k*k) per
+// channel, alpha 255, stored where the trace kernel would have stored it: in the band (`out`, frame f at f*frame_stride) or,
+// scatter mode, at its row of the whole frame out_frames[f].  One work-item per output pixel; rows walked by grid y.
+struct rt_box_launch {
+  const uint32_t *src; uint64_t src_frame_stride;      // in samples (words)
+  uint32_t *out; uint64_t frame_stride; uint32_t *out_frames[RT_MAX_SCATTER]; uint32_t scatter;
+  uint32_t w, h, band_rows, tile_rows, tile_first, tile_stride;
+};
+template <uint32_t K>
+__global__ void __launch_bounds__(256) rt_box_filter_kernel(const rt_box_launch B) {
+  const uint32_t x = blockIdx.x * 256u + threadIdx.x, f = blockIdx.z;
+  if (x >= B.w) return;
+  const uint32_t *__restrict__ src = B.src + (size_t)f * B.src_frame_stride;
+  for (uint32_t lrow = blockIdx.y; lrow < B.band_rows; lrow += gridDim.y) {
+    const uint32_t tile_i = lrow / B.tile_rows, trow = lrow - tile_i * B.tile_rows;
+    const uint32_t frow = (B.tile_first + tile_i * B.tile_stride) * B.tile_rows + trow;
+    if (frow >= B.h) continue;
+    uint32_t r = 0, g = 0, b = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < K; j++) {
+      const uint32_t *__restrict__ p = src + ((size_t)lrow * K + j) * ((size_t)B.w * K) + (size_t)x * K;
+#pragma unroll
+      for (uint32_t i = 0; i < K; i++) { const uint32_t v = p[i]; r += v & 255u; g += (v >> 8) & 255u; b += (v >> 16) & 255u; }
+    }
+    const uint32_t px = ((r + K * K / 2u) / (K * K)) | (((g + K * K / 2u) / (K * K)) << 8) | (((b + K * K / 2u) / (K * K)) << 16) | 0xff000000u;
+    if (B.scatter) B.out_frames[f][(size_t)frow * B.w + x] = px;
+    else B.out[(size_t)f * B.frame_stride + (size_t)lrow * B.w + x] = px;
+  }
+}
+
+// supersample 3 and 4: the k*w x k*h sample frame of this call's tiles is rendered by the ordinary launch
+// (supersample 1 on the sample grid: same kernels, same centre-row/column rule, same tiles with k times the rows) into
+// scratch memory, in pieces of at most ~512 MiB, and box-filtered into the caller's output.
+int render_supersampled(rt_scene_dev *s, uint32_t k, uint32_t w, uint32_t h, const rt_tiles *tiles, uint32_t n_frames, void *d_out, uint64_t frame_stride_bytes,
+                        void *const *d_frames, hipStream_t stream, uint32_t flags, rt_stats *stats) {
+  if (flags & RT_FLAG_RGB24) return fail(RT_ERR_INVALID, "RT_FLAG_RGB24 needs supersample 1 or 2 (the %ux%u box filter stores RGBA8)", k, k);
+  if ((uint64_t)w * k > 65536u || (uint64_t)h * k > 65536u) return fail(RT_ERR_INVALID, "supersample %u: the %llu x %llu sample grid exceeds 65536", k, (unsigned long long)w * k, (unsigned long long)h * k);
+  const auto t_begin = std::chrono::steady_clock::now();
+  const size_t row_bytes = (size_t)w * k * 4u * k;                      // the k sample rows of one output row
+  const size_t budget = (size_t)512u << 20;
+  // pieces: whole tiles while they fit, else (one tile per call, starting on a multiple of the piece height) row pieces of a tile
+  uint32_t tiles_per_piece = (uint32_t)(budget / (row_bytes * tiles->tile_rows * (size_t)n_frames));
+  uint32_t piece_rows = tiles->tile_rows;
+  if (tiles_per_piece == 0) {
+    tiles_per_piece = 1;
+    piece_rows = (uint32_t)(budget / (row_bytes * n_frames)) / RT_TILE_H * RT_TILE_H;
+    if (piece_rows == 0) piece_rows = RT_TILE_H;
+    if (piece_rows >= tiles->tile_rows) piece_rows = tiles->tile_rows;
+    else if (tiles->n_tiles != 1 || ((uint64_t)tiles->tile_first * tiles->tile_rows) % piece_rows != 0)
+      return fail(RT_ERR_NOMEM, "supersample %u: a tile of %u rows needs more than 512 MiB of sample scratch; render smaller tiles", k, tiles->tile_rows);
+  }
+  rt_stats agg;
+  memset(&agg, 0, sizeof agg);
+  for (uint32_t t0 = 0; t0 < tiles->n_tiles; t0 += tiles_per_piece) {
+    const uint32_t nt = (tiles->n_tiles - t0 < tiles_per_piece) ? tiles->n_tiles - t0 : tiles_per_piece;
+    for (uint32_t r0 = 0; r0 < tiles->tile_rows; r0 += piece_rows) {
+      // this piece as a tile set of the OUTPUT frame ...
+      rt_tiles po;
+      if (piece_rows == tiles->tile_rows) po = rt_tiles{tiles->tile_rows, tiles->tile_first + t0 * tiles->tile_stride, tiles->tile_stride, nt};
+      else po = rt_tiles{piece_rows, (uint32_t)(((uint64_t)tiles->tile_first * tiles->tile_rows + r0) / piece_rows), 1u, 1u};
+      if ((uint64_t)po.tile_first * po.tile_rows >= h) continue;
+      // ... and of the sample frame
+      const rt_tiles ps = {po.tile_rows * k, po.tile_first, po.tile_stride, po.n_tiles};
+      const uint32_t band_rows = po.n_tiles * po.tile_rows;
+      const size_t frame_words = (size_t)band_rows * k * w * k;
+      void *scratch = nullptr;
+      hipError_t e = hipMalloc(&scratch, frame_words * 4u * n_frames);
+      if (e != hipSuccess) return fail(RT_ERR_NOMEM, "supersample scratch (%zu bytes): %s", frame_words * 4u * n_frames, hipGetErrorString(e));
+#ifdef RT_TESTING
+      (void)hipMemsetAsync(scratch, 0xA5, frame_words * 4u * n_frames, stream);      // test build: a sample nobody writes shows up as 0xA5, not as stale data
+#endif
+      rt_stats st;
+      int rc = render_batch_impl(s, w * k, h * k, &ps, n_frames, scratch, frame_words * 4u, nullptr, stream, flags, stats ? &st : nullptr, 1u);
+      if (!rc) {
+        rt_box_launch B;
+        memset(&B, 0, sizeof B);
+        B.src = (const uint32_t *)scratch; B.src_frame_stride = frame_words;
+        B.w = w; B.h = h; B.band_rows = band_rows; B.tile_rows = po.tile_rows; B.tile_first = po.tile_first; B.tile_stride = po.tile_stride;
+        const size_t out_row0 = (size_t)t0 * tiles->tile_rows + r0;            // this piece's first row in the caller's band
+        B.out = d_out ? (uint32_t *)d_out + out_row0 * w : nullptr; B.frame_stride = frame_stride_bytes / 4u;
+        B.scatter = d_frames ? 1u : 0u;
+        if (d_frames) for (uint32_t f = 0; f < n_frames; f++) B.out_frames[f] = (uint32_t *)d_frames[f];
+        const dim3 grid((w + 255u) / 256u, band_rows < 65535u ? band_rows : 65535u, n_frames), block(256);
+        if (k == 3u) hipLaunchKernelGGL(rt_box_filter_kernel<3u>, grid, block, 0, stream, B);
+        else hipLaunchKernelGGL(rt_box_filter_kernel<4u>, grid, block, 0, stream, B);
+        e = hipGetLastError();
+        if (e != hipSuccess) rc = fail(RT_ERR_DEVICE, "box filter launch: %s", hipGetErrorString(e));
+      }
+      (void)hipStreamSynchronize(stream);            // (a 9x / 16x render: the allocation and this wait are noise beside it)
+      e = hipFree(scratch);
+      if (rc) return rc;
+      if (e != hipSuccess) return fail(RT_ERR_DEVICE, "supersample scratch release: %s", hipGetErrorString(e));
+      if (stats) { agg.kernel_ms += st.kernel_ms; agg.rays += st.rays; agg.shadow_rays += st.shadow_rays; agg.sphere_tests += st.sphere_tests; }
+    }
+  }
+  if (stats) {
+    HIP_TRY(hipStreamSynchronize(stream));
+    agg.pixels = tile_set_pixels(w, h, tiles) * n_frames;
+    agg.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    *stats = agg;
+  }
+  return RT_OK;
+}
+
+int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, uint32_t n_frames, void *d_out, uint64_t frame_stride_bytes,
+                      void *const *d_frames, void *hip_stream, uint32_t flags, rt_stats *stats, uint32_t ss_override) {
+  if (!s || !tiles) return fail(RT_ERR_INVALID, "NULL scene, tiles or output");
+  if (n_frames == 0 || n_frames > 65535u) return fail(RT_ERR_INVALID, "n_frames %u not in 1..65535", n_frames);
+  if ((frame_stride_bytes & 3u) != 0) return fail(RT_ERR_INVALID, "frame stride must be a multiple of 4 bytes");
+  int rc = check_frame("render", w, h, tiles, flags);
+  if (rc) return rc;
+  if ((uint64_t)tiles->n_tiles * tiles->tile_rows * w >= (1ull << 32)) return fail(RT_ERR_INVALID, "a call may cover at most 2^32 - 1 pixels per frame");
+  if ((flags & (RT_FLAG_NO_SKY | RT_FLAG_SKY_ONLY)) == (RT_FLAG_NO_SKY | RT_FLAG_SKY_ONLY) || ((flags & (RT_FLAG_NO_SKY | RT_FLAG_SKY_ONLY)) && (flags & RT_FLAG_COUNT)))
+    return fail(RT_ERR_INVALID, "RT_FLAG_NO_SKY and RT_FLAG_SKY_ONLY exclude each other and RT_FLAG_COUNT");
+  if ((flags & RT_FLAG_COMPACT) && ((flags & (RT_FLAG_RGB24 | RT_FLAG_NO_SKY | RT_FLAG_COUNT | RT_FLAG_STRICT_FP)) != (RT_FLAG_RGB24 | RT_FLAG_NO_SKY) || d_frames))
+    return fail(RT_ERR_INVALID, "RT_FLAG_COMPACT goes with RT_FLAG_RGB24 | RT_FLAG_NO_SKY into a band (no counting, no strict kernel, no scatter)");
+  if ((rc = ensure_device(s->device))) return rc;
+  device_state &D = G.dev[s->device];
+  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : D.stream;
+  const auto t_begin = std::chrono::steady_clock::now();
+  uint32_t stars_seed;
+  {
+    // which streams the scene's launches run on (rt_scene_set_camera, dispatch_order), and: behind the last write of the camera block
+    std::lock_guard<std::mutex> lk(s->launch_mu);
+    stars_seed = s->hd.stars_seed;                     // (rt_scene_set_stars_seed: this launch's, whatever the next call sets)
+    if ((rc = behind_the_camera(s, stream))) return rc;
+    note_launch(s, stream);
+  }
+
+  const rt_scene_header &hd = s->hd;
+  const uint32_t ss = ss_override ? ss_override : hd.supersample;
+  if (ss > 2u) {
+    // (3x3 / 4x4 supersampling filters whole blocks of samples: a NO_SKY call stores every pixel, a SKY_ONLY call none)
+    if (flags & RT_FLAG_SKY_ONLY) { if (stats) memset(stats, 0, sizeof *stats); return RT_OK; }
+    return render_supersampled(s, ss, w, h, tiles, n_frames, d_out, frame_stride_bytes, d_frames, stream, flags & ~(uint32_t)RT_FLAG_NO_SKY, stats);
+  }
+  const bool ss2 = ss == 2u;
+  const bool count = (flags & RT_FLAG_COUNT) != 0;
+  const bool no_fixup = RT_TEST_ENV("RT_NO_FIXUP") != nullptr;                 // test build: the product kernel's own pixels everywhere (read per call)
+  const bool strict_main = (flags & RT_FLAG_STRICT_FP) != 0 || strict_scene(s);
+  const bool compact = (flags & RT_FLAG_COMPACT) != 0;
+  if (compact && (strict_main || ss > 2u)) return fail(RT_ERR_UNSUPPORTED, "RT_FLAG_COMPACT: this scene is rendered by the strict kernel (or supersampled 3x3 / 4x4), which knows no launch table: send plain bands");
+  const uint8_t *db = (const uint8_t *)s->d_blob;
+  static const bool no_grid = RT_TEST_ENV("RT_NO_SHADOW_GRID") != nullptr;     // A/B switches (test build only)
+  static const bool no_bounce = RT_TEST_ENV("RT_NO_BOUNCE_TABLE") != nullptr;
+  // RT_LDS_PAD (bytes): occupancy experiments only — extra dynamic LDS per workgroup caps the workgroups per CU
+  static const unsigned lds_pad = RT_TEST_ENV("RT_LDS_PAD") ? (unsigned)atoi(RT_TEST_ENV("RT_LDS_PAD")) : 0u;
+  rt_launch L;
+  memset(&L, 0, sizeof L);
+  // the part of the launch record that depends on the kernel: ordering B (enclosing sphere last, outside the loops) and the
+  // shadow grids / bounce table for the product kernel; the strict kernel and the counting variant walk the scene in its own
+  // order so that they stay literal / count what the reference counts
+  auto bind_kernel = [&](rt_launch &K, bool strict) {
+    const bool plain = strict || count;
+    const bool order_b = s->has_b && !plain;
+    const uint8_t *ob = obj_block(s);                 // this generation's spheres
+    const rt_geom *gt = (const rt_geom *)(ob + s->o_geom) + (order_b ? (size_t)hd.n_objects * (1 + hd.n_lights) : 0);      // [plain N | anchored at light k: NL x N]
+    const rt_geom *gc = (const rt_geom *)cam_block(s) + (order_b ? 2 * (size_t)hd.n_objects : 0);     // this camera's block: [anchored at the camera N | cull rectangles N]
+    K.objects = (const rt_sphere *)(ob + (order_b ? s->o_objs_b : s->o_objs));
+    K.geom = gt;
+    K.geom_cam = gc;
+    K.cull = gc + hd.n_objects;
+    K.geom_light = gt + hd.n_objects;
+    K.lds_image = lds_image_of(s) + (order_b ? s->lds_image_bytes : 0);
+    K.shadow_grid = (!plain && !no_grid && s->has_sg) ? ob + s->o_sg : nullptr;
+    K.bounce_table = (!plain && !no_bounce && s->has_bt) ? ob + s->o_bt : nullptr;
+    K.n_loop = order_b ? hd.n_objects - 1 : hd.n_objects;
+    K.enclosing = order_b ? hd.n_objects - 1 : ~0u;
+    K.enclosing_flat = (order_b && s->enclosing_flat) ? 1u : 0u;
+    K.cull_in_lds = s->cull_in_lds ? 1u : 0u;
+    K.sky_fast = (!plain && sky_fast(s)) ? 1u : 0u;
+    for (int c = 0; c < 3; c++) K.sky_rgb[c] = s->sky_rgb[c];
+    memcpy(K.miss_color, hd.miss_color, sizeof K.miss_color);
+    if (K.sky_fast && s->enclosing == ~0u) {
+      // no enclosing sphere at all: a primary ray that meets nothing is the miss colour (main.js:231), a constant as well
+      K.sky_fast = 1u;
+      memcpy(K.sky_rgb, hd.miss_color, sizeof K.sky_rgb);
+    } else if (K.sky_fast) {
+      // A flat sky of constant colour needs no hit record at all: "met nothing in the loops" IS "met the sky", whose pixel term
+      // is the constant the host evaluated - so for the product kernel that constant takes the place of the miss colour
+      // (main.js:231 is unreachable in such a scene: the sky encloses every ray) and the sphere leaves the kernel's view.
+      // Lanes that end on the sky then take the two-instruction miss branch, at every level of the ray tree.
+      K.enclosing = ~0u;
+      memcpy(K.miss_color, s->sky_rgb, sizeof K.miss_color);
+    }
+  };
+  bool four_waves = false;          // (rt_launch::four_waves: set below, once the launch knows whether it is a camera's first frame)
+  auto lds_for = [&](bool strict) {
+    // (the reflection-only many-sphere variants keep only the fold state in LDS: rt_kernel.hip, IMAGE_IN_LDS - and run one-wave
+    // workgroups, rt_device.h, unless they store through the peer-store path)
+    if (!strict && !count && !s->cull_in_lds && !s->refract)
+      return lds_pad + 10u * (rt_one_wave_workgroups(false, count != 0, s->refract, (d_frames != nullptr && !ss2) || four_waves) ? 64u : RT_WG_THREADS) * 8u;
+    if (!strict && rt_one_wave_workgroups(false, count != 0, s->refract, (d_frames != nullptr && !ss2) || four_waves)) return s->lds_bytes + lds_pad + 10u * 64u * 8u;
+    return s->lds_bytes + lds_pad + (!strict ? (s->refract ? 13u : 10u) * RT_WG_THREADS * 8u     // + the product kernels' fold state
+                                             : RT_WG_THREADS * 8u);                              //   (strict: one slot, the scatter store's tile)
+  };
+  bind_kernel(L, strict_main);
+  // the boundary test of the product kernel's samplers (rt_device.h)
+  L.flag_tol = s->flag_tol;
+  bool test_marks = false;               // test build: a switch that changes what is marked or re-traced - nothing is cached then
+#ifdef RT_TESTING
+  if (const char *fs = getenv("RT_FLAG_SCALE")) { L.flag_tol *= atof(fs); test_marks = true; }        // a wider boundary band, to exercise the second launch
+  if (getenv("RT_MARK_ALL") || getenv("RT_EXACT_ALL") || no_fixup) test_marks = true;
+#endif
+  L.mark_flags = (RT_TEST_ENV("RT_MARK_ALL") ? RT_MARK_ALL : 0u) | (no_fixup ? RT_MARK_NEVER : 0u) | (RT_TEST_ENV("RT_TEST_MARK_STRIPES") ? RT_MARK_ZERO : 0u) | (s->unit_weights ? RT_MARK_WEIGHT : 0u);
+  L.marks_cap = RT_MARKS_CAP;
+  L.stars_seed = stars_seed;
+  L.stars_step = (flags & RT_FLAG_STARS_PER_FRAME) ? 1u : 0u;
+  L.textures = s->d_texdesc;
+  L.texel_base = db;
+  L.out = (uint32_t *)d_out;
+  L.counters = D.d_counters;
+  memcpy(L.cam_origin, hd.cam_origin, 12 * sizeof(double));   // origin, axisX, axisY, axisZ are contiguous
+  const launch_geom geom = launch_geometry(hd.fov_deg, w, h, ss, tiles->tile_rows);
+  L.proj_w = geom.proj_w; L.proj_h = geom.proj_h; L.proj_d = geom.proj_d;
+  L.epsilon = hd.epsilon; L.light_intensity = hd.light_intensity;
+  L.n_objects = hd.n_objects; L.n_lights = hd.n_lights; L.segs = hd.segs;
+  L.w = w; L.h = h;
+  L.tile_rows = tiles->tile_rows; L.tile_first = tiles->tile_first; L.tile_stride = tiles->tile_stride; L.n_tiles = tiles->n_tiles;
+  L.tiles_x = geom.tiles_x;
+  memcpy(L.lights, s->lights, sizeof L.lights);
+  L.rb_per_tile = geom.rb_per_tile;
+  L.rb_shift = ~0u;
+  for (uint32_t b = 0; b < 31; b++) if (L.rb_per_tile == (1u << b)) L.rb_shift = b;
+  if ((uint64_t)tiles->n_tiles * L.rb_per_tile > 65535u) return fail(RT_ERR_INVALID, "%u tiles x %u row blocks exceed the grid's y limit (65535)", tiles->n_tiles, L.rb_per_tile);
+  L.n_frames = n_frames;
+  L.frame_stride = frame_stride_bytes / 4u;
+  L.rgb24 = (flags & RT_FLAG_RGB24) ? 1u : 0u;
+  L.compact = compact ? 1u : 0u;
+  L.scatter = d_frames ? 1u : 0u;
+  if (d_frames) for (uint32_t f = 0; f < n_frames; f++) L.out_frames[f] = (uint32_t *)d_frames[f];
+  for (int c = 0; c < 3; c++) L.cam_axis_sum[c] = hd.cam_axis_x[c] + hd.cam_axis_y[c] + hd.cam_axis_z[c];
+  L.ray_bias[0] = 0.5 - L.proj_w; L.ray_bias[1] = L.proj_h - 0.5; L.ray_bias[2] = L.cam_axis_sum[2] * L.proj_d;
+  if (count) HIP_TRY(hipMemsetAsync(D.d_counters, 0, 3 * sizeof(unsigned long long), stream));
+#ifdef RT_TESTING
+  L.probe = g_probe.d_buf; L.probe_x = g_probe.x; L.probe_y = g_probe.y;
+#endif
+
+  event_timer timer;                                     // (a stats call)
+  if (stats) HIP_TRY(timer.start(stream));
+  struct marks_guard {                                   // a per-call mark list is released on every way out, after the stream has drained
+    void *p = nullptr; hipStream_t st = nullptr;
+    ~marks_guard() { if (p) { (void)hipStreamSynchronize(st); (void)hipFree(p); } }
+  } temp_marks;
+  int err = 0;
+  uint32_t marks_read_slot = 0;
+  const uint32_t *marks_read = nullptr;                 // stats: where this launch's mark count can be read afterwards
+  uint64_t centre_items = 0;
+  bool retraced_all = false, overflowed_strict = false;
+  if (strict_main && (flags & RT_FLAG_SKY_ONLY)) {
+    // (the strict kernels know no sky blocks: the RT_FLAG_NO_SKY calls of such a launch store every pixel, this one none)
+  } else if (strict_main) {
+    std::lock_guard<std::mutex> lk(s->launch_mu);
+    if ((rc = guard_kernel_scratch(D, stream, true, false, s->refract, count, ss2, 0, false, (uint64_t)L.tiles_x * L.n_tiles * L.rb_per_tile * n_frames * (RT_WG_THREADS / 64u),
+                                   "the strict trace kernel"))) return rc;
+    err = rt_launch_trace_strict(&L, s->refract, count, ss2, lds_for(true), stream);
+  } else {
+    // ---- the product launch: its table (found, or built on the GPU for this camera), the trace, and - unless this frame is KNOWN
+    //      to have nothing for it - the list-driven strict launch behind it; one step for the threads of this process ----
+    std::lock_guard<std::mutex> lk(s->launch_mu);
+    const frame_kind kind = {w, h, ss, *tiles, sky_part_of(flags)};
+    const uint32_t uses_before = count ? 0u : count_use(s, kind);
+    // the first frame from a camera that has moved: a caller that moves the camera every frame has the next camera's table built
+    // beside this launch (rt_scene_set_camera), and that build needs the trace's workgroups to be as wide as its own (rt_launch::four_waves)
+    four_waves = !count && uses_before == 0u && s->cam_gen != 0u;
+    L.four_waves = four_waves ? 1u : 0u;
+    const int oi = dispatch_order(s, kind, choose_table(s, flags, uses_before), stream);
+    if (oi < 0) return RT_ERR_DEVICE;
+    rt_scene_dev::order_entry &oe = s->orders[oi];
+    L.order = oe.Tb[s->cam_gen & 1u].entries;
+    // one workgroup per table entry (runs of sky blocks share one).  How many there are is known on the device; until the build's
+    // count has reached the host, one workgroup per BLOCK is launched: those behind the last entry read a zero slot and leave
+    uint32_t n_known = known_value(oe.known, s->cam_gen);
+    // A table that rt_scene_set_camera is rebuilding on the side stream - beside the previous frame's trace - publishes its count
+    // while that trace is still running.  A caller that issues frames back to back arrives here earlier than that: it is given a
+    // short, BOUNDED wait for the word (it is ahead of the GPU anyway, and stays one frame ahead: the trace in flight has tens of
+    // microseconds left when the word arrives); one workgroup per block costs a 4K frame 80 us instead of 68.  A caller that comes
+    // later (a frame per display refresh) finds the word there; a word that does not come in time: one workgroup per block.
+    if (!n_known && oe.built_on == s->side && oe.cam_gen == s->cam_gen) {
+      // (the bound grows with the table: a 4K frame's build takes ~50 us beside a trace, an 8K frame's four times that)
+      static const long wait_env = RT_TEST_ENV("RT_COUNT_WAIT_US") ? atol(RT_TEST_ENV("RT_COUNT_WAIT_US")) : -1;       // A/B switch (test build)
+      const long wait_us = wait_env >= 0 ? wait_env : 100 + (long)(oe.n_blocks / 256u);
+      const auto t0 = std::chrono::steady_clock::now();
+      while (!n_known && std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() < wait_us) {
+        __builtin_ia32_pause();
+        n_known = known_value(oe.known, s->cam_gen);
+      }
+    }
+    L.order_n8 = (oe.n_blocks + 7u) / 8u;
+    L.grid_x = n_known ? n_known - 1u : oe.n_blocks;
+    L.grid_y = 1u;
+    rt_scene_dev::mark_state *ms = nullptr;
+    for (rt_scene_dev::mark_state &m : s->mark_states) if (m.order_index == (uint32_t)oi && m.stream == stream) ms = &m;
+    rt_scene_dev::mark_state temp_state = {~0u, stream, nullptr, nullptr, 0u};
+    if (!ms) {
+      // first launch of this (table, stream) pair: a list of its own (beyond RT_KNOWN_WORDS pairs: one per call, nothing cached)
+      const size_t bytes = 16u + (size_t)RT_MARKS_CAP * 8u;
+      uint32_t *d = nullptr;
+      hipError_t e = hipMalloc((void **)&d, bytes);
+      if (e == hipSuccess) e = hipMemsetAsync(d, 0, 16u, stream);
+      if (e != hipSuccess) { if (d) (void)hipFree(d); return fail(RT_ERR_DEVICE, "mark list: %s", hipGetErrorString(e)); }
+      if (s->mark_states.size() >= RT_KNOWN_WORDS) { temp_marks.p = d; temp_marks.st = stream; temp_state.d_marks = d; ms = &temp_state; }
+      else {
+        s->mark_states.push_back(rt_scene_dev::mark_state{(uint32_t)oi, stream, d, known_word(s, s->mark_states.size()), 0u});
+        ms = &s->mark_states.back();
+      }
+    }
+    L.marks = ms->d_marks; L.marks_slot = ms->slot;
+    const uint32_t known = test_marks ? 0u : known_value(ms->h_known, s->cam_gen);        // 0: not known (yet); else the frame's mark count + 1
+    // A frame KNOWN to mark more samples than the list holds (a legal scene can: every hit of a sphere whose sampler coordinate is
+    // an exact integer everywhere) would be traced twice in full, product kernel then rt_retrace over every sample: the strict
+    // kernel renders it once instead, the same bytes (the count stays known: nothing republishes it for this camera).
+    const bool overflow_known = known != 0u && known - 1u > RT_MARKS_CAP && !count && !compact;
+    if (overflow_known) {
+      if (!(flags & RT_FLAG_SKY_ONLY)) {              // (as every strict launch: a NO_SKY call stores every pixel, a SKY_ONLY call none)
+        rt_launch S = L;
+        S.order = nullptr; S.grid_x = S.grid_y = 0u;
+        bind_kernel(S, true);
+        if ((rc = guard_kernel_scratch(D, stream, true, false, s->refract, 0, ss2, 0, false, (uint64_t)L.tiles_x * L.n_tiles * L.rb_per_tile * n_frames * (RT_WG_THREADS / 64u),
+                                       "the strict trace kernel"))) return rc;
+        err = rt_launch_trace_strict(&S, s->refract, 0, ss2, lds_for(true), stream);
+        overflowed_strict = true;
+      }
+    } else {
+    if ((rc = guard_kernel_scratch(D, stream, false, false, s->refract, count, ss2, !count && !L.cull_in_lds,
+                                   rt_one_wave_workgroups(false, count != 0, s->refract, (L.scatter != 0u && !ss2) || four_waves),
+                                   (uint64_t)L.grid_x * n_frames * (RT_WG_THREADS / 64u), "the trace kernel"))) return rc;
+#ifdef RT_WAVE_LOG
+    // measurement build: RT_WAVE_LOG_FILE=<path> - every wave's entry / exit time and place of THIS launch, written after it has finished
+    unsigned long long *d_wave_log = nullptr;
+    const size_t wave_log_words = (size_t)((L.grid_x + 7u) / 8u * 8u) * n_frames * (RT_WG_THREADS / 64u) * 4u;
+    if (getenv("RT_WAVE_LOG_FILE")) {
+      if (hipMalloc((void **)&d_wave_log, wave_log_words * 8u) == hipSuccess) (void)hipMemsetAsync(d_wave_log, 0, wave_log_words * 8u, stream);
+      L.wave_log = d_wave_log;
+    }
+#endif
+    err = rt_launch_trace_fast(&L, s->refract, count, ss2, lds_for(false), stream);
+#ifdef RT_WAVE_LOG
+    if (d_wave_log) {
+      std::vector<unsigned long long> hostlog(wave_log_words);
+      (void)hipStreamSynchronize(stream);
+      (void)hipMemcpy(hostlog.data(), d_wave_log, wave_log_words * 8u, hipMemcpyDeviceToHost);
+      (void)hipFree(d_wave_log);
+      if (FILE *fp = fopen(getenv("RT_WAVE_LOG_FILE"), "wb")) { fwrite(hostlog.data(), 8u, wave_log_words, fp); fclose(fp); }
+      L.wave_log = nullptr;
+    }
+#endif
+    // Centre row / centre column of a sample grid with an ODD number of rows / columns (supersample 2 makes it even).  The primary
+    // rays there have a direction component that is EXACTLY zero (main.js:186: x - w/2 + 0.5 == 0), so they - and every ray they
+    // spawn that stays in that plane - live in a coordinate plane through the camera, and a sphere centred on that plane (the
+    // reference's own scene has several) is met with a normal component of exactly 0: u or v lands exactly ON a texel / checker
+    // boundary (main.js:127-130, 344-347), and on which side the reference falls is decided by whether ITS OWN rounding noise
+    // (e.g. main.js:257-259 at refract_index 1, where q is 0 or 1e-16 depending on the last bit of cosi) pushed the ray off the
+    // plane.  No arithmetic but the reference's own reproduces such coin flips: rt_retrace traces those samples too.
+    rt_launch F = L;
+    F.order = nullptr; F.grid_x = F.grid_y = 0u;
+    F.centre_row = F.centre_col = ~0u;
+    if (!ss2 && (h & 1u)) {
+      const uint32_t crow = (h - 1u) / 2u, tc = crow / tiles->tile_rows;
+      if (tc >= tiles->tile_first && (tc - tiles->tile_first) % tiles->tile_stride == 0 && (tc - tiles->tile_first) / tiles->tile_stride < tiles->n_tiles) { F.centre_row = crow; centre_items += (uint64_t)w * n_frames; }
+    }
+    if (!ss2 && (w & 1u)) { F.centre_col = (w - 1u) / 2u; centre_items += (uint64_t)tiles->n_tiles * tiles->tile_rows * n_frames; }
+    const bool retrace_all = RT_TEST_ENV("RT_EXACT_ALL") != nullptr && !no_fixup;
+    const bool need = !no_fixup && !(flags & RT_FLAG_SKY_ONLY) && (known != 1u || centre_items != 0 || retrace_all);     // (a sky-only launch traces nothing; the centre lines belong to the calls that trace)
+    if (err == 0 && need) {
+      bind_kernel(F, true);                             // the scene in its own order, every sphere in the loops, the reference's own miss colour
+      if (compact) {                                    // where a sample's block sits in the compact band: from the table's own arrays
+        const rt_table_dev &T = oe.Tb[s->cam_gen & 1u];
+        F.tb_item = T.item; F.tb_rank_in_row = T.rank_in_row; F.tb_row_hist = T.row_hist; F.tb_bin_start = T.bin_start; F.tb_bins = oe.cost_bins;
+      }
+      F.marks_known = test_marks ? nullptr : (unsigned long long *)ms->h_known;
+      F.known_tag = (uint32_t)s->cam_gen;
+      F.retrace_all = retrace_all ? 1u : 0u;
+      retraced_all = retrace_all;
+      // The grid.  Count known: its items and the centre lines.  Not known yet (the first frame from a camera): the list may hold up
+      // to RT_MARKS_CAP items or have overflowed - 256 workgroups (idle ones leave at once) walk an overflowed 3840x2160 frame at
+      // ~130 samples per lane, once; from the next frame on the count is known (and an overflow takes the strict kernel above).
+      uint64_t n_wg = (((known ? known - 1u : 0u) + centre_items) * (ss2 ? 4u : 1u) + RT_WG_THREADS - 1) / RT_WG_THREADS + 2u;      // (supersample 2: a lane per sample)
+      if (!known && n_wg < 256u) n_wg = 256u;
+      if (retrace_all) n_wg = ((uint64_t)tiles->n_tiles * tiles->tile_rows * w * n_frames + RT_WG_THREADS - 1) / RT_WG_THREADS;
+      if (n_wg > 8192u) n_wg = 8192u;
+      if ((rc = guard_kernel_scratch(D, stream, true, true, s->refract, 0, ss2, 0, false, n_wg * (RT_WG_THREADS / 64u), "the list-driven strict launch (rt_retrace)"))) return rc;
+      err = rt_launch_retrace(&F, s->refract, ss2, (unsigned)n_wg, stream);
+      marks_read = ms->d_marks; marks_read_slot = ms->slot;
+      ms->slot ^= 1u;                                   // rt_retrace cleared the other counter: the next launch's
+    }
+    }
+  }
+  if (err != 0) return fail(RT_ERR_DEVICE, "kernel launch: %s", hipGetErrorString((hipError_t)err));
+  if (stats) {
+    HIP_TRY(timer.stop(stream));
+    HIP_TRY(hipEventSynchronize(timer.b));
+    float ms = 0.f;
+    HIP_TRY(timer.elapsed(&ms));
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = ms;
+    stats->pixels = tile_set_pixels(w, h, tiles) * n_frames;
+    if (count) {
+      unsigned long long c[3];
+      HIP_TRY(hipMemcpy(c, D.d_counters, sizeof c, hipMemcpyDeviceToHost));
+      stats->rays = c[0]; stats->shadow_rays = c[1]; stats->sphere_tests = c[2];
+    }
+    // samples the second launch traced again: the marked ones (read back from the list's counter) and the odd grid's centre lines
+    if (overflowed_strict) stats->exact_samples = stats->pixels;      // the strict kernel rendered the call
+    if (marks_read) {
+      uint32_t n_marked = 0;
+      HIP_TRY(hipMemcpy(&n_marked, marks_read + marks_read_slot, sizeof n_marked, hipMemcpyDeviceToHost));
+      stats->exact_samples = (n_marked > RT_MARKS_CAP || retraced_all) ? stats->pixels : n_marked + centre_items;   // (list overflow / test build: every pixel of the call)
+    }
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
+}
+}  // namespace
+
+// ------------------------------------------------------------------------------------ compact bands (RT_FLAG_COMPACT)
+namespace {
+// The launch table a compact launch over `tiles` uses (found, or built now on `stream`), under launch_mu: its index in *oi, the rows
+// of a block in *rows_per_wg.  The product launch's own choice (choose_table) for a camera's first frame: masks do not matter for the
+// ORDER of the blocks - a table with and one without them list the same blocks at the same places.
+int compact_table(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, hipStream_t stream, int *oi, uint32_t *rows_per_wg) {
+  const uint32_t flags = RT_FLAG_RGB24 | RT_FLAG_NO_SKY | RT_FLAG_COMPACT;
+  if (!tiles) return fail(RT_ERR_INVALID, "compact band: NULL tiles");
+  if (int rc = check_frame("compact band", w, h, tiles, flags)) return rc;
+  const uint32_t ss = s->hd.supersample;
+  if (ss > 2u || strict_scene(s)) return fail(RT_ERR_UNSUPPORTED, "compact bands: this scene is rendered by the strict kernel (or supersampled 3x3 / 4x4): send plain bands");
+  if (int rc = behind_the_camera(s, stream)) return rc;
+  *rows_per_wg = launch_geometry(s->hd.fov_deg, w, h, ss, tiles->tile_rows).rows_per_wg;
+  *oi = dispatch_order(s, frame_kind{w, h, ss, *tiles, sky_part_of(flags)}, choose_table(s, flags, 0u), stream);
+  return *oi < 0 ? RT_ERR_DEVICE : RT_OK;
+}
+
+struct rt_expand_launch { const uint32_t *entries; uint32_t n8, n_blocks, w, rows_per_wg; const uint8_t *src; uint32_t *dst; };
+// one workgroup of 256 per entry: the block's 32 x RH pixels (RGB24, row by row) to their place in the RGBA8 frame
+__global__ void __launch_bounds__(256) rt_compact_expand_kernel(const rt_expand_launch E) {
+  const uint32_t b = blockIdx.x;
+  const uint4 e = ((const uint4 *)E.entries)[(size_t)(b & 7u) * E.n8 + (b >> 3)];
+  const uint32_t tile_x = e.x & 2047u, rows_valid = (e.x >> 11) & 15u, frow0 = e.x >> 15;
+  if (rows_valid == 0u || (e.y >> 31)) return;                     // (no entry, or a sky run: not part of a compact band)
+  const uint32_t r = threadIdx.x >> 5, i = threadIdx.x & 31u, px = tile_x * RT_TILE_W + i;
+  if (r >= rows_valid || r >= E.rows_per_wg || px >= E.w) return;
+  const uint8_t *p = E.src + (size_t)b * (RT_TILE_W * 3u * E.rows_per_wg) + ((size_t)r * RT_TILE_W + i) * 3u;
+  E.dst[(size_t)(frow0 + r) * E.w + px] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | 0xff000000u;
+}
+}  // namespace
+
+extern "C" int rt_compact_count(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, void *hip_stream, uint32_t *n_blocks, uint32_t *block_bytes) {
+  if (!n_blocks || !block_bytes) return fail(RT_ERR_INVALID, "rt_compact_count: NULL argument");
+  int rc = s ? ensure_device(s->device) : RT_ERR_INVALID;
+  if (rc) return rc == RT_ERR_INVALID ? fail(RT_ERR_INVALID, "NULL scene") : rc;
+  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream;
+  uint32_t rows_per_wg = 0, header[4];
+  const uint32_t *d_header = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(s->launch_mu);
+    int oi = -1;
+    if ((rc = compact_table(s, w, h, tiles, stream, &oi, &rows_per_wg))) return rc;
+    d_header = s->orders[oi].Tb[s->cam_gen & 1u].header;
+  }
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipMemcpy(header, d_header, sizeof header, hipMemcpyDeviceToHost));
+  *n_blocks = header[2];                                             // the entries in front of the sky runs' class: a ranked table's non-sky blocks
+  *block_bytes = RT_TILE_W * 3u * rows_per_wg;
+  return RT_OK;
+}
+
+extern "C" int rt_compact_expand_device(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, const void *d_compact, void *d_frame, void *hip_stream) {
+  if (!d_compact || !d_frame || ((uintptr_t)d_frame & 3u)) return fail(RT_ERR_INVALID, "rt_compact_expand_device: NULL or unaligned buffer");
+  int rc = s ? ensure_device(s->device) : RT_ERR_INVALID;
+  if (rc) return rc == RT_ERR_INVALID ? fail(RT_ERR_INVALID, "NULL scene") : rc;
+  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream;
+  rt_expand_launch E;
+  uint32_t grid = 0;
+  {
+    std::lock_guard<std::mutex> lk(s->launch_mu);
+    uint32_t rows_per_wg = 0;
+    int oi = -1;
+    if ((rc = compact_table(s, w, h, tiles, stream, &oi, &rows_per_wg))) return rc;
+    const rt_scene_dev::order_entry &oe = s->orders[oi];
+    E.entries = oe.Tb[s->cam_gen & 1u].entries; E.n8 = (oe.n_blocks + 7u) / 8u; E.n_blocks = oe.n_blocks; E.w = w; E.rows_per_wg = rows_per_wg;
+    E.src = (const uint8_t *)d_compact; E.dst = (uint32_t *)d_frame;
+    const uint32_t n_known = known_value(oe.known, s->cam_gen);
+    grid = n_known ? n_known - 1u : oe.n_blocks;                     // (workgroups behind the last entry read a zero slot and leave)
+    note_launch(s, stream);
+  }
+  if (grid) hipLaunchKernelGGL(rt_compact_expand_kernel, dim3(grid), dim3(256), 0, stream, E);
+  HIP_TRY(hipGetLastError());
+  return RT_OK;
+}
+
+// ------------------------------------------------------------------------------------ primary hits (rt_hits.hip)
+// What is under a sample: the hit kernels read the sphere records of the scene's current generation (its object block: an object move
+// writes the other one, rt_scene_set_objects) and take the camera from the scene's host state at the call.  So they come behind the
+// generation's preparation on the side stream, like a colour launch, and count as launches of the scene for the next move's events.
+namespace rt_api {
+int hits_frame_check(uint32_t w, uint32_t h, uint32_t k, const char *what) {
+  if (int rc = check_frame(what, w, h, nullptr, 0u)) return rc;
+  if ((uint64_t)k * w * k * h >= (1ull << 32)) return fail(RT_ERR_INVALID, "%s: a sample grid of %ux%u exceeds 2^32 - 1 samples", what, k * w, k * h);
+  return RT_OK;
+}
+
+int pick_points_check(uint32_t w, uint32_t h, uint32_t k, uint32_t n, const uint32_t *xy, const void *out, const char *what) {
+  if (!xy || !out) return fail(RT_ERR_INVALID, "%s: NULL points or output", what);
+  if (n == 0 || n > 65536u) return fail(RT_ERR_INVALID, "%s: n %u not in 1..65536", what, n);
+  int rc = hits_frame_check(w, h, k, what);
+  if (rc) return rc;
+  for (uint32_t j = 0; j < n; j++)
+    if (xy[2 * j] >= k * w || xy[2 * j + 1] >= k * h)
+      return fail(RT_ERR_INVALID, "%s: point %u (%u, %u) lies outside the %ux%u sample grid", what, j, xy[2 * j], xy[2 * j + 1], k * w, k * h);
+  return RT_OK;
+}
+
+// the launch record's scene part: blob-order spheres, the CURRENT camera, the projection of the k w x k h sample grid
+int hits_bind(rt_scene_dev *s, uint32_t w, uint32_t h, rt_hits_launch &L, hipStream_t stream) {
+  memset(&L, 0, sizeof L);
+  std::lock_guard<std::mutex> lk(s->launch_mu);
+  if (int rc = behind_the_camera(s, stream)) return rc;
+  note_launch(s, stream);
+  const rt_scene_header &hd = s->hd;
+  L.objects = (const rt_sphere *)(obj_block(s) + s->o_objs);
+  memcpy(L.cam, hd.cam_origin, 12 * sizeof(double));   // origin, axisX, axisY, axisZ are contiguous
+  L.k = hd.supersample;
+  L.sw = L.k * w; L.sh = L.k * h;
+  const launch_geom g = launch_geometry(hd.fov_deg, w, h, L.k, 0u);
+  L.proj_w = g.proj_w; L.proj_h = g.proj_h; L.proj_d = g.proj_d;
+  L.epsilon = hd.epsilon;
+  L.n_objects = hd.n_objects;
+  return RT_OK;
+}
+}  // namespace rt_api
+
+extern "C" int rt_render_hits_device(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, const rt_hit_buffers *b, void *hip_stream,
+                                     rt_stats *stats) {
+  if (!s) return fail(RT_ERR_STATE, "rt_render_hits_device: NULL scene handle");
+  if (!tiles || !b) return fail(RT_ERR_INVALID, "rt_render_hits_device: NULL tiles or buffers");
+  int rc = hits_frame_check(w, h, s->hd.supersample, "rt_render_hits_device");
+  if (rc) return rc;
+  if ((rc = check_frame("rt_render_hits_device", w, h, tiles, 0u))) return rc;
+  if (((uintptr_t)b->id & 3u) || ((uintptr_t)b->depth & 7u) || ((uintptr_t)b->normal & 3u))
+    return fail(RT_ERR_INVALID, "rt_render_hits_device: misaligned buffer (id and normal need 4 bytes, depth 8)");
+  if ((rc = ensure_device(s->device))) return rc;
+  device_state &D = G.dev[s->device];
+  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : D.stream;
+  const auto t_begin = std::chrono::steady_clock::now();
+  rt_hits_launch L;
+  if ((rc = hits_bind(s, w, h, L, stream))) return rc;
+  L.id = b->id; L.depth = b->depth; L.normal = b->normal;
+  L.tile_rows = tiles->tile_rows; L.tile_first = tiles->tile_first; L.tile_stride = tiles->tile_stride;
+  L.band_rows = tiles->n_tiles * L.k * tiles->tile_rows;
+  event_timer timer;                                     // (a stats call)
+  if (stats) HIP_TRY(timer.start(stream));
+  if (L.id || L.depth || L.normal) {
+    const int e = rt_launch_hits(&L, stream);
+    if (e != 0) return fail(RT_ERR_DEVICE, "hits kernel launch: %s", hipGetErrorString((hipError_t)e));
+  }
+  if (stats) {
+    HIP_TRY(timer.stop(stream));
+    HIP_TRY(hipEventSynchronize(timer.b));
+    float ms = 0.f;
+    HIP_TRY(timer.elapsed(&ms));
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = ms;
+    stats->pixels = tile_set_pixels(w, h, tiles);
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
+}
+
+extern "C" int rt_scene_pick(rt_scene_dev *s, uint32_t w, uint32_t h, uint32_t n, const uint32_t *xy, rt_hit *out) {
+  if (!s) return fail(RT_ERR_STATE, "rt_scene_pick: NULL scene handle");
+  int rc = pick_points_check(w, h, s->hd.supersample, n, xy, out, "rt_scene_pick");
+  if (rc) return rc;
+  if ((rc = ensure_device(s->device))) return rc;
+  device_state &D = G.dev[s->device];
+  rt_hits_launch L;
+  if ((rc = hits_bind(s, w, h, L, D.stream))) return rc;
+  L.n_points = n;
+  struct device_mem { void *p = nullptr; ~device_mem() { if (p) (void)hipFree(p); } } mem;
+  HIP_TRY(hipMalloc(&mem.p, (size_t)n * (sizeof(rt_hit) + 2u * sizeof(uint32_t))));
+  L.hits = (rt_hit *)mem.p;
+  L.points = (const uint32_t *)((uint8_t *)mem.p + (size_t)n * sizeof(rt_hit));
+  HIP_TRY(hipMemcpyAsync((void *)L.points, xy, (size_t)n * 2u * sizeof(uint32_t), hipMemcpyHostToDevice, D.stream));
+  const int e = rt_launch_pick(&L, D.stream);
+  if (e != 0) return fail(RT_ERR_DEVICE, "pick kernel launch: %s", hipGetErrorString((hipError_t)e));
+  HIP_TRY(hipMemcpyAsync(out, L.hits, (size_t)n * sizeof(rt_hit), hipMemcpyDeviceToHost, D.stream));
+  HIP_TRY(hipStreamSynchronize(D.stream));
+  return RT_OK;
+}

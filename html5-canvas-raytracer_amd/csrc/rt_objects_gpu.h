@@ -1,4 +1,4 @@
-// rt_objects_gpu.h — the device-side rebuild of a resident scene's sphere tables (rt_objects_gpu.hip), as rt_api.hip drives it.
+// rt_objects_gpu.h — the device-side rebuild of a resident scene's sphere tables (rt_objects_gpu.hip), as rt_scene.hip drives it.
 #ifndef RT_OBJECTS_GPU_H
 #define RT_OBJECTS_GPU_H
 

@@ -1,4 +1,4 @@
-// rt_objects_gpu.hip — the sphere tables of a resident scene rebuilt ON THE GPU after rt_scene_set_objects (rt_api.hip): the copy
+// rt_objects_gpu.hip — the sphere tables of a resident scene rebuilt ON THE GPU after rt_scene_set_objects (rt_scene.hip): the copy
 // of the host-written part of an object move, the bounce table and the shadow grids' masks.  rt_tables.cpp builds the same tables on
 // the host (rt_scene_upload, and the tests' oracle); both use the per-element arithmetic of rt_objects.h.  Compiled without FMA
 // contraction, like rt_tables.cpp: both builds state the same words.

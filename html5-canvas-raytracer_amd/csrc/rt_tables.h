@@ -1,4 +1,4 @@
-// rt_tables.h — host-built tables of a scene (pure host logic, rt_tables.cpp); shared by rt_api.hip only.
+// rt_tables.h — host-built tables of a scene (pure host logic, rt_tables.cpp); shared by the host units of the C ABI (rt_api_internal.h) only.
 #ifndef RT_TABLES_H
 #define RT_TABLES_H
 

@@ -1,4 +1,4 @@
-// rt_tables_gpu.h — the device-side build of the launch table (rt_tables_gpu.hip), as rt_api.hip drives it.
+// rt_tables_gpu.h — the device-side build of the launch table (rt_tables_gpu.hip), as rt_scene.hip drives it.
 #ifndef RT_TABLES_GPU_H
 #define RT_TABLES_GPU_H
 

@@ -1,4 +1,4 @@
-// rt_tables_gpu.hip — the product kernel's launch table, built ON THE GPU (what rt_api.hip: dispatch_order runs; rt_tables.cpp's
+// rt_tables_gpu.hip — the product kernel's launch table, built ON THE GPU (what rt_scene.hip: dispatch_order runs; rt_tables.cpp's
 // build_launch_table is the same table built on the host: the CPU tests' oracle and the -m gpu test that compares the two).
 //
 // The reference recomputes everything on every redraw() (main.js:180-201) and its camera is a parameter (lookAt, main.js:92-100).

@@ -249,7 +249,7 @@ def main():
                         tot[name]["sky_part_mismatches"] = tot[name].get("sky_part_mismatches", 0) + 1
                 if name == "fma" and len(scene["objects"]) > 16:
                     # many spheres: the first frame from a camera comes from a launch table without shadow masks, the second from the full
-                    # table (rt_api.hip: renders_with_camera) - the second is the one compared below, and the two must be the same bytes
+                    # table (rt_scene.hip: camera_uses) - the second is the one compared below, and the two must be the same bytes
                     first = host.raw
                     r.render_tiles(w, h, d, tiles, flags=flags, want_stats=True)
                     assert lib.rt_copy_to_host(0, host, d, n_px * 4) == 0

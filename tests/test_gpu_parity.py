@@ -1339,7 +1339,7 @@ def test_rt_render_hands_the_frame_over_the_same_bytes_every_way(lib):
 def test_the_first_frame_from_a_camera_and_the_later_ones_are_the_same_picture(lib, scene, w, h):
     """Many-sphere scenes (more than 16 spheres in the loops) render the FIRST frame from a camera with a launch table without shadow
     masks - the masks cost the table build ten times what they save one frame - and get the full table with the second frame
-    (rt_api.hip: renders_with_camera).  Masks only prune tests that cannot succeed: first, second and third frame are the same bytes,
+    (rt_scene.hip: camera_uses).  Masks only prune tests that cannot succeed: first, second and third frame are the same bytes,
     before and after a camera move, and within 1 LSB of the C restatement's rows."""
     if scene.startswith("many:"):
         import soak_gpu_parity as soak

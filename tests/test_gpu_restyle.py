@@ -1,5 +1,5 @@
 """Restyling the spheres of a resident scene on the GPU (include/rt_hip.h: rt_scene_set_objects) in the ways that change the host's
-decisions (rt_api.hip: object_decisions, camera_decisions): the kernel variant (refraction), strict-kernel routing, the samplers'
+decisions (rt_scene.hip: object_decisions, camera_decisions): the kernel variant (refraction), strict-kernel routing, the samplers'
 boundary tolerance, the mark-weight rule, the enclosing sphere's background, the bounce table's used rows, radii (also degenerate
 ones), a camera inside a moved sphere and every texture index of a scene with sixteen textures of odd shapes.  Each edit goes
 A -> B -> A.  The yardsticks: a fresh upload of the edited blob (every sphere-dependent region, the launch table, FAST and STRICT
