@@ -50,9 +50,18 @@ struct rt_mtl {
   double albedo[5];
   double specular_exponent;
   double refract_index;
-  int32_t sampler_kind, texture;
+  int16_t sampler_kind, texture;     // RT_SAMPLER_*; texture index (< RT_MAX_TEXTURES) of a texture sampler, else -1
+  int32_t spec_n;                    // specular_exponent as an integer 0..65536 where it is one, else RT_SPEC_GENERIC (rt_spec_n)
   double c[8];                       // colour: c[0..2] = mtl.color; checker: c[0..5] = its two colours, c[6..7] = its frequencies;
 };                                   // stars: c[6..7] = threshold and gain (rt_sphere.checker_freq)
+static_assert(sizeof(rt_mtl) == 160, "rt_mtl: the LDS image is staged in 16-byte units");
+
+// The product kernel's specular power (rt_kernel.hip: rt_pow_spec) takes integer exponents by square-and-multiply and the rest
+// through OCML's pow.  The host decides which, once per material: n with (double)n == e and 0 <= n <= 65536, or the sentinel.
+#define RT_SPEC_GENERIC (-1)
+static inline int32_t rt_spec_n(double e) {
+  return (e >= 0.0 && e <= 65536.0 && (double)(int32_t)e == e) ? (int32_t)e : RT_SPEC_GENERIC;
+}
 
 // Everything one launch needs, passed by value in the kernarg segment (scalar-loaded into
 // SGPRs: all of it is wave-uniform).

@@ -144,17 +144,36 @@ __device__ __forceinline__ double rt_div_const(double a, double c, double rc) {
 // Non-integer exponents (none in the reference scene) take OCML's pow out of line, so that its ~40
 // temporaries are not part of the register budget of the loop every pixel runs.
 __device__ __attribute__((noinline)) double rt_pow_generic(double x, double e) { return pow(x, e); }
-// x > 0.  Integer exponents (every specular_exponent of the reference scene, main.js:108-123) by
-// square-and-multiply: <= 2*log2(e) multiplies instead of OCML's ~150-instruction pow.
-__device__ __forceinline__ double rt_pow(double x, double e) {
-  const int n = (int)e;
-  if ((double)n == e && n >= 0 && n <= 65536) {
-    double r = 1.0, b = x;
-    unsigned k = (unsigned)n;
-    while (k) { if (k & 1u) r *= b; b *= b; k >>= 1; }
+// x^e, x > 0, of a material whose exponent e (read through `e` only when it is needed) the host classified as n = rt_spec_n(e).
+// Integer exponents (every specular_exponent of the reference scene, main.js:108-123) by square-and-multiply: <= 2*log2(n)
+// multiplies instead of OCML's ~150-instruction pow.  Every path multiplies in the same sequence - for bit i = 0, 1, ...: r *= b
+// where bit i is set, b *= b - with r = b standing for the first r = 1.0 * b (exact), so the result does not depend on the path.
+__device__ __forceinline__ double rt_pow_spec(double x, int32_t n, const double *e) {
+  const int32_t n0 = __builtin_amdgcn_readfirstlane(n);
+  if (__ballot(n != n0) == 0ull) {
+    // every lane here has the same exponent (a wave on one sphere: nearly all of them): walk its bits with scalar control
+    if (n0 < 0) return rt_pow_generic(x, *e);
+    // from set bit to set bit (the multiplies are unconditional: no select per bit)
+    uint32_t k = (uint32_t)n0;
+    if (k == 0u) return 1.0;
+    double b = x;
+    uint32_t g = __builtin_ctz(k);
+    for (uint32_t i = 0; i < g; i++) b *= b;
+    double r = b;
+    for (k >>= g + 1u; k != 0u; k >>= g + 1u) {
+      g = __builtin_ctz(k);
+      for (uint32_t i = 0; i <= g; i++) b *= b;
+      r *= b;
+    }
     return r;
   }
-  return rt_pow_generic(x, e);
+  // several exponents (silhouettes, bounce nodes on different spheres): per lane, for as many bits as the longest exponent among
+  // the lanes has - the loop's exit is wave-uniform, so no lane leaves it on its own
+  if (n < 0) return rt_pow_generic(x, *e);
+  double r = 1.0, b = x;
+  uint32_t k = (uint32_t)n;
+  do { if (k & 1u) r *= b; b *= b; k >>= 1; } while (__ballot(k != 0u) != 0ull);
+  return r;
 }
 // main.js:62-66 — v * (1/len), len = sqrt(v.v); the zero vector is returned unchanged
 __device__ __forceinline__ v3 unit(const v3 v, double *len_out) {
@@ -1130,13 +1149,14 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
 #if !RT_STRICT
               // (materials in HBM - the reflection-only many-sphere variants -: the record's address is derived again here, from the hit
               // code, so that no 64-bit pointer lives across the shadow scans)
-              double spec_e;
+              const rt_mtl *spec_m = &m;
               if constexpr (GRID && !REFRACT && !COUNT) {
                 uint32_t off_ = (uint32_t)hi * (uint32_t)sizeof(rt_mtl);
                 asm volatile("" : "+v"(off_));
-                spec_e = ((const rt_mtl *)((const char *)mtl + off_))->specular_exponent;
-              } else spec_e = m.specular_exponent;
-              if (spd > 0.0) specular += rt_pow(spd, spec_e);
+                spec_m = (const rt_mtl *)((const char *)mtl + off_);
+              }
+              const int32_t spec_n = spec_m->spec_n;
+              if (spd > 0.0) specular += rt_pow_spec(spd, spec_n, &spec_m->specular_exponent);
 #else
               if (spd > 0.0) specular += rt_pow(spd, m.specular_exponent);
 #endif

@@ -93,7 +93,8 @@ void fill_lds_image(const rt_scene_dev *s, uint8_t *dst, int ord) {
     m.inv_r = o.reserved;                           // 1/r, patched at upload
     memcpy(m.albedo, o.albedo, sizeof m.albedo);
     m.specular_exponent = o.specular_exponent; m.refract_index = o.refract_index;
-    m.sampler_kind = o.sampler_kind; m.texture = o.texture;
+    m.spec_n = rt_spec_n(o.specular_exponent);
+    m.sampler_kind = (int16_t)o.sampler_kind; m.texture = (int16_t)(o.sampler_kind == RT_SAMPLER_TEXTURE ? o.texture : -1);   // (check_sphere: 0..3, < RT_MAX_TEXTURES)
     if (o.sampler_kind == RT_SAMPLER_CHECKER) memcpy(m.c, o.checker_color, 6 * sizeof(double));
     else memcpy(m.c, o.color, 3 * sizeof(double));
     m.c[6] = o.checker_freq[0]; m.c[7] = o.checker_freq[1];

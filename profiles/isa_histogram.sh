@@ -1,17 +1,18 @@
 #!/bin/bash
 # Static ISA histogram (instructions by mnemonic) of one rt_trace instantiation of the product build, from the code object.
-#   bash profiles/isa_histogram.sh [REFRACT COUNT SS2 GRID]      default 0 0 0 0 = the headline kernel
+#   bash profiles/isa_histogram.sh [REFRACT COUNT SS2 GRID [W1]]      no flags: 0 0 0 0 1 = the headline kernel; W1 defaults to 0 otherwise
+#   OBJ=build/ab/rt_kernel_fast_<name>.o bash profiles/isa_histogram.sh ...     the kernel object of an A/B build (profiles/ab_build.sh)
 set -e
 B=/opt/rocm/lib/llvm/bin
-R=${1:-0}; C=${2:-0}; S=${3:-0}; G=${4:-0}
-OBJ=$(dirname "$0")/../html5-canvas-raytracer_amd/csrc/rt_kernel_fast.o
+R=${1:-0}; C=${2:-0}; S=${3:-0}; G=${4:-0}; W=${5:-$([ $# -eq 0 ] && echo 1 || echo 0)}
+OBJ=${OBJ:-$(dirname "$0")/../html5-canvas-raytracer_amd/csrc/rt_kernel_fast.o}
 T=$(mktemp -d)
 $B/llvm-objcopy --dump-section .hip_fatbin=$T/k.bin "$OBJ"
 $B/clang-offload-bundler --unbundle --type=o --input=$T/k.bin --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=$T/k.co
 $B/llvm-objdump -d $T/k.co > $T/k.s
-SYM="rt_traceILb${R}ELb${C}ELb${S}ELb${G}E"
+SYM="rt_traceILb${R}ELb${C}ELb${S}ELb${G}ELb${W}E"
 awk -v sym="$SYM" '$0 ~ sym && /^[0-9a-f]+ </ {f=1; next} f && /^[0-9a-f]+ </ {exit} f {print}' $T/k.s | awk 'NF && $1 !~ /:$/ {print $1}' > $T/m.txt
-echo "rt_trace<$R,$C,$S,$G> (product build, gfx950): $(wc -l < $T/m.txt) instructions (static; dynamic counts: the SQ_INSTS_* counters in the rocprof summaries)"
+echo "rt_trace<$R,$C,$S,$G,$W> (product build, gfx950): $(wc -l < $T/m.txt) instructions (static; dynamic counts: the SQ_INSTS_* counters in the rocprof summaries)"
 python3 - "$T/m.txt" <<'PY'
 import sys, collections
 m = [l.strip() for l in open(sys.argv[1]) if l.strip()]
