@@ -34,6 +34,8 @@ extern "C" int rt_launch_retrace(const rt_launch *, int, int, unsigned, hipStrea
 extern "C" int rt_scratch_trace_fast(int, int, int, int, int, size_t *);
 extern "C" int rt_scratch_trace_strict(int, int, int, int, int, size_t *);
 extern "C" int rt_scratch_retrace(int, int, size_t *);
+extern "C" int rt_launch_trace_rays(const rt_launch *, int, unsigned, hipStream_t);
+extern "C" int rt_scratch_trace_rays(int, size_t *);
 
 using namespace rt_tables;   // the host-built tables (pure host logic, rt_tables.cpp)
 
@@ -275,6 +277,10 @@ int dispatch_order(rt_scene_dev *s, const frame_kind &kind, const table_choice &
 // rt_launch.hip: argument checks of the hit entry points
 int hits_frame_check(uint32_t w, uint32_t h, uint32_t k, const char *what);
 int pick_points_check(uint32_t w, uint32_t h, uint32_t k, uint32_t n, const uint32_t *xy, const void *out, const char *what);
+// ... and of the ray entry points; the launch of rays [base, base + n) of a caller's list (device pointers to THOSE rays and their outputs)
+int rays_check(uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *out, const char *what);
+int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *d_rays, uint32_t segs, const rt_ray_outputs &out, hipStream_t stream,
+                      rt_stats *stats);
 
 // rt_frame.hip: RCCL's communicators are destroyed (rt_shutdown)
 void release_rccl();

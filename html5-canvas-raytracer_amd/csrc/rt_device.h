@@ -138,6 +138,12 @@ struct rt_launch {
                                      // workgroups (rt_one_wave_workgroups): the first frame from a new camera, beside which the NEXT camera's launch
                                      // table may be built (rt_scene_set_camera) - one-wave workgroups take every slot the moment it frees, and the
                                      // build's four-wave workgroups would wait for the trace to drain
+  // rt_trace_rays only (rt_scene_trace_rays_device): caller-supplied rays instead of a camera's.  `segs` above is the CALL's depth there
+  const double *rays;                // n_rays records {org[3], dir[3]}, 16-byte aligned: ray j of the launch is ray ray_base + j of the caller's list
+  double *ray_rgb;                   // 3 per ray: intersectWorld's return value, or NULL
+  uint32_t *ray_rgba;                // 1 per ray: the RGBA8 store of 255 * rgb, or NULL
+  uint32_t n_rays;                   // < 2^31
+  uint32_t ray_base;                 // the stars sampler's pix of the launch's first ray (the host form's chunks; ray_base + n_rays <= 2^31)
 #ifdef RT_WAVE_LOG
   // measurement builds only (profiles/ab_build.sh ... "-DRT_WAVE_LOG" hybrid; profiles/wave_timeline.py): per wave of the product launch
   // four words {s_memrealtime at entry, at exit, HW_ID | XCC_ID << 32, workgroup}; NULL = off

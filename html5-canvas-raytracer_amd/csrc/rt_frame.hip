@@ -1,4 +1,4 @@
-// rt_frame.hip — rt_render(width, height, scene) and its kin (rt_render_progressive, rt_render_hits, rt_pick): the resident scene
+// rt_frame.hip — rt_render(width, height, scene) and its kin (rt_render_progressive, rt_render_hits, rt_pick, rt_trace_rays): the resident scene
 // per device (scene_for), the one-GPU plans (banded copy-out, stores straight into a pinned frame) and the single-process multi-GPU
 // frame (interleaved row tiles stored straight into GPU 0's frame over xGMI; fallback: RGB24 bands + one RCCL gather + de-interleave).
 
@@ -249,6 +249,46 @@ extern "C" int rt_pick(const void *blob, size_t bytes, uint32_t w, uint32_t h, u
   rt_scene_dev *s = nullptr;
   if ((rc = scene_for(0, blob, bytes, &s))) return rc;
   return rt_scene_pick(s, w, h, n, xy, out);
+}
+
+// intersectWorld for a list of rays in host memory, with rt_render's resident scene: chunks of RT_RAY_CHUNK rays go through one set of
+// device buffers (ray i of the list keeps pix = i: the chunk's base travels in the launch record), so the device memory of a call does
+// not grow with n.  Synchronous; kernel_ms is the sum over the chunks.
+#define RT_RAY_CHUNK (1u << 18)
+extern "C" int rt_trace_rays(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *ho, rt_stats *stats) {
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  if ((rc = rays_check(n, rays, segs, ho, "rt_trace_rays"))) return rc;
+  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
+  std::lock_guard<std::mutex> lk(G.mu);
+  const auto t_begin = std::chrono::steady_clock::now();
+  rt_scene_dev *s = nullptr;
+  if ((rc = scene_for(0, blob, bytes, &s))) return rc;
+  if ((rc = ensure_device(0))) return rc;
+  device_state &D = G.dev[0];
+  const size_t chunk = n < RT_RAY_CHUNK ? (size_t)n : RT_RAY_CHUNK;
+  struct device_bufs { void *p[4] = {nullptr, nullptr, nullptr, nullptr}; ~device_bufs() { for (void *q : p) if (q) (void)hipFree(q); } } mem;
+  const size_t each[4] = {6u * sizeof(double), 3u * sizeof(double), 4u, sizeof(rt_hit)};
+  uint8_t *const host[4] = {(uint8_t *)rays, (uint8_t *)ho->rgb, ho->rgba, (uint8_t *)ho->hits};
+  for (int i = 0; i < 4; i++) if (host[i]) HIP_TRY(hipMalloc(&mem.p[i], chunk * each[i]));
+  const rt_ray_outputs dout = {(double *)mem.p[1], (uint8_t *)mem.p[2], (rt_hit *)mem.p[3]};
+  double kernel_ms = 0.0;
+  for (uint64_t base = 0; base < n; base += chunk) {
+    const size_t m = n - base < chunk ? (size_t)(n - base) : chunk;
+    HIP_TRY(hipMemcpyAsync(mem.p[0], host[0] + base * each[0], m * each[0], hipMemcpyHostToDevice, D.stream));
+    rt_stats st;
+    if ((rc = trace_rays_launch(s, (uint32_t)m, (uint32_t)base, (const double *)mem.p[0], segs, dout, D.stream, stats ? &st : nullptr))) return rc;
+    if (stats) kernel_ms += st.kernel_ms;
+    for (int i = 1; i < 4; i++) if (host[i]) HIP_TRY(hipMemcpyAsync(host[i] + base * each[i], mem.p[i], m * each[i], hipMemcpyDeviceToHost, D.stream));
+    HIP_TRY(hipStreamSynchronize(D.stream));
+  }
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = kernel_ms;
+    stats->pixels = n;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
 }
 
 namespace {

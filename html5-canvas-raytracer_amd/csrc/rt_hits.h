@@ -23,9 +23,13 @@ struct rt_hits_launch {
   uint32_t tile_rows, tile_first, tile_stride;   // rt_tiles, in OUTPUT rows
   uint32_t band_rows;              // sample rows of the call's band: n_tiles x k x tile_rows
   uint32_t n_points;
+  // rt_scene_trace_rays_device: n_rays records {org[3], dir[3]} (16-byte aligned) ... and their records in `hits`
+  const double *rays;
+  uint32_t n_rays;
 };
 
 extern "C" int rt_launch_hits(const rt_hits_launch *L, hipStream_t stream);
 extern "C" int rt_launch_pick(const rt_hits_launch *L, hipStream_t stream);
+extern "C" int rt_launch_ray_hits(const rt_hits_launch *L, hipStream_t stream);
 
 #endif

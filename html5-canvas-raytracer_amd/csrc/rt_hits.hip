@@ -1,5 +1,5 @@
-// rt_hits.hip — what is under a sample: the primary hit of every sample of a frame (object id, depth, normal) and of single
-// sample points (pick: the whole hit record).  The reference computes all of it per ray and throws it away after shading
+// rt_hits.hip — what is under a sample: the primary hit of every sample of a frame (object id, depth, normal), of single
+// sample points (pick: the whole hit record) and of caller-supplied rays (rt_scene_trace_rays_device: the same record per ray).  The reference computes all of it per ray and throws it away after shading
 // (main.js:216-231, :440-449: hit_i, hit.t, hit.p, hit.n, the inside flag behind hit.l, hit.u / hit.v).
 //
 // Semantics (include/rt_hip.h: rt_render_hits_device, rt_scene_pick), per sample of the k w x k h sample grid:
@@ -34,16 +34,9 @@ struct hit_core {
   double t, p[3], n[3];
 };
 
-// the primary hit of sample (sx, sy): main.js:184-193, 220-231, 420-451, 440-449, operation for operation
-__device__ __forceinline__ hit_core primary_hit(const rt_hits_launch &L, uint32_t sx, uint32_t sy) {
-  const double d0 = ((double)sx - L.proj_w) + 0.5, d1 = (L.proj_h - (double)sy) - 0.5, d2 = L.proj_d;
-  const double ox = L.cam[0], oy = L.cam[1], oz = L.cam[2];
-  const double tx = ox + L.cam[3] * d0 + L.cam[6] * d0 + L.cam[9] * d0;
-  const double ty = oy + L.cam[4] * d1 + L.cam[7] * d1 + L.cam[10] * d1;
-  const double tz = oz + L.cam[5] * d2 + L.cam[8] * d2 + L.cam[11] * d2;
-  double rx = tx - ox, ry = ty - oy, rz = tz - oz;
-  const double l = sqrt(rx * rx + ry * ry + rz * rz);
-  if (l != 0.0) { const double k = 1.0 / l; rx *= k; ry *= k; rz *= k; }
+// the first hit of the ray (o, r), r as given: main.js:220-231, 420-451, 440-449, operation for operation
+__device__ __forceinline__ hit_core ray_hit(const rt_hits_launch &L, const double ox, const double oy, const double oz, const double rx, const double ry,
+                                            const double rz) {
   const double eps = L.epsilon;
   double ht = __builtin_inf();
   int32_t hi = -1, hin = 0;
@@ -82,6 +75,34 @@ __device__ __forceinline__ hit_core primary_hit(const rt_hits_launch &L, uint32_
   return H;
 }
 
+// the primary hit of sample (sx, sy): the ray of main.js:184-193, then ray_hit
+__device__ __forceinline__ hit_core primary_hit(const rt_hits_launch &L, uint32_t sx, uint32_t sy) {
+  const double d0 = ((double)sx - L.proj_w) + 0.5, d1 = (L.proj_h - (double)sy) - 0.5, d2 = L.proj_d;
+  const double ox = L.cam[0], oy = L.cam[1], oz = L.cam[2];
+  const double tx = ox + L.cam[3] * d0 + L.cam[6] * d0 + L.cam[9] * d0;
+  const double ty = oy + L.cam[4] * d1 + L.cam[7] * d1 + L.cam[10] * d1;
+  const double tz = oz + L.cam[5] * d2 + L.cam[8] * d2 + L.cam[11] * d2;
+  double rx = tx - ox, ry = ty - oy, rz = tz - oz;
+  const double l = sqrt(rx * rx + ry * ry + rz * rz);
+  if (l != 0.0) { const double k = 1.0 / l; rx *= k; ry *= k; rz *= k; }
+  return ray_hit(L, ox, oy, oz, rx, ry, rz);
+}
+
+// the record rt_scene_pick and rt_scene_trace_rays_device return (include/rt_hip.h: rt_hit): u, v of main.js:446-447
+__device__ __forceinline__ rt_hit hit_record(const hit_core &H) {
+  rt_hit r;
+  r.object = H.id < 0 ? -1 : (H.id & 0xffff);
+  r.inside = H.id < 0 ? 0 : (H.id >> 16);
+  r.t = H.t;
+  for (int c = 0; c < 3; c++) { r.point[c] = H.p[c]; r.normal[c] = H.n[c]; }
+  r.u = 0.0; r.v = 0.0;
+  if (H.id >= 0) {
+    r.u = fd_atan2(-H.n[2], -H.n[0]) / M_PI / 2 + 0.5;
+    r.v = fd_asin(-H.n[1]) / (M_PI / 2) / 2 + 0.5;
+  }
+  return r;
+}
+
 // rt_render_hits_device: the samples of `tiles` (in output rows; tile slot i holds its k tile_rows sample rows one after another),
 // band sample row by band sample row
 __global__ void __launch_bounds__(RT_HITS_WG) rt_hits_kernel(const rt_hits_launch L) {
@@ -108,22 +129,31 @@ __global__ void __launch_bounds__(RT_HITS_WG) rt_pick_kernel(const rt_hits_launc
   const uint32_t j = blockIdx.x * RT_HITS_WG + threadIdx.x;
   if (j >= L.n_points) return;
   const uint32_t sx = L.points[2u * j], sy = L.points[2u * j + 1u];
-  const hit_core H = primary_hit(L, sx, sy);
-  rt_hit r;
-  r.object = H.id < 0 ? -1 : (H.id & 0xffff);
-  r.inside = H.id < 0 ? 0 : (H.id >> 16);
-  r.t = H.t;
-  for (int c = 0; c < 3; c++) { r.point[c] = H.p[c]; r.normal[c] = H.n[c]; }
-  r.u = 0.0; r.v = 0.0;
-  if (H.id >= 0) {
-    // main.js:446-447
-    r.u = fd_atan2(-H.n[2], -H.n[0]) / M_PI / 2 + 0.5;
-    r.v = fd_asin(-H.n[1]) / (M_PI / 2) / 2 + 0.5;
-  }
-  L.hits[j] = r;
+  L.hits[j] = hit_record(primary_hit(L, sx, sy));
+}
+
+// rt_scene_trace_rays_device, `hits`: one work-item per caller-supplied ray {org[3], dir[3]} (three 16-byte loads from the 16-byte
+// aligned list), the direction as given.  A ray with a non-finite component is not traced: the miss record.
+__global__ void __launch_bounds__(RT_HITS_WG) rt_ray_hit_kernel(const rt_hits_launch L) {
+  typedef double __attribute__((ext_vector_type(2))) d2;
+  const uint32_t j = blockIdx.x * RT_HITS_WG + threadIdx.x;
+  if (j >= L.n_rays) return;
+  const d2 *q = (const d2 *)(L.rays + 6u * (size_t)j);
+  const d2 a = q[0], b = q[1], c = q[2];
+  // x - x is 0 for every finite x and NaN otherwise
+  const bool finite = (a.x - a.x) + (a.y - a.y) + (b.x - b.x) + (b.y - b.y) + (c.x - c.x) + (c.y - c.y) == 0.0;
+  hit_core H;
+  H.id = -1; H.t = __builtin_inf(); H.p[0] = H.p[1] = H.p[2] = 0.0; H.n[0] = H.n[1] = H.n[2] = 0.0;
+  if (finite) H = ray_hit(L, a.x, a.y, b.x, b.y, c.x, c.y);
+  L.hits[j] = hit_record(H);
 }
 
 }  // namespace
+
+extern "C" int rt_launch_ray_hits(const rt_hits_launch *L, hipStream_t stream) {
+  hipLaunchKernelGGL(rt_ray_hit_kernel, dim3((L->n_rays + RT_HITS_WG - 1) / RT_HITS_WG), dim3(RT_HITS_WG), 0, stream, *L);   // (n_rays < 2^31)
+  return (int)hipGetLastError();
+}
 
 extern "C" int rt_launch_hits(const rt_hits_launch *L, hipStream_t stream) {
   const uint32_t gy = L->band_rows < 65535u ? L->band_rows : 65535u;

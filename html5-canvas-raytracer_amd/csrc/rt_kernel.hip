@@ -1717,6 +1717,37 @@ __global__ void __launch_bounds__(RT_WG_THREADS) rt_retrace(const rt_launch L) {
     }
   }
 }
+
+// rt_trace_rays - caller-supplied rays (include/rt_hip.h: rt_scene_trace_rays_device; strict build only).  One work-item per record
+// {org[3], dir[3]} of the list, a grid-stride loop; ray j is intersectWorld(L.segs, objects, org, dir) (main.js:216-336) with the
+// direction as given - trace_pixel in ITEM mode, as rt_retrace runs it: every sphere in the scene's own order with the generic
+// discriminant, materials read from HBM, no launch table, no cull, nothing anchored at a camera, and no wave-wide step (a wave's
+// lanes hold unrelated rays).  The stars sampler's pix is the ray's index in the caller's list, ray_base + j (below 2^31: it is handed
+// over as sample x of row 0).
+// Memory: a record is 48 bytes and the list 16-byte aligned - three 16-byte loads per lane; rgba is one dword per lane (a wave stores
+// 256 contiguous bytes), rgb three 8-byte stores.  A ray with a non-finite component is not traced (NaN x 3; the store rule makes
+// 0, 0, 0, 255 of it): what the caller supplies decides no address here - sphere, texel and checker indices come out of comparisons
+// that NaN fails (no hit), a truncation that is clamped (texel) and to_int32_bit0 (0 or 1) for every finite ray, whatever overflows
+// on the way down the tree - and the guard keeps that argument to finite inputs.
+template <bool REFRACT>
+__global__ void __launch_bounds__(RT_WG_THREADS) rt_trace_rays(const rt_launch L) {
+  typedef double __attribute__((ext_vector_type(2))) d2;
+  const rt_mtl *mtl = (const rt_mtl *)L.lds_image;                         // (HBM: nothing is staged here)
+  const rt_texture_desc *tex = (const rt_texture_desc *)((const char *)L.lds_image + (size_t)L.n_objects * sizeof(rt_mtl));
+  for (uint32_t j = blockIdx.x * RT_WG_THREADS + threadIdx.x; j < L.n_rays; j += gridDim.x * RT_WG_THREADS) {
+    const d2 *q = (const d2 *)(L.rays + 6u * (size_t)j);
+    const d2 a = q[0], b = q[1], c = q[2];
+    double rgb[3] = {__builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
+    // x - x is 0 for every finite x and NaN otherwise
+    if ((a.x - a.x) + (a.y - a.y) + (b.x - b.x) + (b.y - b.y) + (c.x - c.x) + (c.y - c.y) == 0.0) {
+      uint32_t cnt[3] = {0u, 0u, 0u};
+      trace_pixel<REFRACT, false, false, false, true>(L, mtl, tex, nullptr, nullptr, rt_geom{0.0, 0.0, 0.0, 0.0}, 0u, 0.0, 0.0, 0.0, 0.0, mk(a.x, a.y, b.x),
+                                                      mk(b.y, c.x, c.y), rgb, cnt, false, 0u, L.ray_base + j, 0u, 0u);
+    }
+    if (L.ray_rgb) { double *o = L.ray_rgb + 3u * (size_t)j; o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2]; }
+    if (L.ray_rgba) L.ray_rgba[j] = to_byte(rgb[0]) | (to_byte(rgb[1]) << 8) | (to_byte(rgb[2]) << 16) | 0xff000000u;
+  }
+}
 #endif
 
 }  // namespace
@@ -1728,6 +1759,20 @@ extern "C" int rt_launch_retrace(const rt_launch *L, int refract, int ss2, unsig
   if (!refract) { if (!ss2) hipLaunchKernelGGL((rt_retrace<false, false>), grid, block, 0, stream, *L); else hipLaunchKernelGGL((rt_retrace<false, true>), grid, block, 0, stream, *L); }
   else          { if (!ss2) hipLaunchKernelGGL((rt_retrace<true, false>), grid, block, 0, stream, *L);  else hipLaunchKernelGGL((rt_retrace<true, true>), grid, block, 0, stream, *L); }
   return (int)hipGetLastError();
+}
+
+// Host-side launcher of rt_trace_rays (n_wg workgroups of RT_WG_THREADS) and its per-lane scratch.  Return a hipError_t as int.
+extern "C" int rt_launch_trace_rays(const rt_launch *L, int refract, unsigned n_wg, hipStream_t stream) {
+  const dim3 grid(n_wg ? n_wg : 1u), block(RT_WG_THREADS);
+  if (!refract) hipLaunchKernelGGL((rt_trace_rays<false>), grid, block, 0, stream, *L);
+  else hipLaunchKernelGGL((rt_trace_rays<true>), grid, block, 0, stream, *L);
+  return (int)hipGetLastError();
+}
+extern "C" int rt_scratch_trace_rays(int refract, size_t *bytes_per_lane) {
+  hipFuncAttributes fa;
+  const hipError_t e = hipFuncGetAttributes(&fa, !refract ? (const void *)&rt_trace_rays<false> : (const void *)&rt_trace_rays<true>);
+  if (e == hipSuccess) *bytes_per_lane = (size_t)fa.localSizeBytes;
+  return (int)e;
 }
 #endif
 

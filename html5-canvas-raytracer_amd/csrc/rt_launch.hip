@@ -1,6 +1,6 @@
 // rt_launch.hip — the launches of a resident scene (include/rt_hip.h: rt_render_*_device): the product launch with its launch table
 // and the list-driven strict launch behind it (rt_retrace), the strict kernel, 3x3 / 4x4 supersampling with a box filter, compact
-// bands, primary hits and picking, and the test build's per-sample probe.
+// bands, primary hits and picking, caller-supplied rays (rt_trace_rays), and the test build's per-sample probe.
 
 #include "rt_api_internal.h"
 
@@ -649,4 +649,99 @@ extern "C" int rt_scene_pick(rt_scene_dev *s, uint32_t w, uint32_t h, uint32_t n
   HIP_TRY(hipMemcpyAsync(out, L.hits, (size_t)n * sizeof(rt_hit), hipMemcpyDeviceToHost, D.stream));
   HIP_TRY(hipStreamSynchronize(D.stream));
   return RT_OK;
+}
+
+// ------------------------------------------------------------------------------------ caller-supplied rays (rt_kernel.hip: rt_trace_rays)
+// intersectWorld for a list of rays (include/rt_hip.h: rt_scene_trace_rays_device).  One launch decision: the strict build's
+// rt_trace_rays<refract> for the colours - the scene in its own order, every sphere in the loops, the reference's own miss colour, as
+// rt_retrace is bound; camera, launch tables and flags play no part - and rt_hits.hip's rt_ray_hit_kernel for the hit records.  Both
+// read the scene's current generation, so they come behind its preparation like every other launch of the scene.
+namespace rt_api {
+int rays_check(uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *out, const char *what) {
+  if (!rays || !out) return fail(RT_ERR_INVALID, "%s: NULL rays or outputs", what);
+  if (n == 0 || n >= (1ull << 31)) return fail(RT_ERR_INVALID, "%s: n %llu not in 1..2^31 - 1", what, (unsigned long long)n);
+  if (segs > RT_MAX_SEGS) return fail(RT_ERR_INVALID, "%s: segs %u not in 0..%u (0 = the scene's depth)", what, segs, RT_MAX_SEGS);
+  if (!out->rgb && !out->rgba && !out->hits) return fail(RT_ERR_INVALID, "%s: every output is NULL", what);
+  if ((uintptr_t)rays & 15u) return fail(RT_ERR_INVALID, "%s: the ray list must be 16-byte aligned", what);
+  if (((uintptr_t)out->rgb & 7u) || ((uintptr_t)out->rgba & 3u) || ((uintptr_t)out->hits & 7u))
+    return fail(RT_ERR_INVALID, "%s: misaligned output (rgb and hits need 8 bytes, rgba 4)", what);
+  return RT_OK;
+}
+
+int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *d_rays, uint32_t segs, const rt_ray_outputs &out, hipStream_t stream,
+                      rt_stats *stats) {
+  device_state &D = G.dev[s->device];
+  const auto t_begin = std::chrono::steady_clock::now();
+  const rt_scene_header &hd = s->hd;
+  rt_launch L;
+  memset(&L, 0, sizeof L);
+  {
+    std::lock_guard<std::mutex> lk(s->launch_mu);
+    if (int rc = behind_the_camera(s, stream)) return rc;
+    note_launch(s, stream);
+    L.stars_seed = hd.stars_seed;                      // (rt_scene_set_stars_seed: this launch's, whatever the next call sets)
+    const uint8_t *ob = obj_block(s);                 // this generation's spheres, in blob order
+    L.objects = (const rt_sphere *)(ob + s->o_objs);
+    L.geom = (const rt_geom *)(ob + s->o_geom);
+    L.lds_image = lds_image_of(s);                    // its materials and texture descriptors, read from HBM
+  }
+  L.textures = s->d_texdesc;
+  L.texel_base = (const uint8_t *)s->d_blob;
+  L.n_objects = L.n_loop = hd.n_objects;
+  L.enclosing = ~0u;
+  L.n_lights = hd.n_lights;
+  memcpy(L.lights, s->lights, sizeof L.lights);
+  L.epsilon = hd.epsilon; L.light_intensity = hd.light_intensity;
+  memcpy(L.miss_color, hd.miss_color, sizeof L.miss_color);
+  L.segs = segs ? segs : hd.segs;                      // the CALL's depth
+  L.n_frames = 1u;
+  L.rays = d_rays; L.ray_rgb = out.rgb; L.ray_rgba = (uint32_t *)out.rgba; L.n_rays = n; L.ray_base = base;
+  event_timer timer;                                     // (a stats call)
+  if (stats) HIP_TRY(timer.start(stream));
+  if (out.rgb || out.rgba) {
+    // one work-item per ray; the grid-stride loop takes over beyond 2^20 workgroups
+    const uint32_t wgs = (n + RT_WG_THREADS - 1u) / RT_WG_THREADS, n_wg = wgs < (1u << 20) ? wgs : (1u << 20);
+    static std::atomic<long long> scratch_of[2] = {{-1}, {-1}};       // per-lane scratch of the two instantiations, asked once each
+    long long per_lane = scratch_of[s->refract ? 1 : 0].load();
+    if (per_lane < 0) {
+      size_t b = 0;
+      const int e = rt_scratch_trace_rays(s->refract, &b);
+      if (e != 0) return fail(RT_ERR_DEVICE, "hipFuncGetAttributes: %s", hipGetErrorString((hipError_t)e));
+      scratch_of[s->refract ? 1 : 0].store(per_lane = (long long)b);
+    }
+    if (int rc = scratch_guard(D, stream, (size_t)per_lane, (uint64_t)n_wg * (RT_WG_THREADS / 64u), "the ray-list kernel (rt_trace_rays)")) return rc;
+    const int err = rt_launch_trace_rays(&L, s->refract, n_wg, stream);
+    if (err != 0) return fail(RT_ERR_DEVICE, "ray kernel launch: %s", hipGetErrorString((hipError_t)err));
+  }
+  if (out.hits) {
+    rt_hits_launch H;
+    memset(&H, 0, sizeof H);
+    H.objects = L.objects;
+    H.epsilon = hd.epsilon;
+    H.n_objects = hd.n_objects;
+    H.rays = d_rays; H.n_rays = n; H.hits = out.hits;
+    const int err = rt_launch_ray_hits(&H, stream);
+    if (err != 0) return fail(RT_ERR_DEVICE, "ray hit kernel launch: %s", hipGetErrorString((hipError_t)err));
+  }
+  if (stats) {
+    HIP_TRY(timer.stop(stream));
+    HIP_TRY(hipEventSynchronize(timer.b));
+    float ms = 0.f;
+    HIP_TRY(timer.elapsed(&ms));
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = ms;
+    stats->pixels = n;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
+}
+}  // namespace rt_api
+
+extern "C" int rt_scene_trace_rays_device(rt_scene_dev *s, uint64_t n, const double *d_rays, uint32_t segs, const rt_ray_outputs *d_out, void *hip_stream,
+                                          rt_stats *stats) {
+  if (!s) return fail(RT_ERR_STATE, "rt_scene_trace_rays_device: NULL scene handle");
+  int rc = rays_check(n, d_rays, segs, d_out, "rt_scene_trace_rays_device");
+  if (rc) return rc;
+  if ((rc = ensure_device(s->device))) return rc;
+  return trace_rays_launch(s, (uint32_t)n, 0u, d_rays, segs, *d_out, hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream, stats);
 }

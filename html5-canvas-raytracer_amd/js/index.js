@@ -86,10 +86,59 @@ function pick(width, height, sceneObj, x, y) {
   return r;
 }
 
+// The reference's normal3D (main.js:62-66): v * (1 / |v|); the zero vector is returned unchanged.
+function normal3D(v) {
+  const l = Math.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  if (l === 0) return [v[0], v[1], v[2]];
+  const k = 1 / l;
+  return [v[0] * k, v[1] * k, v[2] * k];
+}
+
+// The primary rays of the width x height frame, main.js:184-193 operation for operation, as a Float64Array of 6 numbers per sample
+// {org, dir} in row order of the k*width x k*height sample grid: traceRays of this list is the scene's strict-arithmetic sample
+// frame, stars included (a ray's index in the list is its sample's index in the frame).
+function primaryRays(width, height, sceneObj) {
+  const k = sceneObj.supersample || 1, sw = k * width, sh = k * height;
+  const {origin, axisX, axisY, axisZ} = sceneObj.camera;
+  const fov = sceneObj.fovDeg === undefined ? 60 : sceneObj.fovDeg;
+  const projA = fov * Math.PI / 180, projW = sw / 2, projH = sh / 2, projD = projW / tanHalf(projA);
+  const rays = new Float64Array(6 * sw * sh);
+  let i = 0;
+  for (let y = 0; y < sh; y++) {
+    for (let x = 0; x < sw; x++) {
+      const dist = [x - projW + 0.5, projH - y - 0.5, projD];
+      const target = [
+        origin[0] + axisX[0] * dist[0] + axisY[0] * dist[0] + axisZ[0] * dist[0],
+        origin[1] + axisX[1] * dist[1] + axisY[1] * dist[1] + axisZ[1] * dist[1],
+        origin[2] + axisX[2] * dist[2] + axisY[2] * dist[2] + axisZ[2] * dist[2]];
+      const ray = normal3D([target[0] - origin[0], target[1] - origin[1], target[2] - origin[2]]);
+      rays[i++] = origin[0]; rays[i++] = origin[1]; rays[i++] = origin[2];
+      rays[i++] = ray[0]; rays[i++] = ray[1]; rays[i++] = ray[2];
+    }
+  }
+  return rays;
+}
+function tanHalf(projA) { return Math.tan(projA / 2); }
+
+// intersectWorld(segs, objects, org, dir) (main.js:216-336) for a list of rays: `rays` is a Float64Array of 6 numbers per ray
+// {org, dir}, directions used as given (normal3D above is the reference's).  opts: segs (0 / undefined = the scene's depth) and which
+// outputs to compute - rgb (default true) Float64Array 3 per ray, rgba Uint8ClampedArray 4 per ray, hits Array of pick's records
+// (null = a miss).  The scene's camera plays no part.  A ray with a non-finite component is not traced: NaN x 3 / 0, 0, 0, 255 / null.
+function traceRays(sceneObj, rays, opts) {
+  if (!(rays instanceof Float64Array) || rays.length === 0 || rays.length % 6 !== 0) {
+    throw new TypeError('traceRays: rays must be a non-empty Float64Array of 6 numbers per ray');
+  }
+  if (!inited) init(opts && opts.maxDevices);
+  const o = opts || {};
+  const r = native().traceRays(new Uint8Array(flattenScene(sceneObj)), rays, o.segs || 0, o.rgb !== false, !!o.rgba, !!o.hits);
+  if (r.hits) for (const h of r.hits) if (h) h.object = sceneObj.objects[h.index];
+  return r;
+}
+
 // `const build = '741'` (main.js:3) + this library's revision; every render's `.stats` also carries `.build` and `.report`, the
 // reference's end-of-frame string 'build #<id> (<elapsed>ms)' (main.js:204-205) for that render.
 function buildId() { return native().buildId(); }
 
 function shutdown() { if (addon) addon.shutdown(); inited = false; }
 
-module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, init, shutdown, buildId, flattenScene, scenes, native}, scene);
+module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, primaryRays, normal3D, init, shutdown, buildId, flattenScene, scenes, native}, scene);

@@ -17,6 +17,9 @@
 //   GET /pick?scene=h8&w=1280&h=720&x=640&y=360[&seed=N]
 //                                       what is under output pixel (x, y) (RT.pick): JSON {index, inside, t, point, normal, u, v},
 //                                       or null where the ray meets nothing; x, y outside the frame: 400
+//   GET /ray?scene=h8&ox=0&oy=1.5&oz=10&dx=0&dy=0&dz=-1[&segs=N][&seed=N]
+//                                       intersectWorld for ONE ray (RT.traceRays), the direction as given: JSON {rgb, rgba, hit} - hit as
+//                                       /pick's record, or null; a number that does not parse, segs outside 0..16: 400
 //   GET /scenes                         JSON list of scene names
 // Errors (no GPU, bad scene, bad size) are JSON with status 4xx/5xx; never a CPU-rendered frame.
 //
@@ -108,6 +111,25 @@ function createServer(opts) {
       return res.end(PAGE);
     }
     if (u.pathname === '/scenes') return sendJSON(res, 200, {scenes: listScenes()});
+    if (u.pathname === '/ray') {
+      const num = (k) => (/^[-+0-9.eE]{1,32}$/.test(String(u.query[k])) ? Number(u.query[k]) : NaN);
+      const ray = ['ox', 'oy', 'oz', 'dx', 'dy', 'dz'].map(num);
+      if (!ray.every(Number.isFinite)) return sendJSON(res, 400, {error: 'ox, oy, oz, dx, dy, dz must be finite numbers'});
+      const segs = u.query.segs === undefined ? 0 : (/^[0-9]{1,2}$/.test(String(u.query.segs)) ? Number(u.query.segs) : -1);
+      if (!(segs >= 0 && segs <= 16)) return sendJSON(res, 400, {error: 'segs must be an integer in 0..16 (0 = the scene\'s depth)'});
+      let scene;
+      try { scene = loadNamedScene(String(u.query.scene || 'default14_stars')); } catch (e) { return sendJSON(res, e.status || 500, {error: e.message}); }
+      if (u.query.seed !== undefined) {
+        const seed = /^[0-9]{1,10}$/.test(String(u.query.seed)) ? Number(u.query.seed) : -1;
+        if (!(seed >= 0 && seed < 4294967296)) return sendJSON(res, 400, {error: 'seed must be an integer in [0, 2^32)'});
+        scene = Object.assign({}, scene, {starsSeed: seed});
+      }
+      let r;
+      try { r = RT.traceRays(scene, Float64Array.from(ray), {segs, rgb: true, rgba: true, hits: true}); } catch (e) { return sendJSON(res, 503, {error: e.message}); }
+      const hit = r.hits[0];
+      if (hit) delete hit.object;                    // (the scene's own record: the page knows it by its index)
+      return sendJSON(res, 200, {rgb: Array.from(r.rgb), rgba: Array.from(r.rgba), hit});
+    }
     if (u.pathname === '/frame' || u.pathname === '/pick') {
       const w = parseInt(u.query.w, 10), h = parseInt(u.query.h, 10);
       if (!(w > 0 && h > 0 && w <= 65536 && h <= 65536 && w * h <= maxPixels)) return sendJSON(res, 400, {error: 'w and h must be positive integers within the frame limit'});

@@ -10,7 +10,9 @@
 //           being filled; onBand fires on the main thread as each row band lands in it; the promise resolves to the stats
 //           renderHits(blob, w, h, wantDepth, wantNormal) -> {id: Int32Array, depth: Float64Array | null, normal: Float32Array | null}
 //           pick(blob, w, h, sx, sy) -> {index, inside, t, point, normal, u, v} or null (a miss); sx, sy in sample-grid coordinates
-//           (these two are not enumerable: the enumerable surface is the frame API)
+//           traceRays(blob, rays: Float64Array (6 per ray), segs, wantRgb, wantRgba, wantHits) -> {rgb: Float64Array | null,
+//           rgba: Uint8ClampedArray | null, hits: Array of pick's records (null = a miss) | null}: intersectWorld per ray (rt_trace_rays)
+//           (these three are not enumerable: the enumerable surface is the frame API)
 // Every failure of the library becomes a thrown JS Error carrying rt_last_error().
 //
 // Build: g++ -shared -fPIC -I/usr/include/node rt_napi.cc -L../csrc -lrt_hip  (napi/Makefile; no node-gyp).
@@ -379,6 +381,21 @@ napi_value doubles(napi_env env, const double *x, int n) {
   return arr;
 }
 
+// a hit record as pick and traceRays return it: {index, inside, t, point, normal, u, v}, or null on a miss
+napi_value hit_object(napi_env env, const rt_hit &r) {
+  napi_value res, v;
+  if (r.object < 0) { napi_get_null(env, &res); return res; }
+  NAPI_TRY(napi_create_object(env, &res));
+  napi_create_int32(env, r.object, &v); napi_set_named_property(env, res, "index", v);
+  napi_get_boolean(env, r.inside != 0, &v); napi_set_named_property(env, res, "inside", v);
+  napi_create_double(env, r.t, &v); napi_set_named_property(env, res, "t", v);
+  napi_set_named_property(env, res, "point", doubles(env, r.point, 3));
+  napi_set_named_property(env, res, "normal", doubles(env, r.normal, 3));
+  napi_create_double(env, r.u, &v); napi_set_named_property(env, res, "u", v);
+  napi_create_double(env, r.v, &v); napi_set_named_property(env, res, "v", v);
+  return res;
+}
+
 // pick(blob, w, h, sx, sy): one sample's hit record (rt_pick), or null on a miss
 napi_value Pick(napi_env env, napi_callback_info info) {
   args a;
@@ -396,16 +413,63 @@ napi_value Pick(napi_env env, napi_callback_info info) {
   a.rc = rt_pick(a.blob, a.bytes, a.w, a.h, 1u, xy, &r);
   if (a.owned) free(a.blob);
   if (a.rc != RT_OK) return throw_rt(env, "rt_pick", a.rc);
-  napi_value res, v;
-  if (r.object < 0) { napi_get_null(env, &res); return res; }
-  NAPI_TRY(napi_create_object(env, &res));
-  napi_create_int32(env, r.object, &v); napi_set_named_property(env, res, "index", v);
-  napi_get_boolean(env, r.inside != 0, &v); napi_set_named_property(env, res, "inside", v);
-  napi_create_double(env, r.t, &v); napi_set_named_property(env, res, "t", v);
-  napi_set_named_property(env, res, "point", doubles(env, r.point, 3));
-  napi_set_named_property(env, res, "normal", doubles(env, r.normal, 3));
-  napi_create_double(env, r.u, &v); napi_set_named_property(env, res, "u", v);
-  napi_create_double(env, r.v, &v); napi_set_named_property(env, res, "v", v);
+  return hit_object(env, r);
+}
+
+napi_value TraceRays(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  bool is_ta = false, is_rays = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
+      napi_is_typedarray(env, argv[1], &is_rays) != napi_ok || !is_rays) {
+    napi_throw_type_error(env, nullptr, "traceRays(blob: Uint8Array, rays: Float64Array[, segs, wantRgb, wantRgba, wantHits])");
+    return nullptr;
+  }
+  napi_typedarray_type bt, rt; napi_value ab; size_t off, blob_len = 0, ray_len = 0;
+  void *blob_data = nullptr, *ray_data = nullptr;
+  napi_get_typedarray_info(env, argv[0], &bt, &blob_len, &blob_data, &ab, &off);
+  napi_get_typedarray_info(env, argv[1], &rt, &ray_len, &ray_data, &ab, &off);
+  if ((bt != napi_uint8_array && bt != napi_uint8_clamped_array) || rt != napi_float64_array || ray_len == 0 || ray_len % 6u != 0) {
+    napi_throw_type_error(env, nullptr, "traceRays: the blob must be a Uint8Array and the rays a non-empty Float64Array of 6 numbers per ray");
+    return nullptr;
+  }
+  uint32_t segs = 0;
+  bool want[3] = {true, false, false};
+  if (argc >= 3) napi_get_value_uint32(env, argv[2], &segs);
+  for (size_t i = 0; i < 3 && 3 + i < argc; i++) napi_get_value_bool(env, argv[3 + i], &want[i]);
+  const size_t n = ray_len / 6u;
+  // the library wants the blob 8-byte and the rays 16-byte aligned: one aligned copy holds both
+  const size_t blob_room = (blob_len + 15) & ~(size_t)15;
+  uint8_t *mem = (uint8_t *)aligned_alloc(16, blob_room + ((n * 48u + 15) & ~(size_t)15));
+  napi_value ab_rgb = nullptr, ab_rgba = nullptr, res, v;
+  void *p_rgb = nullptr, *p_rgba = nullptr;
+  rt_hit *hits = want[2] ? (rt_hit *)malloc(n * sizeof(rt_hit)) : nullptr;
+  if (!mem || (want[2] && !hits) || (want[0] && napi_create_arraybuffer(env, n * 24u, &p_rgb, &ab_rgb) != napi_ok) ||
+      (want[1] && napi_create_arraybuffer(env, n * 4u, &p_rgba, &ab_rgba) != napi_ok)) {
+    free(mem); free(hits);
+    napi_throw_error(env, nullptr, "traceRays: out of memory");
+    return nullptr;
+  }
+  memcpy(mem, blob_data, blob_len);
+  memcpy(mem + blob_room, ray_data, n * 48u);
+  const rt_ray_outputs out = {(double *)p_rgb, (uint8_t *)p_rgba, hits};
+  rt_stats st;
+  const int rc = rt_trace_rays(mem, blob_len, n, (const double *)(mem + blob_room), segs, &out, &st);
+  free(mem);
+  if (rc != RT_OK) { free(hits); return throw_rt(env, "rt_trace_rays", rc); }
+  napi_create_object(env, &res);
+  if (want[0]) napi_create_typedarray(env, napi_float64_array, 3 * n, ab_rgb, 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "rgb", v);
+  if (want[1]) napi_create_typedarray(env, napi_uint8_clamped_array, 4 * n, ab_rgba, 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "rgba", v);
+  if (want[2]) {
+    napi_create_array_with_length(env, n, &v);
+    for (size_t i = 0; i < n; i++) napi_set_element(env, v, (uint32_t)i, hit_object(env, hits[i]));
+    free(hits);
+  } else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "hits", v);
+  napi_value ms;
+  napi_create_double(env, st.kernel_ms, &ms); napi_set_named_property(env, res, "kernel_ms", ms);
   return res;
 }
 
@@ -421,6 +485,7 @@ napi_value Module(napi_env env, napi_value exports) {
       {"buildId", nullptr, BuildId, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"renderHits", nullptr, RenderHits, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"pick", nullptr, Pick, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"traceRays", nullptr, TraceRays, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

@@ -167,6 +167,11 @@ class RtHitBuffers(C.Structure):
     _fields_ = [("id", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class RtRayOutputs(C.Structure):
+    """Outputs of a ray list (include/rt_hip.h rt_ray_outputs): 3 float64, 4 uint8, one RtHit per ray; NULL = not wanted."""
+    _fields_ = [("rgb", C.c_void_p), ("rgba", C.c_void_p), ("hits", C.c_void_p)]
+
+
 # every symbol include/rt_hip.h declares: (restype, argtypes)
 ABI = {
     "rt_init": (C.c_int, [C.c_int]),
@@ -216,6 +221,8 @@ ABI = {
     "rt_scene_pick": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(RtHit)]),
     "rt_render_hits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(RtHitBuffers), C.POINTER(RtStats)]),
     "rt_pick": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(RtHit)]),
+    "rt_scene_trace_rays_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(RtRayOutputs), C.c_void_p, C.POINTER(RtStats)]),
+    "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(RtRayOutputs), C.POINTER(RtStats)]),
 }
 
 
@@ -349,6 +356,17 @@ class Renderer:
         n, xy = _points_array(points)
         return _pick_call(self.lib, lambda n, xy, out: self.lib.rt_scene_pick(self.handle, w, h, n, xy, out), n, xy, "rt_scene_pick")
 
+    def trace_rays(self, n, rays_ptr, rgb_ptr, rgba_ptr, hits_ptr, segs=0, stream=None, want_stats=False):
+        """intersectWorld(segs, objects, org, dir) (main.js:216-336) for n rays {org[3], dir[3]} (float64, 16-byte aligned) in DEVICE
+        memory, into DEVICE buffers (0 / None = not wanted): 3 float64 rgb, 4 uint8 rgba, one 80-byte RtHit per ray.  The direction is
+        used as given; segs 0 = the scene's depth; the scene's camera plays no part."""
+        out = RtRayOutputs(rgb_ptr or None, rgba_ptr or None, hits_ptr or None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_trace_rays_device(self.handle, n, C.c_void_p(rays_ptr or 0), segs, C.byref(out), C.c_void_p(stream or 0),
+                                                 C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_trace_rays_device")
+        return st
+
     def close(self):
         if self.handle:
             self.lib.rt_scene_free(self.handle)
@@ -445,3 +463,74 @@ def pick(width, height, scene, points, lib=None):
     _init_once(lib)
     buf = C.create_string_buffer(blob, len(blob))
     return _pick_call(lib, lambda n, xy, out: lib.rt_pick(buf, len(blob), width, height, n, xy, out), n, xy, "rt_pick")
+
+
+def normal3d(v):
+    """The reference's normal3D (main.js:62-66) on an (..., 3) float64 array: multiply by 1 / sqrt(x x + y y + z z); a zero vector is
+    returned unchanged.  trace_rays uses directions as given - this is what the reference applies before it calls intersectWorld."""
+    import numpy as np
+    v = np.asarray(v, np.float64)
+    x, y, z = v[..., 0], v[..., 1], v[..., 2]
+    l = np.sqrt(x * x + y * y + z * z)
+    with np.errstate(divide="ignore"):
+        k = np.where(l != 0.0, 1.0 / l, 1.0)
+    return np.where((l != 0.0)[..., None], v * k[..., None], v)
+
+
+def primary_rays(width, height, scene):
+    """The primary rays of the width x height frame (main.js:184-193, operation for operation in binary64: dist indexed by component -
+    quirk q1 -, the additions in the reference's order, between3D, normal3D with its l != 0 guard) as a (k width * k height, 6) float64
+    array {org, dir} in row order of the k width x k height sample grid (k = the scene's supersample factor).  trace_rays of this list
+    is the scene's RT_FLAG_STRICT_FP sample frame, stars included (a ray's index in the list is its sample's index in the frame)."""
+    import math
+    import numpy as np
+    cam = scene["camera"]
+    k = scene.get("supersample", 1)
+    sw, sh = k * width, k * height
+    proj_w, proj_h = float(width) * k / 2.0, float(height) * k / 2.0
+    proj_d = proj_w / math.tan(float(scene.get("fovDeg", 60)) * math.pi / 180.0 / 2.0)
+    o, ax, ay, az = (np.array(cam[n], np.float64) for n in ("origin", "axisX", "axisY", "axisZ"))
+    d0 = np.broadcast_to((np.arange(sw, dtype=np.float64) - proj_w) + 0.5, (sh, sw))
+    d1 = np.broadcast_to(((proj_h - np.arange(sh, dtype=np.float64)) - 0.5)[:, None], (sh, sw))
+    d2 = np.full((sh, sw), proj_d)
+    rays = np.empty((sh, sw, 6), np.float64)
+    for c, d in enumerate((d0, d1, d2)):
+        target = o[c] + ax[c] * d + ay[c] * d + az[c] * d
+        rays[..., c] = o[c]
+        rays[..., 3 + c] = target - o[c]
+    rays[..., 3:] = normal3d(rays[..., 3:])
+    return rays.reshape(sh * sw, 6)
+
+
+def trace_rays(scene, rays, segs=0, want=("rgb",), lib=None):
+    """trace_rays(scene, rays) -> {"rgb": (n, 3) float64, "rgba": (n, 4) uint8, "hits": [hit dict or None per ray]} (the keys named in
+    `want`): intersectWorld(segs, objects, org, dir) per row {org, dir} of the float64 (n, 6) array `rays`, directions as given, on
+    GPU 0 with rt_render's resident scene.  segs 0 = the scene's depth.  A ray with a non-finite component is not traced: NaN, NaN,
+    NaN / 0, 0, 0, 255 / None."""
+    import numpy as np
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    want = set(want)
+    if not want or want - {"rgb", "rgba", "hits"}:
+        raise ValueError("want names some of 'rgb', 'rgba', 'hits'")
+    rays = np.asarray(rays, np.float64)
+    if rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError("rays must be an (n, 6) array: org[3], dir[3] per row")
+    n = rays.shape[0]
+    aligned = np.empty(n * 6 + 2, np.float64)             # a contiguous copy on a 16-byte boundary
+    aligned = aligned[(aligned.ctypes.data >> 3) & 1:][:n * 6]
+    aligned[:] = rays.reshape(-1)
+    out = {}
+    if "rgb" in want:
+        out["rgb"] = np.empty((n, 3), np.float64)
+    if "rgba" in want:
+        out["rgba"] = np.empty((n, 4), np.uint8)
+    records = (RtHit * max(n, 1))() if "hits" in want else None
+    bufs = RtRayOutputs(out["rgb"].ctypes.data if "rgb" in out else None, out["rgba"].ctypes.data if "rgba" in out else None,
+                        C.addressof(records) if records is not None else None)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    _check(lib, lib.rt_trace_rays(buf, len(blob), n, C.c_void_p(aligned.ctypes.data), segs, C.byref(bufs), None), "rt_trace_rays")
+    if records is not None:
+        out["hits"] = [_hit_dict(r) for r in records[:n]]
+    return out

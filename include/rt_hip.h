@@ -13,7 +13,7 @@
  * of the calling thread's last call.
  *
  * Threads: rt_init, rt_shutdown and rt_render serialise on an internal lock.  The device entry points
- * (rt_scene_upload, rt_render_tiles_device, rt_render_batch_device, rt_deinterleave_*) may be called from several
+ * (rt_scene_upload, rt_render_tiles_device, rt_render_batch_device, rt_scene_trace_rays_device, rt_deinterleave_*) may be called from several
  * threads at once; work on one HIP stream is ordered by the stream.  Launches with RT_FLAG_COUNT share one counter
  * buffer per device: one at a time per device.
  *
@@ -393,6 +393,52 @@ int rt_scene_pick(rt_scene_dev *scene, uint32_t w, uint32_t h, uint32_t n, const
  * (k*w x k*h samples) non-NULL buffers of host_bufs; rt_pick is rt_scene_pick on that scene.  Both synchronous, on GPU 0. */
 int rt_render_hits(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h, const rt_hit_buffers *host_bufs, rt_stats *stats);
 int rt_pick(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h, uint32_t n, const uint32_t *sample_xy, rt_hit *out);
+
+/* Caller-supplied rays.  The reference's unit of work is not the frame but intersectWorld(segs, objs, org, dir) (main.js:216-336), a
+ * function of a ray; these entry points are that function for a LIST of rays - other projections (panoramas, cube faces, orthographic,
+ * fisheye, stereo), depth of field and jittered sampling with the caller's own pattern, reflection / light probes at any point
+ * (inside a glass sphere too), and the colour twin of rt_scene_pick.
+ *
+ * `rays` is n records of six doubles {org[3], dir[3]} (48 bytes each; the array 16-byte aligned).  Ray i is
+ * intersectWorld(segs, objects, org, dir) over the scene's spheres in BLOB order, its lights, light_intensity, epsilon, miss_color and
+ * textures.  `dir` is used AS GIVEN: the reference does not normalise inside intersectWorld either (main.js:192 normalises before the
+ * call); the hosts offer the reference's normal3D for callers who want it.
+ *   segs    1..RT_MAX_SEGS, or 0 = the scene's own depth: intersectWorld's first argument.  The hit record does not depend on it.
+ *   rgb     the return value of intersectWorld, binary64, before any store rule.
+ *   rgba    255 * rgb through the Uint8ClampedArray store of main.js:195-198 (NaN -> 0, clamp, round half to even), alpha 255.
+ *   hits    the ray's first hit, rt_hit exactly as rt_scene_pick fills it: closest hit, strict <, first wins, inside, t, point, normal,
+ *           u, v; a miss: object -1, inside 0, t +Infinity, everything else 0.
+ * The arithmetic is the strict one everywhere (no FMA contraction, correctly rounded sqrt and division, fdlibm atan2 / asin), for any
+ * origin: the scene's camera, its launch tables, RT_FLAG_* and `supersample` play no part.  The resident scene's CURRENT spheres do
+ * (rt_scene_set_objects), and so does its stars seed (rt_scene_set_stars_seed).
+ * Stars sampler: pix = i (the ray's index in the list, 64 bits), path from the root 1, seed as for a frame.  So the list of a w x h
+ * frame's primary rays in row order draws that frame's sky - and, every other sampler being a function of the ray alone, that list
+ * gives the RT_FLAG_STRICT_FP frame byte for byte.
+ * A ray with a non-finite component (NaN, +-Infinity in any of its six slots) is NOT traced: rgb = NaN x 3, rgba = 0, 0, 0, 255 (what
+ * the store rule makes of NaN), hits = the miss record.  (A zero direction is finite and is traced; the reference's arithmetic stays
+ * finite for it.)
+ * Any output may be NULL and is then not touched; all three NULL is RT_ERR_INVALID, as are n == 0, n >= 2^31, segs > RT_MAX_SEGS and
+ * a NULL or misaligned ray pointer (16 bytes; rgb and hits need 8, rgba 4).  Outputs are written for every i < n and nowhere else.
+ * One work-item per ray, and the 64 rays of a wave run in lock step: neighbouring rays in the list should be neighbouring rays in
+ * space.  The library neither sorts nor bins the list - its coherence is the caller's business. */
+typedef struct rt_ray_outputs {
+  double  *rgb;    /* 3 per ray: the return value of intersectWorld, binary64, before any store rule; or NULL */
+  uint8_t *rgba;   /* 4 per ray: 255 * rgb through the Uint8ClampedArray store of main.js:195-198, alpha 255; or NULL */
+  rt_hit  *hits;   /* the first hit of the ray, the record rt_scene_pick returns; or NULL */
+} rt_ray_outputs;
+
+/* Device form: `d_rays` and the buffers `d_out` names are DEVICE memory (d_out itself is a host struct).  Asynchronous on `hip_stream`
+ * (NULL = the library's stream for the scene's device) unless `stats` is non-NULL (then it waits and fills kernel_ms, total_ms and
+ * pixels = n).  Waits by event for a pending rt_scene_set_objects like every other render.  The refracting scenes' kernel keeps its
+ * frame stack in scratch memory: a reservation the device cannot meet is RT_ERR_NOMEM.  Thread rules as rt_render_tiles_device. */
+int rt_scene_trace_rays_device(rt_scene_dev *scene, uint64_t n, const double *d_rays, uint32_t segs,
+                               const rt_ray_outputs *d_out, void *hip_stream, rt_stats *stats);
+
+/* Host form: rt_render's resident scene (a blob that differs from the resident one only in the camera, stars_seed and / or sphere
+ * records is not uploaded again), rays and outputs in HOST memory, synchronous, on GPU 0.  The list is processed in chunks of 2^18
+ * rays (ray i keeps pix = i), so the device memory the call allocates does not grow with n. */
+int rt_trace_rays(const void *scene_blob, size_t blob_bytes, uint64_t n, const double *rays, uint32_t segs,
+                  const rt_ray_outputs *host_out, rt_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,15 @@ step_tests() {              # the whole -m gpu suite, one process
 step_tests_k() {            # K="expr": a slice of the suite
   timeout -k 10 600 python -m pytest tests -x -q -m gpu -k "$K" > ${O}_gpu_tests_k.log 2>&1; rc=$?; tail -15 ${O}_gpu_tests_k.log | cut -c1-400; return $rc
 }
+step_rays_tests() {         # the ray-list tests (tests/test_gpu_rays.py), with the differing-channel counts they print
+  timeout -k 10 500 python -m pytest tests/test_gpu_rays.py -x -q -s -m gpu > ${O}_rays_tests.log 2>&1; rc=$?; grep "^\.*RAYS\|passed\|failed" ${O}_rays_tests.log | cut -c1-300; return $rc
+}
+step_rays_timing() {        # [PARENT_LIB=<librt_hip.so of the parent commit>]: ray lists beside the strict frame (profiles/rays_timing.py)
+  timeout -k 10 400 python profiles/rays_timing.py 200 ${O}_rays_timing.json ${PARENT_LIB:-} > ${O}_rays_timing.log 2>&1; rc=$?; tail -70 ${O}_rays_timing.log | cut -c1-200; return $rc
+}
+step_panorama() {           # the equirectangular panorama of tools/panorama.py (the PNG stays in the output directory)
+  timeout -k 10 120 python tools/panorama.py default14_stars 1024 512 ${O}_panorama_default14_stars.png 0 1.5 4 > ${O}_panorama.log 2>&1; rc=$?; tail -2 ${O}_panorama.log; return $rc
+}
 step_bench() {              # the full default line and the driver's (plain) form
   timeout -k 10 500 python bench.py --full > ${O}_bench_n1.json 2>${O}_bench_n1.err; rc=$?; cut -c1-400 ${O}_bench_n1.json; [ $rc = 0 ] || { tail -5 ${O}_bench_n1.err; return $rc; }
   timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > ${O}_bench_n1_driver_form.json 2>${O}_bench_n1_driver_form.err; rc=$?; cut -c1-300 ${O}_bench_n1_driver_form.json; return $rc
