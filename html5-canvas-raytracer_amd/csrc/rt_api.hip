@@ -33,7 +33,8 @@ int ensure_device(int d) {
   std::lock_guard<std::mutex> lk(G.dev_mu);
   if (!s.stream) {
     hipStream_t st = nullptr;
-    HIP_TRY(hipMalloc(&s.d_counters, 3 * sizeof(unsigned long long)));
+    HIP_TRY(hipMalloc(&s.d_counters, 4 * sizeof(unsigned long long)));      // RT_FLAG_COUNT's three; [3]: the test build's uniform-path waves (rt_test_uniform_waves) - the product build never touches it
+    HIP_TRY(hipMemset(s.d_counters, 0, 4 * sizeof(unsigned long long)));
     HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     s.stream = st;                         // published last: a non-NULL stream means the device state is complete
   }

@@ -153,6 +153,9 @@ struct rt_launch {
   // test build only (librt_hip_test.so): per-node records of ONE sample's ray tree, for parity debugging
   double *probe;                     // RT_PROBE_NODES records of RT_PROBE_WORDS doubles, or NULL
   uint32_t probe_x, probe_y;         // the sample, in sample-grid coordinates
+  // ... and the uniform-material path of the one-wave product kernels (rt_kernel.hip: trace_pixel, UNI)
+  uint32_t no_uniform;               // RT_NO_UNIFORM_BLOCKS: every wave takes the general path
+  unsigned long long *uniform_waves; // counts the waves that took the path (rt_test_uniform_waves), or NULL
 #endif
 };
 

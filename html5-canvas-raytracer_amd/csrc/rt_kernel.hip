@@ -25,6 +25,9 @@
 //   * the per-hit, per-lane data (material + sampler parameters of the sphere that lane hit, texture
 //     descriptors), the primary-ray cull rectangles and the 10-double state of the stackless recursion
 //     fold live in LDS; the LDS image is one contiguous block in HBM, loaded behind the ray generation;
+//   * one-wave product kernels: a wave whose launch-table entry names ONE primary candidate and whose 64 rays all meet it (a floor
+//     block) has ONE material record: it is read with scalar loads from the image in HBM and the wave shades on the uniform-material
+//     path (trace_pixel, UNI) - no staging, no LDS access, no closest-hit selects, no node loop; the same statements otherwise;
 //   * texels are plain global loads (gfx950 has no image/texture path); the two 128 KB textures stay
 //     L2-resident;
 //   * product kernel only: "anchored" line-sphere discriminants for primary rays (camera) and shadow
@@ -148,7 +151,8 @@ __device__ __attribute__((noinline)) double rt_pow_generic(double x, double e) {
 // Integer exponents (every specular_exponent of the reference scene, main.js:108-123) by square-and-multiply: <= 2*log2(n)
 // multiplies instead of OCML's ~150-instruction pow.  Every path multiplies in the same sequence - for bit i = 0, 1, ...: r *= b
 // where bit i is set, b *= b - with r = b standing for the first r = 1.0 * b (exact), so the result does not depend on the path.
-__device__ __forceinline__ double rt_pow_spec(double x, int32_t n, const double *e) {
+template <class EP>                                                  // (EP: where the material lies - const double * in any address space)
+__device__ __forceinline__ double rt_pow_spec(double x, int32_t n, EP e) {
   const int32_t n0 = __builtin_amdgcn_readfirstlane(n);
   if (__ballot(n != n0) == 0ull) {
     // every lane here has the same exponent (a wave on one sphere: nearly all of them): walk its bits with scalar control
@@ -497,13 +501,52 @@ __device__ __forceinline__ float rt_q_of(float qp, float x, float c, float rp_ov
 }
 #endif
 
-template <bool REFRACT, bool COUNT, bool GRID, bool SS2, bool ITEM = false, bool W1 = false>
-__device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mtl, const rt_texture_desc *tex,
+// Where a node's material record comes from.  In general it is per-lane data: the sphere THAT LANE hit, fetched through a per-lane
+// offset (LDS; the many-sphere variants: HBM / L2).  A wave of a block whose launch-table entry names ONE primary candidate has one
+// record for all 64 lanes (trace_pixel, UNI): it is read where it lies in HBM through the constant address space, i.e. with scalar
+// loads into SGPRs at the point of use, like the geometry tables.  The node's code is the same source for both: it is written
+// against rt_mtl_src<UNI>::type and the accessors below.
+#define RT_AS4 __attribute__((address_space(4)))
+template <bool UNI> struct rt_mtl_src { typedef const rt_mtl type; };
+template <> struct rt_mtl_src<true> { typedef const rt_mtl RT_AS4 type; };
+template <bool UNI>
+__device__ __forceinline__ typename rt_mtl_src<UNI>::type *rt_mtl_at(const rt_mtl *mtl, uint32_t i) {     // a 32-bit byte offset from the table's base
+  if constexpr (UNI) return (const rt_mtl RT_AS4 *)((const char RT_AS4 *)(const void *)mtl + i * (uint32_t)sizeof(rt_mtl));
+  else return (const rt_mtl *)((const char *)mtl + i * (uint32_t)sizeof(rt_mtl));
+}
+__device__ __forceinline__ int rt_mtl_kind(const rt_mtl &m) { return m.sampler_kind; }
+__device__ __forceinline__ int rt_mtl_texture(const rt_mtl &m) { return m.texture; }
+// (uniform: the two 16-bit fields as ONE aligned 32-bit scalar load - gfx950 has no 16-bit scalar load, and a 16-bit field that is
+// not 4-byte aligned would come through the vector memory path)
+static_assert(offsetof(rt_mtl, sampler_kind) % 4 == 0 && offsetof(rt_mtl, texture) == offsetof(rt_mtl, sampler_kind) + 2, "rt_mtl: sampler_kind | texture share a word");
+__device__ __forceinline__ uint32_t rt_mtl_kind_word(const rt_mtl RT_AS4 &m) {
+  return *(const uint32_t RT_AS4 *)((const char RT_AS4 *)&m + offsetof(rt_mtl, sampler_kind));
+}
+__device__ __forceinline__ int rt_mtl_kind(const rt_mtl RT_AS4 &m) { return (int)(int16_t)(rt_mtl_kind_word(m) & 0xffffu); }
+__device__ __forceinline__ int rt_mtl_texture(const rt_mtl RT_AS4 &m) { return (int)(int16_t)(rt_mtl_kind_word(m) >> 16); }
+template <bool UNI>
+__device__ __forceinline__ rt_texture_desc rt_tex_desc(const rt_texture_desc *tex, int i) {
+  if constexpr (UNI) { const rt_texture_desc RT_AS4 *t = (const rt_texture_desc RT_AS4 *)(const void *)tex + i; return rt_texture_desc{t->width, t->height, t->texels_offset}; }
+  else return tex[i];
+}
+
+// One intersectWorld call tree for one sample.  UNI (product reflection-only one-wave-workgroup kernels only): the caller has found the
+// wave's launch-table entry to name exactly ONE primary candidate, cand_host & 255, and hands over `mtl` / `tex` as the image in HBM.
+// The call then shades the wave on the uniform-material path - the one anchored test without closest-hit selects, the candidate's
+// record in scalar registers, the sampler, the light loop's material tests and the specular exponent decided on the scalar unit, no
+// LDS access, no fold state, no node loop - if, wave-uniformly, the material spawns no ray at this depth, its sampler is colour,
+// checker or texture, EVERY lane's primary ray meets the candidate, and no lane's sampler coordinate lies in the boundary test's
+// prefilter band (derived, not measured: ~6 x 2^-20 per sample x 64 samples = ~4e-4 of the waves; the general path marks such samples); otherwise it returns false before it has stored or marked
+// anything and the caller runs the general path (UNI = false), unchanged.  The per-lane arithmetic is this function's own: the same
+// statements in the same order, with the general path's bookkeeping compiled out (if constexpr).  Returns true when rgb is set.
+template <bool REFRACT, bool COUNT, bool GRID, bool SS2, bool ITEM = false, bool W1 = false, bool UNI = false>
+__device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mtl, const rt_texture_desc *tex,
                                             [[maybe_unused]] double *acc, [[maybe_unused]] const rt_geom *cull_lds, [[maybe_unused]] const rt_geom cull0, [[maybe_unused]] uint32_t lane,
                                             [[maybe_unused]] double blk_x0, [[maybe_unused]] double blk_x1, [[maybe_unused]] double blk_y0,
                                             [[maybe_unused]] double blk_y1, v3 p, v3 d, double rgb[3], uint32_t cnt[3],
                                             [[maybe_unused]] bool is_probe, [[maybe_unused]] uint32_t cand_host,
                                             [[maybe_unused]] uint32_t own_sx = 0u, [[maybe_unused]] uint32_t own_sy = 0u, [[maybe_unused]] uint32_t own_f = 0u) {
+  static_assert(!UNI || (W1 && !REFRACT && !COUNT && !ITEM && !RT_STRICT), "uniform-material path: the one-wave-workgroup product kernels");
 #ifdef RT_TESTING
   uint32_t probe_n = 0;                                  // test build: nodes of this sample's ray tree recorded so far
   double probe_li = 0.0;
@@ -573,13 +616,16 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
   // 64-bit and one 32-bit select.
   double ht = RT_INF; int hcode = -1;
       // One candidate: the sqrt and the bookkeeping stay inside the hit branch (RT_PIN).
-#define RT_CAND(IDX, TCA, DISC)                                                               \
-      if (!((DISC) < 0.0)) {                                                                  \
-        RT_PIN();                                                                             \
+      // (the candidate root t_ of a ray that meets the sphere's line - DISC >= 0 -, and whether the ray starts inside: in_)
+#define RT_ROOT(TCA, DISC)                                                                    \
         const double thc_ = rt_sqrt_nn(DISC);                                                 \
         const double t0_ = (TCA) - thc_, t1_ = (TCA) + thc_;                                  \
         const bool in_ = (t0_ < eps);                                                         \
-        const double t_ = in_ ? t1_ : t0_;                                                    \
+        const double t_ = in_ ? t1_ : t0_;
+#define RT_CAND(IDX, TCA, DISC)                                                               \
+      if (!((DISC) < 0.0)) {                                                                  \
+        RT_PIN();                                                                             \
+        RT_ROOT(TCA, DISC)                                                                    \
         const bool closer_ = (t_ < ht) && !(t_ < eps);   /* strict <: first wins */           \
         ht = closer_ ? t_ : ht;                                                               \
         hcode = closer_ ? ((int)(2u * (IDX)) + (in_ ? 1 : 0)) : hcode;                        \
@@ -593,10 +639,12 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
         RT_CAND(IDX, tca_, disc_)                                                             \
       }
       // anchored form (origin = camera): disc = tca^2 - Ca
+#define RT_ANCHORED_DISC(G)                                                                   \
+        const double tca_ = d.x * (G).ox + d.y * (G).oy + d.z * (G).oz;                       \
+        const double disc_ = __builtin_fma(tca_, tca_, -(G).r2);
 #define RT_ANCHORED(IDX, G)                                                                   \
       {                                                                                       \
-        const double tca_ = d.x * (G).ox + d.y * (G).oy + d.z * (G).oz;                       \
-        const double disc_ = __builtin_fma(tca_, tca_, -(G).r2);                              \
+        RT_ANCHORED_DISC(G)                                                                   \
         RT_CAND(IDX, tca_, disc_)                                                             \
       }
       // 32-bit byte offset (at most 256 spheres x 32 bytes, times at most 16 lights in the light-anchored table): base +
@@ -606,6 +654,7 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
 #define RT_LOAD_PAIR(TAB, I) rt_load_geom_pair32((TAB), (uint32_t)(I))
       // Both loops are unrolled by two by hand (the pinned branches make them convergent, which rules out
       // the compiler's runtime unrolling); a pair's two records come with ONE s_load_dwordx16 (rt_load_geom_pair32).
+  if constexpr (UNI) { if (segs_left == 0) return false; }
   if (segs_left != 0) {
         // Primary rays.  First a wave-wide cull: lane j compares sphere j's conservative screen rectangle
         // (host, resolution-independent: bounds of X/D and Y/D over the pixels whose LINE meets the sphere)
@@ -617,7 +666,25 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
 #if !RT_STRICT
         // A block for which the table names at most two spheres its primary rays can meet at all (word 3 of its entry;
         // a floor block names the floor) tests those and skips the cull.
-        if (cand_host != 0u) {                           // count << 16 | second << 8 | first (loop indices, ascending)
+        if constexpr (UNI) {
+          // ONE candidate (the caller's test of the entry).  Its material decides first, on the scalar unit; then the one anchored test,
+          // whose root is every lane's closest hit if every lane has one: no (ht, hcode) selects.  A lane that misses - the horizon -
+          // sends the wave back to the general path.
+          const uint32_t i = cand_host & 255u;
+          const rt_geom g0 = RT_LOAD(ga, i);
+          typename rt_mtl_src<true>::type &mu = *rt_mtl_at<true>(mtl, i);
+          if ((mu.albedo[3] > 0.0 && segs_left > 1) || rt_mtl_kind(mu) == RT_SAMPLER_STARS) return false;
+          RT_ANCHORED_DISC(g0)
+          RT_ROOT(tca_, disc_)
+          const bool met_ = !(disc_ < 0.0) && (t_ < ht) && !(t_ < eps);
+          if (__ballot(!met_) != 0ull) return false;
+#if defined(RT_TESTING) && defined(RT_ABLATE_UNIFORM)   /* counting experiment only (profiles/ab_build.sh): what the launch issues WITHOUT the shading of these waves */
+          rgb[0] = rgb[1] = rgb[2] = 0.0;
+          return true;
+#endif
+          ht = t_; hcode = (int)(2u * i) + (in_ ? 1 : 0);
+        } else
+        if (cand_host != 0u) {                        // count << 16 | second << 8 | first (loop indices, ascending)
           { const uint32_t i = cand_host & 255u; const rt_geom g0 = RT_LOAD(ga, i); RT_ANCHORED(i, g0) }
           if (cand_host >= (2u << 16)) { const uint32_t i = (cand_host >> 8) & 255u; const rt_geom g0 = RT_LOAD(ga, i); RT_ANCHORED(i, g0) }
         } else
@@ -662,10 +729,10 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
   // A wave none of whose primary rays met a sphere of the loops, in a scene whose enclosing sphere is flat AND constant in colour
   // (the reference's skybox with a plain colour): every pixel of the wave is that sphere's ambient term, max(color*albedo[0],
   // min(1, color*0 + color*0)) (main.js:326-336 with no light and no child), which the host evaluated once.  Nothing else runs.
-  if (L.sky_fast && segs_left != 0 && __ballot(hcode >= 0) == 0ull) {
+  if (!UNI && L.sky_fast && segs_left != 0 && __ballot(hcode >= 0) == 0ull) {
     if (COUNT) { cnt[0]++; cnt[2] += N; }
     rgb[0] = L.sky_rgb[0]; rgb[1] = L.sky_rgb[1]; rgb[2] = L.sky_rgb[2];
-    return;
+    return true;
   }
 #endif
 
@@ -673,7 +740,7 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
     for (;;) {
       // ---------------- evaluate one intersectWorld node (segs_left > 0 here) ----------------
       if (COUNT) cnt[0]++;
-      if (!searched) {                              // reflection / refraction rays: any origin, generic form
+      if (!UNI && !searched) {                           // reflection / refraction rays: any origin, generic form
         bool scanned = false;
 #if !RT_STRICT
         if constexpr (GRID) {
@@ -730,12 +797,12 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
           if (i < NLOOP) { const rt_geom g0 = RT_LOAD(geom, i); RT_GENERIC(i, g0) }
         }
       }
-      [[maybe_unused]] const bool primary_node = searched;       // wave-uniform: this node is the primary ray's
+      [[maybe_unused]] const bool primary_node = UNI || searched;       // wave-uniform: this node is the primary ray's
       searched = false;
       // The enclosing sphere (every other sphere, light and the camera strictly inside it: a skybox) is
       // kept LAST in the device tables and outside the loops above: it can only be the closest hit of a
       // ray that hits nothing else.  Only the lanes still without a hit evaluate it.
-      if (enc != ~0u && hcode < 0) {
+      if (!UNI && enc != ~0u && hcode < 0) {
         if (L.enclosing_flat) {
           // ... and when that sphere is flat - no lighting, no children, a colour that does not depend on the hit point (the
           // reference's skybox: albedo [1,0,0,0,0], main.js:124) - WHERE the ray meets it does not matter: a ray that starts
@@ -747,16 +814,18 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
         }
       }
 #undef RT_ANCHORED
+#undef RT_ANCHORED_DISC
 #undef RT_GENERIC
 #undef RT_CAND
+#undef RT_ROOT
       if (COUNT) cnt[2] += N;
-      const int hi = hcode >> 1;
+      const int hi = UNI ? (int)(cand_host & 255u) : (hcode >> 1);      // (UNI: the one candidate - a scalar)
       const bool inside = (hcode & 1) != 0;
       bool descend = false;
 #if defined(RT_TESTING) && defined(RT_ABLATE_SHADE)
       if (true) { ret[0] = ht; ret[1] = (double)hcode; ret[2] = 0.0; } else
 #endif
-      if (hcode < 0) {                                // main.js:231 (with a flat sky of constant colour: that sky's pixel term, see rt_launch.hip bind_kernel)
+      if (!UNI && hcode < 0) {                        // main.js:231 (with a flat sky of constant colour: that sky's pixel term, see rt_launch.hip bind_kernel)
 #if RT_STRICT
         ret[0] = L.miss_color[0]; ret[1] = L.miss_color[1]; ret[2] = L.miss_color[2];
 #else
@@ -772,7 +841,7 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
         }
 #endif
       } else {
-        const rt_mtl &m = *(const rt_mtl *)((const char *)mtl + (uint32_t)hi * (uint32_t)sizeof(rt_mtl));      // per-lane index, a 32-bit offset (LDS; the many-sphere variant: HBM / L2)
+        typename rt_mtl_src<UNI>::type &m = *rt_mtl_at<UNI>(mtl, (uint32_t)hi);      // per-lane index, a 32-bit offset (LDS; the many-sphere variant: HBM / L2); UNI: the wave's one record, scalar loads
         // A2 ext part for the closest hit only (main.js:440-447; pure, so deferring it is exact)
         const v3 h = mk(p.x + d.x * ht, p.y + d.y * ht, p.z + d.z * ht);
 #if RT_STRICT
@@ -783,12 +852,18 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
         const double inv_r = m.inv_r;
         const v3 n = mk((h.x - m.origin[0]) * inv_r, (h.y - m.origin[1]) * inv_r, (h.z - m.origin[2]) * inv_r);
 #endif
-        const v3 l = inside ? mk(-n.x, -n.y, -n.z) : n;                 // hit.l, quirk q5
+        v3 l;                                                           // hit.l, quirk q5
+        // (UNI: a camera outside the candidate - no lane inside - takes n as it is, decided once for the wave: the same values, no selects)
+        // (Belt and braces: today the launch table names no sphere the camera is inside of - rt_block.h, rt_ball.everywhere - so under UNI no
+        // lane is ever inside and the scalar branch is always taken; the per-lane form stays so that this path's correctness does not
+        // rest on that property of the table.)
+        if (UNI && __ballot(inside) == 0ull) l = n;
+        else l = inside ? mk(-n.x, -n.y, -n.z) : n;
         const double a0 = m.albedo[0], a1 = m.albedo[1], a2 = m.albedo[2], a3 = m.albedo[3];
         const double a4 = REFRACT ? m.albedo[4] : 0.0;
 #if !RT_STRICT && !defined(RT_ABLATE_QAMP)     /* (RT_ABLATE_QAMP: timing experiment, profiles/ab_build.sh) */
         // Q of this hit (see above): for a bounced ray's hit, and for a primary hit that will spawn a ray (ht is at hand here)
-        if (RT_LVL(level) != 0 || ((a3 > 0.0 || a4 > 0.0) && segs_left > 1)) {
+        if (!UNI && (RT_LVL(level) != 0 || ((a3 > 0.0 || a4 > 0.0) && segs_left > 1))) {      // (UNI: a primary hit that spawns nothing)
           const float ir_ = (float)inv_r;
           const float q_ = RT_Q_OF(RT_Q_GET(level), (float)ht, ir_, __builtin_fabsf((float)dot(d, n)), RT_R_GET(level));
           RT_Q_SET(level, q_);
@@ -802,7 +877,7 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
 #if defined(RT_TESTING) && defined(RT_ABLATE_SAMPLER)   /* timing experiments only (profiles/ab_build.sh); never defined in the product build */
         const int kind = RT_SAMPLER_COLOR;
 #else
-        const int kind = m.sampler_kind;
+        const int kind = rt_mtl_kind(m);
 #endif
 #if RT_STRICT
         if (kind == RT_SAMPLER_TEXTURE) {
@@ -810,7 +885,7 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
           rt_atan2_asin(-n.z, -n.x, -n.y, &t_at, &t_as);
           const double u = RT_DIV_CONST(t_at, M_PI) / 2.0 + 0.5;   // main.js:446 (q6: two divisions)
           const double v = RT_DIV_CONST(t_as, M_PI / 2.0) / 2.0 + 0.5;  // main.js:447
-          const rt_texture_desc td = tex[m.texture];
+          const rt_texture_desc td = rt_tex_desc<UNI>(tex, rt_mtl_texture(m));
           const double xd = ceil(u * (double)td.width) - 1.0, yd = ceil(v * (double)td.height) - 1.0;
           uint32_t xi = (xd > 0.0) ? (uint32_t)xd : 0u, yi = (yd > 0.0) ? (uint32_t)yd : 0u;
           xi = min(xi, td.width - 1u); yi = min(yi, td.height - 1u);   // memory safety only; u,v <= 1
@@ -843,7 +918,10 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
           uint32_t iu = __builtin_amdgcn_alignbit((uint32_t)(su >> 32), (uint32_t)su, 20u) ^ 0x80000000u;       /* floor(x) for x in [0, 2^31) ... */ \
           uint32_t iv = __builtin_amdgcn_alignbit((uint32_t)(sv >> 32), (uint32_t)sv, 20u) ^ 0x80000000u;       \
           /* ... unless the fraction is within 2^-20 of an integer <=> the 20 fraction bits are 0xfffff, 0 or 1 (NaN, infinity: 0) */ \
-          if ((min(((uint32_t)su + 1u) & 0xfffffu, ((uint32_t)sv + 1u) & 0xfffffu) <= 2u)) {           \
+          const bool near_ = (min(((uint32_t)su + 1u) & 0xfffffu, ((uint32_t)sv + 1u) & 0xfffffu) <= 2u);           \
+          /* (UNI: a wave with such a sample - ~4e-4 of them by the band's width, not measured - has stored and marked nothing yet: it goes back to the general path, which decides below) */ \
+          if constexpr (UNI) { if (__ballot(near_) != 0ull) return false; }                                    \
+          if (!UNI && near_) {                                                                                  \
             RT_PIN();                                                                                             \
             iu = (uint32_t)(XU); iv = (uint32_t)(XV);                  /* truncation = floor (x >= 0); NaN -> 0 */  \
             const rt_launch __attribute__((address_space(4))) *K = rt_cold_args();                                \
@@ -872,32 +950,43 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
               rt_mark_append<SS2>(rt_pixel_of<SS2, W1>(L, t3));                                                        \
             }                                                                                                     \
           }
+        // (UNI: the sampler is the wave's - ONE inlined copy of the atan2 / asin pair serves both, its arguments chosen by the scalar kind)
+        [[maybe_unused]] double t_at, t_as;
+        if constexpr (UNI) {
+          if (kind == RT_SAMPLER_TEXTURE || kind == RT_SAMPLER_CHECKER) {
+            const bool tx_ = (kind == RT_SAMPLER_TEXTURE);
+            rt_atan2_asin(tx_ ? -n.z : -n.y, -n.x, tx_ ? -n.y : -n.z, &t_at, &t_as);
+          }
+        }
         if (kind == RT_SAMPLER_TEXTURE) {
-          double t_at, t_as;
-          rt_atan2_asin(-n.z, -n.x, -n.y, &t_at, &t_as);
+          if constexpr (!UNI) rt_atan2_asin(-n.z, -n.x, -n.y, &t_at, &t_as);
           const double u = RT_DIV_CONST(t_at, M_PI) / 2.0 + 0.5;   // main.js:446 (q6: two divisions)
           const double v = RT_DIV_CONST(t_as, M_PI / 2.0) / 2.0 + 0.5;  // main.js:447
-          const rt_texture_desc td = tex[m.texture];
+          const rt_texture_desc td = rt_tex_desc<UNI>(tex, rt_mtl_texture(m));
           const double xu = u * (double)td.width, xv = v * (double)td.height;
           // max(0, ceil(x) - 1) (main.js:344-345) is floor(x) for every x >= 0 that is not an integer, and the integers are marked:
           // the index comes out of the fixed-point sum (u, v in [0, 1]; widths and heights <= 16384)
-          RT_XY_INDEX(xu, xv, 1.0, 1.0)
+          RT_XY_INDEX(xu, xv, 1.0, 1.0)                              // (UNI: `return false` from HERE when a lane is inside the prefilter band)
           const uint32_t xi = min(iu, td.width - 1u), yi = min(iv, td.height - 1u);   // memory safety only; u,v <= 1
           const uint32_t texel = *(const uint32_t *)(rt_cold_args()->texel_base + td.texels_offset + ((size_t)yi * td.width + xi) * 4u);
           col[0] = RT_DIV_CONST((double)(texel & 255u), 255.0); col[1] = RT_DIV_CONST((double)((texel >> 8) & 255u), 255.0);
           col[2] = RT_DIV_CONST((double)((texel >> 16) & 255u), 255.0);
         } else if (kind == RT_SAMPLER_CHECKER) {
-          double t_at, t_as;
-          rt_atan2_asin(-n.y, -n.x, -n.z, &t_at, &t_as);
+          if constexpr (!UNI) rt_atan2_asin(-n.y, -n.x, -n.z, &t_at, &t_as);
           const double u = RT_DIV_CONST(t_at, M_PI) / 2.0 + 0.5;   // main.js:127 (its own axes)
           const double v = RT_DIV_CONST(t_as, M_PI / 2.0) / 2.0 + 0.5;  // main.js:128
           const double xu = u * m.c[6], xv = v * m.c[7];
-          RT_XY_INDEX(xu, xv, m.c[6], m.c[7])
+          RT_XY_INDEX(xu, xv, m.c[6], m.c[7])                        // (UNI: `return false` from HERE when a lane is inside the prefilter band)
           const int c = (int)((iu ^ iv) & 1u);                       // the parity of floor(x) = ToInt32(x) & 1 for x in [0, 2^31)
-          col[0] = m.c[3 * c]; col[1] = m.c[3 * c + 1]; col[2] = m.c[3 * c + 2];
+          if constexpr (UNI) {                                        // both colours are in scalar registers: the lane picks
+            // (opaque copies: the compiler otherwise selects the ADDRESS per lane and fetches through the vector memory path)
+            double k0 = m.c[0], k1 = m.c[1], k2 = m.c[2], k3 = m.c[3], k4 = m.c[4], k5 = m.c[5];
+            asm volatile("" : "+s"(k0), "+s"(k1), "+s"(k2), "+s"(k3), "+s"(k4), "+s"(k5));
+            col[0] = c ? k3 : k0; col[1] = c ? k4 : k1; col[2] = c ? k5 : k2;
+          } else { col[0] = m.c[3 * c]; col[1] = m.c[3 * c + 1]; col[2] = m.c[3 * c + 2]; }
 #undef RT_XY_INDEX
 #endif
-        } else if (kind == RT_SAMPLER_STARS) {
+        } else if (!UNI && kind == RT_SAMPLER_STARS) {      // (UNI: stars stay on the general path)
           // the sample's index in the FRAME (not in this call's tiles), recomputed from the work-item id so that it
           // costs no register outside this branch; `path` is the node's position in the ray tree
           uint32_t sx = own_sx, sy = own_sy, f = own_f;   // rt_retrace hands the sample and its frame over
@@ -1149,8 +1238,8 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
 #if !RT_STRICT
               // (materials in HBM - the reflection-only many-sphere variants -: the record's address is derived again here, from the hit
               // code, so that no 64-bit pointer lives across the shadow scans)
-              const rt_mtl *spec_m = &m;
-              if constexpr (GRID && !REFRACT && !COUNT) {
+              typename rt_mtl_src<UNI>::type *spec_m = &m;
+              if constexpr (GRID && !REFRACT && !COUNT && !UNI) {
                 uint32_t off_ = (uint32_t)hi * (uint32_t)sizeof(rt_mtl);
                 asm volatile("" : "+v"(off_));
                 spec_m = (const rt_mtl *)((const char *)mtl + off_);
@@ -1179,7 +1268,7 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
 #endif
         v3 r = mk(0, 0, 0); double rlen = 0.0;
         // (with segs_left == 1 the child returns [0,0,0] at main.js:221 whatever its direction: skip it)
-        if (a3 > 0.0 && segs_left > 1) r = unit(reflect(d, nq), &rlen);
+        if (!UNI && a3 > 0.0 && segs_left > 1) r = unit(reflect(d, nq), &rlen);     // (UNI: decided against, for the wave, before the hit test)
         // A5 refraction direction
         v3 f = mk(0, 0, 0); double flen = 0.0;
         if (REFRACT && a4 > 0.0 && segs_left > 1) {
@@ -1200,7 +1289,7 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
 #pragma unroll
           for (int c = 0; c < 3; c++) col[c] = acc[(10 + c) * RT_WG_THREADS];
         }
-        const bool go_r = (rlen != 0.0);
+        const bool go_r = !UNI && (rlen != 0.0);
         const bool go_f = REFRACT && (flen != 0.0);
 #ifdef RT_TESTING
         if (is_probe && probe_n < RT_PROBE_NODES) {
@@ -1362,6 +1451,7 @@ __device__ __forceinline__ void trace_pixel(const rt_launch &L, const rt_mtl *mt
 #undef RT_LOAD
 #undef RT_LOAD_PAIR
   rgb[0] = ret[0]; rgb[1] = ret[1]; rgb[2] = ret[2];
+  return true;
 }
 
 // W1: one-wave workgroups (rt_pixel_of), for the reflection-only variants.  A workgroup's waves are placed together: a 4-wave
@@ -1417,14 +1507,23 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
   const uint32_t image_vec = image_words >> 1;                                     // 16-byte units (GRID: the image is whole units)
   [[maybe_unused]] rt_u4 piece[RT_STAGE_PIECES];
   [[maybe_unused]] double stage0 = 0.0;
-  if constexpr (!IMAGE_IN_LDS) {
-  } else if constexpr (GRID || W1) {           // (W1, few spheres: 8 spheres are 112 units - two loads per work-item of the one wave)
-    const rt_u4 *__restrict__ image4 = (const rt_u4 *)L.lds_image;
+  const auto stage_issue = [&](const uint32_t tid) __attribute__((always_inline)) {
+    if constexpr (!IMAGE_IN_LDS) {
+    } else if constexpr (GRID || W1) {           // (W1, few spheres: 8 spheres are 112 units - two loads per work-item of the one wave)
+      const rt_u4 *__restrict__ image4 = (const rt_u4 *)L.lds_image;
 #pragma unroll
-    for (uint32_t i = 0; i < RT_STAGE_PIECES; i++) if (i * KT < image_vec) piece[i] = image4[tid + i * KT];
-  } else {
-    stage0 = (tid < image_words) ? image[tid] : 0.0;
-  }
+      for (uint32_t i = 0; i < RT_STAGE_PIECES; i++) if (i * KT < image_vec) piece[i] = image4[tid + i * KT];
+    } else {
+      stage0 = (tid < image_words) ? image[tid] : 0.0;
+    }
+  };
+  // The one-wave product kernels know a class of blocks whose waves need no LDS image at all (the uniform-material path below): they
+  // read their launch-table entry first and issue the staging loads only for a wave that will use them.  Every other kernel
+  // issues them here, ahead of everything.
+  // (not the many-sphere 2x2 form, cfg5's: the path's scalar material costs that kernel a fifth spilled scalar register, one more
+  // than tests/test_kernel_resources.py allows it)
+  constexpr bool UNI_OK = W1 && !REFRACT && !COUNT && !RT_STRICT && !(GRID && SS2);
+  if constexpr (!UNI_OK) stage_issue(tid);
   const rt_mtl *mtl = IMAGE_IN_LDS ? (const rt_mtl *)lds_raw : (const rt_mtl *)L.lds_image;
   const rt_texture_desc *tex = IMAGE_IN_LDS ? (const rt_texture_desc *)(lds_raw + mtl_words) : (const rt_texture_desc *)((const double *)L.lds_image + mtl_words);
   const rt_geom *cull_lds = (const rt_geom *)(lds_raw + mtl_words + tex_words);
@@ -1448,11 +1547,23 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
   // the others do not send them over the links - are launch tables of their own, without the entries the launch leaves out: this
   // kernel knows nothing of it.  As a test of the launch record here it cost the headline 1.5 %.)
 #endif
+  // Blocks that show ONE sphere (word 3 of the entry: count 1 - a floor, a wall, a planet filling the view; nine in ten of the
+  // headline's tracing waves): the wave tries the uniform-material path (trace_pixel, UNI) - that sphere's record in scalar registers,
+  // no staging, no LDS access, no node loop.  A one-wave workgroup decides for itself: no barrier is involved.  The four-wave forms
+  // (peer stores, a moved camera's first frame, the general kernel) do not take the path.
+  [[maybe_unused]] bool uni_try = false;
+  if constexpr (UNI_OK) {
+    uni_try = !P0.sky && (P0.cand >> 16) == 1u;
+#ifdef RT_TESTING
+    if (L.no_uniform) uni_try = false;                  // test build (RT_NO_UNIFORM_BLOCKS): every wave on the general path
+#endif
+    if (!uni_try && !P0.sky) stage_issue(tid);
+  }
   double rgb[3];
   uint32_t cnt[3] = {0u, 0u, 0u};
   // A workgroup the table build marked as showing no sphere (rt_block.h: the cone test, made once for the workgroup's
-  // box) stores the background constant: no staging, no barrier, no ray, no cull.  (The staging loads issued above are simply
-  // never waited for.)  45 % of the headline's workgroups.
+  // box) stores the background constant: no staging, no barrier, no ray, no cull.  (Staging loads issued above - the four-wave forms -
+  // are simply never waited for.)  45 % of the headline's workgroups.
   if (P0.sky) {
     rgb[0] = L.sky_rgb[0]; rgb[1] = L.sky_rgb[1]; rgb[2] = L.sky_rgb[2];
   } else {
@@ -1484,35 +1595,61 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
   const v3 ray = mk(rawray.x * rl, rawray.y * rl, rawray.z * rl);
 #endif
 
-  // finish the staging (first use of LDS: the cull table or the closest hit's material inside trace_pixel)
-  if constexpr (!IMAGE_IN_LDS) {
-  } else if constexpr (GRID || W1) {
-    rt_u4 *lds4 = (rt_u4 *)lds_raw;
-    const rt_u4 *__restrict__ image4 = (const rt_u4 *)L.lds_image;
-#pragma unroll
-    for (uint32_t i = 0; i < RT_STAGE_PIECES; i++) {
-      const uint32_t k = tid + i * KT;
-      if (i * KT < image_vec && k < image_vec) lds4[k] = piece[i];
-    }
-    for (uint32_t k = tid + RT_STAGE_PIECES * KT; k < image_vec; k += KT) lds4[k] = image4[k];     // more than 73 spheres (one-wave workgroups: 17)
-  } else {
-    if (tid < image_words) lds_raw[tid] = stage0;
-    for (uint32_t k = tid + RT_WG_THREADS; k < image_words; k += RT_WG_THREADS) lds_raw[k] = image[k];
-  }
-  if constexpr (IMAGE_IN_LDS) __syncthreads();
-
-  // this wave's pixel block in the units of d0/d1 (every lane holds the same four numbers)
-  const double bw = SS2 ? 15.0 : 7.0, bh = SS2 ? 3.0 : 7.0;
-  const double lx = SS2 ? (double)(2u * ((lane >> 2) & 7u) + (sub & 1u)) : (double)(lane & 7u);
-  const double ly = SS2 ? (double)(2u * (lane >> 5) + (sub >> 1)) : (double)(lane >> 3);
-  const double blk_x0 = d0 - lx, blk_x1 = blk_x0 + bw, blk_y1 = d1 + ly, blk_y0 = blk_y1 - bh;
 #ifdef RT_TESTING
   const bool is_probe = L.probe != nullptr && sx == L.probe_x && sy == L.probe_y && blockIdx.z == 0;
 #else
   const bool is_probe = false;
 #endif
-  trace_pixel<REFRACT, COUNT, GRID, SS2, false, W1>(L, mtl, tex, acc, cull_lds, cull0, lane, blk_x0, blk_x1, blk_y0, blk_y1, o, ray, rgb, cnt, is_probe, P0.cand);
+  // finish the staging (first use of LDS: the cull table or the closest hit's material inside trace_pixel)
+  const auto stage_finish = [&](const uint32_t tid) __attribute__((always_inline)) {
+    if constexpr (!IMAGE_IN_LDS) {
+    } else if constexpr (GRID || W1) {
+      rt_u4 *lds4 = (rt_u4 *)lds_raw;
+      const rt_u4 *__restrict__ image4 = (const rt_u4 *)L.lds_image;
+#pragma unroll
+      for (uint32_t i = 0; i < RT_STAGE_PIECES; i++) {
+        const uint32_t k = tid + i * KT;
+        if (i * KT < image_vec && k < image_vec) lds4[k] = piece[i];
+      }
+      for (uint32_t k = tid + RT_STAGE_PIECES * KT; k < image_vec; k += KT) lds4[k] = image4[k];     // more than 73 spheres (one-wave workgroups: 17)
+    } else {
+      if (tid < image_words) lds_raw[tid] = stage0;
+      for (uint32_t k = tid + RT_WG_THREADS; k < image_words; k += RT_WG_THREADS) lds_raw[k] = image[k];
+    }
+  };
+  // the uniform-material path: materials and texture descriptors where they lie in HBM, read with scalar loads.  A wave it turns
+  // away (a horizon, a mirror, stars) has touched nothing yet: it stages now and takes the general path
+  [[maybe_unused]] bool uni_done = false;
+  if constexpr (UNI_OK) {
+    if (uni_try) {
+      uni_done = trace_pixel<REFRACT, COUNT, GRID, SS2, false, W1, true>(L, (const rt_mtl *)L.lds_image, (const rt_texture_desc *)((const double *)L.lds_image + mtl_words), acc,
+                                                                         cull_lds, cull0, lane, 0.0, 0.0, 0.0, 0.0, o, ray, rgb, cnt, is_probe, P0.cand);
+      if (!uni_done) {
+        uint32_t tid4 = threadIdx.x;
+        asm volatile("" : "+v"(tid4));                 // opaque: no address is kept in registers across the attempt
+        stage_issue(tid4);
+        stage_finish(tid4);
+      }
+#ifdef RT_TESTING
+      else if (lane == 0u && L.uniform_waves != nullptr) atomicAdd(L.uniform_waves, 1ull);      // test build: waves that took the path
+#endif
+    }
   }
+  if (!uni_done) {                                    // the general path: every wave that did not shade above
+    if (!UNI_OK || !uni_try) stage_finish(tid);
+    if constexpr (IMAGE_IN_LDS) __syncthreads();
+
+    // this wave's pixel block in the units of d0/d1 (every lane holds the same four numbers)
+    const double bw = SS2 ? 15.0 : 7.0, bh = SS2 ? 3.0 : 7.0;
+    const double lx = SS2 ? (double)(2u * ((lane >> 2) & 7u) + (sub & 1u)) : (double)(lane & 7u);
+    const double ly = SS2 ? (double)(2u * (lane >> 5) + (sub >> 1)) : (double)(lane >> 3);
+    // (a wave the uniform-material path turned away has an entry that names its candidate: it skips the cull, the only reader of the
+    // block's rectangle - which is then not computed, so that d0 / d1 are not held in registers across that attempt)
+    double blk_x0 = 0.0, blk_x1 = 0.0, blk_y0 = 0.0, blk_y1 = 0.0;
+    if (!UNI_OK || !uni_try) { blk_x0 = d0 - lx; blk_x1 = blk_x0 + bw; blk_y1 = d1 + ly; blk_y0 = blk_y1 - bh; }
+    trace_pixel<REFRACT, COUNT, GRID, SS2, false, W1>(L, mtl, tex, acc, cull_lds, cull0, lane, blk_x0, blk_x1, blk_y0, blk_y1, o, ray, rgb, cnt, is_probe, P0.cand);
+  }                                                    // if (!uni_done)
+  }                                                    // else of if (P0.sky)
 
   // ---- A10 RGBA8 store ----
   uint32_t tid2 = threadIdx.x;

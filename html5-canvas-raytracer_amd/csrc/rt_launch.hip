@@ -43,6 +43,20 @@ extern "C" int rt_test_probe(rt_scene_dev *s, uint32_t w, uint32_t h, uint32_t s
   (void)hipFree(d_probe); (void)hipFree(d_row);
   return rc;
 }
+
+// Test build only: how many waves of the device's product launches have taken the uniform-material path (rt_kernel.hip: trace_pixel,
+// UNI) since the last call; the device is drained first, and the counter starts again at zero.
+extern "C" int rt_test_uniform_waves(int device, unsigned long long *out_waves) {
+  if (!out_waves) return fail(RT_ERR_INVALID, "rt_test_uniform_waves: NULL argument");
+  int rc = ensure_device(device);
+  if (rc) return rc;
+  device_state &D = G.dev[device];
+  HIP_TRY(hipSetDevice(D.hip_id));                    // (ensure_device has, too: said here because the next call drains THIS device)
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out_waves, D.d_counters + 3, sizeof *out_waves, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemset(D.d_counters + 3, 0, sizeof *out_waves));
+  return RT_OK;
+}
 #endif
 
 extern "C" int rt_render_batch_device(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, uint32_t n_frames, void *d_out,
@@ -298,6 +312,8 @@ int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *t
   if (count) HIP_TRY(hipMemsetAsync(D.d_counters, 0, 3 * sizeof(unsigned long long), stream));
 #ifdef RT_TESTING
   L.probe = g_probe.d_buf; L.probe_x = g_probe.x; L.probe_y = g_probe.y;
+  L.no_uniform = getenv("RT_NO_UNIFORM_BLOCKS") ? 1u : 0u;     // A/B switch, read per call: every wave on the general path (rt_kernel.hip: trace_pixel, UNI)
+  L.uniform_waves = D.d_counters + 3;
 #endif
 
   event_timer timer;                                     // (a stats call)
