@@ -151,7 +151,7 @@ struct rt_scene_dev {
   // when the camera moves (rt_scene_set_camera).
   uint8_t *arena = nullptr;
   size_t arena_bytes = 0;
-  void *d_blob;                  // the uploaded scene blob (its texels and lights; its sphere records are the OBJECT BLOCK's)
+  void *d_blob;                  // the uploaded scene blob (its texels; its sphere records are the OBJECT BLOCK's, its lights travel by value from `lights`)
   rt_texture_desc *d_texdesc;    // RT_MAX_TEXTURES descriptors (zero padded)
   double *d_cones;               // the bounce table's cell cones (rt_tables.cpp: bounce_cell_cones), or NULL (no bounce table)
   // The OBJECT BLOCK: what depends on the spheres but not on the camera, at offsets o_* inside it:
@@ -163,7 +163,8 @@ struct rt_scene_dev {
   //   o_sg       light grids for the product kernel's loop order (has_sg: more than RT_SGRID_MIN_LOOP loop spheres)
   //   o_bt       bounce table for the same order (has_bt: more than RT_BTABLE_MIN_LOOP loop spheres and depth >= 2)
   // Everything up to the shadow grids' masks (obj_host_bytes) is written by the host; the masks and the bounce table are built from it
-  // (rt_objects_gpu.hip after a move; rt_tables.cpp at upload).  TWO blocks, like the camera blocks: generation g reads block g & 1,
+  // (rt_objects_gpu.hip after a move; rt_tables.cpp at upload).  Of these the anchored records and the light grids depend on the lights:
+  // a light move rewrites them alone, for the lights that moved.  TWO blocks, like the camera blocks: generation g reads block g & 1,
   // so that rt_scene_set_objects can write the next one while launches with the current spheres are still running.
   uint8_t *d_obj_buf[2];
   size_t obj_bytes, obj_host_bytes;
@@ -171,6 +172,7 @@ struct rt_scene_dev {
   bool has_sg, has_bt;
   uint64_t obj_version = 0;      // bumped by every object move; slot_version[b]: the version object block b holds
   uint64_t slot_version[2] = {0, 0};
+  double slot_lights[2][RT_MAX_LIGHTS][3];   // the light positions object block b's anchored records and shadow grids were made for (rt_scene_set_lights)
   // The camera block: per ordering [anchored at the camera N | cull rectangles N], then (few spheres) the LDS images.  TWO of them:
   // camera generation g lives in block g & 1, so that the block of the NEXT camera can be written - on the scene's own side stream,
   // by rt_scene_set_camera - while launches with the current one are still running.

@@ -112,29 +112,43 @@ int ensure_rccl(int ndev) {
 int scene_for(int device, const void *blob, size_t bytes, rt_scene_dev **out) {
   device_state &D = G.dev[device];
   if (D.cached_scene && D.cached_blob.size() == bytes && memcmp(D.cached_blob.data(), blob, bytes) == 0) { *out = D.cached_scene; return RT_OK; }
-  // the same scene from another camera, with another stars seed and / or with moved or restyled spheres (an animation: lookAt per
-  // frame, main.js:92-100, a new sky per redraw, main.js:135-139, 180, objects a page changes between redraws): the resident scene
-  // takes the spheres of the smallest range that covers the differences, then the camera, then the seed
+  // the same scene from another camera, with another stars seed, with moved or restyled spheres and / or with moved or dimmed lights
+  // (an animation: lookAt per frame, main.js:92-100, a new sky per redraw, main.js:135-139, 180, objects and lights a page changes
+  // between redraws, main.js:283-284): the resident scene takes the spheres of the smallest range that covers the differences, then
+  // the lights of theirs, then the intensity, then the camera, then the seed
   if (D.cached_scene && D.cached_blob.size() == bytes) {
     const size_t c0 = offsetof(rt_scene_header, cam_origin), c1 = c0 + 12 * sizeof(double);
+    const size_t i0 = offsetof(rt_scene_header, light_intensity), i1 = i0 + sizeof(double);
     const size_t s0 = offsetof(rt_scene_header, stars_seed), s1 = s0 + sizeof(uint32_t);
-    static_assert(c1 <= s0, "the camera lies in front of the stars seed in rt_scene_header");
+    static_assert(c1 <= i0 && i1 <= s0, "the camera lies in front of the light intensity, and that in front of the stars seed in rt_scene_header");
     const uint8_t *a = D.cached_blob.data(), *b = (const uint8_t *)blob;
     const rt_scene_header *nh = (const rt_scene_header *)blob;
-    const size_t o0 = nh->objects_offset, o1 = o0 + (size_t)nh->n_objects * sizeof(rt_sphere);
-    // the header's other fields equal (the object table's place and size included), then everything outside the object table
-    if (memcmp(a, b, c0) == 0 && memcmp(a + c1, b + c1, s0 - c1) == 0 && memcmp(a + s1, b + s1, sizeof(rt_scene_header) - s1) == 0 &&
-        memcmp(a + sizeof(rt_scene_header), b + sizeof(rt_scene_header), o0 - sizeof(rt_scene_header)) == 0 && memcmp(a + o1, b + o1, bytes - o1) == 0) {
-      const rt_sphere *na = (const rt_sphere *)(a + o0), *nb = (const rt_sphere *)(b + o0);
-      uint32_t first = nh->n_objects, last = 0;
-      for (uint32_t i = 0; i < nh->n_objects; i++)
-        if (memcmp(&na[i], &nb[i], sizeof(rt_sphere)) != 0) { if (first == nh->n_objects) first = i; last = i + 1; }
-      if ((first == nh->n_objects || rt_scene_set_objects(D.cached_scene, first, last - first, nb + first, nullptr) == RT_OK) &&
-          rt_scene_set_camera(D.cached_scene, nh->cam_origin, nh->cam_axis_x, nh->cam_axis_y, nh->cam_axis_z, nullptr) == RT_OK &&
-          rt_scene_set_stars_seed(D.cached_scene, nh->stars_seed) == RT_OK) {
-        memcpy(D.cached_blob.data(), b, bytes);
-        *out = D.cached_scene;
-        return RT_OK;
+    // the header's other fields equal (the places and sizes of the object and light tables included: the resident blob's, which
+    // rt_scene_validate has seen), then everything outside the two tables
+    if (memcmp(a, b, c0) == 0 && memcmp(a + c1, b + c1, i0 - c1) == 0 && memcmp(a + i1, b + i1, s0 - i1) == 0 && memcmp(a + s1, b + s1, sizeof(rt_scene_header) - s1) == 0) {
+      const size_t o0 = nh->objects_offset, o1 = o0 + (size_t)nh->n_objects * sizeof(rt_sphere);
+      const size_t l0 = nh->lights_offset, l1 = l0 + (size_t)nh->n_lights * 24u;
+      const size_t t0 = o0 < l0 ? o0 : l0, t1 = o0 < l0 ? o1 : l1, u0 = o0 < l0 ? l0 : o0, u1 = o0 < l0 ? l1 : o1;     // the tables in blob order
+      if (t0 >= sizeof(rt_scene_header) && t1 <= u0 && u1 <= bytes && memcmp(a + sizeof(rt_scene_header), b + sizeof(rt_scene_header), t0 - sizeof(rt_scene_header)) == 0 &&
+          memcmp(a + t1, b + t1, u0 - t1) == 0 && memcmp(a + u1, b + u1, bytes - u1) == 0) {
+        const rt_sphere *na = (const rt_sphere *)(a + o0), *nb = (const rt_sphere *)(b + o0);
+        uint32_t first = nh->n_objects, last = 0;
+        for (uint32_t i = 0; i < nh->n_objects; i++)
+          if (memcmp(&na[i], &nb[i], sizeof(rt_sphere)) != 0) { if (first == nh->n_objects) first = i; last = i + 1; }
+        uint32_t lfirst = nh->n_lights, llast = 0;
+        for (uint32_t k = 0; k < nh->n_lights; k++)
+          if (memcmp(a + l0 + 24u * k, b + l0 + 24u * k, 24u) != 0) { if (lfirst == nh->n_lights) lfirst = k; llast = k + 1; }
+        double xyz[RT_MAX_LIGHTS][3];                    // (the blob's own bytes may be unaligned)
+        if (lfirst < llast && llast - lfirst <= RT_MAX_LIGHTS) memcpy(xyz, b + l0 + 24u * lfirst, (size_t)(llast - lfirst) * 24u);
+        if ((first == nh->n_objects || rt_scene_set_objects(D.cached_scene, first, last - first, nb + first, nullptr) == RT_OK) &&
+            (lfirst == nh->n_lights || rt_scene_set_lights(D.cached_scene, lfirst, llast - lfirst, &xyz[0][0], nullptr) == RT_OK) &&
+            rt_scene_set_light_intensity(D.cached_scene, nh->light_intensity) == RT_OK &&
+            rt_scene_set_camera(D.cached_scene, nh->cam_origin, nh->cam_axis_x, nh->cam_axis_y, nh->cam_axis_z, nullptr) == RT_OK &&
+            rt_scene_set_stars_seed(D.cached_scene, nh->stars_seed) == RT_OK) {
+          memcpy(D.cached_blob.data(), b, bytes);
+          *out = D.cached_scene;
+          return RT_OK;
+        }
       }
     }
   }

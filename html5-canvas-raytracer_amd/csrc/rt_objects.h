@@ -15,6 +15,14 @@
 // finite (not NaN, not infinite)
 RT_HD inline bool rt_finite(double x) { return fabs(x) <= DBL_MAX; }
 
+// A sphere anchored at a point `a` (a light: the object block's [anchored at light k] records): {o - a, |o - a|^2 - r2}, the constant
+// term of the ray-sphere quadratic for rays that start at `a`.  fill_object_block (rt_scene.hip) and the light move's kernel
+// (rt_objects_gpu.hip: rt_light_anchor) both state it from here.
+RT_HD inline rt_geom rt_anchored(const double origin[3], double r2, const double a[3]) {
+  const double lx = origin[0] - a[0], ly = origin[1] - a[1], lz = origin[2] - a[2];
+  return rt_geom{lx, ly, lz, (lx * lx + ly * ly + lz * lz) - r2};
+}
+
 // The root interval of the quadratic of one axis of a cull rectangle (rt_tables.cpp: cull_rect states the geometry); the whole axis
 // where the image is unbounded along it or the case is doubtful.
 RT_HD inline void rt_axis_bounds(double c_axis, double c_z, double s_axis, double s_z, double r2, double *lo, double *hi) {

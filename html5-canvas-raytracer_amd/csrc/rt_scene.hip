@@ -1,8 +1,9 @@
 // rt_scene.hip — a resident scene (include/rt_hip.h: rt_scene_*): upload and free, the host decisions that depend on its spheres and
-// its camera, the blocks it keeps in HBM, the camera / object / stars-seed moves (the generation pipeline), the launch decisions of
-// its product launches and its launch tables (built on the GPU, rt_tables_gpu.hip).
+// its camera, the blocks it keeps in HBM, the camera / object / light / stars-seed moves (the generation pipeline), the launch
+// decisions of its product launches and its launch tables (built on the GPU, rt_tables_gpu.hip).
 
 #include "rt_api_internal.h"
+#include "rt_objects.h"
 
 // ------------------------------------------------------------------------------------ launch decisions of a resident scene
 namespace rt_api {
@@ -139,8 +140,8 @@ void camera_decisions(rt_scene_dev *s) {
   scene_tile_weights(hd, ob, &s->host_cull, &s->tile_weight);
 }
 
-// What of a resident scene depends on its spheres and is decided on the host - in ONE place, for rt_scene_upload and
-// rt_scene_set_objects alike: the device copy of the records (host_blob's, with 1/r in `reserved`), ordering B, the kernel
+// What of a resident scene depends on its spheres (and its lights: the coincidence below) and is decided on the host - in ONE place,
+// for rt_scene_upload, rt_scene_set_objects and rt_scene_set_lights alike: the device copy of the records (host_blob's, with 1/r in `reserved`), ordering B, the kernel
 // variant, the strict-kernel coincidences, the samplers' boundary tolerance, the mark weight rule and the enclosing sphere's
 // background.  Reads host_objects (the records as given); `enclosing` is decided already.
 void object_decisions(rt_scene_dev *s) {
@@ -238,16 +239,12 @@ void fill_object_block(const rt_scene_dev *s, uint8_t *dst) {
   const rt_sphere *pob_a = (const rt_sphere *)(s->host_blob.data() + hd->objects_offset);
   memcpy(dst + s->o_objs, pob_a, (size_t)NO * sizeof(rt_sphere));
   const size_t geom_per_order = (size_t)NO * (1 + NL);                 // [plain N | anchored at light k: NL x N]
-  auto anchored = [&](const rt_sphere &o, const double a[3]) {
-    const double lx = o.origin[0] - a[0], ly = o.origin[1] - a[1], lz = o.origin[2] - a[2];
-    return rt_geom{lx, ly, lz, (lx * lx + ly * ly + lz * lz) - o.r2};
-  };
   for (int ord = 0; ord < n_ord; ord++) {
     const rt_sphere *src = ord ? s->host_objects_b.data() : pob_a;
     rt_geom *g = (rt_geom *)(dst + s->o_geom) + ord * geom_per_order;
     for (uint32_t i = 0; i < NO; i++) {
       g[i] = rt_geom{src[i].origin[0], src[i].origin[1], src[i].origin[2], src[i].r2};
-      for (uint32_t k = 0; k < NL; k++) g[(size_t)NO * (1 + k) + i] = anchored(src[i], s->lights[k]);
+      for (uint32_t k = 0; k < NL; k++) g[(size_t)NO * (1 + k) + i] = rt_anchored(src[i].origin, src[i].r2, s->lights[k]);
     }
   }
   ((rt_geom *)(dst + s->o_geom))[geom_per_order * n_ord] = rt_geom{0.0, 0.0, 0.0, -1.0};   // one record of padding: the kernel's scans fetch a light's first two records at once, also when it has one
@@ -293,6 +290,7 @@ extern "C" int rt_scene_upload(int device, const void *blob, size_t bytes, rt_sc
   const rt_sphere *ob = (const rt_sphere *)(base + hd->objects_offset);
   memset(s->lights, 0, sizeof s->lights);
   if (hd->n_lights) memcpy(s->lights, base + hd->lights_offset, hd->n_lights * 24u);
+  memcpy(s->slot_lights[0], s->lights, sizeof s->lights); memcpy(s->slot_lights[1], s->lights, sizeof s->lights);
   rt_texture_desc (&descs)[RT_MAX_TEXTURES] = s->descs;
   memset(descs, 0, sizeof descs);
   if (hd->n_textures) memcpy(descs, base + hd->textures_offset, hd->n_textures * sizeof(rt_texture_desc));
@@ -427,12 +425,18 @@ int ensure_side(rt_scene_dev *s) {
   return RT_OK;
 }
 
-// The host state of the scene has just changed - its camera (rt_scene_set_camera) or its spheres (rt_scene_set_objects,
-// `objects_moved`), host decisions included - and generation old_gen + 1 begins: on the side stream, behind the launches that read
-// its blocks last (generation old_gen - 1), the camera block is copied and the object block brought up to date (a move: the staged
-// host part, then the masks and the bounce table on the GPU; a camera move after an object move: a copy of the other block), and
-// the launch tables the previous generation's frames used are rebuilt.  Everything keyed to the generation - launch tables, mark
-// counts, camera_uses - is stale from here on.  launch_mu held.
+// The host state of the scene has just changed - its camera (rt_scene_set_camera), its spheres (rt_scene_set_objects,
+// `objects_moved`) or its lights (rt_scene_set_lights), host decisions included - and generation old_gen + 1 begins: on the side
+// stream, behind the launches that read its blocks last (generation old_gen - 1), the camera block is copied and the object block
+// brought up to date, and the launch tables the previous generation's frames used are rebuilt.  The object block, in two steps:
+//   its spheres (slot_version)  an object move: the staged host part, then the masks of every light and the bounce table on the GPU;
+//                               a move of another kind after an object move: a copy of the other block;
+//   its lights (slot_lights)    the lights it holds at other positions than the scene's - the moved ones after a light move, and
+//                               whatever the move before left behind in this block - get their anchored records, their grid
+//                               headers (host-computed, staged) and their grids' masks from rt_objects_gpu.hip.  Nothing else of the
+//                               block depends on a light: no bounce table, no staged object block for a light move.
+// Lights reach the kernels by value (rt_light_list), from s->lights: the copy in d_blob is the upload's and is not read.
+// Everything keyed to the generation - launch tables, mark counts, camera_uses - is stale from here on.  launch_mu held.
 int next_generation(rt_scene_dev *s, uint64_t old_gen, bool objects_moved) {
   // launches of this scene in flight on SEVERAL caller streams: no single event covers them (rare: drain the device)
   if (s->any_launch && s->several_streams) { HIP_TRY(hipDeviceSynchronize()); s->any_launch = false; s->several_streams = false; s->launched_since_move = false; s->old_done_valid[0] = s->old_done_valid[1] = false; }
@@ -448,23 +452,42 @@ int next_generation(rt_scene_dev *s, uint64_t old_gen, bool objects_moved) {
   uint8_t *st = acquire_stage(s, &slot);
   fill_camera_block(s, st);
   if (objects_moved) s->obj_version++;
+  uint8_t *blk = s->d_obj_buf[b];
+  const uint32_t NO = s->hd.n_objects, NL = s->hd.n_lights, n_loop = s->has_b ? NO - 1u : NO;
+  const rt_sphere *loop = (const rt_sphere *)(blk + (s->has_b ? s->o_objs_b : s->o_objs));
+  uint8_t *so = st + up256(s->cam_bytes);              // (the slot's second part: an object move's host part, or a light move's grid headers)
   if (s->slot_version[b] != s->obj_version) {
-    uint8_t *blk = s->d_obj_buf[b];
     hipError_t e = hipSuccess;
     if (objects_moved) {
-      uint8_t *so = st + up256(s->cam_bytes);
       fill_object_block(s, so);
-      const uint32_t NO = s->hd.n_objects, n_loop = s->has_b ? NO - 1u : NO;
-      const rt_sphere *loop = (const rt_sphere *)(blk + (s->has_b ? s->o_objs_b : s->o_objs));
+      rt_light_list all = {};
+      all.n = NL;
+      for (uint32_t k = 0; k < NL; k++) { all.k[k] = k; memcpy(all.xyz[k], s->lights[k], 24u); }
       e = (hipError_t)rt_launch_objects_copy(blk, so, s->obj_host_bytes, s->side);
-      if (e == hipSuccess && s->has_sg)
-        e = (hipError_t)rt_launch_sgrid_build(loop, n_loop, s->hd.n_lights, (const double *)((const uint8_t *)s->d_blob + s->hd.lights_offset), (uint64_t *)(blk + s->o_sg), s->side);
+      if (e == hipSuccess && s->has_sg) e = (hipError_t)rt_launch_sgrid_build(loop, n_loop, NL, &all, (uint64_t *)(blk + s->o_sg), s->side);
       if (e == hipSuccess && s->has_bt) e = (hipError_t)rt_launch_bounce_build(loop, NO, n_loop, s->d_cones, (uint64_t *)(blk + s->o_bt), s->side);
+      memcpy(s->slot_lights[b], s->lights, sizeof s->lights);
     } else {
       e = hipMemcpyAsync(blk, s->d_obj_buf[b ^ 1u], s->obj_bytes, hipMemcpyDeviceToDevice, s->side);
+      memcpy(s->slot_lights[b], s->slot_lights[b ^ 1u], sizeof s->lights);
     }
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "object block: %s", hipGetErrorString(e));
     s->slot_version[b] = s->obj_version;
+  }
+  rt_light_list moved = {};
+  for (uint32_t k = 0; k < NL; k++)
+    if (memcmp(s->slot_lights[b][k], s->lights[k], 24u) != 0) { moved.k[moved.n] = k; memcpy(moved.xyz[moved.n], s->lights[k], 24u); moved.n++; }
+  if (moved.n) {
+    double *headers = (double *)so;
+    if (s->has_sg) {
+      const rt_sphere *hloop = s->has_b ? s->host_objects_b.data() : (const rt_sphere *)(s->host_blob.data() + s->hd.objects_offset);
+      for (uint32_t j = 0; j < moved.n; j++) shadow_grid_frame(hloop, n_loop, moved.xyz[j], headers + 16u * j);
+    }
+    hipError_t e = (hipError_t)rt_launch_light_anchor((const rt_sphere *)(blk + s->o_objs), s->has_b ? (const rt_sphere *)(blk + s->o_objs_b) : nullptr, s->has_b ? 2u : 1u, NO, NL, &moved,
+                                                      (rt_geom *)(blk + s->o_geom), s->has_sg ? (double *)(blk + s->o_sg) : nullptr, headers, s->side);
+    if (e == hipSuccess && s->has_sg) e = (hipError_t)rt_launch_sgrid_build(loop, n_loop, NL, &moved, (uint64_t *)(blk + s->o_sg), s->side);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "object block, lights: %s", hipGetErrorString(e));
+    memcpy(s->slot_lights[b], s->lights, sizeof s->lights);
   }
   // the tables the previous generation's frames used are rebuilt now, on the side stream, beside those frames' launches: the next
   // render of such a frame finds its table (up to four; others are built by the launch that needs them, on its stream).  Many-sphere
@@ -540,6 +563,45 @@ extern "C" int rt_scene_set_objects(rt_scene_dev *s, uint32_t first, uint32_t co
   object_decisions(s);
   camera_decisions(s);
   return next_generation(s, old_gen, true);
+}
+
+// The lights of a resident scene move (the reference's lights are a literal array inside intersectWorld, main.js:283, that a page
+// edits in place).  What depends on them - the host copy every launch record takes, the light-anchored records and the shadow grids
+// of the object block, the launch tables' shadow masks, the "light on a surface" decision - follows through the generation pipeline
+// (next_generation): a move of its own kind, cheaper than an object move - no bounce table, no staged object block.
+extern "C" int rt_scene_set_lights(rt_scene_dev *s, uint32_t first, uint32_t count, const double *xyz, void *hip_stream) {
+  if (!s) return fail(RT_ERR_INVALID, "rt_scene_set_lights: NULL scene");
+  (void)hip_stream;                                  // (as rt_scene_set_camera: the builds run on the scene's side stream)
+  const uint32_t NL = s->hd.n_lights;
+  if (first > NL || count > NL - first) return fail(RT_ERR_INVALID, "rt_scene_set_lights: lights [%u, %u + %u) outside [0, %u)", first, first, count, NL);
+  if (count && !xyz) return fail(RT_ERR_INVALID, "rt_scene_set_lights: NULL positions");
+  int rc = ensure_device(s->device);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(s->launch_mu);
+  double next[RT_MAX_LIGHTS][3];
+  memcpy(next, s->lights, sizeof next);
+  if (count) memcpy(next[first], xyz, (size_t)count * 24u);
+  if (memcmp(next, s->lights, sizeof next) == 0) return RT_OK;
+  if (enclosing_sphere(&s->hd, s->host_objects.data(), next) != s->enclosing)
+    return fail(RT_ERR_UNSUPPORTED, "rt_scene_set_lights: the move changes the sphere that encloses everything (the scene's tables are laid out around it): upload the scene again");
+  if ((rc = ensure_side(s))) return rc;
+  const uint64_t old_gen = s->cam_gen;
+  memcpy(s->lights, next, sizeof next);
+  memcpy(s->host_blob.data() + s->hd.lights_offset, next, (size_t)NL * 24u);
+  object_decisions(s);
+  camera_decisions(s);
+  return next_generation(s, old_gen, false);
+}
+
+// The shared light intensity (main.js:284) is host state like the stars seed: the launch record carries it (rt_launch.hip), and
+// neither a table, nor a host decision, nor a mark count depends on it (a sample is marked by its sampler coordinate and the product
+// of the albedos above it, rt_kernel.hip: RT_XY_INDEX).  Frames already enqueued keep theirs.
+extern "C" int rt_scene_set_light_intensity(rt_scene_dev *s, double light_intensity) {
+  if (!s) return fail(RT_ERR_INVALID, "rt_scene_set_light_intensity: NULL scene");
+  std::lock_guard<std::mutex> lk(s->launch_mu);
+  s->hd.light_intensity = light_intensity;
+  memcpy(s->host_blob.data() + offsetof(rt_scene_header, light_intensity), &light_intensity, sizeof light_intensity);
+  return RT_OK;
 }
 
 // The stars seed (include/rt_hip.h: RT_SAMPLER_STARS) is host state: render_batch_impl copies it into each launch record, so frames

@@ -12,6 +12,7 @@ js/scene.js; blob layout = include/rt_hip.h (rt_scene_header + tables).
 import base64
 import ctypes as C
 import json
+import numbers
 import os
 import struct
 
@@ -109,6 +110,22 @@ def sphere_records(objects):
     return b"".join(_sphere_record(ob) for ob in objects)
 
 
+def light_positions(lights):
+    """A list of 3-vectors -> its numbers in order (3 floats per light), as flatten_scene packs a scene's lights: what
+    rt_scene_set_lights / Renderer.set_lights take.  ValueError for anything else."""
+    if isinstance(lights, (str, bytes, bytearray)) or not hasattr(lights, "__len__") or not hasattr(lights, "__getitem__"):
+        raise ValueError("lights must be a list of 3-vectors")
+    flat = []
+    for l in lights:
+        if isinstance(l, (str, bytes, bytearray)) or not hasattr(l, "__len__") or len(l) != 3:
+            raise ValueError("a light is a 3-vector [x, y, z]")
+        for c in l:
+            if isinstance(c, bool) or not isinstance(c, numbers.Real):
+                raise ValueError("a light's coordinates are numbers")
+            flat.append(float(c))
+    return flat
+
+
 def flatten_scene(scene):
     """scene dict -> pointer-free blob (bytes), byte-identical to js/flatten.js flattenScene."""
     validate_scene(scene)
@@ -191,6 +208,8 @@ ABI = {
     "rt_scene_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "rt_scene_set_stars_seed": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rt_scene_set_objects": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_scene_set_lights": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_void_p]),
+    "rt_scene_set_light_intensity": (C.c_int, [C.c_void_p, C.c_double]),
     "rt_render_tiles_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtTiles), C.c_void_p, C.c_void_p,
                                          C.c_uint32, C.POINTER(RtStats)]),
     "rt_render_batch_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtTiles), C.c_uint32, C.c_void_p, C.c_uint64,
@@ -298,6 +317,23 @@ class Renderer:
         buf = C.create_string_buffer(recs, max(len(recs), 1))
         _check(self.lib, self.lib.rt_scene_set_objects(self.handle, first, len(recs) // SPHERE_BYTES, buf, C.c_void_p(stream or 0)),
                "rt_scene_set_objects")
+
+    def set_lights(self, lights, first=0, stream=None):
+        """Move lights [first, first + len(lights)) of the resident scene (a list of 3-vectors; the reference's literal array,
+        main.js:283): asynchronous, like an object move and cheaper; the next render sees them.  RtError (RT_ERR_UNSUPPORTED) when the
+        move changes the sphere that encloses everything (a light outside the skybox): upload the scene again."""
+        flat = light_positions(lights)
+        if isinstance(first, bool) or not isinstance(first, int) or first < 0:
+            raise ValueError("first must be a light index")
+        xyz = (C.c_double * max(len(flat), 1))(*flat)
+        _check(self.lib, self.lib.rt_scene_set_lights(self.handle, first, len(flat) // 3, xyz, C.c_void_p(stream or 0)), "rt_scene_set_lights")
+
+    def set_light_intensity(self, value):
+        """The intensity all lights share (main.js:284) for the scene's later renders.  Host state only, like the stars seed: renders
+        already enqueued keep theirs."""
+        if isinstance(value, bool) or not isinstance(value, numbers.Real):
+            raise ValueError("light intensity must be a number")
+        _check(self.lib, self.lib.rt_scene_set_light_intensity(self.handle, float(value)), "rt_scene_set_light_intensity")
 
     def render_tiles(self, w, h, d_out, tiles=None, stream=None, flags=0, want_stats=False):
         t = tiles if isinstance(tiles, RtTiles) else RtTiles(*(tiles or (h, 0, 1, 1)))

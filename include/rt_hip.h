@@ -249,6 +249,26 @@ int rt_scene_set_stars_seed(rt_scene_dev *scene, uint32_t seed);
  * skybox) is RT_ERR_UNSUPPORTED: upload the scene again.  `hip_stream` and thread rules as for rt_scene_set_camera. */
 int rt_scene_set_objects(rt_scene_dev *scene, uint32_t first, uint32_t count, const rt_sphere *records, void *hip_stream);
 
+/* Replace the positions of lights [first, first + count) of a resident scene, three doubles per light, in the blob's light order (the
+ * reference's lights are a literal array inside intersectWorld, main.js:283, with two more entries commented out: what a page author
+ * changes first); n_lights, spheres, textures, camera and seed stay.  Positions are accepted by rt_scene_validate's rules for a
+ * blob's light table (any value); a range outside [0, n_lights), or NULL `xyz` with a count, is RT_ERR_INVALID and leaves the scene
+ * as it was.  Positions equal to the current ones change nothing.  Asynchronous, like an object move and cheaper: of the object
+ * block only the records anchored at the moved lights and those lights' shadow grids depend on them, and the library rewrites just
+ * these ON THE GPU on its own stream (the bounce table, the sphere records and the LDS images stay), beside frames still rendering
+ * with the old lights - which keep them: lights travel in each launch's parameters - and rebuilds the launch tables in use (their
+ * shadow masks); the next render of the scene on any stream (colour, strict, batch, scatter, hits, pick, ray list) waits for it by
+ * event.  A light moved exactly onto a sphere's surface makes the scene a strict-kernel scene, as at upload.  A move that changes
+ * the sphere that encloses everything (a light carried outside the skybox) is RT_ERR_UNSUPPORTED and leaves the scene as it was:
+ * upload the scene again.  `hip_stream` and thread rules as for rt_scene_set_camera. */
+int rt_scene_set_lights(rt_scene_dev *scene, uint32_t first, uint32_t count, const double *xyz, void *hip_stream);
+
+/* Set the light intensity of a resident scene (rt_scene_header.light_intensity; the reference's one intensity shared by all lights,
+ * "common (for now)", main.js:284).  Host state only, like the stars seed: it is copied into each later render's launch parameters -
+ * frames already enqueued keep theirs, nothing is uploaded, and no table, launch decision or mark count depends on it.  Thread
+ * rules as for rt_scene_set_camera.  Any value is valid, as in a blob. */
+int rt_scene_set_light_intensity(rt_scene_dev *scene, double light_intensity);
+
 /* Render tiles of the w x h frame into DEVICE memory `d_out_rgba` (at least
  * n_tiles*tile_rows*w*4 bytes) on `hip_stream` (a hipStream_t; NULL = the library's own
  * stream for that device).  Asynchronous unless `stats` is non-NULL (then it waits and
@@ -284,9 +304,10 @@ int rt_ipc_close(int device, void *d_ptr);
  * the next band's render; into smaller pinned frames the trace kernel stores directly, over PCIe.  Either way the call takes about
  * max(kernel, frame bytes / PCIe rate).  With more than one GPU in use the frame is sharded by interleaved row tiles and put
  * together on GPU 0 (peer stores, or one RCCL gather) before the copy-out.  The scene stays resident between calls: a blob that
- * differs from the previous call's only in the camera, stars_seed and / or sphere records is not uploaded again (the resident scene
- * takes the spheres of the smallest range that covers the differences, rt_scene_set_objects, then moves its camera,
- * rt_scene_set_camera, and takes the seed, rt_scene_set_stars_seed; an edit either call refuses with RT_ERR_UNSUPPORTED is uploaded).  Replaces redraw()/spanish() + ImageData (main.js:83,180-201). */
+ * differs from the previous call's only in the camera, stars_seed, sphere records, light positions and / or light_intensity is not
+ * uploaded again (the resident scene takes the spheres of the smallest range that covers the differences, rt_scene_set_objects, then
+ * the lights of theirs, rt_scene_set_lights, then the intensity, rt_scene_set_light_intensity, then moves its camera,
+ * rt_scene_set_camera, and takes the seed, rt_scene_set_stars_seed; an edit any of these refuses with RT_ERR_UNSUPPORTED is uploaded).  Replaces redraw()/spanish() + ImageData (main.js:83,180-201). */
 int rt_render(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h,
               uint8_t *out_rgba, uint32_t flags, rt_stats *stats);
 
@@ -388,8 +409,8 @@ int rt_render_hits_device(rt_scene_dev *scene, uint32_t w, uint32_t h, const rt_
  * the HOST array out[n], with the scene's current camera.  Synchronous. */
 int rt_scene_pick(rt_scene_dev *scene, uint32_t w, uint32_t h, uint32_t n, const uint32_t *sample_xy, rt_hit *out);
 
-/* The host forms: rt_render's resident scene (a blob that differs from the resident one only in the camera and / or stars_seed is
- * not uploaded again: the resident scene moves its camera), outputs in HOST memory.  rt_render_hits fills the whole frame's
+/* The host forms: rt_render's resident scene (a blob that differs from the resident one only in the camera, stars_seed, sphere
+ * records, light positions and / or light_intensity is not uploaded again: the resident scene takes the edits), outputs in HOST memory.  rt_render_hits fills the whole frame's
  * (k*w x k*h samples) non-NULL buffers of host_bufs; rt_pick is rt_scene_pick on that scene.  Both synchronous, on GPU 0. */
 int rt_render_hits(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h, const rt_hit_buffers *host_bufs, rt_stats *stats);
 int rt_pick(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h, uint32_t n, const uint32_t *sample_xy, rt_hit *out);
@@ -410,7 +431,8 @@ int rt_pick(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h, u
  *           u, v; a miss: object -1, inside 0, t +Infinity, everything else 0.
  * The arithmetic is the strict one everywhere (no FMA contraction, correctly rounded sqrt and division, fdlibm atan2 / asin), for any
  * origin: the scene's camera, its launch tables, RT_FLAG_* and `supersample` play no part.  The resident scene's CURRENT spheres do
- * (rt_scene_set_objects), and so does its stars seed (rt_scene_set_stars_seed).
+ * (rt_scene_set_objects), and so do its lights (rt_scene_set_lights, rt_scene_set_light_intensity) and its stars seed
+ * (rt_scene_set_stars_seed).
  * Stars sampler: pix = i (the ray's index in the list, 64 bits), path from the root 1, seed as for a frame.  So the list of a w x h
  * frame's primary rays in row order draws that frame's sky - and, every other sampler being a function of the ray alone, that list
  * gives the RT_FLAG_STRICT_FP frame byte for byte.
@@ -429,13 +451,13 @@ typedef struct rt_ray_outputs {
 
 /* Device form: `d_rays` and the buffers `d_out` names are DEVICE memory (d_out itself is a host struct).  Asynchronous on `hip_stream`
  * (NULL = the library's stream for the scene's device) unless `stats` is non-NULL (then it waits and fills kernel_ms, total_ms and
- * pixels = n).  Waits by event for a pending rt_scene_set_objects like every other render.  The refracting scenes' kernel keeps its
+ * pixels = n).  Waits by event for a pending rt_scene_set_objects or rt_scene_set_lights like every other render.  The refracting scenes' kernel keeps its
  * frame stack in scratch memory: a reservation the device cannot meet is RT_ERR_NOMEM.  Thread rules as rt_render_tiles_device. */
 int rt_scene_trace_rays_device(rt_scene_dev *scene, uint64_t n, const double *d_rays, uint32_t segs,
                                const rt_ray_outputs *d_out, void *hip_stream, rt_stats *stats);
 
-/* Host form: rt_render's resident scene (a blob that differs from the resident one only in the camera, stars_seed and / or sphere
- * records is not uploaded again), rays and outputs in HOST memory, synchronous, on GPU 0.  The list is processed in chunks of 2^18
+/* Host form: rt_render's resident scene (a blob that differs from the resident one only in the camera, stars_seed, sphere records,
+ * light positions and / or light_intensity is not uploaded again), rays and outputs in HOST memory, synchronous, on GPU 0.  The list is processed in chunks of 2^18
  * rays (ray i keeps pix = i), so the device memory the call allocates does not grow with n. */
 int rt_trace_rays(const void *scene_blob, size_t blob_bytes, uint64_t n, const double *rays, uint32_t segs,
                   const rt_ray_outputs *host_out, rt_stats *stats);

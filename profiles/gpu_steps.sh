@@ -30,6 +30,9 @@ step_rays_tests() {         # the ray-list tests (tests/test_gpu_rays.py), with 
 step_rays_timing() {        # [PARENT_LIB=<librt_hip.so of the parent commit>]: ray lists beside the strict frame (profiles/rays_timing.py)
   timeout -k 10 400 python profiles/rays_timing.py 200 ${O}_rays_timing.json ${PARENT_LIB:-} > ${O}_rays_timing.log 2>&1; rc=$?; tail -70 ${O}_rays_timing.log | cut -c1-200; return $rc
 }
+step_lights_loop() {        # [PARENT_LIB=<librt_hip.so of the parent commit, profiles/ab_build.sh parent "" product>]: set_lights beside an upload per frame and set_objects
+  timeout -k 10 ${LOOP_LIMIT:-900} python profiles/moving_lights_loop.py ${O}_moving_lights_loop.json ${PARENT_LIB:-build/ab/librt_hip_parent.so} > ${O}_moving_lights_loop.log 2>&1; rc=$?; tail -4 ${O}_moving_lights_loop.log | cut -c1-300; return $rc
+}
 step_panorama() {           # the equirectangular panorama of tools/panorama.py (the PNG stays in the output directory)
   timeout -k 10 120 python tools/panorama.py default14_stars 1024 512 ${O}_panorama_default14_stars.png 0 1.5 4 > ${O}_panorama.log 2>&1; rc=$?; tail -2 ${O}_panorama.log; return $rc
 }
