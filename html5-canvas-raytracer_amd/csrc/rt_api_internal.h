@@ -2,7 +2,7 @@
 // scene (rt_scene_dev) and the few functions that cross units.  Not part of the ABI.
 //   rt_api.hip     lifetime, errors, device state, the scratch guard, the host-logic probes, memory helpers, IPC
 //   rt_scene.hip   upload and moves of a resident scene (the generation pipeline), its launch decisions and launch tables
-//   rt_launch.hip  the launches: colour (product / strict / retrace), supersampling, compact bands, primary hits and picking
+//   rt_launch.hip  the launches: colour (product / strict / retrace), supersampling, compact bands, primary hits and picking, ray lists
 //   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H
@@ -27,6 +27,7 @@
 #include "rt_tables_gpu.h"
 #include "rt_hits.h"
 #include "rt_objects_gpu.h"
+#include "rt_rays_order.h"
 
 extern "C" int rt_launch_trace_fast(const rt_launch *, int, int, int, unsigned, hipStream_t);
 extern "C" int rt_launch_trace_strict(const rt_launch *, int, int, int, unsigned, hipStream_t);
@@ -34,7 +35,7 @@ extern "C" int rt_launch_retrace(const rt_launch *, int, int, unsigned, hipStrea
 extern "C" int rt_scratch_trace_fast(int, int, int, int, int, size_t *);
 extern "C" int rt_scratch_trace_strict(int, int, int, int, int, size_t *);
 extern "C" int rt_scratch_retrace(int, int, size_t *);
-extern "C" int rt_launch_trace_rays(const rt_launch *, int, unsigned, hipStream_t);
+extern "C" int rt_launch_trace_rays(const rt_launch *, const uint32_t *, int, unsigned, hipStream_t);
 extern "C" int rt_scratch_trace_rays(int, size_t *);
 
 using namespace rt_tables;   // the host-built tables (pure host logic, rt_tables.cpp)
@@ -279,10 +280,13 @@ int dispatch_order(rt_scene_dev *s, const frame_kind &kind, const table_choice &
 // rt_launch.hip: argument checks of the hit entry points
 int hits_frame_check(uint32_t w, uint32_t h, uint32_t k, const char *what);
 int pick_points_check(uint32_t w, uint32_t h, uint32_t k, uint32_t n, const uint32_t *xy, const void *out, const char *what);
-// ... and of the ray entry points; the launch of rays [base, base + n) of a caller's list (device pointers to THOSE rays and their outputs)
+// ... and of the ray entry points; the launch of rays [base, base + n) of a caller's list (device pointers to THOSE rays and their outputs),
+// in the list's order (d_order NULL) or in the order of n entries; the ordering of n rays (rt_rays_order.hip) with its argument check
 int rays_check(uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *out, const char *what);
-int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *d_rays, uint32_t segs, const rt_ray_outputs &out, hipStream_t stream,
-                      rt_stats *stats);
+int rays_order_check(uint64_t n, const double *rays, const uint32_t *order, const void *work, size_t work_bytes, const char *what);
+int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *d_rays, const uint32_t *d_order, uint32_t segs, const rt_ray_outputs &out,
+                      hipStream_t stream, rt_stats *stats);
+int order_rays_launch(uint32_t n, const double *d_rays, uint32_t *d_order, void *d_work, hipStream_t stream);
 
 // rt_frame.hip: RCCL's communicators are destroyed (rt_shutdown)
 void release_rccl();

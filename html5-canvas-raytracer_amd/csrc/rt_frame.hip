@@ -1,4 +1,4 @@
-// rt_frame.hip — rt_render(width, height, scene) and its kin (rt_render_progressive, rt_render_hits, rt_pick, rt_trace_rays): the resident scene
+// rt_frame.hip — rt_render(width, height, scene) and its kin (rt_render_progressive, rt_render_hits, rt_pick, rt_trace_rays, rt_trace_rays_binned): the resident scene
 // per device (scene_for), the one-GPU plans (banded copy-out, stores straight into a pinned frame) and the single-process multi-GPU
 // frame (interleaved row tiles stored straight into GPU 0's frame over xGMI; fallback: RGB24 bands + one RCCL gather + de-interleave).
 
@@ -267,12 +267,16 @@ extern "C" int rt_pick(const void *blob, size_t bytes, uint32_t w, uint32_t h, u
 
 // intersectWorld for a list of rays in host memory, with rt_render's resident scene: chunks of RT_RAY_CHUNK rays go through one set of
 // device buffers (ray i of the list keeps pix = i: the chunk's base travels in the launch record), so the device memory of a call does
-// not grow with n.  Synchronous; kernel_ms is the sum over the chunks.
+// not grow with n.  Synchronous; kernel_ms is the sum over the chunks.  `binned` (rt_trace_rays_binned): every chunk is ordered on the
+// GPU (rt_rays_order.hip) and traced in that order; the order buffer and the workspace are the call's, like its other device memory,
+// and kernel_ms includes the orderings.
 #define RT_RAY_CHUNK (1u << 18)
-extern "C" int rt_trace_rays(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *ho, rt_stats *stats) {
+namespace {
+int trace_rays_to_host(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *ho, rt_stats *stats,
+                       bool binned, const char *what) {
   int rc = rt_scene_validate(blob, bytes);
   if (rc) return rc;
-  if ((rc = rays_check(n, rays, segs, ho, "rt_trace_rays"))) return rc;
+  if ((rc = rays_check(n, rays, segs, ho, what))) return rc;
   if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
   std::lock_guard<std::mutex> lk(G.mu);
   const auto t_begin = std::chrono::steady_clock::now();
@@ -281,17 +285,35 @@ extern "C" int rt_trace_rays(const void *blob, size_t bytes, uint64_t n, const d
   if ((rc = ensure_device(0))) return rc;
   device_state &D = G.dev[0];
   const size_t chunk = n < RT_RAY_CHUNK ? (size_t)n : RT_RAY_CHUNK;
-  struct device_bufs { void *p[4] = {nullptr, nullptr, nullptr, nullptr}; ~device_bufs() { for (void *q : p) if (q) (void)hipFree(q); } } mem;
+  struct device_bufs { void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; ~device_bufs() { for (void *q : p) if (q) (void)hipFree(q); } } mem;
   const size_t each[4] = {6u * sizeof(double), 3u * sizeof(double), 4u, sizeof(rt_hit)};
   uint8_t *const host[4] = {(uint8_t *)rays, (uint8_t *)ho->rgb, ho->rgba, (uint8_t *)ho->hits};
   for (int i = 0; i < 4; i++) if (host[i]) HIP_TRY(hipMalloc(&mem.p[i], chunk * each[i]));
+  if (binned) {                                          // the chunk's order and the ordering's workspace
+    HIP_TRY(hipMalloc(&mem.p[4], chunk * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&mem.p[5], rt_rays_order_work_bytes(chunk)));
+  }
   const rt_ray_outputs dout = {(double *)mem.p[1], (uint8_t *)mem.p[2], (rt_hit *)mem.p[3]};
   double kernel_ms = 0.0;
   for (uint64_t base = 0; base < n; base += chunk) {
     const size_t m = n - base < chunk ? (size_t)(n - base) : chunk;
     HIP_TRY(hipMemcpyAsync(mem.p[0], host[0] + base * each[0], m * each[0], hipMemcpyHostToDevice, D.stream));
+    if (binned) {
+      event_timer timer;                                 // (a stats call)
+      if (stats) HIP_TRY(timer.start(D.stream));
+      if ((rc = order_rays_launch((uint32_t)m, (const double *)mem.p[0], (uint32_t *)mem.p[4], mem.p[5], D.stream))) return rc;
+      if (stats) {
+        HIP_TRY(timer.stop(D.stream));
+        HIP_TRY(hipEventSynchronize(timer.b));
+        float ms = 0.f;
+        HIP_TRY(timer.elapsed(&ms));
+        kernel_ms += ms;
+      }
+    }
     rt_stats st;
-    if ((rc = trace_rays_launch(s, (uint32_t)m, (uint32_t)base, (const double *)mem.p[0], segs, dout, D.stream, stats ? &st : nullptr))) return rc;
+    if ((rc = trace_rays_launch(s, (uint32_t)m, (uint32_t)base, (const double *)mem.p[0], (const uint32_t *)mem.p[4], segs, dout, D.stream,
+                                stats ? &st : nullptr)))
+      return rc;
     if (stats) kernel_ms += st.kernel_ms;
     for (int i = 1; i < 4; i++) if (host[i]) HIP_TRY(hipMemcpyAsync(host[i] + base * each[i], mem.p[i], m * each[i], hipMemcpyDeviceToHost, D.stream));
     HIP_TRY(hipStreamSynchronize(D.stream));
@@ -303,6 +325,16 @@ extern "C" int rt_trace_rays(const void *blob, size_t bytes, uint64_t n, const d
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
   return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_trace_rays(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *ho, rt_stats *stats) {
+  return trace_rays_to_host(blob, bytes, n, rays, segs, ho, stats, false, "rt_trace_rays");
+}
+
+extern "C" int rt_trace_rays_binned(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *ho,
+                                    rt_stats *stats) {
+  return trace_rays_to_host(blob, bytes, n, rays, segs, ho, stats, true, "rt_trace_rays_binned");
 }
 
 namespace {

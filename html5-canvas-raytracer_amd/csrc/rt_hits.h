@@ -26,6 +26,7 @@ struct rt_hits_launch {
   // rt_scene_trace_rays_device: n_rays records {org[3], dir[3]} (16-byte aligned) ... and their records in `hits`
   const double *rays;
   uint32_t n_rays;
+  const uint32_t *ray_order;       // rt_scene_trace_rays_ordered_device: n_rays entries, work-item j takes ray ray_order[j]; or NULL
 };
 
 extern "C" int rt_launch_hits(const rt_hits_launch *L, hipStream_t stream);

@@ -133,10 +133,14 @@ __global__ void __launch_bounds__(RT_HITS_WG) rt_pick_kernel(const rt_hits_launc
 }
 
 // rt_scene_trace_rays_device, `hits`: one work-item per caller-supplied ray {org[3], dir[3]} (three 16-byte loads from the 16-byte
-// aligned list), the direction as given.  A ray with a non-finite component is not traced: the miss record.
+// aligned list), the direction as given.  A ray with a non-finite component is not traced: the miss record.  With L.ray_order
+// (rt_scene_trace_rays_ordered_device) work-item `item` takes ray j = ray_order[item] - record j in, record j out - and skips an entry
+// that names no ray.
 __global__ void __launch_bounds__(RT_HITS_WG) rt_ray_hit_kernel(const rt_hits_launch L) {
   typedef double __attribute__((ext_vector_type(2))) d2;
-  const uint32_t j = blockIdx.x * RT_HITS_WG + threadIdx.x;
+  const uint32_t item = blockIdx.x * RT_HITS_WG + threadIdx.x;
+  if (item >= L.n_rays) return;
+  const uint32_t j = L.ray_order ? L.ray_order[item] : item;
   if (j >= L.n_rays) return;
   const d2 *q = (const d2 *)(L.rays + 6u * (size_t)j);
   const d2 a = q[0], b = q[1], c = q[2];

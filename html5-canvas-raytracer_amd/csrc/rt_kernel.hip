@@ -1861,17 +1861,24 @@ __global__ void __launch_bounds__(RT_WG_THREADS) rt_retrace(const rt_launch L) {
 // discriminant, materials read from HBM, no launch table, no cull, nothing anchored at a camera, and no wave-wide step (a wave's
 // lanes hold unrelated rays).  The stars sampler's pix is the ray's index in the caller's list, ray_base + j (below 2^31: it is handed
 // over as sample x of row 0).
+// `order` (rt_scene_trace_rays_ordered_device; NULL: the list's own order): work-item j takes ray i = order[j] instead of ray j - it
+// reads record i, hands over pix = ray_base + i and stores at i, so every output is what the plain launch puts there, and only which
+// rays share a wave changes.  An entry >= n_rays is skipped.  The pointer is a kernel argument of its own, not a field of rt_launch:
+// the frame kernels' argument segment stays as it is.  With an order the loads and stores below are gathers and scatters of whole
+// records.
 // Memory: a record is 48 bytes and the list 16-byte aligned - three 16-byte loads per lane; rgba is one dword per lane (a wave stores
 // 256 contiguous bytes), rgb three 8-byte stores.  A ray with a non-finite component is not traced (NaN x 3; the store rule makes
 // 0, 0, 0, 255 of it): what the caller supplies decides no address here - sphere, texel and checker indices come out of comparisons
 // that NaN fails (no hit), a truncation that is clamped (texel) and to_int32_bit0 (0 or 1) for every finite ray, whatever overflows
 // on the way down the tree - and the guard keeps that argument to finite inputs.
 template <bool REFRACT>
-__global__ void __launch_bounds__(RT_WG_THREADS) rt_trace_rays(const rt_launch L) {
+__global__ void __launch_bounds__(RT_WG_THREADS) rt_trace_rays(const rt_launch L, const uint32_t *order) {
   typedef double __attribute__((ext_vector_type(2))) d2;
   const rt_mtl *mtl = (const rt_mtl *)L.lds_image;                         // (HBM: nothing is staged here)
   const rt_texture_desc *tex = (const rt_texture_desc *)((const char *)L.lds_image + (size_t)L.n_objects * sizeof(rt_mtl));
-  for (uint32_t j = blockIdx.x * RT_WG_THREADS + threadIdx.x; j < L.n_rays; j += gridDim.x * RT_WG_THREADS) {
+  for (uint32_t item = blockIdx.x * RT_WG_THREADS + threadIdx.x; item < L.n_rays; item += gridDim.x * RT_WG_THREADS) {
+    const uint32_t j = order ? order[item] : item;
+    if (j >= L.n_rays) continue;                                           // (an order's entry that names no ray)
     const d2 *q = (const d2 *)(L.rays + 6u * (size_t)j);
     const d2 a = q[0], b = q[1], c = q[2];
     double rgb[3] = {__builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
@@ -1898,11 +1905,11 @@ extern "C" int rt_launch_retrace(const rt_launch *L, int refract, int ss2, unsig
   return (int)hipGetLastError();
 }
 
-// Host-side launcher of rt_trace_rays (n_wg workgroups of RT_WG_THREADS) and its per-lane scratch.  Return a hipError_t as int.
-extern "C" int rt_launch_trace_rays(const rt_launch *L, int refract, unsigned n_wg, hipStream_t stream) {
+// Host-side launcher of rt_trace_rays (n_wg workgroups of RT_WG_THREADS; `order` NULL or n_rays entries) and its per-lane scratch.  Return a hipError_t as int.
+extern "C" int rt_launch_trace_rays(const rt_launch *L, const uint32_t *order, int refract, unsigned n_wg, hipStream_t stream) {
   const dim3 grid(n_wg ? n_wg : 1u), block(RT_WG_THREADS);
-  if (!refract) hipLaunchKernelGGL((rt_trace_rays<false>), grid, block, 0, stream, *L);
-  else hipLaunchKernelGGL((rt_trace_rays<true>), grid, block, 0, stream, *L);
+  if (!refract) hipLaunchKernelGGL((rt_trace_rays<false>), grid, block, 0, stream, *L, order);
+  else hipLaunchKernelGGL((rt_trace_rays<true>), grid, block, 0, stream, *L, order);
   return (int)hipGetLastError();
 }
 extern "C" int rt_scratch_trace_rays(int refract, size_t *bytes_per_lane) {

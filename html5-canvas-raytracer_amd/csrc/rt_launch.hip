@@ -1,6 +1,7 @@
 // rt_launch.hip — the launches of a resident scene (include/rt_hip.h: rt_render_*_device): the product launch with its launch table
 // and the list-driven strict launch behind it (rt_retrace), the strict kernel, 3x3 / 4x4 supersampling with a box filter, compact
-// bands, primary hits and picking, caller-supplied rays (rt_trace_rays), and the test build's per-sample probe.
+// bands, primary hits and picking, caller-supplied rays (rt_trace_rays) in the list's or a given order and their ordering, and the test
+// build's per-sample probe.
 
 #include "rt_api_internal.h"
 
@@ -672,6 +673,8 @@ extern "C" int rt_scene_pick(rt_scene_dev *s, uint32_t w, uint32_t h, uint32_t n
 // rt_trace_rays<refract> for the colours - the scene in its own order, every sphere in the loops, the reference's own miss colour, as
 // rt_retrace is bound; camera, launch tables and flags play no part - and rt_hits.hip's rt_ray_hit_kernel for the hit records.  Both
 // read the scene's current generation, so they come behind its preparation like every other launch of the scene.
+// With an order (rt_scene_trace_rays_ordered_device) the same two kernels take their rays through it: the same launch, one more pointer.
+// The ordering itself (rt_scene_order_rays_device -> rt_rays_order.hip) reads the rays and nothing of the scene: it waits for no edit.
 namespace rt_api {
 int rays_check(uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *out, const char *what) {
   if (!rays || !out) return fail(RT_ERR_INVALID, "%s: NULL rays or outputs", what);
@@ -684,8 +687,25 @@ int rays_check(uint64_t n, const double *rays, uint32_t segs, const rt_ray_outpu
   return RT_OK;
 }
 
-int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *d_rays, uint32_t segs, const rt_ray_outputs &out, hipStream_t stream,
-                      rt_stats *stats) {
+int rays_order_check(uint64_t n, const double *rays, const uint32_t *order, const void *work, size_t work_bytes, const char *what) {
+  if (!rays || !order || !work) return fail(RT_ERR_INVALID, "%s: NULL rays, order or workspace", what);
+  if (n == 0 || n >= (1ull << 31)) return fail(RT_ERR_INVALID, "%s: n %llu not in 1..2^31 - 1", what, (unsigned long long)n);
+  if ((uintptr_t)rays & 15u) return fail(RT_ERR_INVALID, "%s: the ray list must be 16-byte aligned", what);
+  if (((uintptr_t)order & 3u) || ((uintptr_t)work & 3u)) return fail(RT_ERR_INVALID, "%s: misaligned order or workspace (4 bytes)", what);
+  if (work_bytes < rt_rays_order_work_bytes(n))
+    return fail(RT_ERR_INVALID, "%s: work_bytes %llu below rt_rays_order_work_bytes(%llu) = %llu", what, (unsigned long long)work_bytes,
+                (unsigned long long)n, (unsigned long long)rt_rays_order_work_bytes(n));
+  return RT_OK;
+}
+
+int order_rays_launch(uint32_t n, const double *d_rays, uint32_t *d_order, void *d_work, hipStream_t stream) {
+  const int err = rt_launch_order_rays(n, d_rays, d_order, d_work, stream);
+  if (err != 0) return fail(RT_ERR_DEVICE, "ray ordering launch: %s", hipGetErrorString((hipError_t)err));
+  return RT_OK;
+}
+
+int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *d_rays, const uint32_t *d_order, uint32_t segs, const rt_ray_outputs &out,
+                      hipStream_t stream, rt_stats *stats) {
   device_state &D = G.dev[s->device];
   const auto t_begin = std::chrono::steady_clock::now();
   const rt_scene_header &hd = s->hd;
@@ -726,7 +746,7 @@ int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *
       scratch_of[s->refract ? 1 : 0].store(per_lane = (long long)b);
     }
     if (int rc = scratch_guard(D, stream, (size_t)per_lane, (uint64_t)n_wg * (RT_WG_THREADS / 64u), "the ray-list kernel (rt_trace_rays)")) return rc;
-    const int err = rt_launch_trace_rays(&L, s->refract, n_wg, stream);
+    const int err = rt_launch_trace_rays(&L, d_order, s->refract, n_wg, stream);
     if (err != 0) return fail(RT_ERR_DEVICE, "ray kernel launch: %s", hipGetErrorString((hipError_t)err));
   }
   if (out.hits) {
@@ -735,7 +755,7 @@ int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *
     H.objects = L.objects;
     H.epsilon = hd.epsilon;
     H.n_objects = hd.n_objects;
-    H.rays = d_rays; H.n_rays = n; H.hits = out.hits;
+    H.rays = d_rays; H.n_rays = n; H.hits = out.hits; H.ray_order = d_order;
     const int err = rt_launch_ray_hits(&H, stream);
     if (err != 0) return fail(RT_ERR_DEVICE, "ray hit kernel launch: %s", hipGetErrorString((hipError_t)err));
   }
@@ -759,5 +779,27 @@ extern "C" int rt_scene_trace_rays_device(rt_scene_dev *s, uint64_t n, const dou
   int rc = rays_check(n, d_rays, segs, d_out, "rt_scene_trace_rays_device");
   if (rc) return rc;
   if ((rc = ensure_device(s->device))) return rc;
-  return trace_rays_launch(s, (uint32_t)n, 0u, d_rays, segs, *d_out, hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream, stats);
+  return trace_rays_launch(s, (uint32_t)n, 0u, d_rays, nullptr, segs, *d_out, hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream, stats);
+}
+
+extern "C" size_t rt_rays_order_work_bytes(uint64_t n) { return (n == 0 || n >= (1ull << 31)) ? 0 : rt_order_layout_of(n).bytes; }
+
+// (the arguments first: they are judged without a scene, and before a device is touched)
+extern "C" int rt_scene_order_rays_device(rt_scene_dev *s, uint64_t n, const double *d_rays, uint32_t *d_order, void *d_work, size_t work_bytes,
+                                          void *hip_stream) {
+  int rc = rays_order_check(n, d_rays, d_order, d_work, work_bytes, "rt_scene_order_rays_device");
+  if (rc) return rc;
+  if (!s) return fail(RT_ERR_STATE, "rt_scene_order_rays_device: NULL scene handle");
+  if ((rc = ensure_device(s->device))) return rc;
+  return order_rays_launch((uint32_t)n, d_rays, d_order, d_work, hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream);
+}
+
+extern "C" int rt_scene_trace_rays_ordered_device(rt_scene_dev *s, uint64_t n, const double *d_rays, const uint32_t *d_order, uint32_t segs,
+                                                  const rt_ray_outputs *d_out, void *hip_stream, rt_stats *stats) {
+  int rc = rays_check(n, d_rays, segs, d_out, "rt_scene_trace_rays_ordered_device");
+  if (rc) return rc;
+  if (!d_order || ((uintptr_t)d_order & 3u)) return fail(RT_ERR_INVALID, "rt_scene_trace_rays_ordered_device: NULL or misaligned order (4 bytes)");
+  if (!s) return fail(RT_ERR_STATE, "rt_scene_trace_rays_ordered_device: NULL scene handle");
+  if ((rc = ensure_device(s->device))) return rc;
+  return trace_rays_launch(s, (uint32_t)n, 0u, d_rays, d_order, segs, *d_out, hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream, stats);
 }

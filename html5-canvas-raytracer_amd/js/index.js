@@ -124,13 +124,15 @@ function tanHalf(projA) { return Math.tan(projA / 2); }
 // {org, dir}, directions used as given (normal3D above is the reference's).  opts: segs (0 / undefined = the scene's depth) and which
 // outputs to compute - rgb (default true) Float64Array 3 per ray, rgba Uint8ClampedArray 4 per ray, hits Array of pick's records
 // (null = a miss).  The scene's camera plays no part.  A ray with a non-finite component is not traced: NaN x 3 / 0, 0, 0, 255 / null.
+// opts.bin: the GPU puts each chunk of 2^18 rays into an order in which neighbours in a wave are neighbours in space before it traces
+// them (rt_trace_rays_binned) - the same results, sooner for a list that is not coherent (scattered probes, collected secondary rays).
 function traceRays(sceneObj, rays, opts) {
   if (!(rays instanceof Float64Array) || rays.length === 0 || rays.length % 6 !== 0) {
     throw new TypeError('traceRays: rays must be a non-empty Float64Array of 6 numbers per ray');
   }
   if (!inited) init(opts && opts.maxDevices);
   const o = opts || {};
-  const r = native().traceRays(new Uint8Array(flattenScene(sceneObj)), rays, o.segs || 0, o.rgb !== false, !!o.rgba, !!o.hits);
+  const r = native().traceRays(new Uint8Array(flattenScene(sceneObj)), rays, o.segs || 0, o.rgb !== false, !!o.rgba, !!o.hits, !!o.bin);
   if (r.hits) for (const h of r.hits) if (h) h.object = sceneObj.objects[h.index];
   return r;
 }

@@ -10,8 +10,9 @@
 //           being filled; onBand fires on the main thread as each row band lands in it; the promise resolves to the stats
 //           renderHits(blob, w, h, wantDepth, wantNormal) -> {id: Int32Array, depth: Float64Array | null, normal: Float32Array | null}
 //           pick(blob, w, h, sx, sy) -> {index, inside, t, point, normal, u, v} or null (a miss); sx, sy in sample-grid coordinates
-//           traceRays(blob, rays: Float64Array (6 per ray), segs, wantRgb, wantRgba, wantHits) -> {rgb: Float64Array | null,
-//           rgba: Uint8ClampedArray | null, hits: Array of pick's records (null = a miss) | null}: intersectWorld per ray (rt_trace_rays)
+//           traceRays(blob, rays: Float64Array (6 per ray), segs, wantRgb, wantRgba, wantHits, bin) -> {rgb: Float64Array | null,
+//           rgba: Uint8ClampedArray | null, hits: Array of pick's records (null = a miss) | null}: intersectWorld per ray (rt_trace_rays;
+//           bin: rt_trace_rays_binned, the list ordered on the GPU first - the same results)
 //           (these three are not enumerable: the enumerable surface is the frame API)
 // Every failure of the library becomes a thrown JS Error carrying rt_last_error().
 //
@@ -417,12 +418,12 @@ napi_value Pick(napi_env env, napi_callback_info info) {
 }
 
 napi_value TraceRays(napi_env env, napi_callback_info info) {
-  size_t argc = 6;
-  napi_value argv[6];
+  size_t argc = 7;
+  napi_value argv[7];
   bool is_ta = false, is_rays = false;
   if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
       napi_is_typedarray(env, argv[1], &is_rays) != napi_ok || !is_rays) {
-    napi_throw_type_error(env, nullptr, "traceRays(blob: Uint8Array, rays: Float64Array[, segs, wantRgb, wantRgba, wantHits])");
+    napi_throw_type_error(env, nullptr, "traceRays(blob: Uint8Array, rays: Float64Array[, segs, wantRgb, wantRgba, wantHits, bin])");
     return nullptr;
   }
   napi_typedarray_type bt, rt; napi_value ab; size_t off, blob_len = 0, ray_len = 0;
@@ -437,6 +438,8 @@ napi_value TraceRays(napi_env env, napi_callback_info info) {
   bool want[3] = {true, false, false};
   if (argc >= 3) napi_get_value_uint32(env, argv[2], &segs);
   for (size_t i = 0; i < 3 && 3 + i < argc; i++) napi_get_value_bool(env, argv[3 + i], &want[i]);
+  bool bin = false;                                     // rt_trace_rays_binned: the GPU orders each chunk before it traces it
+  if (argc >= 7) napi_get_value_bool(env, argv[6], &bin);
   const size_t n = ray_len / 6u;
   // the library wants the blob 8-byte and the rays 16-byte aligned: one aligned copy holds both
   const size_t blob_room = (blob_len + 15) & ~(size_t)15;
@@ -454,9 +457,9 @@ napi_value TraceRays(napi_env env, napi_callback_info info) {
   memcpy(mem + blob_room, ray_data, n * 48u);
   const rt_ray_outputs out = {(double *)p_rgb, (uint8_t *)p_rgba, hits};
   rt_stats st;
-  const int rc = rt_trace_rays(mem, blob_len, n, (const double *)(mem + blob_room), segs, &out, &st);
+  const int rc = (bin ? rt_trace_rays_binned : rt_trace_rays)(mem, blob_len, n, (const double *)(mem + blob_room), segs, &out, &st);
   free(mem);
-  if (rc != RT_OK) { free(hits); return throw_rt(env, "rt_trace_rays", rc); }
+  if (rc != RT_OK) { free(hits); return throw_rt(env, bin ? "rt_trace_rays_binned" : "rt_trace_rays", rc); }
   napi_create_object(env, &res);
   if (want[0]) napi_create_typedarray(env, napi_float64_array, 3 * n, ab_rgb, 0, &v); else napi_get_null(env, &v);
   napi_set_named_property(env, res, "rgb", v);

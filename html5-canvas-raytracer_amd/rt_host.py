@@ -242,6 +242,11 @@ ABI = {
     "rt_pick": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(RtHit)]),
     "rt_scene_trace_rays_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(RtRayOutputs), C.c_void_p, C.POINTER(RtStats)]),
     "rt_trace_rays": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(RtRayOutputs), C.POINTER(RtStats)]),
+    "rt_rays_order_work_bytes": (C.c_size_t, [C.c_uint64]),
+    "rt_scene_order_rays_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rt_scene_trace_rays_ordered_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtRayOutputs), C.c_void_p,
+                                                     C.POINTER(RtStats)]),
+    "rt_trace_rays_binned": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(RtRayOutputs), C.POINTER(RtStats)]),
 }
 
 
@@ -403,6 +408,25 @@ class Renderer:
         _check(self.lib, rc, "rt_scene_trace_rays_device")
         return st
 
+    def order_rays(self, n, rays_ptr, order_ptr, work_ptr, work_bytes, stream=None):
+        """Bin n rays in DEVICE memory: order_ptr (n uint32, DEVICE) receives a permutation of 0..n-1 in which 64 consecutive entries
+        are rays close in origin and direction (non-finite rays last); work_ptr is work_bytes >= rays_order_work_bytes(n) bytes of
+        device workspace.  Asynchronous; reads nothing of the scene."""
+        rc = self.lib.rt_scene_order_rays_device(self.handle, n, C.c_void_p(rays_ptr or 0), C.c_void_p(order_ptr or 0), C.c_void_p(work_ptr or 0),
+                                                 work_bytes, C.c_void_p(stream or 0))
+        _check(self.lib, rc, "rt_scene_order_rays_device")
+
+    def trace_rays_ordered(self, n, rays_ptr, order_ptr, rgb_ptr, rgba_ptr, hits_ptr, segs=0, stream=None, want_stats=False):
+        """trace_rays in the order of order_ptr (n uint32, DEVICE: order_rays' result or any permutation of the caller's): work-item j
+        traces ray order[j] and writes its outputs at that ray's index, so the buffers hold what trace_rays puts there.  An entry >= n
+        is skipped."""
+        out = RtRayOutputs(rgb_ptr or None, rgba_ptr or None, hits_ptr or None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_trace_rays_ordered_device(self.handle, n, C.c_void_p(rays_ptr or 0), C.c_void_p(order_ptr or 0), segs, C.byref(out),
+                                                         C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_trace_rays_ordered_device")
+        return st
+
     def close(self):
         if self.handle:
             self.lib.rt_scene_free(self.handle)
@@ -538,12 +562,21 @@ def primary_rays(width, height, scene):
     return rays.reshape(sh * sw, 6)
 
 
-def trace_rays(scene, rays, segs=0, want=("rgb",), lib=None):
+def rays_order_work_bytes(n, lib=None):
+    """Bytes of device workspace Renderer.order_rays needs for n rays (host arithmetic; 0 for n == 0 and n >= 2^31)."""
+    return int((lib or load_library()).rt_rays_order_work_bytes(n))
+
+
+def trace_rays(scene, rays, segs=0, want=("rgb",), lib=None, order="list"):
     """trace_rays(scene, rays) -> {"rgb": (n, 3) float64, "rgba": (n, 4) uint8, "hits": [hit dict or None per ray]} (the keys named in
     `want`): intersectWorld(segs, objects, org, dir) per row {org, dir} of the float64 (n, 6) array `rays`, directions as given, on
     GPU 0 with rt_render's resident scene.  segs 0 = the scene's depth.  A ray with a non-finite component is not traced: NaN, NaN,
-    NaN / 0, 0, 0, 255 / None."""
+    NaN / 0, 0, 0, 255 / None.  order: "list" traces the rays in the list's order; "binned" (rt_trace_rays_binned) has the GPU put
+    each chunk of 2^18 rays into an order in which neighbours are neighbours in space first - the same results, sooner for a list
+    that is not coherent."""
     import numpy as np
+    if order not in ("list", "binned"):
+        raise ValueError("order is 'list' or 'binned'")
     lib = lib or load_library()
     blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
     want = set(want)
@@ -566,7 +599,8 @@ def trace_rays(scene, rays, segs=0, want=("rgb",), lib=None):
                         C.addressof(records) if records is not None else None)
     _init_once(lib)
     buf = C.create_string_buffer(blob, len(blob))
-    _check(lib, lib.rt_trace_rays(buf, len(blob), n, C.c_void_p(aligned.ctypes.data), segs, C.byref(bufs), None), "rt_trace_rays")
+    call, what = (lib.rt_trace_rays, "rt_trace_rays") if order == "list" else (lib.rt_trace_rays_binned, "rt_trace_rays_binned")
+    _check(lib, call(buf, len(blob), n, C.c_void_p(aligned.ctypes.data), segs, C.byref(bufs), None), what)
     if records is not None:
         out["hits"] = [_hit_dict(r) for r in records[:n]]
     return out

@@ -13,7 +13,7 @@
  * of the calling thread's last call.
  *
  * Threads: rt_init, rt_shutdown and rt_render serialise on an internal lock.  The device entry points
- * (rt_scene_upload, rt_render_tiles_device, rt_render_batch_device, rt_scene_trace_rays_device, rt_deinterleave_*) may be called from several
+ * (rt_scene_upload, rt_render_tiles_device, rt_render_batch_device, rt_scene_trace_rays_device, rt_scene_order_rays_device, rt_deinterleave_*) may be called from several
  * threads at once; work on one HIP stream is ordered by the stream.  Launches with RT_FLAG_COUNT share one counter
  * buffer per device: one at a time per device.
  *
@@ -442,7 +442,9 @@ int rt_pick(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h, u
  * Any output may be NULL and is then not touched; all three NULL is RT_ERR_INVALID, as are n == 0, n >= 2^31, segs > RT_MAX_SEGS and
  * a NULL or misaligned ray pointer (16 bytes; rgb and hits need 8, rgba 4).  Outputs are written for every i < n and nowhere else.
  * One work-item per ray, and the 64 rays of a wave run in lock step: neighbouring rays in the list should be neighbouring rays in
- * space.  The library neither sorts nor bins the list - its coherence is the caller's business. */
+ * space.  These two calls take the list in its own order; for a list that is not coherent - probes at scattered points, collected
+ * secondary rays, sampled directions - rt_scene_order_rays_device + rt_scene_trace_rays_ordered_device (rt_trace_rays_binned for host
+ * memory) below bin it on the GPU first, with the same results. */
 typedef struct rt_ray_outputs {
   double  *rgb;    /* 3 per ray: the return value of intersectWorld, binary64, before any store rule; or NULL */
   uint8_t *rgba;   /* 4 per ray: 255 * rgb through the Uint8ClampedArray store of main.js:195-198, alpha 255; or NULL */
@@ -461,6 +463,47 @@ int rt_scene_trace_rays_device(rt_scene_dev *scene, uint64_t n, const double *d_
  * rays (ray i keeps pix = i), so the device memory the call allocates does not grow with n. */
 int rt_trace_rays(const void *scene_blob, size_t blob_bytes, uint64_t n, const double *rays, uint32_t segs,
                   const rt_ray_outputs *host_out, rt_stats *stats);
+
+/* Binning a ray list.  A wave of 64 unrelated rays walks 64 different ray trees in lock step (a shuffled 3840 x 2160 frame of primary
+ * rays costs 4 - 11 times the frame in row order, docs/EVIDENCE.md); these entry points put a list into an order in which the rays
+ * of a wave are neighbours, on the GPU, and trace it in that order.  No result depends on the order: every output of ray i is a
+ * function of the ray, the scene and i, and is written at index i - a binned trace fills the buffers with exactly the bytes of
+ * rt_scene_trace_rays_device.  Binning pays for lists whose neighbours in the list are NOT neighbours in space and whose trace is
+ * dear (many spheres, deep trees); a list that is coherent already (a frame in row order), or a scene whose shuffled trace costs
+ * about what the ordering does (docs/EVIDENCE.md, "Binned ray lists"), gains nothing.
+ *
+ * rt_rays_order_work_bytes: the bytes of DEVICE workspace an ordering of n rays needs; host arithmetic, no GPU, no rt_init.  0 for
+ * n == 0 and n >= 2^31; non-decreasing in n (about 12 bytes per ray + 1 KiB per 4096 rays). */
+size_t rt_rays_order_work_bytes(uint64_t n);
+
+/* Writes into d_order[0..n) (DEVICE memory, 4-byte aligned) a permutation of 0..n-1 in which 64 consecutive entries name rays that are
+ * close in origin and direction: the rays sorted by a 32-bit key that interleaves the bits of the origin's cell and of the direction's
+ * cell (its place on its cube-map face) inside the list's own bounds, axes the list does not vary in left out - a list that shares
+ * one origin is ordered by direction alone, one that shares a direction by origin alone.  Rays with a non-finite component come
+ * after all finite ones.  The sort is stable and the key a function of the list: the same list gives the same order on every call.
+ * The key reads NOTHING of the scene - `scene` names the device and its default stream, and the call waits for no pending
+ * rt_scene_set_objects / rt_scene_set_lights; an order stays valid while the list does, whatever is done to the scene.
+ * Asynchronous on `hip_stream` (NULL = the library's stream for the scene's device); no allocation and no host wait: `d_work` is
+ * work_bytes >= rt_rays_order_work_bytes(n) bytes of device memory (4-byte aligned) the call may overwrite, and d_order is written
+ * more than once on the way.  RT_ERR_INVALID: a NULL pointer, rays not 16-byte aligned, d_order or d_work not 4-byte aligned,
+ * work_bytes too small, n outside 1..2^31 - 1; RT_ERR_STATE: a NULL scene; all of them before a device is touched. */
+int rt_scene_order_rays_device(rt_scene_dev *scene, uint64_t n, const double *d_rays, uint32_t *d_order, void *d_work, size_t work_bytes,
+                               void *hip_stream);
+
+/* rt_scene_trace_rays_device in the order of `d_order` (n entries, DEVICE memory, 4-byte aligned): work-item j traces ray i = d_order[j],
+ * reads record i, draws its stars with pix = i and writes its outputs at index i.  For a permutation of 0..n-1 - the library's or
+ * the caller's own - the buffers hold exactly what rt_scene_trace_rays_device puts there: rgb bit for bit, rgba, hits.  An entry
+ * >= n is skipped: nothing is read or written for it (a ray no entry names keeps what its outputs held; a ray named twice is
+ * traced twice, with the same result).  Everything else - validation, non-finite rays, segs, stats, the scratch reservation, waiting for pending
+ * edits - is the plain call's; a NULL or misaligned d_order is RT_ERR_INVALID. */
+int rt_scene_trace_rays_ordered_device(rt_scene_dev *scene, uint64_t n, const double *d_rays, const uint32_t *d_order, uint32_t segs,
+                                       const rt_ray_outputs *d_out, void *hip_stream, rt_stats *stats);
+
+/* Host form: rt_trace_rays with each chunk of 2^18 rays ordered on the GPU before it is traced (chunks are binned one by one, not
+ * across each other; ray i keeps pix = i over the whole list).  The order buffer and the workspace are the call's own device memory,
+ * like the rest.  stats->kernel_ms includes the orderings.  The same bytes as rt_trace_rays in every output. */
+int rt_trace_rays_binned(const void *scene_blob, size_t blob_bytes, uint64_t n, const double *rays, uint32_t segs,
+                         const rt_ray_outputs *host_out, rt_stats *stats);
 
 #ifdef __cplusplus
 }
