@@ -19,6 +19,9 @@
 //                  beyond the patch.  The union over the block's candidates, per light, is a 16-bit set of loop-order sphere
 //                  indices (0xffffffff = no statement: scan everything); with more than 16 loop spheres a light's set is stored
 //                  as empty (0) or not (0xffff);
+//   * checker cells (RT_TABLE_CELLS) - for a block with ONE candidate whose sampler is the sphere checker: which of its four 8-pixel
+//                  columns lie, with every sample, inside one checker cell, and that cell's parity (rt_column_cell); bits 18..25 of
+//                  the candidates' word;
 //   * cost       - 1 + the weights of the spheres whose screen rectangle (the primary-ray cull's) touches the block, + what its
 //                  mirrors show of the scene's dearest spheres (rt_bounce_cost): what ranks the blocks dearest first.
 #ifndef RT_BLOCK_H
@@ -26,6 +29,8 @@
 
 #include <math.h>
 #include <stdint.h>
+
+#include "rt_fdlibm.h"
 
 #if defined(__HIPCC__)
 #define RT_HD __host__ __device__
@@ -42,7 +47,10 @@
 #define RT_TABLE_NO_SKY 64u      /* RT_FLAG_NO_SKY: the table holds no entry for sky blocks (their slots stay zero: no workgroup renders them) */
 #define RT_TABLE_SKY_ONLY 128u   /* RT_FLAG_SKY_ONLY: the table holds ONLY the sky runs */
 #define RT_TABLE_BOUNCE 256u     /* ranked launch of a scene with a sphere that both reflects and refracts: a block's cost also counts such spheres seen in its mirrors */
+#define RT_TABLE_CELLS 512u      /* checker cells: word 3 also says which 8-pixel columns of a one-candidate block lie inside ONE checker cell (rt_column_cell) */
 #define RT_SKY_RUN_MAX 32u       /* consecutive sky blocks of a row block that share ONE entry */
+#define RT_CAND_MASK 0x3ffffu     /* word 3, bits 0..17: the candidates; what every reader of them keeps */
+#define RT_CELL_SHIFT 18u        /* ... bits 18..21: column c (bit 18 + c) lies inside one checker cell; bits 22..25: that cell's parity */
 #define RT_COST_MAX 1023u        /* costs are clamped here (the ranking only has to order the blocks roughly) */
 
 // a sphere as the cone test sees it (one per sphere but the enclosing one, scene order)
@@ -60,6 +68,10 @@ struct rt_ball {
   uint32_t everywhere;           // the camera is inside / on / too near: no statement about any block
   uint32_t bounce;               // cost ranking only (RT_TABLE_BOUNCE): bit 0 the sphere reflects, bit 1 it refracts (depth >= 3)
   uint32_t heavy;                // ... and its weight if it does BOTH (every hit a two-child node of the ray tree, main.js:268-278), else 0
+  // checker cells (RT_TABLE_CELLS): the sphere's sampler is the checker with both frequencies in (0, 2^17] (the product kernel's range,
+  // zero - stripes - left out); its frequencies and its TRUE radius (the kernel's normal is (h - o) / r)
+  uint32_t checker, pad;
+  double fu, fv, r;
 };
 
 // a sphere's screen rectangle on the workgroup grid and what a block that shows it is expected to cost
@@ -105,13 +117,9 @@ RT_HD inline uint32_t rt_block_cost(const rt_table_params &P, const rt_cost_rect
 // say; doubt: nothing can be said about it (no geometry, or a box wider than a half space: never at these fields of view)
 struct rt_cone { double ax[3], cos_a, sin_a; uint32_t hit, doubt; };
 
-RT_HD inline rt_cone rt_block_cone(const rt_table_params &P, uint32_t x, uint32_t y) {
+// ... of the samples X0 .. X1 x Y0 .. Y1 (sample centres, in the units of the reference's ray)
+RT_HD inline rt_cone rt_box_cone(const rt_table_params &P, double X0, double X1, double Y0, double Y1) {
   rt_cone K;
-  K.ax[0] = K.ax[1] = K.ax[2] = 0.0; K.cos_a = 1.0; K.sin_a = 0.0; K.hit = 1u; K.doubt = 1u;
-  if (!(P.flags & RT_TABLE_GEOMETRY)) return K;
-  const double row0 = rt_block_row0(P, y);
-  const double Y1 = (P.proj_h - 0.5) - row0, Y0 = Y1 - (double)(P.wg_h - 1u);
-  const double X0 = (double)((uint64_t)x * P.wg_w) + (0.5 - P.proj_w), X1 = X0 + (double)(P.wg_w - 1u);
   const double cx[4] = {X0, X1, X0, X1}, cy[4] = {Y0, Y0, Y1, Y1};
   double u[4][3], ax[3] = {0.0, 0.0, 0.0};
   for (int k = 0; k < 4; k++) {                      // the reference's ray: (s0 * X, s1 * Y, s2 * D), main.js:186-193 (q1)
@@ -133,6 +141,16 @@ RT_HD inline rt_cone rt_block_cone(const rt_table_params &P, uint32_t x, uint32_
   K.cos_a = cos_a; K.sin_a = sqrt(fmax(0.0, 1.0 - cos_a * cos_a));
   K.hit = K.doubt = hit ? 1u : 0u;
   return K;
+}
+
+RT_HD inline rt_cone rt_block_cone(const rt_table_params &P, uint32_t x, uint32_t y) {
+  rt_cone K;
+  K.ax[0] = K.ax[1] = K.ax[2] = 0.0; K.cos_a = 1.0; K.sin_a = 0.0; K.hit = 1u; K.doubt = 1u;
+  if (!(P.flags & RT_TABLE_GEOMETRY)) return K;
+  const double row0 = rt_block_row0(P, y);
+  const double Y1 = (P.proj_h - 0.5) - row0, Y0 = Y1 - (double)(P.wg_h - 1u);
+  const double X0 = (double)((uint64_t)x * P.wg_w) + (0.5 - P.proj_w), X1 = X0 + (double)(P.wg_w - 1u);
+  return rt_box_cone(P, X0, X1, Y0, Y1);
 }
 
 // Cost ranking only: what a block's MIRRORS add to its cost.  The scene's dearest pixels are the hits on a sphere that both reflects and
@@ -237,6 +255,68 @@ RT_HD inline bool rt_cand_masks(const rt_table_params &P, const rt_cone &K, cons
   return true;
 }
 
+// Checker cells (RT_TABLE_CELLS).  A block with ONE candidate whose sampler is the sphere checker (main.js:126-133): do all the primary
+// rays of column `col` of the block - the 8 x 8 pixels (supersample 2: the 16 x 4 samples) of one wave of the one-wave trace kernels -
+// meet the candidate, and all inside the SAME checker cell?  Returns 1 | parity << 1 if so, else 0 (no statement).
+//   The column's rays lie in its own cone (rt_box_cone); their hits on the candidate lie in the ball around Q = the axis point at the
+// mid hit distance with radius rho (the bound of rt_cand_masks, here with the column's cone), so h - o lies within rho of W = Q - o -
+// wherever on the patch, whose outline is arcs, not the corners' hull.  From that
+//   v = asin(-(h - o).z / r) / pi + 1/2:   -(h - o).z / r within [(-W.z - rho) / r, (-W.z + rho) / r], asin is monotonic; an end at or
+//                                          beyond a pole: no statement;
+//   u = atan2(-(h - o).y, -(h - o).x) / 2 pi + 1/2:   the point (-(h - o).x, -(h - o).y) lies within rho of p0 = (-W.x, -W.y), so its angle
+//                                          within asin(rho / |p0|) of p0's; the z axis inside that disc, or the interval reaching
+//                                          the branch cut at +-pi: no statement.
+// The statement holds when [u_lo f_u, u_hi f_u] and [v_lo f_v, v_hi f_v] each lie inside one unit cell and at least `margin` off
+// its ends: 2^-18, twice the kernel's prefilter band (RT_XY_INDEX in rt_kernel.hip: a fraction within 2^-20 below or 2^-19 above an
+// integer; the scaled mark tolerance only acts INSIDE that band), plus 1e-10 f for the rounding of this bound and of the kernel's
+// own u, v (a few ulp of 1/2, times f) - so no sample of a flagged column can reach the precise test or the mark list.
+// Plain binary64 and fdlibm's asin / atan2 restated (rt_fdlibm.h): the same bits on the host and on the device.
+RT_HD inline void rt_block_place(const rt_table_params &P, uint32_t x, uint32_t y, uint32_t *w0, uint32_t *w1);
+RT_HD inline uint32_t rt_column_cell(const rt_table_params &P, const rt_ball &B, uint32_t x, uint32_t y, uint32_t col) {
+  if (!B.checker || B.everywhere) return 0u;
+  uint32_t w0, w1;
+  rt_block_place(P, x, y, &w0, &w1);
+  if (((w0 >> 11) & 15u) != P.rows_per_wg) return 0u;            // a block only partly inside its tile or the frame
+  const double row0 = rt_block_row0(P, y);
+  const double Y1 = (P.proj_h - 0.5) - row0, Y0 = Y1 - (double)(P.wg_h - 1u);
+  const uint32_t cw = P.wg_w / 4u;
+  const double X0 = (double)((uint64_t)x * P.wg_w + (uint64_t)col * cw) + (0.5 - P.proj_w), X1 = X0 + (double)(cw - 1u);
+  const rt_cone K = rt_box_cone(P, X0, X1, Y0, Y1);
+  if (K.doubt) return 0u;
+  // the hit distances [t1, t2] and the ball (Q, rho) of the hits: rt_cand_masks' own bound
+  const double *ax = K.ax;
+  const double cos_a = K.cos_a, sin_a = K.sin_a;
+  const double cs = fmin(1.0, fmax(-1.0, ax[0] * B.c[0] + ax[1] * B.c[1] + ax[2] * B.c[2])), sn = sqrt(1.0 - cs * cs);
+  const double c_hi = B.len * ((cs * cos_a + sn * sin_a >= 1.0 || sn <= sin_a) ? 1.0 : cs * cos_a + sn * sin_a);
+  const double c_lo = fmax(B.len * (cs * cos_a - sn * sin_a), B.tangent);
+  if (!(B.k > 0.0) || !(c_hi * c_hi >= B.k) || !(c_hi >= c_lo) || !(B.len - B.R >= 2.0 * fabs(P.epsilon))) return 0u;
+  // EVERY ray of the cone meets the sphere: the cone lies inside the silhouette, clear of the horizon (d.C >= the tangent length, with room)
+  if (!(B.len * (cs * cos_a - sn * sin_a) >= B.tangent * (1.0 + 1e-7))) return 0u;
+  const double t1 = (c_hi - sqrt(fmax(c_hi * c_hi - B.k, 0.0))) * (1.0 - 1e-6), t2 = (c_lo - sqrt(fmax(c_lo * c_lo - B.k, 0.0))) * (1.0 + 1e-6);
+  if (!(t2 >= t1) || !(t1 >= 0.0) || !(t2 <= 1.7976931348623157e308)) return 0u;
+  const double m = 0.5 * (t1 + t2), rho = sqrt(0.25 * (t2 - t1) * (t2 - t1) + 2.0 * t2 * m * (1.0 - cos_a)) * (1.0 + 1e-6) + 1e-9 * t2;
+  const double W[3] = {(P.cam[0] + m * ax[0]) - B.o[0], (P.cam[1] + m * ax[1]) - B.o[1], (P.cam[2] + m * ax[2]) - B.o[2]};
+  if (!(B.r > 0.0) || !(rho <= B.r)) return 0u;
+  // v
+  const double s_lo = (-W[2] - rho) / B.r, s_hi = (-W[2] + rho) / B.r;
+  if (!(s_lo > -1.0) || !(s_hi < 1.0)) return 0u;
+  const double v_lo = fd_asin(s_lo) / (M_PI / 2.0) / 2.0 + 0.5, v_hi = fd_asin(s_hi) / (M_PI / 2.0) / 2.0 + 0.5;
+  // u
+  const double d0 = sqrt(W[0] * W[0] + W[1] * W[1]);
+  if (!(d0 > rho * (1.0 + 1e-6))) return 0u;
+  const double phi = fd_atan2(-W[1], -W[0]), dphi = fd_asin(fmin(1.0, rho / d0)) * (1.0 + 1e-9) + 1e-12;
+  if (!(phi - dphi > -3.14159) || !(phi + dphi < 3.14159)) return 0u;
+  const double u_lo = (phi - dphi) / M_PI / 2.0 + 0.5, u_hi = (phi + dphi) / M_PI / 2.0 + 0.5;
+  const double xu0 = u_lo * B.fu, xu1 = u_hi * B.fu, xv0 = v_lo * B.fv, xv1 = v_hi * B.fv;
+  const double mu = 3.814697265625e-06 + 1e-10 * B.fu, mv = 3.814697265625e-06 + 1e-10 * B.fv;
+  const double ku = floor(xu0), kv = floor(xv0);
+  if (!(ku >= 0.0) || !(kv >= 0.0) || !(xu0 - ku >= mu) || !((ku + 1.0) - xu1 >= mu) || !(xv0 - kv >= mv) || !((kv + 1.0) - xv1 >= mv)) return 0u;
+  return 1u | ((((uint32_t)ku ^ (uint32_t)kv) & 1u) << 1);
+}
+
+// word 3's upper bits for a block whose word 3 names ONE candidate, ball ci: the four columns' statements
+RT_HD inline uint32_t rt_cell_bits(uint32_t col, uint32_t st) { return ((st & 1u) << (RT_CELL_SHIFT + col)) | (((st >> 1) & 1u) << (RT_CELL_SHIFT + 4u + col)); }
+
 // touched / candidates / shadow masks of block (x, y), one block after the other (the host); *touched = 1 also when nothing can be said
 RT_HD inline void rt_block_statement(const rt_table_params &P, const rt_ball *balls, uint32_t x, uint32_t y, uint32_t *touched, uint32_t *cands_out, uint32_t *smask_out,
                                      uint32_t *bounce_extra) {
@@ -255,6 +335,9 @@ RT_HD inline void rt_block_statement(const rt_table_params &P, const rt_ball *ba
   *touched = hit ? 1u : 0u;
   if (doubt || n_cand == 0u) return;
   *cands_out = rt_cand_word(P, balls, cand, n_cand);
+  if ((P.flags & RT_TABLE_CELLS) && (*cands_out >> 16) == 1u)
+    for (uint32_t ci = 0; ci < P.n_balls; ci++)
+      if (cand[ci >> 6] >> (ci & 63u) & 1ull) for (uint32_t col = 0; col < 4u; col++) *cands_out |= rt_cell_bits(col, rt_column_cell(P, balls[ci], x, y, col));
   if (P.flags & RT_TABLE_BOUNCE)
     for (uint32_t ci = 0; ci < P.n_balls; ci++) if (cand[ci >> 6] >> (ci & 63u) & 1ull) *bounce_extra += rt_bounce_cost(P, K, balls, ci);
   if (!(P.flags & RT_TABLE_MASKS)) return;

@@ -5,12 +5,20 @@
 #ifndef RT_FDLIBM_H
 #define RT_FDLIBM_H
 
-#include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
-__device__ __forceinline__ uint32_t fd_hi(double x) { return (uint32_t)(__builtin_bit_cast(unsigned long long, x) >> 32); }
-__device__ __forceinline__ uint32_t fd_lo(double x) { return (uint32_t)__builtin_bit_cast(unsigned long long, x); }
-__device__ __forceinline__ double fd_atan(double x) {
+// (device code of the kernels, and - through rt_block.h - the launch table's host and device builds: the same operations, the same bits)
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define FD_FN __host__ __device__ __forceinline__
+#else
+#define FD_FN static inline
+#endif
+
+FD_FN uint32_t fd_hi(double x) { return (uint32_t)(__builtin_bit_cast(unsigned long long, x) >> 32); }
+FD_FN uint32_t fd_lo(double x) { return (uint32_t)__builtin_bit_cast(unsigned long long, x); }
+FD_FN double fd_atan(double x) {
   const double hi0 = 4.63647609000806093515e-01, hi1 = 7.85398163397448278999e-01, hi2 = 9.82793723247329054082e-01, hi3 = 1.57079632679489655800e+00;
   const double lo0 = 2.26987774529616870924e-17, lo1 = 3.06161699786838301793e-17, lo2 = 1.39033110312309984516e-17, lo3 = 6.12323399573676603587e-17;
   const double a0 = 3.33333333333329318027e-01, a1 = -1.99999999998764832476e-01, a2 = 1.42857142725034663711e-01, a3 = -1.11111104054623557880e-01,
@@ -37,7 +45,7 @@ __device__ __forceinline__ double fd_atan(double x) {
   const double r = ahi - ((x * (s1 + s2) - alo) - x);
   return hx < 0 ? -r : r;
 }
-__device__ __forceinline__ double fd_atan2(double y, double x) {
+FD_FN double fd_atan2(double y, double x) {
   const double tiny = 1.0e-300, pi_o_4 = 7.8539816339744827900E-01, pi_o_2 = 1.5707963267948965580E+00, pi = 3.1415926535897931160E+00, pi_lo = 1.2246467991473531772E-16;
   const int32_t hx = (int32_t)fd_hi(x), hy = (int32_t)fd_hi(y);
   const uint32_t lx = fd_lo(x), ly = fd_lo(y), ix = (uint32_t)hx & 0x7fffffffu, iy = (uint32_t)hy & 0x7fffffffu;
@@ -58,7 +66,7 @@ __device__ __forceinline__ double fd_atan2(double y, double x) {
   else z = fd_atan(__builtin_fabs(y / x));
   return m == 0 ? z : (m == 1 ? -z : (m == 2 ? pi - (z - pi_lo) : (z - pi_lo) - pi));
 }
-__device__ __forceinline__ double fd_asin(double x) {
+FD_FN double fd_asin(double x) {
   const double pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17, pio4_hi = 7.85398163397448278999e-01;
   const double pS0 = 1.66666666666666657415e-01, pS1 = -3.25565818622400915405e-01, pS2 = 2.01212532134862925881e-01, pS3 = -4.00555345006794114027e-02,
                pS4 = 7.91534994289814532176e-04, pS5 = 3.47933107596021167570e-05;

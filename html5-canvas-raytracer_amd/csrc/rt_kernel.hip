@@ -55,6 +55,7 @@
 #include <stdint.h>
 
 #include "rt_device.h"
+#include "rt_block.h"      // the launch table's words (RT_CAND_MASK, RT_CELL_SHIFT)
 
 #ifndef RT_STRICT
 #define RT_STRICT 0
@@ -355,7 +356,7 @@ typedef const rt_sphere __attribute__((address_space(4))) *sphere_kptr;
 // Which pixel (or sample) a work-item owns.  Evaluated twice from the work-item id — before the ray is generated and
 // again after the trace, behind an opaque copy of the id — so that px / lrow / valid are not kept live in VGPRs across
 // the whole trace (they would be the 97th register: the kernel fits the 96 of 5 waves per SIMD without them).
-struct rt_pixel { uint32_t px, trow, frow, lrow, sub, rows_valid, run, cand; bool valid, sky; };
+struct rt_pixel { uint32_t px, trow, frow, lrow, sub, rows_valid, run, cand, cell; bool valid, sky; };
 // W1 - ONE-WAVE workgroups (the reflection-only many-sphere variants, rt_trace): the entry's 32 x 8 block is rendered by FOUR
 // workgroups of one wave each, workgroup b = xcd + 8 * (wave + 4 * e') for entry e = 8 e' + xcd: the four waves of a block are
 // consecutive workgroups of ONE XCD, and an XCD still reads one contiguous eighth of the table.
@@ -392,13 +393,13 @@ __device__ __forceinline__ rt_pixel rt_pixel_of(const rt_launch &L, uint32_t tid
   P.lrow = tile_i * L.tile_rows + P.trow;                                    // row in this call's output band
   P.valid = (P.px < L.w) && (P.trow < L.tile_rows) && (P.frow < L.h);
   P.rows_valid = 0u;                                   // (product kernel only)
-  P.sky = false; P.run = 1u; P.cand = 0u;
+  P.sky = false; P.run = 1u; P.cand = 0u; P.cell = 0u;
   return P;
 }
 #else
 // Product kernel: a FLAT grid (workgroups, 1, frames of the batch) and a launch table with one 16-byte entry per workgroup:
 //   word 0 = tile_x | rows_valid << 11 | first frame row << 15      word 1 = first row in this call's output band | (run - 1) << 24 | sky << 31
-//   word 2 = shadow masks                                            word 3 = primary candidates
+//   word 2 = shadow masks                                            word 3 = primary candidates | checker cells << 18
 // (built on the GPU per camera, frame size and tile set: rt_tables_gpu.hip, rt_block.h).  One scalar load replaces the tile /
 // row-block arithmetic of the plain grid - no division, no tile parameters in registers - and decides the ORDER in which the
 // hardware hands the tiles out: dearest first, so that a launch ends on cheap sky tiles instead of on the floor.  trow is the row
@@ -420,7 +421,8 @@ __device__ __forceinline__ rt_pixel rt_pixel_of(const rt_launch &L, uint32_t tid
   P.lrow = (e1 & 0xffffffu) + P.trow;
   P.sky = (e1 >> 31) != 0u;                            // workgroup-uniform: no sphere can show in these blocks (rt_block.h) ...
   P.run = ((e1 >> 24) & 127u) + 1u;                    // ... a run of this many 32-pixel blocks, starting at tile_x
-  P.cand = e4.w;                                       // the (at most two) loop spheres the block's primary rays can meet (count << 16 | second << 8 | first), or 0: cull
+  P.cand = e4.w & RT_CAND_MASK;                        // the (at most two) loop spheres the block's primary rays can meet (count << 16 | second << 8 | first), or 0: cull
+  P.cell = e4.w >> RT_CELL_SHIFT;                      // checker cells of a one-candidate block (rt_block.h: rt_column_cell): bit c - column c lies inside ONE cell, bit 4 + c - its parity
   P.rows_valid = rows_valid;                           // wave-uniform: rows of the block inside its tile and the frame
   P.valid = (P.px < L.w) && (P.trow < rows_valid);
   return P;
@@ -952,8 +954,12 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
           }
         // (UNI: the sampler is the wave's - ONE inlined copy of the atan2 / asin pair serves both, its arguments chosen by the scalar kind)
         [[maybe_unused]] double t_at, t_as;
+        // (UNI, bit 24 of cand_host: the launch table states that every sample of this wave meets the candidate inside ONE checker cell,
+        // clear of the boundary test's band - parity in bit 28, rt_block.h: rt_column_cell.  The wave then agrees on nothing: no u, v)
+        // (few-sphere kernels only: the many-sphere one-wave form has no scalar register left for it - tests/test_kernel_resources.py)
+        [[maybe_unused]] const bool one_cell = UNI && !GRID && kind == RT_SAMPLER_CHECKER && (cand_host & (1u << 24)) != 0u;
         if constexpr (UNI) {
-          if (kind == RT_SAMPLER_TEXTURE || kind == RT_SAMPLER_CHECKER) {
+          if (kind == RT_SAMPLER_TEXTURE || (kind == RT_SAMPLER_CHECKER && !one_cell)) {
             const bool tx_ = (kind == RT_SAMPLER_TEXTURE);
             rt_atan2_asin(tx_ ? -n.z : -n.y, -n.x, tx_ ? -n.y : -n.z, &t_at, &t_as);
           }
@@ -971,6 +977,10 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
           const uint32_t texel = *(const uint32_t *)(rt_cold_args()->texel_base + td.texels_offset + ((size_t)yi * td.width + xi) * 4u);
           col[0] = RT_DIV_CONST((double)(texel & 255u), 255.0); col[1] = RT_DIV_CONST((double)((texel >> 8) & 255u), 255.0);
           col[2] = RT_DIV_CONST((double)((texel >> 16) & 255u), 255.0);
+        } else if (UNI && one_cell) {
+          // the cell's colour: three scalar operands, fetched through a scalar offset (nothing per lane)
+          const uint32_t c3 = (cand_host >> 28) & 1u ? 3u : 0u;
+          col[0] = m.c[c3]; col[1] = m.c[c3 + 1u]; col[2] = m.c[c3 + 2u];
         } else if (kind == RT_SAMPLER_CHECKER) {
           if constexpr (!UNI) rt_atan2_asin(-n.y, -n.x, -n.z, &t_at, &t_as);
           const double u = RT_DIV_CONST(t_at, M_PI) / 2.0 + 0.5;   // main.js:127 (its own axes)
@@ -1552,10 +1562,13 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
   // no staging, no LDS access, no node loop.  A one-wave workgroup decides for itself: no barrier is involved.  The four-wave forms
   // (peer stores, a moved camera's first frame, the general kernel) do not take the path.
   [[maybe_unused]] bool uni_try = false;
+  [[maybe_unused]] uint32_t cell = 0u;
   if constexpr (UNI_OK) {
     uni_try = !P0.sky && (P0.cand >> 16) == 1u;
+    if constexpr (!GRID) cell = (P0.cell >> rt_wave_of<W1>(tid)) & 0x11u;     // this wave's column of the block: bit 0 - inside one checker cell, bit 4 - the cell's parity
 #ifdef RT_TESTING
     if (L.no_uniform) uni_try = false;                  // test build (RT_NO_UNIFORM_BLOCKS): every wave on the general path
+    if (L.no_cells) cell = 0u;                          // test build (RT_NO_CHECKER_CELLS): every wave works its checker out per sample
 #endif
     if (!uni_try && !P0.sky) stage_issue(tid);
   }
@@ -1623,7 +1636,7 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
   if constexpr (UNI_OK) {
     if (uni_try) {
       uni_done = trace_pixel<REFRACT, COUNT, GRID, SS2, false, W1, true>(L, (const rt_mtl *)L.lds_image, (const rt_texture_desc *)((const double *)L.lds_image + mtl_words), acc,
-                                                                         cull_lds, cull0, lane, 0.0, 0.0, 0.0, 0.0, o, ray, rgb, cnt, is_probe, P0.cand);
+                                                                         cull_lds, cull0, lane, 0.0, 0.0, 0.0, 0.0, o, ray, rgb, cnt, is_probe, P0.cand | (cell << 24));
       if (!uni_done) {
         uint32_t tid4 = threadIdx.x;
         asm volatile("" : "+v"(tid4));                 // opaque: no address is kept in registers across the attempt
@@ -1631,7 +1644,10 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
         stage_finish(tid4);
       }
 #ifdef RT_TESTING
-      else if (lane == 0u && L.uniform_waves != nullptr) atomicAdd(L.uniform_waves, 1ull);      // test build: waves that took the path
+      else if (lane == 0u && L.uniform_waves != nullptr) {                                      // test build: waves that took the path ...
+        atomicAdd(L.uniform_waves, 1ull);
+        if (cell & 1u) atomicAdd(L.uniform_waves + 1, 1ull);                                     // ... and of those, the ones that took their checker cell from the table
+      }
 #endif
     }
   }

@@ -58,6 +58,19 @@ extern "C" int rt_test_uniform_waves(int device, unsigned long long *out_waves) 
   HIP_TRY(hipMemset(D.d_counters + 3, 0, sizeof *out_waves));
   return RT_OK;
 }
+// ... and how many of the waves that took it had their checker cell from the launch table (rt_block.h: rt_column_cell) instead of working
+// it out per sample; a counter of its own, read and cleared the same way
+extern "C" int rt_test_cell_waves(int device, unsigned long long *out_waves) {
+  if (!out_waves) return fail(RT_ERR_INVALID, "rt_test_cell_waves: NULL argument");
+  int rc = ensure_device(device);
+  if (rc) return rc;
+  device_state &D = G.dev[device];
+  HIP_TRY(hipSetDevice(D.hip_id));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out_waves, D.d_counters + 4, sizeof *out_waves, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemset(D.d_counters + 4, 0, sizeof *out_waves));
+  return RT_OK;
+}
 #endif
 
 extern "C" int rt_render_batch_device(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, uint32_t n_frames, void *d_out,
@@ -315,6 +328,7 @@ int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *t
   L.probe = g_probe.d_buf; L.probe_x = g_probe.x; L.probe_y = g_probe.y;
   L.no_uniform = getenv("RT_NO_UNIFORM_BLOCKS") ? 1u : 0u;     // A/B switch, read per call: every wave on the general path (rt_kernel.hip: trace_pixel, UNI)
   L.uniform_waves = D.d_counters + 3;
+  L.no_cells = getenv("RT_NO_CHECKER_CELLS") ? 1u : 0u;        // A/B switch, read per call: the table's checker cells are ignored (rt_kernel.hip: trace_pixel, one_cell)
 #endif
 
   event_timer timer;                                     // (a stats call)

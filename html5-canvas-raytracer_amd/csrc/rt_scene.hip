@@ -43,6 +43,7 @@ uint32_t sky_part_of(uint32_t flags) { return (flags & RT_FLAG_NO_SKY) ? 1u : ((
 //   shadow masks: per block and light, the spheres that can shadow a primary hit of the block at all; needs every lit primary
 //     hit to lie on a loop sphere, i.e. no enclosing sphere or a flat one
 //   candidates: the block's primary candidates
+//   checker cells: which 8-pixel columns of a one-candidate block lie inside one cell of that sphere's checker (rt_block.h)
 //   (a table of nothing but sky runs is read by workgroups that store a constant: neither masks nor candidates)
 table_choice choose_table(const rt_scene_dev *s, uint32_t flags, uint32_t uses_before) {
   static const bool no_order = RT_TEST_ENV("RT_NO_DISPATCH_ORDER") != nullptr;    // A/B switches (test build): the grid's own order,
@@ -55,6 +56,7 @@ table_choice choose_table(const rt_scene_dev *s, uint32_t flags, uint32_t uses_b
   c.mark_sky = !count && !no_sky_tiles && sky_fast(s);
   c.shadow_masks = !count && !no_shadow_masks && masks_pay(s, uses_before) && part != 2u && (s->enclosing == ~0u || s->enclosing_flat);
   c.name_candidates = !count && !no_shadow_masks && part != 2u;
+  c.checker_cells = c.name_candidates;                // (costs the build nothing unless the scene has a checker sphere: rt_tables.cpp)
   return c;
 }
 
@@ -656,7 +658,7 @@ bool build_table(rt_scene_dev *s, int found, hipStream_t stream, rt_scene_dev::s
   std::vector<rt_ball> balls;
   std::vector<rt_cost_rect> rects;
   if (make_table_params(&s->hd, s->host_objects.data(), s->host_cull, s->tile_weight, k.w, k.h, k.ss, &k.tiles, g.tiles_x, g.rb_per_tile, g.proj_w, g.proj_h, g.proj_d, e.ranked,
-                        e.sky, s->enclosing, e.masks, e.cands, s->lights, &P, &balls, &rects)) {
+                        e.sky, s->enclosing, e.masks, e.cands, e.cells, s->lights, &P, &balls, &rects)) {
     fail(RT_ERR_INVALID, "a launch of %llu workgroups is beyond the launch table", (unsigned long long)g.tiles_x * k.tiles.n_tiles * g.rb_per_tile);
     return false;
   }
@@ -730,7 +732,7 @@ int dispatch_order(rt_scene_dev *s, const frame_kind &kind, const table_choice &
   int found = -1;
   for (size_t i = 0; i < s->orders.size(); i++) {
     const rt_scene_dev::order_entry &e = s->orders[i];
-    if (e.kind == kind && e.ranked == c.ranked && e.sky == c.mark_sky && e.masks == c.shadow_masks && e.cands == c.name_candidates) { found = (int)i; break; }
+    if (e.kind == kind && e.ranked == c.ranked && e.sky == c.mark_sky && e.masks == c.shadow_masks && e.cands == c.name_candidates && e.cells == c.checker_cells) { found = (int)i; break; }
   }
   if (found >= 0 && s->orders[found].cam_gen == s->cam_gen) {
     rt_scene_dev::order_entry &e = s->orders[found];
@@ -760,7 +762,7 @@ int dispatch_order(rt_scene_dev *s, const frame_kind &kind, const table_choice &
     rt_scene_dev::order_entry &e = s->orders[found];
     memset(&e, 0, sizeof e);
     e.kind = kind;
-    e.ranked = c.ranked; e.sky = c.mark_sky; e.masks = c.shadow_masks; e.cands = c.name_candidates;
+    e.ranked = c.ranked; e.sky = c.mark_sky; e.masks = c.shadow_masks; e.cands = c.name_candidates; e.cells = c.checker_cells;
     e.known = known_word(s, RT_KNOWN_WORDS + (size_t)found);
     if (e.known) *e.known = 0ull;                        // (a table evicted from this slot may have published its count for the same camera)
   }
@@ -812,7 +814,7 @@ extern "C" int rt_test_launch_table(rt_scene_dev *s, uint32_t w, uint32_t h, con
   const uint32_t ss = s->hd.supersample;
   if (ss > 2u) return fail(RT_ERR_INVALID, "supersample 3 and 4 launch on the sample grid");
   const frame_kind kind = {w, h, ss, *tiles, (ranked & 8) ? 1u : ((ranked & 16) ? 2u : 0u)};
-  const table_choice c = {(ranked & 1) != 0, (ranked & 2) != 0, (ranked & 4) != 0, (ranked & 4) != 0};
+  const table_choice c = {(ranked & 1) != 0, (ranked & 2) != 0, (ranked & 4) != 0, (ranked & 4) != 0, (ranked & 32) != 0};
   std::lock_guard<std::mutex> lk(s->launch_mu);
   if ((rc = behind_the_camera(s, stream))) return rc;
   const int oi = dispatch_order(s, kind, c, stream);

@@ -106,6 +106,15 @@ __global__ void __launch_bounds__(WG_ROWS) rt_table_rows(const rt_table_dev T, u
       touched = (K.hit || everywhere || n_cand) ? 1u : 0u;
       if (!doubt && n_cand) {
         if (sub == 0u) cands = rt_cand_word(P, balls, cand, n_cand);
+        if ((P.flags & RT_TABLE_CELLS) && (P.flags & RT_TABLE_CANDS) && n_cand == 1u) {      // checker cells: work-item `sub` states column `sub` (group-uniform branch)
+          uint32_t ci = 0u, bits = 0u;
+          for (uint32_t wd = 0; wd < 4u; wd++) if (cand[wd]) { ci = wd * 64u + (uint32_t)__builtin_ctzll(cand[wd]); break; }
+          if (balls[ci].checker) {                      // (uniform as well: the statement is only worked out for a checker sphere)
+            for (uint32_t col = sub; col < 4u; col += SUB) bits |= rt_cell_bits(col, rt_column_cell(P, balls[ci], x, y, col));
+            bits = group_or<SUB>(bits);
+            cands |= (sub == 0u) ? bits : 0u;
+          }
+        }
         if (P.flags & RT_TABLE_BOUNCE) {                // (ranking only) what the block's mirrors show of the scene's dearest spheres
           for (uint32_t ci = sub; ci < P.n_balls; ci += SUB) if ((cand[ci >> 6] >> (ci & 63u)) & 1ull) extra += rt_bounce_cost(P, K, balls, ci);
           extra = group_add<SUB>(extra);
