@@ -2,8 +2,8 @@
 // scene (rt_scene_dev) and the few functions that cross units.  Not part of the ABI.
 //   rt_api.hip     lifetime, errors, device state, the scratch guard, the host-logic probes, memory helpers, IPC
 //   rt_scene.hip   upload and moves of a resident scene (the generation pipeline), its launch decisions and launch tables
-//   rt_launch.hip  the launches: colour (product / strict / retrace), supersampling, compact bands, primary hits and picking, ray lists
-//   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick
+//   rt_launch.hip  the launches: colour (product / strict / retrace), supersampling, compact bands, primary hits and picking, ray lists, occlusion queries
+//   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick, rt_trace_rays, rt_occlusion
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H
 
@@ -28,6 +28,7 @@
 #include "rt_hits.h"
 #include "rt_objects_gpu.h"
 #include "rt_rays_order.h"
+#include "rt_occlusion.h"
 
 extern "C" int rt_launch_trace_fast(const rt_launch *, int, int, int, unsigned, hipStream_t);
 extern "C" int rt_launch_trace_strict(const rt_launch *, int, int, int, unsigned, hipStream_t);
@@ -287,6 +288,10 @@ int rays_order_check(uint64_t n, const double *rays, const uint32_t *order, cons
 int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *d_rays, const uint32_t *d_order, uint32_t segs, const rt_ray_outputs &out,
                       hipStream_t stream, rt_stats *stats);
 int order_rays_launch(uint32_t n, const double *d_rays, uint32_t *d_order, void *d_work, hipStream_t stream);
+// ... and of the occlusion entry points (`in` may be NULL); the launch of n segments (device pointers), in the list's order or a given one
+int occlusion_check(uint64_t n, const double *rays, const rt_occlusion_inputs *in, const rt_occlusion_outputs *out, const char *what);
+int occlusion_launch(rt_scene_dev *s, uint32_t n, const double *d_rays, const uint32_t *d_order, const rt_occlusion_inputs &in,
+                     const rt_occlusion_outputs &out, hipStream_t stream, rt_stats *stats);
 
 // rt_frame.hip: RCCL's communicators are destroyed (rt_shutdown)
 void release_rccl();

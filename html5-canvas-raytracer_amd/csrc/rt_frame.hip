@@ -1,4 +1,4 @@
-// rt_frame.hip — rt_render(width, height, scene) and its kin (rt_render_progressive, rt_render_hits, rt_pick, rt_trace_rays, rt_trace_rays_binned): the resident scene
+// rt_frame.hip — rt_render(width, height, scene) and its kin (rt_render_progressive, rt_render_hits, rt_pick, rt_trace_rays, rt_trace_rays_binned, rt_occlusion, rt_occlusion_binned): the resident scene
 // per device (scene_for), the one-GPU plans (banded copy-out, stores straight into a pinned frame) and the single-process multi-GPU
 // frame (interleaved row tiles stored straight into GPU 0's frame over xGMI; fallback: RGB24 bands + one RCCL gather + de-interleave).
 
@@ -335,6 +335,77 @@ extern "C" int rt_trace_rays(const void *blob, size_t bytes, uint64_t n, const d
 extern "C" int rt_trace_rays_binned(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *ho,
                                     rt_stats *stats) {
   return trace_rays_to_host(blob, bytes, n, rays, segs, ho, stats, true, "rt_trace_rays_binned");
+}
+
+// The shadow scan for a list of segments in host memory, with rt_render's resident scene: chunks of RT_RAY_CHUNK segments go through one
+// set of device buffers, as the ray lists do.  Synchronous; kernel_ms is the sum over the chunks.  `binned` (rt_occlusion_binned): every
+// chunk is ordered on the GPU (rt_rays_order.hip) and scanned in that order; kernel_ms includes the orderings.
+namespace {
+int occlusion_to_host(const void *blob, size_t bytes, uint64_t n, const double *rays, const rt_occlusion_inputs *hi, const rt_occlusion_outputs *ho,
+                      rt_stats *stats, bool binned, const char *what) {
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  if ((rc = occlusion_check(n, rays, hi, ho, what))) return rc;
+  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
+  std::lock_guard<std::mutex> lk(G.mu);
+  const auto t_begin = std::chrono::steady_clock::now();
+  rt_scene_dev *s = nullptr;
+  if ((rc = scene_for(0, blob, bytes, &s))) return rc;
+  if ((rc = ensure_device(0))) return rc;
+  device_state &D = G.dev[0];
+  const size_t chunk = n < RT_RAY_CHUNK ? (size_t)n : RT_RAY_CHUNK;
+  // 0 rays, 1 length, 2 intensity in, 3 skip (inputs); 4 intensity, 5 blocker (outputs); 6 order, 7 the ordering's workspace
+  struct device_bufs { void *p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; ~device_bufs() { for (void *q : p) if (q) (void)hipFree(q); } } mem;
+  const size_t each[6] = {6u * sizeof(double), sizeof(double), sizeof(double), sizeof(int32_t), sizeof(double), sizeof(int32_t)};
+  uint8_t *const host[6] = {(uint8_t *)rays, hi ? (uint8_t *)hi->length : nullptr, hi ? (uint8_t *)hi->intensity : nullptr, hi ? (uint8_t *)hi->skip : nullptr,
+                            (uint8_t *)ho->intensity, (uint8_t *)ho->blocker};
+  for (int i = 0; i < 6; i++) if (host[i]) HIP_TRY(hipMalloc(&mem.p[i], chunk * each[i]));
+  if (binned) {
+    HIP_TRY(hipMalloc(&mem.p[6], chunk * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&mem.p[7], rt_rays_order_work_bytes(chunk)));
+  }
+  const rt_occlusion_inputs din = {(const double *)mem.p[1], (const double *)mem.p[2], (const int32_t *)mem.p[3]};
+  const rt_occlusion_outputs dout = {(double *)mem.p[4], (int32_t *)mem.p[5]};
+  double kernel_ms = 0.0;
+  for (uint64_t base = 0; base < n; base += chunk) {
+    const size_t m = n - base < chunk ? (size_t)(n - base) : chunk;
+    for (int i = 0; i < 4; i++) if (host[i]) HIP_TRY(hipMemcpyAsync(mem.p[i], host[i] + base * each[i], m * each[i], hipMemcpyHostToDevice, D.stream));
+    if (binned) {
+      event_timer timer;                                 // (a stats call)
+      if (stats) HIP_TRY(timer.start(D.stream));
+      if ((rc = order_rays_launch((uint32_t)m, (const double *)mem.p[0], (uint32_t *)mem.p[6], mem.p[7], D.stream))) return rc;
+      if (stats) {
+        HIP_TRY(timer.stop(D.stream));
+        HIP_TRY(hipEventSynchronize(timer.b));
+        float ms = 0.f;
+        HIP_TRY(timer.elapsed(&ms));
+        kernel_ms += ms;
+      }
+    }
+    rt_stats st;
+    if ((rc = occlusion_launch(s, (uint32_t)m, (const double *)mem.p[0], (const uint32_t *)mem.p[6], din, dout, D.stream, stats ? &st : nullptr))) return rc;
+    if (stats) kernel_ms += st.kernel_ms;
+    for (int i = 4; i < 6; i++) if (host[i]) HIP_TRY(hipMemcpyAsync(host[i] + base * each[i], mem.p[i], m * each[i], hipMemcpyDeviceToHost, D.stream));
+    HIP_TRY(hipStreamSynchronize(D.stream));
+  }
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = kernel_ms;
+    stats->pixels = n;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_occlusion(const void *blob, size_t bytes, uint64_t n, const double *rays, const rt_occlusion_inputs *hi, const rt_occlusion_outputs *ho,
+                            rt_stats *stats) {
+  return occlusion_to_host(blob, bytes, n, rays, hi, ho, stats, false, "rt_occlusion");
+}
+
+extern "C" int rt_occlusion_binned(const void *blob, size_t bytes, uint64_t n, const double *rays, const rt_occlusion_inputs *hi,
+                                   const rt_occlusion_outputs *ho, rt_stats *stats) {
+  return occlusion_to_host(blob, bytes, n, rays, hi, ho, stats, true, "rt_occlusion_binned");
 }
 
 namespace {

@@ -1,6 +1,6 @@
 // rt_launch.hip — the launches of a resident scene (include/rt_hip.h: rt_render_*_device): the product launch with its launch table
 // and the list-driven strict launch behind it (rt_retrace), the strict kernel, 3x3 / 4x4 supersampling with a box filter, compact
-// bands, primary hits and picking, caller-supplied rays (rt_trace_rays) in the list's or a given order and their ordering, and the test
+// bands, primary hits and picking, caller-supplied rays (rt_trace_rays) in the list's or a given order and their ordering, occlusion queries, and the test
 // build's per-sample probe.
 
 #include "rt_api_internal.h"
@@ -816,4 +816,69 @@ extern "C" int rt_scene_trace_rays_ordered_device(rt_scene_dev *s, uint64_t n, c
   if (!s) return fail(RT_ERR_STATE, "rt_scene_trace_rays_ordered_device: NULL scene handle");
   if ((rc = ensure_device(s->device))) return rc;
   return trace_rays_launch(s, (uint32_t)n, 0u, d_rays, d_order, segs, *d_out, hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream, stats);
+}
+
+// ------------------------------------------------------------------------------------ occlusion queries (rt_occlusion.hip)
+// The reference's shadow scan (main.js:293-304) for a list of segments (include/rt_hip.h: rt_scene_occlusion_device).  One kernel, no
+// launch decision: it reads the current generation's spheres in blob order, epsilon and the light intensity - camera, launch tables,
+// flags, textures and the lights' positions play no part - so it comes behind the scene's preparation like every other launch.
+namespace rt_api {
+int occlusion_check(uint64_t n, const double *rays, const rt_occlusion_inputs *in, const rt_occlusion_outputs *out, const char *what) {
+  if (!rays || !out) return fail(RT_ERR_INVALID, "%s: NULL rays or outputs", what);
+  if (n == 0 || n >= (1ull << 31)) return fail(RT_ERR_INVALID, "%s: n %llu not in 1..2^31 - 1", what, (unsigned long long)n);
+  if (!out->intensity && !out->blocker) return fail(RT_ERR_INVALID, "%s: every output is NULL", what);
+  if ((uintptr_t)rays & 15u) return fail(RT_ERR_INVALID, "%s: the ray list must be 16-byte aligned", what);
+  if (in && (((uintptr_t)in->length & 7u) || ((uintptr_t)in->intensity & 7u) || ((uintptr_t)in->skip & 3u)))
+    return fail(RT_ERR_INVALID, "%s: misaligned input (length and intensity need 8 bytes, skip 4)", what);
+  if (((uintptr_t)out->intensity & 7u) || ((uintptr_t)out->blocker & 3u))
+    return fail(RT_ERR_INVALID, "%s: misaligned output (intensity needs 8 bytes, blocker 4)", what);
+  return RT_OK;
+}
+
+int occlusion_launch(rt_scene_dev *s, uint32_t n, const double *d_rays, const uint32_t *d_order, const rt_occlusion_inputs &in,
+                     const rt_occlusion_outputs &out, hipStream_t stream, rt_stats *stats) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  const rt_scene_header &hd = s->hd;
+  rt_occlusion_launch L;
+  memset(&L, 0, sizeof L);
+  {
+    std::lock_guard<std::mutex> lk(s->launch_mu);
+    if (int rc = behind_the_camera(s, stream)) return rc;
+    note_launch(s, stream);
+    L.objects = (const rt_sphere *)(obj_block(s) + s->o_objs);   // this generation's spheres, in blob order
+    L.light_intensity = hd.light_intensity;                      // (rt_scene_set_light_intensity: this launch's)
+  }
+  L.epsilon = hd.epsilon;
+  L.n_objects = hd.n_objects;
+  L.rays = d_rays; L.n_rays = n; L.order = d_order;
+  L.length = in.length; L.intensity_in = in.intensity; L.skip = in.skip;
+  L.intensity = out.intensity; L.blocker = out.blocker;
+  event_timer timer;                                     // (a stats call)
+  if (stats) HIP_TRY(timer.start(stream));
+  const int err = rt_launch_occlusion(&L, stream);
+  if (err != 0) return fail(RT_ERR_DEVICE, "occlusion kernel launch: %s", hipGetErrorString((hipError_t)err));
+  if (stats) {
+    HIP_TRY(timer.stop(stream));
+    HIP_TRY(hipEventSynchronize(timer.b));
+    float ms = 0.f;
+    HIP_TRY(timer.elapsed(&ms));
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = ms;
+    stats->pixels = n;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
+}
+}  // namespace rt_api
+
+// (the arguments first: they are judged without a scene, and before a device is touched)
+extern "C" int rt_scene_occlusion_device(rt_scene_dev *s, uint64_t n, const double *d_rays, const uint32_t *d_order, const rt_occlusion_inputs *d_in,
+                                         const rt_occlusion_outputs *d_out, void *hip_stream, rt_stats *stats) {
+  int rc = occlusion_check(n, d_rays, d_in, d_out, "rt_scene_occlusion_device");
+  if (rc) return rc;
+  if ((uintptr_t)d_order & 3u) return fail(RT_ERR_INVALID, "rt_scene_occlusion_device: misaligned order (4 bytes)");
+  if (!s) return fail(RT_ERR_STATE, "rt_scene_occlusion_device: NULL scene handle");
+  if ((rc = ensure_device(s->device))) return rc;
+  const rt_occlusion_inputs none = {nullptr, nullptr, nullptr};
+  return occlusion_launch(s, (uint32_t)n, d_rays, d_order, d_in ? *d_in : none, *d_out, hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream, stats);
 }

@@ -137,10 +137,58 @@ function traceRays(sceneObj, rays, opts) {
   return r;
 }
 
+// The segments of the reference's light loop (main.js:286-292) from `points` (Float64Array, 3 per point: hit.p) to every light of the
+// scene, operation for operation: shadow_vec = between3D(hit.p, light), light_mag = mag3D, light_len = sqrt(light_mag), scale3D by
+// 1 / light_len where light_len != 0, shadow_dot = dot3D(shadow_vec, hit.l) with hit.l from `facing` (Float64Array, 3 per point, or
+// null).  `skip` (Int32Array, hit_i per point, or null) is handed through.  Returns one record per light: {rays: Float64Array 6 per
+// point {point, shadow_vec} as occlusion takes them, length (light_len), lightMag, shadowDot (null without facing), mask: Uint8Array
+// (shadow_dot > 0: the surface faces the light; all 1 without facing), skip}.
+function lightSegments(sceneObj, points, facing, skip) {
+  if (!(points instanceof Float64Array) || points.length % 3 !== 0) throw new TypeError('lightSegments: points must be a Float64Array of 3 numbers per point');
+  const n = points.length / 3;
+  if (facing != null && !(facing instanceof Float64Array && facing.length === 3 * n)) throw new TypeError('lightSegments: facing must be a Float64Array of 3 numbers per point, or null');
+  if (skip != null && !(skip instanceof Int32Array && skip.length === n)) throw new TypeError('lightSegments: skip must be an Int32Array of one index per point, or null');
+  return sceneObj.lights.map((light) => {
+    const rays = new Float64Array(6 * n), length = new Float64Array(n), lightMag = new Float64Array(n);
+    const shadowDot = facing != null ? new Float64Array(n) : null, mask = new Uint8Array(n).fill(1);
+    for (let i = 0; i < n; i++) {
+      let v = [light[0] - points[3 * i], light[1] - points[3 * i + 1], light[2] - points[3 * i + 2]];
+      const mag = v[0] * v[0] + v[1] * v[1] + v[2] * v[2], len = Math.sqrt(mag);
+      if (len !== 0) { const k = 1 / len; v = [v[0] * k, v[1] * k, v[2] * k]; }
+      for (let c = 0; c < 3; c++) { rays[6 * i + c] = points[3 * i + c]; rays[6 * i + 3 + c] = v[c]; }
+      length[i] = len; lightMag[i] = mag;
+      if (shadowDot) {
+        shadowDot[i] = v[0] * facing[3 * i] + v[1] * facing[3 * i + 1] + v[2] * facing[3 * i + 2];
+        mask[i] = shadowDot[i] > 0 ? 1 : 0;
+      }
+    }
+    return {rays, length, lightMag, shadowDot, mask, skip: skip != null ? skip : null};
+  });
+}
+
+// The reference's shadow scan (main.js:293-304) for a list of segments: `rays` is a Float64Array of 6 numbers per ray {org, dir},
+// directions used as given (lightSegments builds the reference's).  opts, one element per ray each: length (Float64Array, light_len;
+// default Infinity), intensity (Float64Array, what the scan starts with; default the scene's light_intensity), skip (Int32Array, hit_i:
+// the sphere left out; default none).  The scan walks scene.objects in order: a sphere met before `length` divides the intensity by its
+// albedo[4], or - albedo[4] == 0 - zeroes it, becomes the blocker and ends the scan.  Returns {intensity: Float64Array, blocker:
+// Int32Array (-1 = none; null unless opts.blocker)}.  A ray with a non-finite component is not traced: NaN, -1.  opts.bin: the GPU
+// orders each chunk of 2^18 rays first (rt_occlusion_binned) - the same results.
+function occlusion(sceneObj, rays, opts) {
+  if (!(rays instanceof Float64Array) || rays.length === 0 || rays.length % 6 !== 0) {
+    throw new TypeError('occlusion: rays must be a non-empty Float64Array of 6 numbers per ray');
+  }
+  const o = opts || {}, n = rays.length / 6;
+  for (const [name, kind] of [['length', Float64Array], ['intensity', Float64Array], ['skip', Int32Array]]) {
+    if (o[name] != null && !(o[name] instanceof kind && o[name].length === n)) throw new TypeError('occlusion: ' + name + ' must be a ' + kind.name + ' of one element per ray');
+  }
+  if (!inited) init(o.maxDevices);
+  return native().occlusion(new Uint8Array(flattenScene(sceneObj)), rays, o.length || null, o.intensity || null, o.skip || null, !!o.blocker, !!o.bin);
+}
+
 // `const build = '741'` (main.js:3) + this library's revision; every render's `.stats` also carries `.build` and `.report`, the
 // reference's end-of-frame string 'build #<id> (<elapsed>ms)' (main.js:204-205) for that render.
 function buildId() { return native().buildId(); }
 
 function shutdown() { if (addon) addon.shutdown(); inited = false; }
 
-module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, primaryRays, normal3D, init, shutdown, buildId, flattenScene, scenes, native}, scene);
+module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, primaryRays, normal3D, occlusion, lightSegments, init, shutdown, buildId, flattenScene, scenes, native}, scene);

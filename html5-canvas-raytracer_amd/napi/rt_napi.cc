@@ -476,6 +476,72 @@ napi_value TraceRays(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// occlusion(blob, rays: Float64Array (6 per ray), length: Float64Array | null, intensity: Float64Array | null, skip: Int32Array | null,
+//           wantBlocker, bin) -> {intensity: Float64Array, blocker: Int32Array | null, kernel_ms}  (rt_occlusion / rt_occlusion_binned)
+napi_value Occlusion(napi_env env, napi_callback_info info) {
+  size_t argc = 7;
+  napi_value argv[7];
+  bool is_ta = false, is_rays = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
+      napi_is_typedarray(env, argv[1], &is_rays) != napi_ok || !is_rays) {
+    napi_throw_type_error(env, nullptr, "occlusion(blob: Uint8Array, rays: Float64Array[, length, intensity, skip, wantBlocker, bin])");
+    return nullptr;
+  }
+  napi_typedarray_type bt, rt; napi_value ab; size_t off, blob_len = 0, ray_len = 0;
+  void *blob_data = nullptr, *ray_data = nullptr;
+  napi_get_typedarray_info(env, argv[0], &bt, &blob_len, &blob_data, &ab, &off);
+  napi_get_typedarray_info(env, argv[1], &rt, &ray_len, &ray_data, &ab, &off);
+  if ((bt != napi_uint8_array && bt != napi_uint8_clamped_array) || rt != napi_float64_array || ray_len == 0 || ray_len % 6u != 0) {
+    napi_throw_type_error(env, nullptr, "occlusion: the blob must be a Uint8Array and the rays a non-empty Float64Array of 6 numbers per ray");
+    return nullptr;
+  }
+  const size_t n = ray_len / 6u;
+  // the per-ray inputs: null / undefined = the library's default, else a typed array of n elements of the right kind
+  const napi_typedarray_type kinds[3] = {napi_float64_array, napi_float64_array, napi_int32_array};
+  void *in_data[3] = {nullptr, nullptr, nullptr};
+  for (size_t i = 0; i < 3 && 2 + i < argc; i++) {
+    napi_valuetype vt;
+    napi_typeof(env, argv[2 + i], &vt);
+    if (vt == napi_null || vt == napi_undefined) continue;
+    bool ta = false; napi_typedarray_type kt; size_t len = 0;
+    if (napi_is_typedarray(env, argv[2 + i], &ta) != napi_ok || !ta || napi_get_typedarray_info(env, argv[2 + i], &kt, &len, &in_data[i], &ab, &off) != napi_ok ||
+        kt != kinds[i] || len != n) {
+      napi_throw_type_error(env, nullptr, "occlusion: length and intensity are Float64Arrays and skip an Int32Array of one element per ray, or null");
+      return nullptr;
+    }
+  }
+  bool want_blocker = false, bin = false;
+  if (argc >= 6) napi_get_value_bool(env, argv[5], &want_blocker);
+  if (argc >= 7) napi_get_value_bool(env, argv[6], &bin);
+  // the library wants the blob 8-byte and the rays 16-byte aligned: one aligned copy holds both (typed arrays' own data is aligned to
+  // their element size, which is what the per-ray inputs and outputs need)
+  const size_t blob_room = (blob_len + 15) & ~(size_t)15;
+  uint8_t *mem = (uint8_t *)aligned_alloc(16, blob_room + ((n * 48u + 15) & ~(size_t)15));
+  napi_value ab_li = nullptr, ab_bl = nullptr, res, v;
+  void *p_li = nullptr, *p_bl = nullptr;
+  if (!mem || napi_create_arraybuffer(env, n * 8u, &p_li, &ab_li) != napi_ok || (want_blocker && napi_create_arraybuffer(env, n * 4u, &p_bl, &ab_bl) != napi_ok)) {
+    free(mem);
+    napi_throw_error(env, nullptr, "occlusion: out of memory");
+    return nullptr;
+  }
+  memcpy(mem, blob_data, blob_len);
+  memcpy(mem + blob_room, ray_data, n * 48u);
+  const rt_occlusion_inputs in = {(const double *)in_data[0], (const double *)in_data[1], (const int32_t *)in_data[2]};
+  const rt_occlusion_outputs out = {(double *)p_li, (int32_t *)p_bl};
+  rt_stats st;
+  const int rc = (bin ? rt_occlusion_binned : rt_occlusion)(mem, blob_len, n, (const double *)(mem + blob_room), &in, &out, &st);
+  free(mem);
+  if (rc != RT_OK) return throw_rt(env, bin ? "rt_occlusion_binned" : "rt_occlusion", rc);
+  napi_create_object(env, &res);
+  napi_create_typedarray(env, napi_float64_array, n, ab_li, 0, &v);
+  napi_set_named_property(env, res, "intensity", v);
+  if (want_blocker) napi_create_typedarray(env, napi_int32_array, n, ab_bl, 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "blocker", v);
+  napi_value ms;
+  napi_create_double(env, st.kernel_ms, &ms); napi_set_named_property(env, res, "kernel_ms", ms);
+  return res;
+}
+
 napi_value Module(napi_env env, napi_value exports) {
   const napi_property_descriptor props[] = {
       {"init", nullptr, Init, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
@@ -489,6 +555,7 @@ napi_value Module(napi_env env, napi_value exports) {
       {"renderHits", nullptr, RenderHits, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"pick", nullptr, Pick, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"traceRays", nullptr, TraceRays, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"occlusion", nullptr, Occlusion, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

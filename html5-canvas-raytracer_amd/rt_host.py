@@ -189,6 +189,17 @@ class RtRayOutputs(C.Structure):
     _fields_ = [("rgb", C.c_void_p), ("rgba", C.c_void_p), ("hits", C.c_void_p)]
 
 
+class RtOcclusionInputs(C.Structure):
+    """Per-ray inputs of an occlusion query (include/rt_hip.h rt_occlusion_inputs): float64 length, float64 intensity, int32 skip; NULL =
+    +Infinity / the scene's light intensity / no sphere left out."""
+    _fields_ = [("length", C.c_void_p), ("intensity", C.c_void_p), ("skip", C.c_void_p)]
+
+
+class RtOcclusionOutputs(C.Structure):
+    """Outputs of an occlusion query (include/rt_hip.h rt_occlusion_outputs): float64 intensity, int32 blocker per ray; NULL = not wanted."""
+    _fields_ = [("intensity", C.c_void_p), ("blocker", C.c_void_p)]
+
+
 # every symbol include/rt_hip.h declares: (restype, argtypes)
 ABI = {
     "rt_init": (C.c_int, [C.c_int]),
@@ -247,6 +258,11 @@ ABI = {
     "rt_scene_trace_rays_ordered_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RtRayOutputs), C.c_void_p,
                                                      C.POINTER(RtStats)]),
     "rt_trace_rays_binned": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(RtRayOutputs), C.POINTER(RtStats)]),
+    "rt_scene_occlusion_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtOcclusionInputs), C.POINTER(RtOcclusionOutputs),
+                                            C.c_void_p, C.POINTER(RtStats)]),
+    "rt_occlusion": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.POINTER(RtOcclusionInputs), C.POINTER(RtOcclusionOutputs), C.POINTER(RtStats)]),
+    "rt_occlusion_binned": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.POINTER(RtOcclusionInputs), C.POINTER(RtOcclusionOutputs),
+                                      C.POINTER(RtStats)]),
 }
 
 
@@ -427,6 +443,19 @@ class Renderer:
         _check(self.lib, rc, "rt_scene_trace_rays_ordered_device")
         return st
 
+    def occlusion(self, n, rays_ptr, length_ptr, intensity_ptr, skip_ptr, out_intensity_ptr, out_blocker_ptr, order_ptr=0, stream=None, want_stats=False):
+        """The reference's shadow scan (main.js:293-304) for n segments {org[3], dir[3]} (float64, 16-byte aligned) in DEVICE memory: per
+        ray the light intensity that is left (float64) and the opaque sphere that ended the scan (int32, -1 = none), into DEVICE buffers
+        (0 / None = not wanted).  Inputs per ray, DEVICE, 0 / None = the default: float64 length (+Infinity), float64 intensity (the
+        scene's), int32 skip (no sphere left out).  order_ptr: 0, or n uint32 (DEVICE) as trace_rays_ordered takes them."""
+        ins = RtOcclusionInputs(length_ptr or None, intensity_ptr or None, skip_ptr or None)
+        out = RtOcclusionOutputs(out_intensity_ptr or None, out_blocker_ptr or None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_occlusion_device(self.handle, n, C.c_void_p(rays_ptr or 0), C.c_void_p(order_ptr or 0), C.byref(ins), C.byref(out),
+                                                C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_occlusion_device")
+        return st
+
     def close(self):
         if self.handle:
             self.lib.rt_scene_free(self.handle)
@@ -604,3 +633,117 @@ def trace_rays(scene, rays, segs=0, want=("rgb",), lib=None, order="list"):
     if records is not None:
         out["hits"] = [_hit_dict(r) for r in records[:n]]
     return out
+
+
+def _points3(a, what, n=None):
+    import numpy as np
+    a = np.asarray(a)
+    if a.dtype.kind not in "fiu" or a.ndim != 2 or a.shape[1] != 3 or (n is not None and a.shape[0] != n):
+        raise ValueError("%s must be an (n, 3) array of numbers" % what)
+    return a.astype(np.float64)
+
+
+def _skip_array(skip, n):
+    import numpy as np
+    a = np.asarray(skip)
+    if a.dtype.kind not in "iu" or a.shape != (n,):
+        raise ValueError("skip must be n integers (sphere indices in blob order; -1 = none)")
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError("skip must fit 32 bits")
+    return np.ascontiguousarray(a, np.int32)
+
+
+def light_segments(scene, points, facing=None, skip=None):
+    """The segments of the reference's light loop (main.js:286-292) from `points` ((n, 3): hit.p) to every light of the scene dict, in
+    numpy with the reference's operation order: shadow_vec = light - point, light_mag = (x x + y y) + z z, light_len = sqrt(light_mag),
+    shadow_vec * (1 / light_len) where light_len != 0, shadow_dot = (s0 l0 + s1 l1) + s2 l2 with l = `facing` ((n, 3): hit.l, the normal
+    turned towards the ray's side).  Returns one dict per light: "rays" (n, 6) {point, shadow_vec} as occlusion takes them, "length"
+    (light_len), "light_mag", "shadow_dot" and "mask" (shadow_dot > 0: the surface faces the light) - without `facing` shadow_dot is
+    None and the mask all True - and "skip" (the int32 copy of `skip`, hit_i per point, or None)."""
+    import numpy as np
+    p = _points3(points, "points")
+    n = p.shape[0]
+    l = _points3(facing, "facing", n) if facing is not None else None
+    sk = _skip_array(skip, n) if skip is not None else None
+    out = []
+    for light in np.array(light_positions(scene["lights"]), np.float64).reshape(-1, 3):
+        v = light[None, :] - p
+        mag = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+        length = np.sqrt(mag)
+        with np.errstate(divide="ignore"):
+            k = np.where(length != 0.0, 1.0 / length, 1.0)
+        v = np.where((length != 0.0)[:, None], v * k[:, None], v)
+        rays = np.empty((n, 6), np.float64)
+        rays[:, 0:3] = p
+        rays[:, 3:6] = v
+        dot = (v[:, 0] * l[:, 0] + v[:, 1] * l[:, 1]) + v[:, 2] * l[:, 2] if l is not None else None
+        out.append({"rays": rays, "length": length, "light_mag": mag, "shadow_dot": dot,
+                    "mask": dot > 0.0 if dot is not None else np.ones(n, bool), "skip": sk})
+    return out
+
+
+def occlusion(scene, rays, length=None, intensity=None, skip=None, want=("intensity",), lib=None, order="list"):
+    """occlusion(scene, rays) -> {"intensity": (n,) float64, "blocker": (n,) int32} (the keys named in `want`): the reference's shadow
+    scan (main.js:293-304) per row {org, dir} of the float64 (n, 6) array `rays`, directions as given, on GPU 0 with rt_render's
+    resident scene.  Per ray: `length` (light_len; None = +Infinity), `intensity` (what the scan starts with; None = the scene's
+    light_intensity), `skip` (hit_i, the sphere left out, blob order; None or a value outside the scene = none).  The scan goes through the
+    spheres in blob order: a sphere met before `length` divides the intensity by its albedo[4], or - albedo[4] == 0 - makes it 0, becomes
+    the blocker and ends the scan.  A ray with a non-finite component is not traced: NaN, -1.  order: "list", or "binned"
+    (rt_occlusion_binned: the GPU orders each chunk of 2^18 rays first - the same results)."""
+    import numpy as np
+    if order not in ("list", "binned"):
+        raise ValueError("order is 'list' or 'binned'")
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    want = set(want)
+    if not want or want - {"intensity", "blocker"}:
+        raise ValueError("want names some of 'intensity', 'blocker'")
+    rays = np.asarray(rays)
+    if rays.dtype.kind not in "fiu" or rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError("rays must be an (n, 6) array: org[3], dir[3] per row")
+    n = rays.shape[0]
+    if n == 0:
+        raise ValueError("rays must not be empty")
+    aligned = np.empty(n * 6 + 2, np.float64)             # a contiguous copy on a 16-byte boundary
+    aligned = aligned[(aligned.ctypes.data >> 3) & 1:][:n * 6]
+    aligned[:] = rays.reshape(-1)
+    per_ray = {}
+    for name, a in (("length", length), ("intensity", intensity)):
+        if a is not None:
+            a = np.asarray(a)
+            if a.dtype.kind not in "fiu" or a.shape != (n,):
+                raise ValueError("%s must be n numbers" % name)
+            per_ray[name] = np.ascontiguousarray(a, np.float64)
+    if skip is not None:
+        per_ray["skip"] = _skip_array(skip, n)
+    out = {}
+    if "intensity" in want:
+        out["intensity"] = np.empty(n, np.float64)
+    if "blocker" in want:
+        out["blocker"] = np.empty(n, np.int32)
+    ins = RtOcclusionInputs(*[per_ray[k].ctypes.data if k in per_ray else None for k in ("length", "intensity", "skip")])
+    bufs = RtOcclusionOutputs(*[out[k].ctypes.data if k in out else None for k in ("intensity", "blocker")])
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    call, what = (lib.rt_occlusion, "rt_occlusion") if order == "list" else (lib.rt_occlusion_binned, "rt_occlusion_binned")
+    _check(lib, call(buf, len(blob), n, C.c_void_p(aligned.ctypes.data), C.byref(ins), C.byref(bufs), None), what)
+    return out
+
+
+def light_intensity_at(scene, points, facing, skip, lib=None, order="list"):
+    """The light intensity the reference's whole light loop (main.js:283-305) leaves at `points` ((n, 3) hit.p, with `facing` hit.l and
+    `skip` hit_i per point) of the scene dict: the lights in order, ONE intensity carried from light to light (quirk q2: glass a first
+    light's segment crossed has raised it for the second, and a blocked first light has zeroed it), a light the surface does not face
+    (shadow_dot <= 0) leaves it as it is.  One occlusion call per light over the points that face it.  -> (n,) float64."""
+    import numpy as np
+    segs = light_segments(scene, points, facing, skip)
+    n = np.asarray(points).shape[0]
+    li = np.full(n, float(scene.get("light_intensity", 50)), np.float64)
+    for sg in segs:
+        m = sg["mask"]
+        if not m.any():
+            continue
+        got = occlusion(scene, sg["rays"][m], length=sg["length"][m], intensity=li[m], skip=sg["skip"][m] if sg["skip"] is not None else None,
+                        want=("intensity",), lib=lib, order=order)
+        li[m] = got["intensity"]
+    return li

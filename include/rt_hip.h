@@ -13,7 +13,7 @@
  * of the calling thread's last call.
  *
  * Threads: rt_init, rt_shutdown and rt_render serialise on an internal lock.  The device entry points
- * (rt_scene_upload, rt_render_tiles_device, rt_render_batch_device, rt_scene_trace_rays_device, rt_scene_order_rays_device, rt_deinterleave_*) may be called from several
+ * (rt_scene_upload, rt_render_tiles_device, rt_render_batch_device, rt_scene_trace_rays_device, rt_scene_order_rays_device, rt_scene_occlusion_device, rt_deinterleave_*) may be called from several
  * threads at once; work on one HIP stream is ordered by the stream.  Launches with RT_FLAG_COUNT share one counter
  * buffer per device: one at a time per device.
  *
@@ -504,6 +504,62 @@ int rt_scene_trace_rays_ordered_device(rt_scene_dev *scene, uint64_t n, const do
  * like the rest.  stats->kernel_ms includes the orderings.  The same bytes as rt_trace_rays in every output. */
 int rt_trace_rays_binned(const void *scene_blob, size_t blob_bytes, uint64_t n, const double *rays, uint32_t segs,
                          const rt_ray_outputs *host_out, rt_stats *stats);
+
+/* Occlusion queries: how much of a light reaches a point.  The other loop of the reference, the shadow scan of main.js:293-304, for a
+ * LIST of segments - baked or per-vertex lighting, light probes, "is this point lit" for game logic, shadow and visibility views, a
+ * caller's own shading on top of rt_render_hits.  It is not a closest-hit query (the `hits` of a ray list cannot answer it): the scan
+ * stops at the first OPAQUE sphere in blob order, leaves one sphere out (the receiver, `j != hit_i`), compares against the light's
+ * distance instead of infinity, and divides the intensity by albedo[4] for every transparent sphere it crosses (quirk q2).
+ *
+ * `rays` is the ray list of rt_scene_trace_rays_device: n records {org[3], dir[3]}, 48 bytes each, 16-byte aligned, `dir` used AS GIVEN
+ * (the reference scans along unit(light - hit.p), main.js:287-290; the hosts' lightSegments / light_segments build exactly that).
+ * The same list goes through rt_scene_order_rays_device unchanged.  Ray i, in the strict arithmetic (no FMA contraction, correctly
+ * rounded sqrt and division):
+ *     li = intensity[i]; blocker = -1
+ *     for j in blob order, j != skip[i]:
+ *       t = intersectSphere(obj j, org, dir, null)          main.js:420-439, the epsilon rule included
+ *       if t < length[i]:
+ *         if albedo[4] != 0: li = li / albedo[4]            one division per crossed sphere, in blob order
+ *         else: li = 0; blocker = j; break
+ * A NaN t or a NaN length occludes nothing (the reference's comparison is false).  A ray with a non-finite component in its six slots
+ * is NOT traced: intensity NaN, blocker -1; length and intensity may hold any value.  The reference carries ONE intensity from light
+ * to light (q2): feed the intensity a point's first light left into the segment to its second (the hosts' light_intensity_at).
+ * It reads the scene's CURRENT spheres (rt_scene_set_objects), epsilon and light intensity (rt_scene_set_light_intensity); the camera,
+ * launch tables, RT_FLAG_*, textures and the lights' positions play no part - the caller's segments say where the lights are. */
+typedef struct rt_occlusion_inputs {   /* each one per ray, or NULL */
+  const double  *length;     /* light_len of main.js:288; NULL = +Infinity for every ray */
+  const double  *intensity;  /* the light_intensity the scan starts with; NULL = the scene's current one */
+  const int32_t *skip;       /* hit_i of main.js:294: the sphere (blob order) left out; NULL or a value outside [0, n_objects) = none */
+} rt_occlusion_inputs;
+typedef struct rt_occlusion_outputs {  /* any may be NULL; both NULL is RT_ERR_INVALID */
+  double  *intensity;        /* light_intensity after the scan */
+  int32_t *blocker;          /* the opaque sphere that ended it (blob order), or -1 */
+} rt_occlusion_outputs;
+
+/* Device form: `d_rays`, `d_order` and the arrays `d_in` and `d_out` name are DEVICE memory (d_in and d_out themselves are host structs;
+ * a NULL d_in means all three inputs are NULL).  d_order is NULL or an order as rt_scene_trace_rays_ordered_device takes it: work-item j
+ * takes ray i = d_order[j], an entry >= n is skipped, and ray i reads and writes index i - the buffers hold the bytes of the call
+ * without an order.  Outputs are written for every ray an entry names (every i < n without an order) and nowhere else; an output that
+ * is NULL is not touched.  Asynchronous on `hip_stream` (NULL = the library's stream for the scene's device) unless `stats` is non-NULL
+ * (then it waits and fills kernel_ms, total_ms and pixels = n).  Waits by event for a pending rt_scene_set_objects / rt_scene_set_lights
+ * like every other launch.  One work-item per ray; a lane whose ray has met its opaque sphere goes idle and a wave leaves the scan as
+ * soon as none of its 64 rays is live, so neighbours in the list should be neighbours in space here too.
+ * RT_ERR_INVALID, before a device is touched: n outside 1..2^31 - 1, NULL or misaligned d_rays (16 bytes), a NULL d_out or both of its
+ * outputs NULL, a misaligned length or intensity array (8 bytes), skip, blocker or d_order (4 bytes); then RT_ERR_STATE: a NULL scene.
+ * Thread rules as rt_render_tiles_device. */
+int rt_scene_occlusion_device(rt_scene_dev *scene, uint64_t n, const double *d_rays, const uint32_t *d_order,
+                              const rt_occlusion_inputs *d_in, const rt_occlusion_outputs *d_out, void *hip_stream, rt_stats *stats);
+
+/* Host form: rt_render's resident scene (a blob that differs from the resident one only in the camera, stars_seed, sphere records,
+ * light positions and / or light_intensity is not uploaded again), every array in HOST memory, the list's own order, synchronous, on
+ * GPU 0.  The list is processed in chunks of 2^18 rays, so the device memory the call allocates does not grow with n. */
+int rt_occlusion(const void *scene_blob, size_t blob_bytes, uint64_t n, const double *rays,
+                 const rt_occlusion_inputs *host_in, const rt_occlusion_outputs *host_out, rt_stats *stats);
+
+/* The same with each chunk of 2^18 rays ordered on the GPU (rt_scene_order_rays_device's ordering) before it is scanned, as
+ * rt_trace_rays_binned does; stats->kernel_ms includes the orderings.  The same bytes as rt_occlusion in both outputs. */
+int rt_occlusion_binned(const void *scene_blob, size_t blob_bytes, uint64_t n, const double *rays,
+                        const rt_occlusion_inputs *host_in, const rt_occlusion_outputs *host_out, rt_stats *stats);
 
 #ifdef __cplusplus
 }

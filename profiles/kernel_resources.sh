@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / scratch use of every rt_trace instantiation, read from the code object's metadata notes - and of the list-driven kernels
-# (rt_retrace, rt_trace_rays: the strict object) and the hit kernels (rt_hits.o) where the object holds them.
+# (rt_retrace, rt_trace_rays: the strict object) the hit kernels (rt_hits.o) and the occlusion kernel (rt_occlusion.o) where the object holds them.
 #   bash profiles/kernel_resources.sh [object file]     (default: the product build, rt_kernel_fast.o)
 set -e
 B=/opt/rocm/lib/llvm/bin
@@ -16,7 +16,7 @@ for block in re.split(r"\n\s+- \.agpr_count:", sys.stdin.read())[1:]:
     m = re.search(r"rt_traceILb([01])ELb([01])ELb([01])ELb([01])ELb([01])E", f.get("name", ""))
     if m:
         print("  <%s>                     %4s  %10s  %4s  %10s  %13s" % (",".join(m.groups()), f["vgpr_count"], f["vgpr_spill_count"], f["sgpr_count"], f["sgpr_spill_count"], f["private_segment_fixed_size"]))
-    m = re.search(r"(rt_retrace|rt_trace_rays)((?:ILb[01]E(?:Lb[01]E)*E)?)|(rt_hits_kernel|rt_pick_kernel|rt_ray_hit_kernel)", f.get("name", ""))
+    m = re.search(r"(rt_retrace|rt_trace_rays)((?:ILb[01]E(?:Lb[01]E)*E)?)|(rt_hits_kernel|rt_pick_kernel|rt_ray_hit_kernel|rt_occlusion_kernel)", f.get("name", ""))
     if m:
         label = (m.group(1) + "<" + ",".join(re.findall(r"Lb([01])E", m.group(2))) + ">") if m.group(1) else m.group(3)
         print("  %-30s %4s  %10s  %4s  %10s  %13s" % (label, f["vgpr_count"], f["vgpr_spill_count"], f["sgpr_count"], f["sgpr_spill_count"], f["private_segment_fixed_size"]))
