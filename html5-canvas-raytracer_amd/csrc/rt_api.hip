@@ -1,12 +1,11 @@
 // rt_api.hip — the C ABI of include/rt_hip.h (its other units: rt_api_internal.h): library and device lifetime, errors, the scratch
-// guard, scene validation and the host-logic probes (bounce candidates, cull rectangles, the host-built launch table), pinned
-// framebuffers and device memory, IPC.
+// guard and the per-variant scratch figures, scene validation and the host-logic probes (bounce candidates, cull rectangles, the
+// host-built launch table; test build: the variant of a launch), pinned framebuffers and device memory, IPC.
 //
 // Host-side counterpart of the reference's driver code: main() sets up what a frame needs
 // (main.js:77-105), redraw()/spanish() walks the rows (:180-201).  Here a frame is one kernel
 // launch per GPU.  There is no CPU rendering path in this library: without a GPU every render
 // entry point fails with RT_ERR_DEVICE.
-
 
 #include "rt_api_internal.h"
 
@@ -38,6 +37,12 @@ int ensure_device(int d) {
     HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     s.stream = st;                         // published last: a non-NULL stream means the device state is complete
   }
+  return RT_OK;
+}
+
+int device_stream(int device, void *hip_stream, hipStream_t *stream) {
+  if (int rc = ensure_device(device)) return rc;
+  *stream = hip_stream ? (hipStream_t)hip_stream : G.dev[device].stream;
   return RT_OK;
 }
 
@@ -79,28 +84,38 @@ int scratch_guard(device_state &D, hipStream_t stream, size_t per_lane, uint64_t
   return RT_OK;
 }
 
-// per-lane scratch of a kernel instantiation, from its code object (asked once per instantiation)
-int kernel_scratch(bool strict, bool retrace, int refract, int count, int ss2, int grid_variant, size_t *out, bool one_wave) {
+// Scratch (private segment) bytes per lane of the variant's kernel, from the code object: what the runtime reserves for every wave
+// slot of the device before the first launch.  Returns a hipError_t as int.
+static int variant_scratch(rt_trace_variant v, size_t *bytes_per_lane) {
+  const void *f = (v.strict ? rt_kernel_trace_strict : rt_kernel_trace_fast)(v);
+  if (!f) return (int)hipErrorInvalidDeviceFunction;
+  hipFuncAttributes fa;
+  const hipError_t e = hipFuncGetAttributes(&fa, f);
+  if (e == hipSuccess) *bytes_per_lane = (size_t)fa.localSizeBytes;
+  return (int)e;
+}
+
+// ... asked once per variant
+int kernel_scratch(rt_trace_variant v, size_t *out) {
   static std::mutex mu;
-  static size_t cache[3][2][2][2][4];
-  static bool have[3][2][2][2][4];
-  const int k = retrace ? 2 : (strict ? 1 : 0), c = retrace ? 0 : (count ? 1 : 0), g = (retrace || strict) ? 0 : ((grid_variant ? 1 : 0) + (one_wave ? 2 : 0));
+  static size_t cache[256];
+  static bool have[256];
+  const uint32_t k = rt_variant_bits(v);
   std::lock_guard<std::mutex> lk(mu);
-  if (!have[k][refract ? 1 : 0][c][ss2 ? 1 : 0][g]) {
+  if (!have[k]) {
     size_t b = 0;
-    const int e = retrace ? rt_scratch_retrace(refract, ss2, &b) : (strict ? rt_scratch_trace_strict(refract, count, ss2, 0, 0, &b) : rt_scratch_trace_fast(refract, count, ss2, grid_variant, one_wave ? 1 : 0, &b));
+    const int e = variant_scratch(v, &b);
     if (e != 0) return fail(RT_ERR_DEVICE, "hipFuncGetAttributes: %s", hipGetErrorString((hipError_t)e));
-    cache[k][refract ? 1 : 0][c][ss2 ? 1 : 0][g] = b; have[k][refract ? 1 : 0][c][ss2 ? 1 : 0][g] = true;
+    cache[k] = b; have[k] = true;
   }
-  *out = cache[k][refract ? 1 : 0][c][ss2 ? 1 : 0][g];
+  *out = cache[k];
   return RT_OK;
 }
 
-// the per-lane scratch of a kernel instantiation (kernel_scratch), held against the free device memory (scratch_guard) before its launch
-int guard_kernel_scratch(device_state &D, hipStream_t stream, bool strict, bool retrace, int refract, int count, int ss2, int grid_variant, bool one_wave,
-                         uint64_t waves_in_grid, const char *what) {
+// the per-lane scratch of a variant's kernel (kernel_scratch), held against the free device memory (scratch_guard) before its launch
+int guard_kernel_scratch(device_state &D, hipStream_t stream, rt_trace_variant v, uint64_t waves_in_grid, const char *what) {
   size_t per_lane = 0;
-  if (int rc = kernel_scratch(strict, retrace, refract, count, ss2, grid_variant, &per_lane, one_wave)) return rc;
+  if (int rc = kernel_scratch(v, &per_lane)) return rc;
   return scratch_guard(D, stream, per_lane, waves_in_grid, what);
 }
 
@@ -136,6 +151,13 @@ launch_geom launch_geometry(double fov_deg, uint32_t w, uint32_t h, uint32_t ss,
 }
 
 }  // namespace rt_api
+
+// The product kernels' scratch figure as the tests ask for it: the variant's template arguments (many spheres: GRID; one-wave
+// workgroups: W1), uncached.  Returns a hipError_t as int.
+extern "C" int rt_scratch_trace_fast(int refract, int count, int ss2, int grid_variant, int one_wave, size_t *bytes_per_lane) {
+  const rt_trace_variant v = {false, false, false, refract != 0, count != 0, ss2 != 0, grid_variant != 0, one_wave != 0};
+  return rt_api::variant_scratch(v, bytes_per_lane);
+}
 
 // ------------------------------------------------------------------------------------ lifetime
 extern "C" uint32_t rt_abi_version(void) { return RT_ABI_VERSION; }
@@ -221,6 +243,21 @@ extern "C" int rt_scene_validate(const void *blob, size_t bytes) {
     if (int rc = check_sphere(ob[i], i, hd->n_textures)) return rc;
   return RT_OK;
 }
+
+#ifdef RT_TESTING
+// Host-logic probe (test build, no GPU): the variant of a launch with the facts in `facts` - bit 0 strict, 1 retrace, 2 refract, 3 count,
+// 4 supersample 2, 5 cull_in_lds, 6 scatter, 7 four_waves; bit 8: a ray-list launch instead (refract alone counts) - as rt_variant_bits
+// packs it, and whether the build it belongs to has a kernel for it.
+extern "C" int rt_test_trace_variant(uint32_t facts, uint32_t *out_bits, int *out_has_kernel) {
+  if (!out_bits || !out_has_kernel) return fail(RT_ERR_INVALID, "rt_test_trace_variant: NULL argument");
+  const rt_trace_variant v = (facts & 256u) ? rt_trace_variant_of_rays((facts & 4u) != 0)
+                                            : rt_trace_variant_of((facts & 1u) != 0, (facts & 2u) != 0, (facts & 4u) != 0, (facts & 8u) != 0, (facts & 16u) != 0,
+                                                                  (facts & 32u) != 0, (facts & 64u) != 0, (facts & 128u) != 0);
+  *out_bits = rt_variant_bits(v);
+  *out_has_kernel = (v.strict ? rt_kernel_trace_strict : rt_kernel_trace_fast)(v) != nullptr;
+  return RT_OK;
+}
+#endif
 
 // Host-logic probe for tests: the bounce table's answer for one ray, with the kernel's own direction -> cell mapping
 // (an exact division where the kernel uses a 2^-24 reciprocal: the cells overlap by 1e-6 rad for that).

@@ -1,9 +1,13 @@
 // rt_api_internal.h — what the host units of the C ABI share: errors and test switches, the library and device state, the resident
 // scene (rt_scene_dev) and the few functions that cross units.  Not part of the ABI.
-//   rt_api.hip     lifetime, errors, device state, the scratch guard, the host-logic probes, memory helpers, IPC
+//   rt_api.hip     lifetime, errors, device state, the scratch guard and the per-variant scratch figures, the host-logic probes, memory helpers, IPC
 //   rt_scene.hip   upload and moves of a resident scene (the generation pipeline), its launch decisions and launch tables
-//   rt_launch.hip  the launches: colour (product / strict / retrace), supersampling, compact bands, primary hits and picking, ray lists, occlusion queries
-//   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick, rt_trace_rays, rt_occlusion
+//   rt_launch.hip  the launches: colour (the launch record, then the strict launch or the product launch and rt_retrace), supersampling,
+//                  compact bands, primary hits and picking, ray lists, occlusion queries
+//   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick, and the host lists that go
+//                  through device buffers in chunks (rt_trace_rays, rt_occlusion and their binned forms)
+// Which kernel a launch runs is one value (rt_device.h: rt_trace_variant), worked out once per launch; the two builds of rt_kernel.hip map
+// it to a kernel (rt_kernel_trace_fast / rt_kernel_trace_strict), and the declarations below are all the host sees of them.
 #ifndef RT_API_INTERNAL_H
 #define RT_API_INTERNAL_H
 
@@ -30,14 +34,11 @@
 #include "rt_rays_order.h"
 #include "rt_occlusion.h"
 
-extern "C" int rt_launch_trace_fast(const rt_launch *, int, int, int, unsigned, hipStream_t);
-extern "C" int rt_launch_trace_strict(const rt_launch *, int, int, int, unsigned, hipStream_t);
-extern "C" int rt_launch_retrace(const rt_launch *, int, int, unsigned, hipStream_t);
-extern "C" int rt_scratch_trace_fast(int, int, int, int, int, size_t *);
-extern "C" int rt_scratch_trace_strict(int, int, int, int, int, size_t *);
-extern "C" int rt_scratch_retrace(int, int, size_t *);
-extern "C" int rt_launch_trace_rays(const rt_launch *, const uint32_t *, int, unsigned, hipStream_t);
-extern "C" int rt_scratch_trace_rays(int, size_t *);
+// per build of rt_kernel.hip (product, strict): the variant's kernel (NULL: not this build's) and its launch
+extern "C" const void *rt_kernel_trace_fast(rt_trace_variant);
+extern "C" const void *rt_kernel_trace_strict(rt_trace_variant);
+extern "C" int rt_launch_trace_fast(const rt_launch *, rt_trace_variant, unsigned n_wg, const uint32_t *order, unsigned lds_bytes, hipStream_t);
+extern "C" int rt_launch_trace_strict(const rt_launch *, rt_trace_variant, unsigned n_wg, const uint32_t *order, unsigned lds_bytes, hipStream_t);
 
 using namespace rt_tables;   // the host-built tables (pure host logic, rt_tables.cpp)
 
@@ -100,10 +101,15 @@ struct lib_state {
 extern lib_state G;
 
 int ensure_device(int d);
+// an entry point's prologue: the device is ready and current, and the launch's stream is the caller's or the device's own
+int device_stream(int device, void *hip_stream, hipStream_t *stream);
 int scratch_guard(device_state &D, hipStream_t stream, size_t per_lane, uint64_t waves_in_grid, const char *what);
-int kernel_scratch(bool strict, bool retrace, int refract, int count, int ss2, int grid_variant, size_t *out, bool one_wave = false);
-int guard_kernel_scratch(device_state &D, hipStream_t stream, bool strict, bool retrace, int refract, int count, int ss2, int grid_variant, bool one_wave,
-                         uint64_t waves_in_grid, const char *what);
+int kernel_scratch(rt_trace_variant v, size_t *out);
+int guard_kernel_scratch(device_state &D, hipStream_t stream, rt_trace_variant v, uint64_t waves_in_grid, const char *what);
+// the variant's launch, by the build that has its kernel (n_wg, order: the list-driven kernels'; lds_bytes: rt_trace's)
+inline int launch_variant(const rt_launch &L, rt_trace_variant v, unsigned n_wg, const uint32_t *order, unsigned lds_bytes, hipStream_t stream) {
+  return (v.strict ? rt_launch_trace_strict : rt_launch_trace_fast)(&L, v, n_wg, order, lds_bytes, stream);
+}
 int check_frame(const char *what, uint32_t w, uint32_t h, const rt_tiles *tiles, uint32_t flags);
 uint64_t tile_set_pixels(uint32_t w, uint32_t h, const rt_tiles *tiles);
 
@@ -127,6 +133,33 @@ struct event_timer {
   }
   hipError_t stop(hipStream_t stream) { return hipEventRecord(b, stream); }
   hipError_t elapsed(float *ms) const { return hipEventElapsedTime(ms, a, b); }
+};
+
+// The clock of a call that may report rt_stats: host time from its construction, GPU time on `stream` between start() and finish().
+// Without `stats` (most calls) it creates no event and waits for nothing.
+struct stats_clock {
+  const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+  event_timer timer;
+  hipStream_t stream = nullptr;
+  double host_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); }
+  int start(const rt_stats *stats, hipStream_t on) {
+    stream = on;
+    if (stats) HIP_TRY(timer.start(stream));
+    return RT_OK;
+  }
+  // waits for the stream; *stats = {kernel_ms, pixels, total_ms}, every other field zero
+  int finish(rt_stats *stats, uint64_t pixels) {
+    if (!stats) return RT_OK;
+    HIP_TRY(timer.stop(stream));
+    HIP_TRY(hipEventSynchronize(timer.b));
+    float ms = 0.f;
+    HIP_TRY(timer.elapsed(&ms));
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = ms;
+    stats->pixels = pixels;
+    stats->total_ms = host_ms();
+    return RT_OK;
+  }
 };
 
 }  // namespace rt_api
@@ -260,6 +293,7 @@ constexpr size_t RT_KNOWN_WORDS = 256;
 inline uint8_t *cam_block(const rt_scene_dev *s) { return s->d_cam_buf[s->cam_gen & 1u]; }
 inline uint8_t *obj_block(const rt_scene_dev *s) { return s->d_obj_buf[s->cam_gen & 1u]; }
 inline uint8_t *lds_image_of(const rt_scene_dev *s) { return s->cull_in_lds ? cam_block(s) + s->cam_lds_offset : obj_block(s) + s->o_img; }
+inline int scene_stream(const rt_scene_dev *s, void *hip_stream, hipStream_t *stream) { return device_stream(s->device, hip_stream, stream); }
 
 // rt_api.hip
 int check_sphere(const rt_sphere &o, uint32_t i, uint32_t n_textures);
@@ -281,7 +315,7 @@ int dispatch_order(rt_scene_dev *s, const frame_kind &kind, const table_choice &
 // rt_launch.hip: argument checks of the hit entry points
 int hits_frame_check(uint32_t w, uint32_t h, uint32_t k, const char *what);
 int pick_points_check(uint32_t w, uint32_t h, uint32_t k, uint32_t n, const uint32_t *xy, const void *out, const char *what);
-// ... and of the ray entry points; the launch of rays [base, base + n) of a caller's list (device pointers to THOSE rays and their outputs),
+// ... those of the ray entry points; the launch of rays [base, base + n) of a caller's list (device pointers to THOSE rays and their outputs),
 // in the list's order (d_order NULL) or in the order of n entries; the ordering of n rays (rt_rays_order.hip) with its argument check
 int rays_check(uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *out, const char *what);
 int rays_order_check(uint64_t n, const double *rays, const uint32_t *order, const void *work, size_t work_bytes, const char *what);

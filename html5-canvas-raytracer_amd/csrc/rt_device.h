@@ -18,9 +18,42 @@
  * unless the launch stores through the peer-store path without supersampling, which puts whole 128-byte lines together across a
  * workgroup's four waves (callers pass `scatter` = "that path": a 2x2 launch stores per wave there too).
  * (The general kernel's 13-double fold state and LDS image would leave a CU 16 one-wave workgroups: it keeps four waves.)
- * Host (LDS size, scratch figure) and launcher ask the same question. */
+ * Asked in one place: rt_trace_variant_of, below. */
 static inline bool rt_one_wave_workgroups(bool strict, bool count, bool refract, bool scatter) {
   return !strict && !count && !refract && !scatter;
+}
+/* WHICH kernel instantiation a launch runs, decided once per launch on the host: the LDS size, the scratch figure held against free
+ * memory and the launch itself all take this value, and each build of rt_kernel.hip maps it to a kernel's address in ONE table
+ * (rt_kernel.hip: rt_kernel_trace_fast / rt_kernel_trace_strict).
+ *   strict    the strict build's kernels (RT_FLAG_STRICT_FP, a strict scene, rt_retrace, rt_trace_rays); else the product build's rt_trace
+ *   retrace   rt_retrace<refract, ss2>, the list-driven strict launch behind a product launch
+ *   rays      rt_trace_rays<refract>, a caller's ray list
+ *   else      rt_trace<refract, count, ss2, grid, one_wave>: count = RT_FLAG_COUNT; grid = the many-sphere (shadow grid) variant of the
+ *             product build; one_wave = one-wave workgroups (above) */
+struct rt_trace_variant { bool strict, retrace, rays, refract, count, ss2, grid, one_wave; };
+/* ... from the facts of a frame launch.  cull_in_lds: the scene is a few-sphere one (rt_launch::cull_in_lds); scatter: the launch stores
+ * through the peer-store path; four_waves: rt_launch::four_waves. */
+static inline rt_trace_variant rt_trace_variant_of(bool strict, bool retrace, bool refract, bool count, bool ss2, bool cull_in_lds, bool scatter, bool four_waves) {
+  rt_trace_variant v;
+  v.strict = strict || retrace;                     /* (rt_retrace lives in the strict build) */
+  v.retrace = retrace;
+  v.rays = false;
+  v.refract = refract;
+  v.count = count && !retrace;
+  v.ss2 = ss2;
+  v.grid = !v.strict && !v.count && !cull_in_lds;
+  v.one_wave = rt_one_wave_workgroups(v.strict, v.count, refract, (scatter && !ss2) || four_waves);
+  return v;
+}
+/* ... and of a ray-list launch: camera, sample grid and flags play no part */
+static inline rt_trace_variant rt_trace_variant_of_rays(bool refract) {
+  const rt_trace_variant v = {true, false, true, refract, false, false, false, false};
+  return v;
+}
+/* a variant as a number below 256: the key of the host's scratch cache and of the kernels' tables */
+static inline uint32_t rt_variant_bits(rt_trace_variant v) {
+  return (v.strict ? 1u : 0u) | (v.retrace ? 2u : 0u) | (v.rays ? 4u : 0u) | (v.refract ? 8u : 0u) | (v.count ? 16u : 0u) | (v.ss2 ? 32u : 0u) |
+         (v.grid ? 64u : 0u) | (v.one_wave ? 128u : 0u);
 }
 #define RT_TILE_H 8
 

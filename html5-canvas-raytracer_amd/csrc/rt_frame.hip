@@ -1,4 +1,5 @@
-// rt_frame.hip — rt_render(width, height, scene) and its kin (rt_render_progressive, rt_render_hits, rt_pick, rt_trace_rays, rt_trace_rays_binned, rt_occlusion, rt_occlusion_binned): the resident scene
+// rt_frame.hip — rt_render(width, height, scene) and its kin (rt_render_progressive, rt_render_hits, rt_pick; rt_trace_rays, rt_occlusion
+// and their binned forms, which share one chunked list call): the resident scene
 // per device (scene_for), the one-GPU plans (banded copy-out, stores straight into a pinned frame) and the single-process multi-GPU
 // frame (interleaved row tiles stored straight into GPU 0's frame over xGMI; fallback: RGB24 bands + one RCCL gather + de-interleave).
 
@@ -22,9 +23,9 @@ __global__ void __launch_bounds__(256) rt_deinterleave_kernel(const T *__restric
 extern "C" int rt_deinterleave_device(int device, const void *d_src, void *d_dst, uint32_t w, uint32_t h, uint32_t tile_rows, uint32_t n_ranks,
                                       uint64_t rank_stride_bytes, void *hip_stream) {
   if (!d_src || !d_dst || !w || !h || !tile_rows || !n_ranks || (rank_stride_bytes & 3u) || h > 65535u * 16u) return fail(RT_ERR_INVALID, "bad de-interleave arguments");
-  int rc = ensure_device(device);
+  hipStream_t stream = nullptr;
+  int rc = device_stream(device, hip_stream, &stream);
   if (rc) return rc;
-  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : G.dev[device].stream;
   if (h > 65535u) return fail(RT_ERR_INVALID, "de-interleave: more than 65535 rows");
   const bool wide = (w % 4u == 0) && (rank_stride_bytes % 16u == 0) && (((uintptr_t)d_src | (uintptr_t)d_dst) % 16u == 0);
   const uint32_t row_elems = wide ? w / 4u : w;
@@ -64,9 +65,9 @@ extern "C" int rt_deinterleave_rgb24_device(int device, const void *d_src, void 
   if (!d_src || !d_dst || !w || !h || !tile_rows || !n_ranks || (rank_stride_bytes & 3u) || (w & 3u) || (((uintptr_t)d_src) & 3u) || (((uintptr_t)d_dst) & 15u))
     return fail(RT_ERR_INVALID, "bad RGB24 de-interleave arguments (w must be a multiple of 4, dst 16-byte aligned)");
   if (h > 65535u) return fail(RT_ERR_INVALID, "de-interleave: more than 65535 rows");
-  int rc = ensure_device(device);
+  hipStream_t stream = nullptr;
+  int rc = device_stream(device, hip_stream, &stream);
   if (rc) return rc;
-  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : G.dev[device].stream;
   const uint32_t row_quads = w / 4u;
   const dim3 grid((row_quads + 255u) / 256u, h), block(256);
   hipLaunchKernelGGL(rt_deinterleave_rgb24_kernel, grid, block, 0, stream, (const uint32_t *)d_src, (uint4 *)d_dst, row_quads, tile_rows, n_ranks,
@@ -192,6 +193,11 @@ void rt_api::release_rccl() {
 
 // ------------------------------------------------------------------------------------ render(width,height,scene)
 namespace {
+// device buffers of one call, released on every way out
+template <int N> struct device_bufs {
+  void *p[N] = {};
+  ~device_bufs() { for (void *q : p) if (q) (void)hipFree(q); }
+};
 int render_to_host(const void *blob, size_t bytes, uint32_t w, uint32_t h, uint8_t *out_rgba, uint32_t flags, rt_stats *stats,
                    uint32_t want_bands, rt_band_callback on_band, void *user);
 int g_last_plan = 0;      // how the last rt_render put its frame together: 0 one GPU (banded copy-out), 1 peer stores, 2 ncclGather (or its emulation), 3 one GPU storing into the pinned frame
@@ -237,7 +243,7 @@ extern "C" int rt_render_hits(const void *blob, size_t bytes, uint32_t w, uint32
   if ((rc = ensure_device(0))) return rc;
   device_state &D = G.dev[0];
   const size_t samples = (size_t)k * w * k * h;
-  struct device_bufs { void *p[3] = {nullptr, nullptr, nullptr}; ~device_bufs() { for (void *q : p) if (q) (void)hipFree(q); } } mem;
+  device_bufs<3> mem;
   const size_t each[3] = {sizeof(int32_t), sizeof(double), 3u * sizeof(float)};
   void *const host[3] = {hb->id, hb->depth, hb->normal};
   for (int i = 0; i < 3; i++) if (host[i]) HIP_TRY(hipMalloc(&mem.p[i], samples * each[i]));
@@ -265,57 +271,54 @@ extern "C" int rt_pick(const void *blob, size_t bytes, uint32_t w, uint32_t h, u
   return rt_scene_pick(s, w, h, n, xy, out);
 }
 
-// intersectWorld for a list of rays in host memory, with rt_render's resident scene: chunks of RT_RAY_CHUNK rays go through one set of
-// device buffers (ray i of the list keeps pix = i: the chunk's base travels in the launch record), so the device memory of a call does
-// not grow with n.  Synchronous; kernel_ms is the sum over the chunks.  `binned` (rt_trace_rays_binned): every chunk is ordered on the
-// GPU (rt_rays_order.hip) and traced in that order; the order buffer and the workspace are the call's, like its other device memory,
-// and kernel_ms includes the orderings.
+// A list in host memory - rays (rt_trace_rays) or segments (rt_occlusion) - goes through rt_render's resident scene in chunks of
+// RT_RAY_CHUNK elements and one set of device buffers, so the device memory of a call does not grow with n (element i of the list keeps
+// pix = i: the chunk's base travels to the launch).  `rows`: the list's arrays, the ray records first; a row without a host pointer
+// gets no buffer.  Per chunk: the inputs are copied in, `binned`: the chunk is ordered on the GPU (rt_rays_order.hip; the order buffer
+// and the workspace are the call's, like its other device memory), `launch` runs it, the outputs are copied back, and the stream is
+// drained.  Synchronous; kernel_ms is the sum over the chunks, the orderings included.
 #define RT_RAY_CHUNK (1u << 18)
 namespace {
-int trace_rays_to_host(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *ho, rt_stats *stats,
-                       bool binned, const char *what) {
-  int rc = rt_scene_validate(blob, bytes);
-  if (rc) return rc;
-  if ((rc = rays_check(n, rays, segs, ho, what))) return rc;
+struct list_row { const void *host; size_t each; bool out; };       // one array of the list: element size, and which way it is copied
+constexpr int RT_LIST_ROWS = 6;
+// launch(scene, m, base, d, d_order, stream, st): elements [base, base + m), whose arrays are the device buffers d[row] (NULL: none),
+// in the list's order (d_order NULL) or in that of m entries
+template <typename Launch>
+int chunked_list_call(const void *blob, size_t bytes, uint64_t n, const list_row *rows, int n_rows, bool binned, rt_stats *stats, Launch launch) {
+  if (n_rows > RT_LIST_ROWS) return fail(RT_ERR_INVALID, "a list call has at most %d arrays", RT_LIST_ROWS);
   if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
   std::lock_guard<std::mutex> lk(G.mu);
   const auto t_begin = std::chrono::steady_clock::now();
   rt_scene_dev *s = nullptr;
-  if ((rc = scene_for(0, blob, bytes, &s))) return rc;
+  int rc = scene_for(0, blob, bytes, &s);
+  if (rc) return rc;
   if ((rc = ensure_device(0))) return rc;
   device_state &D = G.dev[0];
   const size_t chunk = n < RT_RAY_CHUNK ? (size_t)n : RT_RAY_CHUNK;
-  struct device_bufs { void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; ~device_bufs() { for (void *q : p) if (q) (void)hipFree(q); } } mem;
-  const size_t each[4] = {6u * sizeof(double), 3u * sizeof(double), 4u, sizeof(rt_hit)};
-  uint8_t *const host[4] = {(uint8_t *)rays, (uint8_t *)ho->rgb, ho->rgba, (uint8_t *)ho->hits};
-  for (int i = 0; i < 4; i++) if (host[i]) HIP_TRY(hipMalloc(&mem.p[i], chunk * each[i]));
-  if (binned) {                                          // the chunk's order and the ordering's workspace
-    HIP_TRY(hipMalloc(&mem.p[4], chunk * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&mem.p[5], rt_rays_order_work_bytes(chunk)));
+  device_bufs<RT_LIST_ROWS + 2> mem;                     // the rows, then the chunk's order and the ordering's workspace
+  void **d_order = &mem.p[RT_LIST_ROWS], **d_work = &mem.p[RT_LIST_ROWS + 1];
+  for (int i = 0; i < n_rows; i++) if (rows[i].host) HIP_TRY(hipMalloc(&mem.p[i], chunk * rows[i].each));
+  if (binned) {
+    HIP_TRY(hipMalloc(d_order, chunk * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(d_work, rt_rays_order_work_bytes(chunk)));
   }
-  const rt_ray_outputs dout = {(double *)mem.p[1], (uint8_t *)mem.p[2], (rt_hit *)mem.p[3]};
   double kernel_ms = 0.0;
   for (uint64_t base = 0; base < n; base += chunk) {
     const size_t m = n - base < chunk ? (size_t)(n - base) : chunk;
-    HIP_TRY(hipMemcpyAsync(mem.p[0], host[0] + base * each[0], m * each[0], hipMemcpyHostToDevice, D.stream));
-    if (binned) {
-      event_timer timer;                                 // (a stats call)
-      if (stats) HIP_TRY(timer.start(D.stream));
-      if ((rc = order_rays_launch((uint32_t)m, (const double *)mem.p[0], (uint32_t *)mem.p[4], mem.p[5], D.stream))) return rc;
-      if (stats) {
-        HIP_TRY(timer.stop(D.stream));
-        HIP_TRY(hipEventSynchronize(timer.b));
-        float ms = 0.f;
-        HIP_TRY(timer.elapsed(&ms));
-        kernel_ms += ms;
-      }
-    }
+    for (int i = 0; i < n_rows; i++)
+      if (rows[i].host && !rows[i].out) HIP_TRY(hipMemcpyAsync(mem.p[i], (const uint8_t *)rows[i].host + base * rows[i].each, m * rows[i].each, hipMemcpyHostToDevice, D.stream));
     rt_stats st;
-    if ((rc = trace_rays_launch(s, (uint32_t)m, (uint32_t)base, (const double *)mem.p[0], (const uint32_t *)mem.p[4], segs, dout, D.stream,
-                                stats ? &st : nullptr)))
-      return rc;
+    if (binned) {
+      stats_clock step;
+      if ((rc = step.start(stats, D.stream))) return rc;
+      if ((rc = order_rays_launch((uint32_t)m, (const double *)mem.p[0], (uint32_t *)*d_order, *d_work, D.stream))) return rc;
+      if ((rc = step.finish(stats ? &st : nullptr, m))) return rc;
+      if (stats) kernel_ms += st.kernel_ms;
+    }
+    if ((rc = launch(s, (uint32_t)m, (uint32_t)base, mem.p, (const uint32_t *)*d_order, D.stream, stats ? &st : nullptr))) return rc;
     if (stats) kernel_ms += st.kernel_ms;
-    for (int i = 1; i < 4; i++) if (host[i]) HIP_TRY(hipMemcpyAsync(host[i] + base * each[i], mem.p[i], m * each[i], hipMemcpyDeviceToHost, D.stream));
+    for (int i = 0; i < n_rows; i++)
+      if (rows[i].host && rows[i].out) HIP_TRY(hipMemcpyAsync((uint8_t *)rows[i].host + base * rows[i].each, mem.p[i], m * rows[i].each, hipMemcpyDeviceToHost, D.stream));
     HIP_TRY(hipStreamSynchronize(D.stream));
   }
   if (stats) {
@@ -325,6 +328,20 @@ int trace_rays_to_host(const void *blob, size_t bytes, uint64_t n, const double 
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
   return RT_OK;
+}
+
+// intersectWorld for a list of rays in host memory (`binned`: rt_trace_rays_binned)
+int trace_rays_to_host(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *ho, rt_stats *stats,
+                       bool binned, const char *what) {
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  if ((rc = rays_check(n, rays, segs, ho, what))) return rc;
+  const list_row rows[4] = {{rays, 6u * sizeof(double), false}, {ho->rgb, 3u * sizeof(double), true}, {ho->rgba, 4u, true}, {ho->hits, sizeof(rt_hit), true}};
+  return chunked_list_call(blob, bytes, n, rows, 4, binned, stats,
+                           [segs](rt_scene_dev *s, uint32_t m, uint32_t base, void *const *d, const uint32_t *d_order, hipStream_t stream, rt_stats *st) {
+                             const rt_ray_outputs dout = {(double *)d[1], (uint8_t *)d[2], (rt_hit *)d[3]};
+                             return trace_rays_launch(s, m, base, (const double *)d[0], d_order, segs, dout, stream, st);
+                           });
 }
 }  // namespace
 
@@ -337,64 +354,21 @@ extern "C" int rt_trace_rays_binned(const void *blob, size_t bytes, uint64_t n, 
   return trace_rays_to_host(blob, bytes, n, rays, segs, ho, stats, true, "rt_trace_rays_binned");
 }
 
-// The shadow scan for a list of segments in host memory, with rt_render's resident scene: chunks of RT_RAY_CHUNK segments go through one
-// set of device buffers, as the ray lists do.  Synchronous; kernel_ms is the sum over the chunks.  `binned` (rt_occlusion_binned): every
-// chunk is ordered on the GPU (rt_rays_order.hip) and scanned in that order; kernel_ms includes the orderings.
+// The shadow scan for a list of segments in host memory (`binned`: rt_occlusion_binned)
 namespace {
 int occlusion_to_host(const void *blob, size_t bytes, uint64_t n, const double *rays, const rt_occlusion_inputs *hi, const rt_occlusion_outputs *ho,
                       rt_stats *stats, bool binned, const char *what) {
   int rc = rt_scene_validate(blob, bytes);
   if (rc) return rc;
   if ((rc = occlusion_check(n, rays, hi, ho, what))) return rc;
-  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
-  std::lock_guard<std::mutex> lk(G.mu);
-  const auto t_begin = std::chrono::steady_clock::now();
-  rt_scene_dev *s = nullptr;
-  if ((rc = scene_for(0, blob, bytes, &s))) return rc;
-  if ((rc = ensure_device(0))) return rc;
-  device_state &D = G.dev[0];
-  const size_t chunk = n < RT_RAY_CHUNK ? (size_t)n : RT_RAY_CHUNK;
-  // 0 rays, 1 length, 2 intensity in, 3 skip (inputs); 4 intensity, 5 blocker (outputs); 6 order, 7 the ordering's workspace
-  struct device_bufs { void *p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; ~device_bufs() { for (void *q : p) if (q) (void)hipFree(q); } } mem;
-  const size_t each[6] = {6u * sizeof(double), sizeof(double), sizeof(double), sizeof(int32_t), sizeof(double), sizeof(int32_t)};
-  uint8_t *const host[6] = {(uint8_t *)rays, hi ? (uint8_t *)hi->length : nullptr, hi ? (uint8_t *)hi->intensity : nullptr, hi ? (uint8_t *)hi->skip : nullptr,
-                            (uint8_t *)ho->intensity, (uint8_t *)ho->blocker};
-  for (int i = 0; i < 6; i++) if (host[i]) HIP_TRY(hipMalloc(&mem.p[i], chunk * each[i]));
-  if (binned) {
-    HIP_TRY(hipMalloc(&mem.p[6], chunk * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&mem.p[7], rt_rays_order_work_bytes(chunk)));
-  }
-  const rt_occlusion_inputs din = {(const double *)mem.p[1], (const double *)mem.p[2], (const int32_t *)mem.p[3]};
-  const rt_occlusion_outputs dout = {(double *)mem.p[4], (int32_t *)mem.p[5]};
-  double kernel_ms = 0.0;
-  for (uint64_t base = 0; base < n; base += chunk) {
-    const size_t m = n - base < chunk ? (size_t)(n - base) : chunk;
-    for (int i = 0; i < 4; i++) if (host[i]) HIP_TRY(hipMemcpyAsync(mem.p[i], host[i] + base * each[i], m * each[i], hipMemcpyHostToDevice, D.stream));
-    if (binned) {
-      event_timer timer;                                 // (a stats call)
-      if (stats) HIP_TRY(timer.start(D.stream));
-      if ((rc = order_rays_launch((uint32_t)m, (const double *)mem.p[0], (uint32_t *)mem.p[6], mem.p[7], D.stream))) return rc;
-      if (stats) {
-        HIP_TRY(timer.stop(D.stream));
-        HIP_TRY(hipEventSynchronize(timer.b));
-        float ms = 0.f;
-        HIP_TRY(timer.elapsed(&ms));
-        kernel_ms += ms;
-      }
-    }
-    rt_stats st;
-    if ((rc = occlusion_launch(s, (uint32_t)m, (const double *)mem.p[0], (const uint32_t *)mem.p[6], din, dout, D.stream, stats ? &st : nullptr))) return rc;
-    if (stats) kernel_ms += st.kernel_ms;
-    for (int i = 4; i < 6; i++) if (host[i]) HIP_TRY(hipMemcpyAsync(host[i] + base * each[i], mem.p[i], m * each[i], hipMemcpyDeviceToHost, D.stream));
-    HIP_TRY(hipStreamSynchronize(D.stream));
-  }
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = kernel_ms;
-    stats->pixels = n;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
-  return RT_OK;
+  const list_row rows[6] = {{rays, 6u * sizeof(double), false}, {hi ? hi->length : nullptr, sizeof(double), false}, {hi ? hi->intensity : nullptr, sizeof(double), false},
+                            {hi ? hi->skip : nullptr, sizeof(int32_t), false}, {ho->intensity, sizeof(double), true}, {ho->blocker, sizeof(int32_t), true}};
+  return chunked_list_call(blob, bytes, n, rows, 6, binned, stats,
+                           [](rt_scene_dev *s, uint32_t m, uint32_t, void *const *d, const uint32_t *d_order, hipStream_t stream, rt_stats *st) {
+                             const rt_occlusion_inputs din = {(const double *)d[1], (const double *)d[2], (const int32_t *)d[3]};
+                             const rt_occlusion_outputs dout = {(double *)d[4], (int32_t *)d[5]};
+                             return occlusion_launch(s, m, (const double *)d[0], d_order, din, dout, stream, st);
+                           });
 }
 }  // namespace
 

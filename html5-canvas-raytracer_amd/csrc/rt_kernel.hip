@@ -1912,107 +1912,69 @@ __global__ void __launch_bounds__(RT_WG_THREADS) rt_trace_rays(const rt_launch L
 
 }  // namespace
 
+// ---- host side: this translation unit's kernels by variant (rt_device.h: rt_trace_variant), and their launch ----
 #if RT_STRICT
-// Host-side launcher of rt_retrace (n_wg workgroups of RT_WG_THREADS).  Returns a hipError_t as int.
-extern "C" int rt_launch_retrace(const rt_launch *L, int refract, int ss2, unsigned n_wg, hipStream_t stream) {
-  const dim3 grid(n_wg ? n_wg : 1u), block(RT_WG_THREADS);
-  if (!refract) { if (!ss2) hipLaunchKernelGGL((rt_retrace<false, false>), grid, block, 0, stream, *L); else hipLaunchKernelGGL((rt_retrace<false, true>), grid, block, 0, stream, *L); }
-  else          { if (!ss2) hipLaunchKernelGGL((rt_retrace<true, false>), grid, block, 0, stream, *L);  else hipLaunchKernelGGL((rt_retrace<true, true>), grid, block, 0, stream, *L); }
-  return (int)hipGetLastError();
+#define RT_KERNEL_NAME rt_kernel_trace_strict
+#else
+#define RT_KERNEL_NAME rt_kernel_trace_fast
+#endif
+// The ONE place that names this build's instantiations: one line each.  NULL: the variant is not this build's (or no launch has it).
+// The host's scratch query (rt_api.hip: variant_scratch) and the launcher below both go by this address.
+extern "C" const void *RT_KERNEL_NAME(rt_trace_variant v) {
+  struct row { rt_trace_variant v; const void *kernel; };
+#define RT_TRACE(R, C, S, G, W1) {{RT_STRICT != 0, false, false, R, C, S, G, W1}, (const void *)&rt_trace<R, C, S, G, W1>}
+  static const row table[] = {                      // (the code object lists its kernels in the order of these rows)
+#if !RT_STRICT
+    // GRID: the shadow-grid variant, a separate instantiation so that scenes with few spheres do not carry its registers (the host
+    // leaves the cull rectangles out of the LDS image exactly for the scenes that have a shadow grid or a bounce table).
+    // GRID, one-wave workgroups (reflection only): SS2
+    RT_TRACE(false, false, false, true, true),   RT_TRACE(false, false, true, true, true),
+    // GRID, four-wave workgroups: REFRACT x SS2
+    RT_TRACE(false, false, false, true, false),  RT_TRACE(false, false, true, true, false),
+    RT_TRACE(true, false, false, true, false),   RT_TRACE(true, false, true, true, false),
+    // few spheres, one-wave workgroups (reflection only): SS2
+    RT_TRACE(false, false, false, false, true),  RT_TRACE(false, false, true, false, true),
+    // few spheres, four-wave workgroups: REFRACT x SS2
+    RT_TRACE(false, false, false, false, false), RT_TRACE(false, false, true, false, false),
+    RT_TRACE(true, false, false, false, false),  RT_TRACE(true, false, true, false, false),
+    // counting: REFRACT x SS2
+    RT_TRACE(false, true, false, false, false),  RT_TRACE(false, true, true, false, false),
+    RT_TRACE(true, true, false, false, false),   RT_TRACE(true, true, true, false, false),
+#else
+    // rt_retrace: REFRACT x SS2
+    {{true, true, false, false, false, false, false, false}, (const void *)&rt_retrace<false, false>},
+    {{true, true, false, false, false, true, false, false}, (const void *)&rt_retrace<false, true>},
+    {{true, true, false, true, false, false, false, false}, (const void *)&rt_retrace<true, false>},
+    {{true, true, false, true, false, true, false, false}, (const void *)&rt_retrace<true, true>},
+    // rt_trace_rays: REFRACT
+    {{true, false, true, false, false, false, false, false}, (const void *)&rt_trace_rays<false>},
+    {{true, false, true, true, false, false, false, false}, (const void *)&rt_trace_rays<true>},
+    // rt_trace: REFRACT x COUNT x SS2
+    RT_TRACE(false, false, false, false, false), RT_TRACE(false, false, true, false, false),
+    RT_TRACE(true, false, false, false, false),  RT_TRACE(true, false, true, false, false),
+    RT_TRACE(false, true, false, false, false),  RT_TRACE(false, true, true, false, false),
+    RT_TRACE(true, true, false, false, false),   RT_TRACE(true, true, true, false, false),
+#endif
+  };
+#undef RT_TRACE
+  for (const row &r : table) if (rt_variant_bits(r.v) == rt_variant_bits(v)) return r.kernel;
+  return nullptr;
 }
 
-// Host-side launcher of rt_trace_rays (n_wg workgroups of RT_WG_THREADS; `order` NULL or n_rays entries) and its per-lane scratch.  Return a hipError_t as int.
-extern "C" int rt_launch_trace_rays(const rt_launch *L, const uint32_t *order, int refract, unsigned n_wg, hipStream_t stream) {
-  const dim3 grid(n_wg ? n_wg : 1u), block(RT_WG_THREADS);
-  if (!refract) hipLaunchKernelGGL((rt_trace_rays<false>), grid, block, 0, stream, *L, order);
-  else hipLaunchKernelGGL((rt_trace_rays<true>), grid, block, 0, stream, *L, order);
-  return (int)hipGetLastError();
-}
-extern "C" int rt_scratch_trace_rays(int refract, size_t *bytes_per_lane) {
-  hipFuncAttributes fa;
-  const hipError_t e = hipFuncGetAttributes(&fa, !refract ? (const void *)&rt_trace_rays<false> : (const void *)&rt_trace_rays<true>);
-  if (e == hipSuccess) *bytes_per_lane = (size_t)fa.localSizeBytes;
-  return (int)e;
-}
-#endif
-
-// Scratch (private segment) bytes per lane of the kernel instantiation the launcher below would pick, from the code object: what the
-// runtime reserves for every wave slot of the device before the first launch (rt_api.hip: scratch_guard).  Returns a hipError_t as int.
-extern "C" int RT_SCRATCH_NAME(int refract, int count, int ss2, int grid_variant, int one_wave, size_t *bytes_per_lane) {
-  const void *f = nullptr;
-#define RT_PICK(R, C, S, G) f = (const void *)&rt_trace<R, C, S, G>
-  if (!RT_STRICT && grid_variant && !count) {
-#if !RT_STRICT
-    if (!refract && one_wave) { if (!ss2) f = (const void *)&rt_trace<false, false, false, true, true>; else f = (const void *)&rt_trace<false, false, true, true, true>; }
-    else if (!refract) { if (!ss2) RT_PICK(false, false, false, true); else RT_PICK(false, false, true, true); }
-    else          { if (!ss2) RT_PICK(true, false, false, true);  else RT_PICK(true, false, true, true); }
-#endif
-#if !RT_STRICT
-  } else if (!count && !refract && one_wave) {
-    if (!ss2) f = (const void *)&rt_trace<false, false, false, false, true>; else f = (const void *)&rt_trace<false, false, true, false, true>;
-#endif
-  } else if (!count) {
-    if (!refract) { if (!ss2) RT_PICK(false, false, false, false); else RT_PICK(false, false, true, false); }
-    else          { if (!ss2) RT_PICK(true, false, false, false);  else RT_PICK(true, false, true, false); }
-  } else {
-    if (!refract) { if (!ss2) RT_PICK(false, true, false, false); else RT_PICK(false, true, true, false); }
-    else          { if (!ss2) RT_PICK(true, true, false, false);  else RT_PICK(true, true, true, false); }
-  }
-#undef RT_PICK
-  hipFuncAttributes fa;
-  const hipError_t e = hipFuncGetAttributes(&fa, f);
-  if (e == hipSuccess) *bytes_per_lane = (size_t)fa.localSizeBytes;
-  return (int)e;
-}
-#if RT_STRICT
-extern "C" int rt_scratch_retrace(int refract, int ss2, size_t *bytes_per_lane) {
-  const void *f = !refract ? (!ss2 ? (const void *)&rt_retrace<false, false> : (const void *)&rt_retrace<false, true>)
-                           : (!ss2 ? (const void *)&rt_retrace<true, false> : (const void *)&rt_retrace<true, true>);
-  hipFuncAttributes fa;
-  const hipError_t e = hipFuncGetAttributes(&fa, f);
-  if (e == hipSuccess) *bytes_per_lane = (size_t)fa.localSizeBytes;
-  return (int)e;
-}
-#endif
-
-// Host-side launcher for this translation unit's kernels.  Returns a hipError_t as int.
-extern "C" int RT_LAUNCH_NAME(const rt_launch *L, int refract, int count, int ss2, unsigned lds_bytes, hipStream_t stream) {
-  // x: 32-pixel tiles across the frame; y: tiles x row blocks (8 rows, or 2 when supersampling); z: frames
-  (void)ss2;
-  // (the product launch is flat: L->grid_x workgroups, one per launch-table entry)
-  const dim3 grid(L->grid_x ? L->grid_x : (L->order ? L->tiles_x * L->n_tiles * L->rb_per_tile : L->tiles_x),
-                  L->grid_y ? L->grid_y : (L->order ? 1u : L->n_tiles * L->rb_per_tile), L->n_frames), block(RT_WG_THREADS);
-#define RT_CASE(R, C, S, G) hipLaunchKernelGGL((rt_trace<R, C, S, G>), grid, block, lds_bytes, stream, *L)
-#if !RT_STRICT
+// Launch of the variant's kernel.  A frame launch (rt_trace): the grid comes from the record - flat (L->grid_x workgroups, one per
+// launch-table entry: the product launch) or the plain grid (x: 32-pixel tiles across the frame; y: tiles x row blocks of 8 rows, or 2
+// when supersampling; z: frames) - with lds_bytes of dynamic LDS.  A list-driven launch (rt_retrace, rt_trace_rays): n_wg workgroups;
+// `order` is rt_trace_rays' second argument (NULL or n_rays entries).  Returns a hipError_t as int.
+extern "C" int RT_LAUNCH_NAME(const rt_launch *L, rt_trace_variant v, unsigned n_wg, const uint32_t *order, unsigned lds_bytes, hipStream_t stream) {
+  const void *f = RT_KERNEL_NAME(v);
+  if (!f) return (int)hipErrorInvalidDeviceFunction;
+  dim3 grid(L->grid_x ? L->grid_x : (L->order ? L->tiles_x * L->n_tiles * L->rb_per_tile : L->tiles_x),
+            L->grid_y ? L->grid_y : (L->order ? 1u : L->n_tiles * L->rb_per_tile), L->n_frames), block(RT_WG_THREADS);
+  if (v.retrace || v.rays) { grid = dim3(n_wg ? n_wg : 1u); lds_bytes = 0u; }
   // one-wave workgroups (rt_pixel_of, W1): four per table entry, whole groups of eight entries (the slots behind the last entry are
   // zero: their workgroups leave at once)
-  if (rt_one_wave_workgroups(false, count != 0, refract != 0, (L->scatter != 0u && !ss2) || L->four_waves != 0u)) {
-    const dim3 grid1(((grid.x + 7u) / 8u) * 32u, 1u, L->n_frames), block1(64u);
-    if (!L->cull_in_lds) {
-      if (!ss2) hipLaunchKernelGGL((rt_trace<false, false, false, true, true>), grid1, block1, lds_bytes, stream, *L);
-      else hipLaunchKernelGGL((rt_trace<false, false, true, true, true>), grid1, block1, lds_bytes, stream, *L);
-    } else {
-      if (!ss2) hipLaunchKernelGGL((rt_trace<false, false, false, false, true>), grid1, block1, lds_bytes, stream, *L);
-      else hipLaunchKernelGGL((rt_trace<false, false, true, false, true>), grid1, block1, lds_bytes, stream, *L);
-    }
-    return (int)hipGetLastError();
-  }
-#endif
-  // GRID: the shadow-grid variant, a separate instantiation so that scenes with few spheres do not carry its registers
-  // (the host leaves the cull rectangles out of the LDS image exactly for the scenes that have a shadow grid or a bounce table)
-  const bool grid_variant = !RT_STRICT && !count && !L->cull_in_lds;
-  if (grid_variant) {
-#if !RT_STRICT
-    if (!refract) { if (!ss2) RT_CASE(false, false, false, true); else RT_CASE(false, false, true, true); }
-    else          { if (!ss2) RT_CASE(true, false, false, true);  else RT_CASE(true, false, true, true); }
-#endif
-  } else if (!count) {
-    if (!refract) { if (!ss2) RT_CASE(false, false, false, false); else RT_CASE(false, false, true, false); }
-    else          { if (!ss2) RT_CASE(true, false, false, false);  else RT_CASE(true, false, true, false); }
-  } else {
-    if (!refract) { if (!ss2) RT_CASE(false, true, false, false); else RT_CASE(false, true, true, false); }
-    else          { if (!ss2) RT_CASE(true, true, false, false);  else RT_CASE(true, true, true, false); }
-  }
-#undef RT_CASE
+  else if (v.one_wave) { grid = dim3(((grid.x + 7u) / 8u) * 32u, 1u, L->n_frames); block = dim3(64u); }
+  void *args[] = {(void *)L}, *args_rays[] = {(void *)L, (void *)&order};          // (`order` is rt_trace_rays' alone)
+  (void)hipLaunchKernel(f, grid, block, v.rays ? args_rays : args, lds_bytes, stream);
   return (int)hipGetLastError();
 }

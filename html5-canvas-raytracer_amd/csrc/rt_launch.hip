@@ -1,7 +1,9 @@
-// rt_launch.hip — the launches of a resident scene (include/rt_hip.h: rt_render_*_device): the product launch with its launch table
-// and the list-driven strict launch behind it (rt_retrace), the strict kernel, 3x3 / 4x4 supersampling with a box filter, compact
-// bands, primary hits and picking, caller-supplied rays (rt_trace_rays) in the list's or a given order and their ordering, occlusion queries, and the test
-// build's per-sample probe.
+// rt_launch.hip — the launches of a resident scene (include/rt_hip.h: rt_render_*_device).  A colour launch is render_batch_impl: the
+// argument checks, the launch record (fill_launch, bind_kernel), then the strict launch or the product launch with its launch table and
+// the list-driven strict launch behind it (rt_retrace), then the stats; every launch works out its kernel variant once
+// (rt_device.h: rt_trace_variant) and hands that value to the LDS size, the scratch guard and the launcher.  Also here: 3x3 / 4x4
+// supersampling with a box filter, compact bands, primary hits and picking, caller-supplied rays (rt_trace_rays) in the list's or a
+// given order and their ordering, occlusion queries, and the test build's per-sample probe.
 
 #include "rt_api_internal.h"
 
@@ -17,6 +19,18 @@ int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *t
 #ifdef RT_TESTING
 thread_local struct { double *d_buf; uint32_t x, y; } g_probe = {nullptr, 0u, 0u};
 #endif
+
+// The scene in its own order, every sphere in the loops, the reference's own miss colour: what the strict kernels, the counting
+// variant, rt_retrace and rt_trace_rays walk (the rest of a frame launch's binding: bind_kernel).  Under launch_mu where an edit may run.
+void bind_scene_order(const rt_scene_dev *s, rt_launch &K) {
+  const uint8_t *ob = obj_block(s);                   // this generation's spheres, in blob order
+  K.objects = (const rt_sphere *)(ob + s->o_objs);
+  K.geom = (const rt_geom *)(ob + s->o_geom);
+  K.lds_image = lds_image_of(s);                      // its materials and texture descriptors
+  K.n_loop = s->hd.n_objects;
+  K.enclosing = ~0u;
+  memcpy(K.miss_color, s->hd.miss_color, sizeof K.miss_color);
+}
 }  // namespace
 
 #ifdef RT_TESTING
@@ -194,8 +208,301 @@ int render_supersampled(rt_scene_dev *s, uint32_t k, uint32_t w, uint32_t h, con
   return RT_OK;
 }
 
+// ---- one colour launch (supersample 1 or 2), as steps: what they share, the launch record, the strict launch, the product launch
+//      with its mark list and the list-driven strict launch behind it (rt_retrace), the stats ----
+// The test build's switches of a colour launch, read at ONE place.  The product build reads no environment variable: every switch is off.
+struct test_switches {
+  bool no_grid, no_bounce; unsigned lds_pad; long count_wait_us;                 // once per process (A/B runs)
+  bool no_fixup, mark_all, exact_all, mark_stripes, no_uniform, no_cells;        // per call: tests set these between calls
+  double flag_scale;                                                             // (RT_FLAG_SCALE; 1: not set)
+  bool uncached_marks;                   // a switch that changes what is marked or re-traced is on - nothing is cached then
+};
+test_switches read_test_switches() {
+  static const bool no_grid = RT_TEST_ENV("RT_NO_SHADOW_GRID") != nullptr, no_bounce = RT_TEST_ENV("RT_NO_BOUNCE_TABLE") != nullptr;     // A/B switches
+  // RT_LDS_PAD (bytes): occupancy experiments only — extra dynamic LDS per workgroup caps the workgroups per CU
+  static const unsigned lds_pad = RT_TEST_ENV("RT_LDS_PAD") ? (unsigned)atoi(RT_TEST_ENV("RT_LDS_PAD")) : 0u;
+  static const long count_wait_us = RT_TEST_ENV("RT_COUNT_WAIT_US") ? atol(RT_TEST_ENV("RT_COUNT_WAIT_US")) : -1;
+  test_switches t = {no_grid, no_bounce, lds_pad, count_wait_us};
+  t.no_fixup = RT_TEST_ENV("RT_NO_FIXUP") != nullptr;                           // the product kernel's own pixels everywhere
+  t.mark_all = RT_TEST_ENV("RT_MARK_ALL") != nullptr; t.exact_all = RT_TEST_ENV("RT_EXACT_ALL") != nullptr; t.mark_stripes = RT_TEST_ENV("RT_TEST_MARK_STRIPES") != nullptr;
+  t.no_uniform = RT_TEST_ENV("RT_NO_UNIFORM_BLOCKS") != nullptr;                // every wave on the general path (rt_kernel.hip: trace_pixel, UNI)
+  t.no_cells = RT_TEST_ENV("RT_NO_CHECKER_CELLS") != nullptr;                   // the table's checker cells are ignored (rt_kernel.hip: trace_pixel, one_cell)
+  const char *fs = RT_TEST_ENV("RT_FLAG_SCALE");                                // a wider boundary band, to exercise the second launch
+  t.flag_scale = fs ? atof(fs) : 1.0;
+  t.uncached_marks = fs || t.mark_all || t.exact_all || t.no_fixup;
+  return t;
+}
+
+// what the steps of one colour launch share
+struct colour_call {
+  rt_scene_dev *s; device_state &D; hipStream_t stream;
+  uint32_t w, h, ss; const rt_tiles *tiles; uint32_t n_frames, flags;
+  bool ss2, count, compact;
+  test_switches t;
+};
+// what the product launch leaves for the stats
+struct retrace_result {
+  const uint32_t *marks_read = nullptr; uint32_t marks_read_slot = 0;    // where this launch's mark count can be read afterwards
+  uint64_t centre_items = 0;
+  bool retraced_all = false, strict_rendered = false;
+};
+struct marks_guard {                                     // a per-call mark list is released on every way out, after the stream has drained
+  void *p = nullptr; hipStream_t st = nullptr;
+  ~marks_guard() { if (p) { (void)hipStreamSynchronize(st); (void)hipFree(p); } }
+};
+
+int launched(int err) { return err != 0 ? fail(RT_ERR_DEVICE, "kernel launch: %s", hipGetErrorString((hipError_t)err)) : RT_OK; }
+
+// Dynamic LDS of a variant's workgroup: the scene's LDS image and the fold state (10 doubles per lane, the general kernel 13; the strict
+// kernels one slot, the scatter store's tile).  The reflection-only many-sphere variants keep only the fold state in LDS (rt_kernel.hip:
+// IMAGE_IN_LDS); one-wave workgroups have 64 lanes.
+unsigned lds_for(const rt_scene_dev *s, rt_trace_variant v, unsigned lds_pad) {
+  if (v.strict) return s->lds_bytes + lds_pad + RT_WG_THREADS * 8u;
+  const unsigned fold = (v.refract ? 13u : 10u) * (v.one_wave ? 64u : RT_WG_THREADS) * 8u;
+  return ((v.grid && !v.refract) ? 0u : s->lds_bytes) + lds_pad + fold;
+}
+
+// The part of the launch record that depends on the kernel: ordering B (enclosing sphere last, outside the loops) and the shadow grids /
+// bounce table for the product kernel; `plain` - the strict kernels, rt_retrace and the counting variant - walks the scene in its own
+// order (bind_scene_order) so that it stays literal / counts what the reference counts.
+void bind_kernel(const rt_scene_dev *s, rt_launch &K, bool plain, const test_switches &t) {
+  const rt_scene_header &hd = s->hd;
+  const bool order_b = s->has_b && !plain;
+  const uint8_t *ob = obj_block(s);                   // this generation's spheres
+  if (order_b) {
+    K.objects = (const rt_sphere *)(ob + s->o_objs_b);
+    K.geom = (const rt_geom *)(ob + s->o_geom) + (size_t)hd.n_objects * (1 + hd.n_lights);      // [plain N | anchored at light k: NL x N]
+    K.lds_image = lds_image_of(s) + s->lds_image_bytes;
+    K.n_loop = K.enclosing = hd.n_objects - 1;
+    memcpy(K.miss_color, hd.miss_color, sizeof K.miss_color);
+  } else bind_scene_order(s, K);
+  const rt_geom *gc = (const rt_geom *)cam_block(s) + (order_b ? 2 * (size_t)hd.n_objects : 0);     // this camera's block: [anchored at the camera N | cull rectangles N]
+  K.geom_cam = gc;
+  K.cull = gc + hd.n_objects;
+  K.geom_light = K.geom + hd.n_objects;
+  K.shadow_grid = (!plain && !t.no_grid && s->has_sg) ? ob + s->o_sg : nullptr;
+  K.bounce_table = (!plain && !t.no_bounce && s->has_bt) ? ob + s->o_bt : nullptr;
+  K.enclosing_flat = (order_b && s->enclosing_flat) ? 1u : 0u;
+  K.cull_in_lds = s->cull_in_lds ? 1u : 0u;
+  K.sky_fast = (!plain && sky_fast(s)) ? 1u : 0u;
+  for (int c = 0; c < 3; c++) K.sky_rgb[c] = s->sky_rgb[c];
+  if (K.sky_fast && s->enclosing == ~0u) {
+    // no enclosing sphere at all: a primary ray that meets nothing is the miss colour (main.js:231), a constant as well
+    memcpy(K.sky_rgb, hd.miss_color, sizeof K.sky_rgb);
+  } else if (K.sky_fast) {
+    // A flat sky of constant colour needs no hit record at all: "met nothing in the loops" IS "met the sky", whose pixel term
+    // is the constant the host evaluated - so for the product kernel that constant takes the place of the miss colour
+    // (main.js:231 is unreachable in such a scene: the sky encloses every ray) and the sphere leaves the kernel's view.
+    // Lanes that end on the sky then take the two-instruction miss branch, at every level of the ray tree.
+    K.enclosing = ~0u;
+    memcpy(K.miss_color, s->sky_rgb, sizeof K.miss_color);
+  }
+}
+
+// Step 2: the launch record of the call, bound to the strict kernel (`strict_main`) or to the product kernel.  The launch table, the
+// mark list and the grid are the product launch's to add.
+int fill_launch(const colour_call &c, bool strict_main, uint32_t stars_seed, void *d_out, uint64_t frame_stride_bytes, void *const *d_frames, rt_launch &L) {
+  const rt_scene_dev *s = c.s;
+  const rt_scene_header &hd = s->hd;
+  const rt_tiles *tiles = c.tiles;
+  memset(&L, 0, sizeof L);
+  bind_kernel(s, L, strict_main || c.count, c.t);
+  // the boundary test of the product kernel's samplers (rt_device.h)
+  L.flag_tol = s->flag_tol * c.t.flag_scale;
+  L.mark_flags = (c.t.mark_all ? RT_MARK_ALL : 0u) | (c.t.no_fixup ? RT_MARK_NEVER : 0u) | (c.t.mark_stripes ? RT_MARK_ZERO : 0u) | (s->unit_weights ? RT_MARK_WEIGHT : 0u);
+  L.marks_cap = RT_MARKS_CAP;
+  L.stars_seed = stars_seed;
+  L.stars_step = (c.flags & RT_FLAG_STARS_PER_FRAME) ? 1u : 0u;
+  L.textures = s->d_texdesc;
+  L.texel_base = (const uint8_t *)s->d_blob;
+  L.out = (uint32_t *)d_out;
+  L.counters = c.D.d_counters;
+  memcpy(L.cam_origin, hd.cam_origin, 12 * sizeof(double));   // origin, axisX, axisY, axisZ are contiguous
+  const launch_geom geom = launch_geometry(hd.fov_deg, c.w, c.h, c.ss, tiles->tile_rows);
+  L.proj_w = geom.proj_w; L.proj_h = geom.proj_h; L.proj_d = geom.proj_d;
+  L.epsilon = hd.epsilon; L.light_intensity = hd.light_intensity;
+  L.n_objects = hd.n_objects; L.n_lights = hd.n_lights; L.segs = hd.segs;
+  L.w = c.w; L.h = c.h;
+  L.tile_rows = tiles->tile_rows; L.tile_first = tiles->tile_first; L.tile_stride = tiles->tile_stride; L.n_tiles = tiles->n_tiles;
+  L.tiles_x = geom.tiles_x;
+  memcpy(L.lights, s->lights, sizeof L.lights);
+  L.rb_per_tile = geom.rb_per_tile;
+  L.rb_shift = ~0u;
+  for (uint32_t b = 0; b < 31; b++) if (L.rb_per_tile == (1u << b)) L.rb_shift = b;
+  if ((uint64_t)tiles->n_tiles * L.rb_per_tile > 65535u) return fail(RT_ERR_INVALID, "%u tiles x %u row blocks exceed the grid's y limit (65535)", tiles->n_tiles, L.rb_per_tile);
+  L.n_frames = c.n_frames;
+  L.frame_stride = frame_stride_bytes / 4u;
+  L.rgb24 = (c.flags & RT_FLAG_RGB24) ? 1u : 0u;
+  L.compact = c.compact ? 1u : 0u;
+  L.scatter = d_frames ? 1u : 0u;
+  if (d_frames) for (uint32_t f = 0; f < c.n_frames; f++) L.out_frames[f] = (uint32_t *)d_frames[f];
+  for (int k = 0; k < 3; k++) L.cam_axis_sum[k] = hd.cam_axis_x[k] + hd.cam_axis_y[k] + hd.cam_axis_z[k];
+  L.ray_bias[0] = 0.5 - L.proj_w; L.ray_bias[1] = L.proj_h - 0.5; L.ray_bias[2] = L.cam_axis_sum[2] * L.proj_d;
+#ifdef RT_TESTING
+  L.probe = g_probe.d_buf; L.probe_x = g_probe.x; L.probe_y = g_probe.y;
+  L.no_uniform = c.t.no_uniform ? 1u : 0u;
+  L.uniform_waves = c.D.d_counters + 3;
+  L.no_cells = c.t.no_cells ? 1u : 0u;
+#endif
+  return RT_OK;
+}
+
+// Step 3, strict: the strict kernel renders the whole call on the plain grid - a strict call or scene, and a frame known to overflow
+// the mark list.  Under launch_mu.
+int strict_launch(const colour_call &c, const rt_launch &L, bool count) {
+  const rt_trace_variant v = rt_trace_variant_of(true, false, c.s->refract, count, c.ss2, L.cull_in_lds != 0u, L.scatter != 0u, false);
+  if (int rc = guard_kernel_scratch(c.D, c.stream, v, (uint64_t)L.tiles_x * L.n_tiles * L.rb_per_tile * c.n_frames * (RT_WG_THREADS / 64u), "the strict trace kernel")) return rc;
+  return launched(launch_variant(L, v, 0u, nullptr, lds_for(c.s, v, c.t.lds_pad), c.stream));
+}
+
+// How many entries the launch table has, if the host knows (0: not yet).  One workgroup per table entry is launched (runs of sky blocks
+// share one).  How many there are is known on the device; until the build's count has reached the host, one workgroup per BLOCK is
+// launched: those behind the last entry read a zero slot and leave.
+uint32_t table_entries_known(const rt_scene_dev *s, const rt_scene_dev::order_entry &oe, const test_switches &t) {
+  uint32_t n_known = known_value(oe.known, s->cam_gen);
+  // A table that rt_scene_set_camera is rebuilding on the side stream - beside the previous frame's trace - publishes its count
+  // while that trace is still running.  A caller that issues frames back to back arrives here earlier than that: it is given a
+  // short, BOUNDED wait for the word (it is ahead of the GPU anyway, and stays one frame ahead: the trace in flight has tens of
+  // microseconds left when the word arrives); one workgroup per block costs a 4K frame 80 us instead of 68.  A caller that comes
+  // later (a frame per display refresh) finds the word there; a word that does not come in time: one workgroup per block.
+  if (!n_known && oe.built_on == s->side && oe.cam_gen == s->cam_gen) {
+    // (the bound grows with the table: a 4K frame's build takes ~50 us beside a trace, an 8K frame's four times that)
+    const long wait_us = t.count_wait_us >= 0 ? t.count_wait_us : 100 + (long)(oe.n_blocks / 256u);
+    const auto t0 = std::chrono::steady_clock::now();
+    while (!n_known && std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() < wait_us) {
+      __builtin_ia32_pause();
+      n_known = known_value(oe.known, s->cam_gen);
+    }
+  }
+  return n_known;
+}
+
+// The mark state of a (launch table, stream) pair, found or made.  The first launch of a pair gets a list of its own; beyond
+// RT_KNOWN_WORDS pairs: one per call (`temp`, released through `temp_marks`), nothing cached.
+int mark_state_for(rt_scene_dev *s, uint32_t order_index, hipStream_t stream, marks_guard &temp_marks, rt_scene_dev::mark_state &temp,
+                   rt_scene_dev::mark_state **out) {
+  for (rt_scene_dev::mark_state &m : s->mark_states) if (m.order_index == order_index && m.stream == stream) { *out = &m; return RT_OK; }
+  const size_t bytes = 16u + (size_t)RT_MARKS_CAP * 8u;
+  uint32_t *d = nullptr;
+  hipError_t e = hipMalloc((void **)&d, bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(d, 0, 16u, stream);
+  if (e != hipSuccess) { if (d) (void)hipFree(d); return fail(RT_ERR_DEVICE, "mark list: %s", hipGetErrorString(e)); }
+  if (s->mark_states.size() >= RT_KNOWN_WORDS) { temp_marks.p = d; temp_marks.st = stream; temp.d_marks = d; *out = &temp; }
+  else {
+    s->mark_states.push_back(rt_scene_dev::mark_state{order_index, stream, d, known_word(s, s->mark_states.size()), 0u});
+    *out = &s->mark_states.back();
+  }
+  return RT_OK;
+}
+
+// Step 3, behind the product launch `L`: the list-driven strict launch (rt_retrace) over the samples the product kernel marked and the
+// centre lines - unless this frame is KNOWN to have nothing for it.  `known`: 0 not known (yet), else the frame's mark count + 1.
+// Centre row / centre column of a sample grid with an ODD number of rows / columns (supersample 2 makes it even).  The primary
+// rays there have a direction component that is EXACTLY zero (main.js:186: x - w/2 + 0.5 == 0), so they - and every ray they
+// spawn that stays in that plane - live in a coordinate plane through the camera, and a sphere centred on that plane (the
+// reference's own scene has several) is met with a normal component of exactly 0: u or v lands exactly ON a texel / checker
+// boundary (main.js:127-130, 344-347), and on which side the reference falls is decided by whether ITS OWN rounding noise
+// (e.g. main.js:257-259 at refract_index 1, where q is 0 or 1e-16 depending on the last bit of cosi) pushed the ray off the
+// plane.  No arithmetic but the reference's own reproduces such coin flips: rt_retrace traces those samples too.
+int retrace_launch(const colour_call &c, const rt_launch &L, const rt_scene_dev::order_entry &oe, rt_scene_dev::mark_state &ms, uint32_t known, retrace_result &o) {
+  const rt_scene_dev *s = c.s;
+  const rt_tiles *tiles = c.tiles;
+  rt_launch F = L;
+  F.order = nullptr; F.grid_x = F.grid_y = 0u;
+  F.centre_row = F.centre_col = ~0u;
+  if (!c.ss2 && (c.h & 1u)) {
+    const uint32_t crow = (c.h - 1u) / 2u, tc = crow / tiles->tile_rows;
+    if (tc >= tiles->tile_first && (tc - tiles->tile_first) % tiles->tile_stride == 0 && (tc - tiles->tile_first) / tiles->tile_stride < tiles->n_tiles) { F.centre_row = crow; o.centre_items += (uint64_t)c.w * c.n_frames; }
+  }
+  if (!c.ss2 && (c.w & 1u)) { F.centre_col = (c.w - 1u) / 2u; o.centre_items += (uint64_t)tiles->n_tiles * tiles->tile_rows * c.n_frames; }
+  const bool retrace_all = c.t.exact_all && !c.t.no_fixup;
+  // (a sky-only launch traces nothing; the centre lines belong to the calls that trace)
+  if (c.t.no_fixup || (c.flags & RT_FLAG_SKY_ONLY) || !(known != 1u || o.centre_items != 0 || retrace_all)) return RT_OK;
+  bind_kernel(s, F, true, c.t);                         // the scene in its own order, every sphere in the loops, the reference's own miss colour
+  if (c.compact) {                                      // where a sample's block sits in the compact band: from the table's own arrays
+    const rt_table_dev &T = oe.Tb[s->cam_gen & 1u];
+    F.tb_item = T.item; F.tb_rank_in_row = T.rank_in_row; F.tb_row_hist = T.row_hist; F.tb_bin_start = T.bin_start; F.tb_bins = oe.cost_bins;
+  }
+  F.marks_known = c.t.uncached_marks ? nullptr : (unsigned long long *)ms.h_known;
+  F.known_tag = (uint32_t)s->cam_gen;
+  F.retrace_all = retrace_all ? 1u : 0u;
+  o.retraced_all = retrace_all;
+  // The grid.  Count known: its items and the centre lines.  Not known yet (the first frame from a camera): the list may hold up
+  // to RT_MARKS_CAP items or have overflowed - 256 workgroups (idle ones leave at once) walk an overflowed 3840x2160 frame at
+  // ~130 samples per lane, once; from the next frame on the count is known (and an overflow takes the strict kernel instead).
+  uint64_t n_wg = (((known ? known - 1u : 0u) + o.centre_items) * (c.ss2 ? 4u : 1u) + RT_WG_THREADS - 1) / RT_WG_THREADS + 2u;      // (supersample 2: a lane per sample)
+  if (!known && n_wg < 256u) n_wg = 256u;
+  if (retrace_all) n_wg = ((uint64_t)tiles->n_tiles * tiles->tile_rows * c.w * c.n_frames + RT_WG_THREADS - 1) / RT_WG_THREADS;
+  if (n_wg > 8192u) n_wg = 8192u;
+  const rt_trace_variant v = rt_trace_variant_of(true, true, s->refract, false, c.ss2, L.cull_in_lds != 0u, L.scatter != 0u, false);
+  if (int rc = guard_kernel_scratch(c.D, c.stream, v, n_wg * (RT_WG_THREADS / 64u), "the list-driven strict launch (rt_retrace)")) return rc;
+  if (int rc = launched(launch_variant(F, v, (unsigned)n_wg, nullptr, 0u, c.stream))) return rc;
+  o.marks_read = ms.d_marks; o.marks_read_slot = ms.slot;
+  ms.slot ^= 1u;                                        // rt_retrace cleared the other counter: the next launch's
+  return RT_OK;
+}
+
+// Step 3, product: the launch table (found, or built on the GPU for this camera), the trace, and the list-driven strict launch behind
+// it; one step for the threads of this process (under launch_mu).
+int product_launch(const colour_call &c, rt_launch &L, marks_guard &temp_marks, retrace_result &o) {
+  rt_scene_dev *s = c.s;
+  const frame_kind kind = {c.w, c.h, c.ss, *c.tiles, sky_part_of(c.flags)};
+  const uint32_t uses_before = c.count ? 0u : count_use(s, kind);
+  // the first frame from a camera that has moved: a caller that moves the camera every frame has the next camera's table built
+  // beside this launch (rt_scene_set_camera), and that build needs the trace's workgroups to be as wide as its own (rt_launch::four_waves)
+  L.four_waves = (!c.count && uses_before == 0u && s->cam_gen != 0u) ? 1u : 0u;
+  const int oi = dispatch_order(s, kind, choose_table(s, c.flags, uses_before), c.stream);
+  if (oi < 0) return RT_ERR_DEVICE;
+  rt_scene_dev::order_entry &oe = s->orders[oi];
+  L.order = oe.Tb[s->cam_gen & 1u].entries;
+  const uint32_t n_known = table_entries_known(s, oe, c.t);
+  L.order_n8 = (oe.n_blocks + 7u) / 8u;
+  L.grid_x = n_known ? n_known - 1u : oe.n_blocks;
+  L.grid_y = 1u;
+  rt_scene_dev::mark_state temp_state = {~0u, c.stream, nullptr, nullptr, 0u}, *ms = nullptr;
+  if (int rc = mark_state_for(s, (uint32_t)oi, c.stream, temp_marks, temp_state, &ms)) return rc;
+  L.marks = ms->d_marks; L.marks_slot = ms->slot;
+  const uint32_t known = c.t.uncached_marks ? 0u : known_value(ms->h_known, s->cam_gen);        // 0: not known (yet); else the frame's mark count + 1
+  // A frame KNOWN to mark more samples than the list holds (a legal scene can: every hit of a sphere whose sampler coordinate is
+  // an exact integer everywhere) would be traced twice in full, product kernel then rt_retrace over every sample: the strict
+  // kernel renders it once instead, the same bytes (the count stays known: nothing republishes it for this camera).
+  if (known != 0u && known - 1u > RT_MARKS_CAP && !c.count && !c.compact) {
+    if (c.flags & RT_FLAG_SKY_ONLY) return RT_OK;       // (as every strict launch: a NO_SKY call stores every pixel, a SKY_ONLY call none)
+    rt_launch S = L;
+    S.order = nullptr; S.grid_x = S.grid_y = 0u;
+    bind_kernel(s, S, true, c.t);
+    o.strict_rendered = true;
+    return strict_launch(c, S, false);
+  }
+  const rt_trace_variant v = rt_trace_variant_of(false, false, s->refract, c.count, c.ss2, L.cull_in_lds != 0u, L.scatter != 0u, L.four_waves != 0u);
+  if (int rc = guard_kernel_scratch(c.D, c.stream, v, (uint64_t)L.grid_x * c.n_frames * (RT_WG_THREADS / 64u), "the trace kernel")) return rc;
+#ifdef RT_WAVE_LOG
+  // measurement build: RT_WAVE_LOG_FILE=<path> - every wave's entry / exit time and place of THIS launch, written after it has finished
+  unsigned long long *d_wave_log = nullptr;
+  const size_t wave_log_words = (size_t)((L.grid_x + 7u) / 8u * 8u) * c.n_frames * (RT_WG_THREADS / 64u) * 4u;
+  if (getenv("RT_WAVE_LOG_FILE")) {
+    if (hipMalloc((void **)&d_wave_log, wave_log_words * 8u) == hipSuccess) (void)hipMemsetAsync(d_wave_log, 0, wave_log_words * 8u, c.stream);
+    L.wave_log = d_wave_log;
+  }
+#endif
+  const int err = launch_variant(L, v, 0u, nullptr, lds_for(s, v, c.t.lds_pad), c.stream);
+#ifdef RT_WAVE_LOG
+  if (d_wave_log) {
+    std::vector<unsigned long long> hostlog(wave_log_words);
+    (void)hipStreamSynchronize(c.stream);
+    (void)hipMemcpy(hostlog.data(), d_wave_log, wave_log_words * 8u, hipMemcpyDeviceToHost);
+    (void)hipFree(d_wave_log);
+    if (FILE *fp = fopen(getenv("RT_WAVE_LOG_FILE"), "wb")) { fwrite(hostlog.data(), 8u, wave_log_words, fp); fclose(fp); }
+    L.wave_log = nullptr;
+  }
+#endif
+  if (int rc = launched(err)) return rc;
+  return retrace_launch(c, L, oe, *ms, known, o);
+}
+
 int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, uint32_t n_frames, void *d_out, uint64_t frame_stride_bytes,
                       void *const *d_frames, void *hip_stream, uint32_t flags, rt_stats *stats, uint32_t ss_override) {
+  // ---- 1. the arguments ----
   if (!s || !tiles) return fail(RT_ERR_INVALID, "NULL scene, tiles or output");
   if (n_frames == 0 || n_frames > 65535u) return fail(RT_ERR_INVALID, "n_frames %u not in 1..65535", n_frames);
   if ((frame_stride_bytes & 3u) != 0) return fail(RT_ERR_INVALID, "frame stride must be a multiple of 4 bytes");
@@ -206,10 +513,10 @@ int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *t
     return fail(RT_ERR_INVALID, "RT_FLAG_NO_SKY and RT_FLAG_SKY_ONLY exclude each other and RT_FLAG_COUNT");
   if ((flags & RT_FLAG_COMPACT) && ((flags & (RT_FLAG_RGB24 | RT_FLAG_NO_SKY | RT_FLAG_COUNT | RT_FLAG_STRICT_FP)) != (RT_FLAG_RGB24 | RT_FLAG_NO_SKY) || d_frames))
     return fail(RT_ERR_INVALID, "RT_FLAG_COMPACT goes with RT_FLAG_RGB24 | RT_FLAG_NO_SKY into a band (no counting, no strict kernel, no scatter)");
-  if ((rc = ensure_device(s->device))) return rc;
+  hipStream_t stream = nullptr;
+  if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
   device_state &D = G.dev[s->device];
-  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : D.stream;
-  const auto t_begin = std::chrono::steady_clock::now();
+  stats_clock clock;
   uint32_t stars_seed;
   {
     // which streams the scene's launches run on (rt_scene_set_camera, dispatch_order), and: behind the last write of the camera block
@@ -218,291 +525,48 @@ int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *t
     if ((rc = behind_the_camera(s, stream))) return rc;
     note_launch(s, stream);
   }
-
-  const rt_scene_header &hd = s->hd;
-  const uint32_t ss = ss_override ? ss_override : hd.supersample;
+  const uint32_t ss = ss_override ? ss_override : s->hd.supersample;
   if (ss > 2u) {
     // (3x3 / 4x4 supersampling filters whole blocks of samples: a NO_SKY call stores every pixel, a SKY_ONLY call none)
     if (flags & RT_FLAG_SKY_ONLY) { if (stats) memset(stats, 0, sizeof *stats); return RT_OK; }
     return render_supersampled(s, ss, w, h, tiles, n_frames, d_out, frame_stride_bytes, d_frames, stream, flags & ~(uint32_t)RT_FLAG_NO_SKY, stats);
   }
-  const bool ss2 = ss == 2u;
-  const bool count = (flags & RT_FLAG_COUNT) != 0;
-  const bool no_fixup = RT_TEST_ENV("RT_NO_FIXUP") != nullptr;                 // test build: the product kernel's own pixels everywhere (read per call)
+  const colour_call c = {s, D, stream, w, h, ss, tiles, n_frames, flags, ss == 2u, (flags & RT_FLAG_COUNT) != 0, (flags & RT_FLAG_COMPACT) != 0, read_test_switches()};
   const bool strict_main = (flags & RT_FLAG_STRICT_FP) != 0 || strict_scene(s);
-  const bool compact = (flags & RT_FLAG_COMPACT) != 0;
-  if (compact && (strict_main || ss > 2u)) return fail(RT_ERR_UNSUPPORTED, "RT_FLAG_COMPACT: this scene is rendered by the strict kernel (or supersampled 3x3 / 4x4), which knows no launch table: send plain bands");
-  const uint8_t *db = (const uint8_t *)s->d_blob;
-  static const bool no_grid = RT_TEST_ENV("RT_NO_SHADOW_GRID") != nullptr;     // A/B switches (test build only)
-  static const bool no_bounce = RT_TEST_ENV("RT_NO_BOUNCE_TABLE") != nullptr;
-  // RT_LDS_PAD (bytes): occupancy experiments only — extra dynamic LDS per workgroup caps the workgroups per CU
-  static const unsigned lds_pad = RT_TEST_ENV("RT_LDS_PAD") ? (unsigned)atoi(RT_TEST_ENV("RT_LDS_PAD")) : 0u;
-  rt_launch L;
-  memset(&L, 0, sizeof L);
-  // the part of the launch record that depends on the kernel: ordering B (enclosing sphere last, outside the loops) and the
-  // shadow grids / bounce table for the product kernel; the strict kernel and the counting variant walk the scene in its own
-  // order so that they stay literal / count what the reference counts
-  auto bind_kernel = [&](rt_launch &K, bool strict) {
-    const bool plain = strict || count;
-    const bool order_b = s->has_b && !plain;
-    const uint8_t *ob = obj_block(s);                 // this generation's spheres
-    const rt_geom *gt = (const rt_geom *)(ob + s->o_geom) + (order_b ? (size_t)hd.n_objects * (1 + hd.n_lights) : 0);      // [plain N | anchored at light k: NL x N]
-    const rt_geom *gc = (const rt_geom *)cam_block(s) + (order_b ? 2 * (size_t)hd.n_objects : 0);     // this camera's block: [anchored at the camera N | cull rectangles N]
-    K.objects = (const rt_sphere *)(ob + (order_b ? s->o_objs_b : s->o_objs));
-    K.geom = gt;
-    K.geom_cam = gc;
-    K.cull = gc + hd.n_objects;
-    K.geom_light = gt + hd.n_objects;
-    K.lds_image = lds_image_of(s) + (order_b ? s->lds_image_bytes : 0);
-    K.shadow_grid = (!plain && !no_grid && s->has_sg) ? ob + s->o_sg : nullptr;
-    K.bounce_table = (!plain && !no_bounce && s->has_bt) ? ob + s->o_bt : nullptr;
-    K.n_loop = order_b ? hd.n_objects - 1 : hd.n_objects;
-    K.enclosing = order_b ? hd.n_objects - 1 : ~0u;
-    K.enclosing_flat = (order_b && s->enclosing_flat) ? 1u : 0u;
-    K.cull_in_lds = s->cull_in_lds ? 1u : 0u;
-    K.sky_fast = (!plain && sky_fast(s)) ? 1u : 0u;
-    for (int c = 0; c < 3; c++) K.sky_rgb[c] = s->sky_rgb[c];
-    memcpy(K.miss_color, hd.miss_color, sizeof K.miss_color);
-    if (K.sky_fast && s->enclosing == ~0u) {
-      // no enclosing sphere at all: a primary ray that meets nothing is the miss colour (main.js:231), a constant as well
-      K.sky_fast = 1u;
-      memcpy(K.sky_rgb, hd.miss_color, sizeof K.sky_rgb);
-    } else if (K.sky_fast) {
-      // A flat sky of constant colour needs no hit record at all: "met nothing in the loops" IS "met the sky", whose pixel term
-      // is the constant the host evaluated - so for the product kernel that constant takes the place of the miss colour
-      // (main.js:231 is unreachable in such a scene: the sky encloses every ray) and the sphere leaves the kernel's view.
-      // Lanes that end on the sky then take the two-instruction miss branch, at every level of the ray tree.
-      K.enclosing = ~0u;
-      memcpy(K.miss_color, s->sky_rgb, sizeof K.miss_color);
-    }
-  };
-  bool four_waves = false;          // (rt_launch::four_waves: set below, once the launch knows whether it is a camera's first frame)
-  auto lds_for = [&](bool strict) {
-    // (the reflection-only many-sphere variants keep only the fold state in LDS: rt_kernel.hip, IMAGE_IN_LDS - and run one-wave
-    // workgroups, rt_device.h, unless they store through the peer-store path)
-    if (!strict && !count && !s->cull_in_lds && !s->refract)
-      return lds_pad + 10u * (rt_one_wave_workgroups(false, count != 0, s->refract, (d_frames != nullptr && !ss2) || four_waves) ? 64u : RT_WG_THREADS) * 8u;
-    if (!strict && rt_one_wave_workgroups(false, count != 0, s->refract, (d_frames != nullptr && !ss2) || four_waves)) return s->lds_bytes + lds_pad + 10u * 64u * 8u;
-    return s->lds_bytes + lds_pad + (!strict ? (s->refract ? 13u : 10u) * RT_WG_THREADS * 8u     // + the product kernels' fold state
-                                             : RT_WG_THREADS * 8u);                              //   (strict: one slot, the scatter store's tile)
-  };
-  bind_kernel(L, strict_main);
-  // the boundary test of the product kernel's samplers (rt_device.h)
-  L.flag_tol = s->flag_tol;
-  bool test_marks = false;               // test build: a switch that changes what is marked or re-traced - nothing is cached then
-#ifdef RT_TESTING
-  if (const char *fs = getenv("RT_FLAG_SCALE")) { L.flag_tol *= atof(fs); test_marks = true; }        // a wider boundary band, to exercise the second launch
-  if (getenv("RT_MARK_ALL") || getenv("RT_EXACT_ALL") || no_fixup) test_marks = true;
-#endif
-  L.mark_flags = (RT_TEST_ENV("RT_MARK_ALL") ? RT_MARK_ALL : 0u) | (no_fixup ? RT_MARK_NEVER : 0u) | (RT_TEST_ENV("RT_TEST_MARK_STRIPES") ? RT_MARK_ZERO : 0u) | (s->unit_weights ? RT_MARK_WEIGHT : 0u);
-  L.marks_cap = RT_MARKS_CAP;
-  L.stars_seed = stars_seed;
-  L.stars_step = (flags & RT_FLAG_STARS_PER_FRAME) ? 1u : 0u;
-  L.textures = s->d_texdesc;
-  L.texel_base = db;
-  L.out = (uint32_t *)d_out;
-  L.counters = D.d_counters;
-  memcpy(L.cam_origin, hd.cam_origin, 12 * sizeof(double));   // origin, axisX, axisY, axisZ are contiguous
-  const launch_geom geom = launch_geometry(hd.fov_deg, w, h, ss, tiles->tile_rows);
-  L.proj_w = geom.proj_w; L.proj_h = geom.proj_h; L.proj_d = geom.proj_d;
-  L.epsilon = hd.epsilon; L.light_intensity = hd.light_intensity;
-  L.n_objects = hd.n_objects; L.n_lights = hd.n_lights; L.segs = hd.segs;
-  L.w = w; L.h = h;
-  L.tile_rows = tiles->tile_rows; L.tile_first = tiles->tile_first; L.tile_stride = tiles->tile_stride; L.n_tiles = tiles->n_tiles;
-  L.tiles_x = geom.tiles_x;
-  memcpy(L.lights, s->lights, sizeof L.lights);
-  L.rb_per_tile = geom.rb_per_tile;
-  L.rb_shift = ~0u;
-  for (uint32_t b = 0; b < 31; b++) if (L.rb_per_tile == (1u << b)) L.rb_shift = b;
-  if ((uint64_t)tiles->n_tiles * L.rb_per_tile > 65535u) return fail(RT_ERR_INVALID, "%u tiles x %u row blocks exceed the grid's y limit (65535)", tiles->n_tiles, L.rb_per_tile);
-  L.n_frames = n_frames;
-  L.frame_stride = frame_stride_bytes / 4u;
-  L.rgb24 = (flags & RT_FLAG_RGB24) ? 1u : 0u;
-  L.compact = compact ? 1u : 0u;
-  L.scatter = d_frames ? 1u : 0u;
-  if (d_frames) for (uint32_t f = 0; f < n_frames; f++) L.out_frames[f] = (uint32_t *)d_frames[f];
-  for (int c = 0; c < 3; c++) L.cam_axis_sum[c] = hd.cam_axis_x[c] + hd.cam_axis_y[c] + hd.cam_axis_z[c];
-  L.ray_bias[0] = 0.5 - L.proj_w; L.ray_bias[1] = L.proj_h - 0.5; L.ray_bias[2] = L.cam_axis_sum[2] * L.proj_d;
-  if (count) HIP_TRY(hipMemsetAsync(D.d_counters, 0, 3 * sizeof(unsigned long long), stream));
-#ifdef RT_TESTING
-  L.probe = g_probe.d_buf; L.probe_x = g_probe.x; L.probe_y = g_probe.y;
-  L.no_uniform = getenv("RT_NO_UNIFORM_BLOCKS") ? 1u : 0u;     // A/B switch, read per call: every wave on the general path (rt_kernel.hip: trace_pixel, UNI)
-  L.uniform_waves = D.d_counters + 3;
-  L.no_cells = getenv("RT_NO_CHECKER_CELLS") ? 1u : 0u;        // A/B switch, read per call: the table's checker cells are ignored (rt_kernel.hip: trace_pixel, one_cell)
-#endif
+  if (c.compact && strict_main) return fail(RT_ERR_UNSUPPORTED, "RT_FLAG_COMPACT: this scene is rendered by the strict kernel (or supersampled 3x3 / 4x4), which knows no launch table: send plain bands");
 
-  event_timer timer;                                     // (a stats call)
-  if (stats) HIP_TRY(timer.start(stream));
-  struct marks_guard {                                   // a per-call mark list is released on every way out, after the stream has drained
-    void *p = nullptr; hipStream_t st = nullptr;
-    ~marks_guard() { if (p) { (void)hipStreamSynchronize(st); (void)hipFree(p); } }
-  } temp_marks;
-  int err = 0;
-  uint32_t marks_read_slot = 0;
-  const uint32_t *marks_read = nullptr;                 // stats: where this launch's mark count can be read afterwards
-  uint64_t centre_items = 0;
-  bool retraced_all = false, overflowed_strict = false;
-  if (strict_main && (flags & RT_FLAG_SKY_ONLY)) {
-    // (the strict kernels know no sky blocks: the RT_FLAG_NO_SKY calls of such a launch store every pixel, this one none)
-  } else if (strict_main) {
+  // ---- 2. the launch record ----
+  rt_launch L;
+  if ((rc = fill_launch(c, strict_main, stars_seed, d_out, frame_stride_bytes, d_frames, L))) return rc;
+  if (c.count) HIP_TRY(hipMemsetAsync(D.d_counters, 0, 3 * sizeof(unsigned long long), stream));
+  if ((rc = clock.start(stats, stream))) return rc;
+
+  // ---- 3. the strict launch, or the product launch and the list-driven strict launch behind it ----
+  marks_guard temp_marks;
+  retrace_result o;
+  // (the strict kernels know no sky blocks: the RT_FLAG_NO_SKY calls of a strict launch store every pixel, its RT_FLAG_SKY_ONLY call none)
+  if (!(strict_main && (flags & RT_FLAG_SKY_ONLY))) {
     std::lock_guard<std::mutex> lk(s->launch_mu);
-    if ((rc = guard_kernel_scratch(D, stream, true, false, s->refract, count, ss2, 0, false, (uint64_t)L.tiles_x * L.n_tiles * L.rb_per_tile * n_frames * (RT_WG_THREADS / 64u),
-                                   "the strict trace kernel"))) return rc;
-    err = rt_launch_trace_strict(&L, s->refract, count, ss2, lds_for(true), stream);
-  } else {
-    // ---- the product launch: its table (found, or built on the GPU for this camera), the trace, and - unless this frame is KNOWN
-    //      to have nothing for it - the list-driven strict launch behind it; one step for the threads of this process ----
-    std::lock_guard<std::mutex> lk(s->launch_mu);
-    const frame_kind kind = {w, h, ss, *tiles, sky_part_of(flags)};
-    const uint32_t uses_before = count ? 0u : count_use(s, kind);
-    // the first frame from a camera that has moved: a caller that moves the camera every frame has the next camera's table built
-    // beside this launch (rt_scene_set_camera), and that build needs the trace's workgroups to be as wide as its own (rt_launch::four_waves)
-    four_waves = !count && uses_before == 0u && s->cam_gen != 0u;
-    L.four_waves = four_waves ? 1u : 0u;
-    const int oi = dispatch_order(s, kind, choose_table(s, flags, uses_before), stream);
-    if (oi < 0) return RT_ERR_DEVICE;
-    rt_scene_dev::order_entry &oe = s->orders[oi];
-    L.order = oe.Tb[s->cam_gen & 1u].entries;
-    // one workgroup per table entry (runs of sky blocks share one).  How many there are is known on the device; until the build's
-    // count has reached the host, one workgroup per BLOCK is launched: those behind the last entry read a zero slot and leave
-    uint32_t n_known = known_value(oe.known, s->cam_gen);
-    // A table that rt_scene_set_camera is rebuilding on the side stream - beside the previous frame's trace - publishes its count
-    // while that trace is still running.  A caller that issues frames back to back arrives here earlier than that: it is given a
-    // short, BOUNDED wait for the word (it is ahead of the GPU anyway, and stays one frame ahead: the trace in flight has tens of
-    // microseconds left when the word arrives); one workgroup per block costs a 4K frame 80 us instead of 68.  A caller that comes
-    // later (a frame per display refresh) finds the word there; a word that does not come in time: one workgroup per block.
-    if (!n_known && oe.built_on == s->side && oe.cam_gen == s->cam_gen) {
-      // (the bound grows with the table: a 4K frame's build takes ~50 us beside a trace, an 8K frame's four times that)
-      static const long wait_env = RT_TEST_ENV("RT_COUNT_WAIT_US") ? atol(RT_TEST_ENV("RT_COUNT_WAIT_US")) : -1;       // A/B switch (test build)
-      const long wait_us = wait_env >= 0 ? wait_env : 100 + (long)(oe.n_blocks / 256u);
-      const auto t0 = std::chrono::steady_clock::now();
-      while (!n_known && std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() < wait_us) {
-        __builtin_ia32_pause();
-        n_known = known_value(oe.known, s->cam_gen);
-      }
-    }
-    L.order_n8 = (oe.n_blocks + 7u) / 8u;
-    L.grid_x = n_known ? n_known - 1u : oe.n_blocks;
-    L.grid_y = 1u;
-    rt_scene_dev::mark_state *ms = nullptr;
-    for (rt_scene_dev::mark_state &m : s->mark_states) if (m.order_index == (uint32_t)oi && m.stream == stream) ms = &m;
-    rt_scene_dev::mark_state temp_state = {~0u, stream, nullptr, nullptr, 0u};
-    if (!ms) {
-      // first launch of this (table, stream) pair: a list of its own (beyond RT_KNOWN_WORDS pairs: one per call, nothing cached)
-      const size_t bytes = 16u + (size_t)RT_MARKS_CAP * 8u;
-      uint32_t *d = nullptr;
-      hipError_t e = hipMalloc((void **)&d, bytes);
-      if (e == hipSuccess) e = hipMemsetAsync(d, 0, 16u, stream);
-      if (e != hipSuccess) { if (d) (void)hipFree(d); return fail(RT_ERR_DEVICE, "mark list: %s", hipGetErrorString(e)); }
-      if (s->mark_states.size() >= RT_KNOWN_WORDS) { temp_marks.p = d; temp_marks.st = stream; temp_state.d_marks = d; ms = &temp_state; }
-      else {
-        s->mark_states.push_back(rt_scene_dev::mark_state{(uint32_t)oi, stream, d, known_word(s, s->mark_states.size()), 0u});
-        ms = &s->mark_states.back();
-      }
-    }
-    L.marks = ms->d_marks; L.marks_slot = ms->slot;
-    const uint32_t known = test_marks ? 0u : known_value(ms->h_known, s->cam_gen);        // 0: not known (yet); else the frame's mark count + 1
-    // A frame KNOWN to mark more samples than the list holds (a legal scene can: every hit of a sphere whose sampler coordinate is
-    // an exact integer everywhere) would be traced twice in full, product kernel then rt_retrace over every sample: the strict
-    // kernel renders it once instead, the same bytes (the count stays known: nothing republishes it for this camera).
-    const bool overflow_known = known != 0u && known - 1u > RT_MARKS_CAP && !count && !compact;
-    if (overflow_known) {
-      if (!(flags & RT_FLAG_SKY_ONLY)) {              // (as every strict launch: a NO_SKY call stores every pixel, a SKY_ONLY call none)
-        rt_launch S = L;
-        S.order = nullptr; S.grid_x = S.grid_y = 0u;
-        bind_kernel(S, true);
-        if ((rc = guard_kernel_scratch(D, stream, true, false, s->refract, 0, ss2, 0, false, (uint64_t)L.tiles_x * L.n_tiles * L.rb_per_tile * n_frames * (RT_WG_THREADS / 64u),
-                                       "the strict trace kernel"))) return rc;
-        err = rt_launch_trace_strict(&S, s->refract, 0, ss2, lds_for(true), stream);
-        overflowed_strict = true;
-      }
-    } else {
-    if ((rc = guard_kernel_scratch(D, stream, false, false, s->refract, count, ss2, !count && !L.cull_in_lds,
-                                   rt_one_wave_workgroups(false, count != 0, s->refract, (L.scatter != 0u && !ss2) || four_waves),
-                                   (uint64_t)L.grid_x * n_frames * (RT_WG_THREADS / 64u), "the trace kernel"))) return rc;
-#ifdef RT_WAVE_LOG
-    // measurement build: RT_WAVE_LOG_FILE=<path> - every wave's entry / exit time and place of THIS launch, written after it has finished
-    unsigned long long *d_wave_log = nullptr;
-    const size_t wave_log_words = (size_t)((L.grid_x + 7u) / 8u * 8u) * n_frames * (RT_WG_THREADS / 64u) * 4u;
-    if (getenv("RT_WAVE_LOG_FILE")) {
-      if (hipMalloc((void **)&d_wave_log, wave_log_words * 8u) == hipSuccess) (void)hipMemsetAsync(d_wave_log, 0, wave_log_words * 8u, stream);
-      L.wave_log = d_wave_log;
-    }
-#endif
-    err = rt_launch_trace_fast(&L, s->refract, count, ss2, lds_for(false), stream);
-#ifdef RT_WAVE_LOG
-    if (d_wave_log) {
-      std::vector<unsigned long long> hostlog(wave_log_words);
-      (void)hipStreamSynchronize(stream);
-      (void)hipMemcpy(hostlog.data(), d_wave_log, wave_log_words * 8u, hipMemcpyDeviceToHost);
-      (void)hipFree(d_wave_log);
-      if (FILE *fp = fopen(getenv("RT_WAVE_LOG_FILE"), "wb")) { fwrite(hostlog.data(), 8u, wave_log_words, fp); fclose(fp); }
-      L.wave_log = nullptr;
-    }
-#endif
-    // Centre row / centre column of a sample grid with an ODD number of rows / columns (supersample 2 makes it even).  The primary
-    // rays there have a direction component that is EXACTLY zero (main.js:186: x - w/2 + 0.5 == 0), so they - and every ray they
-    // spawn that stays in that plane - live in a coordinate plane through the camera, and a sphere centred on that plane (the
-    // reference's own scene has several) is met with a normal component of exactly 0: u or v lands exactly ON a texel / checker
-    // boundary (main.js:127-130, 344-347), and on which side the reference falls is decided by whether ITS OWN rounding noise
-    // (e.g. main.js:257-259 at refract_index 1, where q is 0 or 1e-16 depending on the last bit of cosi) pushed the ray off the
-    // plane.  No arithmetic but the reference's own reproduces such coin flips: rt_retrace traces those samples too.
-    rt_launch F = L;
-    F.order = nullptr; F.grid_x = F.grid_y = 0u;
-    F.centre_row = F.centre_col = ~0u;
-    if (!ss2 && (h & 1u)) {
-      const uint32_t crow = (h - 1u) / 2u, tc = crow / tiles->tile_rows;
-      if (tc >= tiles->tile_first && (tc - tiles->tile_first) % tiles->tile_stride == 0 && (tc - tiles->tile_first) / tiles->tile_stride < tiles->n_tiles) { F.centre_row = crow; centre_items += (uint64_t)w * n_frames; }
-    }
-    if (!ss2 && (w & 1u)) { F.centre_col = (w - 1u) / 2u; centre_items += (uint64_t)tiles->n_tiles * tiles->tile_rows * n_frames; }
-    const bool retrace_all = RT_TEST_ENV("RT_EXACT_ALL") != nullptr && !no_fixup;
-    const bool need = !no_fixup && !(flags & RT_FLAG_SKY_ONLY) && (known != 1u || centre_items != 0 || retrace_all);     // (a sky-only launch traces nothing; the centre lines belong to the calls that trace)
-    if (err == 0 && need) {
-      bind_kernel(F, true);                             // the scene in its own order, every sphere in the loops, the reference's own miss colour
-      if (compact) {                                    // where a sample's block sits in the compact band: from the table's own arrays
-        const rt_table_dev &T = oe.Tb[s->cam_gen & 1u];
-        F.tb_item = T.item; F.tb_rank_in_row = T.rank_in_row; F.tb_row_hist = T.row_hist; F.tb_bin_start = T.bin_start; F.tb_bins = oe.cost_bins;
-      }
-      F.marks_known = test_marks ? nullptr : (unsigned long long *)ms->h_known;
-      F.known_tag = (uint32_t)s->cam_gen;
-      F.retrace_all = retrace_all ? 1u : 0u;
-      retraced_all = retrace_all;
-      // The grid.  Count known: its items and the centre lines.  Not known yet (the first frame from a camera): the list may hold up
-      // to RT_MARKS_CAP items or have overflowed - 256 workgroups (idle ones leave at once) walk an overflowed 3840x2160 frame at
-      // ~130 samples per lane, once; from the next frame on the count is known (and an overflow takes the strict kernel above).
-      uint64_t n_wg = (((known ? known - 1u : 0u) + centre_items) * (ss2 ? 4u : 1u) + RT_WG_THREADS - 1) / RT_WG_THREADS + 2u;      // (supersample 2: a lane per sample)
-      if (!known && n_wg < 256u) n_wg = 256u;
-      if (retrace_all) n_wg = ((uint64_t)tiles->n_tiles * tiles->tile_rows * w * n_frames + RT_WG_THREADS - 1) / RT_WG_THREADS;
-      if (n_wg > 8192u) n_wg = 8192u;
-      if ((rc = guard_kernel_scratch(D, stream, true, true, s->refract, 0, ss2, 0, false, n_wg * (RT_WG_THREADS / 64u), "the list-driven strict launch (rt_retrace)"))) return rc;
-      err = rt_launch_retrace(&F, s->refract, ss2, (unsigned)n_wg, stream);
-      marks_read = ms->d_marks; marks_read_slot = ms->slot;
-      ms->slot ^= 1u;                                   // rt_retrace cleared the other counter: the next launch's
-    }
-    }
+    rc = strict_main ? strict_launch(c, L, c.count) : product_launch(c, L, temp_marks, o);
   }
-  if (err != 0) return fail(RT_ERR_DEVICE, "kernel launch: %s", hipGetErrorString((hipError_t)err));
+  if (rc) return rc;
+
+  // ---- 4. the stats ----
+  if ((rc = clock.finish(stats, stats ? tile_set_pixels(w, h, tiles) * n_frames : 0u))) return rc;
   if (stats) {
-    HIP_TRY(timer.stop(stream));
-    HIP_TRY(hipEventSynchronize(timer.b));
-    float ms = 0.f;
-    HIP_TRY(timer.elapsed(&ms));
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = ms;
-    stats->pixels = tile_set_pixels(w, h, tiles) * n_frames;
-    if (count) {
-      unsigned long long c[3];
-      HIP_TRY(hipMemcpy(c, D.d_counters, sizeof c, hipMemcpyDeviceToHost));
-      stats->rays = c[0]; stats->shadow_rays = c[1]; stats->sphere_tests = c[2];
+    if (c.count) {
+      unsigned long long n[3];
+      HIP_TRY(hipMemcpy(n, D.d_counters, sizeof n, hipMemcpyDeviceToHost));
+      stats->rays = n[0]; stats->shadow_rays = n[1]; stats->sphere_tests = n[2];
     }
     // samples the second launch traced again: the marked ones (read back from the list's counter) and the odd grid's centre lines
-    if (overflowed_strict) stats->exact_samples = stats->pixels;      // the strict kernel rendered the call
-    if (marks_read) {
+    if (o.strict_rendered) stats->exact_samples = stats->pixels;      // the strict kernel rendered the call
+    if (o.marks_read) {
       uint32_t n_marked = 0;
-      HIP_TRY(hipMemcpy(&n_marked, marks_read + marks_read_slot, sizeof n_marked, hipMemcpyDeviceToHost));
-      stats->exact_samples = (n_marked > RT_MARKS_CAP || retraced_all) ? stats->pixels : n_marked + centre_items;   // (list overflow / test build: every pixel of the call)
+      HIP_TRY(hipMemcpy(&n_marked, o.marks_read + o.marks_read_slot, sizeof n_marked, hipMemcpyDeviceToHost));
+      stats->exact_samples = (n_marked > RT_MARKS_CAP || o.retraced_all) ? stats->pixels : n_marked + o.centre_items;   // (list overflow / test build: every pixel of the call)
     }
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    stats->total_ms = clock.host_ms();                  // (with the read-backs)
   }
   return RT_OK;
 }
@@ -541,9 +605,9 @@ __global__ void __launch_bounds__(256) rt_compact_expand_kernel(const rt_expand_
 
 extern "C" int rt_compact_count(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, void *hip_stream, uint32_t *n_blocks, uint32_t *block_bytes) {
   if (!n_blocks || !block_bytes) return fail(RT_ERR_INVALID, "rt_compact_count: NULL argument");
-  int rc = s ? ensure_device(s->device) : RT_ERR_INVALID;
+  hipStream_t stream = nullptr;
+  int rc = s ? scene_stream(s, hip_stream, &stream) : RT_ERR_INVALID;
   if (rc) return rc == RT_ERR_INVALID ? fail(RT_ERR_INVALID, "NULL scene") : rc;
-  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream;
   uint32_t rows_per_wg = 0, header[4];
   const uint32_t *d_header = nullptr;
   {
@@ -561,9 +625,9 @@ extern "C" int rt_compact_count(rt_scene_dev *s, uint32_t w, uint32_t h, const r
 
 extern "C" int rt_compact_expand_device(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, const void *d_compact, void *d_frame, void *hip_stream) {
   if (!d_compact || !d_frame || ((uintptr_t)d_frame & 3u)) return fail(RT_ERR_INVALID, "rt_compact_expand_device: NULL or unaligned buffer");
-  int rc = s ? ensure_device(s->device) : RT_ERR_INVALID;
+  hipStream_t stream = nullptr;
+  int rc = s ? scene_stream(s, hip_stream, &stream) : RT_ERR_INVALID;
   if (rc) return rc == RT_ERR_INVALID ? fail(RT_ERR_INVALID, "NULL scene") : rc;
-  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream;
   rt_expand_launch E;
   uint32_t grid = 0;
   {
@@ -633,32 +697,20 @@ extern "C" int rt_render_hits_device(rt_scene_dev *s, uint32_t w, uint32_t h, co
   if ((rc = check_frame("rt_render_hits_device", w, h, tiles, 0u))) return rc;
   if (((uintptr_t)b->id & 3u) || ((uintptr_t)b->depth & 7u) || ((uintptr_t)b->normal & 3u))
     return fail(RT_ERR_INVALID, "rt_render_hits_device: misaligned buffer (id and normal need 4 bytes, depth 8)");
-  if ((rc = ensure_device(s->device))) return rc;
-  device_state &D = G.dev[s->device];
-  hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : D.stream;
-  const auto t_begin = std::chrono::steady_clock::now();
+  hipStream_t stream = nullptr;
+  if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
+  stats_clock clock;
   rt_hits_launch L;
   if ((rc = hits_bind(s, w, h, L, stream))) return rc;
   L.id = b->id; L.depth = b->depth; L.normal = b->normal;
   L.tile_rows = tiles->tile_rows; L.tile_first = tiles->tile_first; L.tile_stride = tiles->tile_stride;
   L.band_rows = tiles->n_tiles * L.k * tiles->tile_rows;
-  event_timer timer;                                     // (a stats call)
-  if (stats) HIP_TRY(timer.start(stream));
+  if ((rc = clock.start(stats, stream))) return rc;
   if (L.id || L.depth || L.normal) {
     const int e = rt_launch_hits(&L, stream);
     if (e != 0) return fail(RT_ERR_DEVICE, "hits kernel launch: %s", hipGetErrorString((hipError_t)e));
   }
-  if (stats) {
-    HIP_TRY(timer.stop(stream));
-    HIP_TRY(hipEventSynchronize(timer.b));
-    float ms = 0.f;
-    HIP_TRY(timer.elapsed(&ms));
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = ms;
-    stats->pixels = tile_set_pixels(w, h, tiles);
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
-  return RT_OK;
+  return clock.finish(stats, stats ? tile_set_pixels(w, h, tiles) : 0u);
 }
 
 extern "C" int rt_scene_pick(rt_scene_dev *s, uint32_t w, uint32_t h, uint32_t n, const uint32_t *xy, rt_hit *out) {
@@ -684,18 +736,22 @@ extern "C" int rt_scene_pick(rt_scene_dev *s, uint32_t w, uint32_t h, uint32_t n
 
 // ------------------------------------------------------------------------------------ caller-supplied rays (rt_kernel.hip: rt_trace_rays)
 // intersectWorld for a list of rays (include/rt_hip.h: rt_scene_trace_rays_device).  One launch decision: the strict build's
-// rt_trace_rays<refract> for the colours - the scene in its own order, every sphere in the loops, the reference's own miss colour, as
-// rt_retrace is bound; camera, launch tables and flags play no part - and rt_hits.hip's rt_ray_hit_kernel for the hit records.  Both
+// rt_trace_rays<refract> for the colours - the scene in its own order, every sphere in the loops, the reference's own miss colour
+// (bind_scene_order, as rt_retrace is bound); camera, launch tables and flags play no part - and rt_hits.hip's rt_ray_hit_kernel for the hit records.  Both
 // read the scene's current generation, so they come behind its preparation like every other launch of the scene.
 // With an order (rt_scene_trace_rays_ordered_device) the same two kernels take their rays through it: the same launch, one more pointer.
 // The ordering itself (rt_scene_order_rays_device -> rt_rays_order.hip) reads the rays and nothing of the scene: it waits for no edit.
 namespace rt_api {
+// what every list of rays or segments must be, once it is known not to be NULL: its count, and (each check at its own place) its alignment
+int ray_list_count_check(uint64_t n, const char *what) { return (n == 0 || n >= (1ull << 31)) ? fail(RT_ERR_INVALID, "%s: n %llu not in 1..2^31 - 1", what, (unsigned long long)n) : RT_OK; }
+int ray_list_align_check(const double *rays, const char *what) { return ((uintptr_t)rays & 15u) ? fail(RT_ERR_INVALID, "%s: the ray list must be 16-byte aligned", what) : RT_OK; }
+
 int rays_check(uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *out, const char *what) {
   if (!rays || !out) return fail(RT_ERR_INVALID, "%s: NULL rays or outputs", what);
-  if (n == 0 || n >= (1ull << 31)) return fail(RT_ERR_INVALID, "%s: n %llu not in 1..2^31 - 1", what, (unsigned long long)n);
+  if (int rc = ray_list_count_check(n, what)) return rc;
   if (segs > RT_MAX_SEGS) return fail(RT_ERR_INVALID, "%s: segs %u not in 0..%u (0 = the scene's depth)", what, segs, RT_MAX_SEGS);
   if (!out->rgb && !out->rgba && !out->hits) return fail(RT_ERR_INVALID, "%s: every output is NULL", what);
-  if ((uintptr_t)rays & 15u) return fail(RT_ERR_INVALID, "%s: the ray list must be 16-byte aligned", what);
+  if (int rc = ray_list_align_check(rays, what)) return rc;
   if (((uintptr_t)out->rgb & 7u) || ((uintptr_t)out->rgba & 3u) || ((uintptr_t)out->hits & 7u))
     return fail(RT_ERR_INVALID, "%s: misaligned output (rgb and hits need 8 bytes, rgba 4)", what);
   return RT_OK;
@@ -703,8 +759,8 @@ int rays_check(uint64_t n, const double *rays, uint32_t segs, const rt_ray_outpu
 
 int rays_order_check(uint64_t n, const double *rays, const uint32_t *order, const void *work, size_t work_bytes, const char *what) {
   if (!rays || !order || !work) return fail(RT_ERR_INVALID, "%s: NULL rays, order or workspace", what);
-  if (n == 0 || n >= (1ull << 31)) return fail(RT_ERR_INVALID, "%s: n %llu not in 1..2^31 - 1", what, (unsigned long long)n);
-  if ((uintptr_t)rays & 15u) return fail(RT_ERR_INVALID, "%s: the ray list must be 16-byte aligned", what);
+  if (int rc = ray_list_count_check(n, what)) return rc;
+  if (int rc = ray_list_align_check(rays, what)) return rc;
   if (((uintptr_t)order & 3u) || ((uintptr_t)work & 3u)) return fail(RT_ERR_INVALID, "%s: misaligned order or workspace (4 bytes)", what);
   if (work_bytes < rt_rays_order_work_bytes(n))
     return fail(RT_ERR_INVALID, "%s: work_bytes %llu below rt_rays_order_work_bytes(%llu) = %llu", what, (unsigned long long)work_bytes,
@@ -720,8 +776,7 @@ int order_rays_launch(uint32_t n, const double *d_rays, uint32_t *d_order, void 
 
 int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *d_rays, const uint32_t *d_order, uint32_t segs, const rt_ray_outputs &out,
                       hipStream_t stream, rt_stats *stats) {
-  device_state &D = G.dev[s->device];
-  const auto t_begin = std::chrono::steady_clock::now();
+  stats_clock clock;
   const rt_scene_header &hd = s->hd;
   rt_launch L;
   memset(&L, 0, sizeof L);
@@ -730,37 +785,23 @@ int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *
     if (int rc = behind_the_camera(s, stream)) return rc;
     note_launch(s, stream);
     L.stars_seed = hd.stars_seed;                      // (rt_scene_set_stars_seed: this launch's, whatever the next call sets)
-    const uint8_t *ob = obj_block(s);                 // this generation's spheres, in blob order
-    L.objects = (const rt_sphere *)(ob + s->o_objs);
-    L.geom = (const rt_geom *)(ob + s->o_geom);
-    L.lds_image = lds_image_of(s);                    // its materials and texture descriptors, read from HBM
+    bind_scene_order(s, L);                            // (materials and texture descriptors are read from HBM)
   }
   L.textures = s->d_texdesc;
   L.texel_base = (const uint8_t *)s->d_blob;
-  L.n_objects = L.n_loop = hd.n_objects;
-  L.enclosing = ~0u;
-  L.n_lights = hd.n_lights;
+  L.n_objects = hd.n_objects; L.n_lights = hd.n_lights;
   memcpy(L.lights, s->lights, sizeof L.lights);
   L.epsilon = hd.epsilon; L.light_intensity = hd.light_intensity;
-  memcpy(L.miss_color, hd.miss_color, sizeof L.miss_color);
   L.segs = segs ? segs : hd.segs;                      // the CALL's depth
   L.n_frames = 1u;
   L.rays = d_rays; L.ray_rgb = out.rgb; L.ray_rgba = (uint32_t *)out.rgba; L.n_rays = n; L.ray_base = base;
-  event_timer timer;                                     // (a stats call)
-  if (stats) HIP_TRY(timer.start(stream));
+  if (int rc = clock.start(stats, stream)) return rc;
   if (out.rgb || out.rgba) {
     // one work-item per ray; the grid-stride loop takes over beyond 2^20 workgroups
     const uint32_t wgs = (n + RT_WG_THREADS - 1u) / RT_WG_THREADS, n_wg = wgs < (1u << 20) ? wgs : (1u << 20);
-    static std::atomic<long long> scratch_of[2] = {{-1}, {-1}};       // per-lane scratch of the two instantiations, asked once each
-    long long per_lane = scratch_of[s->refract ? 1 : 0].load();
-    if (per_lane < 0) {
-      size_t b = 0;
-      const int e = rt_scratch_trace_rays(s->refract, &b);
-      if (e != 0) return fail(RT_ERR_DEVICE, "hipFuncGetAttributes: %s", hipGetErrorString((hipError_t)e));
-      scratch_of[s->refract ? 1 : 0].store(per_lane = (long long)b);
-    }
-    if (int rc = scratch_guard(D, stream, (size_t)per_lane, (uint64_t)n_wg * (RT_WG_THREADS / 64u), "the ray-list kernel (rt_trace_rays)")) return rc;
-    const int err = rt_launch_trace_rays(&L, d_order, s->refract, n_wg, stream);
+    const rt_trace_variant v = rt_trace_variant_of_rays(s->refract);
+    if (int rc = guard_kernel_scratch(G.dev[s->device], stream, v, (uint64_t)n_wg * (RT_WG_THREADS / 64u), "the ray-list kernel (rt_trace_rays)")) return rc;
+    const int err = launch_variant(L, v, n_wg, d_order, 0u, stream);
     if (err != 0) return fail(RT_ERR_DEVICE, "ray kernel launch: %s", hipGetErrorString((hipError_t)err));
   }
   if (out.hits) {
@@ -773,17 +814,7 @@ int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *
     const int err = rt_launch_ray_hits(&H, stream);
     if (err != 0) return fail(RT_ERR_DEVICE, "ray hit kernel launch: %s", hipGetErrorString((hipError_t)err));
   }
-  if (stats) {
-    HIP_TRY(timer.stop(stream));
-    HIP_TRY(hipEventSynchronize(timer.b));
-    float ms = 0.f;
-    HIP_TRY(timer.elapsed(&ms));
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = ms;
-    stats->pixels = n;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
-  return RT_OK;
+  return clock.finish(stats, n);
 }
 }  // namespace rt_api
 
@@ -792,8 +823,9 @@ extern "C" int rt_scene_trace_rays_device(rt_scene_dev *s, uint64_t n, const dou
   if (!s) return fail(RT_ERR_STATE, "rt_scene_trace_rays_device: NULL scene handle");
   int rc = rays_check(n, d_rays, segs, d_out, "rt_scene_trace_rays_device");
   if (rc) return rc;
-  if ((rc = ensure_device(s->device))) return rc;
-  return trace_rays_launch(s, (uint32_t)n, 0u, d_rays, nullptr, segs, *d_out, hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream, stats);
+  hipStream_t stream = nullptr;
+  if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
+  return trace_rays_launch(s, (uint32_t)n, 0u, d_rays, nullptr, segs, *d_out, stream, stats);
 }
 
 extern "C" size_t rt_rays_order_work_bytes(uint64_t n) { return (n == 0 || n >= (1ull << 31)) ? 0 : rt_order_layout_of(n).bytes; }
@@ -804,8 +836,9 @@ extern "C" int rt_scene_order_rays_device(rt_scene_dev *s, uint64_t n, const dou
   int rc = rays_order_check(n, d_rays, d_order, d_work, work_bytes, "rt_scene_order_rays_device");
   if (rc) return rc;
   if (!s) return fail(RT_ERR_STATE, "rt_scene_order_rays_device: NULL scene handle");
-  if ((rc = ensure_device(s->device))) return rc;
-  return order_rays_launch((uint32_t)n, d_rays, d_order, d_work, hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream);
+  hipStream_t stream = nullptr;
+  if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
+  return order_rays_launch((uint32_t)n, d_rays, d_order, d_work, stream);
 }
 
 extern "C" int rt_scene_trace_rays_ordered_device(rt_scene_dev *s, uint64_t n, const double *d_rays, const uint32_t *d_order, uint32_t segs,
@@ -814,8 +847,9 @@ extern "C" int rt_scene_trace_rays_ordered_device(rt_scene_dev *s, uint64_t n, c
   if (rc) return rc;
   if (!d_order || ((uintptr_t)d_order & 3u)) return fail(RT_ERR_INVALID, "rt_scene_trace_rays_ordered_device: NULL or misaligned order (4 bytes)");
   if (!s) return fail(RT_ERR_STATE, "rt_scene_trace_rays_ordered_device: NULL scene handle");
-  if ((rc = ensure_device(s->device))) return rc;
-  return trace_rays_launch(s, (uint32_t)n, 0u, d_rays, d_order, segs, *d_out, hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream, stats);
+  hipStream_t stream = nullptr;
+  if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
+  return trace_rays_launch(s, (uint32_t)n, 0u, d_rays, d_order, segs, *d_out, stream, stats);
 }
 
 // ------------------------------------------------------------------------------------ occlusion queries (rt_occlusion.hip)
@@ -825,9 +859,9 @@ extern "C" int rt_scene_trace_rays_ordered_device(rt_scene_dev *s, uint64_t n, c
 namespace rt_api {
 int occlusion_check(uint64_t n, const double *rays, const rt_occlusion_inputs *in, const rt_occlusion_outputs *out, const char *what) {
   if (!rays || !out) return fail(RT_ERR_INVALID, "%s: NULL rays or outputs", what);
-  if (n == 0 || n >= (1ull << 31)) return fail(RT_ERR_INVALID, "%s: n %llu not in 1..2^31 - 1", what, (unsigned long long)n);
+  if (int rc = ray_list_count_check(n, what)) return rc;
   if (!out->intensity && !out->blocker) return fail(RT_ERR_INVALID, "%s: every output is NULL", what);
-  if ((uintptr_t)rays & 15u) return fail(RT_ERR_INVALID, "%s: the ray list must be 16-byte aligned", what);
+  if (int rc = ray_list_align_check(rays, what)) return rc;
   if (in && (((uintptr_t)in->length & 7u) || ((uintptr_t)in->intensity & 7u) || ((uintptr_t)in->skip & 3u)))
     return fail(RT_ERR_INVALID, "%s: misaligned input (length and intensity need 8 bytes, skip 4)", what);
   if (((uintptr_t)out->intensity & 7u) || ((uintptr_t)out->blocker & 3u))
@@ -837,7 +871,7 @@ int occlusion_check(uint64_t n, const double *rays, const rt_occlusion_inputs *i
 
 int occlusion_launch(rt_scene_dev *s, uint32_t n, const double *d_rays, const uint32_t *d_order, const rt_occlusion_inputs &in,
                      const rt_occlusion_outputs &out, hipStream_t stream, rt_stats *stats) {
-  const auto t_begin = std::chrono::steady_clock::now();
+  stats_clock clock;
   const rt_scene_header &hd = s->hd;
   rt_occlusion_launch L;
   memset(&L, 0, sizeof L);
@@ -853,21 +887,10 @@ int occlusion_launch(rt_scene_dev *s, uint32_t n, const double *d_rays, const ui
   L.rays = d_rays; L.n_rays = n; L.order = d_order;
   L.length = in.length; L.intensity_in = in.intensity; L.skip = in.skip;
   L.intensity = out.intensity; L.blocker = out.blocker;
-  event_timer timer;                                     // (a stats call)
-  if (stats) HIP_TRY(timer.start(stream));
+  if (int rc = clock.start(stats, stream)) return rc;
   const int err = rt_launch_occlusion(&L, stream);
   if (err != 0) return fail(RT_ERR_DEVICE, "occlusion kernel launch: %s", hipGetErrorString((hipError_t)err));
-  if (stats) {
-    HIP_TRY(timer.stop(stream));
-    HIP_TRY(hipEventSynchronize(timer.b));
-    float ms = 0.f;
-    HIP_TRY(timer.elapsed(&ms));
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = ms;
-    stats->pixels = n;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
-  return RT_OK;
+  return clock.finish(stats, n);
 }
 }  // namespace rt_api
 
@@ -878,7 +901,8 @@ extern "C" int rt_scene_occlusion_device(rt_scene_dev *s, uint64_t n, const doub
   if (rc) return rc;
   if ((uintptr_t)d_order & 3u) return fail(RT_ERR_INVALID, "rt_scene_occlusion_device: misaligned order (4 bytes)");
   if (!s) return fail(RT_ERR_STATE, "rt_scene_occlusion_device: NULL scene handle");
-  if ((rc = ensure_device(s->device))) return rc;
+  hipStream_t stream = nullptr;
+  if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
   const rt_occlusion_inputs none = {nullptr, nullptr, nullptr};
-  return occlusion_launch(s, (uint32_t)n, d_rays, d_order, d_in ? *d_in : none, *d_out, hip_stream ? (hipStream_t)hip_stream : G.dev[s->device].stream, stats);
+  return occlusion_launch(s, (uint32_t)n, d_rays, d_order, d_in ? *d_in : none, *d_out, stream, stats);
 }
