@@ -5,7 +5,8 @@
 //   rt_launch.hip  the launches: colour (the launch record, then the strict launch or the product launch and rt_retrace), supersampling,
 //                  compact bands, primary hits and picking, ray lists, occlusion queries
 //   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick, and the host lists that go
-//                  through device buffers in chunks (rt_trace_rays, rt_occlusion and their binned forms)
+//                  through device buffers in chunks (rt_trace_rays, rt_occlusion and their binned forms, rt_shade_rays), rt_trace_rays_wavefront
+//   rt_nodes_api.hip  the wavefront form's device entry points: one level of nodes, the next level's ray list, the fold (rt_nodes.hip)
 // Which kernel a launch runs is one value (rt_device.h: rt_trace_variant), worked out once per launch; the two builds of rt_kernel.hip map
 // it to a kernel (rt_kernel_trace_fast / rt_kernel_trace_strict), and the declarations below are all the host sees of them.
 #ifndef RT_API_INTERNAL_H
@@ -33,6 +34,7 @@
 #include "rt_objects_gpu.h"
 #include "rt_rays_order.h"
 #include "rt_occlusion.h"
+#include "rt_nodes.h"
 
 // per build of rt_kernel.hip (product, strict): the variant's kernel (NULL: not this build's) and its launch
 extern "C" const void *rt_kernel_trace_fast(rt_trace_variant);
@@ -326,6 +328,15 @@ int order_rays_launch(uint32_t n, const double *d_rays, uint32_t *d_order, void 
 int occlusion_check(uint64_t n, const double *rays, const rt_occlusion_inputs *in, const rt_occlusion_outputs *out, const char *what);
 int occlusion_launch(rt_scene_dev *s, uint32_t n, const double *d_rays, const uint32_t *d_order, const rt_occlusion_inputs &in,
                      const rt_occlusion_outputs &out, hipStream_t stream, rt_stats *stats);
+
+// rt_nodes_api.hip: the wavefront form's argument checks and launches (device pointers): one level of nodes for rays [base, base + n) of
+// a caller's list, the next level's ray list, and the fold of a level
+int shade_check(uint64_t n, const double *rays, const uint32_t *order, const uint32_t *pix, const uint32_t *path, const rt_node *nodes, const char *what);
+int shade_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *d_rays, const uint32_t *d_order, const uint32_t *d_pix, const uint32_t *d_path,
+                 rt_node *d_nodes, hipStream_t stream, rt_stats *stats);
+int spawn_launch(uint32_t n, uint32_t base, const rt_node *d_nodes, const uint32_t *d_pix, const uint32_t *d_path, double *d_child_rays, uint32_t *d_child_pix,
+                 uint32_t *d_child_path, int32_t *d_links, uint32_t *d_count, void *d_work, hipStream_t stream);
+int fold_launch(uint32_t n, const rt_node *d_nodes, const int32_t *d_links, const double *d_child_rgb, double *d_rgb, uint8_t *d_rgba, hipStream_t stream);
 
 // rt_frame.hip: RCCL's communicators are destroyed (rt_shutdown)
 void release_rccl();

@@ -1,5 +1,5 @@
 // rt_frame.hip — rt_render(width, height, scene) and its kin (rt_render_progressive, rt_render_hits, rt_pick; rt_trace_rays, rt_occlusion
-// and their binned forms, which share one chunked list call): the resident scene
+// and their binned forms and rt_shade_rays, which share one chunked list call; rt_trace_rays_wavefront): the resident scene
 // per device (scene_for), the one-GPU plans (banded copy-out, stores straight into a pinned frame) and the single-process multi-GPU
 // frame (interleaved row tiles stored straight into GPU 0's frame over xGMI; fallback: RGB24 bands + one RCCL gather + de-interleave).
 
@@ -352,6 +352,161 @@ extern "C" int rt_trace_rays(const void *blob, size_t bytes, uint64_t n, const d
 extern "C" int rt_trace_rays_binned(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *ho,
                                     rt_stats *stats) {
   return trace_rays_to_host(blob, bytes, n, rays, segs, ho, stats, true, "rt_trace_rays_binned");
+}
+
+// One level of intersectWorld for a list of rays in host memory (rt_nodes.hip: the shade kernel)
+extern "C" int rt_shade_rays(const void *blob, size_t bytes, uint64_t n, const double *rays, const uint32_t *pix, const uint32_t *path, int binned,
+                             rt_node *nodes, rt_stats *stats) {
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  if ((rc = shade_check(n, rays, nullptr, pix, path, nodes, "rt_shade_rays"))) return rc;
+  const list_row rows[4] = {{rays, 6u * sizeof(double), false}, {pix, sizeof(uint32_t), false}, {path, sizeof(uint32_t), false}, {nodes, sizeof(rt_node), true}};
+  return chunked_list_call(blob, bytes, n, rows, 4, binned != 0, stats,
+                           [](rt_scene_dev *s, uint32_t m, uint32_t base, void *const *d, const uint32_t *d_order, hipStream_t stream, rt_stats *st) {
+                             return shade_launch(s, m, base, (const double *)d[0], d_order, (const uint32_t *)d[1], (const uint32_t *)d[2], (rt_node *)d[3], stream, st);
+                           });
+}
+
+// rt_trace_rays through the wavefront form (include/rt_hip.h: rt_trace_rays_wavefront): per chunk of the list, level after level is
+// shaded (rt_nodes.hip) and its children spawned - a level's buffers are sized from the count read back after the spawn that made it -
+// down to the call's depth or an empty level, then the levels are folded back up and level 1's colours copied out.  A chunk keeps the
+// nodes and links of all its levels until the fold: RT_WAVEFRONT_NODES bounds them, a chunk that would exceed it is halved and started
+// again.  Everything else of a level (rays, pix, path, order, workspace, the children's buffers, rgb) lives for that level only.
+#define RT_WAVEFRONT_NODES (1u << 21)
+namespace {
+// the device allocations of one chunk: released one by one as the levels are done with them, and all on every way out
+struct device_pool {
+  std::vector<void *> held;
+  ~device_pool() { for (void *q : held) if (q) (void)hipFree(q); }
+  hipError_t get(void **out, size_t bytes) {
+    *out = nullptr;
+    const hipError_t e = hipMalloc(out, bytes ? bytes : 1u);
+    if (e == hipSuccess) held.push_back(*out);
+    return e;
+  }
+  void release(void *q) {
+    if (!q) return;
+    for (void *&h : held) if (h == q) { (void)hipFree(q); h = nullptr; return; }
+  }
+};
+struct wave_level { rt_node *nodes; int32_t *links; uint32_t count; };
+
+// rays [base, base + m) of the list.  *overflow: the chunk's trees hold more than RT_WAVEFRONT_NODES nodes (and m > 1): nothing was written
+int wavefront_chunk(rt_scene_dev *s, hipStream_t stream, const double *rays, uint64_t base, uint32_t m, uint32_t segs, bool order_levels,
+                    const rt_ray_outputs *ho, bool timed, double *kernel_ms, uint64_t *level_counts, bool *overflow) {
+  device_pool mem;
+  std::vector<wave_level> levels;
+  int rc;
+  *overflow = false;
+  event_timer timer;                                     // one pair of events, used again for every stretch between two host waits
+  if (timed) { HIP_TRY(hipEventCreate(&timer.a)); HIP_TRY(hipEventCreate(&timer.b)); }
+  auto lap_start = [&]() -> hipError_t { return timed ? hipEventRecord(timer.a, stream) : hipSuccess; };
+  auto lap_stop = [&]() -> hipError_t {                  // (the stream has been waited for)
+    if (!timed) return hipSuccess;
+    hipError_t e = hipEventRecord(timer.b, stream);
+    if (e == hipSuccess) e = hipEventSynchronize(timer.b);
+    float ms = 0.f;
+    if (e == hipSuccess) e = timer.elapsed(&ms);
+    *kernel_ms += ms;
+    return e;
+  };
+  void *d_rays = nullptr, *d_pix = nullptr, *d_path = nullptr, *d_count = nullptr;
+  HIP_TRY(mem.get(&d_rays, (size_t)m * 48u));
+  HIP_TRY(mem.get(&d_count, sizeof(uint32_t)));
+  HIP_TRY(hipMemcpyAsync(d_rays, rays + 6u * base, (size_t)m * 48u, hipMemcpyHostToDevice, stream));
+  uint32_t c = m;
+  uint64_t total = 0;
+  for (uint32_t lv = 0; lv < segs && c != 0u; lv++) {
+    const uint32_t pix_base = lv == 0u ? (uint32_t)base : 0u;  // (below the first level pix travels in d_pix)
+    wave_level L = {nullptr, nullptr, c};
+    void *d_order = nullptr, *d_owork = nullptr, *d_swork = nullptr, *d_crays = nullptr, *d_cpix = nullptr, *d_cpath = nullptr;
+    HIP_TRY(mem.get((void **)&L.nodes, (size_t)c * sizeof(rt_node)));
+    levels.push_back(L);
+    total += c;
+    HIP_TRY(lap_start());
+    if (order_levels && lv != 0u) {
+      HIP_TRY(mem.get(&d_order, (size_t)c * sizeof(uint32_t)));
+      HIP_TRY(mem.get(&d_owork, rt_rays_order_work_bytes(c)));
+      if ((rc = order_rays_launch(c, (const double *)d_rays, (uint32_t *)d_order, d_owork, stream))) return rc;
+    }
+    if ((rc = shade_launch(s, c, pix_base, (const double *)d_rays, (const uint32_t *)d_order, (const uint32_t *)d_pix, (const uint32_t *)d_path, L.nodes, stream,
+                           nullptr)))
+      return rc;
+    uint32_t next = 0u;
+    if (lv + 1u < segs) {
+      HIP_TRY(mem.get((void **)&levels.back().links, (size_t)c * 2u * sizeof(int32_t)));
+      HIP_TRY(mem.get(&d_swork, rt_nodes_spawn_work_bytes(c)));
+      HIP_TRY(mem.get(&d_crays, (size_t)c * 2u * 48u));
+      HIP_TRY(mem.get(&d_cpix, (size_t)c * 2u * sizeof(uint32_t)));
+      HIP_TRY(mem.get(&d_cpath, (size_t)c * 2u * sizeof(uint32_t)));
+      if ((rc = spawn_launch(c, pix_base, L.nodes, (const uint32_t *)d_pix, (const uint32_t *)d_path, (double *)d_crays, (uint32_t *)d_cpix, (uint32_t *)d_cpath,
+                             levels.back().links, (uint32_t *)d_count, d_swork, stream)))
+        return rc;
+      HIP_TRY(hipMemcpyAsync(&next, d_count, sizeof next, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(lap_stop());
+    mem.release(d_rays); mem.release(d_pix); mem.release(d_path); mem.release(d_order); mem.release(d_owork); mem.release(d_swork);
+    d_rays = d_crays; d_pix = d_cpix; d_path = d_cpath;
+    if (total + next > RT_WAVEFRONT_NODES && m > 1u) { *overflow = true; return RT_OK; }
+    c = next;
+  }
+  // the fold, from the deepest level up; level 1 writes the call's outputs
+  void *d_child_rgb = nullptr, *d_rgba = nullptr;
+  if (ho->rgba) HIP_TRY(mem.get(&d_rgba, (size_t)m * 4u));
+  HIP_TRY(lap_start());
+  for (size_t lv = levels.size(); lv-- > 0;) {
+    const wave_level &L = levels[lv];
+    void *d_rgb = nullptr;
+    if (lv != 0 || ho->rgb) HIP_TRY(mem.get(&d_rgb, (size_t)L.count * 24u));
+    if ((rc = fold_launch(L.count, L.nodes, lv + 1 < levels.size() ? L.links : nullptr, (const double *)d_child_rgb, (double *)d_rgb,
+                          lv == 0 ? (uint8_t *)d_rgba : nullptr, stream)))
+      return rc;
+    HIP_TRY(hipStreamSynchronize(stream));               // (the level below is released next: hipFree waits anyway)
+    mem.release(d_child_rgb); mem.release(L.nodes); mem.release(L.links);
+    d_child_rgb = d_rgb;
+  }
+  HIP_TRY(lap_stop());
+  if (ho->rgb) HIP_TRY(hipMemcpyAsync(ho->rgb + 3u * base, d_child_rgb, (size_t)m * 24u, hipMemcpyDeviceToHost, stream));
+  if (ho->rgba) HIP_TRY(hipMemcpyAsync(ho->rgba + 4u * base, d_rgba, (size_t)m * 4u, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (level_counts) for (size_t lv = 0; lv < levels.size(); lv++) level_counts[lv] += levels[lv].count;
+  return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_trace_rays_wavefront(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, int order_levels,
+                                       const rt_ray_outputs *ho, rt_stats *stats, uint64_t *level_counts) {
+  const char *what = "rt_trace_rays_wavefront";
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  if ((rc = rays_check(n, rays, segs, ho, what))) return rc;
+  if (ho->hits) return fail(RT_ERR_INVALID, "%s: no hit records (level 1 of rt_scene_shade_rays_device holds them)", what);
+  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
+  std::lock_guard<std::mutex> lk(G.mu);
+  const auto t_begin = std::chrono::steady_clock::now();
+  rt_scene_dev *s = nullptr;
+  if ((rc = scene_for(0, blob, bytes, &s))) return rc;
+  if ((rc = ensure_device(0))) return rc;
+  device_state &D = G.dev[0];
+  const uint32_t depth = segs ? segs : s->hd.segs;
+  if (level_counts) memset(level_counts, 0, RT_MAX_SEGS * sizeof(uint64_t));
+  double kernel_ms = 0.0;
+  uint32_t chunk = n < RT_RAY_CHUNK ? (uint32_t)n : RT_RAY_CHUNK;
+  for (uint64_t base = 0; base < n;) {
+    const uint32_t m = n - base < chunk ? (uint32_t)(n - base) : chunk;
+    bool overflow = false;
+    if ((rc = wavefront_chunk(s, D.stream, rays, base, m, depth, order_levels != 0, ho, stats != nullptr, &kernel_ms, level_counts, &overflow))) return rc;
+    if (overflow) { chunk = m / 2u; continue; }            // (m > 1; a chunk of one ray always fits)
+    base += m;
+  }
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = kernel_ms;
+    stats->pixels = n;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
 }
 
 // The shadow scan for a list of segments in host memory (`binned`: rt_occlusion_binned)

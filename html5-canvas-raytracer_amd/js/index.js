@@ -126,14 +126,48 @@ function tanHalf(projA) { return Math.tan(projA / 2); }
 // (null = a miss).  The scene's camera plays no part.  A ray with a non-finite component is not traced: NaN x 3 / 0, 0, 0, 255 / null.
 // opts.bin: the GPU puts each chunk of 2^18 rays into an order in which neighbours in a wave are neighbours in space before it traces
 // them (rt_trace_rays_binned) - the same results, sooner for a list that is not coherent (scattered probes, collected secondary rays).
+// opts.wavefront: level by level through shade, spawn and fold (rt_trace_rays_wavefront) instead of the one recursive kernel - the same
+// bytes in rgb and rgba, no hits, plus levelCounts (the rays shaded per level); opts.orderLevels bins every level after the first.
 function traceRays(sceneObj, rays, opts) {
   if (!(rays instanceof Float64Array) || rays.length === 0 || rays.length % 6 !== 0) {
     throw new TypeError('traceRays: rays must be a non-empty Float64Array of 6 numbers per ray');
   }
   if (!inited) init(opts && opts.maxDevices);
   const o = opts || {};
-  const r = native().traceRays(new Uint8Array(flattenScene(sceneObj)), rays, o.segs || 0, o.rgb !== false, !!o.rgba, !!o.hits, !!o.bin);
+  if (o.wavefront && (o.hits || o.bin)) throw new TypeError('traceRays: {wavefront: true} returns no hits and takes no {bin: true} (orderLevels bins the later levels)');
+  const r = native().traceRays(new Uint8Array(flattenScene(sceneObj)), rays, o.segs || 0, o.rgb !== false, !!o.rgba, !!o.hits, !!o.bin, !!o.wavefront, !!o.orderLevels);
   if (r.hits) for (const h of r.hits) if (h) h.object = sceneObj.objects[h.index];
+  return r;
+}
+
+// One level of intersectWorld (main.js:216-336 WITHOUT its two recursive calls) for a list of rays: {nodes: ArrayBuffer of 200-byte
+// rt_node records (include/rt_hip.h), count, node(i)}.  opts: pix, path (Uint32Array per ray: the stars sampler's; default i and 1),
+// bin (the GPU orders the list first - the same nodes).  node(i) reads record i: {hit: pick's record or null, sample, diffuse,
+// specular, ambient, reflectWeight, refractWeight, reflectDir, refractDir, children (bit 0 reflect, bit 1 refract)}; the child rays
+// start at hit.point.
+const NODE_BYTES = 200;
+function nodeAt(buf, i, sceneObj) {
+  const d = new DataView(buf, i * NODE_BYTES, NODE_BYTES);
+  const f = (off) => d.getFloat64(off, true), v3 = (off) => [f(off), f(off + 8), f(off + 16)];
+  const index = d.getInt32(0, true);
+  const hit = index < 0 ? null : {index, inside: d.getInt32(4, true) !== 0, t: f(8), point: v3(16), normal: v3(40), u: f(64), v: f(72), object: sceneObj.objects[index]};
+  return {hit, sample: v3(80), diffuse: f(104), specular: f(112), ambient: f(120), reflectWeight: f(128), refractWeight: f(136),
+    reflectDir: v3(144), refractDir: v3(168), children: d.getUint32(192, true)};
+}
+function shadeRays(sceneObj, rays, opts) {
+  if (!(rays instanceof Float64Array) || rays.length === 0 || rays.length % 6 !== 0) {
+    throw new TypeError('shadeRays: rays must be a non-empty Float64Array of 6 numbers per ray');
+  }
+  const o = opts || {}, n = rays.length / 6;
+  for (const name of ['pix', 'path']) {
+    if (o[name] != null && !(o[name] instanceof Uint32Array && o[name].length === n)) throw new TypeError('shadeRays: ' + name + ' must be a Uint32Array of one element per ray');
+  }
+  if (!inited) init(o.maxDevices);
+  const r = native().shadeRays(new Uint8Array(flattenScene(sceneObj)), rays, o.pix || null, o.path || null, !!o.bin);
+  r.node = (i) => {
+    if (!Number.isInteger(i) || i < 0 || i >= r.count) throw new RangeError('node index out of range');
+    return nodeAt(r.nodes, i, sceneObj);
+  };
   return r;
 }
 
@@ -191,4 +225,4 @@ function buildId() { return native().buildId(); }
 
 function shutdown() { if (addon) addon.shutdown(); inited = false; }
 
-module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, primaryRays, normal3D, occlusion, lightSegments, init, shutdown, buildId, flattenScene, scenes, native}, scene);
+module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, shadeRays, primaryRays, normal3D, occlusion, lightSegments, init, shutdown, buildId, flattenScene, scenes, native}, scene);

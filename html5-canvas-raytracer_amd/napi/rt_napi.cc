@@ -12,7 +12,9 @@
 //           pick(blob, w, h, sx, sy) -> {index, inside, t, point, normal, u, v} or null (a miss); sx, sy in sample-grid coordinates
 //           traceRays(blob, rays: Float64Array (6 per ray), segs, wantRgb, wantRgba, wantHits, bin) -> {rgb: Float64Array | null,
 //           rgba: Uint8ClampedArray | null, hits: Array of pick's records (null = a miss) | null}: intersectWorld per ray (rt_trace_rays;
-//           bin: rt_trace_rays_binned, the list ordered on the GPU first - the same results)
+//           bin: rt_trace_rays_binned, the list ordered on the GPU first - the same results; two more booleans, wavefront and
+//           orderLevels: rt_trace_rays_wavefront, the same rgb and rgba level by level, plus levelCounts)
+//           shadeRays(blob, rays, pix: Uint32Array | null, path: Uint32Array | null, bin) -> {nodes: ArrayBuffer of rt_node records, count}
 //           (these three are not enumerable: the enumerable surface is the frame API)
 // Every failure of the library becomes a thrown JS Error carrying rt_last_error().
 //
@@ -418,8 +420,8 @@ napi_value Pick(napi_env env, napi_callback_info info) {
 }
 
 napi_value TraceRays(napi_env env, napi_callback_info info) {
-  size_t argc = 7;
-  napi_value argv[7];
+  size_t argc = 9;
+  napi_value argv[9];
   bool is_ta = false, is_rays = false;
   if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
       napi_is_typedarray(env, argv[1], &is_rays) != napi_ok || !is_rays) {
@@ -440,6 +442,13 @@ napi_value TraceRays(napi_env env, napi_callback_info info) {
   for (size_t i = 0; i < 3 && 3 + i < argc; i++) napi_get_value_bool(env, argv[3 + i], &want[i]);
   bool bin = false;                                     // rt_trace_rays_binned: the GPU orders each chunk before it traces it
   if (argc >= 7) napi_get_value_bool(env, argv[6], &bin);
+  bool wavefront = false, order_levels = false;         // rt_trace_rays_wavefront: level by level through shade, spawn and fold - the same bytes
+  if (argc >= 8) napi_get_value_bool(env, argv[7], &wavefront);
+  if (argc >= 9) napi_get_value_bool(env, argv[8], &order_levels);
+  if (wavefront && (want[2] || bin)) {
+    napi_throw_type_error(env, nullptr, "traceRays: the wavefront form returns no hit records and takes the first level in the list's order");
+    return nullptr;
+  }
   const size_t n = ray_len / 6u;
   // the library wants the blob 8-byte and the rays 16-byte aligned: one aligned copy holds both
   const size_t blob_room = (blob_len + 15) & ~(size_t)15;
@@ -457,10 +466,18 @@ napi_value TraceRays(napi_env env, napi_callback_info info) {
   memcpy(mem + blob_room, ray_data, n * 48u);
   const rt_ray_outputs out = {(double *)p_rgb, (uint8_t *)p_rgba, hits};
   rt_stats st;
-  const int rc = (bin ? rt_trace_rays_binned : rt_trace_rays)(mem, blob_len, n, (const double *)(mem + blob_room), segs, &out, &st);
+  uint64_t level_counts[RT_MAX_SEGS] = {0};
+  const int rc = wavefront ? rt_trace_rays_wavefront(mem, blob_len, n, (const double *)(mem + blob_room), segs, order_levels ? 1 : 0, &out, &st, level_counts)
+                           : (bin ? rt_trace_rays_binned : rt_trace_rays)(mem, blob_len, n, (const double *)(mem + blob_room), segs, &out, &st);
   free(mem);
-  if (rc != RT_OK) { free(hits); return throw_rt(env, bin ? "rt_trace_rays_binned" : "rt_trace_rays", rc); }
+  if (rc != RT_OK) { free(hits); return throw_rt(env, wavefront ? "rt_trace_rays_wavefront" : bin ? "rt_trace_rays_binned" : "rt_trace_rays", rc); }
   napi_create_object(env, &res);
+  if (wavefront) {                                      // the rays shaded per level
+    napi_value lc, c;
+    napi_create_array_with_length(env, RT_MAX_SEGS, &lc);
+    for (uint32_t i = 0; i < RT_MAX_SEGS; i++) { napi_create_double(env, (double)level_counts[i], &c); napi_set_element(env, lc, i, c); }
+    napi_set_named_property(env, res, "levelCounts", lc);
+  }
   if (want[0]) napi_create_typedarray(env, napi_float64_array, 3 * n, ab_rgb, 0, &v); else napi_get_null(env, &v);
   napi_set_named_property(env, res, "rgb", v);
   if (want[1]) napi_create_typedarray(env, napi_uint8_clamped_array, 4 * n, ab_rgba, 0, &v); else napi_get_null(env, &v);
@@ -542,6 +559,63 @@ napi_value Occlusion(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// shadeRays(blob, rays: Float64Array (6 per ray), pix: Uint32Array | null, path: Uint32Array | null, bin) -> {nodes: ArrayBuffer (200 bytes
+//           per ray: rt_node), count, kernel_ms}  (rt_shade_rays: one level of intersectWorld)
+napi_value ShadeRays(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  bool is_ta = false, is_rays = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
+      napi_is_typedarray(env, argv[1], &is_rays) != napi_ok || !is_rays) {
+    napi_throw_type_error(env, nullptr, "shadeRays(blob: Uint8Array, rays: Float64Array[, pix, path, bin])");
+    return nullptr;
+  }
+  napi_typedarray_type bt, rt; napi_value ab; size_t off, blob_len = 0, ray_len = 0;
+  void *blob_data = nullptr, *ray_data = nullptr;
+  napi_get_typedarray_info(env, argv[0], &bt, &blob_len, &blob_data, &ab, &off);
+  napi_get_typedarray_info(env, argv[1], &rt, &ray_len, &ray_data, &ab, &off);
+  if ((bt != napi_uint8_array && bt != napi_uint8_clamped_array) || rt != napi_float64_array || ray_len == 0 || ray_len % 6u != 0) {
+    napi_throw_type_error(env, nullptr, "shadeRays: the blob must be a Uint8Array and the rays a non-empty Float64Array of 6 numbers per ray");
+    return nullptr;
+  }
+  const size_t n = ray_len / 6u;
+  void *in_data[2] = {nullptr, nullptr};                // pix, path: null / undefined = the library's default
+  for (size_t i = 0; i < 2 && 2 + i < argc; i++) {
+    napi_valuetype vt;
+    napi_typeof(env, argv[2 + i], &vt);
+    if (vt == napi_null || vt == napi_undefined) continue;
+    bool ta = false; napi_typedarray_type kt; size_t len = 0;
+    if (napi_is_typedarray(env, argv[2 + i], &ta) != napi_ok || !ta || napi_get_typedarray_info(env, argv[2 + i], &kt, &len, &in_data[i], &ab, &off) != napi_ok ||
+        kt != napi_uint32_array || len != n) {
+      napi_throw_type_error(env, nullptr, "shadeRays: pix and path are Uint32Arrays of one element per ray, or null");
+      return nullptr;
+    }
+  }
+  bool bin = false;
+  if (argc >= 5) napi_get_value_bool(env, argv[4], &bin);
+  const size_t blob_room = (blob_len + 15) & ~(size_t)15;
+  uint8_t *mem = (uint8_t *)aligned_alloc(16, blob_room + ((n * 48u + 15) & ~(size_t)15));
+  napi_value ab_nodes = nullptr, res, v;
+  void *p_nodes = nullptr;
+  if (!mem || napi_create_arraybuffer(env, n * sizeof(rt_node), &p_nodes, &ab_nodes) != napi_ok) {
+    free(mem);
+    napi_throw_error(env, nullptr, "shadeRays: out of memory");
+    return nullptr;
+  }
+  memcpy(mem, blob_data, blob_len);
+  memcpy(mem + blob_room, ray_data, n * 48u);
+  rt_stats st;
+  const int rc = rt_shade_rays(mem, blob_len, n, (const double *)(mem + blob_room), (const uint32_t *)in_data[0], (const uint32_t *)in_data[1], bin ? 1 : 0,
+                               (rt_node *)p_nodes, &st);
+  free(mem);
+  if (rc != RT_OK) return throw_rt(env, "rt_shade_rays", rc);
+  napi_create_object(env, &res);
+  napi_set_named_property(env, res, "nodes", ab_nodes);
+  napi_create_double(env, (double)n, &v); napi_set_named_property(env, res, "count", v);
+  napi_create_double(env, st.kernel_ms, &v); napi_set_named_property(env, res, "kernel_ms", v);
+  return res;
+}
+
 napi_value Module(napi_env env, napi_value exports) {
   const napi_property_descriptor props[] = {
       {"init", nullptr, Init, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
@@ -556,6 +630,7 @@ napi_value Module(napi_env env, napi_value exports) {
       {"pick", nullptr, Pick, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"traceRays", nullptr, TraceRays, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"occlusion", nullptr, Occlusion, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"shadeRays", nullptr, ShadeRays, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

@@ -263,7 +263,23 @@ ABI = {
     "rt_occlusion": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.POINTER(RtOcclusionInputs), C.POINTER(RtOcclusionOutputs), C.POINTER(RtStats)]),
     "rt_occlusion_binned": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.POINTER(RtOcclusionInputs), C.POINTER(RtOcclusionOutputs),
                                       C.POINTER(RtStats)]),
+    "rt_scene_shade_rays_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(RtStats)]),
+    "rt_shade_rays": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_nodes_spawn_work_bytes": (C.c_size_t, [C.c_uint64]),
+    "rt_scene_spawn_rays_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rt_scene_fold_nodes_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_trace_rays_wavefront": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(RtRayOutputs), C.POINTER(RtStats),
+                                          C.POINTER(C.c_uint64)]),
 }
+
+RT_MAX_SEGS = 16
+
+# include/rt_hip.h rt_node (200 bytes) as numpy fields, in the header's order; NODE_DTYPE (below) is the structured dtype
+NODE_FIELDS = [("object", "<i4"), ("inside", "<i4"), ("t", "<f8"), ("point", "<f8", (3,)), ("normal", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"),
+               ("sample", "<f8", (3,)), ("diffuse", "<f8"), ("specular", "<f8"), ("ambient", "<f8"), ("reflect_weight", "<f8"),
+               ("refract_weight", "<f8"), ("reflect_dir", "<f8", (3,)), ("refract_dir", "<f8", (3,)), ("children", "<u4"), ("reserved", "<u4")]
 
 
 class RtError(RuntimeError):
@@ -456,6 +472,36 @@ class Renderer:
         _check(self.lib, rc, "rt_scene_occlusion_device")
         return st
 
+    def shade_rays(self, n, rays_ptr, nodes_ptr, order_ptr=0, pix_ptr=0, path_ptr=0, stream=None, want_stats=False):
+        """One level of intersectWorld (main.js:216-336 without its two recursive calls) for n rays in DEVICE memory: node i (NODE_DTYPE,
+        200 bytes, 8-byte aligned) per ray i into nodes_ptr (DEVICE).  order_ptr as trace_rays_ordered takes it; pix_ptr / path_ptr: n uint32
+        each (DEVICE), the stars sampler's pix and path per ray, 0 / None = i and 1."""
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_shade_rays_device(self.handle, n, C.c_void_p(rays_ptr or 0), C.c_void_p(order_ptr or 0), C.c_void_p(pix_ptr or 0),
+                                                 C.c_void_p(path_ptr or 0), C.c_void_p(nodes_ptr or 0), C.c_void_p(stream or 0),
+                                                 C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_shade_rays_device")
+        return st
+
+    def spawn_rays(self, n, nodes_ptr, child_rays_ptr, links_ptr, count_ptr, work_ptr, work_bytes, pix_ptr=0, path_ptr=0, child_pix_ptr=0,
+                   child_path_ptr=0, stream=None):
+        """The children of n nodes (DEVICE) as the next level's ray list: child_rays_ptr (2n x 6 float64), child_pix_ptr / child_path_ptr
+        (2n uint32 each, 0 = not wanted), links_ptr (2n int32: per parent its reflect and refract child's index, or -1), count_ptr (one
+        uint32), all DEVICE; stable, by parent, reflect before refract.  work_ptr: work_bytes >= nodes_spawn_work_bytes(n) of device
+        workspace.  Asynchronous, no host wait."""
+        rc = self.lib.rt_scene_spawn_rays_device(self.handle, n, C.c_void_p(nodes_ptr or 0), C.c_void_p(pix_ptr or 0), C.c_void_p(path_ptr or 0),
+                                                 C.c_void_p(child_rays_ptr or 0), C.c_void_p(child_pix_ptr or 0), C.c_void_p(child_path_ptr or 0),
+                                                 C.c_void_p(links_ptr or 0), C.c_void_p(count_ptr or 0), C.c_void_p(work_ptr or 0), work_bytes,
+                                                 C.c_void_p(stream or 0))
+        _check(self.lib, rc, "rt_scene_spawn_rays_device")
+
+    def fold_nodes(self, n, nodes_ptr, links_ptr, child_rgb_ptr, rgb_ptr, rgba_ptr, stream=None):
+        """main.js:322-336 for n nodes (DEVICE): the children's colours (child_rgb_ptr, 3 float64 each) gathered through links_ptr (0 = the
+        deepest level: every child is [0, 0, 0]) into rgb_ptr (3 float64 per node) and / or rgba_ptr (4 uint8), DEVICE, 0 = not wanted."""
+        rc = self.lib.rt_scene_fold_nodes_device(self.handle, n, C.c_void_p(nodes_ptr or 0), C.c_void_p(links_ptr or 0), C.c_void_p(child_rgb_ptr or 0),
+                                                 C.c_void_p(rgb_ptr or 0), C.c_void_p(rgba_ptr or 0), C.c_void_p(stream or 0))
+        _check(self.lib, rc, "rt_scene_fold_nodes_device")
+
     def close(self):
         if self.handle:
             self.lib.rt_scene_free(self.handle)
@@ -596,21 +642,29 @@ def rays_order_work_bytes(n, lib=None):
     return int((lib or load_library()).rt_rays_order_work_bytes(n))
 
 
-def trace_rays(scene, rays, segs=0, want=("rgb",), lib=None, order="list"):
+def trace_rays(scene, rays, segs=0, want=("rgb",), lib=None, order="list", method="recursive", order_levels=False):
     """trace_rays(scene, rays) -> {"rgb": (n, 3) float64, "rgba": (n, 4) uint8, "hits": [hit dict or None per ray]} (the keys named in
     `want`): intersectWorld(segs, objects, org, dir) per row {org, dir} of the float64 (n, 6) array `rays`, directions as given, on
     GPU 0 with rt_render's resident scene.  segs 0 = the scene's depth.  A ray with a non-finite component is not traced: NaN, NaN,
     NaN / 0, 0, 0, 255 / None.  order: "list" traces the rays in the list's order; "binned" (rt_trace_rays_binned) has the GPU put
     each chunk of 2^18 rays into an order in which neighbours are neighbours in space first - the same results, sooner for a list
-    that is not coherent."""
+    that is not coherent.  method: "recursive" (the one kernel that runs the whole ray tree), or "wavefront" (rt_trace_rays_wavefront:
+    level by level through shade, spawn and fold - the same bytes in rgb and rgba; no hits; order "list" only; order_levels=True bins
+    every level after the first before it is shaded; `want` may name "level_counts": uint64[16], the rays shaded per level)."""
     import numpy as np
     if order not in ("list", "binned"):
         raise ValueError("order is 'list' or 'binned'")
+    if method not in ("recursive", "wavefront"):
+        raise ValueError("method is 'recursive' or 'wavefront'")
+    wavefront = method == "wavefront"
+    if wavefront and order != "list":
+        raise ValueError("method 'wavefront' takes the first level in the list's order (order_levels bins the others)")
     lib = lib or load_library()
     blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
     want = set(want)
-    if not want or want - {"rgb", "rgba", "hits"}:
-        raise ValueError("want names some of 'rgb', 'rgba', 'hits'")
+    allowed = {"rgb", "rgba", "level_counts"} if wavefront else {"rgb", "rgba", "hits"}
+    if not (want - {"level_counts"}) or want - allowed:
+        raise ValueError("want names some of %s" % ", ".join(repr(k) for k in sorted(allowed)))
     rays = np.asarray(rays, np.float64)
     if rays.ndim != 2 or rays.shape[1] != 6:
         raise ValueError("rays must be an (n, 6) array: org[3], dir[3] per row")
@@ -628,6 +682,14 @@ def trace_rays(scene, rays, segs=0, want=("rgb",), lib=None, order="list"):
                         C.addressof(records) if records is not None else None)
     _init_once(lib)
     buf = C.create_string_buffer(blob, len(blob))
+    if wavefront:
+        counts = np.zeros(RT_MAX_SEGS, np.uint64)
+        rc = lib.rt_trace_rays_wavefront(buf, len(blob), n, C.c_void_p(aligned.ctypes.data), segs, 1 if order_levels else 0, C.byref(bufs), None,
+                                         counts.ctypes.data_as(C.POINTER(C.c_uint64)))
+        _check(lib, rc, "rt_trace_rays_wavefront")
+        if "level_counts" in want:
+            out["level_counts"] = counts
+        return out
     call, what = (lib.rt_trace_rays, "rt_trace_rays") if order == "list" else (lib.rt_trace_rays_binned, "rt_trace_rays_binned")
     _check(lib, call(buf, len(blob), n, C.c_void_p(aligned.ctypes.data), segs, C.byref(bufs), None), what)
     if records is not None:
@@ -747,3 +809,87 @@ def light_intensity_at(scene, points, facing, skip, lib=None, order="list"):
                         want=("intensity",), lib=lib, order=order)
         li[m] = got["intensity"]
     return li
+
+
+# --------------------------------------------------------------------------- wavefront ray lists (include/rt_hip.h: rt_node)
+def _node_dtype():
+    import numpy as np
+    return np.dtype(NODE_FIELDS)
+
+
+def __getattr__(name):                                   # NODE_DTYPE: built on first use, so that importing this module does not need numpy
+    if name == "NODE_DTYPE":
+        return _node_dtype()
+    raise AttributeError(name)
+
+
+def nodes_spawn_work_bytes(n, lib=None):
+    """Bytes of device workspace Renderer.spawn_rays needs for n nodes (host arithmetic; 0 for n == 0 and n >= 2^31)."""
+    return int((lib or load_library()).rt_nodes_spawn_work_bytes(n))
+
+
+def shade_rays(scene, rays, pix=None, path=None, order="list", lib=None):
+    """shade_rays(scene, rays) -> structured array (NODE_DTYPE), node i for row i {org, dir} of the float64 (n, 6) array `rays`: one level
+    of intersectWorld (main.js:216-336 without its two recursive calls), directions as given, on GPU 0 with rt_render's resident scene.
+    pix / path: n uint32 each, the stars sampler's pix and path per ray (None: i and 1).  order: "list", or "binned" (the GPU orders each
+    chunk of 2^18 rays first - the same nodes)."""
+    import numpy as np
+    if order not in ("list", "binned"):
+        raise ValueError("order is 'list' or 'binned'")
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    rays = np.asarray(rays)
+    if rays.dtype.kind not in "fiu" or rays.ndim != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
+        raise ValueError("rays must be a non-empty (n, 6) array: org[3], dir[3] per row")
+    n = rays.shape[0]
+    aligned = np.empty(n * 6 + 2, np.float64)             # a contiguous copy on a 16-byte boundary
+    aligned = aligned[(aligned.ctypes.data >> 3) & 1:][:n * 6]
+    aligned[:] = rays.reshape(-1)
+    extra = {}
+    for name, a in (("pix", pix), ("path", path)):
+        if a is not None:
+            a = np.asarray(a)
+            if a.dtype.kind not in "iu" or a.shape != (n,) or (a.size and (int(a.min()) < 0 or int(a.max()) >= 2 ** 32)):
+                raise ValueError("%s must be n integers in [0, 2^32)" % name)
+            extra[name] = np.ascontiguousarray(a.astype(np.uint32))
+    nodes = np.zeros(n, _node_dtype())
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    rc = lib.rt_shade_rays(buf, len(blob), n, C.c_void_p(aligned.ctypes.data), C.c_void_p(extra["pix"].ctypes.data if "pix" in extra else 0),
+                           C.c_void_p(extra["path"].ctypes.data if "path" in extra else 0), 1 if order == "binned" else 0, C.c_void_p(nodes.ctypes.data), None)
+    _check(lib, rc, "rt_shade_rays")
+    return nodes
+
+
+def _jsmin(a, b):
+    import numpy as np
+    return np.where(np.isnan(a) | np.isnan(b), np.nan, np.where(a < b, a, b))
+
+
+def _jsmax(a, b):
+    import numpy as np
+    return np.where(np.isnan(a) | np.isnan(b), np.nan, np.where(a > b, a, b))
+
+
+def fold_nodes_host(nodes, links, child_rgb):
+    """The fold of Renderer.fold_nodes in numpy, operation for operation (main.js:322-336): nodes (NODE_DTYPE, n), links ((n, 2) int32,
+    or None = the deepest level), child_rgb ((m, 3) float64) -> (n, 3) float64.  A miss keeps its sample; otherwise per channel
+    max(sample * ambient, min(1, sample * diffuse + sample * specular + re + rf)), the terms added left to right, re / rf the linked
+    child's colour times reflect_weight / refract_weight or +0.0, Math.min / Math.max with JavaScript's NaN rule."""
+    import numpy as np
+    nodes = np.asarray(nodes)
+    n = nodes.shape[0]
+    s = nodes["sample"].astype(np.float64)
+    re, rf = np.zeros((n, 3)), np.zeros((n, 3))
+    if links is not None:
+        links = np.asarray(links).reshape(n, 2)
+        child_rgb = np.asarray(child_rgb, np.float64).reshape(-1, 3)
+        for k, (dst, w) in enumerate(((re, nodes["reflect_weight"]), (rf, nodes["refract_weight"]))):
+            m = links[:, k] >= 0
+            dst[m] = child_rgb[links[m, k]] * w[m, None]
+    with np.errstate(invalid="ignore", over="ignore"):
+        shade = s * nodes["diffuse"][:, None] + s * nodes["specular"][:, None] + re + rf
+        out = _jsmax(s * nodes["ambient"][:, None], _jsmin(np.float64(1.0), shade))
+    miss = nodes["object"] < 0
+    out[miss] = s[miss]
+    return out

@@ -13,7 +13,7 @@
  * of the calling thread's last call.
  *
  * Threads: rt_init, rt_shutdown and rt_render serialise on an internal lock.  The device entry points
- * (rt_scene_upload, rt_render_tiles_device, rt_render_batch_device, rt_scene_trace_rays_device, rt_scene_order_rays_device, rt_scene_occlusion_device, rt_deinterleave_*) may be called from several
+ * (rt_scene_upload, rt_render_tiles_device, rt_render_batch_device, rt_scene_trace_rays_device, rt_scene_order_rays_device, rt_scene_occlusion_device, rt_scene_shade_rays_device, rt_scene_spawn_rays_device, rt_scene_fold_nodes_device, rt_deinterleave_*) may be called from several
  * threads at once; work on one HIP stream is ordered by the stream.  Launches with RT_FLAG_COUNT share one counter
  * buffer per device: one at a time per device.
  *
@@ -560,6 +560,84 @@ int rt_occlusion(const void *scene_blob, size_t blob_bytes, uint64_t n, const do
  * rt_trace_rays_binned does; stats->kernel_ms includes the orderings.  The same bytes as rt_occlusion in both outputs. */
 int rt_occlusion_binned(const void *scene_blob, size_t blob_bytes, uint64_t n, const double *rays,
                         const rt_occlusion_inputs *host_in, const rt_occlusion_outputs *host_out, rt_stats *stats);
+
+/* Wavefront tracing of ray lists: ONE level of intersectWorld per call.  rt_scene_trace_rays_device runs the reference's recursion
+ * (main.js:268-278) inside one kernel; these entry points open it: a node per ray (what intersectWorld computes WITHOUT its two
+ * recursive calls), the child rays the nodes spawn as the next level's ray list, and the fold that puts the colours of a level's
+ * children back into their parents (main.js:322-336).  A caller can put their own shading on the reference's geometry, look at bounce k
+ * alone, keep per-bounce buffers, or bin each level (rt_scene_order_rays_device) before it is shaded.  Shading level 1, spawning,
+ * shading again down to `segs` levels (or an empty level) and folding back up gives the rgb of rt_scene_trace_rays_device bit for bit.
+ *
+ * The arithmetic is the strict one (no FMA contraction, correctly rounded sqrt and division, fdlibm atan2 / asin, the strict build's
+ * pow); spheres in blob order, strict <, first wins; the shadow scan is rt_scene_occlusion_device's loop per light with ONE intensity
+ * carried from light to light (q2).  It reads the resident scene's current spheres, lights, light_intensity, epsilon, miss_color,
+ * textures and stars seed; the camera, launch tables and RT_FLAG_* play no part.
+ * A ray with a non-finite component is not traced: the miss record, sample = NaN x 3, children = 0, every other double 0. */
+typedef struct rt_node {        /* intersectWorld(segs >= 1, objs, org, dir) WITHOUT its two recursive calls */
+  rt_hit  hit;                  /* exactly the record `hits` of rt_scene_trace_rays_device holds for this ray */
+  double  sample[3];            /* hit.m.sampler(hit), main.js:320;   a miss: miss_color (main.js:231) */
+  double  diffuse, specular;    /* diffuse_intensity, specular_intensity AFTER main.js:316-317; 0 when neither albedo[1] nor [2] > 0, or a miss */
+  double  ambient, reflect_weight, refract_weight;   /* albedo[0], albedo[3], albedo[4] of the hit sphere; a miss: 0 */
+  double  reflect_dir[3];       /* the direction handed to the first recursive call (main.js:236-238, normalised); 0,0,0 when reflect_len == 0 */
+  double  refract_dir[3];       /* the same for main.js:243-265, total internal reflection included */
+  uint32_t children;            /* bit 0: reflect_len != 0, bit 1: refract_len != 0 - whatever the depth left */
+  uint32_t reserved;            /* 0 */
+} rt_node;                      /* 200 bytes; the child rays' origin is hit.point */
+
+/* One level: node i of ray i into d_nodes[i] (DEVICE memory, 8-byte aligned, n records).  d_rays and d_order as for
+ * rt_scene_trace_rays_ordered_device (d_order NULL or an order; an entry >= n is skipped and nothing is written for it).  d_pix and
+ * d_path (uint32 per ray, 4-byte aligned, or NULL) are the stars sampler's pix and path of ray i; NULL means pix = i and path = 1, so a
+ * root list behaves as rt_scene_trace_rays_device does.  Stream, thread, stats and pending-edit rules are rt_scene_occlusion_device's.
+ * RT_ERR_INVALID, before a device is touched: n outside 1..2^31 - 1, NULL or misaligned d_rays (16 bytes), NULL or misaligned
+ * d_nodes (8 bytes), misaligned d_order, d_pix or d_path (4 bytes); then RT_ERR_STATE: a NULL scene.
+ * One work-item per ray; the kernel keeps no stack and uses no scratch memory. */
+int rt_scene_shade_rays_device(rt_scene_dev *scene, uint64_t n, const double *d_rays, const uint32_t *d_order, const uint32_t *d_pix,
+                               const uint32_t *d_path, rt_node *d_nodes, void *hip_stream, rt_stats *stats);
+
+/* Host form of one level: rt_render's resident scene, every array in HOST memory (pix and path may be NULL: i and 1), the list's own
+ * order or (binned != 0) each chunk ordered on the GPU first - the same nodes; synchronous, on GPU 0, in chunks of 2^18 rays like
+ * rt_trace_rays (ray i keeps pix = i without d_pix).  host_nodes: n records, 8-byte aligned. */
+int rt_shade_rays(const void *scene_blob, size_t blob_bytes, uint64_t n, const double *rays, const uint32_t *pix, const uint32_t *path,
+                  int binned, rt_node *host_nodes, rt_stats *stats);
+
+/* The bytes of DEVICE workspace rt_scene_spawn_rays_device needs for n nodes; host arithmetic.  0 for n == 0 and n >= 2^31;
+ * non-decreasing in n (4 bytes per 256 nodes). */
+size_t rt_nodes_spawn_work_bytes(uint64_t n);
+
+/* Compacts the children of n nodes into the next level's ray list, in a stable order: by parent index, reflect before refract (the
+ * reference's recursion order).  Child c: d_child_rays[c] = {hit.point, dir}, d_child_pix[c] = the parent's pix, d_child_path[c] =
+ * 2p (reflect) or 2p + 1 (refract) for the parent's path p (d_pix / d_path NULL: i and 1, as above).  Parent i: d_links[2i] and
+ * d_links[2i + 1] (int32) = the index of its reflect / refract child in the new list, or -1.  *d_count (a device uint32) = the number
+ * of children.  The child buffers hold 2n entries; d_child_pix and d_child_path may be NULL.  No allocation and no host wait: the scan
+ * lives in d_work (work_bytes >= rt_nodes_spawn_work_bytes(n), 4-byte aligned).  Reads nothing of the scene: `scene` names the device
+ * and its default stream.  RT_ERR_INVALID, before a device is touched: n outside 1..2^31 - 1, a NULL d_nodes, d_child_rays, d_links,
+ * d_count or d_work, misaligned pointers (nodes 8, child rays 16, the others 4), work_bytes too small; then RT_ERR_STATE: a NULL scene. */
+int rt_scene_spawn_rays_device(rt_scene_dev *scene, uint64_t n, const rt_node *d_nodes, const uint32_t *d_pix, const uint32_t *d_path,
+                               double *d_child_rays, uint32_t *d_child_pix, uint32_t *d_child_path, int32_t *d_links, uint32_t *d_count,
+                               void *d_work, size_t work_bytes, void *hip_stream);
+
+/* main.js:322-336 for node i: a miss gives rgb = sample; otherwise per channel
+ *     max(sample * ambient, min(1, sample * diffuse + sample * specular + re + rf))
+ * with re = d_child_rgb[3 * link] * reflect_weight when d_links[2i] >= 0, else +0.0, rf the same through d_links[2i + 1] and
+ * refract_weight; the four terms added left to right; Math.min / Math.max with JavaScript's NaN rule.  d_links == NULL marks the
+ * deepest level: every child is intersectWorld(0, ...) = [0,0,0].  d_rgb (3 doubles per node, 8-byte aligned) and d_rgba (the store
+ * rule of main.js:195-198, alpha 255, 4-byte aligned): either may be NULL, not both.  Reads nothing of the scene.  RT_ERR_INVALID,
+ * before a device is touched: n outside 1..2^31 - 1, NULL or misaligned d_nodes, both outputs NULL, d_links without d_child_rgb,
+ * misaligned pointers; then RT_ERR_STATE: a NULL scene. */
+int rt_scene_fold_nodes_device(rt_scene_dev *scene, uint64_t n, const rt_node *d_nodes, const int32_t *d_links, const double *d_child_rgb,
+                               double *d_rgb, uint8_t *d_rgba, void *hip_stream);
+
+/* Host form: rt_trace_rays' rgb and rgba through the wavefront loop, on rt_render's resident scene, synchronous, on GPU 0: level 1 is
+ * shaded, its children spawned and shaded, down to `segs` levels (0 = the scene's depth) or an empty level, then the levels are folded
+ * back up.  order_levels != 0: every level after the first goes through rt_scene_order_rays_device before it is shaded.  The list is
+ * processed in chunks of at most 2^18 rays (ray i keeps pix = i); a level's buffers are sized from the count read back after the
+ * spawn that made it, and the nodes of all levels of a chunk together are held to 2^21: a chunk whose trees would exceed that is
+ * halved and started again (one ray's tree has at most 2^16 - 1 nodes), so the device memory of a call stays below 2^21 x 400 bytes
+ * (node and links of every level, and the transient ray, pix, path, order, child and rgb records of one) = 800 MiB, whatever n.
+ * level_counts (uint64[RT_MAX_SEGS], or NULL): the rays shaded at each level, summed over the chunks.  host_out->hits must be NULL.
+ * The bytes are rt_trace_rays' in both outputs, for every list. */
+int rt_trace_rays_wavefront(const void *scene_blob, size_t blob_bytes, uint64_t n, const double *rays, uint32_t segs, int order_levels,
+                            const rt_ray_outputs *host_out, rt_stats *stats, uint64_t *level_counts);
 
 #ifdef __cplusplus
 }
