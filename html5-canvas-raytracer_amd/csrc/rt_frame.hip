@@ -493,7 +493,17 @@ extern "C" int rt_trace_rays_wavefront(const void *blob, size_t bytes, uint64_t 
   if (level_counts) memset(level_counts, 0, RT_MAX_SEGS * sizeof(uint64_t));
   double kernel_ms = 0.0;
   uint32_t chunk = n < RT_RAY_CHUNK ? (uint32_t)n : RT_RAY_CHUNK;
-  for (uint64_t base = 0; base < n;) {
+  if (depth == 0u) {
+    // intersectWorld(0, ...) is [0,0,0] (main.js:221): no level is shaded, so there is nothing to fold and nothing to launch.  What is
+    // left of rt_trace_rays is its guard: a ray with a non-finite component gives NaN x 3, which the store rule makes 0, 0, 0, 255 too
+    for (uint64_t i = 0; i < n; i++) {
+      const double *q = rays + 6u * i;
+      const bool finite = (q[0] - q[0]) + (q[1] - q[1]) + (q[2] - q[2]) + (q[3] - q[3]) + (q[4] - q[4]) + (q[5] - q[5]) == 0.0;
+      if (ho->rgb) ho->rgb[3u * i] = ho->rgb[3u * i + 1u] = ho->rgb[3u * i + 2u] = finite ? 0.0 : __builtin_nan("");
+      if (ho->rgba) { uint8_t *o = ho->rgba + 4u * i; o[0] = o[1] = o[2] = 0u; o[3] = 255u; }
+    }
+  }
+  for (uint64_t base = 0; depth != 0u && base < n;) {
     const uint32_t m = n - base < chunk ? (uint32_t)(n - base) : chunk;
     bool overflow = false;
     if ((rc = wavefront_chunk(s, D.stream, rays, base, m, depth, order_levels != 0, ho, stats != nullptr, &kernel_ms, level_counts, &overflow))) return rc;

@@ -635,6 +635,8 @@ int rt_scene_fold_nodes_device(rt_scene_dev *scene, uint64_t n, const rt_node *d
  * halved and started again (one ray's tree has at most 2^16 - 1 nodes), so the device memory of a call stays below 2^21 x 400 bytes
  * (node and links of every level, and the transient ray, pix, path, order, child and rgb records of one) = 800 MiB, whatever n.
  * level_counts (uint64[RT_MAX_SEGS], or NULL): the rays shaded at each level, summed over the chunks.  host_out->hits must be NULL.
+ * At depth 0 (segs 0 on a scene whose own depth is 0) no level is shaded and nothing is launched: the outputs are rt_trace_rays' all
+ * the same ([0,0,0] and 0,0,0,255 per finite ray), level_counts all zero.
  * The bytes are rt_trace_rays' in both outputs, for every list. */
 int rt_trace_rays_wavefront(const void *scene_blob, size_t blob_bytes, uint64_t n, const double *rays, uint32_t segs, int order_levels,
                             const rt_ray_outputs *host_out, rt_stats *stats, uint64_t *level_counts);

@@ -1,7 +1,8 @@
-"""TEST INFRASTRUCTURE for the wavefront tests (tests/test_nodes.py, tests/test_gpu_nodes.py): the C restatement's probe records
+"""TEST INFRASTRUCTURE for the wavefront tests (tests/test_nodes.py, tests/test_gpu_nodes.py, tests/test_gpu_nodes_edges.py): the C restatement's probe records
 (oracle/rt_oracle.c oracle_probe_sample: every node of a sample's ray tree) for micro-cameras (tests/rays_util.py) at a given depth,
 those records as rt_node arrays level by level, and a walk of a ray list level by level through Renderer.shade_rays / spawn_rays."""
 import ctypes as C
+import math
 import struct
 
 import numpy as np
@@ -172,15 +173,20 @@ def shade(lib, r, rays, pix=None, path=None, order=None, fill=CANARY):
                 b.close()
 
 
-def fold(lib, r, nodes, links=None, child_rgb=None):
-    """Renderer.fold_nodes of host arrays -> (rgb (n, 3) float64, rgba (n, 4) uint8)."""
+def fold(lib, r, nodes, links=None, child_rgb=None, want_rgb=True, want_rgba=True):
+    """Renderer.fold_nodes of host arrays -> (rgb (n, 3) float64, rgba (n, 4) uint8).  An output that is not wanted is handed over as
+    NULL and comes back as None: its buffer is there all the same, and must still hold the canary throughout."""
     n = len(nodes)
     d_nodes, d_rgb, d_rgba = Dev(lib, n * 200, nodes), Dev(lib, n * 24), Dev(lib, n * 4)
     d_links = Dev(lib, n * 8, np.asarray(links, np.int32)) if links is not None else None
     d_child = Dev(lib, max(len(child_rgb), 1) * 24, np.asarray(child_rgb, np.float64) if len(child_rgb) else np.zeros(3)) if links is not None else None
     try:
-        r.fold_nodes(n, d_nodes.ptr, d_links.ptr if d_links else 0, d_child.ptr if d_child else 0, d_rgb.ptr, d_rgba.ptr)
-        return d_rgb.read(np.float64).reshape(n, 3), d_rgba.read().reshape(n, 4)
+        r.fold_nodes(n, d_nodes.ptr, d_links.ptr if d_links else 0, d_child.ptr if d_child else 0, d_rgb.ptr if want_rgb else 0,
+                     d_rgba.ptr if want_rgba else 0)
+        rgb, rgba = d_rgb.read(np.float64).reshape(n, 3), d_rgba.read().reshape(n, 4)
+        assert want_rgb or (rgb.view(np.uint8) == CANARY).all(), "a write to the rgb that was not asked for"
+        assert want_rgba or (rgba == CANARY).all(), "a write to the rgba that was not asked for"
+        return rgb if want_rgb else None, rgba if want_rgba else None
     finally:
         for b in (d_nodes, d_rgb, d_rgba, d_links, d_child):
             if b:
@@ -224,3 +230,71 @@ def walk(lib, r, rays, segs):
 
 def same_bits(a, b):
     return np.ascontiguousarray(a, np.float64).tobytes() == np.ascontiguousarray(b, np.float64).tobytes()
+
+
+# ------------------------------------------------------------------ walked nodes against the restatement's
+def probe_uv(oracle):
+    """hit.u / hit.v of main.js:446-447 from the restatement's normal (two successive divisions each, fdlibm): MicroOracle.hit_of's."""
+    def uv(n):
+        return (oracle.lib.oracle_fd_atan2(-n[2], -n[0]) / math.pi / 2 + 0.5, oracle.lib.oracle_fd_asin(-n[1]) / (math.pi / 2) / 2 + 0.5)
+    return uv
+
+
+def assert_nodes_are_the_restatements(levels, trees, oracle, objs, segs, tag):
+    """Every node of walk()'s levels is the probe record of its (root ray, path), bit for bit: the ray it was shaded for, the hit record,
+    u and v, sample, diffuse, the three weights, the children mask, and as many nodes per tree as the probe has.
+    -> (nodes, hits, two-child nodes)."""
+    albedo = np.array([o["mtl"]["albedo"] for o in objs], np.float64)
+    per_tree = np.zeros(len(trees), np.int64)
+    fd = probe_uv(oracle)
+    n_nodes = n_hits = n_children = 0
+    for depth, lv in enumerate(levels):
+        nd, n = lv["nodes"], len(lv["nodes"])
+        assert all(int(p) in trees[int(j)] for j, p in zip(lv["root"], lv["path"])), "a node the restatement does not have"
+        Q = np.array([trees[int(j)][int(p)] for j, p in zip(lv["root"], lv["path"])])
+        assert (Q[:, 17] == segs - depth).all()                                          # segs left: the level
+        np.add.at(per_tree, lv["root"], 1)
+        # the ray this node was shaded for: the list's (level 1), or the one spawn wrote
+        assert same_bits(lv["rays"][:, 0:3], Q[:, 19:22]) and same_bits(lv["rays"][:, 3:6], Q[:, 9:12]), (tag, segs, depth)
+        code = Q[:, 1].astype(int)
+        hit = code >= 0
+        assert (nd["object"] == np.where(hit, code >> 1, -1)).all() and (nd["inside"] == np.where(hit, code & 1, 0)).all()
+        assert same_bits(nd["t"], Q[:, 2])
+        assert same_bits(nd["point"], Q[:, 3:6]) and same_bits(nd["normal"], Q[:, 6:9])
+        uv = np.array([fd(q[6:9]) if c >= 0 else (0.0, 0.0) for q, c in zip(Q, code)]).reshape(n, 2)
+        assert same_bits(nd["u"], uv[:, 0]) and same_bits(nd["v"], uv[:, 1])
+        want_sample = np.where(hit[:, None], Q[:, 12:15], np.array(oracle.miss_color)[None, :])
+        assert same_bits(nd["sample"], want_sample), (tag, segs, depth, int((nd["sample"] != want_sample).sum()))
+        assert same_bits(nd["diffuse"], Q[:, 15]), (tag, segs, depth, int((nd["diffuse"] != Q[:, 15]).sum()))
+        a = albedo[np.where(hit, code >> 1, 0)] * hit[:, None]
+        assert same_bits(nd["ambient"], a[:, 0]) and same_bits(nd["reflect_weight"], a[:, 3]) and same_bits(nd["refract_weight"], a[:, 4])
+        assert (nd["specular"][a[:, 2] == 0] == 0).all() and (nd["reserved"] == 0).all()
+        if depth + 1 < segs:
+            assert (nd["children"] == Q[:, 22].astype(int)).all()
+        assert (nd["children"][~hit] == 0).all()
+        assert not nd["reflect_dir"][(nd["children"] & 1) == 0].any() and not nd["refract_dir"][(nd["children"] & 2) == 0].any()
+        n_nodes, n_hits, n_children = n_nodes + n, n_hits + int(hit.sum()), n_children + int((nd["children"] == 3).sum())
+    assert (per_tree == np.array([len(t) for t in trees])).all()                        # the number of nodes per tree is the probe's
+    return n_nodes, n_hits, n_children
+
+
+def trace_wavefront_abi(lib, scene, rays, segs=0, want=("rgb", "rgba"), with_stats=False, order_levels=False):
+    """rt_trace_rays_wavefront through ctypes, with an RtStats where asked (rt_host.trace_rays passes none)
+    -> dict(rgb, rgba (those wanted), level_counts, stats or None)."""
+    blob = scene if isinstance(scene, (bytes, bytearray)) else rt_host.flatten_scene(scene)
+    rays = np.asarray(rays, np.float64)
+    n = len(rays)
+    aligned = np.empty(n * 6 + 2, np.float64)             # a contiguous copy on a 16-byte boundary
+    aligned = aligned[(aligned.ctypes.data >> 3) & 1:][:n * 6]
+    aligned[:] = rays.reshape(-1)
+    out = {"level_counts": np.zeros(rt_host.RT_MAX_SEGS, np.uint64), "stats": rt_host.RtStats() if with_stats else None}
+    if "rgb" in want:
+        out["rgb"] = np.empty((n, 3), np.float64)
+    if "rgba" in want:
+        out["rgba"] = np.empty((n, 4), np.uint8)
+    bufs = rt_host.RtRayOutputs(out["rgb"].ctypes.data if "rgb" in out else None, out["rgba"].ctypes.data if "rgba" in out else None, None)
+    buf = C.create_string_buffer(bytes(blob), len(blob))
+    rc = lib.rt_trace_rays_wavefront(buf, len(blob), n, C.c_void_p(aligned.ctypes.data), segs, 1 if order_levels else 0, C.byref(bufs),
+                                     C.byref(out["stats"]) if with_stats else None, out["level_counts"].ctypes.data_as(C.POINTER(C.c_uint64)))
+    assert rc == 0, lib.rt_last_error()
+    return out

@@ -82,7 +82,6 @@ def test_every_node_is_the_restatements(anylib, name, segs):
     scene, cams, rays = scene_of(name)
     oracle, trees = oracle_of(name, segs)
     objs = scene["objects"]
-    albedo = np.array([o["mtl"]["albedo"] for o in objs], np.float64)
     r = rt_host.Renderer(scene, 0, anylib)
     try:
         levels = nu.walk(anylib, r, rays, segs)
@@ -96,46 +95,10 @@ def test_every_node_is_the_restatements(anylib, name, segs):
     assert any(objs[i]["mtl"]["albedo"][4] > 0 for i in inside) or name == "h8"
     if name == "default14":
         assert (np.linalg.norm(rays[:, 0:3], axis=1) > 5000.0).sum() >= 12
-    per_tree = np.zeros(len(trees), np.int64)
-    fd = hu_probe_uv(oracle)
-    n_nodes = n_hits = n_children = 0
-    for depth, lv in enumerate(levels):
-        nd, n = lv["nodes"], len(lv["nodes"])
-        assert all(int(p) in trees[int(j)] for j, p in zip(lv["root"], lv["path"])), "a node the restatement does not have"
-        Q = np.array([trees[int(j)][int(p)] for j, p in zip(lv["root"], lv["path"])])
-        assert (Q[:, 17] == segs - depth).all()                                          # segs left: the level
-        np.add.at(per_tree, lv["root"], 1)
-        # the ray this node was shaded for: the list's (level 1), or the one spawn wrote
-        assert nu.same_bits(lv["rays"][:, 0:3], Q[:, 19:22]) and nu.same_bits(lv["rays"][:, 3:6], Q[:, 9:12]), (name, segs, depth)
-        code = Q[:, 1].astype(int)
-        hit = code >= 0
-        assert (nd["object"] == np.where(hit, code >> 1, -1)).all() and (nd["inside"] == np.where(hit, code & 1, 0)).all()
-        assert nu.same_bits(nd["t"], Q[:, 2])
-        assert nu.same_bits(nd["point"], Q[:, 3:6]) and nu.same_bits(nd["normal"], Q[:, 6:9])
-        uv = np.array([fd(q[6:9]) if c >= 0 else (0.0, 0.0) for q, c in zip(Q, code)]).reshape(n, 2)
-        assert nu.same_bits(nd["u"], uv[:, 0]) and nu.same_bits(nd["v"], uv[:, 1])
-        want_sample = np.where(hit[:, None], Q[:, 12:15], np.array(oracle.miss_color)[None, :])
-        assert nu.same_bits(nd["sample"], want_sample), (name, segs, depth, int((nd["sample"] != want_sample).sum()))
-        assert nu.same_bits(nd["diffuse"], Q[:, 15]), (name, segs, depth, int((nd["diffuse"] != Q[:, 15]).sum()))
-        a = albedo[np.where(hit, code >> 1, 0)] * hit[:, None]
-        assert nu.same_bits(nd["ambient"], a[:, 0]) and nu.same_bits(nd["reflect_weight"], a[:, 3]) and nu.same_bits(nd["refract_weight"], a[:, 4])
-        assert (nd["specular"][a[:, 2] == 0] == 0).all() and (nd["reserved"] == 0).all()
-        if depth + 1 < segs:
-            assert (nd["children"] == Q[:, 22].astype(int)).all()
-        assert (nd["children"][~hit] == 0).all()
-        assert not nd["reflect_dir"][(nd["children"] & 1) == 0].any() and not nd["refract_dir"][(nd["children"] & 2) == 0].any()
-        n_nodes, n_hits, n_children = n_nodes + n, n_hits + int(hit.sum()), n_children + int((nd["children"] == 3).sum())
-    assert (per_tree == np.array([len(t) for t in trees])).all()                        # the number of nodes per tree is the probe's
+    n_nodes, n_hits, n_children = nu.assert_nodes_are_the_restatements(levels, trees, oracle, objs, segs, name)
     print("NODES %s segs %d: %d nodes in %d levels, %d hits, %d two-child nodes" % (name, segs, n_nodes, len(levels), n_hits, n_children))
     if name != "h8" and segs > 1:
         assert n_children > 0
-
-
-def hu_probe_uv(oracle):
-    """hit.u / hit.v of main.js:446-447 from the restatement's normal (two successive divisions each, fdlibm): MicroOracle.hit_of's."""
-    def uv(n):
-        return (oracle.lib.oracle_fd_atan2(-n[2], -n[0]) / math.pi / 2 + 0.5, oracle.lib.oracle_fd_asin(-n[1]) / (math.pi / 2) / 2 + 0.5)
-    return uv
 
 
 # ------------------------------------------------------------------ 6. wavefront equals the recursive trace
@@ -207,7 +170,7 @@ def test_wavefront_halves_a_chunk_whose_trees_exceed_the_node_budget(lib):
 
 
 # ------------------------------------------------------------------ 7. spawn
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 4097])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 4097, 65536, 65537, 65536 + 257, 2 ** 18])
 def test_spawn(lib, n):
     rng = np.random.default_rng(n)
     nodes = np.zeros(n, rt_host.NODE_DTYPE)
@@ -215,6 +178,9 @@ def test_spawn(lib, n):
     if n > 300:
         nodes["children"][256:512] = 0                                               # a workgroup without children, then a full one
         nodes["children"][512:768] = 3
+    if n > 65536:                                                                    # above 256 workgroups the scan carries: the same pair astride the carry
+        nodes["children"][65536:65792] = 0
+        nodes["children"][65792:66048] = 3
     nodes["point"], nodes["reflect_dir"], nodes["refract_dir"] = rng.normal(size=(n, 3)), rng.normal(size=(n, 3)), rng.normal(size=(n, 3))
     pix, path = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32), rng.integers(1, 2 ** 30, n).astype(np.uint32)
     r = rt_host.Renderer(rt_host.load_scene("h8"), 0, lib)
@@ -226,7 +192,8 @@ def test_spawn(lib, n):
         r.close()
     ch = nodes["children"]
     has = np.stack([(ch & 1) != 0, (ch & 2) != 0], axis=1)
-    assert a["count"] == int(has.sum()) == sum(bin(int(c)).count("1") for c in ch)
+    assert a["count"] == int(has.sum()) == int(np.array([0, 1, 1, 2])[ch].sum())
+    print("NODES spawn n %d: %d tiles, %d children" % (n, (n + 255) // 256, a["count"]))
     links = a["links"]
     assert ((links >= 0) == has).all() and (links[~has] == -1).all()
     flat = links.reshape(-1)
