@@ -1,7 +1,7 @@
 // rt_api_internal.h — what the host units of the C ABI share: errors and test switches, the library and device state, the resident
 // scene (rt_scene_dev) and the few functions that cross units.  Not part of the ABI.
 //   rt_api.hip     lifetime, errors, device state, the scratch guard and the per-variant scratch figures, the host-logic probes, memory helpers, IPC
-//   rt_scene.hip   upload and moves of a resident scene (the generation pipeline), its launch decisions and launch tables
+//   rt_scene.hip   upload and moves of a resident scene (the generation pipeline), its texel edits (rt_texels.hip), its launch decisions and launch tables
 //   rt_launch.hip  the launches: colour (the launch record, then the strict launch or the product launch and rt_retrace), supersampling,
 //                  compact bands, primary hits and picking, ray lists, occlusion queries
 //   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick, and the host lists that go
@@ -35,6 +35,7 @@
 #include "rt_rays_order.h"
 #include "rt_occlusion.h"
 #include "rt_nodes.h"
+#include "rt_texels.h"
 
 // per build of rt_kernel.hip (product, strict): the variant's kernel (NULL: not this build's) and its launch
 extern "C" const void *rt_kernel_trace_fast(rt_trace_variant);
@@ -244,6 +245,22 @@ struct rt_scene_dev {
   uint8_t *stage_pool = nullptr;
   size_t stage_bytes = 0;
   uint32_t stage_next = 0;
+  // Texel edits (rt_scene_set_texels, rt_scene_set_texels_device).  Texels live once, in d_blob, and every kernel reads them through
+  // texel_base + texels_offset; no table, host decision or mark count reads a texel's VALUE (flag_tol and the strict routing read
+  // widths and heights; a texture sampler is never a constant sky).  So an edit is no generation: it is one write on the caller's
+  // stream, ordered by stream and event against the launches around it.
+  //   tex_before    recorded on the stream of the scene's launches in flight when the edit's stream is another one: the write waits for it
+  //   tex_done      recorded behind the write; the next launch on every OTHER stream waits for it (tex_waited: which already do),
+  //                 and so does the next edit on another stream
+  // Neither exists before the first edit.  host_blob keeps the texels of the upload: nothing reads them.
+  hipEvent_t tex_before = nullptr, tex_done = nullptr;
+  hipStream_t tex_stream = nullptr;      // the stream of the last edit
+  uint64_t tex_seq = 0;                  // edits so far
+  std::vector<waited_on> tex_waited;     // (stream, tex_seq) pairs
+  // the host form's pinned staging: a ring of RT_TEXEL_STAGE_SLOTS slots of RT_TEXEL_STAGE_SLOT bytes, allocated by the first host edit
+  stage_slot tex_stages[16];
+  uint8_t *tex_pool = nullptr;
+  uint32_t tex_stage_next = 0;
   std::vector<uint8_t> host_blob;        // the scene as uploaded (patched: 1/r per sphere), for rebuilding the camera block
   std::vector<rt_sphere> host_objects_b; // ordering B of its sphere records
   rt_scene_header hd;            // host copy
@@ -338,6 +355,12 @@ int spawn_launch(uint32_t n, uint32_t base, const rt_node *d_nodes, const uint32
                  uint32_t *d_child_path, int32_t *d_links, uint32_t *d_count, void *d_work, hipStream_t stream);
 int fold_launch(uint32_t n, const rt_node *d_nodes, const int32_t *d_links, const double *d_child_rgb, double *d_rgb, uint8_t *d_rgba, hipStream_t stream);
 
+// rt_frame.hip: what scene_for does with a blob that differs from the resident one: per texture whose texels differ the smallest row
+// range that covers the differences, in texture order.  -1: the blobs differ in something no edit of a resident scene reaches (anything
+// outside the camera, light intensity and stars seed of the header, the sphere and light tables and the textures' texels: a
+// descriptor, the padding between two textures).  `a` is a blob rt_scene_validate has accepted, `b` any `bytes` bytes.
+struct texel_edit { uint32_t texture, first_row, rows; };
+int texel_edits(const uint8_t *a, const uint8_t *b, size_t bytes, std::vector<texel_edit> *out);
 // rt_frame.hip: RCCL's communicators are destroyed (rt_shutdown)
 void release_rccl();
 }  // namespace rt_api

@@ -76,7 +76,68 @@ extern "C" int rt_deinterleave_rgb24_device(int device, const void *d_src, void 
   return RT_OK;
 }
 
-// ------------------------------------------------------------------------------------ RCCL (lazy)
+// ------------------------------------------------------------------------------------ the blob diff of scene_for
+namespace rt_api {
+// What scene_for does with a blob of the resident one's size (rt_api_internal.h).  The header but for camera, intensity and seed, the
+// descriptors, and every byte outside the sphere table, the light table and the textures' texel ranges must be equal: a byte of the
+// padding between two textures that differs is -1, like any other byte no edit call reaches (a flattener writes zeros there).
+int texel_edits(const uint8_t *a, const uint8_t *b, size_t bytes, std::vector<texel_edit> *out) {
+  out->clear();
+  const size_t c0 = offsetof(rt_scene_header, cam_origin), c1 = c0 + 12 * sizeof(double);
+  const size_t i0 = offsetof(rt_scene_header, light_intensity), i1 = i0 + sizeof(double);
+  const size_t s0 = offsetof(rt_scene_header, stars_seed), s1 = s0 + sizeof(uint32_t);
+  static_assert(c1 <= i0 && i1 <= s0, "the camera lies in front of the light intensity, and that in front of the stars seed in rt_scene_header");
+  if (bytes < sizeof(rt_scene_header)) return -1;
+  // the header's other fields equal (the places and sizes of the three tables included: the resident blob's, which rt_scene_validate has seen)
+  if (memcmp(a, b, c0) != 0 || memcmp(a + c1, b + c1, i0 - c1) != 0 || memcmp(a + i1, b + i1, s0 - i1) != 0 || memcmp(a + s1, b + s1, sizeof(rt_scene_header) - s1) != 0) return -1;
+  const rt_scene_header *hd = (const rt_scene_header *)a;
+  // the ranges an edit reaches, in blob order: [begin, end, texture or -1)
+  struct range { size_t begin, end; int texture; };
+  std::vector<range> r;
+  r.push_back(range{(size_t)hd->objects_offset, (size_t)hd->objects_offset + (size_t)hd->n_objects * sizeof(rt_sphere), -1});
+  r.push_back(range{(size_t)hd->lights_offset, (size_t)hd->lights_offset + (size_t)hd->n_lights * 24u, -1});
+  const size_t d0 = hd->textures_offset, d1 = d0 + (size_t)hd->n_textures * sizeof(rt_texture_desc);
+  if (hd->n_textures > RT_MAX_TEXTURES || d1 > bytes) return -1;
+  rt_texture_desc td[RT_MAX_TEXTURES];                   // (the blob's own bytes may be unaligned)
+  if (hd->n_textures) memcpy(td, a + d0, d1 - d0);
+  for (uint32_t t = 0; t < hd->n_textures; t++) r.push_back(range{(size_t)td[t].texels_offset, (size_t)td[t].texels_offset + (size_t)td[t].width * td[t].height * 4u, (int)t});
+  for (size_t i = 1; i < r.size(); i++)                  // (at most 18 entries)
+    for (size_t j = i; j > 0 && r[j].begin < r[j - 1].begin; j--) std::swap(r[j], r[j - 1]);
+  // everything between them is equal - the descriptors too, wherever they lie; ranges that overlap (two descriptors of the same texels,
+  // a table inside a texture: nothing a flattener writes) are left to the upload
+  size_t at = sizeof(rt_scene_header);
+  for (const range &q : r) {
+    if (q.begin == q.end) continue;
+    if (q.begin < at || q.end > bytes) return -1;
+    if (memcmp(a + at, b + at, q.begin - at) != 0) return -1;
+    at = q.end;
+  }
+  if (memcmp(a + at, b + at, bytes - at) != 0) return -1;
+  for (const range &q : r) if (q.begin < d1 && d0 < q.end && q.begin != q.end) return -1;      // (the descriptors lie in none of them)
+  for (uint32_t t = 0; t < hd->n_textures; t++) {
+    const size_t row = (size_t)td[t].width * 4u;
+    const uint8_t *ta = a + td[t].texels_offset, *tb = b + td[t].texels_offset;
+    uint32_t first = 0, end = td[t].height;
+    while (first < end && memcmp(ta + first * row, tb + first * row, row) == 0) first++;
+    while (end > first && memcmp(ta + (end - 1u) * row, tb + (end - 1u) * row, row) == 0) end--;
+    if (first < end) out->push_back(texel_edit{t, first, end - first});
+  }
+  return 0;
+}
+}  // namespace rt_api
+
+#ifdef RT_TESTING
+// Test build only: texel_edits as scene_for calls it, without a GPU: {texture, first_row, rows} per changed texture into out_triples (at
+// most `cap` of them).  Returns their number, or -1 (blob_a is no valid scene, or the blobs differ in what no edit reaches).
+extern "C" int rt_test_texel_edits(const void *blob_a, const void *blob_b, size_t bytes, uint32_t *out_triples, uint32_t cap) {
+  if (!blob_a || !blob_b || rt_scene_validate(blob_a, bytes) != RT_OK) return -1;
+  std::vector<texel_edit> edits;
+  if (texel_edits((const uint8_t *)blob_a, (const uint8_t *)blob_b, bytes, &edits) != 0) return -1;
+  for (size_t i = 0; i < edits.size() && i < cap && out_triples; i++) { out_triples[3 * i] = edits[i].texture; out_triples[3 * i + 1] = edits[i].first_row; out_triples[3 * i + 2] = edits[i].rows; }
+  return (int)edits.size();
+}
+#endif
+
 namespace {
 typedef int (*nccl_comm_init_all_t)(void **comms, int ndev, const int *devlist);
 typedef int (*nccl_gather_t)(const void *send, void *recv, size_t count, int dtype, int root, void *comm, hipStream_t stream);
@@ -113,44 +174,39 @@ int ensure_rccl(int ndev) {
 int scene_for(int device, const void *blob, size_t bytes, rt_scene_dev **out) {
   device_state &D = G.dev[device];
   if (D.cached_scene && D.cached_blob.size() == bytes && memcmp(D.cached_blob.data(), blob, bytes) == 0) { *out = D.cached_scene; return RT_OK; }
-  // the same scene from another camera, with another stars seed, with moved or restyled spheres and / or with moved or dimmed lights
-  // (an animation: lookAt per frame, main.js:92-100, a new sky per redraw, main.js:135-139, 180, objects and lights a page changes
-  // between redraws, main.js:283-284): the resident scene takes the spheres of the smallest range that covers the differences, then
-  // the lights of theirs, then the intensity, then the camera, then the seed
-  if (D.cached_scene && D.cached_blob.size() == bytes) {
-    const size_t c0 = offsetof(rt_scene_header, cam_origin), c1 = c0 + 12 * sizeof(double);
-    const size_t i0 = offsetof(rt_scene_header, light_intensity), i1 = i0 + sizeof(double);
-    const size_t s0 = offsetof(rt_scene_header, stars_seed), s1 = s0 + sizeof(uint32_t);
-    static_assert(c1 <= i0 && i1 <= s0, "the camera lies in front of the light intensity, and that in front of the stars seed in rt_scene_header");
+  // the same scene with other texels in its textures, from another camera, with another stars seed, with moved or restyled spheres
+  // and / or with moved or dimmed lights (an animation: a video on a sphere, main.js:339-395, lookAt per frame, main.js:92-100, a new
+  // sky per redraw, main.js:135-139, 180, objects and lights a page changes between redraws, main.js:283-284): the resident scene
+  // takes, per texture whose texels differ, the rows of the smallest range that covers the differences, then the spheres of the
+  // smallest range that covers theirs, then the lights of theirs, then the intensity, then the camera, then the seed
+  std::vector<texel_edit> edits;
+  if (D.cached_scene && D.cached_blob.size() == bytes && texel_edits(D.cached_blob.data(), (const uint8_t *)blob, bytes, &edits) == 0) {
     const uint8_t *a = D.cached_blob.data(), *b = (const uint8_t *)blob;
     const rt_scene_header *nh = (const rt_scene_header *)blob;
-    // the header's other fields equal (the places and sizes of the object and light tables included: the resident blob's, which
-    // rt_scene_validate has seen), then everything outside the two tables
-    if (memcmp(a, b, c0) == 0 && memcmp(a + c1, b + c1, i0 - c1) == 0 && memcmp(a + i1, b + i1, s0 - i1) == 0 && memcmp(a + s1, b + s1, sizeof(rt_scene_header) - s1) == 0) {
-      const size_t o0 = nh->objects_offset, o1 = o0 + (size_t)nh->n_objects * sizeof(rt_sphere);
-      const size_t l0 = nh->lights_offset, l1 = l0 + (size_t)nh->n_lights * 24u;
-      const size_t t0 = o0 < l0 ? o0 : l0, t1 = o0 < l0 ? o1 : l1, u0 = o0 < l0 ? l0 : o0, u1 = o0 < l0 ? l1 : o1;     // the tables in blob order
-      if (t0 >= sizeof(rt_scene_header) && t1 <= u0 && u1 <= bytes && memcmp(a + sizeof(rt_scene_header), b + sizeof(rt_scene_header), t0 - sizeof(rt_scene_header)) == 0 &&
-          memcmp(a + t1, b + t1, u0 - t1) == 0 && memcmp(a + u1, b + u1, bytes - u1) == 0) {
-        const rt_sphere *na = (const rt_sphere *)(a + o0), *nb = (const rt_sphere *)(b + o0);
-        uint32_t first = nh->n_objects, last = 0;
-        for (uint32_t i = 0; i < nh->n_objects; i++)
-          if (memcmp(&na[i], &nb[i], sizeof(rt_sphere)) != 0) { if (first == nh->n_objects) first = i; last = i + 1; }
-        uint32_t lfirst = nh->n_lights, llast = 0;
-        for (uint32_t k = 0; k < nh->n_lights; k++)
-          if (memcmp(a + l0 + 24u * k, b + l0 + 24u * k, 24u) != 0) { if (lfirst == nh->n_lights) lfirst = k; llast = k + 1; }
-        double xyz[RT_MAX_LIGHTS][3];                    // (the blob's own bytes may be unaligned)
-        if (lfirst < llast && llast - lfirst <= RT_MAX_LIGHTS) memcpy(xyz, b + l0 + 24u * lfirst, (size_t)(llast - lfirst) * 24u);
-        if ((first == nh->n_objects || rt_scene_set_objects(D.cached_scene, first, last - first, nb + first, nullptr) == RT_OK) &&
-            (lfirst == nh->n_lights || rt_scene_set_lights(D.cached_scene, lfirst, llast - lfirst, &xyz[0][0], nullptr) == RT_OK) &&
-            rt_scene_set_light_intensity(D.cached_scene, nh->light_intensity) == RT_OK &&
-            rt_scene_set_camera(D.cached_scene, nh->cam_origin, nh->cam_axis_x, nh->cam_axis_y, nh->cam_axis_z, nullptr) == RT_OK &&
-            rt_scene_set_stars_seed(D.cached_scene, nh->stars_seed) == RT_OK) {
-          memcpy(D.cached_blob.data(), b, bytes);
-          *out = D.cached_scene;
-          return RT_OK;
-        }
-      }
+    const size_t o0 = nh->objects_offset, l0 = nh->lights_offset;
+    bool ok = true;
+    for (const texel_edit &e : edits) {
+      rt_texture_desc d;
+      memcpy(&d, a + nh->textures_offset + e.texture * sizeof(rt_texture_desc), sizeof d);
+      ok = ok && rt_scene_set_texels(D.cached_scene, e.texture, 0u, e.first_row, d.width, e.rows, b + d.texels_offset + (size_t)e.first_row * d.width * 4u, 0u, nullptr) == RT_OK;
+    }
+    const rt_sphere *na = (const rt_sphere *)(a + o0), *nb = (const rt_sphere *)(b + o0);
+    uint32_t first = nh->n_objects, last = 0;
+    for (uint32_t i = 0; i < nh->n_objects; i++)
+      if (memcmp(&na[i], &nb[i], sizeof(rt_sphere)) != 0) { if (first == nh->n_objects) first = i; last = i + 1; }
+    uint32_t lfirst = nh->n_lights, llast = 0;
+    for (uint32_t k = 0; k < nh->n_lights; k++)
+      if (memcmp(a + l0 + 24u * k, b + l0 + 24u * k, 24u) != 0) { if (lfirst == nh->n_lights) lfirst = k; llast = k + 1; }
+    double xyz[RT_MAX_LIGHTS][3];                    // (the blob's own bytes may be unaligned)
+    if (lfirst < llast && llast - lfirst <= RT_MAX_LIGHTS) memcpy(xyz, b + l0 + 24u * lfirst, (size_t)(llast - lfirst) * 24u);
+    if (ok && (first == nh->n_objects || rt_scene_set_objects(D.cached_scene, first, last - first, nb + first, nullptr) == RT_OK) &&
+        (lfirst == nh->n_lights || rt_scene_set_lights(D.cached_scene, lfirst, llast - lfirst, &xyz[0][0], nullptr) == RT_OK) &&
+        rt_scene_set_light_intensity(D.cached_scene, nh->light_intensity) == RT_OK &&
+        rt_scene_set_camera(D.cached_scene, nh->cam_origin, nh->cam_axis_x, nh->cam_axis_y, nh->cam_axis_z, nullptr) == RT_OK &&
+        rt_scene_set_stars_seed(D.cached_scene, nh->stars_seed) == RT_OK) {
+      memcpy(D.cached_blob.data(), b, bytes);
+      *out = D.cached_scene;
+      return RT_OK;
     }
   }
   if (D.cached_scene) { rt_scene_free(D.cached_scene); D.cached_scene = nullptr; D.cached_blob.clear(); }

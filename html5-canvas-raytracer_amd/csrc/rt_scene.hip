@@ -1,5 +1,5 @@
 // rt_scene.hip — a resident scene (include/rt_hip.h: rt_scene_*): upload and free, the host decisions that depend on its spheres and
-// its camera, the blocks it keeps in HBM, the camera / object / light / stars-seed moves (the generation pipeline), the launch
+// its camera, the blocks it keeps in HBM, the camera / object / light / stars-seed moves (the generation pipeline), the texel edits, the launch
 // decisions of its product launches and its launch tables (built on the GPU, rt_tables_gpu.hip).
 
 #include "rt_api_internal.h"
@@ -397,6 +397,10 @@ extern "C" void rt_scene_free(rt_scene_dev *s) {
   if (s->stage_pool) (void)hipHostFree(s->stage_pool);
   for (int b = 0; b < 2; b++) { if (s->old_done[b]) (void)hipEventDestroy(s->old_done[b]); if (s->prep_done[b]) (void)hipEventDestroy(s->prep_done[b]); }
   if (s->side) (void)hipStreamDestroy(s->side);
+  if (s->tex_before) (void)hipEventDestroy(s->tex_before);
+  if (s->tex_done) (void)hipEventDestroy(s->tex_done);
+  for (rt_scene_dev::stage_slot &g : s->tex_stages) if (g.done) (void)hipEventDestroy(g.done);
+  if (s->tex_pool) (void)hipHostFree(s->tex_pool);
   for (rt_scene_dev::order_entry &e : s->orders) free_order_entry(e);
   for (const rt_scene_dev::mark_state &m : s->mark_states) (void)hipFree(m.d_marks);
   if (s->h_known_pool) (void)hipHostFree(s->h_known_pool);
@@ -617,6 +621,119 @@ extern "C" int rt_scene_set_stars_seed(rt_scene_dev *s, uint32_t seed) {
   return RT_OK;
 }
 
+// ------------------------------------------------------------------------------------ texel edits
+// The texels of a resident scene's textures are replaced (the reference's textures are ImageData a page may draw into between two
+// redraws, main.js:339-395; sampled one texel at a time, main.js:343-351).  No generation, no table, no launch decision (rt_scene_dev:
+// tex_done): one write by rt_texels_blit on the caller's stream - behind the scene's launches in flight (stream order, or tex_before;
+// launches on several streams: the device is drained, as next_generation does) and in front of every later one (stream order, or
+// tex_done in behind_the_camera).  Only kernel boundaries order it: nothing relies on caches being coherent inside a kernel.
+namespace {
+constexpr size_t RT_TEXEL_STAGE_SLOT = 256u * 1024u, RT_TEXEL_STAGE_SLOTS = 16u;    // 4 MiB of pinned memory (include/rt_hip.h says so)
+
+// the checks of both forms that need no scene
+int texels_args_check(const char *what, uint32_t w, uint32_t h, const void *src, size_t pitch_bytes, bool device) {
+  if (!src && w && h) return fail(RT_ERR_INVALID, "%s: NULL source for a rectangle of %ux%u texels", what, w, h);
+  if (pitch_bytes && (pitch_bytes < 4u * (size_t)w || (pitch_bytes & 3u))) return fail(RT_ERR_INVALID, "%s: a pitch of %zu bytes is below 4 x %u or no multiple of 4", what, pitch_bytes, w);
+  if (device && ((uintptr_t)src & 3u)) return fail(RT_ERR_INVALID, "%s: the device source is not 4-byte aligned", what);
+  return RT_OK;
+}
+// ... and those that need one
+int texels_rect_check(const char *what, const rt_scene_dev *s, uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h) {
+  if (texture >= s->hd.n_textures) return fail(RT_ERR_INVALID, "%s: texture %u of %u", what, texture, s->hd.n_textures);
+  const rt_texture_desc &d = s->descs[texture];
+  if ((uint64_t)x + w > d.width || (uint64_t)y + h > d.height)
+    return fail(RT_ERR_INVALID, "%s: the rectangle [%u, %u + %u) x [%u, %u + %u) leaves texture %u (%ux%u): another size is an upload", what, x, x, w, y, y, h, texture, d.width, d.height);
+  return RT_OK;
+}
+
+// The write about to be enqueued on `stream` comes behind every launch of the scene so far and behind the edit before it; launch_mu held
+int texels_order_before(rt_scene_dev *s, hipStream_t stream) {
+  if (!s->tex_done) {
+    HIP_TRY(hipEventCreateWithFlags(&s->tex_before, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&s->tex_done, hipEventDisableTiming));
+  }
+  if (s->any_launch && s->several_streams) {
+    // launches of this scene in flight on SEVERAL caller streams: no single event covers them (rare: drain the device, like a move)
+    HIP_TRY(hipDeviceSynchronize());
+    s->any_launch = false; s->several_streams = false; s->launched_since_move = false; s->old_done_valid[0] = s->old_done_valid[1] = false;
+  } else if (s->any_launch && s->last_stream != stream) {
+    HIP_TRY(hipEventRecord(s->tex_before, s->last_stream));
+    HIP_TRY(hipStreamWaitEvent(stream, s->tex_before, 0));
+  }
+  if (s->tex_seq && s->tex_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->tex_done, 0));   // (two edits may overlap)
+  return RT_OK;
+}
+
+// ... and is in front of every later one
+int texels_order_after(rt_scene_dev *s, hipStream_t stream) {
+  HIP_TRY(hipEventRecord(s->tex_done, stream));
+  s->tex_seq++;
+  s->tex_stream = stream;
+  s->tex_waited.clear();
+  return RT_OK;
+}
+
+uint32_t *texel_at(const rt_scene_dev *s, uint32_t texture, uint32_t x, uint32_t y) {
+  const rt_texture_desc &d = s->descs[texture];
+  return (uint32_t *)((uint8_t *)s->d_blob + d.texels_offset) + (size_t)y * d.width + x;
+}
+
+int set_texels(rt_scene_dev *s, uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const void *src, size_t pitch_bytes, void *hip_stream, bool device) {
+  const char *what = device ? "rt_scene_set_texels_device" : "rt_scene_set_texels";
+  int rc = texels_args_check(what, w, h, src, pitch_bytes, device);
+  if (rc) return rc;
+  if (!s) return fail(RT_ERR_STATE, "%s: NULL scene handle", what);
+  if ((rc = texels_rect_check(what, s, texture, x, y, w, h))) return rc;
+  if (w == 0u || h == 0u) return RT_OK;
+  hipStream_t stream = nullptr;
+  if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
+  const size_t pitch = pitch_bytes ? pitch_bytes : 4u * (size_t)w;
+  const uint32_t tex_w = s->descs[texture].width;
+  std::lock_guard<std::mutex> lk(s->launch_mu);
+  if (!device) {
+    if (!s->tex_pool) HIP_TRY(hipHostMalloc((void **)&s->tex_pool, RT_TEXEL_STAGE_SLOT * RT_TEXEL_STAGE_SLOTS, hipHostMallocDefault));
+    for (size_t i = 0; i < RT_TEXEL_STAGE_SLOTS; i++) {
+      s->tex_stages[i].h = s->tex_pool + i * RT_TEXEL_STAGE_SLOT;
+      if (!s->tex_stages[i].done) HIP_TRY(hipEventCreateWithFlags(&s->tex_stages[i].done, hipEventDisableTiming));
+    }
+  }
+  if ((rc = texels_order_before(s, stream))) return rc;
+  auto write = [&]() -> int {
+    if (device) {
+      const rt_texels_launch L = {texel_at(s, texture, x, y), (const uint32_t *)src, tex_w, pitch / 4u, w};
+      HIP_TRY((hipError_t)rt_launch_texels_blit(&L, h, stream));
+      return RT_OK;
+    }
+    // the rows are packed into pinned slots, which the blit reads over the host link: pieces of whole rows (a texture row is at most
+    // 64 KiB: four rows and more per slot).  A slot is written again only after the piece that read it (its event): the one host wait,
+    // taken when the caller is RT_TEXEL_STAGE_SLOTS pieces ahead of the GPU.
+    const uint32_t rows_per = (uint32_t)(RT_TEXEL_STAGE_SLOT / (4u * (size_t)w));
+    for (uint32_t j0 = 0; j0 < h; j0 += rows_per) {
+      const uint32_t rows = h - j0 < rows_per ? h - j0 : rows_per;
+      rt_scene_dev::stage_slot &g = s->tex_stages[s->tex_stage_next++ % RT_TEXEL_STAGE_SLOTS];
+      if (g.used) HIP_TRY(hipEventSynchronize(g.done));
+      g.used = true;
+      for (uint32_t j = 0; j < rows; j++) memcpy(g.h + (size_t)j * 4u * w, (const uint8_t *)src + (size_t)(j0 + j) * pitch, 4u * (size_t)w);
+      const rt_texels_launch L = {texel_at(s, texture, x, y + j0), (const uint32_t *)g.h, tex_w, w, w};
+      HIP_TRY((hipError_t)rt_launch_texels_blit(&L, rows, stream));
+      HIP_TRY(hipEventRecord(g.done, stream));
+    }
+    return RT_OK;
+  };
+  rc = write();
+  const int rc_after = texels_order_after(s, stream);       // (also behind pieces of an edit that failed half way)
+  return rc ? rc : rc_after;
+}
+}  // namespace
+
+extern "C" int rt_scene_set_texels(rt_scene_dev *s, uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const void *rgba, size_t pitch_bytes, void *hip_stream) {
+  return set_texels(s, texture, x, y, w, h, rgba, pitch_bytes, hip_stream, false);
+}
+
+extern "C" int rt_scene_set_texels_device(rt_scene_dev *s, uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const void *d_rgba, size_t pitch_bytes, void *hip_stream) {
+  return set_texels(s, texture, x, y, w, h, d_rgba, pitch_bytes, hip_stream, true);
+}
+
 namespace rt_api {
 // a pinned host word of the scene's pool (generation << 32 | value + 1, written by a kernel): [0, RT_KNOWN_WORDS) the mark states',
 // [RT_KNOWN_WORDS, 2 RT_KNOWN_WORDS) the launch tables'
@@ -637,6 +754,16 @@ uint32_t known_value(const volatile unsigned long long *p, uint64_t gen) {
 // The camera has moved since `stream` last launched the scene: its work comes behind the copy of the camera's block and the tables
 // rebuilt for it on the scene's side stream (rt_scene_set_camera).  One event wait per (stream, camera); launch_mu held.
 int behind_the_camera(rt_scene_dev *s, hipStream_t stream) {
+  // ... and behind the last texel edit, when that ran on another stream (rt_scene_set_texels): one event wait per (stream, edit)
+  if (s->tex_seq && stream != s->tex_stream) {
+    bool waits = false;
+    for (const rt_scene_dev::waited_on &q : s->tex_waited) if (q.stream == stream && q.gen == s->tex_seq) waits = true;
+    if (!waits) {
+      HIP_TRY(hipStreamWaitEvent(stream, s->tex_done, 0));
+      if (s->tex_waited.size() >= 16u) s->tex_waited.clear();
+      s->tex_waited.push_back(rt_scene_dev::waited_on{stream, s->tex_seq});
+    }
+  }
   const uint32_t cb = (uint32_t)(s->cam_gen & 1u);
   if (!s->prep_valid[cb]) return RT_OK;
   for (const rt_scene_dev::waited_on &q : s->prep_waited) if (q.stream == stream && q.gen == s->cam_gen) return RT_OK;
@@ -799,6 +926,22 @@ extern "C" long long rt_test_scene_state(rt_scene_dev *s, int part, void *out, s
   if (out && n && bytes >= n) {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, src, n, hipMemcpyDeviceToHost));
+  }
+  return (long long)n;
+}
+
+// Test build only: the resident blob's bytes from its first texel to its end (the textures' texels and whatever lies between them), read
+// back after a drain.  Returns their count (0: a scene without textures), copied to `out` when `bytes` holds it; < 0: an RT_ERR_* code.
+extern "C" long long rt_test_scene_texels(rt_scene_dev *s, void *out, size_t bytes) {
+  if (!s) return fail(RT_ERR_INVALID, "rt_test_scene_texels: NULL scene");
+  if (int rc = ensure_device(s->device)) return rc;
+  std::lock_guard<std::mutex> lk(s->launch_mu);
+  size_t first = s->host_blob.size();
+  for (uint32_t t = 0; t < s->hd.n_textures; t++) if (s->descs[t].texels_offset < first) first = s->descs[t].texels_offset;
+  const size_t n = s->host_blob.size() - first;
+  if (out && n && bytes >= n) {
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, (const uint8_t *)s->d_blob + first, n, hipMemcpyDeviceToHost));
   }
   return (long long)n;
 }

@@ -221,6 +221,8 @@ ABI = {
     "rt_scene_set_objects": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_scene_set_lights": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_void_p]),
     "rt_scene_set_light_intensity": (C.c_int, [C.c_void_p, C.c_double]),
+    "rt_scene_set_texels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rt_scene_set_texels_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rt_render_tiles_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtTiles), C.c_void_p, C.c_void_p,
                                          C.c_uint32, C.POINTER(RtStats)]),
     "rt_render_batch_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtTiles), C.c_uint32, C.c_void_p, C.c_uint64,
@@ -371,6 +373,54 @@ class Renderer:
         if isinstance(value, bool) or not isinstance(value, numbers.Real):
             raise ValueError("light intensity must be a number")
         _check(self.lib, self.lib.rt_scene_set_light_intensity(self.handle, float(value)), "rt_scene_set_light_intensity")
+
+    def texture_size(self, texture):
+        """(width, height) of texture `texture` of the resident scene, from the blob it was uploaded from (an edit never changes them)."""
+        n_textures, = struct.unpack_from("<I", self.blob, 176)
+        tex_off, = struct.unpack_from("<Q", self.blob, 200)
+        if isinstance(texture, bool) or not isinstance(texture, int) or not 0 <= texture < n_textures:
+            raise ValueError("texture must be an index below %d" % n_textures)
+        return struct.unpack_from("<II", self.blob, tex_off + TEXDESC_BYTES * texture)
+
+    def set_texels(self, texture, texels, x=0, y=0, width=None, height=None, pitch=0, stream=None):
+        """Replace the texels of the rectangle [x, x + width) x [y, y + height) of texture `texture` of the resident scene (default: from
+        (x, y) to the texture's right and bottom edge; with x = y = 0 the whole texture) with `texels`: bytes (height rows of `pitch`
+        bytes, 0 = 4 * width; the last row may end with its texels) or a (height, width, 4) uint8 array.  HOST memory, free again when
+        the call returns; enqueued on `stream` (None = the library's), ordered against the scene's renders on every stream: renders
+        issued before keep the old texels, the next one sees the new ones, nothing waits.  ValueError, before any library call, for
+        texels of the wrong size."""
+        tw, th = self.texture_size(texture)
+        for v in (x, y, pitch):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError("x, y and pitch must be non-negative integers")
+        w = tw - x if width is None else width
+        h = th - y if height is None else height
+        for v in (w, h):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError("the rectangle [%r, %r + %r) x [%r, %r + %r) is none of texture %d (%dx%d)" % (x, x, w, y, y, h, texture, tw, th))
+        if hasattr(texels, "shape"):
+            if tuple(texels.shape) != (h, w, 4) or str(texels.dtype) != "uint8" or pitch not in (0, 4 * w):
+                raise ValueError("texels must be a (%d, %d, 4) uint8 array (got %r %s)" % (h, w, tuple(texels.shape), texels.dtype))
+            data = texels.tobytes()
+        elif isinstance(texels, (bytes, bytearray, memoryview)):
+            data = bytes(texels)
+        else:
+            raise ValueError("texels must be bytes or a (height, width, 4) uint8 array")
+        row = pitch or 4 * w
+        if pitch and (pitch < 4 * w or pitch % 4):
+            raise ValueError("pitch must be 0 or a multiple of 4 that is at least 4 * width")
+        need = 0 if w == 0 or h == 0 else (h - 1) * row + 4 * w
+        if len(data) != need and len(data) != h * row:
+            raise ValueError("%d rows of %d texels at a pitch of %d bytes are %d bytes, got %d" % (h, w, row, need, len(data)))
+        buf = C.create_string_buffer(data, max(len(data), 1))
+        _check(self.lib, self.lib.rt_scene_set_texels(self.handle, texture, x, y, w, h, buf, pitch, C.c_void_p(stream or 0)), "rt_scene_set_texels")
+
+    def set_texels_device(self, texture, src_ptr, x, y, width, height, pitch=0, stream=None):
+        """The same from DEVICE memory (src_ptr: 4-byte aligned, `height` rows of `pitch` bytes, 0 = 4 * width): one copy kernel on
+        `stream`, behind whatever wrote src_ptr there - a frame render_tiles has just put into it becomes the texture without leaving
+        the GPU and without a host wait."""
+        _check(self.lib, self.lib.rt_scene_set_texels_device(self.handle, texture, x, y, width, height, C.c_void_p(src_ptr or 0), pitch,
+                                                             C.c_void_p(stream or 0)), "rt_scene_set_texels_device")
 
     def render_tiles(self, w, h, d_out, tiles=None, stream=None, flags=0, want_stats=False):
         t = tiles if isinstance(tiles, RtTiles) else RtTiles(*(tiles or (h, 0, 1, 1)))

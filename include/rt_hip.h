@@ -269,6 +269,36 @@ int rt_scene_set_lights(rt_scene_dev *scene, uint32_t first, uint32_t count, con
  * rules as for rt_scene_set_camera.  Any value is valid, as in a blob. */
 int rt_scene_set_light_intensity(rt_scene_dev *scene, double light_intensity);
 
+/* Replace texels of one texture of a resident scene (the reference's textures are ImageData, createTexture / loadTexture,
+ * main.js:339-395, which a page may draw into between two redraws; sampled one texel at a time, main.js:343-351): the rectangle
+ * [x, x + w) x [y, y + h) of texture `texture` takes h source rows of w RGBA8 texels, top row first.  Source row j starts at
+ * rgba + j * pitch_bytes; pitch_bytes 0 means 4 * w.  All four bytes of a texel are stored as given (the samplers never read alpha).
+ * Widths, heights, descriptors, n_textures and everything else of the scene stay: a texture of another size is an upload.
+ * ORDER is the contract: a launch of this scene issued before the call - colour, strict, batch, scatter, hits, pick, ray list,
+ * occlusion, shade, on any stream, in the order the API was called - reads the old texels in full, a launch issued after it the new
+ * ones in full, and nothing waits on the host.  Unlike the other edits this one USES `hip_stream` (NULL = the library's stream for the
+ * scene's device): the write is enqueued there.  Launches of the scene in flight on another stream are covered by an event (on
+ * several streams: the device is drained first, as for a camera move), and later launches on other streams wait for the write by
+ * event, as they wait for a move.  Only stream and event order at kernel boundaries is relied on.  Texels need no generation: they
+ * live once in the resident scene, and no table, launch decision or mark count depends on a texel's value.
+ * rt_scene_set_texels: `rgba` is HOST memory (any alignment), free to be reused as soon as the call returns: the rows are staged in
+ * pinned memory of the scene - 4 MiB, sixteen slots of 256 KiB, allocated by the scene's first host edit - and an edit of more than a
+ * slot goes through in pieces of whole rows.  A piece waits on the host only for the slot it needs, i.e. for a piece sixteen pieces
+ * before it (of this edit, or - a caller that many edits ahead of the GPU - of an earlier one).
+ * rt_scene_set_texels_device: `d_rgba` is DEVICE memory, 4-byte aligned, that does not overlap the texture; the library's kernel
+ * rt_texels_blit - one dword per work-item, grid ceil(w / 256) x h - copies it on `hip_stream`, behind whatever produced d_rgba there.
+ * The renderer writes RGBA8 rows, top row first, so a frame or an equirectangular panorama traced on the GPU becomes a texture of this
+ * or another scene without leaving the GPU: `render probe; rt_scene_set_texels_device; render frame` on one stream holds no runtime
+ * copy and no host wait.
+ * RT_ERR_INVALID, before a device is touched and with the scene left as it was: a NULL source with w * h > 0; pitch_bytes non-zero
+ * and below 4 * w, or no multiple of 4; a device source that is not 4-byte aligned; then RT_ERR_STATE for a NULL scene; then
+ * RT_ERR_INVALID for texture >= n_textures and for a rectangle that leaves the texture (computed in 64 bits: x = 2^32 - 1, w = 2 is
+ * refused).  w == 0 or h == 0 with the rest valid is RT_OK and changes nothing.  Thread rules as for rt_scene_set_camera. */
+int rt_scene_set_texels(rt_scene_dev *scene, uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const void *rgba,
+                        size_t pitch_bytes, void *hip_stream);
+int rt_scene_set_texels_device(rt_scene_dev *scene, uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const void *d_rgba,
+                               size_t pitch_bytes, void *hip_stream);
+
 /* Render tiles of the w x h frame into DEVICE memory `d_out_rgba` (at least
  * n_tiles*tile_rows*w*4 bytes) on `hip_stream` (a hipStream_t; NULL = the library's own
  * stream for that device).  Asynchronous unless `stats` is non-NULL (then it waits and
@@ -304,8 +334,9 @@ int rt_ipc_close(int device, void *d_ptr);
  * the next band's render; into smaller pinned frames the trace kernel stores directly, over PCIe.  Either way the call takes about
  * max(kernel, frame bytes / PCIe rate).  With more than one GPU in use the frame is sharded by interleaved row tiles and put
  * together on GPU 0 (peer stores, or one RCCL gather) before the copy-out.  The scene stays resident between calls: a blob that
- * differs from the previous call's only in the camera, stars_seed, sphere records, light positions and / or light_intensity is not
- * uploaded again (the resident scene takes the spheres of the smallest range that covers the differences, rt_scene_set_objects, then
+ * differs from the previous call's only in the texels of its textures, the camera, stars_seed, sphere records, light positions and /
+ * or light_intensity is not uploaded again (the resident scene takes, per texture whose texels differ, the full-width rows of the
+ * smallest range that covers the differences, rt_scene_set_texels, then the spheres of the smallest range that covers theirs, rt_scene_set_objects, then
  * the lights of theirs, rt_scene_set_lights, then the intensity, rt_scene_set_light_intensity, then moves its camera,
  * rt_scene_set_camera, and takes the seed, rt_scene_set_stars_seed; an edit any of these refuses with RT_ERR_UNSUPPORTED is uploaded).  Replaces redraw()/spanish() + ImageData (main.js:83,180-201). */
 int rt_render(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h,
