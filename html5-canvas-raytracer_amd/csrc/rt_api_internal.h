@@ -3,7 +3,7 @@
 //   rt_api.hip     lifetime, errors, device state, the scratch guard and the per-variant scratch figures, the host-logic probes, memory helpers, IPC
 //   rt_scene.hip   upload and moves of a resident scene (the generation pipeline), its texel edits (rt_texels.hip), its launch decisions and launch tables
 //   rt_launch.hip  the launches: colour (the launch record, then the strict launch or the product launch and rt_retrace), supersampling,
-//                  compact bands, primary hits and picking, ray lists, occlusion queries
+//                  compact bands, adaptive supersampling (rt_adaptive.hip), primary hits and picking, ray lists, occlusion queries
 //   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick, and the host lists that go
 //                  through device buffers in chunks (rt_trace_rays, rt_occlusion and their binned forms, rt_shade_rays), rt_trace_rays_wavefront
 //   rt_nodes_api.hip  the wavefront form's device entry points: one level of nodes, the next level's ray list, the fold (rt_nodes.hip)
@@ -36,6 +36,7 @@
 #include "rt_occlusion.h"
 #include "rt_nodes.h"
 #include "rt_texels.h"
+#include "rt_adaptive.h"
 
 // per build of rt_kernel.hip (product, strict): the variant's kernel (NULL: not this build's) and its launch
 extern "C" const void *rt_kernel_trace_fast(rt_trace_variant);

@@ -316,6 +316,41 @@ extern "C" int rt_render_hits(const void *blob, size_t bytes, uint32_t w, uint32
   return RT_OK;
 }
 
+// Adaptive supersampling of a whole frame on the resident scene (rt_launch.hip: rt_render_adaptive_device), outputs in HOST memory.
+extern "C" int rt_render_adaptive(const void *blob, size_t bytes, uint32_t w, uint32_t h, uint32_t k, uint32_t threshold, uint8_t *out_rgba, uint8_t *out_mask,
+                                  uint32_t flags, rt_stats *stats, uint64_t *refined) {
+  if (!out_rgba) return fail(RT_ERR_INVALID, "rt_render_adaptive: NULL output");
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  const size_t work_bytes = rt_adaptive_work_bytes(w, h);
+  if (!work_bytes) return fail(RT_ERR_INVALID, "rt_render_adaptive: frame size %ux%u not in 1..32768", w, h);
+  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
+  std::lock_guard<std::mutex> lk(G.mu);
+  const auto t_begin = std::chrono::steady_clock::now();
+  rt_scene_dev *s = nullptr;
+  if ((rc = scene_for(0, blob, bytes, &s))) return rc;
+  if ((rc = ensure_device(0))) return rc;
+  device_state &D = G.dev[0];
+  const size_t pixels = (size_t)w * h;
+  device_bufs<3> mem;                                  // the frame, the workspace, the mask
+  HIP_TRY(hipMalloc(&mem.p[0], pixels * 4u));
+  HIP_TRY(hipMalloc(&mem.p[1], work_bytes));
+  if (out_mask) HIP_TRY(hipMalloc(&mem.p[2], pixels));
+  rt_stats st;
+  if ((rc = rt_render_adaptive_device(s, w, h, k, threshold, mem.p[0], (uint8_t *)mem.p[2], mem.p[1], work_bytes, D.stream, flags, &st))) return rc;
+  uint32_t n_refined = 0;
+  HIP_TRY(hipMemcpyAsync(out_rgba, mem.p[0], pixels * 4u, hipMemcpyDeviceToHost, D.stream));
+  HIP_TRY(hipMemcpyAsync(&n_refined, mem.p[1], sizeof n_refined, hipMemcpyDeviceToHost, D.stream));
+  if (out_mask) HIP_TRY(hipMemcpyAsync(out_mask, mem.p[2], pixels, hipMemcpyDeviceToHost, D.stream));
+  HIP_TRY(hipStreamSynchronize(D.stream));
+  if (refined) *refined = n_refined;
+  if (stats) {
+    *stats = st;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return RT_OK;
+}
+
 extern "C" int rt_pick(const void *blob, size_t bytes, uint32_t w, uint32_t h, uint32_t n, const uint32_t *xy, rt_hit *out) {
   int rc = rt_scene_validate(blob, bytes);
   if (rc) return rc;

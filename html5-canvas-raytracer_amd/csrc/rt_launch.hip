@@ -572,6 +572,103 @@ int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *t
 }
 }  // namespace
 
+// ------------------------------------------------------------------------------------ adaptive supersampling (rt_adaptive.hip)
+// k x k samples only where the frame has edges (include/rt_hip.h: rt_render_adaptive_device).  Three launches follow each other on the
+// caller's stream, with no allocation and no host wait between them: the ordinary colour launch of the supersample-1 frame
+// (render_batch_impl, unchanged: the same tables, marks and rt_retrace, the same bytes), rt_adaptive_mark - the criterion on that frame,
+// the list of pixels to refine in the caller's workspace - and rt_adaptive_refine<refract, k>, which traces the listed pixels' samples
+// on a launch record of the k w x k h sample grid bound as rt_retrace's (fill_launch with the plain binding) and stores their box-filtered
+// bytes over the base frame's.  The refine kernel keeps a recursion stack: its scratch figure goes through scratch_guard like every other.
+extern "C" size_t rt_adaptive_work_bytes(uint32_t w, uint32_t h) {
+  return (w == 0 || h == 0 || w > 65536u / 2u || h > 65536u / 2u) ? 0 : (size_t)rt_adaptive_bytes(w, h);      // (k >= 2: a side above 32768 is refused for every k)
+}
+
+#ifdef RT_TESTING
+// Test build only: the criterion and the box rule of rt_adaptive.h as plain host code, without a GPU.  mask_out: w * h bytes, 1 = refined.
+extern "C" int rt_test_adaptive_mask(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t threshold, uint8_t *mask_out) {
+  if (!rgba || !mask_out || w == 0 || h == 0 || threshold > 256u) return fail(RT_ERR_INVALID, "rt_test_adaptive_mask: NULL argument, empty frame or threshold above 256");
+  const auto at = [&](uint32_t x, uint32_t y) { uint32_t v; memcpy(&v, rgba + ((size_t)y * w + x) * 4u, 4u); return v; };
+  for (uint32_t y = 0; y < h; y++)
+    for (uint32_t x = 0; x < w; x++) {
+      const uint32_t c = at(x, y);
+      mask_out[(size_t)y * w + x] = rt_adaptive_refines(c, x > 0u ? at(x - 1u, y) : c, x + 1u < w ? at(x + 1u, y) : c, y > 0u ? at(x, y - 1u) : c,
+                                                        y + 1u < h ? at(x, y + 1u) : c, threshold) ? 1u : 0u;
+    }
+  return RT_OK;
+}
+extern "C" uint32_t rt_test_adaptive_box(uint32_t sum, uint32_t k) { return rt_adaptive_box(sum, k); }
+#endif
+
+namespace {
+// the scratch bytes per lane of rt_adaptive_refine<refract, k>, asked once per kernel
+int adaptive_scratch(bool refract, uint32_t k, size_t *out) {
+  static std::mutex mu;
+  static size_t cache[2][5];
+  static bool have[2][5];
+  std::lock_guard<std::mutex> lk(mu);
+  if (!have[refract][k]) {
+    size_t b = 0;
+    const int e = rt_scratch_adaptive_refine(refract, k, &b);
+    if (e != 0) return fail(RT_ERR_DEVICE, "hipFuncGetAttributes: %s", hipGetErrorString((hipError_t)e));
+    cache[refract][k] = b; have[refract][k] = true;
+  }
+  *out = cache[refract][k];
+  return RT_OK;
+}
+}  // namespace
+
+// (the arguments first: they are judged without a scene, and before a device is touched)
+extern "C" int rt_render_adaptive_device(rt_scene_dev *s, uint32_t w, uint32_t h, uint32_t k, uint32_t threshold, void *d_out, uint8_t *d_mask,
+                                         void *d_work, size_t work_bytes, void *hip_stream, uint32_t flags, rt_stats *stats) {
+  const char *const what = "rt_render_adaptive_device";
+  if (k < 2u || k > 4u) return fail(RT_ERR_INVALID, "%s: k %u not in 2..4", what, k);
+  if (threshold > 256u) return fail(RT_ERR_INVALID, "%s: threshold %u not in 0..256", what, threshold);
+  if (w == 0 || h == 0 || (uint64_t)w * k > 65536u || (uint64_t)h * k > 65536u)
+    return fail(RT_ERR_INVALID, "%s: frame size %ux%u: the %llu x %llu sample grid is not in 1..65536", what, w, h, (unsigned long long)w * k, (unsigned long long)h * k);
+  if (!d_out || !d_work) return fail(RT_ERR_INVALID, "%s: NULL output or workspace", what);
+  if (((uintptr_t)d_out & 3u) || ((uintptr_t)d_work & 3u)) return fail(RT_ERR_INVALID, "%s: misaligned output or workspace (4 bytes)", what);
+  if (work_bytes < rt_adaptive_work_bytes(w, h))
+    return fail(RT_ERR_INVALID, "%s: work_bytes %llu below rt_adaptive_work_bytes(%u, %u) = %llu", what, (unsigned long long)work_bytes, w, h, (unsigned long long)rt_adaptive_work_bytes(w, h));
+  if (flags & ~(uint32_t)RT_FLAG_STRICT_FP) return fail(RT_ERR_INVALID, "%s: flags 0x%x: only RT_FLAG_STRICT_FP applies (to the base launch)", what, flags);
+  if (!s) return fail(RT_ERR_STATE, "%s: NULL scene handle", what);
+  if (s->hd.supersample != 1u) return fail(RT_ERR_INVALID, "%s: the scene's header supersample is %u: the base frame is a supersample-1 frame", what, s->hd.supersample);
+  hipStream_t stream = nullptr;
+  int rc = scene_stream(s, hip_stream, &stream);
+  if (rc) return rc;
+  device_state &D = G.dev[s->device];
+  // the refine launch's grid: a workgroup holds 4 waves x 64 / (k k) pixels per turn of its loop; the count is only known on the device
+  const uint64_t per_wg = (uint64_t)(RT_WG_THREADS / 64u) * (64u / (k * k)), wgs = ((uint64_t)w * h + per_wg - 1u) / per_wg;
+  const unsigned n_wg = (unsigned)(wgs < 8192u ? wgs : 8192u);      // (measured at 3840x2160: 2048, 1024, 512, 256 workgroups are each slower: docs/EVIDENCE.md)
+  size_t per_lane = 0;
+  if ((rc = adaptive_scratch(s->refract, k, &per_lane))) return rc;
+  if ((rc = scratch_guard(D, stream, per_lane, (uint64_t)n_wg * (RT_WG_THREADS / 64u), "the adaptive refine kernel (rt_adaptive_refine)"))) return rc;
+  stats_clock clock;
+  if ((rc = clock.start(stats, stream))) return rc;
+
+  // 1. the base frame
+  const rt_tiles whole = {h, 0u, 1u, 1u};
+  if ((rc = render_batch_impl(s, w, h, &whole, 1u, d_out, 0u, nullptr, hip_stream, flags, nullptr))) return rc;
+
+  // 2. the criterion
+  HIP_TRY(hipMemsetAsync(d_work, 0, RT_ADAPTIVE_HEADER_BYTES, stream));
+  const rt_adaptive_mark_launch M = {(const uint32_t *)d_out, d_mask, (uint32_t *)d_work, w, h, threshold};
+  if ((rc = launched(rt_launch_adaptive_mark(&M, stream)))) return rc;
+
+  // 3. the listed pixels, from the k w x k h sample grid (a whole frame of it, one sample per "pixel" of the record: supersample 1)
+  const rt_tiles grid_tiles = {h * k, 0u, 1u, 1u};
+  const colour_call c = {s, D, stream, w * k, h * k, 1u, &grid_tiles, 1u, 0u, false, false, false, read_test_switches()};
+  rt_launch F;
+  {
+    std::lock_guard<std::mutex> lk(s->launch_mu);
+    if ((rc = behind_the_camera(s, stream))) return rc;
+    note_launch(s, stream);
+    if ((rc = fill_launch(c, true, s->hd.stars_seed, nullptr, 0u, nullptr, F))) return rc;      // (strict: the scene in its own order, as rt_retrace is bound)
+  }
+  const rt_adaptive_refine_launch A = {(const uint32_t *)d_work, (uint32_t *)d_out, w};
+  if ((rc = launched(rt_launch_adaptive_refine(&F, &A, s->refract ? 1 : 0, k, n_wg, stream)))) return rc;
+  return clock.finish(stats, (uint64_t)w * h);
+}
+
 // ------------------------------------------------------------------------------------ compact bands (RT_FLAG_COMPACT)
 namespace {
 // The launch table a compact launch over `tiles` uses (found, or built now on `stream`), under launch_mu: its index in *oi, the rows

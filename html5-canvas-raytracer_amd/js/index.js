@@ -33,9 +33,19 @@ function flagsOf(opts) { return ((opts && opts.count) ? FLAG_COUNT : 0) | ((opts
 // writes into it again (main.js:195-200).  Hand in what an earlier render() returned (pinned memory: the GPU stores into it
 // directly, nothing is allocated) - or any Uint8ClampedArray of 4*width*height bytes, e.g. a canvas ImageData.data (pageable
 // memory: the frame is copied out of the GPU's memory, about half the rate).  Returns that same array.
+// opts.adaptive: {k, threshold} - adaptive supersampling: the frame of a scene whose own supersample is 1, with k x k samples (k 2..4,
+// default 4) for the pixels that differ from a 4-neighbour by `threshold` (0..256, default 32) or more in R, G or B; `.stats.refined`
+// says how many pixels that were.  On one GPU.
+function adaptiveOf(opts) {
+  const a = opts && opts.adaptive;
+  if (!a) return null;
+  return {k: a.k === undefined ? 4 : a.k, threshold: a.threshold === undefined ? 32 : a.threshold};
+}
 function render(width, height, sceneObj, opts) {
   if (!inited) init(opts && opts.maxDevices);
-  const r = native().render(flattenScene(sceneObj), width, height, flagsOf(opts), (opts && opts.into) || undefined);
+  const ad = adaptiveOf(opts);
+  const r = ad ? native().renderAdaptive(flattenScene(sceneObj), width, height, flagsOf(opts), ad.k, ad.threshold, (opts && opts.into) || undefined)
+    : native().render(flattenScene(sceneObj), width, height, flagsOf(opts), (opts && opts.into) || undefined);
   r.data.stats = r.stats;
   return r.data;
 }
@@ -43,7 +53,10 @@ function render(width, height, sceneObj, opts) {
 // Promise variant: the launch and the copy-out run off the event loop (napi_async_work)
 function renderAsync(width, height, sceneObj, opts) {
   try { if (!inited) init(opts && opts.maxDevices); } catch (e) { return Promise.reject(e); }
-  return native().renderAsync(flattenScene(sceneObj), width, height, flagsOf(opts)).then((r) => { r.data.stats = r.stats; return r.data; });
+  const ad = adaptiveOf(opts);
+  const p = ad ? native().renderAdaptive(flattenScene(sceneObj), width, height, flagsOf(opts), ad.k, ad.threshold, undefined, true)
+    : native().renderAsync(flattenScene(sceneObj), width, height, flagsOf(opts));
+  return p.then((r) => { r.data.stats = r.stats; return r.data; });
 }
 
 // Progressive variant: the reference shows its frame row by row (one spanish(y) per macrotask, main.js:183-201); here

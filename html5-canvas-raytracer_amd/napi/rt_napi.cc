@@ -6,6 +6,8 @@
 //
 // Exports:  init(maxDevices) -> deviceCount      render(blob, w, h, flags) -> {data, width, height, stats}
 //           renderAsync(blob, w, h, flags) -> Promise of the same        shutdown()      abiVersion()
+//           renderAdaptive(blob, w, h, flags, k, threshold[, into[, async]]) -> the same (or a Promise of it), stats.refined added:
+//           adaptive supersampling (rt_render_adaptive)
 //           renderProgressive(blob, w, h, flags, bands, onBand(firstRow, nRows)) -> {data, promise}: `data` is the frame
 //           being filled; onBand fires on the main thread as each row band lands in it; the promise resolves to the stats
 //           renderHits(blob, w, h, wantDepth, wantNormal) -> {id: Int32Array, depth: Float64Array | null, normal: Float32Array | null}
@@ -15,7 +17,7 @@
 //           bin: rt_trace_rays_binned, the list ordered on the GPU first - the same results; two more booleans, wavefront and
 //           orderLevels: rt_trace_rays_wavefront, the same rgb and rgba level by level, plus levelCounts)
 //           shadeRays(blob, rays, pix: Uint32Array | null, path: Uint32Array | null, bin) -> {nodes: ArrayBuffer of rt_node records, count}
-//           (these three are not enumerable: the enumerable surface is the frame API)
+//           (these, and renderAdaptive, are not enumerable: the enumerable surface is the frame API of the first revision)
 // Every failure of the library becomes a thrown JS Error carrying rt_last_error().
 //
 // Build: g++ -shared -fPIC -I/usr/include/node rt_napi.cc -L../csrc -lrt_hip  (napi/Makefile; no node-gyp).
@@ -52,6 +54,8 @@ struct args {
   bool owned = false;
   size_t bytes = 0;
   uint32_t w = 0, h = 0, flags = 0;
+  uint32_t k = 0, threshold = 0;   // renderAdaptive: k x k samples where the frame has edges (k == 0: a plain render)
+  uint64_t refined = 0;
   uint8_t *out = nullptr;
   rt_stats st{};
   int rc = 0;
@@ -116,6 +120,7 @@ napi_value make_result(napi_env env, args *a, napi_value into = nullptr) {
   napi_create_double(env, (double)a->st.shadow_rays, &v); napi_set_named_property(env, stats, "shadow_rays", v);
   napi_create_double(env, (double)a->st.sphere_tests, &v); napi_set_named_property(env, stats, "sphere_tests", v);
   napi_create_double(env, (double)a->st.exact_samples, &v); napi_set_named_property(env, stats, "exact_samples", v);
+  if (a->k) { napi_create_double(env, (double)a->refined, &v); napi_set_named_property(env, stats, "refined", v); }
   { char rep[96]; napi_value sv; if (rt_elapsed_report(&a->st, rep, sizeof rep) > 0) { napi_create_string_utf8(env, rep, NAPI_AUTO_LENGTH, &sv); napi_set_named_property(env, stats, "report", sv); }
     napi_create_string_utf8(env, rt_build_id(), NAPI_AUTO_LENGTH, &sv); napi_set_named_property(env, stats, "build", sv); }
   napi_set_named_property(env, res, "stats", stats);
@@ -179,7 +184,8 @@ void exec_async(napi_env, void *p) {
   args *a = (args *)p;
   a->out = (uint8_t *)rt_alloc_pinned((size_t)a->w * a->h * 4u);
   if (!a->out) { a->rc = RT_ERR_NOMEM; a->err = rt_last_error(); return; }
-  a->rc = rt_render(a->blob, a->bytes, a->w, a->h, a->out, a->flags, &a->st);
+  a->rc = a->k ? rt_render_adaptive(a->blob, a->bytes, a->w, a->h, a->k, a->threshold, a->out, nullptr, a->flags, &a->st, &a->refined)
+               : rt_render(a->blob, a->bytes, a->w, a->h, a->out, a->flags, &a->st);
   if (a->rc != RT_OK) { a->err = rt_last_error(); rt_free_pinned(a->out); a->out = nullptr; }   // rt_last_error is per thread: read it here
 }
 
@@ -190,7 +196,7 @@ void done_async(napi_env env, napi_status, void *p) {
     if (res) napi_resolve_deferred(env, a->deferred, res);
   } else {
     napi_value msg, err;
-    std::string m = "rt_render failed (" + std::to_string(a->rc) + "): " + a->err;
+    std::string m = std::string(a->k ? "rt_render_adaptive" : "rt_render") + " failed (" + std::to_string(a->rc) + "): " + a->err;
     napi_create_string_utf8(env, m.c_str(), NAPI_AUTO_LENGTH, &msg);
     napi_create_error(env, nullptr, msg, &err);
     napi_reject_deferred(env, a->deferred, err);
@@ -209,6 +215,59 @@ napi_value RenderAsync(napi_env env, napi_callback_info info) {
   NAPI_TRY(napi_create_async_work(env, nullptr, name, exec_async, done_async, a, &a->work));
   NAPI_TRY(napi_queue_async_work(env, a->work));
   return promise;
+}
+
+// renderAdaptive(blob, width, height, flags, k, threshold[, into[, async]]): the supersample-1 frame with k x k samples (k 2..4) for
+// the pixels that differ from a 4-neighbour by `threshold` (0..256) or more (rt_render_adaptive); stats.refined is how many there were.
+// `into` as for render; async === true: a Promise of the same result, the work off the event loop (no `into` then).
+napi_value RenderAdaptive(napi_env env, napi_callback_info info) {
+  size_t argc = 8;
+  napi_value argv[8];
+  napi_valuetype t = napi_undefined;
+  bool async = false;
+  uint32_t k = 0, threshold = 0;
+  napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr);
+  if (argc < 6 || napi_get_value_uint32(env, argv[4], &k) != napi_ok || napi_get_value_uint32(env, argv[5], &threshold) != napi_ok || k == 0) {
+    napi_throw_type_error(env, nullptr, "renderAdaptive(blob, width, height, flags, k, threshold[, into[, async]])");
+    return nullptr;
+  }
+  if (argc >= 8) napi_get_value_bool(env, argv[7], &async);
+  if (argc >= 7) napi_typeof(env, argv[6], &t);
+  const bool have_into = argc >= 7 && t != napi_undefined && t != napi_null;
+  args *a = new args();
+  if (!parse(env, info, a, async)) { if (a->owned) free(a->blob); delete a; return nullptr; }
+  a->k = k; a->threshold = threshold;
+  if (async) {
+    napi_value promise, name;
+    if (have_into) { if (a->owned) free(a->blob); delete a; napi_throw_type_error(env, nullptr, "renderAdaptive: no `into` with async"); return nullptr; }
+    NAPI_TRY(napi_create_promise(env, &a->deferred, &promise));
+    napi_create_string_utf8(env, "rt_render_adaptive", NAPI_AUTO_LENGTH, &name);
+    NAPI_TRY(napi_create_async_work(env, nullptr, name, exec_async, done_async, a, &a->work));
+    NAPI_TRY(napi_queue_async_work(env, a->work));
+    return promise;
+  }
+  napi_value res = nullptr;
+  uint8_t *dst = nullptr;
+  if (have_into) {
+    bool is_ta = false;
+    napi_is_typedarray(env, argv[6], &is_ta);
+    napi_typedarray_type tt = napi_int8_array; size_t len = 0, off = 0; void *data = nullptr; napi_value ab;
+    if (is_ta) napi_get_typedarray_info(env, argv[6], &tt, &len, &data, &ab, &off);
+    if (!is_ta || (tt != napi_uint8_array && tt != napi_uint8_clamped_array) || len != (size_t)a->w * a->h * 4u || !data)
+      napi_throw_type_error(env, nullptr, "into must be a Uint8ClampedArray / Uint8Array of 4*width*height bytes");
+    else dst = (uint8_t *)data;
+  } else {
+    dst = a->out = (uint8_t *)rt_alloc_pinned((size_t)a->w * a->h * 4u);
+    if (!dst) throw_rt(env, "rt_alloc_pinned", RT_ERR_NOMEM);
+  }
+  if (dst) {
+    a->rc = rt_render_adaptive(a->blob, a->bytes, a->w, a->h, a->k, a->threshold, dst, nullptr, a->flags, &a->st, &a->refined);
+    if (a->rc != RT_OK) { if (a->out) rt_free_pinned(a->out); a->out = nullptr; res = throw_rt(env, "rt_render_adaptive", a->rc); }
+    else res = make_result(env, a, have_into ? argv[6] : nullptr);
+  }
+  if (a->owned) free(a->blob);
+  delete a;
+  return res;
 }
 
 // ---- progressive delivery: the frame buffer exists from the start (the page can keep a view of it), bands are announced
@@ -621,6 +680,7 @@ napi_value Module(napi_env env, napi_value exports) {
       {"init", nullptr, Init, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"render", nullptr, Render, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"renderAsync", nullptr, RenderAsync, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"renderAdaptive", nullptr, RenderAdaptive, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"renderProgressive", nullptr, RenderProgressive, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"validate", nullptr, Validate, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"shutdown", nullptr, Shutdown, nullptr, nullptr, nullptr, napi_enumerable, nullptr},

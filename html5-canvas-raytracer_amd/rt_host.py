@@ -250,6 +250,11 @@ ABI = {
                                                C.c_uint64, C.c_void_p]),
     "rt_render_hits_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RtTiles), C.POINTER(RtHitBuffers), C.c_void_p,
                                         C.POINTER(RtStats)]),
+    "rt_adaptive_work_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_render_adaptive_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_void_p, C.c_uint32, C.POINTER(RtStats)]),
+    "rt_render_adaptive": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                     C.POINTER(RtStats), C.POINTER(C.c_uint64)]),
     "rt_scene_pick": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(RtHit)]),
     "rt_render_hits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(RtHitBuffers), C.POINTER(RtStats)]),
     "rt_pick": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(RtHit)]),
@@ -473,6 +478,17 @@ class Renderer:
         _check(self.lib, rc, "rt_render_hits_device")
         return st
 
+    def render_adaptive(self, w, h, d_out, k, threshold, work_ptr, work_bytes, mask_ptr=0, stream=None, flags=0, want_stats=False):
+        """Adaptive supersampling of the whole w x h frame into DEVICE memory: the supersample-1 frame, then k x k samples (k 2..4) for
+        the pixels that differ from a 4-neighbour by `threshold` (0..256) or more in R, G or B.  work_ptr: work_bytes >=
+        adaptive_work_bytes(w, h) bytes of device workspace, whose first uint32 holds the number of refined pixels when the work is
+        done; mask_ptr (0 / None = not wanted): w * h bytes, 1 = refined.  flags: 0 or RT_FLAG_STRICT_FP (the base launch's)."""
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_render_adaptive_device(self.handle, w, h, k, threshold, C.c_void_p(d_out or 0), C.c_void_p(mask_ptr or 0), C.c_void_p(work_ptr or 0),
+                                                work_bytes, C.c_void_p(stream or 0), flags, C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_render_adaptive_device")
+        return st
+
     def pick(self, w, h, points):
         """Hit records of sample points [(x, y), ...] (sample-grid coordinates), with the scene's current camera: a list of dicts
         (_hit_dict), None for a miss."""
@@ -648,6 +664,53 @@ def pick(width, height, scene, points, lib=None):
     _init_once(lib)
     buf = C.create_string_buffer(blob, len(blob))
     return _pick_call(lib, lambda n, xy, out: lib.rt_pick(buf, len(blob), width, height, n, xy, out), n, xy, "rt_pick")
+
+
+def adaptive_work_bytes(w, h, lib=None):
+    """Bytes of device workspace Renderer.render_adaptive needs for a w x h frame (host arithmetic: 16 + 4 w h; 0 for an empty frame or a
+    side above 32768)."""
+    return int((lib or load_library()).rt_adaptive_work_bytes(w, h))
+
+
+def render_adaptive(width, height, scene, k=4, threshold=32, want_mask=False, flags=0, lib=None):
+    """render_adaptive(width,height,scene) -> (bytes RGBA8, RtStats, refined pixels[, mask bytes]): the supersample-1 frame with k x k
+    samples where it has edges (Renderer.render_adaptive), on GPU 0 with rt_render's resident scene, host buffers out."""
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    _init_once(lib)
+    out = C.create_string_buffer(width * height * 4)
+    mask = C.create_string_buffer(width * height) if want_mask else None
+    st, refined = RtStats(), C.c_uint64()
+    buf = C.create_string_buffer(blob, len(blob))
+    _check(lib, lib.rt_render_adaptive(buf, len(blob), width, height, k, threshold, out, mask, flags, C.byref(st), C.byref(refined)), "rt_render_adaptive")
+    res = (out.raw, st, int(refined.value))
+    return res + (mask.raw,) if want_mask else res
+
+
+def adaptive_mask(frame, w, h, threshold):
+    """The criterion of adaptive supersampling in numpy: an (h, w) uint8 array, 1 where the pixel of the RGBA8 `frame` (bytes or array)
+    has a 4-neighbour inside the frame that differs from it by at least `threshold` in R, G or B (integers; alpha plays no part).
+    threshold 0 marks every pixel - a 1 x 1 frame's too -, 256 none."""
+    import numpy as np
+    f = np.frombuffer(frame, np.uint8) if isinstance(frame, (bytes, bytearray, memoryview)) else np.asarray(frame, np.uint8)
+    f = f.reshape(h, w, 4)[..., :3].astype(np.int32)
+    m = np.zeros((h, w), np.int32)                        # the largest difference to a neighbour; no neighbour: 0
+    dx = np.abs(f[:, 1:] - f[:, :-1]).max(axis=2)
+    dy = np.abs(f[1:, :] - f[:-1, :]).max(axis=2)
+    m[:, 1:] = np.maximum(m[:, 1:], dx); m[:, :-1] = np.maximum(m[:, :-1], dx)
+    m[1:, :] = np.maximum(m[1:, :], dy); m[:-1, :] = np.maximum(m[:-1, :], dy)
+    return (m >= int(threshold)).astype(np.uint8)
+
+
+def adaptive_compose(base, fine, mask):
+    """The adaptive frame from its parts: `fine`'s pixel where `mask` is set, `base`'s elsewhere.  base, fine: RGBA8 frames of one size
+    (bytes or arrays); mask: (h, w).  Returns an (h, w, 4) uint8 array."""
+    import numpy as np
+    m = np.asarray(mask).astype(bool)
+    h, w = m.shape
+    b = (np.frombuffer(base, np.uint8) if isinstance(base, (bytes, bytearray, memoryview)) else np.asarray(base, np.uint8)).reshape(h, w, 4)
+    f = (np.frombuffer(fine, np.uint8) if isinstance(fine, (bytes, bytearray, memoryview)) else np.asarray(fine, np.uint8)).reshape(h, w, 4)
+    return np.where(m[..., None], f, b)
 
 
 def normal3d(v):

@@ -446,6 +446,47 @@ int rt_scene_pick(rt_scene_dev *scene, uint32_t w, uint32_t h, uint32_t n, const
 int rt_render_hits(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h, const rt_hit_buffers *host_bufs, rt_stats *stats);
 int rt_pick(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h, uint32_t n, const uint32_t *sample_xy, rt_hit *out);
 
+/* Adaptive supersampling: k x k samples only where the frame has edges.  `supersample` k renders every pixel k k times; Whitted's own
+ * paper supersampled only where neighbouring samples disagree.  For a resident scene whose header supersample is 1, a frame size
+ * w x h, a factor k in {2, 3, 4} and a threshold T in 0..256:
+ *   base      B is the frame rt_render_tiles_device(scene, w, h, the whole frame, flags) stores: the same launches, the same bytes.
+ *   criterion pixel (x, y) is refined iff it has a 4-neighbour (x +- 1, y) or (x, y +- 1) inside the frame whose stored byte differs from
+ *             its own by at least T in R, G or B (integers; alpha plays no part).  T = 0 refines every pixel (a 1 x 1 frame's too),
+ *             T = 256 none.  The criterion is evaluated entirely on B: no refined pixel is seen by it.
+ *   refine    a refined pixel becomes the pixel of the k-supersampled strict frame: its samples (k x + i, k y + j) of the k w x k h sample
+ *             grid - the primary ray of main.js:184-193 on that grid, the reference's own operation sequence without FMA contraction,
+ *             the scene's own segs, stars drawn with pix = sy * (k w) + sx and the scene's current seed, stored with the rule of
+ *             main.js:195-198 - averaged as (sum + k k / 2) / (k k) per channel, alpha 255: the bytes
+ *             rt_render_tiles_device(..., RT_FLAG_STRICT_FP) stores for the same scene with header supersample = k.
+ *   every other pixel keeps B's bytes.
+ * The whole frame only: the criterion looks across rows, so a tile set would change the picture.
+ *
+ * rt_adaptive_work_bytes: the bytes of DEVICE workspace a w x h frame needs; host arithmetic, no GPU, no rt_init: 16 + 4 w h; 0 for
+ * w == 0, h == 0 or a frame the call refuses for every k (a side above 32768). */
+size_t rt_adaptive_work_bytes(uint32_t w, uint32_t h);
+
+/* The adaptive frame into d_out_rgba (DEVICE memory, w * h RGBA8, 4-byte aligned).  d_mask (DEVICE, w * h bytes, or NULL) receives 1
+ * for a refined pixel and 0 for every other; d_work is work_bytes >= rt_adaptive_work_bytes(w, h) bytes of DEVICE workspace, 4-byte
+ * aligned: when the call's work is done its first uint32 holds the number of refined pixels (the words behind it are the list the
+ * refine launch walked, x | y << 16 each, in no particular order).  d_out_rgba, d_mask and d_work must not overlap.
+ * flags: 0 or RT_FLAG_STRICT_FP, which goes to the base launch.  Three launches follow each other on `hip_stream` (NULL = the library's
+ * stream for the scene's device) - the base frame, the criterion, the refined pixels - with no allocation and no host wait between
+ * them: asynchronous unless `stats` is non-NULL (then it waits and fills kernel_ms - all three -, total_ms and pixels = w h).  Pending
+ * edits of the scene (camera, objects, lights, texels) are waited for by event, as by every other launch; thread rules as
+ * rt_render_tiles_device.  The refine kernel keeps a recursion stack in scratch memory: a reservation the device cannot meet is
+ * RT_ERR_NOMEM.
+ * RT_ERR_INVALID, before a device is touched and with the scene left as it was: k outside 2..4, threshold above 256, w or h 0, k w or
+ * k h above 65536, a NULL or misaligned d_out_rgba or d_work, work_bytes too small, flags other than RT_FLAG_STRICT_FP; then
+ * RT_ERR_STATE: a NULL scene; then RT_ERR_INVALID: a scene whose header supersample is not 1. */
+int rt_render_adaptive_device(rt_scene_dev *scene, uint32_t w, uint32_t h, uint32_t k, uint32_t threshold,
+                              void *d_out_rgba, uint8_t *d_mask, void *d_work, size_t work_bytes, void *hip_stream, uint32_t flags, rt_stats *stats);
+
+/* The host form: rt_render's resident scene (a blob that differs from the resident one only in what an edit reaches is not uploaded
+ * again, as for rt_render_hits), outputs in HOST memory: out_rgba w * h * 4 bytes, out_mask w * h bytes or NULL, *refined (or NULL)
+ * the number of refined pixels.  Synchronous, on GPU 0. */
+int rt_render_adaptive(const void *scene_blob, size_t blob_bytes, uint32_t w, uint32_t h, uint32_t k, uint32_t threshold,
+                       uint8_t *out_rgba, uint8_t *out_mask, uint32_t flags, rt_stats *stats, uint64_t *refined);
+
 /* Caller-supplied rays.  The reference's unit of work is not the frame but intersectWorld(segs, objs, org, dir) (main.js:216-336), a
  * function of a ray; these entry points are that function for a LIST of rays - other projections (panoramas, cube faces, orthographic,
  * fisheye, stereo), depth of field and jittered sampling with the caller's own pattern, reflection / light probes at any point
