@@ -46,6 +46,16 @@ RT_HD inline uint32_t rt_adaptive_box(uint32_t sum, uint32_t k) { return (sum + 
 #define RT_ADAPTIVE_HEADER_BYTES 16u
 static inline uint64_t rt_adaptive_bytes(uint64_t w, uint64_t h) { return RT_ADAPTIVE_HEADER_BYTES + 4u * w * h; }
 
+// The refine launch's grid for a w x h frame at k x k samples: a workgroup is RT_ADAPTIVE_REFINE_WAVES waves and a wave holds 64 / (k k)
+// listed pixels per turn of its grid-stride loop (rt_adaptive.hip: rt_adaptive_refine).  The count is only known on the device, so the
+// grid is sized for the whole frame and capped; a list longer than one turn of the capped grid takes further turns.
+#define RT_ADAPTIVE_REFINE_WAVES 4u                                   // (RT_WG_THREADS / 64: rt_launch.hip holds the two to each other)
+#define RT_ADAPTIVE_REFINE_MAX_WGS 8192u                              // (measured at 3840x2160: 2048, 1024, 512, 256 workgroups are each slower: docs/EVIDENCE.md)
+static inline uint32_t rt_adaptive_refine_grid(uint32_t w, uint32_t h, uint32_t k) {
+  const uint64_t per_wg = (uint64_t)RT_ADAPTIVE_REFINE_WAVES * (64u / (k * k)), wgs = ((uint64_t)w * h + per_wg - 1u) / per_wg;
+  return (uint32_t)(wgs < RT_ADAPTIVE_REFINE_MAX_WGS ? wgs : RT_ADAPTIVE_REFINE_MAX_WGS);
+}
+
 #if defined(__HIPCC__)
 // rt_adaptive_mark's arguments (by value in the kernarg segment)
 struct rt_adaptive_mark_launch {

@@ -597,6 +597,8 @@ extern "C" int rt_test_adaptive_mask(const uint8_t *rgba, uint32_t w, uint32_t h
   return RT_OK;
 }
 extern "C" uint32_t rt_test_adaptive_box(uint32_t sum, uint32_t k) { return rt_adaptive_box(sum, k); }
+// ... and the refine launch's grid, so that a test knows whether a frame's list can outrun one turn of the kernel's loop
+extern "C" uint32_t rt_test_adaptive_refine_grid(uint32_t w, uint32_t h, uint32_t k) { return rt_adaptive_refine_grid(w, h, k); }
 #endif
 
 namespace {
@@ -636,9 +638,9 @@ extern "C" int rt_render_adaptive_device(rt_scene_dev *s, uint32_t w, uint32_t h
   int rc = scene_stream(s, hip_stream, &stream);
   if (rc) return rc;
   device_state &D = G.dev[s->device];
-  // the refine launch's grid: a workgroup holds 4 waves x 64 / (k k) pixels per turn of its loop; the count is only known on the device
-  const uint64_t per_wg = (uint64_t)(RT_WG_THREADS / 64u) * (64u / (k * k)), wgs = ((uint64_t)w * h + per_wg - 1u) / per_wg;
-  const unsigned n_wg = (unsigned)(wgs < 8192u ? wgs : 8192u);      // (measured at 3840x2160: 2048, 1024, 512, 256 workgroups are each slower: docs/EVIDENCE.md)
+  // the refine launch's grid (rt_adaptive.h): the count is only known on the device
+  static_assert(RT_ADAPTIVE_REFINE_WAVES == RT_WG_THREADS / 64u, "rt_adaptive_refine_grid counts the waves of a trace workgroup");
+  const unsigned n_wg = rt_adaptive_refine_grid(w, h, k);
   size_t per_lane = 0;
   if ((rc = adaptive_scratch(s->refract, k, &per_lane))) return rc;
   if ((rc = scratch_guard(D, stream, per_lane, (uint64_t)n_wg * (RT_WG_THREADS / 64u), "the adaptive refine kernel (rt_adaptive_refine)"))) return rc;
@@ -926,6 +928,12 @@ extern "C" int rt_scene_trace_rays_device(rt_scene_dev *s, uint64_t n, const dou
 }
 
 extern "C" size_t rt_rays_order_work_bytes(uint64_t n) { return (n == 0 || n >= (1ull << 31)) ? 0 : rt_order_layout_of(n).bytes; }
+#ifdef RT_TESTING
+// Test build only: the grid of the bounds and key kernels and the sort's tile count for n rays (rt_rays_order.h), so that a test knows
+// whether a list reaches the second turn of their loops and the second chunk of rt_order_scan.  Host arithmetic, no GPU.
+extern "C" uint32_t rt_test_order_grid(uint32_t n) { return rt_order_grid(n); }
+extern "C" uint32_t rt_test_order_tiles(uint64_t n) { return rt_order_layout_of(n).tiles; }
+#endif
 
 // (the arguments first: they are judged without a scene, and before a device is touched)
 extern "C" int rt_scene_order_rays_device(rt_scene_dev *s, uint64_t n, const double *d_rays, uint32_t *d_order, void *d_work, size_t work_bytes,

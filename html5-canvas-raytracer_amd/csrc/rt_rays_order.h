@@ -32,6 +32,14 @@ static inline rt_order_layout rt_order_layout_of(uint64_t n) {
   return l;
 }
 
+// The workgroups (of RT_ORDER_WG work-items, one ray each per turn) of rt_order_bounds and rt_order_keys for a list of n rays: capped, a
+// grid-stride loop takes the rays beyond RT_ORDER_MAX_WGS x RT_ORDER_WG.
+#define RT_ORDER_MAX_WGS 4096u
+static inline uint32_t rt_order_grid(uint32_t n) {
+  const uint32_t wgs = (uint32_t)(((uint64_t)n + RT_ORDER_WG - 1u) / RT_ORDER_WG);
+  return wgs < RT_ORDER_MAX_WGS ? wgs : RT_ORDER_MAX_WGS;
+}
+
 // Enqueues the ordering of rays [0, n) on `stream`: bounds, keys, four radix passes; d_order receives the permutation.  Returns a
 // hipError_t as int.
 extern "C" int rt_launch_order_rays(uint32_t n, const double *d_rays, uint32_t *d_order, void *d_work, hipStream_t stream);

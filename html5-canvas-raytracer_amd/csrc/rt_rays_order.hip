@@ -236,7 +236,7 @@ extern "C" int rt_launch_order_rays(uint32_t n, const double *d_rays, uint32_t *
   hipError_t e = hipMemsetAsync(bounds, 0xff, RT_ORDER_COORDS * 4u, stream);
   if (e == hipSuccess) e = hipMemsetAsync(bounds + RT_ORDER_COORDS, 0, RT_ORDER_COORDS * 4u, stream);
   if (e != hipSuccess) return (int)e;
-  const uint32_t wgs = (n + RT_ORDER_WG - 1u) / RT_ORDER_WG, grid = wgs < 4096u ? wgs : 4096u;     // grid-stride beyond
+  const uint32_t grid = rt_order_grid(n);                                                           // grid-stride beyond
   hipLaunchKernelGGL(rt_order_bounds, dim3(grid), dim3(RT_ORDER_WG), 0, stream, d_rays, n, bounds);
   hipLaunchKernelGGL(rt_order_keys, dim3(grid), dim3(RT_ORDER_WG), 0, stream, d_rays, n, (const uint32_t *)bounds, keys_a);
   const uint32_t *keys_in[4] = {keys_a, keys_b, keys_a, keys_b};

@@ -10,6 +10,7 @@ import pytest
 
 import oracle_util as ou
 import rt_host
+from test_gpu_adaptive import BEYOND_ONE_TURN, HOLES, LARGEST_EXTENTS      # (tables only: importing the module needs no GPU)
 
 OK, INVALID, STATE = 0, -1, -5
 
@@ -21,6 +22,8 @@ def lib(built):
     lib.rt_test_adaptive_mask.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.rt_test_adaptive_box.restype = C.c_uint32
     lib.rt_test_adaptive_box.argtypes = [C.c_uint32, C.c_uint32]
+    lib.rt_test_adaptive_refine_grid.restype = C.c_uint32
+    lib.rt_test_adaptive_refine_grid.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     return lib
 
 
@@ -184,3 +187,60 @@ def test_box_rule(lib, k):
         assert lib.rt_test_adaptive_box(s, k) == (s + n // 2) // n, (k, s)
     assert lib.rt_test_adaptive_box(0, k) == 0 and lib.rt_test_adaptive_box(255 * n, k) == 255
     assert all(lib.rt_test_adaptive_box(s, k) == (s + n // 2) // n for s in range(255 * n + 1))
+
+
+# ------------------------------------------------------------------ the refine launch's grid, and the GPU cases that must outrun it
+CAP = 8192                                              # (today's; the cap itself is found below, not assumed by the GPU cases)
+
+
+def frame_of(px):
+    """A frame of exactly px pixels with both sides in 1..32768 if there is one (the hook is plain arithmetic and takes any)."""
+    return next(((px // h, h) for h in range(1, 4097) if px % h == 0 and px // h <= 32768), (px, 1))
+
+
+@pytest.mark.parametrize("k", [2, 3, 4])
+def test_refine_grid(lib, k):
+    """rt_adaptive_refine_grid(w, h, k) = min(ceil(w h / (4 waves x 64 // k^2 pixels)), 8192): small frames, frames at the cap, and the
+    cap plus or minus one workgroup - each of those as exactly that many workgroups' pixels, one pixel fewer and one more."""
+    per_wg = 4 * (64 // (k * k))
+    want = lambda w, h: min(-(-w * h // per_wg), CAP)
+    frames = [(1, 1), (per_wg, 1), (per_wg + 1, 1), (1, per_wg + 1), (131, 60), (240, 135), (3840, 2160), (32768, 1), (1, 32768), (16384, 16384)]
+    for wgs in (CAP - 1, CAP, CAP + 1):
+        for px in (wgs * per_wg - 1, wgs * per_wg, wgs * per_wg + 1):
+            w, h = frame_of(px)
+            assert w * h == px
+            frames += [(w, h), (h, w)]
+    got = {(w, h): lib.rt_test_adaptive_refine_grid(w, h, k) for w, h in frames}
+    assert got == {(w, h): want(w, h) for w, h in frames}
+    assert got[frame_of((CAP - 1) * per_wg)] == CAP - 1 and got[frame_of((CAP - 1) * per_wg + 1)] == CAP
+    assert got[frame_of(CAP * per_wg + 1)] == CAP and got[frame_of((CAP + 1) * per_wg + 1)] == CAP and got[(1, 1)] == 1
+
+
+@pytest.mark.parametrize("k,w,h", BEYOND_ONE_TURN)
+def test_the_large_gpu_cases_outrun_one_turn_and_end_in_a_partly_filled_wave(lib, k, w, h):
+    """What makes tests/test_gpu_adaptive.py's T = 0 cases reach the second turn of rt_adaptive_refine's loop, against the library's
+    own grid: one turn cannot hold the fully refined frame, and what is left over does not fill its last wave."""
+    ppw = 64 // (k * k)
+    turn = lib.rt_test_adaptive_refine_grid(w, h, k) * 4 * ppw
+    assert w * h > turn
+    assert (w * h - turn) % ppw != 0
+    assert w * h - turn < turn                          # (and it is the second turn that ends the list: a few seconds' frame)
+    assert call(lib, None, w=w, h=h, k=k, t=0) == STATE  # the call admits the frame
+
+
+def test_every_k_has_a_large_gpu_case_and_the_case_with_holes_can_outrun_one_turn(lib):
+    assert sorted(c[0] for c in BEYOND_ONE_TURN) == [2, 3, 4]
+    name, w, h, k, t = HOLES
+    assert 0 < t < 256 and k == 4
+    # check() caps the refined share of such a frame at 0.60: a list under that cap must still be able to exceed one turn
+    assert 0.60 * w * h > lib.rt_test_adaptive_refine_grid(w, h, k) * 4 * (64 // (k * k))
+    assert call(lib, None, w=w, h=h, k=k, t=t) == STATE
+
+
+def test_the_largest_extents_are_admitted_and_one_more_is_not(lib):
+    for w, h, k in LARGEST_EXTENTS:
+        assert max(k * w, k * h) == 65536 and max(w, h) - 1 <= 0x7fff
+        assert call(lib, None, w=w, h=h, k=k, t=16) == STATE, (w, h, k, lib.rt_last_error())
+        bigger = dict(w=w + 1, h=h) if w > h else dict(w=w, h=h + 1)
+        assert call(lib, None, k=k, t=16, work_bytes=1 << 40, **bigger) == INVALID
+    assert {(w > h, k) for w, h, k in LARGEST_EXTENTS} == {(True, 4), (False, 4), (True, 2), (False, 2)}

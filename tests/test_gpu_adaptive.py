@@ -69,6 +69,18 @@ def scene_of(name):
     return rt_host.load_scene(name)
 
 
+def refine_grid(lib, w, h, k):
+    """The workgroups of the refine launch for a w x h frame (csrc/rt_adaptive.h: rt_adaptive_refine_grid, exported by the test build)."""
+    lib.rt_test_adaptive_refine_grid.restype = C.c_uint32
+    lib.rt_test_adaptive_refine_grid.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    return int(lib.rt_test_adaptive_refine_grid(w, h, k))
+
+
+def one_turn(lib, w, h, k):
+    """The listed pixels one turn of the refine kernel's grid-stride loop covers: workgroups x 4 waves x 64 // k^2 pixels."""
+    return refine_grid(lib, w, h, k) * 4 * (64 // (k * k))
+
+
 def check(lib, scene, w, h, k, t, flags=FAST, r=None, tag=None, fine=None):
     """The adaptive frame of `scene` (on `r`, a Renderer that holds it - or is said to, after edits - else a fresh one) against its
     yardsticks; returns (frame, base, fine, mask)."""
@@ -128,6 +140,79 @@ def test_threshold_0_is_the_supersampled_frame(lib, name, golden, k):
 def test_threshold_256_is_the_base_frame(lib):
     got, base, _, m = check(lib, scene_of("h8"), 131, 60, 4, 256, tag="h8 T=256")
     assert not m.any() and got == base
+
+
+# ------------------------------------------------------------------ lists longer than one turn of the refine kernel's loop
+# The refine grid is capped (csrc/rt_adaptive.h), so a list longer than grid x 4 waves x 64 // k^2 pixels is finished by the loop's
+# further turns.  (k, w, h): the smallest frames whose w h pixels exceed one turn of the capped grid by a count that is no multiple
+# of 64 // k^2, so that the second turn ends in a partly filled wave - 3 pixels past the stride for k = 4, 384 = 54 x 7 + 6 for k = 3,
+# 511 = 31 x 16 + 15 for k = 2.  tests/test_adaptive.py holds both properties against the library's own grid, without a GPU.
+BEYOND_ONE_TURN = [(4, 749, 175), (3, 640, 359), (2, 1023, 513)]
+# (scene, w, h, k, T): 0 < T < 256, a list with holes that is still longer than one turn
+HOLES = ("h8", 1920, 1080, 4, 4)
+# (w, h, k): the largest extents the call admits - k w or k h = 65536 in the launch record, py up to 32767 in a list entry
+LARGEST_EXTENTS = [(16384, 2, 4), (2, 16384, 4), (32768, 1, 2), (1, 32768, 2)]
+
+
+@pytest.mark.parametrize("name", ["h8", "default14"])
+@pytest.mark.parametrize("k,w,h", BEYOND_ONE_TURN, ids=["k%d_%dx%d" % c for c in BEYOND_ONE_TURN])
+def test_threshold_0_beyond_one_turn_of_the_refine_loop(lib, name, k, w, h):
+    """Every pixel is listed and the list outruns one turn: the frame is the strict supersample-k frame, whose kernel has no such loop.
+    h8 runs the <false, k> kernels, default14 (depth 8, refraction) the <true, k> ones."""
+    assert w * h > one_turn(lib, w, h, k)
+    got, _, fine, m = check(lib, scene_of(name), w, h, k, 0, tag=name)
+    assert m.all() and got == fine
+
+
+def noise_scene(refract):
+    """A frame in which no pixel is flat: the camera of h8 inside one sphere that shines with the stars sampler's hash of the sample
+    index, every sample a grey drawn uniformly from [0, 1) (threshold 1, scale 1).  A base pixel is one draw of the w x h grid, a
+    refined one the box of k k draws of the k w x k h grid: the two bytes agree by chance alone, for about 1 pixel in 256, so a listed
+    pixel that is not refined, or refined into another pixel's place, shows whichever pixel it is.  refract: a glass bead behind the
+    camera, which no ray meets, makes the scene one of the <true, k> kernels'."""
+    s = dict(scene_of("h8"))
+    sky = next(o for o in s["objects"] if o["r2"] > 1e6)
+    s["objects"] = [dict(sky, mtl=dict(sky["mtl"], sampler={"kind": rt_host.SAMPLER_STARS, "threshold": 1.0, "scale": 1.0}))]
+    if refract:
+        bead = {"origin": [0.0, 1.5, 40.0], "r2": 0.01, "mtl": {"color": [1, 1, 1], "albedo": [0, 0, 0.5, 0.1, 0.8], "specular_exponent": 125,
+                                                                   "refract_index": 1.5, "sampler": {"kind": rt_host.SAMPLER_COLOR}}}
+        s["objects"] = [bead] + s["objects"]
+    return s
+
+
+@pytest.mark.parametrize("refract", [False, True], ids=["opaque", "refracting"])
+@pytest.mark.parametrize("k,w,h", BEYOND_ONE_TURN, ids=["k%d_%dx%d" % c for c in BEYOND_ONE_TURN])
+def test_every_entry_beyond_one_turn_is_refined_into_its_own_pixel(lib, refract, k, w, h):
+    """The frames above at T = 0 on noise_scene: in h8 and default14 most pixels are flat - the supersampled pixel is the base pixel - and
+    which entries the list's second turn holds is up to the atomics of rt_adaptive_mark, so a loop that skips a few entries can go
+    unseen there.  Here at least 99 % of the pixels differ between the base and the strict supersample-k frame (expected: 255 in 256)."""
+    assert w * h > one_turn(lib, w, h, k)
+    got, base, fine, m = check(lib, noise_scene(refract), w, h, k, 0, tag="noise, %s" % ("refracting" if refract else "opaque"))
+    assert m.all() and got == fine
+    differ = (np.frombuffer(base, np.uint8).reshape(h, w, 4) != np.frombuffer(fine, np.uint8).reshape(h, w, 4)).any(axis=2)
+    assert differ.mean() >= 0.99, differ.mean()
+
+
+def test_a_list_with_holes_beyond_one_turn_of_the_refine_loop(lib):
+    """0 < T < 256: the list names some pixels only, and still more than one turn of the k = 4 loop covers.  Both inequalities are
+    conditions on the input, read back from the call.  Observed on an MI355X: 178 717 of 2 073 600 pixels
+    refined (8.6 %), against 131 072 in one turn."""
+    name, w, h, k, t = HOLES
+    _, _, _, m = check(lib, scene_of(name), w, h, k, t, tag=name)
+    count = int(m.sum())                                           # (check() held the call's own count and mask to it)
+    assert one_turn(lib, w, h, k) < count < w * h, (count, one_turn(lib, w, h, k))
+
+
+@pytest.mark.parametrize("w,h,k", LARGEST_EXTENTS, ids=["%dx%d_k%d" % c for c in LARGEST_EXTENTS])
+def test_largest_extents(lib, w, h, k):
+    assert 65536 in (k * w, k * h)
+    check(lib, scene_of("h8"), w, h, k, 16, tag="h8")
+
+
+def test_largest_extents_threshold_0(lib):
+    w, h, k = LARGEST_EXTENTS[1]                                   # the tall one: py up to 16383 in every list entry's upper half
+    got, _, fine, m = check(lib, scene_of("h8"), w, h, k, 0, tag="h8")
+    assert m.all() and got == fine
 
 
 # ------------------------------------------------------------------ sizes that cross the row ends, the 64-lane pieces and the 7-pixel waves

@@ -225,6 +225,59 @@ def test_row_tiles_reassemble_to_the_frame(name, built):
     r.close()
 
 
+# ------------------------------------------------------------------ 65536 band rows: the one row grid y leaves to the loop's second turn
+# rt_hits_kernel's grid y is capped at 65535 and `brow += gridDim.y` takes the rest: of the 65536 sample rows the ABI admits, band row
+# 65535 alone belongs to a second turn.
+TALL = [("h8", 8, 65536), ("h8_ss4", 2, 16384)]                      # both a sample grid of 8 x 65536
+
+
+@pytest.mark.parametrize("name,w,h", TALL, ids=["%s_%dx%d" % c for c in TALL])
+def test_65536_band_rows_match_the_oracle(name, w, h, built):
+    scene = rt_host.load_scene(name)
+    k = scene.get("supersample", 1)
+    assert (k * w, k * h) == (8, 65536)
+    r = rt_host.Renderer(scene)
+    ids, depth, normal, raw = _render_hits(r, w, h, k)
+    r.close()
+    assert not any((b.reshape(k * h, -1) == SENTINEL).all(axis=1).any() for b in raw)      # no row of any buffer was left out
+    rng = np.random.default_rng(20261018)
+    samples = [(x, y) for y in (0, 1, 32767, 65534, 65535) for x in range(k * w)]
+    samples += list(zip(rng.integers(0, k * w, 2000).tolist(), rng.integers(0, k * h, 2000).tolist()))
+    _check_samples(hu.Probe(scene, w, h), ids, depth, normal, samples)
+    assert len(np.unique(ids)) >= 2
+
+
+def test_65536_band_rows_are_two_row_tiles_that_do_not_loop(built):
+    """The same frame as two tiles of 32768 rows, one call each: neither call's band reaches the grid's cap, so neither loops; their
+    bytes are the halves of the whole-frame call's."""
+    scene, w, h = rt_host.load_scene("h8"), 8, 65536
+    r = rt_host.Renderer(scene)
+    _, _, _, whole = _render_hits(r, w, h, 1)
+    halves = [_render_hits(r, w, h, 1, tiles=rt_host.RtTiles(32768, g, 1, 1), band_rows=32768)[3] for g in (0, 1)]
+    r.close()
+    for b, nb in enumerate((4, 8, 12)):
+        cut = 32768 * w * nb
+        assert np.array_equal(halves[0][b], whole[b][:cut]) and np.array_equal(halves[1][b], whole[b][cut:]), nb
+        assert not np.array_equal(halves[0][b], halves[1][b])
+
+
+def test_a_second_turn_row_past_the_frame_is_not_stored(built):
+    """8 x 65530 in two tiles of 32768 rows is a band of 65536 rows whose last six lie past the frame - band row 65535, the second turn's
+    only row, among them: they keep the sentinel in all three buffers, and the rows above are the frame's, rendered in tiles of 16384
+    rows (four calls, none of which loops)."""
+    scene, w, h = rt_host.load_scene("h8"), 8, 65530
+    r = rt_host.Renderer(scene)
+    _, _, _, band = _render_hits(r, w, h, 1, tiles=rt_host.RtTiles(32768, 0, 1, 2), band_rows=65536)
+    parts = [_render_hits(r, w, h, 1, tiles=rt_host.RtTiles(16384, g, 1, 1), band_rows=16384)[3] for g in range(4)]
+    r.close()
+    for b, nb in enumerate((4, 8, 12)):
+        cut = h * w * nb
+        assert (band[b][cut:] == SENTINEL).all(), nb
+        assert (parts[3][b][(h - 3 * 16384) * w * nb:] == SENTINEL).all(), nb
+        assert np.array_equal(band[b][:cut], np.concatenate([p[b] for p in parts])[:cut]), nb
+        assert not (band[b][:cut].reshape(h, -1) == SENTINEL).all(axis=1).any()
+
+
 def test_hits_do_not_disturb_colour_frames_and_null_buffers_stay_untouched(built):
     scene, w, h = rt_host.load_scene("default14"), 160, 90
     r = rt_host.Renderer(scene)

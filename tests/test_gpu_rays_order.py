@@ -144,6 +144,58 @@ def test_identical_rays_and_non_finite_rays(lib):
         r.close()
 
 
+# ------------------------------------------------------------------ 1b. an exact yardstick for an order above 2^20 rays
+# The bounds and key kernels run on a capped grid (csrc/rt_rays_order.h: rt_order_grid) and reach the rays beyond it with a grid-stride
+# loop; rt_order_scan carries across chunks of 256 tiles.  The list below needs both; tests/test_rays_order.py holds its sizes against the
+# library's own grid and tile count, without a GPU.  frame: w x h = m primary rays; extra: the displaced rays behind two copies of them.
+ORDER_BEYOND = {"scene": "h8", "w": 1024, "h": 512, "extra": 4096 + 5}
+
+
+def beyond_lists(scene):
+    """-> (B, T, T'): the shuffled primary rays of the frame; `extra` more of them (another shuffle's first) with their origins
+    displaced by 20..60 units along each axis, both signs on each; and the same without the displacement."""
+    c = ORDER_BEYOND
+    every = rt_host.primary_rays(c["w"], c["h"], scene)
+    b = shuffled(every, 91)
+    plain = shuffled(every, 92)[:c["extra"]].copy()
+    rng = np.random.default_rng(93)
+    moved = plain.copy()
+    moved[:, 0:3] += rng.uniform(20.0, 60.0, (len(plain), 3)) * rng.choice([-1.0, 1.0], (len(plain), 3))
+    return b, moved, plain
+
+
+def test_order_beyond_one_turn_is_the_order_of_the_same_rays_in_one_turn(lib):
+    """full = B ++ B ++ T, more than 2^20 rays and more than 256 tiles: every ray of T lies where only the second turn of rt_order_bounds
+    and rt_order_keys reaches it, and T alone gives the origin coordinates an extent.  Y = B ++ T is the same set of rays - the same
+    bounds, the same keys - in one turn and 130 tiles.  The order is the list sorted by (key, index), so full's order restricted to the
+    first copy and T is Y's, element for element, and its second copy follows its first."""
+    scene = rt_host.load_scene(ORDER_BEYOND["scene"])
+    b, t, t_plain = beyond_lists(scene)
+    m, k = len(b), len(t)
+    full, y = np.concatenate([b, b, t]), np.concatenate([b, t])
+    n = len(full)
+    assert n == 2 * m + k > 2 ** 20 and 2 * m >= 2 ** 20 > m + k
+    assert (np.abs(t[:, 0:3] - b[0, 0:3]) > 19.0).all() and (t[:, 0:3] > b[0, 0:3]).any(axis=0).all() and (t[:, 0:3] < b[0, 0:3]).any(axis=0).all()
+    assert (b[:, 0:3] == b[0, 0:3]).all()                               # one origin: within B the origin decides nothing
+    r = rt_host.Renderer(scene, 0, lib)
+    try:
+        o_full, o_y, o_plain = order_of(lib, r, full), order_of(lib, r, y), order_of(lib, r, np.concatenate([b, t_plain]))
+        assert np.array_equal(np.sort(o_full), np.arange(n, dtype=np.uint32))
+        assert np.array_equal(np.sort(o_y), np.arange(m + k, dtype=np.uint32))
+        assert not np.array_equal(o_y, o_plain)                         # T moves the keys at all: bounds that never saw T would show
+        first_and_t = o_full[(o_full < m) | (o_full >= 2 * m)].astype(np.int64)
+        first_and_t = np.where(first_and_t >= 2 * m, first_and_t - m, first_and_t)
+        differ = np.flatnonzero(first_and_t != o_y)
+        assert differ.size == 0, ("entries that differ from the one-turn order", differ.size, differ[:8].tolist())
+        second = o_full[(o_full >= m) & (o_full < 2 * m)].astype(np.int64) - m
+        assert np.array_equal(second, o_full[o_full < m])
+        plain, ordered = both_ways(lib, r, full)
+    finally:
+        r.close()
+    assert_same(plain, ordered, "beyond one turn")
+    assert len({bytes(p) for p in plain["rgba"][::997]}) > 50          # not all sky
+
+
 # ------------------------------------------------------------------ 2. ordered results are the plain results
 def both_ways(lib, r, rays, order=None):
     """-> (plain, ordered): {output: array} of rt_scene_trace_rays_device and of the ordered trace (the library's order, or `order`),

@@ -11,6 +11,7 @@ import pytest
 
 import oracle_util as ou
 import rt_host
+from test_gpu_rays_order import ORDER_BEYOND                     # (a table only: importing the module needs no GPU)
 from test_rays import RT_ERR_DEVICE, RT_ERR_INVALID, RT_ERR_STATE, TOOLS, _aligned, _blob, _resources
 
 ROOT = ou.ROOT
@@ -60,6 +61,44 @@ def test_work_bytes(built):
     assert [rt_host.rays_order_work_bytes(n) for n in ns] == got
     assert lib.rt_rays_order_work_bytes(2 ** 31 - 1) >= got[-1]
     assert got[-1] >= 3 * 4 * 2 ** 23                      # two key arrays and an index array at least
+
+
+@pytest.fixture(scope="module")
+def tlib(built):
+    """The test build: rt_order_grid and the sort's tile count (csrc/rt_rays_order.h) as host arithmetic."""
+    lib = rt_host.load_library(rt_host.TEST_LIB_PATH)
+    lib.rt_test_order_grid.restype = C.c_uint32
+    lib.rt_test_order_grid.argtypes = [C.c_uint32]
+    lib.rt_test_order_tiles.restype = C.c_uint32
+    lib.rt_test_order_tiles.argtypes = [C.c_uint64]
+    return lib
+
+
+def test_order_grid(tlib):
+    """rt_order_grid(n) = min(ceil(n / 256), 4096): small lists, lists at the cap, the cap plus or minus one workgroup - each as exactly
+    that many workgroups' rays, one ray fewer and one more - and the longest list."""
+    cap = 4096
+    ns = [1, 2, 255, 256, 257, 511, 512, 513, 2 ** 18 + 5, 2 ** 23, 2 ** 31 - 1]
+    for wgs in (cap - 1, cap, cap + 1):
+        ns += [wgs * 256 - 1, wgs * 256, wgs * 256 + 1]
+    got = {n: tlib.rt_test_order_grid(n) for n in ns}
+    assert got == {n: min(-(-n // 256), cap) for n in ns}
+    assert got[1] == 1 and got[257] == 2 and got[(cap - 1) * 256] == cap - 1 and got[(cap - 1) * 256 + 1] == cap and got[cap * 256 + 1] == cap
+    for n in (1, 4096, 4097, 2 ** 20, 2 ** 20 + 1, 2 ** 31 - 1):
+        assert tlib.rt_test_order_tiles(n) == -(-n // 4096)
+
+
+def test_the_large_gpu_case_reaches_the_second_turn_and_the_second_scan_chunk(tlib):
+    """What makes tests/test_gpu_rays_order.py's list B ++ B ++ T non-vacuous, against the library's own grid and layout: the list is
+    longer than one turn of the bounds and key kernels, every ray of T lies past that turn, its tile count needs a second chunk of
+    rt_order_scan - and the yardstick list B ++ T needs neither."""
+    m, k = ORDER_BEYOND["w"] * ORDER_BEYOND["h"], ORDER_BEYOND["extra"]
+    n = 2 * m + k
+    turn = tlib.rt_test_order_grid(n) * 256
+    assert n > turn and 2 * m >= turn
+    assert tlib.rt_test_order_tiles(n) > 256
+    assert tlib.rt_test_order_grid(m + k) * 256 >= m + k and tlib.rt_test_order_tiles(m + k) <= 256
+    assert rt_host.rays_order_work_bytes(n, tlib) >= 3 * 4 * n + 256 * 4 * tlib.rt_test_order_tiles(n)
 
 
 def test_bad_arguments_are_invalid(built):
