@@ -1,7 +1,10 @@
 // rt_api_internal.h — what the host units of the C ABI share: errors and test switches, the library and device state, the resident
 // scene (rt_scene_dev) and the few functions that cross units.  Not part of the ABI.
+//   rt_scene_sync.h  the stream ordering of a resident scene's launches, moves and texel edits (rules R1-R6) and the events, side stream
+//                  and pinned rings it owns for it: header-only, HIP's API and nothing of the project
 //   rt_api.hip     lifetime, errors, device state, the scratch guard and the per-variant scratch figures, the host-logic probes, memory helpers, IPC
-//   rt_scene.hip   upload and moves of a resident scene (the generation pipeline), its texel edits (rt_texels.hip), its launch decisions and launch tables
+//   rt_scene.hip   upload and moves of a resident scene (the generation pipeline), its texel edits (rt_texels.hip), its launch decisions and launch
+//                  tables, and the launch prologue (enter_launch)
 //   rt_launch.hip  the launches: colour (the launch record, then the strict launch or the product launch and rt_retrace), supersampling,
 //                  compact bands, adaptive supersampling (rt_adaptive.hip), primary hits and picking, ray lists, occlusion queries
 //   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick, and the host lists that go
@@ -37,6 +40,7 @@
 #include "rt_nodes.h"
 #include "rt_texels.h"
 #include "rt_adaptive.h"
+#include "rt_scene_sync.h"
 
 // per build of rt_kernel.hip (product, strict): the variant's kernel (NULL: not this build's) and its launch
 extern "C" const void *rt_kernel_trace_fast(rt_trace_variant);
@@ -122,6 +126,8 @@ uint64_t tile_set_pixels(uint32_t w, uint32_t h, const rt_tiles *tiles);
 struct launch_geom { uint32_t tiles_x, rows_per_wg, rb_per_tile; double proj_w, proj_h, proj_d; };
 launch_geom launch_geometry(double fov_deg, uint32_t w, uint32_t h, uint32_t ss, uint32_t tile_rows);
 
+using device_mem = owned<void *, hipFree>;   // (rt_scene_sync.h; pinned_mem: hipHostFree)
+
 // GPU time between start() and stop() on a stream; the events are released on every way out
 struct event_timer {
   hipEvent_t a = nullptr, b = nullptr;
@@ -188,7 +194,7 @@ struct rt_scene_dev {
   // Its last part is the CAMERA BLOCK - what depends on the camera: per ordering the camera-anchored geometry and the cull
   // rectangles, and (few spheres) the LDS images, whose tails are the cull rectangles - rewritten with one small asynchronous copy
   // when the camera moves (rt_scene_set_camera).
-  uint8_t *arena = nullptr;
+  device_mem arena;
   size_t arena_bytes = 0;
   void *d_blob;                  // the uploaded scene blob (its texels; its sphere records are the OBJECT BLOCK's, its lights travel by value from `lights`)
   rt_texture_desc *d_texdesc;    // RT_MAX_TEXTURES descriptors (zero padded)
@@ -226,42 +232,10 @@ struct rt_scene_dev {
   // product launches per frame kind since the camera last moved: many-sphere scenes get their shadow masks with the SECOND frame of a kind
   struct camera_use { frame_kind kind; uint64_t cam_gen; uint32_t uses; };
   std::vector<camera_use> camera_uses;
-  hipStream_t last_stream = nullptr;     // the stream of the scene's last launch; several: launches of this scene are in flight on more than one
-  bool any_launch = false, several_streams = false, launched_since_move = false;
-  // The camera pipeline (rt_scene_set_camera).  `side`: a stream of the scene's own, on which a move's camera block is copied and the
-  // launch tables of the frame sizes in use are rebuilt - beside the previous camera's launches, which run on the caller's stream.
-  //   old_done[x]   recorded on the caller's stream at the move to generation g (x = (g - 1) & 1): every launch with generations < g
-  //                 precedes it.  The move to g + 1 writes block / tables (g + 1) & 1 = x only behind it.
-  //   prep_done[b]  recorded on `side` behind the copy and the builds of generation g (b = g & 1): the first launch of generation g
-  //                 on a stream waits for it (prep_waited: which streams already do).
-  hipStream_t side = nullptr;
-  hipEvent_t old_done[2] = {nullptr, nullptr}, prep_done[2] = {nullptr, nullptr};
-  bool old_done_valid[2] = {false, false}, prep_valid[2] = {false, false};
-  struct waited_on { hipStream_t stream; uint64_t gen; };
-  std::vector<waited_on> prep_waited;
-  // pinned staging for the small copies that follow a camera move (the camera block; a launch table's parameters): a ring of slots,
-  // each guarded by an event recorded behind the copy that read it
-  struct stage_slot { uint8_t *h = nullptr; hipEvent_t done = nullptr; bool used = false; };
-  stage_slot stages[16];                 // (16: the host may run eight frames ahead of the GPU in an animation; one pinned allocation behind them)
-  uint8_t *stage_pool = nullptr;
-  size_t stage_bytes = 0;
-  uint32_t stage_next = 0;
-  // Texel edits (rt_scene_set_texels, rt_scene_set_texels_device).  Texels live once, in d_blob, and every kernel reads them through
-  // texel_base + texels_offset; no table, host decision or mark count reads a texel's VALUE (flag_tol and the strict routing read
-  // widths and heights; a texture sampler is never a constant sky).  So an edit is no generation: it is one write on the caller's
-  // stream, ordered by stream and event against the launches around it.
-  //   tex_before    recorded on the stream of the scene's launches in flight when the edit's stream is another one: the write waits for it
-  //   tex_done      recorded behind the write; the next launch on every OTHER stream waits for it (tex_waited: which already do),
-  //                 and so does the next edit on another stream
-  // Neither exists before the first edit.  host_blob keeps the texels of the upload: nothing reads them.
-  hipEvent_t tex_before = nullptr, tex_done = nullptr;
-  hipStream_t tex_stream = nullptr;      // the stream of the last edit
-  uint64_t tex_seq = 0;                  // edits so far
-  std::vector<waited_on> tex_waited;     // (stream, tex_seq) pairs
-  // the host form's pinned staging: a ring of RT_TEXEL_STAGE_SLOTS slots of RT_TEXEL_STAGE_SLOT bytes, allocated by the first host edit
-  stage_slot tex_stages[16];
-  uint8_t *tex_pool = nullptr;
-  uint32_t tex_stage_next = 0;
+  scene_sync sync;               // the stream ordering of launches, moves and texel edits, and what it owns (rt_scene_sync.h)
+  // Texels live once, in d_blob, and every kernel reads them through texel_base + texels_offset; no table, host decision or mark count
+  // reads a texel's VALUE (flag_tol and the strict routing read widths and heights; a texture sampler is never a constant sky).  So a
+  // texel edit is no generation (rt_scene_sync.h: R4).  host_blob keeps the texels of the upload: nothing reads them.
   std::vector<uint8_t> host_blob;        // the scene as uploaded (patched: 1/r per sphere), for rebuilding the camera block
   std::vector<rt_sphere> host_objects_b; // ordering B of its sphere records
   rt_scene_header hd;            // host copy
@@ -283,10 +257,10 @@ struct rt_scene_dev {
   // (`known`: generation << 32 | entries + 1, a pinned host word), from then on exactly that many.
   struct order_entry {
     frame_kind kind; int ranked; bool sky, masks, cands, cells;     // ranked: 0 grid order, 1 ranked when large enough, 2 always (a compact band's launch)
-    uint64_t cam_gen; uint32_t n_blocks; volatile unsigned long long *known; hipStream_t built_on; hipEvent_t built;
+    uint64_t cam_gen; uint32_t n_blocks; volatile unsigned long long *known; hipStream_t built_on; event built;
     bool shared;                   // launched with on a stream other than the one it was built on
     // two tables, like the camera blocks: generation g's is Tb[g & 1] (the next camera's is built while this one's is still read)
-    rt_table_dev Tb[2]; uint8_t *d_blockb[2]; size_t hist_wordsb[2];
+    rt_table_dev Tb[2]; device_mem d_blockb[2]; size_t hist_wordsb[2];
     uint32_t cost_bins;            // of the current build (rt_retrace of a compact launch)
     uint64_t used_gen;             // the last camera generation a launch used it with: a move rebuilds the tables in use ahead of the next render
   };
@@ -298,9 +272,9 @@ struct rt_scene_dev {
   // rt_retrace publishes how many samples a frame of this scene, camera, size and tile set marks - the same every time, so once it
   // says "none" (and the sample grid has no odd centre) the second launch is skipped.  Launches that share a state share a
   // stream, i.e. they are ordered; mark_mu makes a launch pair one step for the threads of this process.
-  struct mark_state { uint32_t order_index; hipStream_t stream; uint32_t *d_marks; volatile unsigned long long *h_known; uint32_t slot; };   // *h_known: camera generation << 32 | marks + 1
+  struct mark_state { uint32_t order_index; hipStream_t stream; device_mem d_marks; volatile unsigned long long *h_known; uint32_t slot; };   // *h_known: camera generation << 32 | marks + 1
   std::vector<mark_state> mark_states;
-  unsigned long long *h_known_pool = nullptr;      // 2 x RT_KNOWN_WORDS pinned words: the mark states', then the launch tables'
+  pinned_mem h_known_pool;       // 2 x RT_KNOWN_WORDS pinned words: the mark states', then the launch tables'
   std::mutex launch_mu;          // a product launch - its table (found or built), the trace launch, rt_retrace - is one step for the threads of this process
   bool needs_strict;             // the scene sits on an exact coincidence (below): every launch uses the strict kernel
   bool needs_strict_scene;       // ... whatever the camera (a light on a surface, a sphere without a radius, exotic checker frequencies)
@@ -319,7 +293,7 @@ inline int scene_stream(const rt_scene_dev *s, void *hip_stream, hipStream_t *st
 int check_sphere(const rt_sphere &o, uint32_t i, uint32_t n_textures);
 
 // rt_scene.hip: the launch decisions of a resident scene, its launch tables
-void note_launch(rt_scene_dev *s, hipStream_t stream);
+int enter_launch(rt_scene_dev *s, hipStream_t stream);
 bool strict_scene(const rt_scene_dev *s);
 bool sky_fast(const rt_scene_dev *s);
 bool masks_pay(const rt_scene_dev *s, uint32_t uses_before);
@@ -329,7 +303,6 @@ table_choice choose_table(const rt_scene_dev *s, uint32_t flags, uint32_t uses_b
 uint32_t count_use(rt_scene_dev *s, const frame_kind &kind);
 volatile unsigned long long *known_word(rt_scene_dev *s, size_t index);
 uint32_t known_value(const volatile unsigned long long *p, uint64_t gen);
-int behind_the_camera(rt_scene_dev *s, hipStream_t stream);
 int dispatch_order(rt_scene_dev *s, const frame_kind &kind, const table_choice &c, hipStream_t stream);
 
 // rt_launch.hip: argument checks of the hit entry points

@@ -246,9 +246,9 @@ struct retrace_result {
   uint64_t centre_items = 0;
   bool retraced_all = false, strict_rendered = false;
 };
-struct marks_guard {                                     // a per-call mark list is released on every way out, after the stream has drained
-  void *p = nullptr; hipStream_t st = nullptr;
-  ~marks_guard() { if (p) { (void)hipStreamSynchronize(st); (void)hipFree(p); } }
+struct marks_guard {                                     // a per-call mark state: its list is released on every way out, after the stream has drained
+  rt_scene_dev::mark_state temp = {~0u, nullptr, device_mem(), nullptr, 0u};
+  ~marks_guard() { if (temp.d_marks.h) (void)hipStreamSynchronize(temp.stream); }
 };
 
 int launched(int err) { return err != 0 ? fail(RT_ERR_DEVICE, "kernel launch: %s", hipGetErrorString((hipError_t)err)) : RT_OK; }
@@ -365,7 +365,7 @@ uint32_t table_entries_known(const rt_scene_dev *s, const rt_scene_dev::order_en
   // short, BOUNDED wait for the word (it is ahead of the GPU anyway, and stays one frame ahead: the trace in flight has tens of
   // microseconds left when the word arrives); one workgroup per block costs a 4K frame 80 us instead of 68.  A caller that comes
   // later (a frame per display refresh) finds the word there; a word that does not come in time: one workgroup per block.
-  if (!n_known && oe.built_on == s->side && oe.cam_gen == s->cam_gen) {
+  if (!n_known && oe.built_on == s->sync.side.h && oe.cam_gen == s->cam_gen) {
     // (the bound grows with the table: a 4K frame's build takes ~50 us beside a trace, an 8K frame's four times that)
     const long wait_us = t.count_wait_us >= 0 ? t.count_wait_us : 100 + (long)(oe.n_blocks / 256u);
     const auto t0 = std::chrono::steady_clock::now();
@@ -378,18 +378,17 @@ uint32_t table_entries_known(const rt_scene_dev *s, const rt_scene_dev::order_en
 }
 
 // The mark state of a (launch table, stream) pair, found or made.  The first launch of a pair gets a list of its own; beyond
-// RT_KNOWN_WORDS pairs: one per call (`temp`, released through `temp_marks`), nothing cached.
-int mark_state_for(rt_scene_dev *s, uint32_t order_index, hipStream_t stream, marks_guard &temp_marks, rt_scene_dev::mark_state &temp,
-                   rt_scene_dev::mark_state **out) {
+// RT_KNOWN_WORDS pairs: one per call (`temp_marks`), nothing cached.
+int mark_state_for(rt_scene_dev *s, uint32_t order_index, hipStream_t stream, marks_guard &temp_marks, rt_scene_dev::mark_state **out) {
   for (rt_scene_dev::mark_state &m : s->mark_states) if (m.order_index == order_index && m.stream == stream) { *out = &m; return RT_OK; }
   const size_t bytes = 16u + (size_t)RT_MARKS_CAP * 8u;
-  uint32_t *d = nullptr;
-  hipError_t e = hipMalloc((void **)&d, bytes);
-  if (e == hipSuccess) e = hipMemsetAsync(d, 0, 16u, stream);
-  if (e != hipSuccess) { if (d) (void)hipFree(d); return fail(RT_ERR_DEVICE, "mark list: %s", hipGetErrorString(e)); }
-  if (s->mark_states.size() >= RT_KNOWN_WORDS) { temp_marks.p = d; temp_marks.st = stream; temp.d_marks = d; *out = &temp; }
+  device_mem d;
+  hipError_t e = hipMalloc(&d.h, bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(d.h, 0, 16u, stream);
+  if (e != hipSuccess) return fail(RT_ERR_DEVICE, "mark list: %s", hipGetErrorString(e));
+  if (s->mark_states.size() >= RT_KNOWN_WORDS) { temp_marks.temp.stream = stream; temp_marks.temp.d_marks = std::move(d); *out = &temp_marks.temp; }
   else {
-    s->mark_states.push_back(rt_scene_dev::mark_state{order_index, stream, d, known_word(s, s->mark_states.size()), 0u});
+    s->mark_states.push_back(rt_scene_dev::mark_state{order_index, stream, std::move(d), known_word(s, s->mark_states.size()), 0u});
     *out = &s->mark_states.back();
   }
   return RT_OK;
@@ -437,7 +436,7 @@ int retrace_launch(const colour_call &c, const rt_launch &L, const rt_scene_dev:
   const rt_trace_variant v = rt_trace_variant_of(true, true, s->refract, false, c.ss2, L.cull_in_lds != 0u, L.scatter != 0u, false);
   if (int rc = guard_kernel_scratch(c.D, c.stream, v, n_wg * (RT_WG_THREADS / 64u), "the list-driven strict launch (rt_retrace)")) return rc;
   if (int rc = launched(launch_variant(F, v, (unsigned)n_wg, nullptr, 0u, c.stream))) return rc;
-  o.marks_read = ms.d_marks; o.marks_read_slot = ms.slot;
+  o.marks_read = (const uint32_t *)ms.d_marks.h; o.marks_read_slot = ms.slot;
   ms.slot ^= 1u;                                        // rt_retrace cleared the other counter: the next launch's
   return RT_OK;
 }
@@ -459,9 +458,9 @@ int product_launch(const colour_call &c, rt_launch &L, marks_guard &temp_marks, 
   L.order_n8 = (oe.n_blocks + 7u) / 8u;
   L.grid_x = n_known ? n_known - 1u : oe.n_blocks;
   L.grid_y = 1u;
-  rt_scene_dev::mark_state temp_state = {~0u, c.stream, nullptr, nullptr, 0u}, *ms = nullptr;
-  if (int rc = mark_state_for(s, (uint32_t)oi, c.stream, temp_marks, temp_state, &ms)) return rc;
-  L.marks = ms->d_marks; L.marks_slot = ms->slot;
+  rt_scene_dev::mark_state *ms = nullptr;
+  if (int rc = mark_state_for(s, (uint32_t)oi, c.stream, temp_marks, &ms)) return rc;
+  L.marks = (uint32_t *)ms->d_marks.h; L.marks_slot = ms->slot;
   const uint32_t known = c.t.uncached_marks ? 0u : known_value(ms->h_known, s->cam_gen);        // 0: not known (yet); else the frame's mark count + 1
   // A frame KNOWN to mark more samples than the list holds (a legal scene can: every hit of a sphere whose sampler coordinate is
   // an exact integer everywhere) would be traced twice in full, product kernel then rt_retrace over every sample: the strict
@@ -522,8 +521,7 @@ int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *t
     // which streams the scene's launches run on (rt_scene_set_camera, dispatch_order), and: behind the last write of the camera block
     std::lock_guard<std::mutex> lk(s->launch_mu);
     stars_seed = s->hd.stars_seed;                     // (rt_scene_set_stars_seed: this launch's, whatever the next call sets)
-    if ((rc = behind_the_camera(s, stream))) return rc;
-    note_launch(s, stream);
+    if ((rc = enter_launch(s, stream))) return rc;
   }
   const uint32_t ss = ss_override ? ss_override : s->hd.supersample;
   if (ss > 2u) {
@@ -662,8 +660,7 @@ extern "C" int rt_render_adaptive_device(rt_scene_dev *s, uint32_t w, uint32_t h
   rt_launch F;
   {
     std::lock_guard<std::mutex> lk(s->launch_mu);
-    if ((rc = behind_the_camera(s, stream))) return rc;
-    note_launch(s, stream);
+    if ((rc = enter_launch(s, stream))) return rc;
     if ((rc = fill_launch(c, true, s->hd.stars_seed, nullptr, 0u, nullptr, F))) return rc;      // (strict: the scene in its own order, as rt_retrace is bound)
   }
   const rt_adaptive_refine_launch A = {(const uint32_t *)d_work, (uint32_t *)d_out, w};
@@ -682,7 +679,7 @@ int compact_table(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles
   if (int rc = check_frame("compact band", w, h, tiles, flags)) return rc;
   const uint32_t ss = s->hd.supersample;
   if (ss > 2u || strict_scene(s)) return fail(RT_ERR_UNSUPPORTED, "compact bands: this scene is rendered by the strict kernel (or supersampled 3x3 / 4x4): send plain bands");
-  if (int rc = behind_the_camera(s, stream)) return rc;
+  HIP_TRY(s->sync.before_launch(stream, s->cam_gen));
   *rows_per_wg = launch_geometry(s->hd.fov_deg, w, h, ss, tiles->tile_rows).rows_per_wg;
   *oi = dispatch_order(s, frame_kind{w, h, ss, *tiles, sky_part_of(flags)}, choose_table(s, flags, 0u), stream);
   return *oi < 0 ? RT_ERR_DEVICE : RT_OK;
@@ -739,7 +736,7 @@ extern "C" int rt_compact_expand_device(rt_scene_dev *s, uint32_t w, uint32_t h,
     E.src = (const uint8_t *)d_compact; E.dst = (uint32_t *)d_frame;
     const uint32_t n_known = known_value(oe.known, s->cam_gen);
     grid = n_known ? n_known - 1u : oe.n_blocks;                     // (workgroups behind the last entry read a zero slot and leave)
-    note_launch(s, stream);
+    s->sync.note_launch(stream);
   }
   if (grid) hipLaunchKernelGGL(rt_compact_expand_kernel, dim3(grid), dim3(256), 0, stream, E);
   HIP_TRY(hipGetLastError());
@@ -772,8 +769,7 @@ int pick_points_check(uint32_t w, uint32_t h, uint32_t k, uint32_t n, const uint
 int hits_bind(rt_scene_dev *s, uint32_t w, uint32_t h, rt_hits_launch &L, hipStream_t stream) {
   memset(&L, 0, sizeof L);
   std::lock_guard<std::mutex> lk(s->launch_mu);
-  if (int rc = behind_the_camera(s, stream)) return rc;
-  note_launch(s, stream);
+  if (int rc = enter_launch(s, stream)) return rc;
   const rt_scene_header &hd = s->hd;
   L.objects = (const rt_sphere *)(obj_block(s) + s->o_objs);
   memcpy(L.cam, hd.cam_origin, 12 * sizeof(double));   // origin, axisX, axisY, axisZ are contiguous
@@ -821,10 +817,10 @@ extern "C" int rt_scene_pick(rt_scene_dev *s, uint32_t w, uint32_t h, uint32_t n
   rt_hits_launch L;
   if ((rc = hits_bind(s, w, h, L, D.stream))) return rc;
   L.n_points = n;
-  struct device_mem { void *p = nullptr; ~device_mem() { if (p) (void)hipFree(p); } } mem;
-  HIP_TRY(hipMalloc(&mem.p, (size_t)n * (sizeof(rt_hit) + 2u * sizeof(uint32_t))));
-  L.hits = (rt_hit *)mem.p;
-  L.points = (const uint32_t *)((uint8_t *)mem.p + (size_t)n * sizeof(rt_hit));
+  device_mem mem;
+  HIP_TRY(hipMalloc(&mem.h, (size_t)n * (sizeof(rt_hit) + 2u * sizeof(uint32_t))));
+  L.hits = (rt_hit *)mem.h;
+  L.points = (const uint32_t *)((uint8_t *)mem.h + (size_t)n * sizeof(rt_hit));
   HIP_TRY(hipMemcpyAsync((void *)L.points, xy, (size_t)n * 2u * sizeof(uint32_t), hipMemcpyHostToDevice, D.stream));
   const int e = rt_launch_pick(&L, D.stream);
   if (e != 0) return fail(RT_ERR_DEVICE, "pick kernel launch: %s", hipGetErrorString((hipError_t)e));
@@ -881,8 +877,7 @@ int trace_rays_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *
   memset(&L, 0, sizeof L);
   {
     std::lock_guard<std::mutex> lk(s->launch_mu);
-    if (int rc = behind_the_camera(s, stream)) return rc;
-    note_launch(s, stream);
+    if (int rc = enter_launch(s, stream)) return rc;
     L.stars_seed = hd.stars_seed;                      // (rt_scene_set_stars_seed: this launch's, whatever the next call sets)
     bind_scene_order(s, L);                            // (materials and texture descriptors are read from HBM)
   }
@@ -982,8 +977,7 @@ int occlusion_launch(rt_scene_dev *s, uint32_t n, const double *d_rays, const ui
   memset(&L, 0, sizeof L);
   {
     std::lock_guard<std::mutex> lk(s->launch_mu);
-    if (int rc = behind_the_camera(s, stream)) return rc;
-    note_launch(s, stream);
+    if (int rc = enter_launch(s, stream)) return rc;
     L.objects = (const rt_sphere *)(obj_block(s) + s->o_objs);   // this generation's spheres, in blob order
     L.light_intensity = hd.light_intensity;                      // (rt_scene_set_light_intensity: this launch's)
   }

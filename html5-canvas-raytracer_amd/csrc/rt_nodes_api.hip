@@ -27,8 +27,7 @@ int shade_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *d_ray
   memset(&L, 0, sizeof L);
   {
     std::lock_guard<std::mutex> lk(s->launch_mu);
-    if (int rc = behind_the_camera(s, stream)) return rc;
-    note_launch(s, stream);
+    if (int rc = enter_launch(s, stream)) return rc;
     L.objects = (const rt_sphere *)(obj_block(s) + s->o_objs);   // this generation's spheres, in blob order
     L.light_intensity = hd.light_intensity;                      // (rt_scene_set_light_intensity: this launch's)
     L.stars_seed = hd.stars_seed;                                // (rt_scene_set_stars_seed: this launch's)

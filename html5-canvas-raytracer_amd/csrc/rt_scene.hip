@@ -7,10 +7,12 @@
 
 // ------------------------------------------------------------------------------------ launch decisions of a resident scene
 namespace rt_api {
-// A launch of the scene is enqueued on `stream` (launch_mu held): what the next camera or object move orders itself behind
-void note_launch(rt_scene_dev *s, hipStream_t stream) {
-  if (s->any_launch && s->last_stream != stream) s->several_streams = true;
-  s->last_stream = stream; s->any_launch = true; s->launched_since_move = true;
+// The prologue of a launch of the scene on `stream` (launch_mu held): it comes behind the last texel edit and the current generation's
+// preparation, and the next move or edit orders itself behind it (rt_scene_sync.h: R1)
+int enter_launch(rt_scene_dev *s, hipStream_t stream) {
+  HIP_TRY(s->sync.before_launch(stream, s->cam_gen));
+  s->sync.note_launch(stream);
+  return RT_OK;
 }
 
 // Which kernel.  The product (FMA) kernel unless the caller asks for the strict one - or the scene itself sits on an exact
@@ -76,12 +78,6 @@ uint32_t count_use(rt_scene_dev *s, const frame_kind &kind) {
 
 // ------------------------------------------------------------------------------------ upload
 namespace {
-
-void free_order_entry(rt_scene_dev::order_entry &e) {
-  for (int b = 0; b < 2; b++) { if (e.d_blockb[b]) (void)hipFree(e.d_blockb[b]); e.d_blockb[b] = nullptr; }
-  if (e.built) (void)hipEventDestroy(e.built);
-  e.built = nullptr;
-}
 
 // [materials (rt_mtl) | 16 texture descriptors | cull rectangles (few spheres)] of ordering `ord`: the workgroup's LDS image
 void fill_lds_image(const rt_scene_dev *s, uint8_t *dst, int ord) {
@@ -260,15 +256,6 @@ void fill_object_block(const rt_scene_dev *s, uint8_t *dst) {
   }
 }
 
-// a staging slot of `bytes` (<= stage_bytes), free to be written: its previous copy has been read
-uint8_t *acquire_stage(rt_scene_dev *s, rt_scene_dev::stage_slot **slot) {
-  rt_scene_dev::stage_slot &g = s->stages[s->stage_next++ & 15u];
-  if (g.used) (void)hipEventSynchronize(g.done);
-  g.used = true;
-  *slot = &g;
-  return g.h;
-}
-
 std::atomic<int> g_uploads{0};       // rt_scene_upload calls (test build: rt_test_upload_count)
 constexpr size_t up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 }  // namespace
@@ -360,30 +347,23 @@ extern "C" int rt_scene_upload(int device, const void *blob, size_t bytes, rt_sc
   fill_camera_block(s, host.data() + off_cam0);
   memcpy(host.data() + off_cam1, host.data() + off_cam0, s->cam_bytes_used);
   // ---- one allocation, one copy ----
-  hipError_t e = hipMalloc((void **)&s->arena, s->arena_bytes);
-  if (e == hipSuccess) e = hipMemcpy(s->arena, host.data(), s->arena_bytes, hipMemcpyHostToDevice);
+  hipError_t e = hipMalloc(&s->arena.h, s->arena_bytes);
+  if (e == hipSuccess) e = hipMemcpy(s->arena.h, host.data(), s->arena_bytes, hipMemcpyHostToDevice);
   // pinned staging for what follows a camera move (the camera block) or an object move (the camera block, then the host-written
-  // part of the object block)
-  {
-    const size_t table_dyn = 512u + (size_t)NO * (sizeof(rt_ball) + sizeof(rt_cost_rect));      // a launch table's parameters, cone-test spheres and cost rectangles
-    const size_t move = up256(s->cam_bytes) + s->obj_host_bytes;
-    s->stage_bytes = up256(move > table_dyn ? move : table_dyn);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->stage_pool, s->stage_bytes * 16u, hipHostMallocDefault);
-    for (size_t i = 0; i < 16u; i++) {
-      s->stages[i].h = s->stage_pool ? s->stage_pool + i * s->stage_bytes : nullptr;
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&s->stages[i].done, hipEventDisableTiming);
-    }
-  }
+  // part of the object block): the ring's slots hold either, or a launch table's parameters, cone-test spheres and cost rectangles
+  const size_t table_dyn = 512u + (size_t)NO * (sizeof(rt_ball) + sizeof(rt_cost_rect)), move_bytes = up256(s->cam_bytes) + s->obj_host_bytes;
+  if (e == hipSuccess) e = s->sync.moves.make(up256(move_bytes > table_dyn ? move_bytes : table_dyn));
   if (e != hipSuccess) {
     const std::string why = hipGetErrorString(e);
     rt_scene_free(s);
     return fail(RT_ERR_DEVICE, "scene upload: %s", why.c_str());
   }
-  s->d_blob = s->arena + off_blob;
-  s->d_texdesc = (rt_texture_desc *)(s->arena + off_tex);
-  s->d_cones = s->has_bt ? (double *)(s->arena + off_cones) : nullptr;
-  s->d_obj_buf[0] = s->arena + off_obj0; s->d_obj_buf[1] = s->arena + off_obj1;
-  s->d_cam_buf[0] = s->arena + off_cam0; s->d_cam_buf[1] = s->arena + off_cam1;
+  uint8_t *arena = (uint8_t *)s->arena.h;
+  s->d_blob = arena + off_blob;
+  s->d_texdesc = (rt_texture_desc *)(arena + off_tex);
+  s->d_cones = s->has_bt ? (double *)(arena + off_cones) : nullptr;
+  s->d_obj_buf[0] = arena + off_obj0; s->d_obj_buf[1] = arena + off_obj1;
+  s->d_cam_buf[0] = arena + off_cam0; s->d_cam_buf[1] = arena + off_cam1;
   *out = s;
   return RT_OK;
 }
@@ -391,19 +371,7 @@ extern "C" int rt_scene_upload(int device, const void *blob, size_t bytes, rt_sc
 extern "C" void rt_scene_free(rt_scene_dev *s) {
   if (!s) return;
   if (G.inited && s->device < (int)G.dev.size()) (void)hipSetDevice(G.dev[s->device].hip_id);
-  (void)hipDeviceSynchronize();                    // nothing of this scene is in flight any more
-  if (s->arena) (void)hipFree(s->arena);
-  for (rt_scene_dev::stage_slot &g : s->stages) if (g.done) (void)hipEventDestroy(g.done);
-  if (s->stage_pool) (void)hipHostFree(s->stage_pool);
-  for (int b = 0; b < 2; b++) { if (s->old_done[b]) (void)hipEventDestroy(s->old_done[b]); if (s->prep_done[b]) (void)hipEventDestroy(s->prep_done[b]); }
-  if (s->side) (void)hipStreamDestroy(s->side);
-  if (s->tex_before) (void)hipEventDestroy(s->tex_before);
-  if (s->tex_done) (void)hipEventDestroy(s->tex_done);
-  for (rt_scene_dev::stage_slot &g : s->tex_stages) if (g.done) (void)hipEventDestroy(g.done);
-  if (s->tex_pool) (void)hipHostFree(s->tex_pool);
-  for (rt_scene_dev::order_entry &e : s->orders) free_order_entry(e);
-  for (const rt_scene_dev::mark_state &m : s->mark_states) (void)hipFree(m.d_marks);
-  if (s->h_known_pool) (void)hipHostFree(s->h_known_pool);
+  (void)hipDeviceSynchronize();                    // nothing of this scene is in flight any more: its members release what they own
   delete s;
 }
 
@@ -412,25 +380,14 @@ extern "C" void rt_scene_free(rt_scene_dev *s) {
 // arena) and the launch tables of the frame sizes in use - exists twice, for even and odd camera generations.  The move stages the
 // new block (pinned host memory) and, on the scene's OWN side stream, copies it and rebuilds the tables the previous camera's frames
 // used: beside those frames' launches, which are still running on the caller's stream, and ordered against them by two events
-// (rt_scene_dev: old_done, prep_done).  A plain `set_camera; render; set_camera; render ...` loop on one stream thereby overlaps frame
+// (rt_scene_sync.h: OLD, PREP).  A plain `set_camera; render; set_camera; render ...` loop on one stream thereby overlaps frame
 // k + 1's table build with frame k's trace - what round 3 needed two scene handles on two streams for.  Nothing waits on the host
 // unless launches of this scene are in flight on several caller streams (then the device is drained first).
 namespace rt_api {
-bool build_table(rt_scene_dev *s, int found, hipStream_t stream, rt_scene_dev::stage_slot *cam);
+bool build_table(rt_scene_dev *s, int found, hipStream_t stream, pinned_ring::slot *cam);
 }  // namespace rt_api
 
 namespace {
-// the scene's side stream (HIGH priority: its few hundred waves are launched INTO a chip the previous frame's trace keeps full; at
-// normal priority the table build's workgroups waited for slots and took 77 us instead of 20, profiles/r04_ab_log.md) and its events
-int ensure_side(rt_scene_dev *s) {
-  if (s->side) return RT_OK;
-  int prio_lo = 0, prio_hi = 0;
-  (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-  HIP_TRY(hipStreamCreateWithPriority(&s->side, hipStreamNonBlocking, prio_hi));
-  for (int b = 0; b < 2; b++) { HIP_TRY(hipEventCreateWithFlags(&s->old_done[b], hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&s->prep_done[b], hipEventDisableTiming)); }
-  return RT_OK;
-}
-
 // The host state of the scene has just changed - its camera (rt_scene_set_camera), its spheres (rt_scene_set_objects,
 // `objects_moved`) or its lights (rt_scene_set_lights), host decisions included - and generation old_gen + 1 begins: on the side
 // stream, behind the launches that read its blocks last (generation old_gen - 1), the camera block is copied and the object block
@@ -444,18 +401,14 @@ int ensure_side(rt_scene_dev *s) {
 // Lights reach the kernels by value (rt_light_list), from s->lights: the copy in d_blob is the upload's and is not read.
 // Everything keyed to the generation - launch tables, mark counts, camera_uses - is stale from here on.  launch_mu held.
 int next_generation(rt_scene_dev *s, uint64_t old_gen, bool objects_moved) {
-  // launches of this scene in flight on SEVERAL caller streams: no single event covers them (rare: drain the device)
-  if (s->any_launch && s->several_streams) { HIP_TRY(hipDeviceSynchronize()); s->any_launch = false; s->several_streams = false; s->launched_since_move = false; s->old_done_valid[0] = s->old_done_valid[1] = false; }
+  hipStream_t side = s->sync.side.h;
   const uint64_t G = ++s->cam_gen;
   const uint32_t b = (uint32_t)(G & 1u);
-  // every launch so far (generations < G) precedes this event on the caller's stream; the move to G + 1 will write blocks / tables
-  // (G + 1) & 1 - the ones generation G - 1 used - only behind it.  (No launch since the last move: the older record still covers them.)
-  if (s->launched_since_move && s->any_launch) { HIP_TRY(hipEventRecord(s->old_done[(G - 1u) & 1u], s->last_stream)); s->old_done_valid[(G - 1u) & 1u] = true; }
-  s->launched_since_move = false;
-  // blocks and tables b were last read by generation G - 2
-  if (s->old_done_valid[b]) HIP_TRY(hipStreamWaitEvent(s->side, s->old_done[b], 0));
-  rt_scene_dev::stage_slot *slot = nullptr;
-  uint8_t *st = acquire_stage(s, &slot);
+  // the side stream is behind the launches that read blocks and tables b last (generation G - 2)
+  HIP_TRY(s->sync.begin_generation(G));
+  pinned_ring::slot *slot = nullptr;
+  HIP_TRY(s->sync.moves.acquire(&slot));
+  uint8_t *st = slot->h;
   fill_camera_block(s, st);
   if (objects_moved) s->obj_version++;
   uint8_t *blk = s->d_obj_buf[b];
@@ -469,12 +422,12 @@ int next_generation(rt_scene_dev *s, uint64_t old_gen, bool objects_moved) {
       rt_light_list all = {};
       all.n = NL;
       for (uint32_t k = 0; k < NL; k++) { all.k[k] = k; memcpy(all.xyz[k], s->lights[k], 24u); }
-      e = (hipError_t)rt_launch_objects_copy(blk, so, s->obj_host_bytes, s->side);
-      if (e == hipSuccess && s->has_sg) e = (hipError_t)rt_launch_sgrid_build(loop, n_loop, NL, &all, (uint64_t *)(blk + s->o_sg), s->side);
-      if (e == hipSuccess && s->has_bt) e = (hipError_t)rt_launch_bounce_build(loop, NO, n_loop, s->d_cones, (uint64_t *)(blk + s->o_bt), s->side);
+      e = (hipError_t)rt_launch_objects_copy(blk, so, s->obj_host_bytes, side);
+      if (e == hipSuccess && s->has_sg) e = (hipError_t)rt_launch_sgrid_build(loop, n_loop, NL, &all, (uint64_t *)(blk + s->o_sg), side);
+      if (e == hipSuccess && s->has_bt) e = (hipError_t)rt_launch_bounce_build(loop, NO, n_loop, s->d_cones, (uint64_t *)(blk + s->o_bt), side);
       memcpy(s->slot_lights[b], s->lights, sizeof s->lights);
     } else {
-      e = hipMemcpyAsync(blk, s->d_obj_buf[b ^ 1u], s->obj_bytes, hipMemcpyDeviceToDevice, s->side);
+      e = hipMemcpyAsync(blk, s->d_obj_buf[b ^ 1u], s->obj_bytes, hipMemcpyDeviceToDevice, side);
       memcpy(s->slot_lights[b], s->slot_lights[b ^ 1u], sizeof s->lights);
     }
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "object block: %s", hipGetErrorString(e));
@@ -490,8 +443,8 @@ int next_generation(rt_scene_dev *s, uint64_t old_gen, bool objects_moved) {
       for (uint32_t j = 0; j < moved.n; j++) shadow_grid_frame(hloop, n_loop, moved.xyz[j], headers + 16u * j);
     }
     hipError_t e = (hipError_t)rt_launch_light_anchor((const rt_sphere *)(blk + s->o_objs), s->has_b ? (const rt_sphere *)(blk + s->o_objs_b) : nullptr, s->has_b ? 2u : 1u, NO, NL, &moved,
-                                                      (rt_geom *)(blk + s->o_geom), s->has_sg ? (double *)(blk + s->o_sg) : nullptr, headers, s->side);
-    if (e == hipSuccess && s->has_sg) e = (hipError_t)rt_launch_sgrid_build(loop, n_loop, NL, &moved, (uint64_t *)(blk + s->o_sg), s->side);
+                                                      (rt_geom *)(blk + s->o_geom), s->has_sg ? (double *)(blk + s->o_sg) : nullptr, headers, side);
+    if (e == hipSuccess && s->has_sg) e = (hipError_t)rt_launch_sgrid_build(loop, n_loop, NL, &moved, (uint64_t *)(blk + s->o_sg), side);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "object block, lights: %s", hipGetErrorString(e));
     memcpy(s->slot_lights[b], s->lights, sizeof s->lights);
   }
@@ -503,18 +456,16 @@ int next_generation(rt_scene_dev *s, uint64_t old_gen, bool objects_moved) {
   for (size_t i = 0; i < s->orders.size() && built < 4; i++) {
     rt_scene_dev::order_entry &e = s->orders[i];
     if (e.used_gen != old_gen || !e.built || (e.masks && !masks_pay(s, 0u))) continue;
-    if (!build_table(s, (int)i, s->side, cam_sent ? nullptr : slot)) return RT_ERR_DEVICE;
+    if (!build_table(s, (int)i, side, cam_sent ? nullptr : slot)) return RT_ERR_DEVICE;
     cam_sent = true;
     built++;
   }
   if (!cam_sent) {
-    hipError_t e = (hipError_t)rt_launch_small_copy(cam_block(s), st, s->cam_bytes_used, nullptr, nullptr, 0u, s->side);
-    if (e == hipSuccess) e = hipEventRecord(slot->done, s->side);
+    hipError_t e = (hipError_t)rt_launch_small_copy(cam_block(s), st, s->cam_bytes_used, nullptr, nullptr, 0u, side);
+    if (e == hipSuccess) e = s->sync.moves.done(slot, side);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "camera block: %s", hipGetErrorString(e));
   }
-  HIP_TRY(hipEventRecord(s->prep_done[b], s->side));
-  s->prep_valid[b] = true;
-  s->prep_waited.clear();
+  HIP_TRY(s->sync.end_generation(G));
   return RT_OK;
 }
 }  // namespace
@@ -531,7 +482,7 @@ extern "C" int rt_scene_set_camera(rt_scene_dev *s, const double origin[3], cons
   // the two orderings of the scene's tables are built around the sphere that encloses everything INCLUDING the camera
   if (enclosing_sphere(&nh, s->host_objects.data(), s->lights) != s->enclosing)
     return fail(RT_ERR_UNSUPPORTED, "rt_scene_set_camera: the camera crossed the enclosing sphere (the scene's tables are laid out around it): upload the scene again");
-  if ((rc = ensure_side(s))) return rc;
+  HIP_TRY(s->sync.ensure_side());
   const uint64_t old_gen = s->cam_gen;
   s->hd = nh;
   memcpy(s->host_blob.data(), &nh, sizeof nh);
@@ -563,7 +514,7 @@ extern "C" int rt_scene_set_objects(rt_scene_dev *s, uint32_t first, uint32_t co
   if (memcmp(next.data(), s->host_objects.data(), (size_t)NO * sizeof(rt_sphere)) == 0) return RT_OK;
   if (enclosing_sphere(&s->hd, next.data(), s->lights) != s->enclosing)
     return fail(RT_ERR_UNSUPPORTED, "rt_scene_set_objects: the edit changes the sphere that encloses everything (the scene's tables are laid out around it): upload the scene again");
-  if ((rc = ensure_side(s))) return rc;
+  HIP_TRY(s->sync.ensure_side());
   const uint64_t old_gen = s->cam_gen;
   s->host_objects.swap(next);
   object_decisions(s);
@@ -590,7 +541,7 @@ extern "C" int rt_scene_set_lights(rt_scene_dev *s, uint32_t first, uint32_t cou
   if (memcmp(next, s->lights, sizeof next) == 0) return RT_OK;
   if (enclosing_sphere(&s->hd, s->host_objects.data(), next) != s->enclosing)
     return fail(RT_ERR_UNSUPPORTED, "rt_scene_set_lights: the move changes the sphere that encloses everything (the scene's tables are laid out around it): upload the scene again");
-  if ((rc = ensure_side(s))) return rc;
+  HIP_TRY(s->sync.ensure_side());
   const uint64_t old_gen = s->cam_gen;
   memcpy(s->lights, next, sizeof next);
   memcpy(s->host_blob.data() + s->hd.lights_offset, next, (size_t)NL * 24u);
@@ -624,11 +575,11 @@ extern "C" int rt_scene_set_stars_seed(rt_scene_dev *s, uint32_t seed) {
 // ------------------------------------------------------------------------------------ texel edits
 // The texels of a resident scene's textures are replaced (the reference's textures are ImageData a page may draw into between two
 // redraws, main.js:339-395; sampled one texel at a time, main.js:343-351).  No generation, no table, no launch decision (rt_scene_dev:
-// tex_done): one write by rt_texels_blit on the caller's stream - behind the scene's launches in flight (stream order, or tex_before;
-// launches on several streams: the device is drained, as next_generation does) and in front of every later one (stream order, or
-// tex_done in behind_the_camera).  Only kernel boundaries order it: nothing relies on caches being coherent inside a kernel.
+// R4): one write by rt_texels_blit on the caller's stream - behind the scene's launches in flight (stream order, or TEXB;
+// launches on several streams: the device is drained, as a move does) and in front of every later one (stream order, or TEXD in
+// enter_launch).  Only kernel boundaries order it: nothing relies on caches being coherent inside a kernel.
 namespace {
-constexpr size_t RT_TEXEL_STAGE_SLOT = 256u * 1024u, RT_TEXEL_STAGE_SLOTS = 16u;    // 4 MiB of pinned memory (include/rt_hip.h says so)
+constexpr size_t RT_TEXEL_STAGE_SLOT = 256u * 1024u;    // of pinned_ring::n_slots = 16: 4 MiB of pinned memory (include/rt_hip.h says so)
 
 // the checks of both forms that need no scene
 int texels_args_check(const char *what, uint32_t w, uint32_t h, const void *src, size_t pitch_bytes, bool device) {
@@ -643,33 +594,6 @@ int texels_rect_check(const char *what, const rt_scene_dev *s, uint32_t texture,
   const rt_texture_desc &d = s->descs[texture];
   if ((uint64_t)x + w > d.width || (uint64_t)y + h > d.height)
     return fail(RT_ERR_INVALID, "%s: the rectangle [%u, %u + %u) x [%u, %u + %u) leaves texture %u (%ux%u): another size is an upload", what, x, x, w, y, y, h, texture, d.width, d.height);
-  return RT_OK;
-}
-
-// The write about to be enqueued on `stream` comes behind every launch of the scene so far and behind the edit before it; launch_mu held
-int texels_order_before(rt_scene_dev *s, hipStream_t stream) {
-  if (!s->tex_done) {
-    HIP_TRY(hipEventCreateWithFlags(&s->tex_before, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&s->tex_done, hipEventDisableTiming));
-  }
-  if (s->any_launch && s->several_streams) {
-    // launches of this scene in flight on SEVERAL caller streams: no single event covers them (rare: drain the device, like a move)
-    HIP_TRY(hipDeviceSynchronize());
-    s->any_launch = false; s->several_streams = false; s->launched_since_move = false; s->old_done_valid[0] = s->old_done_valid[1] = false;
-  } else if (s->any_launch && s->last_stream != stream) {
-    HIP_TRY(hipEventRecord(s->tex_before, s->last_stream));
-    HIP_TRY(hipStreamWaitEvent(stream, s->tex_before, 0));
-  }
-  if (s->tex_seq && s->tex_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, s->tex_done, 0));   // (two edits may overlap)
-  return RT_OK;
-}
-
-// ... and is in front of every later one
-int texels_order_after(rt_scene_dev *s, hipStream_t stream) {
-  HIP_TRY(hipEventRecord(s->tex_done, stream));
-  s->tex_seq++;
-  s->tex_stream = stream;
-  s->tex_waited.clear();
   return RT_OK;
 }
 
@@ -690,14 +614,8 @@ int set_texels(rt_scene_dev *s, uint32_t texture, uint32_t x, uint32_t y, uint32
   const size_t pitch = pitch_bytes ? pitch_bytes : 4u * (size_t)w;
   const uint32_t tex_w = s->descs[texture].width;
   std::lock_guard<std::mutex> lk(s->launch_mu);
-  if (!device) {
-    if (!s->tex_pool) HIP_TRY(hipHostMalloc((void **)&s->tex_pool, RT_TEXEL_STAGE_SLOT * RT_TEXEL_STAGE_SLOTS, hipHostMallocDefault));
-    for (size_t i = 0; i < RT_TEXEL_STAGE_SLOTS; i++) {
-      s->tex_stages[i].h = s->tex_pool + i * RT_TEXEL_STAGE_SLOT;
-      if (!s->tex_stages[i].done) HIP_TRY(hipEventCreateWithFlags(&s->tex_stages[i].done, hipEventDisableTiming));
-    }
-  }
-  if ((rc = texels_order_before(s, stream))) return rc;
+  if (!device) HIP_TRY(s->sync.texels.make(RT_TEXEL_STAGE_SLOT));
+  HIP_TRY(s->sync.begin_edit(stream));
   auto write = [&]() -> int {
     if (device) {
       const rt_texels_launch L = {texel_at(s, texture, x, y), (const uint32_t *)src, tex_w, pitch / 4u, w};
@@ -706,23 +624,23 @@ int set_texels(rt_scene_dev *s, uint32_t texture, uint32_t x, uint32_t y, uint32
     }
     // the rows are packed into pinned slots, which the blit reads over the host link: pieces of whole rows (a texture row is at most
     // 64 KiB: four rows and more per slot).  A slot is written again only after the piece that read it (its event): the one host wait,
-    // taken when the caller is RT_TEXEL_STAGE_SLOTS pieces ahead of the GPU.
+    // taken when the caller is sixteen pieces ahead of the GPU.
     const uint32_t rows_per = (uint32_t)(RT_TEXEL_STAGE_SLOT / (4u * (size_t)w));
     for (uint32_t j0 = 0; j0 < h; j0 += rows_per) {
       const uint32_t rows = h - j0 < rows_per ? h - j0 : rows_per;
-      rt_scene_dev::stage_slot &g = s->tex_stages[s->tex_stage_next++ % RT_TEXEL_STAGE_SLOTS];
-      if (g.used) HIP_TRY(hipEventSynchronize(g.done));
-      g.used = true;
-      for (uint32_t j = 0; j < rows; j++) memcpy(g.h + (size_t)j * 4u * w, (const uint8_t *)src + (size_t)(j0 + j) * pitch, 4u * (size_t)w);
-      const rt_texels_launch L = {texel_at(s, texture, x, y + j0), (const uint32_t *)g.h, tex_w, w, w};
+      pinned_ring::slot *g = nullptr;
+      HIP_TRY(s->sync.texels.acquire(&g));
+      for (uint32_t j = 0; j < rows; j++) memcpy(g->h + (size_t)j * 4u * w, (const uint8_t *)src + (size_t)(j0 + j) * pitch, 4u * (size_t)w);
+      const rt_texels_launch L = {texel_at(s, texture, x, y + j0), (const uint32_t *)g->h, tex_w, w, w};
       HIP_TRY((hipError_t)rt_launch_texels_blit(&L, rows, stream));
-      HIP_TRY(hipEventRecord(g.done, stream));
+      HIP_TRY(s->sync.texels.done(g, stream));
     }
     return RT_OK;
   };
   rc = write();
-  const int rc_after = texels_order_after(s, stream);       // (also behind pieces of an edit that failed half way)
-  return rc ? rc : rc_after;
+  const hipError_t after = s->sync.end_edit(stream);         // (also behind pieces of an edit that failed half way)
+  if (rc == RT_OK) HIP_TRY(after);
+  return rc;
 }
 }  // namespace
 
@@ -738,11 +656,11 @@ namespace rt_api {
 // a pinned host word of the scene's pool (generation << 32 | value + 1, written by a kernel): [0, RT_KNOWN_WORDS) the mark states',
 // [RT_KNOWN_WORDS, 2 RT_KNOWN_WORDS) the launch tables'
 volatile unsigned long long *known_word(rt_scene_dev *s, size_t index) {
-  if (!s->h_known_pool) {
-    if (hipHostMalloc((void **)&s->h_known_pool, 2 * RT_KNOWN_WORDS * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); s->h_known_pool = nullptr; return nullptr; }
-    memset(s->h_known_pool, 0, 2 * RT_KNOWN_WORDS * sizeof(unsigned long long));
+  if (!s->h_known_pool.h) {
+    if (hipHostMalloc(&s->h_known_pool.h, 2 * RT_KNOWN_WORDS * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); s->h_known_pool.h = nullptr; return nullptr; }
+    memset(s->h_known_pool.h, 0, 2 * RT_KNOWN_WORDS * sizeof(unsigned long long));
   }
-  return index < 2 * RT_KNOWN_WORDS ? s->h_known_pool + index : nullptr;
+  return index < 2 * RT_KNOWN_WORDS ? (unsigned long long *)s->h_known_pool.h + index : nullptr;
 }
 // what a kernel published for camera generation `gen`: value + 1, or 0 (nothing yet, or an older camera's)
 uint32_t known_value(const volatile unsigned long long *p, uint64_t gen) {
@@ -751,32 +669,10 @@ uint32_t known_value(const volatile unsigned long long *p, uint64_t gen) {
   return (uint32_t)(v >> 32) == (uint32_t)gen ? (uint32_t)v : 0u;
 }
 
-// The camera has moved since `stream` last launched the scene: its work comes behind the copy of the camera's block and the tables
-// rebuilt for it on the scene's side stream (rt_scene_set_camera).  One event wait per (stream, camera); launch_mu held.
-int behind_the_camera(rt_scene_dev *s, hipStream_t stream) {
-  // ... and behind the last texel edit, when that ran on another stream (rt_scene_set_texels): one event wait per (stream, edit)
-  if (s->tex_seq && stream != s->tex_stream) {
-    bool waits = false;
-    for (const rt_scene_dev::waited_on &q : s->tex_waited) if (q.stream == stream && q.gen == s->tex_seq) waits = true;
-    if (!waits) {
-      HIP_TRY(hipStreamWaitEvent(stream, s->tex_done, 0));
-      if (s->tex_waited.size() >= 16u) s->tex_waited.clear();
-      s->tex_waited.push_back(rt_scene_dev::waited_on{stream, s->tex_seq});
-    }
-  }
-  const uint32_t cb = (uint32_t)(s->cam_gen & 1u);
-  if (!s->prep_valid[cb]) return RT_OK;
-  for (const rt_scene_dev::waited_on &q : s->prep_waited) if (q.stream == stream && q.gen == s->cam_gen) return RT_OK;
-  HIP_TRY(hipStreamWaitEvent(stream, s->prep_done[cb], 0));
-  if (s->prep_waited.size() >= 16u) s->prep_waited.clear();
-  s->prep_waited.push_back(rt_scene_dev::waited_on{stream, s->cam_gen});
-  return RT_OK;
-}
-
 // Build the launch table of entry `found` for the scene's CURRENT camera (generation g, into the entry's table g & 1) on `stream`:
 // one small copy of its parameters - which also carries the staged camera block `cam` of a move, if given - and three small launches
 // (rt_tables_gpu.hip); nothing waits for them.  Called with the scene's launch_mu held.  false: rt_last_error says why.
-bool build_table(rt_scene_dev *s, int found, hipStream_t stream, rt_scene_dev::stage_slot *cam) {
+bool build_table(rt_scene_dev *s, int found, hipStream_t stream, pinned_ring::slot *cam) {
   rt_scene_dev::order_entry &e = s->orders[found];
   const frame_kind &k = e.kind;
   const launch_geom g = launch_geometry(s->hd.fov_deg, k.w, k.h, k.ss, k.tiles.tile_rows);
@@ -794,8 +690,8 @@ bool build_table(rt_scene_dev *s, int found, hipStream_t stream, rt_scene_dev::s
   const size_t hist_words = (size_t)P.ny * P.cost_bins;
   rt_table_dev &T = e.Tb[tb];
   // the table's device memory: one allocation behind all its arrays; the per-row histograms grow with the camera's cost range
-  if (!e.d_blockb[tb] || e.hist_wordsb[tb] < hist_words) {
-    if (e.d_blockb[tb]) { (void)hipDeviceSynchronize(); (void)hipFree(e.d_blockb[tb]); e.d_blockb[tb] = nullptr; }
+  if (!e.d_blockb[tb].h || e.hist_wordsb[tb] < hist_words) {
+    if (e.d_blockb[tb].h) { (void)hipDeviceSynchronize(); e.d_blockb[tb].reset(); }
     auto up = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
     const size_t cap_hist = hist_words > (size_t)P.ny * 128u ? hist_words : (size_t)P.ny * 128u;
     const size_t dyn_bytes = up(sizeof(rt_table_params)) + up((size_t)RT_MAX_OBJECTS * sizeof(rt_ball)) + up((size_t)RT_MAX_OBJECTS * sizeof(rt_cost_rect)) + 256u;
@@ -810,9 +706,9 @@ bool build_table(rt_scene_dev *s, int found, hipStream_t stream, rt_scene_dev::s
     uint8_t *blk = nullptr;
     hipError_t er = hipMalloc((void **)&blk, at);
     if (er == hipSuccess) er = hipMemsetAsync(blk + o_dyn + dyn_bytes - 256u, 0, 256u, stream);     // the scan's ticket
-    if (er == hipSuccess && !e.built) er = hipEventCreateWithFlags(&e.built, hipEventDisableTiming);
+    if (er == hipSuccess) er = e.built.make();
     if (er != hipSuccess) { if (blk) (void)hipFree(blk); fail(RT_ERR_DEVICE, "launch table (%zu bytes): %s", at, hipGetErrorString(er)); return false; }
-    e.d_blockb[tb] = blk;
+    e.d_blockb[tb].h = blk;
     e.hist_wordsb[tb] = cap_hist;
     T.params = (const rt_table_params *)(blk + o_dyn);
     T.ticket = (uint32_t *)(blk + o_dyn + dyn_bytes - 256u);
@@ -820,9 +716,9 @@ bool build_table(rt_scene_dev *s, int found, hipStream_t stream, rt_scene_dev::s
     T.row_hist = (uint32_t *)(blk + o_hist); T.bin_start = (uint32_t *)(blk + o_bins);
     T.header = (uint32_t *)(blk + o_head); T.entries = T.header + 4;
     T.known = (unsigned long long *)e.known;
-  } else if (e.shared && stream != s->side) {
+  } else if (e.shared && stream != s->sync.side.h) {
     // rebuilt lazily on a caller's stream while launches on ANOTHER caller's stream may still read this table's older contents: only
-    // when nothing is in flight (rare; a move's own rebuilds, on the side stream, come behind old_done instead)
+    // when nothing is in flight (rare; a move's own rebuilds, on the side stream, come behind OLD instead)
     (void)hipDeviceSynchronize();
   }
   e.n_blocks = n;
@@ -832,8 +728,9 @@ bool build_table(rt_scene_dev *s, int found, hipStream_t stream, rt_scene_dev::s
   e.built_on = stream; e.shared = false;
   // parameters, cone-test spheres and cost rectangles, packed: one staging slot, ONE small copy kernel - which also carries the
   // scene's camera block of a move (an SDMA copy in front of the build would cost two engine hand-overs, more than the copy)
-  rt_scene_dev::stage_slot *slot = nullptr;
-  uint8_t *st = acquire_stage(s, &slot);
+  pinned_ring::slot *slot = nullptr;
+  hipError_t er = s->sync.moves.acquire(&slot);
+  uint8_t *st = slot->h;
   const size_t o_balls = (sizeof(rt_table_params) + 15u) & ~(size_t)15u, o_rects = o_balls + balls.size() * sizeof(rt_ball);
   const size_t copy_bytes = o_rects + rects.size() * sizeof(rt_cost_rect);
   T.balls = (const rt_ball *)((const uint8_t *)T.params + o_balls);
@@ -841,11 +738,11 @@ bool build_table(rt_scene_dev *s, int found, hipStream_t stream, rt_scene_dev::s
   memcpy(st, &P, sizeof P);
   if (!balls.empty()) memcpy(st + o_balls, balls.data(), balls.size() * sizeof(rt_ball));
   if (!rects.empty()) memcpy(st + o_rects, rects.data(), rects.size() * sizeof(rt_cost_rect));
-  hipError_t er = (hipError_t)rt_launch_small_copy((void *)T.params, st, copy_bytes, cam ? cam_block(s) : nullptr, cam ? cam->h : nullptr, cam ? s->cam_bytes_used : 0u, stream);
-  if (er == hipSuccess) er = hipEventRecord(slot->done, stream);
-  if (er == hipSuccess && cam) er = hipEventRecord(cam->done, stream);
-  if (er == hipSuccess) er = (hipError_t)rt_launch_table_build(&T, P.tiles_x, P.ny, P.cost_bins, (uint32_t)copy_bytes, ((P.flags & RT_TABLE_WIDE) ? 1 : 0) | (stream == s->side ? 2 : 0), stream);
-  if (er == hipSuccess) er = hipEventRecord(e.built, stream);
+  if (er == hipSuccess) er = (hipError_t)rt_launch_small_copy((void *)T.params, st, copy_bytes, cam ? cam_block(s) : nullptr, cam ? cam->h : nullptr, cam ? s->cam_bytes_used : 0u, stream);
+  if (er == hipSuccess) er = s->sync.moves.done(slot, stream);
+  if (er == hipSuccess && cam) er = s->sync.moves.done(cam, stream);
+  if (er == hipSuccess) er = (hipError_t)rt_launch_table_build(&T, P.tiles_x, P.ny, P.cost_bins, (uint32_t)copy_bytes, ((P.flags & RT_TABLE_WIDE) ? 1 : 0) | (stream == s->sync.side.h ? 2 : 0), stream);
+  if (er == hipSuccess) er = hipEventRecord(e.built.h, stream);
   if (er != hipSuccess) { e.cam_gen = 0; fail(RT_ERR_DEVICE, "launch table build: %s", hipGetErrorString(er)); return false; }
   return true;
 }
@@ -863,9 +760,9 @@ int dispatch_order(rt_scene_dev *s, const frame_kind &kind, const table_choice &
   }
   if (found >= 0 && s->orders[found].cam_gen == s->cam_gen) {
     rt_scene_dev::order_entry &e = s->orders[found];
-    // built on another caller's stream: this stream's launches come behind the build (the side stream's builds: behind prep_done,
+    // built on another caller's stream: this stream's launches come behind the build (the side stream's builds: behind PREP,
     // which every stream waits for before its first launch with a camera)
-    if (e.built_on != stream && e.built_on != s->side) { if (hipStreamWaitEvent(stream, e.built, 0) != hipSuccess) { fail(RT_ERR_DEVICE, "launch table: hipStreamWaitEvent"); return -1; } e.shared = true; }
+    if (e.built_on != stream && e.built_on != s->sync.side.h) { if (hipStreamWaitEvent(stream, e.built.h, 0) != hipSuccess) { fail(RT_ERR_DEVICE, "launch table: hipStreamWaitEvent"); return -1; } e.shared = true; }
     e.used_gen = s->cam_gen;
     return found;
   }
@@ -879,7 +776,6 @@ int dispatch_order(rt_scene_dev *s, const frame_kind &kind, const table_choice &
     // in flight: the device is drained first; rare)
     if (s->orders.size() >= 64u) {
       (void)hipDeviceSynchronize();
-      free_order_entry(s->orders[s->order_evict % 64u]);
       found = (int)(s->order_evict++ % 64u);
       for (rt_scene_dev::mark_state &m : s->mark_states) if (m.order_index == (uint32_t)found && m.h_known) *m.h_known = 0ull;     // its mark counts were another table's
     } else {
@@ -887,7 +783,7 @@ int dispatch_order(rt_scene_dev *s, const frame_kind &kind, const table_choice &
       found = (int)s->orders.size() - 1;
     }
     rt_scene_dev::order_entry &e = s->orders[found];
-    memset(&e, 0, sizeof e);
+    e = rt_scene_dev::order_entry();                     // (an evicted table's memory and event go with it)
     e.kind = kind;
     e.ranked = c.ranked; e.sky = c.mark_sky; e.masks = c.shadow_masks; e.cands = c.name_candidates; e.cells = c.checker_cells;
     e.known = known_word(s, RT_KNOWN_WORDS + (size_t)found);
@@ -959,7 +855,7 @@ extern "C" int rt_test_launch_table(rt_scene_dev *s, uint32_t w, uint32_t h, con
   const frame_kind kind = {w, h, ss, *tiles, (ranked & 8) ? 1u : ((ranked & 16) ? 2u : 0u)};
   const table_choice c = {(ranked & 1) != 0, (ranked & 2) != 0, (ranked & 4) != 0, (ranked & 4) != 0, (ranked & 32) != 0};
   std::lock_guard<std::mutex> lk(s->launch_mu);
-  if ((rc = behind_the_camera(s, stream))) return rc;
+  HIP_TRY(s->sync.before_launch(stream, s->cam_gen));
   const int oi = dispatch_order(s, kind, c, stream);
   if (oi < 0) return RT_ERR_DEVICE;
   HIP_TRY(hipStreamSynchronize(stream));

@@ -11,6 +11,7 @@ import math
 import numpy as np
 import pytest
 
+import nodes_util as nu
 import rt_host
 import texture_util as tu
 from objects_util import FAST, PARTS, SKYBOX_R2, STRICT, Frames, fresh, gpu_table, host_table, load, oracle_gap, state, tlib  # noqa: F401
@@ -427,6 +428,59 @@ def test_the_host_form_turns_restyles_into_set_objects(tlib):
         got, _ = rt_host.render(w, h, s, lib=tlib)
         assert tlib.rt_test_upload_count() == uploads, fn.__name__
         assert got == fresh(tlib, s, w, h), fn.__name__
+
+
+def test_moves_between_renders_on_two_streams(tlib):
+    """Launches of the scene in flight on TWO caller streams when a move starts: no single event covers them, and the move drains the
+    device and forgets its launch state (rt_scene_sync.h: R2).  Three rounds of render on A, render on B, move - a camera move, a
+    one-sphere set_objects, a one-light set_lights - and a last frame on each stream, with the product and the strict kernel: every
+    frame is the fresh upload's frame of the scene in that state."""
+    w, h = 64, 32
+    states = [load("h8")]
+    for k in range(3):
+        s = copy.deepcopy(states[-1])
+        if k == 0:
+            s["camera"]["origin"] = [s["camera"]["origin"][0] + 0.75, s["camera"]["origin"][1] + 0.25, s["camera"]["origin"][2] - 0.5]
+        elif k == 1:
+            s["objects"][small(s)]["origin"][1] += 0.5
+        else:
+            s["lights"][0] = [s["lights"][0][0] - 3.0, s["lights"][0][1] + 2.0, s["lights"][0][2] + 1.0]
+        states.append(s)
+    streams = [C.c_void_p(), C.c_void_p()]
+    for st in streams:
+        assert nu.hip().hipStreamCreate(C.byref(st)) == 0
+    try:
+        for flags in (FAST, STRICT):
+            want = [fresh(tlib, sc, w, h, None, flags) for sc in states]
+            assert len(set(want)) == 4                             # (every move shows in the frame)
+            r = rt_host.Renderer(rt_host.flatten_scene(states[0]), 0, tlib)
+            try:
+                bufs = []
+                for k in range(4):                                 # three rounds, and the frames of the last move
+                    for st in streams:
+                        d = tlib.rt_alloc_device(0, w * h * 4)
+                        assert d, tlib.rt_last_error()
+                        bufs.append(d)
+                        r.render_tiles(w, h, d, None, stream=st.value, flags=flags)
+                    if k == 0:
+                        r.set_camera(states[1]["camera"])
+                    elif k == 1:
+                        i = small(states[1])
+                        r.set_objects(states[2]["objects"][i:i + 1], i)
+                    elif k == 2:
+                        r.set_lights(states[3]["lights"][:1], 0)
+                for st in streams:
+                    assert nu.hip().hipStreamSynchronize(st) == 0
+                for j, d in enumerate(bufs):
+                    host = C.create_string_buffer(w * h * 4)
+                    assert tlib.rt_copy_to_host(0, host, d, w * h * 4) == 0, tlib.rt_last_error()
+                    tlib.rt_free_device(0, d)
+                    assert host.raw == want[j // 2], (flags, "round", j // 2, "stream", j % 2)
+            finally:
+                r.close()
+    finally:
+        for st in streams:
+            assert nu.hip().hipStreamDestroy(st) == 0
 
 
 # ---- every texture index of a scene with sixteen textures of odd shapes
