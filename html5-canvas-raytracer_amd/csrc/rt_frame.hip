@@ -4,6 +4,7 @@
 // frame (interleaved row tiles stored straight into GPU 0's frame over xGMI; fallback: RGB24 bands + one RCCL gather + de-interleave).
 
 #include "rt_api_internal.h"
+#include "rt_literal.h"       // lit_finite6
 
 // ------------------------------------------------------------------------------------ de-interleave
 // src: for rank g, its tiles (g, g+R, g+2R, ...) stored contiguously, ranks `rank_stride` bytes apart.
@@ -589,7 +590,7 @@ extern "C" int rt_trace_rays_wavefront(const void *blob, size_t bytes, uint64_t 
     // left of rt_trace_rays is its guard: a ray with a non-finite component gives NaN x 3, which the store rule makes 0, 0, 0, 255 too
     for (uint64_t i = 0; i < n; i++) {
       const double *q = rays + 6u * i;
-      const bool finite = (q[0] - q[0]) + (q[1] - q[1]) + (q[2] - q[2]) + (q[3] - q[3]) + (q[4] - q[4]) + (q[5] - q[5]) == 0.0;
+      const bool finite = lit_finite6(q[0], q[1], q[2], q[3], q[4], q[5]);
       if (ho->rgb) ho->rgb[3u * i] = ho->rgb[3u * i + 1u] = ho->rgb[3u * i + 2u] = finite ? 0.0 : __builtin_nan("");
       if (ho->rgba) { uint8_t *o = ho->rgba + 4u * i; o[0] = o[1] = o[2] = 0u; o[3] = 255u; }
     }

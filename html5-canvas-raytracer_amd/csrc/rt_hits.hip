@@ -9,7 +9,8 @@
 //   * hit.p = p + d t, hit.n = (hit.p - origin) * (1 / |hit.p - origin|) (quirk q7); u, v with two divisions each (q6) and
 //     fdlibm's atan2 / asin (rt_fdlibm.h).
 // This file is compiled WITHOUT FMA contraction (csrc/Makefile), so t, p and n carry the bits of the C restatement
-// (oracle/rt_oracle.c) - no tolerance.  It shares no code with the colour kernels but fdlibm's functions: no launch table, no cull,
+// (oracle/rt_oracle.c) - no tolerance.  The sphere test, the closest-hit step and the hit record are rt_literal.h's, which the other list
+// kernels share; with the colour kernels it shares fdlibm's functions and rt_trace_rays' list head, nothing else: no launch table, no cull,
 // no camera-anchored tables (primary rays only; the loop is short and every sphere is a scalar load).
 //
 // MI355X mapping: one work-item per sample, 256 samples of one sample row per workgroup (grid y walks the rows of the band); the
@@ -25,7 +26,7 @@
 
 namespace {
 
-#include "rt_fdlibm.h"
+#include "rt_literal.h"       // the sphere test, the closest-hit step, the hit record, the ray record; rt_fdlibm.h
 
 #define RT_HITS_WG 256u
 
@@ -34,7 +35,7 @@ struct hit_core {
   double t, p[3], n[3];
 };
 
-// the first hit of the ray (o, r), r as given: main.js:220-231, 420-451, 440-449, operation for operation
+// the first hit of the ray (o, r), r as given: main.js:220-231, 420-451, 440-449 (rt_literal.h), every sphere a scalar load
 __device__ __forceinline__ hit_core ray_hit(const rt_hits_launch &L, const double ox, const double oy, const double oz, const double rx, const double ry,
                                             const double rz) {
   const double eps = L.epsilon;
@@ -44,19 +45,7 @@ __device__ __forceinline__ hit_core ray_hit(const rt_hits_launch &L, const doubl
   for (uint32_t i = 0; i < L.n_objects; i++) {
     // origin[3], r2: the first 32 bytes of the 192-byte rt_sphere record, one scalar load
     const double __attribute__((address_space(4))) *g = (const double __attribute__((address_space(4))) *)(tab + (size_t)i * sizeof(rt_sphere));
-    const double lx = g[0] - ox, ly = g[1] - oy, lz = g[2] - oz, r2 = g[3];
-    const double tca = rx * lx + ry * ly + rz * lz;
-    const double dd = (lx * lx + ly * ly + lz * lz) - tca * tca;
-    if (dd > r2) continue;
-    const double thc = sqrt(r2 - dd);
-    const double t0 = tca - thc, t1 = tca + thc;
-    double t;
-    if (t0 < t1) {
-      if (t0 < eps) { if (t1 < eps) continue; t = t1; } else t = t0;
-    } else {
-      if (t1 < eps) { if (t0 < eps) continue; t = t0; } else t = t1;
-    }
-    if (t < ht) { ht = t; hi = (int32_t)i; hin = (t0 < eps) || (t1 < eps); }
+    lit_closest_step((int32_t)i, g[0], g[1], g[2], g[3], ox, oy, oz, rx, ry, rz, eps, &ht, &hi, &hin);
   }
   hit_core H;
   H.t = ht;
@@ -67,11 +56,7 @@ __device__ __forceinline__ hit_core ray_hit(const rt_hits_launch &L, const doubl
   }
   H.id = hi | (hin << 16);
   const rt_sphere *s = L.objects + hi;                   // (per lane: the sphere this lane hit)
-  H.p[0] = ox + rx * ht; H.p[1] = oy + ry * ht; H.p[2] = oz + rz * ht;
-  double nx = H.p[0] - s->origin[0], ny = H.p[1] - s->origin[1], nz = H.p[2] - s->origin[2];
-  const double nl = sqrt(nx * nx + ny * ny + nz * nz);
-  if (nl != 0.0) { const double k = 1.0 / nl; nx *= k; ny *= k; nz *= k; }
-  H.n[0] = nx; H.n[1] = ny; H.n[2] = nz;
+  lit_hit_point(ox, oy, oz, rx, ry, rz, ht, s->origin[0], s->origin[1], s->origin[2], H.p, H.n);
   return H;
 }
 
@@ -83,8 +68,7 @@ __device__ __forceinline__ hit_core primary_hit(const rt_hits_launch &L, uint32_
   const double ty = oy + L.cam[4] * d1 + L.cam[7] * d1 + L.cam[10] * d1;
   const double tz = oz + L.cam[5] * d2 + L.cam[8] * d2 + L.cam[11] * d2;
   double rx = tx - ox, ry = ty - oy, rz = tz - oz;
-  const double l = sqrt(rx * rx + ry * ry + rz * rz);
-  if (l != 0.0) { const double k = 1.0 / l; rx *= k; ry *= k; rz *= k; }
+  (void)lit_unit(&rx, &ry, &rz);
   return ray_hit(L, ox, oy, oz, rx, ry, rz);
 }
 
@@ -96,10 +80,7 @@ __device__ __forceinline__ rt_hit hit_record(const hit_core &H) {
   r.t = H.t;
   for (int c = 0; c < 3; c++) { r.point[c] = H.p[c]; r.normal[c] = H.n[c]; }
   r.u = 0.0; r.v = 0.0;
-  if (H.id >= 0) {
-    r.u = fd_atan2(-H.n[2], -H.n[0]) / M_PI / 2 + 0.5;
-    r.v = fd_asin(-H.n[1]) / (M_PI / 2) / 2 + 0.5;
-  }
+  if (H.id >= 0) lit_hit_uv(H.n, &r.u, &r.v);
   return r;
 }
 
@@ -137,18 +118,12 @@ __global__ void __launch_bounds__(RT_HITS_WG) rt_pick_kernel(const rt_hits_launc
 // (rt_scene_trace_rays_ordered_device) work-item `item` takes ray j = ray_order[item] - record j in, record j out - and skips an entry
 // that names no ray.
 __global__ void __launch_bounds__(RT_HITS_WG) rt_ray_hit_kernel(const rt_hits_launch L) {
-  typedef double __attribute__((ext_vector_type(2))) d2;
-  const uint32_t item = blockIdx.x * RT_HITS_WG + threadIdx.x;
-  if (item >= L.n_rays) return;
-  const uint32_t j = L.ray_order ? L.ray_order[item] : item;
-  if (j >= L.n_rays) return;
-  const d2 *q = (const d2 *)(L.rays + 6u * (size_t)j);
-  const d2 a = q[0], b = q[1], c = q[2];
-  // x - x is 0 for every finite x and NaN otherwise
-  const bool finite = (a.x - a.x) + (a.y - a.y) + (b.x - b.x) + (b.y - b.y) + (c.x - c.x) + (c.y - c.y) == 0.0;
+  uint32_t j;
+  if (!lit_ordered(L.ray_order, blockIdx.x * RT_HITS_WG + threadIdx.x, L.n_rays, &j)) return;   // (past the list, or an order's entry that names no ray)
+  const lit_ray R = lit_load_ray(L.rays, j);
   hit_core H;
   H.id = -1; H.t = __builtin_inf(); H.p[0] = H.p[1] = H.p[2] = 0.0; H.n[0] = H.n[1] = H.n[2] = 0.0;
-  if (finite) H = ray_hit(L, a.x, a.y, b.x, b.y, c.x, c.y);
+  if (R.finite) H = ray_hit(L, R.ox, R.oy, R.oz, R.rx, R.ry, R.rz);
   L.hits[j] = hit_record(H);
 }
 

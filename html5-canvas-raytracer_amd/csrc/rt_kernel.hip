@@ -77,6 +77,7 @@
 
 namespace {
 
+#include "rt_literal.h"          // the list head of rt_trace_rays: lit_ordered, lit_load_ray
 #include "rt_kernel_math.h"      // v3, rt_sqrt / rt_rcp / rt_div / rt_pow*, rt_atan2_asin, to_byte, the stars hash
 #include "rt_kernel_entry.h"     // rt_pixel_of, rt_entry_*, rt_cold_args, rt_mark_append
 #include "rt_kernel_tables.h"    // rt_load_*, rt_mtl_*, rt_tex_desc, frame, park
@@ -507,20 +508,17 @@ __global__ void __launch_bounds__(RT_WG_THREADS) rt_retrace(const rt_launch L) {
 // on the way down the tree - and the guard keeps that argument to finite inputs.
 template <bool REFRACT>
 __global__ void __launch_bounds__(RT_WG_THREADS) rt_trace_rays(const rt_launch L, const uint32_t *order) {
-  typedef double __attribute__((ext_vector_type(2))) d2;
   const rt_mtl *mtl = (const rt_mtl *)L.lds_image;                         // (HBM: nothing is staged here)
   const rt_texture_desc *tex = (const rt_texture_desc *)((const char *)L.lds_image + (size_t)L.n_objects * sizeof(rt_mtl));
   for (uint32_t item = blockIdx.x * RT_WG_THREADS + threadIdx.x; item < L.n_rays; item += gridDim.x * RT_WG_THREADS) {
-    const uint32_t j = order ? order[item] : item;
-    if (j >= L.n_rays) continue;                                           // (an order's entry that names no ray)
-    const d2 *q = (const d2 *)(L.rays + 6u * (size_t)j);
-    const d2 a = q[0], b = q[1], c = q[2];
+    uint32_t j;
+    if (!lit_ordered(order, item, L.n_rays, &j)) continue;                 // (an order's entry that names no ray)
+    const lit_ray R = lit_load_ray(L.rays, j);
     double rgb[3] = {__builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
-    // x - x is 0 for every finite x and NaN otherwise
-    if ((a.x - a.x) + (a.y - a.y) + (b.x - b.x) + (b.y - b.y) + (c.x - c.x) + (c.y - c.y) == 0.0) {
+    if (R.finite) {
       uint32_t cnt[3] = {0u, 0u, 0u};
-      trace_pixel<REFRACT, false, false, false, true>(L, mtl, tex, nullptr, nullptr, rt_geom{0.0, 0.0, 0.0, 0.0}, 0u, 0.0, 0.0, 0.0, 0.0, mk(a.x, a.y, b.x),
-                                                      mk(b.y, c.x, c.y), rgb, cnt, false, 0u, L.ray_base + j, 0u, 0u);
+      trace_pixel<REFRACT, false, false, false, true>(L, mtl, tex, nullptr, nullptr, rt_geom{0.0, 0.0, 0.0, 0.0}, 0u, 0.0, 0.0, 0.0, 0.0, mk(R.ox, R.oy, R.oz),
+                                                      mk(R.rx, R.ry, R.rz), rgb, cnt, false, 0u, L.ray_base + j, 0u, 0u);
     }
     if (L.ray_rgb) { double *o = L.ray_rgb + 3u * (size_t)j; o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2]; }
     if (L.ray_rgba) L.ray_rgba[j] = to_byte(rgb[0]) | (to_byte(rgb[1]) << 8) | (to_byte(rgb[2]) << 16) | 0xff000000u;

@@ -8,9 +8,8 @@
 // This file is compiled WITHOUT FMA contraction (csrc/Makefile), sqrt and the division are correctly rounded, atan2 / asin are
 // fdlibm's (rt_fdlibm.h) and pow is OCML's, as in the strict build of rt_kernel.hip: a node carries the bits of the C restatement
 // (oracle/rt_oracle.c), and shade / spawn / fold level by level give rt_trace_rays' rgb bit for bit.  The arithmetic helpers are the
-// strict side of rt_kernel_math.h, included here as rt_kernel.hip includes it; restated here (their homes are other translation
-// units' anonymous namespaces, or C): the closest-hit loop and hit record of rt_hits.hip (ray_hit, hit_record), the shadow scan of
-// rt_occlusion.hip, the workgroup scan of rt_rays_order.hip, and the restatement's jsmin / jsmax.
+// strict side of rt_kernel_math.h, included here as rt_kernel.hip includes it; the closest-hit step, the hit record, the shadow-scan
+// step, the workgroup scan and jsmin / jsmax are rt_literal.h's, which rt_hits.hip, rt_occlusion.hip and rt_rays_order.hip share.
 //
 // MI355X mapping.  Shade: one work-item per ray, 256 per workgroup.  The hit loop, the light loop and the shadow scans run at the top
 // level of the kernel over wave-uniform indices - a lane that has no part in a step is masked, it does not branch around the loop -
@@ -33,6 +32,7 @@ namespace {
 
 #define RT_STRICT 1
 #define RT_INF __builtin_inf()
+#include "rt_literal.h"          // lit_closest_step, lit_hit_point / lit_hit_uv, lit_scan_step, lit_load_ray, workgroup_exclusive, jsmin / jsmax
 #include "rt_kernel_math.h"      // v3, unit, reflect, min1, rt_sqrt / rt_rcp / rt_pow, rt_atan2_asin (fdlibm), star_uniform, to_int32_bit0, to_byte
 
 typedef double __attribute__((ext_vector_type(2))) d2;
@@ -41,61 +41,39 @@ typedef double __attribute__((ext_vector_type(2), aligned(8))) d2u;     // a 16-
 static_assert(sizeof(rt_node) == 200 && offsetof(rt_node, sample) == 80 && offsetof(rt_node, reflect_dir) == 144 && offsetof(rt_node, children) == 192,
               "rt_node: the stores below go by these offsets");
 
-// Math.min / Math.max (oracle/rt_oracle.c: jsmin, jsmax): NaN if either argument is
-__device__ __forceinline__ double jsmin(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : (a < b ? a : b); }
-__device__ __forceinline__ double jsmax(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : (a > b ? a : b); }
-
 typedef const double __attribute__((address_space(4))) *kdouble;
 
 // ---------------------------------------------------------------------------------------------------------------- shade
 __global__ void __launch_bounds__(RT_NODES_WG) rt_nodes_shade(const rt_shade_launch L) {
-  const uint32_t item = blockIdx.x * RT_NODES_WG + threadIdx.x;
-  if (item >= L.n_rays) return;
-  const uint32_t i = L.order ? L.order[item] : item;
-  if (i >= L.n_rays) return;                                          // (an order's entry that names no ray)
-  const d2 *rq = (const d2 *)(L.rays + 6u * (size_t)i);
-  const d2 ra = rq[0], rb = rq[1], rc = rq[2];
-  const v3 p = mk(ra.x, ra.y, rb.x), d = mk(rb.y, rc.x, rc.y);
-  // x - x is 0 for every finite x and NaN otherwise
-  const bool finite = (ra.x - ra.x) + (ra.y - ra.y) + (rb.x - rb.x) + (rb.y - rb.y) + (rc.x - rc.x) + (rc.y - rc.y) == 0.0;
+  uint32_t i;
+  if (!lit_ordered(L.order, blockIdx.x * RT_NODES_WG + threadIdx.x, L.n_rays, &i)) return;   // (past the list, or an order's entry that names no ray)
+  const lit_ray R = lit_load_ray(L.rays, i);
+  const v3 p = mk(R.ox, R.oy, R.oz), d = mk(R.rx, R.ry, R.rz);
   const double eps = L.epsilon;
   const uint32_t N = L.n_objects;
   const char __attribute__((address_space(4))) *tab = (const char __attribute__((address_space(4))) *)L.objects;
   d2u *out = (d2u *)(L.nodes + i);
 
-  // ---- the closest hit: main.js:220-231, 420-451 (rt_hits.hip: ray_hit), every sphere in blob order, strict <, first wins
+  // ---- the closest hit: main.js:220-231, 420-451, every sphere in blob order, strict <, first wins
   double ht = __builtin_inf();
   int32_t hi = -1, hin = 0;
   for (uint32_t j = 0; j < N; j++) {
     const kdouble g = (kdouble)(tab + (size_t)j * sizeof(rt_sphere));
     const double gx = g[0], gy = g[1], gz = g[2], r2 = g[3];
-    if (!finite) continue;
-    const double lx = gx - p.x, ly = gy - p.y, lz = gz - p.z;
-    const double tca = d.x * lx + d.y * ly + d.z * lz;
-    const double dd = (lx * lx + ly * ly + lz * lz) - tca * tca;
-    if (dd > r2) continue;
-    const double thc = sqrt(r2 - dd);
-    const double t0 = tca - thc, t1 = tca + thc;
-    double t;
-    if (t0 < t1) {
-      if (t0 < eps) { if (t1 < eps) continue; t = t1; } else t = t0;
-    } else {
-      if (t1 < eps) { if (t0 < eps) continue; t = t0; } else t = t1;
-    }
-    if (t < ht) { ht = t; hi = (int32_t)j; hin = (t0 < eps) || (t1 < eps); }
+    if (!R.finite) continue;
+    lit_closest_step((int32_t)j, gx, gy, gz, r2, p.x, p.y, p.z, d.x, d.y, d.z, eps, &ht, &hi, &hin);
   }
   const bool hit = hi >= 0;
   const rt_sphere *s = L.objects + (hit ? hi : 0);                      // (per lane: the sphere this lane hit; a miss reads sphere 0 and uses nothing of it)
 
-  // ---- hit.p, hit.n, u, v (main.js:440-447; rt_hits.hip: hit_record), stored at once
+  // ---- hit.p, hit.n, u, v (main.js:440-447), stored at once
   v3 h = mk(0.0, 0.0, 0.0), n = mk(0.0, 0.0, 0.0);
   double hu = 0.0, hv = 0.0;
   if (hit) {
-    h = mk(p.x + d.x * ht, p.y + d.y * ht, p.z + d.z * ht);
-    double nl;
-    n = unit(mk(h.x - s->origin[0], h.y - s->origin[1], h.z - s->origin[2]), &nl);
-    hu = fd_atan2(-n.z, -n.x) / M_PI / 2 + 0.5;
-    hv = fd_asin(-n.y) / (M_PI / 2) / 2 + 0.5;
+    double hp[3], hn[3];
+    lit_hit_point(p.x, p.y, p.z, d.x, d.y, d.z, ht, s->origin[0], s->origin[1], s->origin[2], hp, hn);
+    lit_hit_uv(hn, &hu, &hv);
+    h = mk(hp[0], hp[1], hp[2]); n = mk(hn[0], hn[1], hn[2]);
   }
   {
     const unsigned long long head = (unsigned long long)(uint32_t)hi | ((unsigned long long)(uint32_t)hin << 32);
@@ -114,7 +92,7 @@ __global__ void __launch_bounds__(RT_NODES_WG) rt_nodes_shade(const rt_shade_lau
   double col[3];
   if (!hit) {
     const double nan = __builtin_nan("");
-    col[0] = finite ? L.miss_color[0] : nan; col[1] = finite ? L.miss_color[1] : nan; col[2] = finite ? L.miss_color[2] : nan;
+    col[0] = R.finite ? L.miss_color[0] : nan; col[1] = R.finite ? L.miss_color[1] : nan; col[2] = R.finite ? L.miss_color[2] : nan;
   } else {
     const int kind = s->sampler_kind;
     if (kind == RT_SAMPLER_TEXTURE) {
@@ -154,30 +132,16 @@ __global__ void __launch_bounds__(RT_NODES_WG) rt_nodes_shade(const rt_shade_lau
     const v3 sv = unit(sraw, &llen);
     const double sdot = dot(sv, l);
     const bool lit = shading && !(sdot <= 0.0);                          // surface faces away (main.js:292)
-    // rt_occlusion.hip's loop from the hit point along sv, the hit sphere left out (a lane whose intensity is 0 already can gain nothing)
+    // the shadow scan (rt_occlusion.hip's loop) from the hit point along sv, the hit sphere left out (a lane whose intensity is 0 already can gain nothing)
     bool live = lit && li != 0.0;
+    int32_t blocker;                                                    // (the scan names it; a node does not keep it)
     for (uint32_t j = 0; j < N; j++) {
       if (__builtin_amdgcn_ballot_w64(live) == 0) break;                // no lane of the wave has a sphere left to meet
       const kdouble g = (kdouble)(tab + (size_t)j * sizeof(rt_sphere));
       const double gx = g[0], gy = g[1], gz = g[2], r2 = g[3];
       const double o4 = g[12];                                          // albedo[4]: byte 96 of the record
       if (!live || (int32_t)j == hi) continue;
-      const double lx = gx - h.x, ly = gy - h.y, lz = gz - h.z;
-      const double tca = sv.x * lx + sv.y * ly + sv.z * lz;
-      const double dd = (lx * lx + ly * ly + lz * lz) - tca * tca;
-      if (dd > r2) continue;
-      const double thc = sqrt(r2 - dd);
-      const double t0 = tca - thc, t1 = tca + thc;
-      double t;
-      if (t0 < t1) {
-        if (t0 < eps) { if (t1 < eps) continue; t = t1; } else t = t0;
-      } else {
-        if (t1 < eps) { if (t0 < eps) continue; t = t0; } else t = t1;
-      }
-      if (t < llen) {
-        if (o4 != 0.0) li = li / o4;                                    // transparent occluder brightens (q2)
-        else { li = 0.0; live = false; }
-      }
+      lit_scan_step((int32_t)j, gx, gy, gz, r2, o4, h.x, h.y, h.z, sv.x, sv.y, sv.z, eps, llen, &li, &blocker, &live);   // (a transparent occluder brightens: q2)
     }
     if (lit && li != 0.0) {
       diffuse += li * sdot / lmag;                                      // main.js:306
@@ -228,23 +192,6 @@ __global__ void __launch_bounds__(RT_NODES_WG) rt_nodes_shade(const rt_shade_lau
 }
 
 // ---------------------------------------------------------------------------------------------------------------- spawn
-// the exclusive prefix of v over the workgroup's RT_NODES_WG work-items (tmp: RT_NODES_WG words of LDS); *total = the sum
-// (rt_rays_order.hip: workgroup_exclusive)
-__device__ __forceinline__ uint32_t workgroup_exclusive(uint32_t v, volatile uint32_t *tmp, uint32_t *total) {
-  const uint32_t t = threadIdx.x;
-  __syncthreads();                                              // (tmp may still be read from the previous use)
-  tmp[t] = v;
-  __syncthreads();
-  for (uint32_t off = 1u; off < RT_NODES_WG; off <<= 1) {
-    const uint32_t below = t >= off ? tmp[t - off] : 0u;
-    __syncthreads();
-    tmp[t] += below;
-    __syncthreads();
-  }
-  *total = tmp[RT_NODES_WG - 1u];
-  return tmp[t] - v;
-}
-
 __device__ __forceinline__ uint32_t children_of(const rt_node *nodes, uint32_t i, uint32_t n) { return i < n ? (nodes[i].children & 3u) : 0u; }
 
 // workgroup b: the children of parents [256 b, 256 b + 256) -> totals[b]
@@ -252,7 +199,7 @@ __global__ void __launch_bounds__(RT_NODES_WG) rt_nodes_spawn_count(const rt_spa
   __shared__ uint32_t s_tmp[RT_NODES_WG];
   const uint32_t ch = children_of(L.nodes, blockIdx.x * RT_NODES_WG + threadIdx.x, L.n);
   uint32_t total;
-  (void)workgroup_exclusive((ch & 1u) + (ch >> 1), s_tmp, &total);
+  (void)workgroup_exclusive<RT_NODES_WG>((ch & 1u) + (ch >> 1), s_tmp, &total);
   if (threadIdx.x == 0u) L.totals[blockIdx.x] = total;
 }
 
@@ -264,7 +211,7 @@ __global__ void __launch_bounds__(RT_NODES_WG) rt_nodes_spawn_scan(const rt_spaw
     const uint32_t i = base + threadIdx.x;
     const uint32_t v = i < tiles ? L.totals[i] : 0u;
     uint32_t total;
-    const uint32_t ex = workgroup_exclusive(v, s_tmp, &total);
+    const uint32_t ex = workgroup_exclusive<RT_NODES_WG>(v, s_tmp, &total);
     if (i < tiles) L.totals[i] = carry + ex;
     carry += total;
   }
@@ -277,7 +224,7 @@ __global__ void __launch_bounds__(RT_NODES_WG) rt_nodes_spawn_scatter(const rt_s
   const uint32_t i = blockIdx.x * RT_NODES_WG + threadIdx.x;
   const uint32_t ch = children_of(L.nodes, i, L.n);
   uint32_t total;
-  const uint32_t at = L.totals[blockIdx.x] + workgroup_exclusive((ch & 1u) + (ch >> 1), s_tmp, &total);
+  const uint32_t at = L.totals[blockIdx.x] + workgroup_exclusive<RT_NODES_WG>((ch & 1u) + (ch >> 1), s_tmp, &total);
   if (i >= L.n) return;
   const uint32_t c_r = at, c_f = at + (ch & 1u);                     // (< 2n: the prefixes are of these very counts)
   L.links[2u * (size_t)i] = (ch & 1u) ? (int32_t)c_r : -1;

@@ -26,26 +26,21 @@
 
 namespace {
 
+#include "rt_literal.h"       // the scan step, the ray record, the order indirection
+
 #define RT_OCCLUSION_WG 256u
 
 // With L.order (an order as rt_scene_trace_rays_ordered_device takes it) work-item `item` takes ray i = order[item] - every input of
 // ray i in, its outputs at index i out - and skips an entry that names no ray.  A ray with a non-finite component is not traced.
 __global__ void __launch_bounds__(RT_OCCLUSION_WG) rt_occlusion_kernel(const rt_occlusion_launch L) {
-  typedef double __attribute__((ext_vector_type(2))) d2;
-  const uint32_t item = blockIdx.x * RT_OCCLUSION_WG + threadIdx.x;
-  if (item >= L.n_rays) return;
-  const uint32_t i = L.order ? L.order[item] : item;
-  if (i >= L.n_rays) return;
-  const d2 *q = (const d2 *)(L.rays + 6u * (size_t)i);
-  const d2 a = q[0], b = q[1], c = q[2];
-  const double ox = a.x, oy = a.y, oz = b.x, rx = b.y, ry = c.x, rz = c.y;
-  // x - x is 0 for every finite x and NaN otherwise
-  const bool finite = (a.x - a.x) + (a.y - a.y) + (b.x - b.x) + (b.y - b.y) + (c.x - c.x) + (c.y - c.y) == 0.0;
+  uint32_t i;
+  if (!lit_ordered(L.order, blockIdx.x * RT_OCCLUSION_WG + threadIdx.x, L.n_rays, &i)) return;   // (past the list, or an order's entry that names no ray)
+  const lit_ray R = lit_load_ray(L.rays, i);
   const double len = L.length ? L.length[i] : __builtin_inf();
   const uint32_t skip = L.skip ? (uint32_t)L.skip[i] : ~0u;         // (a value outside [0, n_objects) matches no j)
   double li = L.intensity_in ? L.intensity_in[i] : L.light_intensity;
   int32_t blocker = -1;
-  bool live = finite;
+  bool live = R.finite;
   const double eps = L.epsilon;
   const char __attribute__((address_space(4))) *tab = (const char __attribute__((address_space(4))) *)L.objects;
   for (uint32_t j = 0; j < L.n_objects; j++) {
@@ -54,24 +49,9 @@ __global__ void __launch_bounds__(RT_OCCLUSION_WG) rt_occlusion_kernel(const rt_
     const double gx = g[0], gy = g[1], gz = g[2], r2 = g[3];
     const double a4 = g[12];                                        // albedo[4]: byte 96 of the record
     if (!live || j == skip) continue;
-    const double lx = gx - ox, ly = gy - oy, lz = gz - oz;
-    const double tca = rx * lx + ry * ly + rz * lz;
-    const double dd = (lx * lx + ly * ly + lz * lz) - tca * tca;
-    if (dd > r2) continue;
-    const double thc = sqrt(r2 - dd);
-    const double t0 = tca - thc, t1 = tca + thc;
-    double t;
-    if (t0 < t1) {
-      if (t0 < eps) { if (t1 < eps) continue; t = t1; } else t = t0;
-    } else {
-      if (t1 < eps) { if (t0 < eps) continue; t = t0; } else t = t1;
-    }
-    if (t < len) {
-      if (a4 != 0.0) li = li / a4;
-      else { li = 0.0; blocker = (int32_t)j; live = false; }
-    }
+    lit_scan_step((int32_t)j, gx, gy, gz, r2, a4, R.ox, R.oy, R.oz, R.rx, R.ry, R.rz, eps, len, &li, &blocker, &live);
   }
-  if (!finite) li = __builtin_nan("");
+  if (!R.finite) li = __builtin_nan("");
   if (L.intensity) L.intensity[i] = li;
   if (L.blocker) L.blocker[i] = blocker;
 }

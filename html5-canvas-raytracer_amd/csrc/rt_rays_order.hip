@@ -21,11 +21,13 @@
 // stores are runs of consecutive addresses, one run per digit.  Keys and indices are separate arrays: the histogram reads 4 bytes
 // per key, the first pass reads no indices (they are 0..n-1) and the last writes no keys.
 // Traffic per ray: 48 (bounds) + 48 + 4 (keys) + 4 x 4 (histograms) + 12 + 16 + 16 + 12 (scatters) = 176 bytes.
+#include <math.h>
+
 #include "rt_rays_order.h"
 
 namespace {
 
-typedef double __attribute__((ext_vector_type(2))) d2;
+#include "rt_literal.h"       // the ray record and its finite test, workgroup_exclusive
 
 // word w of the bounds block: min of coordinate w (w < 6), max of coordinate w - 6 (6 <= w < 12), as ordered integers
 #define RT_ORDER_COORDS 6u
@@ -39,15 +41,12 @@ __device__ __forceinline__ float float_of(uint32_t u) { return __uint_as_float(u
 
 // the six coordinates of ray i, every one a finite float whatever the record holds; false: the ray has a non-finite component
 __device__ __forceinline__ bool ray_coords(const double *rays, uint32_t i, float c[RT_ORDER_COORDS]) {
-  const d2 *q = (const d2 *)(rays + 6u * (size_t)i);
-  const d2 a = q[0], b = q[1], e = q[2];
-  // x - x is 0 for every finite x and NaN otherwise
-  const bool finite = (a.x - a.x) + (a.y - a.y) + (b.x - b.x) + (b.y - b.y) + (e.x - e.x) + (e.y - e.y) == 0.0;
+  const lit_ray R = lit_load_ray(rays, i);
   const double big = 3.0e38;                                    // (binary64 origins beyond binary32's range share the outermost cell)
-  c[0] = (float)fmin(fmax(a.x, -big), big);
-  c[1] = (float)fmin(fmax(a.y, -big), big);
-  c[2] = (float)fmin(fmax(b.x, -big), big);
-  const double dx = b.y, dy = e.x, dz = e.y;
+  c[0] = (float)fmin(fmax(R.ox, -big), big);
+  c[1] = (float)fmin(fmax(R.oy, -big), big);
+  c[2] = (float)fmin(fmax(R.oz, -big), big);
+  const double dx = R.rx, dy = R.ry, dz = R.rz;
   const double ax = fabs(dx), ay = fabs(dy), az = fabs(dz);
   // the major axis (the first of equals), then the two others over it
   const int axis = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
@@ -57,7 +56,7 @@ __device__ __forceinline__ bool ray_coords(const double *rays, uint32_t i, float
   c[3] = fminf(fmaxf((float)(u * r), -1.f), 1.f);               // (a zero direction: 0 x inf = NaN, which fmaxf drops)
   c[4] = fminf(fmaxf((float)(v * r), -1.f), 1.f);
   c[5] = (float)(2 * axis + (major < 0.0 ? 1 : 0));
-  return finite;
+  return R.finite;
 }
 
 // ---- the list's bounds: per coordinate min and max over the finite rays, as ordered integers (atomic min / max: any order of
@@ -110,22 +109,6 @@ __global__ void __launch_bounds__(RT_ORDER_WG) rt_order_keys(const double *rays,
 }
 
 // ---- the radix passes
-// the exclusive prefix of v over the workgroup's RT_ORDER_WG work-items (tmp: RT_ORDER_WG words of LDS); *total = the sum
-__device__ __forceinline__ uint32_t workgroup_exclusive(uint32_t v, volatile uint32_t *tmp, uint32_t *total) {
-  const uint32_t t = threadIdx.x;
-  __syncthreads();                                              // (tmp may still be read from the previous use)
-  tmp[t] = v;
-  __syncthreads();
-  for (uint32_t off = 1u; off < RT_ORDER_WG; off <<= 1) {
-    const uint32_t below = t >= off ? tmp[t - off] : 0u;
-    __syncthreads();
-    tmp[t] += below;
-    __syncthreads();
-  }
-  *total = tmp[RT_ORDER_WG - 1u];
-  return tmp[t] - v;
-}
-
 // tile b's digit counts -> hist[digit * tiles + b]
 __global__ void __launch_bounds__(RT_ORDER_WG) rt_order_histogram(const uint32_t *keys, uint32_t n, uint32_t shift, uint32_t tiles, uint32_t *hist) {
   __shared__ uint32_t s_h[RT_ORDER_DIGITS];
@@ -149,7 +132,7 @@ __global__ void __launch_bounds__(RT_ORDER_WG) rt_order_scan(uint32_t *hist, uin
     const uint32_t i = base + threadIdx.x;
     const uint32_t v = i < tiles ? row[i] : 0u;
     uint32_t total;
-    const uint32_t ex = workgroup_exclusive(v, s_tmp, &total);
+    const uint32_t ex = workgroup_exclusive<RT_ORDER_WG>(v, s_tmp, &total);
     if (i < tiles) row[i] = carry + ex;
     carry += total;
   }
@@ -198,8 +181,8 @@ __global__ void __launch_bounds__(RT_ORDER_WG) rt_order_scatter(const uint32_t *
     uint32_t count = 0u;
     for (uint32_t w = 0; w < WAVES; w++) { const uint32_t c = s_wave[w][tid]; s_wave[w][tid] = count; count += c; }
     uint32_t total;
-    s_tile[tid] = workgroup_exclusive(count, s_tmp, &total);
-    s_dest[tid] = workgroup_exclusive(totals[tid], s_tmp, &total) + hist[(size_t)tid * tiles + blockIdx.x];
+    s_tile[tid] = workgroup_exclusive<RT_ORDER_WG>(count, s_tmp, &total);
+    s_dest[tid] = workgroup_exclusive<RT_ORDER_WG>(totals[tid], s_tmp, &total) + hist[(size_t)tid * tiles + blockIdx.x];
   }
   __syncthreads();
 #pragma unroll
