@@ -314,7 +314,8 @@ extern "C" int rt_scene_launch_table(const void *blob, size_t bytes, uint32_t w,
   const uint32_t ss = hd->supersample;
   const launch_geom g = launch_geometry(hd->fov_deg, w, h, ss, tiles->tile_rows);
   if ((uint64_t)tiles->n_tiles * g.rb_per_tile > 65535u) return fail(RT_ERR_INVALID, "too many row blocks");
-  // (bit 5 of `ranked`, with bit 2: word 3 also carries the checker cells of one-candidate blocks, as a product frame's table does)
+  // (bit 5 of `ranked`, with bit 2: word 3 also carries the checker cells of one-candidate blocks, as a product frame's table does;
+  // bit 6, with bit 5: and the per-axis statements of the columns that are not inside one cell, rt_block.h: rt_cells_word)
   // (bit 1 of `ranked`: also mark the workgroups no sphere but the enclosing one can show in, as a launch of a constant-background scene does)
   double lights[RT_MAX_LIGHTS][3];
   memset(lights, 0, sizeof lights);
@@ -322,7 +323,7 @@ extern "C" int rt_scene_launch_table(const void *blob, size_t bytes, uint32_t w,
   const uint32_t sky_sphere = enclosing_sphere(hd, ob, lights);
   uint32_t n_entries = 0;
   const std::vector<uint32_t> table = build_launch_table(hd, ob, cull, weight, w, h, ss, tiles, g.tiles_x, g.rb_per_tile, g.proj_w, g.proj_h, g.proj_d, (ranked & 1) != 0, (ranked & 2) != 0, sky_sphere,
-                                                         (ranked & 4) != 0, (ranked & 4) != 0, (ranked & 32) != 0, lights, &n_entries, (ranked & 8) ? 1u : ((ranked & 16) ? 2u : 0u));
+                                                         (ranked & 4) != 0, (ranked & 4) != 0, (ranked & 32) ? ((ranked & 64) ? 2 : 1) : 0, lights, &n_entries, (ranked & 8) ? 1u : ((ranked & 16) ? 2u : 0u));
   if (table.empty()) return fail(RT_ERR_INVALID, "a launch of this size is beyond the launch table");
   *n_workgroups = n_entries;
   if (n_blocks) *n_blocks = g.tiles_x * tiles->n_tiles * g.rb_per_tile;

@@ -21,7 +21,8 @@
 //                  as empty (0) or not (0xffff);
 //   * checker cells (RT_TABLE_CELLS) - for a block with ONE candidate whose sampler is the sphere checker: which of its four 8-pixel
 //                  columns lie, with every sample, inside one checker cell, and that cell's parity (rt_column_cell); bits 18..25 of
-//                  the candidates' word;
+//                  the candidates' word; with RT_TABLE_AXES also which of the other columns lie inside one cell of ONE of the checker's
+//                  two axes (rt_cells_word); bits 26..30;
 //   * cost       - 1 + the weights of the spheres whose screen rectangle (the primary-ray cull's) touches the block, + what its
 //                  mirrors show of the scene's dearest spheres (rt_bounce_cost): what ranks the blocks dearest first.
 #ifndef RT_BLOCK_H
@@ -48,9 +49,10 @@
 #define RT_TABLE_SKY_ONLY 128u   /* RT_FLAG_SKY_ONLY: the table holds ONLY the sky runs */
 #define RT_TABLE_BOUNCE 256u     /* ranked launch of a scene with a sphere that both reflects and refracts: a block's cost also counts such spheres seen in its mirrors */
 #define RT_TABLE_CELLS 512u      /* checker cells: word 3 also says which 8-pixel columns of a one-candidate block lie inside ONE checker cell (rt_column_cell) */
+#define RT_TABLE_AXES 1024u      /* checker cells, per axis (with RT_TABLE_CELLS): a column that is NOT inside one cell may still lie inside one cell of ONE axis (rt_cells_word) */
 #define RT_SKY_RUN_MAX 32u       /* consecutive sky blocks of a row block that share ONE entry */
 #define RT_CAND_MASK 0x3ffffu     /* word 3, bits 0..17: the candidates; what every reader of them keeps */
-#define RT_CELL_SHIFT 18u        /* ... bits 18..21: column c (bit 18 + c) lies inside one checker cell; bits 22..25: that cell's parity */
+#define RT_CELL_SHIFT 18u        /* ... bits 18..21: column c (bit 18 + c) lies inside one checker cell; bits 22..25: that cell's parity; RT_TABLE_AXES: and bits 26..30, rt_cells_word */
 #define RT_COST_MAX 1023u        /* costs are clamped here (the ranking only has to order the blocks roughly) */
 
 // a sphere as the cone test sees it (one per sphere but the enclosing one, scene order)
@@ -257,21 +259,50 @@ RT_HD inline bool rt_cand_masks(const rt_table_params &P, const rt_cone &K, cons
 
 // Checker cells (RT_TABLE_CELLS).  A block with ONE candidate whose sampler is the sphere checker (main.js:126-133): do all the primary
 // rays of column `col` of the block - the 8 x 8 pixels (supersample 2: the 16 x 4 samples) of one wave of the one-wave trace kernels -
-// meet the candidate, and all inside the SAME checker cell?  Returns 1 | parity << 1 if so, else 0 (no statement).
-//   The column's rays lie in its own cone (rt_box_cone); their hits on the candidate lie in the ball around Q = the axis point at the
-// mid hit distance with radius rho (the bound of rt_cand_masks, here with the column's cone), so h - o lies within rho of W = Q - o -
-// wherever on the patch, whose outline is arcs, not the corners' hull.  From that
-//   v = asin(-(h - o).z / r) / pi + 1/2:   -(h - o).z / r within [(-W.z - rho) / r, (-W.z + rho) / r], asin is monotonic; an end at or
-//                                          beyond a pole: no statement;
-//   u = atan2(-(h - o).y, -(h - o).x) / 2 pi + 1/2:   the point (-(h - o).x, -(h - o).y) lies within rho of p0 = (-W.x, -W.y), so its angle
-//                                          within asin(rho / |p0|) of p0's; the z axis inside that disc, or the interval reaching
-//                                          the branch cut at +-pi: no statement.
-// The statement holds when [u_lo f_u, u_hi f_u] and [v_lo f_v, v_hi f_v] each lie inside one unit cell and at least `margin` off
-// its ends: 2^-18, twice the kernel's prefilter band (RT_XY_INDEX in rt_kernel.hip: a fraction within 2^-20 below or 2^-19 above an
-// integer; the scaled mark tolerance only acts INSIDE that band), plus 1e-10 f for the rounding of this bound and of the kernel's
-// own u, v (a few ulp of 1/2, times f) - so no sample of a flagged column can reach the precise test or the mark list.
+// meet the candidate, and all inside the SAME checker cell?  Returns a set of RT_COL_* bits: RT_COL_U / RT_COL_V - every sample's u f_u
+// (v f_v) lies inside ONE unit cell, RT_COL_U_ODD / RT_COL_V_ODD - that cell's index is odd; RT_COL_CELL (| RT_COL_ODD) - both hold, so
+// all samples lie in one checker cell (of that parity).  0: no statement.
+//   The hit point is bounded PER OBJECT AXIS, not by a ball: a floor column seen at a grazing angle is a strip, long in depth and a few
+// centimetres across, and a ball around it hands the strip's length to every coordinate.
+//   direction   the column's raw rays are (s0 X, s1 Y, s2 D), X in [X0, X1], Y in [Y0, Y1] (quirk q1: a box with the frame's axes as edges);
+//               the length's range [L0, L1] follows from the ranges of (s0 X)^2 and (s1 Y)^2, and a component of the unit direction is
+//               the raw component's interval over [L0, L1], each end times the reciprocal of the length that pushes it outwards;
+//   distance    t = c - sqrt(c^2 - k), c = d.C (C: camera -> centre), decreasing in c; c = N / L with N = raw ray . C linear in X, Y - its
+//               range is that of its four corner values - so c lies in [N_lo / L1, min(N_hi / L0, |C|)], N_lo > 0.  EVERY ray meets the
+//               sphere: the column's cone (rt_box_cone) lies inside the silhouette, clear of the horizon, as before;
+//   hit point   (h - o).a lies in (cam - o).a + [t1, t2] x [d_lo, d_hi].a (an interval product), t widened by 1e-6 relative and each end by
+//               1e-9 t2 and the rounding of cam - o; v first: without RT_TABLE_AXES a column whose v cannot be stated is done;
+//   v = asin(-(h - o).z / r) / pi + 1/2:   asin is monotonic; an end at or beyond a pole: no statement about v;
+//   u = atan2(-(h - o).y, -(h - o).x) / 2 pi + 1/2:   the point (-(h - o).x, -(h - o).y) lies in a rectangle; one that contains or touches the
+//               z axis, or the branch cut at +-pi: no statement about u.  Else the angle has no extremum inside the rectangle and is monotonic
+//               along each edge: its range is attained at two corners, chosen by the rectangle's signs (d angle / dx = -y / rho^2,
+//               d angle / dy = x / rho^2).
+// An axis is stated when [lo f, hi f] lies inside one unit cell and at least `margin` off its ends: 2^-18, twice the kernel's prefilter
+// band (RT_XY_INDEX in rt_kernel.hip: a fraction within 2^-20 below or 2^-19 above an integer; the scaled mark tolerance only acts INSIDE
+// that band), plus 1e-10 f for the rounding of this bound and of the kernel's own u, v (a few ulp of 1/2, times f) - so no sample of a
+// stated column can reach the precise test or the mark list on that axis.
 // Plain binary64 and fdlibm's asin / atan2 restated (rt_fdlibm.h): the same bits on the host and on the device.
+#define RT_COL_CELL 1u
+#define RT_COL_ODD 2u
+#define RT_COL_U 4u
+#define RT_COL_U_ODD 8u
+#define RT_COL_V 16u
+#define RT_COL_V_ODD 32u
 RT_HD inline void rt_block_place(const rt_table_params &P, uint32_t x, uint32_t y, uint32_t *w0, uint32_t *w1);
+// lo f .. hi f inside one unit cell, `margin` off its ends: 1 | (the cell's index & 1) << 1, else 0
+RT_HD inline uint32_t rt_axis_cell(double lo, double hi, double f) {
+  const double x0 = lo * f, x1 = hi * f, mg = 3.814697265625e-06 + 1e-10 * f, k = floor(x0);
+  if (!(x1 >= x0) || !(k >= 0.0) || !(k <= 4294967295.0) || !(x0 - k >= mg) || !((k + 1.0) - x1 >= mg)) return 0u;
+  return 1u | (((uint32_t)k & 1u) << 1);
+}
+// (h - o).a for hit distances in [t1, t2] and the raw ray's component in [r0, r1]; i0 >= i1 > 0: the reciprocals of the length's ends
+RT_HD inline void rt_axis_range(double r0, double r1, double i0, double i1, double t1, double t2, double cam, double o, double *lo, double *hi) {
+  const double d_lo = r0 * (r0 >= 0.0 ? i1 : i0), d_hi = r1 * (r1 >= 0.0 ? i0 : i1);
+  const double pad = 1e-9 * t2 + 4e-16 * (fabs(cam) + fabs(o)), e = cam - o;
+  *lo = e + fmin(t1 * d_lo, t2 * d_lo) - pad; *hi = e + fmax(t1 * d_hi, t2 * d_hi) + pad;
+}
+// (not forced inline: inlined into the device build's row kernel it spills well over a hundred scalar registers there and the table build
+// is slower than with the call: docs/EVIDENCE.md)
 RT_HD inline uint32_t rt_column_cell(const rt_table_params &P, const rt_ball &B, uint32_t x, uint32_t y, uint32_t col) {
   if (!B.checker || B.everywhere) return 0u;
   uint32_t w0, w1;
@@ -283,39 +314,81 @@ RT_HD inline uint32_t rt_column_cell(const rt_table_params &P, const rt_ball &B,
   const double X0 = (double)((uint64_t)x * P.wg_w + (uint64_t)col * cw) + (0.5 - P.proj_w), X1 = X0 + (double)(cw - 1u);
   const rt_cone K = rt_box_cone(P, X0, X1, Y0, Y1);
   if (K.doubt) return 0u;
-  // the hit distances [t1, t2] and the ball (Q, rho) of the hits: rt_cand_masks' own bound
-  const double *ax = K.ax;
-  const double cos_a = K.cos_a, sin_a = K.sin_a;
-  const double cs = fmin(1.0, fmax(-1.0, ax[0] * B.c[0] + ax[1] * B.c[1] + ax[2] * B.c[2])), sn = sqrt(1.0 - cs * cs);
-  const double c_hi = B.len * ((cs * cos_a + sn * sin_a >= 1.0 || sn <= sin_a) ? 1.0 : cs * cos_a + sn * sin_a);
-  const double c_lo = fmax(B.len * (cs * cos_a - sn * sin_a), B.tangent);
-  if (!(B.k > 0.0) || !(c_hi * c_hi >= B.k) || !(c_hi >= c_lo) || !(B.len - B.R >= 2.0 * fabs(P.epsilon))) return 0u;
-  // EVERY ray of the cone meets the sphere: the cone lies inside the silhouette, clear of the horizon (d.C >= the tangent length, with room)
-  if (!(B.len * (cs * cos_a - sn * sin_a) >= B.tangent * (1.0 + 1e-7))) return 0u;
+  // EVERY ray of the column's cone meets the sphere from outside: the cone lies inside the silhouette, clear of the horizon (d.C >= the
+  // tangent length, with room).  (The kernel takes the FAR root when the near one lies within epsilon of the origin, main.js:431-436: a
+  // camera that close to a sphere gets no statement.)
+  const double cs = fmin(1.0, fmax(-1.0, K.ax[0] * B.c[0] + K.ax[1] * B.c[1] + K.ax[2] * B.c[2])), sn = sqrt(1.0 - cs * cs);
+  if (!(B.k > 0.0) || !(B.len - B.R >= 2.0 * fabs(P.epsilon)) || !(B.r > 0.0)) return 0u;
+  if (!(B.len * (cs * K.cos_a - sn * K.sin_a) >= B.tangent * (1.0 + 1e-7))) return 0u;
+  // the raw rays' box, the length's range and the unit direction's components
+  const double ax = P.as0 * X0, bx = P.as0 * X1, ay = P.as1 * Y0, by = P.as1 * Y1, rz = P.as2 * P.proj_d;
+  const double rx0 = fmin(ax, bx), rx1 = fmax(ax, bx), ry0 = fmin(ay, by), ry1 = fmax(ay, by);
+  const double qx0 = (rx0 <= 0.0 && rx1 >= 0.0) ? 0.0 : fmin(ax * ax, bx * bx), qx1 = fmax(ax * ax, bx * bx);
+  const double qy0 = (ry0 <= 0.0 && ry1 >= 0.0) ? 0.0 : fmin(ay * ay, by * by), qy1 = fmax(ay * ay, by * by);
+  const double L0 = sqrt(qx0 + qy0 + rz * rz) * (1.0 - 1e-15), L1 = sqrt(qx1 + qy1 + rz * rz) * (1.0 + 1e-15);
+  if (!(L0 > 0.0) || !(L1 <= 1.7976931348623157e308)) return 0u;
+  // the hit distances [t1, t2]: c = N / L, N linear over the box
+  const double Cx = B.c[0] * B.len, Cy = B.c[1] * B.len, Cz = B.c[2] * B.len;
+  const double n00 = ax * Cx + ay * Cy + rz * Cz, n10 = bx * Cx + ay * Cy + rz * Cz, n01 = ax * Cx + by * Cy + rz * Cz, n11 = bx * Cx + by * Cy + rz * Cz;
+  const double N_lo = fmin(fmin(n00, n10), fmin(n01, n11)), N_hi = fmax(fmax(n00, n10), fmax(n01, n11));
+  if (!(N_lo > 0.0)) return 0u;
+  const double c_hi = fmin(N_hi / L0, B.len), c_lo = fmax(N_lo / L1, B.tangent);
+  if (!(c_hi * c_hi >= B.k) || !(c_hi >= c_lo)) return 0u;
   const double t1 = (c_hi - sqrt(fmax(c_hi * c_hi - B.k, 0.0))) * (1.0 - 1e-6), t2 = (c_lo - sqrt(fmax(c_lo * c_lo - B.k, 0.0))) * (1.0 + 1e-6);
   if (!(t2 >= t1) || !(t1 >= 0.0) || !(t2 <= 1.7976931348623157e308)) return 0u;
-  const double m = 0.5 * (t1 + t2), rho = sqrt(0.25 * (t2 - t1) * (t2 - t1) + 2.0 * t2 * m * (1.0 - cos_a)) * (1.0 + 1e-6) + 1e-9 * t2;
-  const double W[3] = {(P.cam[0] + m * ax[0]) - B.o[0], (P.cam[1] + m * ax[1]) - B.o[1], (P.cam[2] + m * ax[2]) - B.o[2]};
-  if (!(B.r > 0.0) || !(rho <= B.r)) return 0u;
+  // h - o per axis (the reciprocal lengths' two roundings - 2e-16 of a component - vanish in the 1e-9 t2 added to each end)
+  const double i0 = 1.0 / L0, i1 = 1.0 / L1;
+  double wz0, wz1;
+  rt_axis_range(rz, rz, i0, i1, t1, t2, P.cam[2], B.o[2], &wz0, &wz1);
   // v
-  const double s_lo = (-W[2] - rho) / B.r, s_hi = (-W[2] + rho) / B.r;
-  if (!(s_lo > -1.0) || !(s_hi < 1.0)) return 0u;
-  const double v_lo = fd_asin(s_lo) / (M_PI / 2.0) / 2.0 + 0.5, v_hi = fd_asin(s_hi) / (M_PI / 2.0) / 2.0 + 0.5;
-  // u
-  const double d0 = sqrt(W[0] * W[0] + W[1] * W[1]);
-  if (!(d0 > rho * (1.0 + 1e-6))) return 0u;
-  const double phi = fd_atan2(-W[1], -W[0]), dphi = fd_asin(fmin(1.0, rho / d0)) * (1.0 + 1e-9) + 1e-12;
-  if (!(phi - dphi > -3.14159) || !(phi + dphi < 3.14159)) return 0u;
-  const double u_lo = (phi - dphi) / M_PI / 2.0 + 0.5, u_hi = (phi + dphi) / M_PI / 2.0 + 0.5;
-  const double xu0 = u_lo * B.fu, xu1 = u_hi * B.fu, xv0 = v_lo * B.fv, xv1 = v_hi * B.fv;
-  const double mu = 3.814697265625e-06 + 1e-10 * B.fu, mv = 3.814697265625e-06 + 1e-10 * B.fv;
-  const double ku = floor(xu0), kv = floor(xv0);
-  if (!(ku >= 0.0) || !(kv >= 0.0) || !(xu0 - ku >= mu) || !((ku + 1.0) - xu1 >= mu) || !(xv0 - kv >= mv) || !((kv + 1.0) - xv1 >= mv)) return 0u;
-  return 1u | ((((uint32_t)ku ^ (uint32_t)kv) & 1u) << 1);
+  uint32_t sv = 0u;
+  const double s_lo = -wz1 / B.r, s_hi = -wz0 / B.r;
+  if (s_lo > -1.0 && s_hi < 1.0) sv = rt_axis_cell(fd_asin(s_lo) / (M_PI / 2.0) / 2.0 + 0.5, fd_asin(s_hi) / (M_PI / 2.0) / 2.0 + 0.5, B.fv);
+  if (!(sv & 1u) && !(P.flags & RT_TABLE_AXES)) return 0u;         // no whole cell without v, and nobody asks for u alone
+  // u: the rectangle [px0, px1] x [py0, py1] of (-(h - o).x, -(h - o).y)
+  uint32_t su = 0u;
+  double wx0, wx1, wy0, wy1;
+  rt_axis_range(rx0, rx1, i0, i1, t1, t2, P.cam[0], B.o[0], &wx0, &wx1);
+  rt_axis_range(ry0, ry1, i0, i1, t1, t2, P.cam[1], B.o[1], &wy0, &wy1);
+  const double px0 = -wx1, px1 = -wx0, py0 = -wy1, py1 = -wy0;
+  if ((py0 > 0.0 || py1 < 0.0 || px0 > 0.0) && px1 >= px0 && py1 >= py0) {        // neither the axis nor the branch cut
+    const double xa = py1 < 0.0 ? px1 : px0, ya = xa > 0.0 ? py1 : py0;          // the corner of the largest angle
+    const double xb = py0 > 0.0 ? px1 : px0, yb = xb > 0.0 ? py0 : py1;          // ... of the smallest
+    const double phi_hi = fd_atan2(ya, xa) + 1e-12, phi_lo = fd_atan2(yb, xb) - 1e-12;
+    if (phi_lo > -3.14159 && phi_hi < 3.14159) su = rt_axis_cell(phi_lo / M_PI / 2.0 + 0.5, phi_hi / M_PI / 2.0 + 0.5, B.fu);
+  }
+  uint32_t st = ((su & 1u) ? RT_COL_U | ((su & 2u) ? RT_COL_U_ODD : 0u) : 0u) | ((sv & 1u) ? RT_COL_V | ((sv & 2u) ? RT_COL_V_ODD : 0u) : 0u);
+  if ((su & 1u) && (sv & 1u)) st |= RT_COL_CELL | (((su ^ sv) & 2u) ? RT_COL_ODD : 0u);
+  return st;
 }
 
 // word 3's upper bits for a block whose word 3 names ONE candidate, ball ci: the four columns' statements
 RT_HD inline uint32_t rt_cell_bits(uint32_t col, uint32_t st) { return ((st & 1u) << (RT_CELL_SHIFT + col)) | (((st >> 1) & 1u) << (RT_CELL_SHIFT + 4u + col)); }
+// ... from the four columns' RT_COL_* sets, six bits per column (st4 = OR of rt_column_cell(col) << 6 col).  Bits 18..25 are the whole-cell
+// statements, and what bits 18..21 say never depends on the option: bit 18 + c set means "column c lies inside ONE checker cell", and a
+// reader that knows nothing of the per-axis statements (every trace kernel today) reads bit 22 + c only beside it.  RT_TABLE_AXES
+// adds, for the columns WITHOUT a whole-cell statement, ONE axis' statement (a column that can state both axes has its whole cell
+// stated); the entry names one axis for all its columns - the one more of them can state (a tie: u) -
+//   bit 26 + c   column c lies inside one unit cell of that axis: a wave would have to work out the OTHER coordinate only;
+//   bit 22 + c   (the parity slot, unused by a column without bit 18 + c) that cell's index & 1;
+//   bit 30       the axis: 0 - u is stated (main.js:127), 1 - v (main.js:128).
+// Without RT_TABLE_AXES bits 26..31 are zero, and bits 22..25 are only set beside their column's bit 18 + c.
+RT_HD inline uint32_t rt_cells_word(const rt_table_params &P, uint32_t st4) {
+  uint32_t bits = 0u, nu = 0u, nv = 0u;
+  for (uint32_t col = 0; col < 4u; col++) {
+    const uint32_t st = (st4 >> (6u * col)) & 63u;
+    bits |= rt_cell_bits(col, st);
+    if (!(st & RT_COL_CELL)) { nu += (st & RT_COL_U) ? 1u : 0u; nv += (st & RT_COL_V) ? 1u : 0u; }
+  }
+  if (!(P.flags & RT_TABLE_AXES) || nu + nv == 0u) return bits;
+  const bool v = nv > nu;
+  for (uint32_t col = 0; col < 4u; col++) {
+    const uint32_t st = (st4 >> (6u * col)) & 63u;
+    if ((st & RT_COL_CELL) || !(st & (v ? RT_COL_V : RT_COL_U))) continue;
+    bits |= (1u << (RT_CELL_SHIFT + 8u + col)) | (((st & (v ? RT_COL_V_ODD : RT_COL_U_ODD)) ? 1u : 0u) << (RT_CELL_SHIFT + 4u + col));
+  }
+  return bits | (v ? 1u << (RT_CELL_SHIFT + 12u) : 0u);
+}
 
 // touched / candidates / shadow masks of block (x, y), one block after the other (the host); *touched = 1 also when nothing can be said
 RT_HD inline void rt_block_statement(const rt_table_params &P, const rt_ball *balls, uint32_t x, uint32_t y, uint32_t *touched, uint32_t *cands_out, uint32_t *smask_out,
@@ -337,7 +410,11 @@ RT_HD inline void rt_block_statement(const rt_table_params &P, const rt_ball *ba
   *cands_out = rt_cand_word(P, balls, cand, n_cand);
   if ((P.flags & RT_TABLE_CELLS) && (*cands_out >> 16) == 1u)
     for (uint32_t ci = 0; ci < P.n_balls; ci++)
-      if (cand[ci >> 6] >> (ci & 63u) & 1ull) for (uint32_t col = 0; col < 4u; col++) *cands_out |= rt_cell_bits(col, rt_column_cell(P, balls[ci], x, y, col));
+      if (cand[ci >> 6] >> (ci & 63u) & 1ull) {
+        uint32_t st4 = 0u;
+        for (uint32_t col = 0; col < 4u; col++) st4 |= rt_column_cell(P, balls[ci], x, y, col) << (6u * col);
+        *cands_out |= rt_cells_word(P, st4);
+      }
   if (P.flags & RT_TABLE_BOUNCE)
     for (uint32_t ci = 0; ci < P.n_balls; ci++) if (cand[ci >> 6] >> (ci & 63u) & 1ull) *bounce_extra += rt_bounce_cost(P, K, balls, ci);
   if (!(P.flags & RT_TABLE_MASKS)) return;

@@ -58,7 +58,8 @@ table_choice choose_table(const rt_scene_dev *s, uint32_t flags, uint32_t uses_b
   c.mark_sky = !count && !no_sky_tiles && sky_fast(s);
   c.shadow_masks = !count && !no_shadow_masks && masks_pay(s, uses_before) && part != 2u && (s->enclosing == ~0u || s->enclosing_flat);
   c.name_candidates = !count && !no_shadow_masks && part != 2u;
-  c.checker_cells = c.name_candidates;                // (costs the build nothing unless the scene has a checker sphere: rt_tables.cpp)
+  // (whole cells only: the trace kernels do not read the per-axis statements - docs/EVIDENCE.md, "Checker cells, per axis")
+  c.checker_cells = c.name_candidates ? 1 : 0;        // (costs the build nothing unless the scene has a checker sphere: rt_tables.cpp)
   return c;
 }
 
@@ -853,7 +854,7 @@ extern "C" int rt_test_launch_table(rt_scene_dev *s, uint32_t w, uint32_t h, con
   const uint32_t ss = s->hd.supersample;
   if (ss > 2u) return fail(RT_ERR_INVALID, "supersample 3 and 4 launch on the sample grid");
   const frame_kind kind = {w, h, ss, *tiles, (ranked & 8) ? 1u : ((ranked & 16) ? 2u : 0u)};
-  const table_choice c = {(ranked & 1) != 0, (ranked & 2) != 0, (ranked & 4) != 0, (ranked & 4) != 0, (ranked & 32) != 0};
+  const table_choice c = {(ranked & 1) != 0, (ranked & 2) != 0, (ranked & 4) != 0, (ranked & 4) != 0, (ranked & 32) ? ((ranked & 64) ? 2 : 1) : 0};
   std::lock_guard<std::mutex> lk(s->launch_mu);
   HIP_TRY(s->sync.before_launch(stream, s->cam_gen));
   const int oi = dispatch_order(s, kind, c, stream);

@@ -219,7 +219,7 @@ bool table_is_ranked(int ranked, uint64_t n_blocks) { return ranked && (n_blocks
 
 int make_table_params(const rt_scene_header *hd, const rt_sphere *ob, const std::vector<rt_geom> &cull, const std::vector<uint32_t> &weight,
                       uint32_t w, uint32_t h, uint32_t ss, const rt_tiles *tiles, uint32_t tiles_x, uint32_t rb_per_tile, double proj_w, double proj_h, double proj_d,
-                      int ranked, bool mark_sky, uint32_t sky_sphere, bool shadow_masks, bool name_candidates, bool checker_cells, const double lights[][3],
+                      int ranked, bool mark_sky, uint32_t sky_sphere, bool shadow_masks, bool name_candidates, int checker_cells, const double lights[][3],
                       rt_table_params *P, std::vector<rt_ball> *balls, std::vector<rt_cost_rect> *rects) {
   const uint32_t ny = tiles->n_tiles * rb_per_tile;
   const uint64_t n64 = (uint64_t)tiles_x * ny;
@@ -252,7 +252,8 @@ int make_table_params(const rt_scene_header *hd, const rt_sphere *ob, const std:
                         std::isfinite(proj_d) && proj_d > 0.0;
   P->flags = (mark_sky ? RT_TABLE_SKY : 0u) | (want_masks ? RT_TABLE_MASKS : 0u) | (want_cands ? RT_TABLE_CANDS : 0u) | (n_loop > 16u ? RT_TABLE_WIDE : 0u) |
              (table_is_ranked(ranked, n64) ? RT_TABLE_RANK : 0u) | ((geometry && (mark_sky || want_masks || want_cands || want_bounce)) ? RT_TABLE_GEOMETRY : 0u) |
-             ((geometry && want_bounce) ? RT_TABLE_BOUNCE : 0u) | ((geometry && want_cells) ? RT_TABLE_CELLS : 0u);
+             ((geometry && want_bounce) ? RT_TABLE_BOUNCE : 0u) | ((geometry && want_cells) ? RT_TABLE_CELLS : 0u) |
+             ((geometry && want_cells && checker_cells >= 2) ? RT_TABLE_AXES : 0u);
   P->cost_bins = 1u;
   P->n_lights = want_masks ? hd->n_lights : 0u;
   for (uint32_t k = 0; k < P->n_lights; k++) for (int c = 0; c < 3; c++) P->lights[k][c] = lights[k][c];
@@ -325,7 +326,7 @@ int make_table_params(const rt_scene_header *hd, const rt_sphere *ob, const std:
 std::vector<uint32_t> build_launch_table(const rt_scene_header *hd, const rt_sphere *ob, const std::vector<rt_geom> &cull, const std::vector<uint32_t> &weight,
                                          uint32_t w, uint32_t h, uint32_t ss,
                                          const rt_tiles *tiles, uint32_t tiles_x, uint32_t rb_per_tile, double proj_w, double proj_h, double proj_d, int ranked,
-                                         bool mark_sky, uint32_t sky_sphere, bool shadow_masks, bool name_candidates, bool checker_cells, const double lights[][3], uint32_t *n_entries, uint32_t sky_part) {
+                                         bool mark_sky, uint32_t sky_sphere, bool shadow_masks, bool name_candidates, int checker_cells, const double lights[][3], uint32_t *n_entries, uint32_t sky_part) {
   if (n_entries) *n_entries = 0;
   rt_table_params P;
   std::vector<rt_ball> balls;

@@ -110,9 +110,9 @@ __global__ void __launch_bounds__(WG_ROWS) rt_table_rows(const rt_table_dev T, u
           uint32_t ci = 0u, bits = 0u;
           for (uint32_t wd = 0; wd < 4u; wd++) if (cand[wd]) { ci = wd * 64u + (uint32_t)__builtin_ctzll(cand[wd]); break; }
           if (balls[ci].checker) {                      // (uniform as well: the statement is only worked out for a checker sphere)
-            for (uint32_t col = sub; col < 4u; col += SUB) bits |= rt_cell_bits(col, rt_column_cell(P, balls[ci], x, y, col));
+            for (uint32_t col = sub; col < 4u; col += SUB) bits |= rt_column_cell(P, balls[ci], x, y, col) << (6u * col);
             bits = group_or<SUB>(bits);
-            cands |= (sub == 0u) ? bits : 0u;
+            cands |= (sub == 0u) ? rt_cells_word(P, bits) : 0u;
           }
         }
         if (P.flags & RT_TABLE_BOUNCE) {                // (ranking only) what the block's mirrors show of the scene's dearest spheres
