@@ -23,6 +23,9 @@
 //                  columns lie, with every sample, inside one checker cell, and that cell's parity (rt_column_cell); bits 18..25 of
 //                  the candidates' word; with RT_TABLE_AXES also which of the other columns lie inside one cell of ONE of the checker's
 //                  two axes (rt_cells_word); bits 26..30;
+//   * first-bounce set (RT_TABLE_FIRST_BOUNCE) - for a block of one or two candidates of which at least one is a mirror: the loop-order
+//                  spheres a ray REFLECTED at a primary hit of the block can meet at all (rt_first_bounce_set); bit 31 and bits 18..30
+//                  of the candidates' word, never beside checker cells;
 //   * cost       - 1 + the weights of the spheres whose screen rectangle (the primary-ray cull's) touches the block, + what its
 //                  mirrors show of the scene's dearest spheres (rt_bounce_cost): what ranks the blocks dearest first.
 #ifndef RT_BLOCK_H
@@ -50,9 +53,17 @@
 #define RT_TABLE_BOUNCE 256u     /* ranked launch of a scene with a sphere that both reflects and refracts: a block's cost also counts such spheres seen in its mirrors */
 #define RT_TABLE_CELLS 512u      /* checker cells: word 3 also says which 8-pixel columns of a one-candidate block lie inside ONE checker cell (rt_column_cell) */
 #define RT_TABLE_AXES 1024u      /* checker cells, per axis (with RT_TABLE_CELLS): a column that is NOT inside one cell may still lie inside one cell of ONE axis (rt_cells_word) */
+#define RT_TABLE_FIRST_BOUNCE 2048u /* first-bounce sets: word 3 of a block whose candidates include a mirror also names the spheres its reflected rays can meet (rt_first_bounce_set) */
 #define RT_SKY_RUN_MAX 32u       /* consecutive sky blocks of a row block that share ONE entry */
 #define RT_CAND_MASK 0x3ffffu     /* word 3, bits 0..17: the candidates; what every reader of them keeps */
 #define RT_CELL_SHIFT 18u        /* ... bits 18..21: column c (bit 18 + c) lies inside one checker cell; bits 22..25: that cell's parity; RT_TABLE_AXES: and bits 26..30, rt_cells_word */
+// Word 3's bits 18..31 hold EITHER checker cells (bit 31 clear) OR a first-bounce set (bit 31 set; bit 18 + j: loop sphere j, at most 13 of them),
+// never both: a set is only stated for an entry without a cell bit, and every candidate of a stating entry is a sphere of a scene without
+// refraction - and without an enclosing sphere that reflects: that sphere is outside the loops, the candidates and this statement, and a lane
+// of a stating block that misses every candidate meets it - at least one of them a mirror at a depth of 2 or more.  So an entry with bit 31 set is either not tried by the trace kernels' uniform-material path
+// (two candidates) or - one candidate, which is then the mirror - turned away by that path's material test before it reads a cell bit.
+#define RT_FB_STATED 0x80000000u  /* word 3, bit 31: bits 18..30 are the block's first-bounce set */
+#define RT_FB_MAX_LOOP 13u        /* ... which names loop spheres 0..12: scenes of more state nothing */
 #define RT_COST_MAX 1023u        /* costs are clamped here (the ranking only has to order the blocks roughly) */
 
 // a sphere as the cone test sees it (one per sphere but the enclosing one, scene order)
@@ -68,7 +79,7 @@ struct rt_ball {
   uint32_t always[2];
   uint32_t loop;                 // index in the product kernel's loop order (enclosing sphere last)
   uint32_t everywhere;           // the camera is inside / on / too near: no statement about any block
-  uint32_t bounce;               // cost ranking only (RT_TABLE_BOUNCE): bit 0 the sphere reflects, bit 1 it refracts (depth >= 3)
+  uint32_t bounce;               // cost ranking (RT_TABLE_BOUNCE, depth >= 3) and first-bounce sets (RT_TABLE_FIRST_BOUNCE, depth >= 2): bit 0 the sphere reflects, bit 1 it refracts
   uint32_t heavy;                // ... and its weight if it does BOTH (every hit a two-child node of the ray tree, main.js:268-278), else 0
   // checker cells (RT_TABLE_CELLS): the sphere's sampler is the checker with both frequencies in (0, 2^17] (the product kernel's range,
   // zero - stripes - left out); its frequencies and its TRUE radius (the kernel's normal is (h - o) / r)
@@ -216,10 +227,9 @@ RT_HD inline uint32_t rt_cand_word(const rt_table_params &P, const rt_ball *ball
   return (n_cand << 16) | (i1 << 8) | i0;
 }
 
-// candidate sphere ci: which spheres can stand between the block's primary hits on it and light k - OR-ed into mk[k].  false: no
-// statement can be made (the block's word is then 0xffffffff whatever the other candidates say)
-RT_HD inline bool rt_cand_masks(const rt_table_params &P, const rt_cone &K, const rt_ball *balls, uint32_t ci, uint32_t mk[2]) {
-  const rt_ball &B = balls[ci];
+// where the block's primary hits on candidate sphere B lie: inside the ball (Q, rho).  false: no statement can be made
+struct rt_patch { double Q[3], rho; };
+RT_HD inline bool rt_cand_patch(const rt_table_params &P, const rt_cone &K, const rt_ball &B, rt_patch *pt) {
   const double *ax = K.ax;
   const double cos_a = K.cos_a, sin_a = K.sin_a;
   // the primary hits on sphere ci: distances [t1, t2] along rays within alpha of the axis
@@ -231,8 +241,16 @@ RT_HD inline bool rt_cand_masks(const rt_table_params &P, const rt_cone &K, cons
   if (!(B.k > 0.0) || !(c_hi * c_hi >= B.k) || !(c_hi >= c_lo) || !(B.len - B.R >= 2.0 * fabs(P.epsilon))) return false;
   const double t1 = (c_hi - sqrt(fmax(c_hi * c_hi - B.k, 0.0))) * (1.0 - 1e-6), t2 = (c_lo - sqrt(fmax(c_lo * c_lo - B.k, 0.0))) * (1.0 + 1e-6);
   if (!(t2 >= t1) || !(t1 >= 0.0) || !(t2 <= 1.7976931348623157e308)) return false;
-  const double m = 0.5 * (t1 + t2), rho = sqrt(0.25 * (t2 - t1) * (t2 - t1) + 2.0 * t2 * m * (1.0 - cos_a)) * (1.0 + 1e-6) + 1e-9 * t2;
-  const double Q[3] = {P.cam[0] + m * ax[0], P.cam[1] + m * ax[1], P.cam[2] + m * ax[2]};
+  const double m = 0.5 * (t1 + t2);
+  pt->rho = sqrt(0.25 * (t2 - t1) * (t2 - t1) + 2.0 * t2 * m * (1.0 - cos_a)) * (1.0 + 1e-6) + 1e-9 * t2;
+  pt->Q[0] = P.cam[0] + m * ax[0]; pt->Q[1] = P.cam[1] + m * ax[1]; pt->Q[2] = P.cam[2] + m * ax[2];
+  return true;
+}
+
+// candidate sphere ci, its primary hits inside the patch `pt`: which spheres can stand between them and light k - OR-ed into mk[k]
+RT_HD inline void rt_cand_masks(const rt_table_params &P, const rt_patch &pt, const rt_ball *balls, uint32_t ci, uint32_t mk[2]) {
+  const double *Q = pt.Q;
+  const double rho = pt.rho;
   const bool wide = (P.flags & RT_TABLE_WIDE) != 0u;
   for (uint32_t k = 0; k < P.n_lights; k++) {
     if (wide && mk[k] == 0xffffu) continue;        // many spheres: a light's set is "empty or not", and it already is not
@@ -254,7 +272,74 @@ RT_HD inline bool rt_cand_masks(const rt_table_params &P, const rt_cone &K, cons
       if (inc) { if (wide) { mk[k] = 0xffffu; break; } mk[k] |= 1u << O.loop; }
     }
   }
+}
+
+// ... patch and masks in one step, for a caller that wants nothing else of the patch.  false: no statement can be made (the block's word is
+// then 0xffffffff whatever the other candidates say)
+RT_HD inline bool rt_cand_patch_masks(const rt_table_params &P, const rt_cone &K, const rt_ball *balls, uint32_t ci, uint32_t mk[2]) {
+  rt_patch pt;
+  if (!rt_cand_patch(P, K, balls[ci], &pt)) return false;
+  rt_cand_masks(P, pt, balls, ci, mk);
   return true;
+}
+
+// First-bounce set (RT_TABLE_FIRST_BOUNCE).  Candidate sphere ci is a mirror, its primary hits lie inside the patch `pt` = (Q, rho): which
+// loop spheres can a ray REFLECTED at such a hit meet at any t >= 0?  Returns their set (bit j: loop sphere j; ci itself is always in), or
+// 0: no statement.  No estimate anywhere: every step is a bound, with the margins of this file's other tests.
+//   normal     a hit h has h - o = qo + e, qo = Q - o, |e| <= rho: the normal lies within dn of n0 = qo / |qo|, sin dn = rho / |qo|
+//              (rho < 0.7 |qo| is required: dn < 45 degrees);
+//   direction  the primary direction lies within alpha of the cone's axis ax.  Reflection at a FIXED normal keeps the angle between two
+//              directions; reflecting a FIXED direction at two normals dn apart gives results 2 dn apart (the two reflections differ by
+//              a rotation of twice the normals' angle).  So every reflected direction lies within sigma = alpha + 2 dn of
+//              r0 = ax - 2 (ax . n0) n0; sines and cosines by the addition formulas; sigma >= pi / 2: no statement;
+//   sphere j   a reflected ray starts within rho of Q, so it meets sphere j at t >= 0 only if the ray from Q with the same direction meets
+//              the ball (C_j, R_j (1 + 1e-7) + rho) at t >= 0: Q inside that ball, or angle(r0, C_j - Q) <= sigma + asin((R_j + rho) /
+//              |C_j - Q|) - a sum below pi, tested as a cosine scaled by |C_j - Q|.
+RT_HD inline uint32_t rt_first_bounce_set(const rt_table_params &P, const rt_cone &K, const rt_patch &pt, const rt_ball *balls, uint32_t ci) {
+  const rt_ball &B = balls[ci];
+  const double qo[3] = {pt.Q[0] - B.o[0], pt.Q[1] - B.o[1], pt.Q[2] - B.o[2]};
+  const double lq = sqrt(qo[0] * qo[0] + qo[1] * qo[1] + qo[2] * qo[2]);
+  if (!(pt.rho < 0.7 * lq) || !(lq <= 1.7976931348623157e308)) return 0u;
+  const double s_dn = pt.rho / lq * (1.0 + 1e-7), c_dn = sqrt(1.0 - s_dn * s_dn);
+  const double s_2dn = 2.0 * s_dn * c_dn, c_2dn = 1.0 - 2.0 * s_dn * s_dn;
+  const double c_sig = (K.cos_a * c_2dn - K.sin_a * s_2dn) - 1e-7;                 // cos(alpha + 2 dn), a slightly wider cone
+  if (!(c_sig > 0.0)) return 0u;
+  const double s_sig = sqrt(1.0 - c_sig * c_sig);
+  const double il = 1.0 / lq, n0[3] = {qo[0] * il, qo[1] * il, qo[2] * il};
+  const double an = K.ax[0] * n0[0] + K.ax[1] * n0[1] + K.ax[2] * n0[2];
+  const double r0[3] = {K.ax[0] - 2.0 * an * n0[0], K.ax[1] - 2.0 * an * n0[1], K.ax[2] - 2.0 * an * n0[2]};
+  uint32_t set = 1u << B.loop;
+  for (uint32_t j = 0; j < P.n_balls; j++) {
+    if (j == ci) continue;
+    const rt_ball &O = balls[j];
+    const double W[3] = {O.o[0] - pt.Q[0], O.o[1] - pt.Q[1], O.o[2] - pt.Q[2]};
+    const double wl2 = W[0] * W[0] + W[1] * W[1] + W[2] * W[2], Rb = O.R + pt.rho;
+    bool in = true;                                // Q inside the widened ball, or nothing finite can be said
+    if (wl2 > Rb * Rb * (1.0 + 1e-6) && wl2 <= 1.7976931348623157e308) {
+      // cos(sigma + beta) |W| with sin beta = Rb / |W|: cos beta |W| = sqrt(|W|^2 - Rb^2), sin beta |W| = Rb - one square root per sphere, no
+      // division; the margin 1e-7 |W| taken from the 1-norm, which is no smaller
+      const double w1 = fabs(W[0]) + fabs(W[1]) + fabs(W[2]);
+      in = !(r0[0] * W[0] + r0[1] * W[1] + r0[2] * W[2] < (c_sig * sqrt(wl2 - Rb * Rb) - s_sig * Rb) - 1e-7 * w1);
+    }
+    if (in) set |= 1u << O.loop;
+  }
+  return set;
+}
+// ... of a block: OR `*set` over its candidates, one call each.  false: the block states no set (a candidate refracts, or a mirror among
+// them has no patch or no bound); a candidate that does not reflect adds nothing (its hits spawn no ray)
+RT_HD inline bool rt_cand_first_bounce(const rt_table_params &P, const rt_cone &K, const rt_ball *balls, uint32_t ci, bool patch_ok, const rt_patch &pt, uint32_t *set) {
+  const rt_ball &B = balls[ci];
+  if (B.bounce & 2u) return false;
+  if (!(B.bounce & 1u)) return true;
+  const uint32_t s = patch_ok ? rt_first_bounce_set(P, K, pt, balls, ci) : 0u;
+  *set |= s;
+  return s != 0u;
+}
+// word 3's upper bits from the block's set (0: none of its candidates is a mirror), whether every candidate could be stated, and the
+// word so far (candidates and checker cells)
+RT_HD inline uint32_t rt_first_bounce_word(const rt_table_params &P, uint32_t cands, bool ok, uint32_t set) {
+  if (!(P.flags & RT_TABLE_FIRST_BOUNCE) || !ok || !set || !(cands & RT_CAND_MASK) || (cands >> RT_CELL_SHIFT)) return 0u;
+  return RT_FB_STATED | (set << RT_CELL_SHIFT);
 }
 
 // Checker cells (RT_TABLE_CELLS).  A block with ONE candidate whose sampler is the sphere checker (main.js:126-133): do all the primary
@@ -417,14 +502,24 @@ RT_HD inline void rt_block_statement(const rt_table_params &P, const rt_ball *ba
       }
   if (P.flags & RT_TABLE_BOUNCE)
     for (uint32_t ci = 0; ci < P.n_balls; ci++) if (cand[ci >> 6] >> (ci & 63u) & 1ull) *bounce_extra += rt_bounce_cost(P, K, balls, ci);
-  if (!(P.flags & RT_TABLE_MASKS)) return;
-  uint32_t mk[2] = {0u, 0u};
+  // shadow masks and first-bounce set: each candidate's patch worked out once for both (as the device build does)
+  const bool want_masks = (P.flags & RT_TABLE_MASKS) != 0u;
+  const bool want_fb = (P.flags & RT_TABLE_FIRST_BOUNCE) && (*cands_out & RT_CAND_MASK) && !(*cands_out >> RT_CELL_SHIFT);
+  if (!want_masks && !want_fb) return;
+  uint32_t mk[2] = {0u, 0u}, fb_set = 0u;
+  bool masks_ok = want_masks, fb_ok = true;
   for (uint32_t ci = 0; ci < P.n_balls; ci++) {
     if (!(cand[ci >> 6] >> (ci & 63u) & 1ull)) continue;
-    if (!rt_cand_masks(P, K, balls, ci, mk)) return;
-    if (mk[0] == 0xffffu && mk[1] == 0xffffu) return;       // many spheres, both sets not empty: the word is 0xffffffff whatever follows
+    rt_patch pt;
+    const bool patch_ok = rt_cand_patch(P, K, balls[ci], &pt);
+    if (want_fb) fb_ok = rt_cand_first_bounce(P, K, balls, ci, patch_ok, pt, &fb_set) && fb_ok;
+    if (masks_ok) {
+      if (!patch_ok) masks_ok = false; else rt_cand_masks(P, pt, balls, ci, mk);
+      if (mk[0] == 0xffffu && mk[1] == 0xffffu) masks_ok = false;       // many spheres, both sets not empty: the word is 0xffffffff whatever follows
+    }
   }
-  *smask_out = mk[0] | (mk[1] << 16);
+  if (want_fb) *cands_out |= rt_first_bounce_word(P, *cands_out, fb_ok, fb_set);
+  if (masks_ok) *smask_out = mk[0] | (mk[1] << 16);
 }
 
 // the two words of an entry that describe WHERE its block is: word 0 = tile_x | rows_valid << 11 | first frame row << 15,

@@ -188,8 +188,10 @@ struct rt_launch {
   uint32_t probe_x, probe_y;         // the sample, in sample-grid coordinates
   // ... and the uniform-material path of the one-wave product kernels (rt_kernel.hip: trace_pixel, UNI)
   uint32_t no_uniform;               // RT_NO_UNIFORM_BLOCKS: every wave takes the general path
-  unsigned long long *uniform_waves; // counts the waves that took the path (rt_test_uniform_waves), or NULL; [1]: those whose checker cell came from the launch table (rt_test_cell_waves)
+  unsigned long long *uniform_waves; // counts the waves that took the path (rt_test_uniform_waves), or NULL; [1]: those whose checker cell came from the launch table (rt_test_cell_waves);
+                                     // [2]: the waves of the general path that scanned a first-bounce set (rt_test_first_bounce_waves)
   uint32_t no_cells;                 // RT_NO_CHECKER_CELLS: the kernel ignores the launch table's checker cells
+  uint32_t no_first_bounce;          // RT_NO_FIRST_BOUNCE: the kernel ignores the launch table's first-bounce sets (every bounced ray scans every sphere)
 #endif
 };
 

@@ -48,7 +48,7 @@ __device__ __forceinline__ rt_pixel rt_pixel_of(const rt_launch &L, uint32_t tid
 #else
 // Product kernel: a FLAT grid (workgroups, 1, frames of the batch) and a launch table with one 16-byte entry per workgroup:
 //   word 0 = tile_x | rows_valid << 11 | first frame row << 15      word 1 = first row in this call's output band | (run - 1) << 24 | sky << 31
-//   word 2 = shadow masks                                            word 3 = primary candidates | checker cells << 18
+//   word 2 = shadow masks                                            word 3 = primary candidates | checker cells << 18, or (bit 31) | first-bounce set << 18
 // (built on the GPU per camera, frame size and tile set: rt_tables_gpu.hip, rt_block.h).  One scalar load replaces the tile /
 // row-block arithmetic of the plain grid - no division, no tile parameters in registers - and decides the ORDER in which the
 // hardware hands the tiles out: dearest first, so that a launch ends on cheap sky tiles instead of on the floor.  trow is the row
@@ -71,6 +71,8 @@ __device__ __forceinline__ rt_pixel rt_pixel_of(const rt_launch &L, uint32_t tid
   P.sky = (e1 >> 31) != 0u;                            // workgroup-uniform: no sphere can show in these blocks (rt_block.h) ...
   P.run = ((e1 >> 24) & 127u) + 1u;                    // ... a run of this many 32-pixel blocks, starting at tile_x
   P.cand = e4.w & RT_CAND_MASK;                        // the (at most two) loop spheres the block's primary rays can meet (count << 16 | second << 8 | first), or 0: cull
+  // (an entry with bit 31 holds a first-bounce set in these bits instead: rt_entry_first_bounce below.  Its one candidate is then a mirror at a depth that
+  // lets it reflect, and the uniform-material path - the only reader of the cells - turns the wave away by its material before it reads one: rt_block.h)
   P.cell = e4.w >> RT_CELL_SHIFT;                      // checker cells of a one-candidate block (rt_block.h: rt_column_cell): bit c - column c lies inside ONE cell, bit 4 + c - its parity
   P.rows_valid = rows_valid;                           // wave-uniform: rows of the block inside its tile and the frame
   P.valid = (P.px < L.w) && (P.trow < rows_valid);
@@ -86,6 +88,13 @@ template <bool W1>
 __device__ __forceinline__ uint32_t rt_entry_shadow_masks(const rt_launch &L) {
   const uint32_t slot = rt_entry_slot<W1>(L);
   return *(const uint32_t __attribute__((address_space(4))) *)((const char __attribute__((address_space(4))) *)L.order + ((size_t)slot << 4) + 8u);
+}
+// Word 3 of this workgroup's launch-table entry, for its first-bounce set (rt_block.h: rt_first_bounce_set): bit 31 - bits 18..30 name the loop
+// spheres a ray reflected at a primary hit of the block can meet.  Read again where it is used - the node after the primary - like word 2.
+template <bool W1>
+__device__ __forceinline__ uint32_t rt_entry_first_bounce(const rt_launch &L) {
+  const uint32_t slot = rt_entry_slot<W1>(L);
+  return *(const uint32_t __attribute__((address_space(4))) *)((const char __attribute__((address_space(4))) *)L.order + ((size_t)slot << 4) + 12u);
 }
 #endif
 

@@ -330,6 +330,9 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
         }
   }
   bool searched = true;                // the primary ray's candidates were found above (culled; camera-anchored in the product kernel)
+  // (few-sphere reflection-only product kernels) wave-uniform like `searched`: the node being evaluated is the one AFTER the primary - in these kernels
+  // every node has at most one child, so every lane still in the loop is at the same level in every turn of it
+  [[maybe_unused]] bool first_bounce = false;
 #if !RT_STRICT
   // A wave none of whose primary rays met a sphere of the loops, in a scene whose enclosing sphere is flat AND constant in colour
   // (the reference's skybox with a plain colour): every pixel of the wave is that sphere's ambient term, max(color*albedo[0],
@@ -391,6 +394,33 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
           }
         }
 #endif
+#if !RT_STRICT
+        // Few spheres, no refraction: at the node after the primary the launch table may name the spheres a ray reflected at a primary hit of this
+        // block can meet at all (word 3 of the entry: rt_block.h, rt_first_bounce_set).  The wave walks that set on the scalar unit, like the primary
+        // cull's survivors, in index order - the strict-< tie-break of the full scan is kept - and tests nothing else.
+        if constexpr (!GRID && !REFRACT && !COUNT && !ITEM) {
+          if (first_bounce) {
+            uint32_t fb = rt_entry_first_bounce<W1>(L);
+#ifdef RT_TESTING
+            if (L.no_first_bounce) fb = 0u;               // test build (RT_NO_FIRST_BOUNCE): every wave on the full scan
+#endif
+            if (fb >> 31) {
+              ht = RT_INF; hcode = -1;
+              uint32_t m = (fb >> RT_CELL_SHIFT) & ((1u << RT_FB_MAX_LOOP) - 1u);
+              while (m) {
+                const uint32_t i = (uint32_t)__builtin_ctz(m);
+                m &= m - 1u;
+                const rt_geom g0 = rt_load_geom32(geom, i);
+                RT_GENERIC(i, g0)
+              }
+              scanned = true;
+#ifdef RT_TESTING
+              if (L.uniform_waves != nullptr && __builtin_ctzll(__ballot(true)) == (int)lane) atomicAdd(L.uniform_waves + 2, 1ull);
+#endif
+            }
+          }
+        }
+#endif
         if (!scanned) {
           ht = RT_INF; hcode = -1;
           uint32_t i = 0;
@@ -403,6 +433,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
         }
       }
       [[maybe_unused]] const bool primary_node = UNI || searched;       // wave-uniform: this node is the primary ray's
+      first_bounce = searched;                                          // ... and the next one, if any, the first bounce's
       searched = false;
       // ---- the enclosing sphere ----
       // The enclosing sphere (every other sphere, light and the camera strictly inside it: a skybox) is

@@ -219,7 +219,7 @@ bool table_is_ranked(int ranked, uint64_t n_blocks) { return ranked && (n_blocks
 
 int make_table_params(const rt_scene_header *hd, const rt_sphere *ob, const std::vector<rt_geom> &cull, const std::vector<uint32_t> &weight,
                       uint32_t w, uint32_t h, uint32_t ss, const rt_tiles *tiles, uint32_t tiles_x, uint32_t rb_per_tile, double proj_w, double proj_h, double proj_d,
-                      int ranked, bool mark_sky, uint32_t sky_sphere, bool shadow_masks, bool name_candidates, int checker_cells, const double lights[][3],
+                      int ranked, bool mark_sky, uint32_t sky_sphere, bool shadow_masks, bool name_candidates, int checker_cells, bool first_bounce, const double lights[][3],
                       rt_table_params *P, std::vector<rt_ball> *balls, std::vector<rt_cost_rect> *rects) {
   const uint32_t ny = tiles->n_tiles * rb_per_tile;
   const uint64_t n64 = (uint64_t)tiles_x * ny;
@@ -244,6 +244,16 @@ int make_table_params(const rt_scene_header *hd, const rt_sphere *ob, const std:
   };
   bool want_cells = false;
   if (checker_cells && want_cands) for (uint32_t j = 0; j < hd->n_objects; j++) want_cells = want_cells || cell_sphere(j);
+  // first-bounce sets ride there too: scenes without refraction, with a mirror among the loop spheres, at a depth that lets it reflect, of at
+  // most 13 loop spheres - and whose enclosing sphere, if any, does not reflect: a lane of a stating block whose primary ray misses every
+  // candidate meets that sphere, which is outside the loops, the candidates and the statement, and a ray it reflected would be at its first
+  // bounce like the mirrors' (rt_block.h: rt_first_bounce_set)
+  bool want_first_bounce = false;
+  if (first_bounce && want_cands && hd->segs >= 2u && n_loop <= RT_FB_MAX_LOOP && (sky_sphere == ~0u || ob[sky_sphere].albedo[3] <= 0.0)) {
+    bool refracts = false;
+    for (uint32_t j = 0; j < hd->n_objects; j++) { refracts = refracts || ob[j].albedo[4] > 0.0; want_first_bounce = want_first_bounce || (j != sky_sphere && ob[j].albedo[3] > 0.0); }
+    want_first_bounce = want_first_bounce && !refracts;
+  }
   // (ranking) blocks whose mirrors show a sphere that both reflects and refracts are nearly as dear as that sphere's own: rt_block.h, rt_bounce_cost
   bool want_bounce = false;
   if (table_is_ranked(ranked, n64) && hd->segs >= 3u)
@@ -253,7 +263,7 @@ int make_table_params(const rt_scene_header *hd, const rt_sphere *ob, const std:
   P->flags = (mark_sky ? RT_TABLE_SKY : 0u) | (want_masks ? RT_TABLE_MASKS : 0u) | (want_cands ? RT_TABLE_CANDS : 0u) | (n_loop > 16u ? RT_TABLE_WIDE : 0u) |
              (table_is_ranked(ranked, n64) ? RT_TABLE_RANK : 0u) | ((geometry && (mark_sky || want_masks || want_cands || want_bounce)) ? RT_TABLE_GEOMETRY : 0u) |
              ((geometry && want_bounce) ? RT_TABLE_BOUNCE : 0u) | ((geometry && want_cells) ? RT_TABLE_CELLS : 0u) |
-             ((geometry && want_cells && checker_cells >= 2) ? RT_TABLE_AXES : 0u);
+             ((geometry && want_cells && checker_cells >= 2) ? RT_TABLE_AXES : 0u) | ((geometry && want_first_bounce) ? RT_TABLE_FIRST_BOUNCE : 0u);
   P->cost_bins = 1u;
   P->n_lights = want_masks ? hd->n_lights : 0u;
   for (uint32_t k = 0; k < P->n_lights; k++) for (int c = 0; c < 3; c++) P->lights[k][c] = lights[k][c];
@@ -272,8 +282,8 @@ int make_table_params(const rt_scene_header *hd, const rt_sphere *ob, const std:
       if (!B.everywhere) { for (int c = 0; c < 3; c++) B.c[c] /= B.len; B.sin_b = B.R / B.len; B.cos_b = sqrt(1.0 - B.sin_b * B.sin_b); }
       B.tangent = sqrt(fmax(B.k, 0.0));
       if ((P->flags & RT_TABLE_CELLS) && cell_sphere(j)) { B.checker = 1u; B.fu = ob[j].checker_freq[0]; B.fv = ob[j].checker_freq[1]; B.r = sqrt(ob[j].r2); }
+      if (P->flags & (RT_TABLE_BOUNCE | RT_TABLE_FIRST_BOUNCE)) B.bounce = (ob[j].albedo[3] > 0.0 ? 1u : 0u) | (ob[j].albedo[4] > 0.0 ? 2u : 0u);
       if (P->flags & RT_TABLE_BOUNCE) {
-        B.bounce = (ob[j].albedo[3] > 0.0 ? 1u : 0u) | (ob[j].albedo[4] > 0.0 ? 2u : 0u);
         B.heavy = (B.bounce == 3u && weight[j] >= 16u) ? weight[j] : 0u;
       }
       for (uint32_t k = 0; k < P->n_lights; k++) {      // the sphere as an occluder seen from light k
@@ -326,12 +336,12 @@ int make_table_params(const rt_scene_header *hd, const rt_sphere *ob, const std:
 std::vector<uint32_t> build_launch_table(const rt_scene_header *hd, const rt_sphere *ob, const std::vector<rt_geom> &cull, const std::vector<uint32_t> &weight,
                                          uint32_t w, uint32_t h, uint32_t ss,
                                          const rt_tiles *tiles, uint32_t tiles_x, uint32_t rb_per_tile, double proj_w, double proj_h, double proj_d, int ranked,
-                                         bool mark_sky, uint32_t sky_sphere, bool shadow_masks, bool name_candidates, int checker_cells, const double lights[][3], uint32_t *n_entries, uint32_t sky_part) {
+                                         bool mark_sky, uint32_t sky_sphere, bool shadow_masks, bool name_candidates, int checker_cells, bool first_bounce, const double lights[][3], uint32_t *n_entries, uint32_t sky_part) {
   if (n_entries) *n_entries = 0;
   rt_table_params P;
   std::vector<rt_ball> balls;
   std::vector<rt_cost_rect> rects;
-  if (make_table_params(hd, ob, cull, weight, w, h, ss, tiles, tiles_x, rb_per_tile, proj_w, proj_h, proj_d, ranked, mark_sky, sky_sphere, shadow_masks, name_candidates, checker_cells, lights,
+  if (make_table_params(hd, ob, cull, weight, w, h, ss, tiles, tiles_x, rb_per_tile, proj_w, proj_h, proj_d, ranked, mark_sky, sky_sphere, shadow_masks, name_candidates, checker_cells, first_bounce, lights,
                         &P, &balls, &rects)) return {};
   const uint32_t ny = P.ny, n = tiles_x * ny;
   const bool rank = (P.flags & RT_TABLE_RANK) != 0u;

@@ -119,16 +119,45 @@ __global__ void __launch_bounds__(WG_ROWS) rt_table_rows(const rt_table_dev T, u
           for (uint32_t ci = sub; ci < P.n_balls; ci += SUB) if ((cand[ci >> 6] >> (ci & 63u)) & 1ull) extra += rt_bounce_cost(P, K, balls, ci);
           extra = group_add<SUB>(extra);
         }
-        if (P.flags & RT_TABLE_MASKS) {
-          uint32_t mk[2] = {0u, 0u}, none = 0u;
+        // shadow masks and first-bounce set: work-item `sub` takes candidates sub, sub + SUB, ..., each one's patch worked out once for both
+        const bool want_masks = (P.flags & RT_TABLE_MASKS) != 0u;
+        // (compiled into the few-sphere instantiations alone: a scene of more than 13 loop spheres states no set, and the many-sphere forms have no register for it)
+        constexpr bool FB = STAGED && SUB == 4u;
+        const bool want_fb = FB && (P.flags & RT_TABLE_FIRST_BOUNCE) && (P.flags & RT_TABLE_CANDS) && n_cand <= 2u;      // (group-uniform)
+        if constexpr (!FB) {
+          if (want_masks) {
+            uint32_t mk[2] = {0u, 0u}, none = 0u;
+            for (uint32_t ci = sub; ci < P.n_balls; ci += SUB)
+              if ((cand[ci >> 6] >> (ci & 63u)) & 1ull) {
+                if (!rt_cand_patch_masks(P, K, balls, ci, mk)) none = 1u;
+                if (mk[0] == 0xffffu && mk[1] == 0xffffu) break;       // (as on the host: the word is 0xffffffff whatever follows)
+              }
+            none = group_or<SUB>(none);
+            const uint32_t m0 = group_or<SUB>(mk[0]), m1 = group_or<SUB>(mk[1]);
+            if (!none) smask = m0 | (m1 << 16);
+          }
+        } else
+        if (want_masks || want_fb) {
+          uint32_t mk[2] = {0u, 0u}, none = 0u, fb_set = 0u, fb_none = 0u;
           for (uint32_t ci = sub; ci < P.n_balls; ci += SUB)
             if ((cand[ci >> 6] >> (ci & 63u)) & 1ull) {
-              if (!rt_cand_masks(P, K, balls, ci, mk)) none = 1u;
-              if (mk[0] == 0xffffu && mk[1] == 0xffffu) break;       // (as on the host: the word is 0xffffffff whatever follows)
+              rt_patch pt;
+              const bool patch_ok = rt_cand_patch(P, K, balls[ci], &pt);
+              if (want_fb && !rt_cand_first_bounce(P, K, balls, ci, patch_ok, pt, &fb_set)) fb_none = 1u;
+              if (want_masks) {
+                if (!patch_ok) none = 1u; else rt_cand_masks(P, pt, balls, ci, mk);
+                if (mk[0] == 0xffffu && mk[1] == 0xffffu) break;       // (as on the host: the word is 0xffffffff whatever follows; never with a first-bounce set's 13 spheres)
+              }
             }
-          none = group_or<SUB>(none);
-          const uint32_t m0 = group_or<SUB>(mk[0]), m1 = group_or<SUB>(mk[1]);
-          if (!none) smask = m0 | (m1 << 16);
+          if (want_fb) {
+            fb_none = group_or<SUB>(fb_none); fb_set = group_or<SUB>(fb_set);
+            if (sub == 0u) cands |= rt_first_bounce_word(P, cands, !fb_none, fb_set);
+          }
+          if (want_masks) {
+            none = group_or<SUB>(none);
+            const uint32_t m0 = group_or<SUB>(mk[0]), m1 = group_or<SUB>(mk[1]);
+            if (!none) smask = m0 | (m1 << 16);
+          }
         }
       }
     }
