@@ -168,6 +168,8 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
   const uint32_t lane = tid & 63u;
   const rt_pixel P0 = rt_pixel_of<SS2, W1>(L, tid);
 #if !RT_STRICT
+  // (the few-sphere one-wave kernels: the launch-record fields of the prologue go out beside the entry's load - rt_kernel_entry.h)
+  if constexpr (W1 && !REFRACT && !COUNT && !GRID) rt_head_batch(L);
   // workgroup-uniform: a block wholly past its tile's or the frame's last row - or no entry at all: while the host does not know how
   // many entries a table built on the GPU a moment ago has, it launches one workgroup per BLOCK, and the slots behind the last
   // entry are zero (rt_tables_gpu.hip)

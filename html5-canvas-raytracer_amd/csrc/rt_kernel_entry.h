@@ -81,6 +81,19 @@ __device__ __forceinline__ rt_pixel rt_pixel_of(const rt_launch &L, uint32_t tid
 #endif
 
 #if !RT_STRICT
+// The HEAD BATCH of the few-sphere one-wave kernels: every launch-record field that the prologue, the ray generation and a one-candidate
+// wave's anchored test read and that does not depend on the launch-table entry, used by ONE empty asm statement placed behind the
+// entry's load (rt_trace, after rt_pixel_of).  The use keeps each field's scalar load in the kernel's first block - the compiler
+// otherwise sinks every load to its first use, and a one-candidate wave then stands through a wait per field on its way to its
+// primary root - where they go out beside the entry's load: the entry is unique to the wave (L2 or HBM), the fields hit the scalar
+// cache, and the one wait for the entry covers them all.  Every later read of these fields is the same load; all of them are consumed
+// by the end of the ray generation or were live across the kernel before (n_objects, epsilon, the image).  Headline +1.5 %; the same
+// batch at the kernel's top, ahead of the table pointer's wait, +1.0 % (docs/EVIDENCE.md, first section).
+__device__ __forceinline__ void rt_head_batch(const rt_launch &L) {
+  asm volatile("" :: "s"(L.order), "s"(L.order_n8), "s"(L.n_objects), "s"(L.n_loop), "s"(L.segs), "s"(L.objects), "s"(L.geom_cam), "s"(L.lds_image),
+               "s"(L.cam_origin[0]), "s"(L.cam_origin[1]), "s"(L.cam_origin[2]), "s"(L.ray_bias[0]), "s"(L.ray_bias[1]), "s"(L.ray_bias[2]),
+               "s"(L.cam_axis_sum[0]), "s"(L.cam_axis_sum[1]), "s"(L.epsilon));
+}
 // Word 2 of this workgroup's launch-table entry: per light, the 16-bit set of loop-order spheres that can shadow a primary hit of
 // its block (rt_block.h), or ~0u.  Read again where it is used - the primary node's lighting - instead of being kept in a
 // scalar register across the cull and the search (the kernel has none to spare).

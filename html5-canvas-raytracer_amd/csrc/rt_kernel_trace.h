@@ -622,9 +622,12 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
             // light k from the kernarg segment through a 32-bit byte offset (scalar load with an SGPR offset)
             const double *lk = (const double *)((const char *)&L.lights[0][0] + (uint32_t)(k * 24u));
 #if !RT_STRICT
-            // few spheres (no shadow grid): the scan's first two records are fetched HERE, with the light's position - their latency
-            // hides behind the light vector's normalisation instead of standing in front of the scan (a wave whose lanes all
-            // face away wasted one load); measured -0.3 % on the headline, and +0.4 % where the grid path made it a wasted load
+            // few spheres (no shadow grid): the scan's first two records are READ here, with the light's position, so that their latency
+            // could hide behind the light vector's normalisation (measured -0.3 % on the headline when it was written, and +0.4 % where
+            // the grid path made it a wasted load).  In today's code object the compiler sinks the load to its use: the s_load_dwordx16
+            // stands behind the normalisation, in front of the scan's first pair, in both copies of the loop - and a block whose entry
+            // says that nothing can shadow it (no_occluder) does not load at all.  Pinning the load here (an opaque copy of the pair
+            // in front of the facing test) makes every light of every wave pay for it: headline -1.7 % (docs/EVIDENCE.md, first section)
             [[maybe_unused]] rt_geom_pair gp_first;
             if constexpr (!GRID && !COUNT) {
               [[maybe_unused]] const geom_kptr gl = (geom_kptr)L.geom_light;
