@@ -32,8 +32,8 @@ int ensure_device(int d) {
   std::lock_guard<std::mutex> lk(G.dev_mu);
   if (!s.stream) {
     hipStream_t st = nullptr;
-    HIP_TRY(hipMalloc(&s.d_counters, 6 * sizeof(unsigned long long)));      // RT_FLAG_COUNT's three; [3], [4], [5]: the test build's uniform-path waves, checker-cell waves and first-bounce-set waves (rt_test_uniform_waves, rt_test_cell_waves, rt_test_first_bounce_waves) - the product build never touches them
-    HIP_TRY(hipMemset(s.d_counters, 0, 6 * sizeof(unsigned long long)));
+    HIP_TRY(hipMalloc(&s.d_counters, 7 * sizeof(unsigned long long)));      // RT_FLAG_COUNT's three; [3] .. [6]: the test build's uniform-path waves, checker-cell waves, first-bounce-set waves and second-node waves (rt_test_uniform_waves, rt_test_cell_waves, rt_test_first_bounce_waves, rt_test_second_node_waves) - the product build never touches them
+    HIP_TRY(hipMemset(s.d_counters, 0, 7 * sizeof(unsigned long long)));
     HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     s.stream = st;                         // published last: a non-NULL stream means the device state is complete
   }
@@ -316,7 +316,9 @@ extern "C" int rt_scene_launch_table(const void *blob, size_t bytes, uint32_t w,
   if ((uint64_t)tiles->n_tiles * g.rb_per_tile > 65535u) return fail(RT_ERR_INVALID, "too many row blocks");
   // (bit 5 of `ranked`, with bit 2: word 3 also carries the checker cells of one-candidate blocks, as a product frame's table does;
   // bit 6, with bit 5: and the per-axis statements of the columns that are not inside one cell, rt_block.h: rt_cells_word;
-  // bit 7, with bit 2: and the first-bounce sets of the blocks that show a mirror, rt_block.h: rt_first_bounce_set)
+  // bit 7, with bit 2: and the first-bounce sets of the blocks that show a mirror, rt_block.h: rt_first_bounce_set;
+  // bit 8, with bit 7: and in word 1 of those entries what the node after the primary may skip, rt_block.h: rt_second_node_bits;
+  // bit 9, with bit 8: and the two bits about that node's shadow scans, rt_block.h: rt_cand_second_dark - no launch's table has them)
   // (bit 1 of `ranked`: also mark the workgroups no sphere but the enclosing one can show in, as a launch of a constant-background scene does)
   double lights[RT_MAX_LIGHTS][3];
   memset(lights, 0, sizeof lights);
@@ -324,7 +326,7 @@ extern "C" int rt_scene_launch_table(const void *blob, size_t bytes, uint32_t w,
   const uint32_t sky_sphere = enclosing_sphere(hd, ob, lights);
   uint32_t n_entries = 0;
   const std::vector<uint32_t> table = build_launch_table(hd, ob, cull, weight, w, h, ss, tiles, g.tiles_x, g.rb_per_tile, g.proj_w, g.proj_h, g.proj_d, (ranked & 1) != 0, (ranked & 2) != 0, sky_sphere,
-                                                         (ranked & 4) != 0, (ranked & 4) != 0, (ranked & 32) ? ((ranked & 64) ? 2 : 1) : 0, (ranked & 128) != 0, lights, &n_entries, (ranked & 8) ? 1u : ((ranked & 16) ? 2u : 0u));
+                                                         (ranked & 4) != 0, (ranked & 4) != 0, (ranked & 32) ? ((ranked & 64) ? 2 : 1) : 0, (ranked & 128) != 0, (ranked & 256) ? ((ranked & 512) ? 2 : 1) : 0, lights, &n_entries, (ranked & 8) ? 1u : ((ranked & 16) ? 2u : 0u));
   if (table.empty()) return fail(RT_ERR_INVALID, "a launch of this size is beyond the launch table");
   *n_workgroups = n_entries;
   if (n_blocks) *n_blocks = g.tiles_x * tiles->n_tiles * g.rb_per_tile;

@@ -256,7 +256,7 @@ struct rt_scene_dev {
   // behind all of T's arrays; `n_blocks` workgroups are launched until the host has seen the number of entries the build published
   // (`known`: generation << 32 | entries + 1, a pinned host word), from then on exactly that many.
   struct order_entry {
-    frame_kind kind; int ranked; bool sky, masks, cands; int cells; bool first_bounce;     // ranked: 0 grid order, 1 ranked when large enough, 2 always (a compact band's launch)
+    frame_kind kind; int ranked; bool sky, masks, cands; int cells; bool first_bounce; int second_node;     // ranked: 0 grid order, 1 ranked when large enough, 2 always (a compact band's launch)
     uint64_t cam_gen; uint32_t n_blocks; volatile unsigned long long *known; hipStream_t built_on; event built;
     bool shared;                   // launched with on a stream other than the one it was built on
     // two tables, like the camera blocks: generation g's is Tb[g & 1] (the next camera's is built while this one's is still read)
@@ -298,7 +298,7 @@ bool strict_scene(const rt_scene_dev *s);
 bool sky_fast(const rt_scene_dev *s);
 bool masks_pay(const rt_scene_dev *s, uint32_t uses_before);
 uint32_t sky_part_of(uint32_t flags);
-struct table_choice { int ranked; bool mark_sky, shadow_masks, name_candidates; int checker_cells; bool first_bounce; };      // checker_cells: 0 none, 1 whole cells, 2 and single axes; first_bounce: first-bounce sets (rt_block.h)
+struct table_choice { int ranked; bool mark_sky, shadow_masks, name_candidates; int checker_cells; bool first_bounce; int second_node; };      // checker_cells: 0 none, 1 whole cells, 2 and single axes; first_bounce: first-bounce sets, second_node: 1 and what the node after the primary may skip; 2 (the HOST probe's host-built table only, never a launch's) and its shadow bits (rt_block.h)
 table_choice choose_table(const rt_scene_dev *s, uint32_t flags, uint32_t uses_before);
 uint32_t count_use(rt_scene_dev *s, const frame_kind &kind);
 volatile unsigned long long *known_word(rt_scene_dev *s, size_t index);

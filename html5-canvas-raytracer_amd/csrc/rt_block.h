@@ -26,6 +26,10 @@
 //   * first-bounce set (RT_TABLE_FIRST_BOUNCE) - for a block of one or two candidates of which at least one is a mirror: the loop-order
 //                  spheres a ray REFLECTED at a primary hit of the block can meet at all (rt_first_bounce_set); bit 31 and bits 18..30
 //                  of the candidates' word, never beside checker cells;
+//   * second node (RT_TABLE_SECOND_NODE) - for a block that states a first-bounce set: which of its candidates the walk of that set may leave
+//                  out (a ray reflected at a mirror cannot be accepted at that mirror again: rt_self_clear), and whether nothing is left then - every
+//                  reflected ray of the block ends on the background (rt_second_node_bits); bits 24..26 of word 1, which a block that is
+//                  no sky run leaves free;
 //   * cost       - 1 + the weights of the spheres whose screen rectangle (the primary-ray cull's) touches the block, + what its
 //                  mirrors show of the scene's dearest spheres (rt_bounce_cost): what ranks the blocks dearest first.
 #ifndef RT_BLOCK_H
@@ -54,6 +58,8 @@
 #define RT_TABLE_CELLS 512u      /* checker cells: word 3 also says which 8-pixel columns of a one-candidate block lie inside ONE checker cell (rt_column_cell) */
 #define RT_TABLE_AXES 1024u      /* checker cells, per axis (with RT_TABLE_CELLS): a column that is NOT inside one cell may still lie inside one cell of ONE axis (rt_cells_word) */
 #define RT_TABLE_FIRST_BOUNCE 2048u /* first-bounce sets: word 3 of a block whose candidates include a mirror also names the spheres its reflected rays can meet (rt_first_bounce_set) */
+#define RT_TABLE_SECOND_NODE 4096u /* second node (with RT_TABLE_FIRST_BOUNCE): word 1 of an entry that states a first-bounce set also says what the node after the primary may skip (rt_second_node_bits) */
+#define RT_TABLE_SECOND_DARK 8192u /* ... and (with shadow masks) whether anything can shadow that node's hits (rt_cand_second_dark).  HOST BUILD ONLY, set by the host probe alone: counted below what pays, the device build does not know it, no kernel reads it (docs/EVIDENCE.md) */
 #define RT_SKY_RUN_MAX 32u       /* consecutive sky blocks of a row block that share ONE entry */
 #define RT_CAND_MASK 0x3ffffu     /* word 3, bits 0..17: the candidates; what every reader of them keeps */
 #define RT_CELL_SHIFT 18u        /* ... bits 18..21: column c (bit 18 + c) lies inside one checker cell; bits 22..25: that cell's parity; RT_TABLE_AXES: and bits 26..30, rt_cells_word */
@@ -64,6 +70,19 @@
 // (two candidates) or - one candidate, which is then the mirror - turned away by that path's material test before it reads a cell bit.
 #define RT_FB_STATED 0x80000000u  /* word 3, bit 31: bits 18..30 are the block's first-bounce set */
 #define RT_FB_MAX_LOOP 13u        /* ... which names loop spheres 0..12: scenes of more state nothing */
+// Word 1's bits 24..30 hold `run - 1` in a sky run's entry (bit 31 set) and are free in every other entry: an entry that states a first-bounce
+// set says there what the node AFTER the primary may skip (RT_TABLE_SECOND_NODE; rt_second_node_bits).  Bits 27 and 28 say the same
+// about that node's shadow scans (RT_TABLE_SECOND_DARK: the host probe's flag; the host build alone states them).
+// WHO READS WHAT: the trace kernels read SELF0 and SELF1 and NOTHING ELSE.  SKY, DARK0 and DARK1 are held to the reference's rules by
+// tests/test_second_node.py, but no GPU test covers a kernel that acts on them, because none does: a kernel that starts to read one owes its
+// own byte-for-byte test first.
+#define RT_SN_SHIFT 24u           /* word 1, bit 24 + ... */
+#define RT_SN_SELF0 1u            /* ... 0: the walk of the set may leave out candidate 0 (word 3's bits 0..7) */
+#define RT_SN_SELF1 2u            /* ... 1: and candidate 1 (bits 8..15; only beside a count of 2) */
+#define RT_SN_SKY 4u              /* ... 2: the set without the candidates left out is empty - every reflected ray of the block meets no loop sphere (NO KERNEL READS IT: ending such rays at the primary node measured no gain, docs/EVIDENCE.md) */
+#define RT_SN_DARK0 8u            /* ... 3: no loop sphere can stand between light 0 and any second-node hit of the block (rt_cand_second_dark; NO KERNEL READS IT, no launch's table states it) */
+#define RT_SN_DARK1 16u           /* ... 4: the same for light 1 */
+#define RT_SN_MASK 0x1fu          /* (bits 24..28: what a reader keeps) */
 #define RT_COST_MAX 1023u        /* costs are clamped here (the ranking only has to order the blocks roughly) */
 
 // a sphere as the cone test sees it (one per sphere but the enclosing one, scene order)
@@ -295,19 +314,26 @@ RT_HD inline bool rt_cand_patch_masks(const rt_table_params &P, const rt_cone &K
 //   sphere j   a reflected ray starts within rho of Q, so it meets sphere j at t >= 0 only if the ray from Q with the same direction meets
 //              the ball (C_j, R_j (1 + 1e-7) + rho) at t >= 0: Q inside that ball, or angle(r0, C_j - Q) <= sigma + asin((R_j + rho) /
 //              |C_j - Q|) - a sum below pi, tested as a cosine scaled by |C_j - Q|.
-RT_HD inline uint32_t rt_first_bounce_set(const rt_table_params &P, const rt_cone &K, const rt_patch &pt, const rt_ball *balls, uint32_t ci) {
-  const rt_ball &B = balls[ci];
+// (the cone of the reflected rays: axis r0, cos / sin of sigma; their origins lie within pt.rho of pt.Q.  false: no bound)
+struct rt_fb_cone { double r0[3], c_sig, s_sig; };
+RT_HD inline bool rt_first_bounce_cone(const rt_cone &K, const rt_patch &pt, const rt_ball &B, rt_fb_cone *F) {
   const double qo[3] = {pt.Q[0] - B.o[0], pt.Q[1] - B.o[1], pt.Q[2] - B.o[2]};
   const double lq = sqrt(qo[0] * qo[0] + qo[1] * qo[1] + qo[2] * qo[2]);
-  if (!(pt.rho < 0.7 * lq) || !(lq <= 1.7976931348623157e308)) return 0u;
+  if (!(pt.rho < 0.7 * lq) || !(lq <= 1.7976931348623157e308)) return false;
   const double s_dn = pt.rho / lq * (1.0 + 1e-7), c_dn = sqrt(1.0 - s_dn * s_dn);
   const double s_2dn = 2.0 * s_dn * c_dn, c_2dn = 1.0 - 2.0 * s_dn * s_dn;
   const double c_sig = (K.cos_a * c_2dn - K.sin_a * s_2dn) - 1e-7;                 // cos(alpha + 2 dn), a slightly wider cone
-  if (!(c_sig > 0.0)) return 0u;
-  const double s_sig = sqrt(1.0 - c_sig * c_sig);
+  if (!(c_sig > 0.0)) return false;
+  F->c_sig = c_sig; F->s_sig = sqrt(1.0 - c_sig * c_sig);
   const double il = 1.0 / lq, n0[3] = {qo[0] * il, qo[1] * il, qo[2] * il};
   const double an = K.ax[0] * n0[0] + K.ax[1] * n0[1] + K.ax[2] * n0[2];
-  const double r0[3] = {K.ax[0] - 2.0 * an * n0[0], K.ax[1] - 2.0 * an * n0[1], K.ax[2] - 2.0 * an * n0[2]};
+  F->r0[0] = K.ax[0] - 2.0 * an * n0[0]; F->r0[1] = K.ax[1] - 2.0 * an * n0[1]; F->r0[2] = K.ax[2] - 2.0 * an * n0[2];
+  return true;
+}
+RT_HD inline uint32_t rt_first_bounce_set(const rt_table_params &P, const rt_patch &pt, const rt_fb_cone &F, const rt_ball *balls, uint32_t ci) {
+  const rt_ball &B = balls[ci];
+  const double *r0 = F.r0;
+  const double c_sig = F.c_sig, s_sig = F.s_sig;
   uint32_t set = 1u << B.loop;
   for (uint32_t j = 0; j < P.n_balls; j++) {
     if (j == ci) continue;
@@ -325,14 +351,62 @@ RT_HD inline uint32_t rt_first_bounce_set(const rt_table_params &P, const rt_con
   }
   return set;
 }
+// Second node (RT_TABLE_SECOND_NODE).  A mirror B of a stating block is in the block's set because its own reflected rays start ON it: the walk
+// at the node after the primary tests B with the reference's generic form (main.js:420-439) from the hit point h along the reflected direction
+// d, and in exact arithmetic finds the roots t0 = 2 tca <= 0 and t1 = 0, neither of them >= epsilon.  rt_self_clear bounds what rounding can
+// make of t1 - the kernels' rounding and the reference's alike (u = 1.2e-16 above the unit roundoff 2^-53; the product kernel's rsqrt, good to
+// 4.1e-15 = 36 u, scales a direction and is counted where a scale reaches the result) - in terms of
+//     S = |C| + R + |camera|_1 + |centre|_1,
+// which is no smaller than any coordinate of h, than the hit distance t, than the sphere's radius r and than |C| = |centre - camera|.
+//   primary discriminant  disc = tca^2 - (C.C - r^2) with tca = d0.C: the dot products, the square and the host's C.C - r^2 are each good to a few
+//              u S^2; together dp = 16 u S^2.  Its square root thc is then off by min(sqrt(dp), dp / thc) - at grazing incidence, thc -> 0, the
+//              error of the root is the SQUARE ROOT of the rounding - and the hit distance t = tca - thc by Dt <= that + 5 u S;
+//   hit point  h = camera + d0 t is rounded per coordinate (<= 4 u S) and d0's scale moves it by 36 u t; sliding h along the ray by Dt moves
+//              its distance from the centre by Dt thc / r + Dt^2 / (2 r) (thc = r cos(incidence)), which with the line above is at most
+//              2 dp / r: the hit lies eta = 2 dp / r + 64 u S off the sphere at most.  eta <= r / 1000 is required (the normal (h - o) / r is
+//              then a unit vector to 1e-3 and the reflection keeps the sign of d0.n);
+//   direction  the reflected ray leaves the sphere: d.(o - h) = d0.(h - o) (1 + O(eta / r)), and d0.(h - o) = Dt - thc up to 64 u S, which is
+//              positive only where thc < Dt <= dp / thc, i.e. by less than sqrt(dp).  So tca2 = d.(o - h) <= tau = sqrt(dp) + 64 u S;
+//   second discriminant  disc2 = r^2 - (|o - h|^2 - tca2^2) = tca2^2 - (|o - h|^2 - r^2) + rounding, |o - h|^2 - r^2 >= -(2 r eta + eta^2), the
+//              rounding of the three dot products, of the differences and of d's scale (72 u tca2^2) at most 128 u S^2:
+//              disc2 <= tca2^2 + k, k = 2 r eta + eta^2 + 128 u S^2 - "the square root of rounding times r^2" once more;
+//   far root   t1 = tca2 + sqrt(disc2) grows with tca2, so t1 <= tau + sqrt(tau^2 + k) <= 2 tau + sqrt(k); t0 <= tca2 <= tau.
+// The statement is made when SIXTEEN times that bound (256 times the unit roundoff under the square roots) is still no more than epsilon:
+// neither root can then reach epsilon and the test cannot accept.  For the reference's scene (S ~ 30, epsilon 1e-3) the bound is 7e-6; a
+// mirror hundreds of units across or away, or an epsilon of 1e-6, states nothing.  The primary hit is the NEAR root of a camera outside the
+// sphere: rt_cand_patch (a stating block has one) requires |C| - R >= 2 |epsilon|.
+// The forms of the primary hit the bound was written against: the product kernels' anchored test (rt_kernel_trace.h: RT_ANCHORED, disc =
+// fma(tca, tca, -Ca) with the host's Ca = C.C - r^2, h = p + d t) and the reference's generic one (disc = r^2 - (C.C - tca^2): the same terms,
+// rounded in another order, inside the same dp), which the strict kernels and the C restatement run; the product kernels' square root and
+// rsqrt as rt_kernel_math.h measures them (1.1e-16 and 4.1e-15).  A kernel that finds its primary hit another way - through a transformed
+// ray, in lower precision - is outside the derivation and must not read the bits.
+RT_HD inline bool rt_self_clear(const rt_table_params &P, const rt_ball &B) {
+  const double u = 1.2e-16, r = B.R;
+  const double S = B.len + r + (fabs(P.cam[0]) + fabs(P.cam[1]) + fabs(P.cam[2])) + (fabs(B.o[0]) + fabs(B.o[1]) + fabs(B.o[2]));
+  if (!(r > 0.0) || !(S <= 1.7976931348623157e308)) return false;
+  const double dp = 16.0 * u * S * S, eta = 2.0 * dp / r + 64.0 * u * S;
+  if (!(eta <= 1e-3 * r)) return false;
+  const double tau = sqrt(dp) + 64.0 * u * S, k = 2.0 * r * eta + eta * eta + 128.0 * u * S * S;
+  return 16.0 * (2.0 * tau + sqrt(k)) <= P.epsilon;                // (a negative or NaN epsilon states nothing)
+}
+// ... of a block: what candidate ci keeps IN the walk - the other spheres its reflected rays can meet (s: its rt_first_bounce_set, 0 if it is no
+// mirror or states none), and itself unless rt_self_clear holds.  OR-ed over the block's candidates: a candidate of the block's set that is
+// in no candidate's keep may be left out.
+RT_HD inline uint32_t rt_cand_second_keep(const rt_table_params &P, const rt_ball *balls, uint32_t ci, uint32_t s) {
+  const rt_ball &B = balls[ci];
+  if (!(P.flags & RT_TABLE_SECOND_NODE) || !s) return 0u;
+  return (s & ~(1u << B.loop)) | (rt_self_clear(P, B) ? 0u : 1u << B.loop);
+}
 // ... of a block: OR `*set` over its candidates, one call each.  false: the block states no set (a candidate refracts, or a mirror among
-// them has no patch or no bound); a candidate that does not reflect adds nothing (its hits spawn no ray)
-RT_HD inline bool rt_cand_first_bounce(const rt_table_params &P, const rt_cone &K, const rt_ball *balls, uint32_t ci, bool patch_ok, const rt_patch &pt, uint32_t *set) {
+// them has no patch or no bound); a candidate that does not reflect adds nothing (its hits spawn no ray); *keep: OR of rt_cand_second_keep
+RT_HD inline bool rt_cand_first_bounce(const rt_table_params &P, const rt_cone &K, const rt_ball *balls, uint32_t ci, bool patch_ok, const rt_patch &pt, uint32_t *set, uint32_t *keep) {
   const rt_ball &B = balls[ci];
   if (B.bounce & 2u) return false;
   if (!(B.bounce & 1u)) return true;
-  const uint32_t s = patch_ok ? rt_first_bounce_set(P, K, pt, balls, ci) : 0u;
+  rt_fb_cone F;
+  const uint32_t s = (patch_ok && rt_first_bounce_cone(K, pt, B, &F)) ? rt_first_bounce_set(P, pt, F, balls, ci) : 0u;
   *set |= s;
+  *keep |= rt_cand_second_keep(P, balls, ci, s);
   return s != 0u;
 }
 // word 3's upper bits from the block's set (0: none of its candidates is a mirror), whether every candidate could be stated, and the
@@ -340,6 +414,71 @@ RT_HD inline bool rt_cand_first_bounce(const rt_table_params &P, const rt_cone &
 RT_HD inline uint32_t rt_first_bounce_word(const rt_table_params &P, uint32_t cands, bool ok, uint32_t set) {
   if (!(P.flags & RT_TABLE_FIRST_BOUNCE) || !ok || !set || !(cands & RT_CAND_MASK) || (cands >> RT_CELL_SHIFT)) return 0u;
   return RT_FB_STATED | (set << RT_CELL_SHIFT);
+}
+
+// word 1's upper bits from word 3 (candidates and, if stated, the set) and the block's keep
+RT_HD inline uint32_t rt_second_node_bits(const rt_table_params &P, uint32_t cands, uint32_t keep) {
+  if (!(P.flags & RT_TABLE_SECOND_NODE) || !(cands & RT_FB_STATED)) return 0u;
+  const uint32_t set = (cands >> RT_CELL_SHIFT) & ((1u << RT_FB_MAX_LOOP) - 1u), drop = set & ~keep;
+  const uint32_t c0 = cands & 255u, c1 = (cands >> 8) & 255u, n = (cands >> 16) & 3u;
+  uint32_t bits = 0u;
+  if (c0 < RT_FB_MAX_LOOP && ((drop >> c0) & 1u)) bits |= RT_SN_SELF0;
+  if (n == 2u && c1 < RT_FB_MAX_LOOP && ((drop >> c1) & 1u)) bits |= RT_SN_SELF1;
+  if (!(set & ~drop)) bits |= RT_SN_SKY;
+  return bits << RT_SN_SHIFT;
+}
+
+// DARK (RT_TABLE_SECOND_DARK, with RT_TABLE_SECOND_NODE and shadow masks) - HOST ONLY: rt_block_statement, the host's build, states it for the
+// host probe (profiles/count_second_node.py counts with it; tests/test_second_node.py holds it); the device build neither calls nor compiles
+// any of it, no launch's table carries the bits and no kernel reads them - counted below what pays (docs/EVIDENCE.md).  Where can the SECOND-node hits of mirror candidate ci lie on receiver sphere B, and which
+// spheres can stand between them and light k?  rt_cand_patch, generalised from the camera's cone to the reflected rays' (origins within
+// rho of Q, directions within sigma of r0): a hit is h = (Q + e) + t d, |e| <= rho, and t is the near root from Q of the sphere shifted by
+// -e: c = d.(C - e) lies in |C| cos(angle +- sigma) +- rho, k = |C - e|^2 - r^2 in [(|C| - rho)^2 - R^2, (|C| + rho)^2 - r_lo^2] (R the widened
+// radius, r_lo = R (1 - 2e-7) below the true one); t = k / (c + sqrt(c^2 - k)) grows with k and falls with c, so it lies between its values
+// at (c_hi, k_lo) and (c_lo, k_hi).  EVERY ray must meet the sphere from outside (c_lo >= sqrt(k_hi), with room; origins 2 epsilon off it):
+// a cone that grazes the receiver has no finite patch and nothing is stated.  The ball is rt_cand_patch's, around Q + m r0, plus rho.
+inline bool rt_bounce_patch(const rt_table_params &P, const rt_patch &pt, const rt_fb_cone &F, const rt_ball &B, rt_patch *out) {
+  const double W[3] = {B.o[0] - pt.Q[0], B.o[1] - pt.Q[1], B.o[2] - pt.Q[2]};
+  const double len = sqrt(W[0] * W[0] + W[1] * W[1] + W[2] * W[2]), rho = pt.rho;
+  if (!(len - B.R - rho >= 2.0 * fabs(P.epsilon)) || !(len <= 1.7976931348623157e308)) return false;
+  const double cs = fmin(1.0, fmax(-1.0, (F.r0[0] * W[0] + F.r0[1] * W[1] + F.r0[2] * W[2]) / len)), sn = sqrt(1.0 - cs * cs);
+  const double up = cs * F.c_sig + sn * F.s_sig;
+  const double c_hi = len * ((up >= 1.0 || sn <= F.s_sig) ? 1.0 : up) + rho, c_lo = len * (cs * F.c_sig - sn * F.s_sig) - rho;
+  const double r_lo = B.R * (1.0 - 2e-7), k_lo = (len - rho) * (len - rho) - B.R * B.R, k_hi = (len + rho) * (len + rho) - r_lo * r_lo;
+  if (!(k_lo > 0.0) || !(c_lo >= sqrt(k_hi) * (1.0 + 1e-7)) || !(c_hi >= c_lo)) return false;
+  const double t1 = (c_hi - sqrt(fmax(c_hi * c_hi - k_lo, 0.0))) * (1.0 - 1e-6), t2 = (c_lo - sqrt(fmax(c_lo * c_lo - k_hi, 0.0))) * (1.0 + 1e-6);
+  if (!(t2 >= t1) || !(t1 >= 0.0) || !(t2 <= 1.7976931348623157e308)) return false;
+  const double m = 0.5 * (t1 + t2);
+  out->rho = sqrt(0.25 * (t2 - t1) * (t2 - t1) + 2.0 * t2 * m * (1.0 - F.c_sig)) * (1.0 + 1e-6) + 1e-9 * t2 + rho * (1.0 + 1e-6);
+  out->Q[0] = pt.Q[0] + m * F.r0[0]; out->Q[1] = pt.Q[1] + m * F.r0[1]; out->Q[2] = pt.Q[2] + m * F.r0[2];
+  return true;
+}
+// ... of mirror candidate ci with first-bounce set s: per light the spheres that can shadow a second-node hit on any receiver of s (its own
+// sphere is no receiver when rt_self_clear holds), as mk[0] | mk[1] << 16; 0xffffffff: a receiver without a patch - no statement
+inline uint32_t rt_cand_second_dark(const rt_table_params &P, const rt_patch &pt, const rt_fb_cone &F, const rt_ball *balls, uint32_t ci, uint32_t s) {
+  uint32_t mk[2] = {0u, 0u};
+  for (uint32_t j = 0; j < P.n_balls; j++) {
+    const rt_ball &R = balls[j];
+    if (!((s >> R.loop) & 1u)) continue;
+    if (j == ci) { if (rt_self_clear(P, R)) continue; return 0xffffffffu; }
+    rt_patch q;
+    if (!rt_bounce_patch(P, pt, F, R, &q)) return 0xffffffffu;
+    rt_cand_masks(P, q, balls, j, mk);
+  }
+  return mk[0] | (mk[1] << 16);
+}
+// ... of a block with a stated set: bits 27 / 28 of word 1 (each mirror candidate's patch, cone and set worked out once more: the host has the time)
+inline uint32_t rt_block_second_dark(const rt_table_params &P, const rt_cone &K, const rt_ball *balls, const uint64_t cand[4]) {
+  if (!(P.flags & RT_TABLE_SECOND_DARK) || !(P.flags & RT_TABLE_MASKS) || !P.n_lights) return 0u;
+  uint32_t dark = 0u;
+  for (uint32_t ci = 0; ci < P.n_balls; ci++) {
+    if (!(cand[ci >> 6] >> (ci & 63u) & 1ull) || !(balls[ci].bounce & 1u)) continue;
+    rt_patch pt;
+    rt_fb_cone F;
+    if (!rt_cand_patch(P, K, balls[ci], &pt) || !rt_first_bounce_cone(K, pt, balls[ci], &F)) return 0u;
+    dark |= rt_cand_second_dark(P, pt, F, balls, ci, rt_first_bounce_set(P, pt, F, balls, ci));
+  }
+  return ((!(dark & 0xffffu) ? RT_SN_DARK0 : 0u) | ((P.n_lights >= 2u && !(dark >> 16)) ? RT_SN_DARK1 : 0u)) << RT_SN_SHIFT;
 }
 
 // Checker cells (RT_TABLE_CELLS).  A block with ONE candidate whose sampler is the sphere checker (main.js:126-133): do all the primary
@@ -477,8 +616,8 @@ RT_HD inline uint32_t rt_cells_word(const rt_table_params &P, uint32_t st4) {
 
 // touched / candidates / shadow masks of block (x, y), one block after the other (the host); *touched = 1 also when nothing can be said
 RT_HD inline void rt_block_statement(const rt_table_params &P, const rt_ball *balls, uint32_t x, uint32_t y, uint32_t *touched, uint32_t *cands_out, uint32_t *smask_out,
-                                     uint32_t *bounce_extra) {
-  *touched = 1u; *cands_out = 0u; *smask_out = 0xffffffffu; *bounce_extra = 0u;
+                                     uint32_t *bounce_extra, uint32_t *second_out) {
+  *touched = 1u; *cands_out = 0u; *smask_out = 0xffffffffu; *bounce_extra = 0u; *second_out = 0u;
   const rt_cone K = rt_block_cone(P, x, y);
   bool hit = K.hit != 0u, doubt = K.doubt != 0u;
   if (!(P.flags & RT_TABLE_GEOMETRY)) return;
@@ -506,24 +645,27 @@ RT_HD inline void rt_block_statement(const rt_table_params &P, const rt_ball *ba
   const bool want_masks = (P.flags & RT_TABLE_MASKS) != 0u;
   const bool want_fb = (P.flags & RT_TABLE_FIRST_BOUNCE) && (*cands_out & RT_CAND_MASK) && !(*cands_out >> RT_CELL_SHIFT);
   if (!want_masks && !want_fb) return;
-  uint32_t mk[2] = {0u, 0u}, fb_set = 0u;
+  uint32_t mk[2] = {0u, 0u}, fb_set = 0u, fb_keep = 0u;
   bool masks_ok = want_masks, fb_ok = true;
   for (uint32_t ci = 0; ci < P.n_balls; ci++) {
     if (!(cand[ci >> 6] >> (ci & 63u) & 1ull)) continue;
     rt_patch pt;
     const bool patch_ok = rt_cand_patch(P, K, balls[ci], &pt);
-    if (want_fb) fb_ok = rt_cand_first_bounce(P, K, balls, ci, patch_ok, pt, &fb_set) && fb_ok;
+    if (want_fb) fb_ok = rt_cand_first_bounce(P, K, balls, ci, patch_ok, pt, &fb_set, &fb_keep) && fb_ok;
     if (masks_ok) {
       if (!patch_ok) masks_ok = false; else rt_cand_masks(P, pt, balls, ci, mk);
       if (mk[0] == 0xffffu && mk[1] == 0xffffu) masks_ok = false;       // many spheres, both sets not empty: the word is 0xffffffff whatever follows
     }
   }
-  if (want_fb) *cands_out |= rt_first_bounce_word(P, *cands_out, fb_ok, fb_set);
+  if (want_fb) { *cands_out |= rt_first_bounce_word(P, *cands_out, fb_ok, fb_set); *second_out = rt_second_node_bits(P, *cands_out, fb_keep); }
+#if !defined(__HIP_DEVICE_COMPILE__)
+  if (want_fb && (*cands_out & RT_FB_STATED)) *second_out |= rt_block_second_dark(P, K, balls, cand);      // (the host probe's flag: rt_block_second_dark)
+#endif
   if (masks_ok) *smask_out = mk[0] | (mk[1] << 16);
 }
 
 // the two words of an entry that describe WHERE its block is: word 0 = tile_x | rows_valid << 11 | first frame row << 15,
-// word 1 = first row in this call's output band (| (run - 1) << 24 | sky << 31, added by the caller)
+// word 1 = first row in this call's output band (| (run - 1) << 24 | sky << 31, or | rt_second_node_bits, added by the caller)
 RT_HD inline void rt_block_place(const rt_table_params &P, uint32_t x, uint32_t y, uint32_t *w0, uint32_t *w1) {
   const uint32_t tile_i = y / P.rb_per_tile, rb = y - tile_i * P.rb_per_tile;
   const uint32_t trow0 = rb * P.rows_per_wg;                                             // first row of the block inside its tile

@@ -189,9 +189,11 @@ struct rt_launch {
   // ... and the uniform-material path of the one-wave product kernels (rt_kernel.hip: trace_pixel, UNI)
   uint32_t no_uniform;               // RT_NO_UNIFORM_BLOCKS: every wave takes the general path
   unsigned long long *uniform_waves; // counts the waves that took the path (rt_test_uniform_waves), or NULL; [1]: those whose checker cell came from the launch table (rt_test_cell_waves);
-                                     // [2]: the waves of the general path that scanned a first-bounce set (rt_test_first_bounce_waves)
+                                     // [2]: the waves of the general path that scanned a first-bounce set (rt_test_first_bounce_waves);
+                                     // [3]: those of them that left a candidate out of that walk (rt_test_second_node_waves)
   uint32_t no_cells;                 // RT_NO_CHECKER_CELLS: the kernel ignores the launch table's checker cells
   uint32_t no_first_bounce;          // RT_NO_FIRST_BOUNCE: the kernel ignores the launch table's first-bounce sets (every bounced ray scans every sphere)
+  uint32_t no_second_node;           // RT_NO_SECOND_NODE (and RT_NO_FIRST_BOUNCE): the kernel ignores the table's second-node bits (rt_block.h: rt_second_node_bits)
 #endif
 };
 

@@ -47,7 +47,7 @@ __device__ __forceinline__ rt_pixel rt_pixel_of(const rt_launch &L, uint32_t tid
 }
 #else
 // Product kernel: a FLAT grid (workgroups, 1, frames of the batch) and a launch table with one 16-byte entry per workgroup:
-//   word 0 = tile_x | rows_valid << 11 | first frame row << 15      word 1 = first row in this call's output band | (run - 1) << 24 | sky << 31
+//   word 0 = tile_x | rows_valid << 11 | first frame row << 15      word 1 = first row in this call's output band | (run - 1) << 24 | sky << 31, or (bit 31 clear) | second-node bits << 24
 //   word 2 = shadow masks                                            word 3 = primary candidates | checker cells << 18, or (bit 31) | first-bounce set << 18
 // (built on the GPU per camera, frame size and tile set: rt_tables_gpu.hip, rt_block.h).  One scalar load replaces the tile /
 // row-block arithmetic of the plain grid - no division, no tile parameters in registers - and decides the ORDER in which the
@@ -69,7 +69,7 @@ __device__ __forceinline__ rt_pixel rt_pixel_of(const rt_launch &L, uint32_t tid
   P.frow = frow0 + P.trow;
   P.lrow = (e1 & 0xffffffu) + P.trow;
   P.sky = (e1 >> 31) != 0u;                            // workgroup-uniform: no sphere can show in these blocks (rt_block.h) ...
-  P.run = ((e1 >> 24) & 127u) + 1u;                    // ... a run of this many 32-pixel blocks, starting at tile_x
+  P.run = ((e1 >> 24) & 127u) + 1u;                    // ... a run of this many 32-pixel blocks, starting at tile_x (read beside P.sky only: without bit 31 these bits are the entry's second-node bits, rt_entry_second_node below)
   P.cand = e4.w & RT_CAND_MASK;                        // the (at most two) loop spheres the block's primary rays can meet (count << 16 | second << 8 | first), or 0: cull
   // (an entry with bit 31 holds a first-bounce set in these bits instead: rt_entry_first_bounce below.  Its one candidate is then a mirror at a depth that
   // lets it reflect, and the uniform-material path - the only reader of the cells - turns the wave away by its material before it reads one: rt_block.h)
@@ -108,6 +108,15 @@ template <bool W1>
 __device__ __forceinline__ uint32_t rt_entry_first_bounce(const rt_launch &L) {
   const uint32_t slot = rt_entry_slot<W1>(L);
   return *(const uint32_t __attribute__((address_space(4))) *)((const char __attribute__((address_space(4))) *)L.order + ((size_t)slot << 4) + 12u);
+}
+// Word 1 of this workgroup's launch-table entry, for its second-node bits (rt_block.h: rt_second_node_bits; bits 24..28 of an entry that
+// states a first-bounce set, zero in every other entry that is no sky run): bit 24 / 25 - the first-bounce walk may leave out candidate 0 / 1,
+// bit 26 - nothing is left of the set then: every reflected ray of the block meets no loop sphere; bits 27 / 28 - nothing can shadow that
+// node's hits from light 0 / 1 (in no launch's table).  The kernels read bits 24 and 25 ALONE (rt_block.h says why).  Read again where it is used - the node after the primary - like words 2 and 3.
+template <bool W1>
+__device__ __forceinline__ uint32_t rt_entry_second_node(const rt_launch &L) {
+  const uint32_t slot = rt_entry_slot<W1>(L);
+  return *(const uint32_t __attribute__((address_space(4))) *)((const char __attribute__((address_space(4))) *)L.order + ((size_t)slot << 4) + 4u) >> RT_SN_SHIFT;
 }
 #endif
 

@@ -407,6 +407,16 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
             if (fb >> 31) {
               ht = RT_INF; hcode = -1;
               uint32_t m = (fb >> RT_CELL_SHIFT) & ((1u << RT_FB_MAX_LOOP) - 1u);
+              // ... less the candidates that word 1 of the entry says no reflected ray of the block can be accepted at: the mirror the ray
+              // starts on, whose test finds a far root of 0 up to rounding (rt_block.h: rt_self_clear).  Scalar work only.  (The word's own
+              // load, not one 16-byte load for both words: measured the same, docs/EVIDENCE.md.)
+              uint32_t sn = rt_entry_second_node<W1>(L);
+#ifdef RT_TESTING
+              if (L.no_second_node) sn = 0u;                // test build (RT_NO_SECOND_NODE): the whole set is walked
+              if ((sn & (RT_SN_SELF0 | RT_SN_SELF1)) && L.uniform_waves != nullptr && __builtin_ctzll(__ballot(true)) == (int)lane) atomicAdd(L.uniform_waves + 3, 1ull);
+#endif
+              if (sn & RT_SN_SELF0) m &= ~(1u << (fb & 255u));
+              if (sn & RT_SN_SELF1) m &= ~(1u << ((fb >> 8) & 255u));
               while (m) {
                 const uint32_t i = (uint32_t)__builtin_ctz(m);
                 m &= m - 1u;

@@ -98,6 +98,19 @@ extern "C" int rt_test_first_bounce_waves(int device, unsigned long long *out_wa
   HIP_TRY(hipMemset(D.d_counters + 5, 0, sizeof *out_waves));
   return RT_OK;
 }
+// ... and how many of those waves left a candidate out of their walk, as the second-node bits of their entry allow (rt_block.h:
+// rt_second_node_bits); a counter of its own, read and cleared the same way
+extern "C" int rt_test_second_node_waves(int device, unsigned long long *out_waves) {
+  if (!out_waves) return fail(RT_ERR_INVALID, "rt_test_second_node_waves: NULL argument");
+  int rc = ensure_device(device);
+  if (rc) return rc;
+  device_state &D = G.dev[device];
+  HIP_TRY(hipSetDevice(D.hip_id));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out_waves, D.d_counters + 6, sizeof *out_waves, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemset(D.d_counters + 6, 0, sizeof *out_waves));
+  return RT_OK;
+}
 #endif
 
 extern "C" int rt_render_batch_device(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *tiles, uint32_t n_frames, void *d_out,
@@ -226,7 +239,7 @@ int render_supersampled(rt_scene_dev *s, uint32_t k, uint32_t w, uint32_t h, con
 // The test build's switches of a colour launch, read at ONE place.  The product build reads no environment variable: every switch is off.
 struct test_switches {
   bool no_grid, no_bounce; unsigned lds_pad; long count_wait_us;                 // once per process (A/B runs)
-  bool no_fixup, mark_all, exact_all, mark_stripes, no_uniform, no_cells, no_first_bounce;      // per call: tests set these between calls
+  bool no_fixup, mark_all, exact_all, mark_stripes, no_uniform, no_cells, no_first_bounce, no_second_node;      // per call: tests set these between calls
   double flag_scale;                                                             // (RT_FLAG_SCALE; 1: not set)
   bool uncached_marks;                   // a switch that changes what is marked or re-traced is on - nothing is cached then
 };
@@ -241,6 +254,7 @@ test_switches read_test_switches() {
   t.no_uniform = RT_TEST_ENV("RT_NO_UNIFORM_BLOCKS") != nullptr;                // every wave on the general path (rt_kernel.hip: trace_pixel, UNI)
   t.no_cells = RT_TEST_ENV("RT_NO_CHECKER_CELLS") != nullptr;                   // the table's checker cells are ignored (rt_kernel.hip: trace_pixel, one_cell)
   t.no_first_bounce = RT_TEST_ENV("RT_NO_FIRST_BOUNCE") != nullptr;             // the table's first-bounce sets are ignored (rt_kernel_trace.h: the node after the primary)
+  t.no_second_node = RT_TEST_ENV("RT_NO_SECOND_NODE") != nullptr;               // the table's second-node bits are ignored (rt_kernel_trace.h: the first-bounce walk)
   const char *fs = RT_TEST_ENV("RT_FLAG_SCALE");                                // a wider boundary band, to exercise the second launch
   t.flag_scale = fs ? atof(fs) : 1.0;
   t.uncached_marks = fs || t.mark_all || t.exact_all || t.no_fixup;
@@ -358,6 +372,7 @@ int fill_launch(const colour_call &c, bool strict_main, uint32_t stars_seed, voi
   L.uniform_waves = c.D.d_counters + 3;
   L.no_cells = c.t.no_cells ? 1u : 0u;
   L.no_first_bounce = c.t.no_first_bounce ? 1u : 0u;
+  L.no_second_node = (c.t.no_second_node || c.t.no_first_bounce) ? 1u : 0u;
 #endif
   return RT_OK;
 }

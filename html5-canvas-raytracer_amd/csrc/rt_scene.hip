@@ -47,6 +47,7 @@ uint32_t sky_part_of(uint32_t flags) { return (flags & RT_FLAG_NO_SKY) ? 1u : ((
 //   candidates: the block's primary candidates
 //   checker cells: which 8-pixel columns of a one-candidate block lie inside one cell of that sphere's checker (rt_block.h)
 //   first-bounce sets: which spheres the rays reflected at a block's primary hits can meet (rt_block.h)
+//   second node: which of a stating block's mirrors its reflected rays cannot meet again, and whether they meet nothing at all (rt_block.h)
 //   (a table of nothing but sky runs is read by workgroups that store a constant: neither masks nor candidates)
 table_choice choose_table(const rt_scene_dev *s, uint32_t flags, uint32_t uses_before) {
   static const bool no_order = RT_TEST_ENV("RT_NO_DISPATCH_ORDER") != nullptr;    // A/B switches (test build): the grid's own order,
@@ -65,6 +66,9 @@ table_choice choose_table(const rt_scene_dev *s, uint32_t flags, uint32_t uses_b
   // in a scene whose enclosing sphere - outside the loops and the statement - spawns no reflected ray of its own (rt_tables.cpp: make_table_params)
   c.first_bounce = c.name_candidates && !s->refract && s->cull_in_lds && s->hd.segs >= 2u &&
                    (s->enclosing == ~0u || s->host_objects[s->enclosing].albedo[3] <= 0.0);
+  // ... and beside them what the node after the primary may skip (rt_block.h: rt_second_node_bits), read by the same kernels
+  // (always beside the sets in a product launch: the field of its own in the table cache's key differs only through rt_test_launch_table's flags)
+  c.second_node = c.first_bounce ? 1 : 0;
   return c;
 }
 
@@ -687,7 +691,7 @@ bool build_table(rt_scene_dev *s, int found, hipStream_t stream, pinned_ring::sl
   std::vector<rt_ball> balls;
   std::vector<rt_cost_rect> rects;
   if (make_table_params(&s->hd, s->host_objects.data(), s->host_cull, s->tile_weight, k.w, k.h, k.ss, &k.tiles, g.tiles_x, g.rb_per_tile, g.proj_w, g.proj_h, g.proj_d, e.ranked,
-                        e.sky, s->enclosing, e.masks, e.cands, e.cells, e.first_bounce, s->lights, &P, &balls, &rects)) {
+                        e.sky, s->enclosing, e.masks, e.cands, e.cells, e.first_bounce, e.second_node, s->lights, &P, &balls, &rects)) {
     fail(RT_ERR_INVALID, "a launch of %llu workgroups is beyond the launch table", (unsigned long long)g.tiles_x * k.tiles.n_tiles * g.rb_per_tile);
     return false;
   }
@@ -762,7 +766,7 @@ int dispatch_order(rt_scene_dev *s, const frame_kind &kind, const table_choice &
   int found = -1;
   for (size_t i = 0; i < s->orders.size(); i++) {
     const rt_scene_dev::order_entry &e = s->orders[i];
-    if (e.kind == kind && e.ranked == c.ranked && e.sky == c.mark_sky && e.masks == c.shadow_masks && e.cands == c.name_candidates && e.cells == c.checker_cells && e.first_bounce == c.first_bounce) { found = (int)i; break; }
+    if (e.kind == kind && e.ranked == c.ranked && e.sky == c.mark_sky && e.masks == c.shadow_masks && e.cands == c.name_candidates && e.cells == c.checker_cells && e.first_bounce == c.first_bounce && e.second_node == c.second_node) { found = (int)i; break; }
   }
   if (found >= 0 && s->orders[found].cam_gen == s->cam_gen) {
     rt_scene_dev::order_entry &e = s->orders[found];
@@ -791,7 +795,7 @@ int dispatch_order(rt_scene_dev *s, const frame_kind &kind, const table_choice &
     rt_scene_dev::order_entry &e = s->orders[found];
     e = rt_scene_dev::order_entry();                     // (an evicted table's memory and event go with it)
     e.kind = kind;
-    e.ranked = c.ranked; e.sky = c.mark_sky; e.masks = c.shadow_masks; e.cands = c.name_candidates; e.cells = c.checker_cells; e.first_bounce = c.first_bounce;
+    e.ranked = c.ranked; e.sky = c.mark_sky; e.masks = c.shadow_masks; e.cands = c.name_candidates; e.cells = c.checker_cells; e.first_bounce = c.first_bounce; e.second_node = c.second_node;
     e.known = known_word(s, RT_KNOWN_WORDS + (size_t)found);
     if (e.known) *e.known = 0ull;                        // (a table evicted from this slot may have published its count for the same camera)
   }
@@ -859,7 +863,7 @@ extern "C" int rt_test_launch_table(rt_scene_dev *s, uint32_t w, uint32_t h, con
   const uint32_t ss = s->hd.supersample;
   if (ss > 2u) return fail(RT_ERR_INVALID, "supersample 3 and 4 launch on the sample grid");
   const frame_kind kind = {w, h, ss, *tiles, (ranked & 8) ? 1u : ((ranked & 16) ? 2u : 0u)};
-  const table_choice c = {(ranked & 1) != 0, (ranked & 2) != 0, (ranked & 4) != 0, (ranked & 4) != 0, (ranked & 32) ? ((ranked & 64) ? 2 : 1) : 0, (ranked & 128) != 0};
+  const table_choice c = {(ranked & 1) != 0, (ranked & 2) != 0, (ranked & 4) != 0, (ranked & 4) != 0, (ranked & 32) ? ((ranked & 64) ? 2 : 1) : 0, (ranked & 128) != 0, (ranked & 256) ? 1 : 0};
   std::lock_guard<std::mutex> lk(s->launch_mu);
   HIP_TRY(s->sync.before_launch(stream, s->cam_gen));
   const int oi = dispatch_order(s, kind, c, stream);

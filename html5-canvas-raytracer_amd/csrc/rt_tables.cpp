@@ -197,7 +197,7 @@ void scene_tile_weights(const rt_scene_header *hd, const rt_sphere *ob, std::vec
 
 // ------------------------------------------------------------------------------------ launch table (host side)
 // The product kernel runs on a FLAT grid and reads, per workgroup, one 16-byte entry {tile_x | rows_valid << 11 | first frame row <<
-// 15, first row in the output band | (run - 1) << 24 | sky << 31, shadow masks, primary candidates} (rt_kernel.hip: rt_pixel_of) -
+// 15, first row in the output band | (run - 1) << 24 | sky << 31 (or | second-node bits << 24), shadow masks, primary candidates} (rt_kernel.hip: rt_pixel_of) -
 // the tile / row-block arithmetic of the plain grid done once, plus what can be told about a block in advance (rt_block.h: sky
 // blocks, shadow masks, candidates).  That also decides the ORDER in which the hardware hands the blocks out.  In grid order a frame
 // ends on whatever lies at the bottom right - for the reference's scenes the floor and the sphere that both reflects and refracts,
@@ -219,7 +219,7 @@ bool table_is_ranked(int ranked, uint64_t n_blocks) { return ranked && (n_blocks
 
 int make_table_params(const rt_scene_header *hd, const rt_sphere *ob, const std::vector<rt_geom> &cull, const std::vector<uint32_t> &weight,
                       uint32_t w, uint32_t h, uint32_t ss, const rt_tiles *tiles, uint32_t tiles_x, uint32_t rb_per_tile, double proj_w, double proj_h, double proj_d,
-                      int ranked, bool mark_sky, uint32_t sky_sphere, bool shadow_masks, bool name_candidates, int checker_cells, bool first_bounce, const double lights[][3],
+                      int ranked, bool mark_sky, uint32_t sky_sphere, bool shadow_masks, bool name_candidates, int checker_cells, bool first_bounce, int second_node, const double lights[][3],
                       rt_table_params *P, std::vector<rt_ball> *balls, std::vector<rt_cost_rect> *rects) {
   const uint32_t ny = tiles->n_tiles * rb_per_tile;
   const uint64_t n64 = (uint64_t)tiles_x * ny;
@@ -263,7 +263,9 @@ int make_table_params(const rt_scene_header *hd, const rt_sphere *ob, const std:
   P->flags = (mark_sky ? RT_TABLE_SKY : 0u) | (want_masks ? RT_TABLE_MASKS : 0u) | (want_cands ? RT_TABLE_CANDS : 0u) | (n_loop > 16u ? RT_TABLE_WIDE : 0u) |
              (table_is_ranked(ranked, n64) ? RT_TABLE_RANK : 0u) | ((geometry && (mark_sky || want_masks || want_cands || want_bounce)) ? RT_TABLE_GEOMETRY : 0u) |
              ((geometry && want_bounce) ? RT_TABLE_BOUNCE : 0u) | ((geometry && want_cells) ? RT_TABLE_CELLS : 0u) |
-             ((geometry && want_cells && checker_cells >= 2) ? RT_TABLE_AXES : 0u) | ((geometry && want_first_bounce) ? RT_TABLE_FIRST_BOUNCE : 0u);
+             ((geometry && want_cells && checker_cells >= 2) ? RT_TABLE_AXES : 0u) | ((geometry && want_first_bounce) ? RT_TABLE_FIRST_BOUNCE : 0u) |
+             ((geometry && want_first_bounce && second_node) ? RT_TABLE_SECOND_NODE : 0u) |
+             ((geometry && want_first_bounce && second_node >= 2 && want_masks) ? RT_TABLE_SECOND_DARK : 0u);      // (rides on the sets: nothing to say without them)
   P->cost_bins = 1u;
   P->n_lights = want_masks ? hd->n_lights : 0u;
   for (uint32_t k = 0; k < P->n_lights; k++) for (int c = 0; c < 3; c++) P->lights[k][c] = lights[k][c];
@@ -336,21 +338,21 @@ int make_table_params(const rt_scene_header *hd, const rt_sphere *ob, const std:
 std::vector<uint32_t> build_launch_table(const rt_scene_header *hd, const rt_sphere *ob, const std::vector<rt_geom> &cull, const std::vector<uint32_t> &weight,
                                          uint32_t w, uint32_t h, uint32_t ss,
                                          const rt_tiles *tiles, uint32_t tiles_x, uint32_t rb_per_tile, double proj_w, double proj_h, double proj_d, int ranked,
-                                         bool mark_sky, uint32_t sky_sphere, bool shadow_masks, bool name_candidates, int checker_cells, bool first_bounce, const double lights[][3], uint32_t *n_entries, uint32_t sky_part) {
+                                         bool mark_sky, uint32_t sky_sphere, bool shadow_masks, bool name_candidates, int checker_cells, bool first_bounce, int second_node, const double lights[][3], uint32_t *n_entries, uint32_t sky_part) {
   if (n_entries) *n_entries = 0;
   rt_table_params P;
   std::vector<rt_ball> balls;
   std::vector<rt_cost_rect> rects;
-  if (make_table_params(hd, ob, cull, weight, w, h, ss, tiles, tiles_x, rb_per_tile, proj_w, proj_h, proj_d, ranked, mark_sky, sky_sphere, shadow_masks, name_candidates, checker_cells, first_bounce, lights,
+  if (make_table_params(hd, ob, cull, weight, w, h, ss, tiles, tiles_x, rb_per_tile, proj_w, proj_h, proj_d, ranked, mark_sky, sky_sphere, shadow_masks, name_candidates, checker_cells, first_bounce, second_node, lights,
                         &P, &balls, &rects)) return {};
   const uint32_t ny = P.ny, n = tiles_x * ny;
   const bool rank = (P.flags & RT_TABLE_RANK) != 0u;
-  std::vector<uint32_t> touched(n), cands(n), smask(n), cost(n, 1u);
+  std::vector<uint32_t> touched(n), cands(n), smask(n), second(n), cost(n, 1u);
   for (uint32_t y = 0; y < ny; y++)
     for (uint32_t x = 0; x < tiles_x; x++) {
       const size_t at = (size_t)y * tiles_x + x;
       uint32_t extra = 0u;
-      rt_block_statement(P, balls.data(), x, y, &touched[at], &cands[at], &smask[at], &extra);
+      rt_block_statement(P, balls.data(), x, y, &touched[at], &cands[at], &smask[at], &extra, &second[at]);
       if (rank) { const uint32_t c = rt_block_cost(P, rects.data(), x, y) + extra; cost[at] = c < RT_COST_MAX ? c : RT_COST_MAX; }
     }
   // The entries: one per workgroup.  A block that shows a sphere is an entry of its own; consecutive sky blocks of one row
@@ -394,7 +396,7 @@ std::vector<uint32_t> build_launch_table(const rt_scene_header *hd, const rt_sph
     const size_t at = (size_t)(b & 7u) * n8 + (b >> 3);
     const size_t blk = (size_t)it.y * tiles_x + it.x;
     table[RT_ENTRY_WORDS * at] = w0;
-    table[RT_ENTRY_WORDS * at + 1u] = w1 | (it.run ? (0x80000000u | ((it.run - 1u) << 24)) : 0u);
+    table[RT_ENTRY_WORDS * at + 1u] = w1 | (it.run ? (0x80000000u | ((it.run - 1u) << 24)) : ((words23 && (P.flags & RT_TABLE_CANDS)) ? second[blk] : 0u));
     table[RT_ENTRY_WORDS * at + 2u] = (words23 && (P.flags & RT_TABLE_MASKS)) ? smask[blk] : 0xffffffffu;
     table[RT_ENTRY_WORDS * at + 3u] = (words23 && (P.flags & RT_TABLE_CANDS)) ? cands[blk] : 0u;
   }

@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(WG_ROWS) rt_table_rows(const rt_table_dev T, u
   for (uint32_t c = threadIdx.x; c < bins; c += WG_ROWS) l_hist[c] = 0u;
   const uint32_t sub = threadIdx.x % SUB;
   for (uint32_t x = threadIdx.x / SUB; x < tiles_x; x += WG_ROWS / SUB) {
-    uint32_t touched = 1u, cands = 0u, smask = 0xffffffffu, extra = 0u;
+    uint32_t touched = 1u, cands = 0u, smask = 0xffffffffu, extra = 0u, second = 0u;
     if (P.flags & RT_TABLE_GEOMETRY) {
       const rt_cone K = rt_block_cone(P, x, y);
       uint64_t cand[4] = {0ull, 0ull, 0ull, 0ull};
@@ -138,12 +138,12 @@ __global__ void __launch_bounds__(WG_ROWS) rt_table_rows(const rt_table_dev T, u
           }
         } else
         if (want_masks || want_fb) {
-          uint32_t mk[2] = {0u, 0u}, none = 0u, fb_set = 0u, fb_none = 0u;
+          uint32_t mk[2] = {0u, 0u}, none = 0u, fb_set = 0u, fb_none = 0u, fb_keep = 0u;
           for (uint32_t ci = sub; ci < P.n_balls; ci += SUB)
             if ((cand[ci >> 6] >> (ci & 63u)) & 1ull) {
               rt_patch pt;
               const bool patch_ok = rt_cand_patch(P, K, balls[ci], &pt);
-              if (want_fb && !rt_cand_first_bounce(P, K, balls, ci, patch_ok, pt, &fb_set)) fb_none = 1u;
+              if (want_fb && !rt_cand_first_bounce(P, K, balls, ci, patch_ok, pt, &fb_set, &fb_keep)) fb_none = 1u;
               if (want_masks) {
                 if (!patch_ok) none = 1u; else rt_cand_masks(P, pt, balls, ci, mk);
                 if (mk[0] == 0xffffu && mk[1] == 0xffffu) break;       // (as on the host: the word is 0xffffffff whatever follows; never with a first-bounce set's 13 spheres)
@@ -152,6 +152,10 @@ __global__ void __launch_bounds__(WG_ROWS) rt_table_rows(const rt_table_dev T, u
           if (want_fb) {
             fb_none = group_or<SUB>(fb_none); fb_set = group_or<SUB>(fb_set);
             if (sub == 0u) cands |= rt_first_bounce_word(P, cands, !fb_none, fb_set);
+            if (P.flags & RT_TABLE_SECOND_NODE) {         // (group-uniform) word 1's second-node bits: they ride above the block's cost until rt_table_emit
+              fb_keep = group_or<SUB>(fb_keep);
+              if (sub == 0u) second = rt_second_node_bits(P, cands, fb_keep);
+            }
           }
           if (want_masks) {
             none = group_or<SUB>(none);
@@ -165,7 +169,7 @@ __global__ void __launch_bounds__(WG_ROWS) rt_table_rows(const rt_table_dev T, u
     uint32_t cost = rank ? rt_block_cost(P, rects, x, y) + extra : 1u;
     cost = cost < RT_COST_MAX ? cost : RT_COST_MAX;
     const size_t at = (size_t)y * tiles_x + x;
-    T.blk[3u * at] = cost; T.blk[3u * at + 1u] = smask; T.blk[3u * at + 2u] = cands;
+    T.blk[3u * at] = cost | second; T.blk[3u * at + 1u] = smask; T.blk[3u * at + 2u] = cands;      // (cost <= RT_COST_MAX: bits 0..9; second: bits 24..28)
     l_touched[x] = (!sky || touched) ? 1u : 0u;
     // every slot of the table starts as zero (rt_table_emit fills the entries in; a trace workgroup that reads a zero slot has no rows
     // and leaves): block `at` clears slot `at`, the first blocks also the up to 7 slots behind the last block
@@ -176,7 +180,7 @@ __global__ void __launch_bounds__(WG_ROWS) rt_table_rows(const rt_table_dev T, u
   __syncthreads();
   for (uint32_t x = threadIdx.x; x < tiles_x; x += WG_ROWS) {
     uint32_t key = 0u, run = 0u;
-    if (l_touched[x]) key = 1u + (bins - T.blk[3u * ((size_t)y * tiles_x + x)]);          // dearest first: bin 0 = the largest cost
+    if (l_touched[x]) key = 1u + (bins - (T.blk[3u * ((size_t)y * tiles_x + x)] & RT_COST_MAX));          // dearest first: bin 0 = the largest cost
     else if (x % RT_SKY_RUN_MAX == 0u || l_touched[x - 1u]) {                            // a sky run starts here
       run = 1u;
       while (x + run < tiles_x && (x + run) % RT_SKY_RUN_MAX != 0u && !l_touched[x + run]) run++;
@@ -269,7 +273,7 @@ __global__ void __launch_bounds__(WG) rt_table_emit(const rt_table_dev T) {
   const bool words23 = (P.flags & RT_TABLE_GEOMETRY) != 0u;
   uint4 e;
   e.x = w0;
-  e.y = w1 | (run ? (0x80000000u | ((run - 1u) << 24)) : 0u);
+  e.y = w1 | (run ? (0x80000000u | ((run - 1u) << 24)) : ((words23 && (P.flags & RT_TABLE_CANDS)) ? T.blk[3u * (size_t)at] & (RT_SN_MASK << RT_SN_SHIFT) : 0u));
   e.z = (words23 && (P.flags & RT_TABLE_MASKS)) ? T.blk[3u * (size_t)at + 1u] : 0xffffffffu;
   e.w = (words23 && (P.flags & RT_TABLE_CANDS)) ? T.blk[3u * (size_t)at + 2u] : 0u;
   ((uint4 *)T.entries)[(size_t)(b & 7u) * n8 + (b >> 3)] = e;
