@@ -8,6 +8,7 @@
 // entry point fails with RT_ERR_DEVICE.
 
 #include "rt_api_internal.h"
+#include "rt_wide.h"          // the test build's probe of the 16-byte frame stores (rt_test_wide_stores)
 
 // ------------------------------------------------------------------------------------ state
 namespace rt_api {
@@ -255,6 +256,29 @@ extern "C" int rt_test_trace_variant(uint32_t facts, uint32_t *out_bits, int *ou
                                                                   (facts & 32u) != 0, (facts & 64u) != 0, (facts & 128u) != 0);
   *out_bits = rt_variant_bits(v);
   *out_has_kernel = (v.strict ? rt_kernel_trace_strict : rt_kernel_trace_fast)(v) != nullptr;
+  return RT_OK;
+}
+
+// Host-logic probe (test build, no GPU): how a launch with these facts stores the frame (rt_device.h: rt_wide_stores_of) - bit 0 strict,
+// 1 rgb24, 2 scatter of `facts`; out_bytes: what the launch writes, all frames - as RT_WIDE_* flags, 0: one 4-byte store per pixel.
+extern "C" int rt_test_wide_rule(uint32_t facts, uint32_t w, uint64_t out_address, uint32_t n_frames, uint64_t frame_stride_words, uint64_t out_bytes, uint32_t *out_flags) {
+  if (!out_flags) return fail(RT_ERR_INVALID, "rt_test_wide_rule: NULL argument");
+  *out_flags = rt_wide_stores_of((facts & 1u) != 0, (facts & 2u) != 0, (facts & 4u) != 0, w, out_address, n_frames, frame_stride_words, out_bytes);
+  return RT_OK;
+}
+
+// Host-logic probe (test build, no GPU): the 16-byte stores of ONE launch-table entry (its words 0 and 1, as rt_scene_launch_table returns
+// them) of a frame `w` pixels wide, enumerated by the header the kernel's epilogue is written from (rt_wide.h: rt_wide_entry_stores):
+// out receives {wave of the entry, row in the call's output band, first pixel} per store, at most `cap` of them; *n_stores = how many
+// there are.
+extern "C" int rt_test_wide_stores(uint32_t e0, uint32_t e1, int ss2, uint32_t w, uint32_t *out, uint32_t cap, uint32_t *n_stores) {
+  if (!n_stores || (!out && cap)) return fail(RT_ERR_INVALID, "rt_test_wide_stores: NULL argument");
+  uint32_t n = 0;
+  rt_wide_entry_stores(e0, e1, ss2 != 0, w, [&](uint32_t wave, uint32_t lrow, uint32_t px) {
+    if (n < cap) { out[3u * n] = wave; out[3u * n + 1u] = lrow; out[3u * n + 2u] = px; }
+    n++;
+  });
+  *n_stores = n;
   return RT_OK;
 }
 #endif

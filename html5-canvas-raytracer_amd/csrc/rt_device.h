@@ -3,6 +3,7 @@
 #ifndef RT_DEVICE_H
 #define RT_DEVICE_H
 
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/rt_hip.h"
 
@@ -21,6 +22,30 @@
  * Asked in one place: rt_trace_variant_of, below. */
 static inline bool rt_one_wave_workgroups(bool strict, bool count, bool refract, bool scatter) {
   return !strict && !count && !refract && !scatter;
+}
+/* Which product launches store the frame 16 BYTES PER LANE (rt_wide.h; rt_kernel.hip, A10), and which of those stores are write-through:
+ * RGBA8 into the call's band (not RGB24 / compact, not the peer-store path), a width that is a multiple of four pixels, a 16-byte aligned
+ * `out`, and - a batch - a frame stride that is a multiple of four words.  Then every group of four pixels is wholly inside or outside the
+ * frame and every 16-byte store is aligned, in a band of tiles (rows of the band are w pixels apart) as in a whole frame.  0: the launch
+ * keeps one 4-byte store per pixel.  Decided once per launch (rt_launch.hip: product_launch) into rt_launch::wide_stores.
+ * Write-through (sc1) drops the line from L2 as it is stored instead of leaving the frame dirty for the end-of-kernel release; both the sky
+ * runs' whole-line stores and the traced blocks' stores take it (docs/EVIDENCE.md, first section: the three forms measured).
+ * `out_bytes`: what the launch writes, all frames.  Write-through pays while the frame would otherwise have stayed in the chip's 32 MB of
+ * L2 until the kernel ends (8 MB: +3.4 %, 33 MB: +2.9 %); a frame several times that size leaves L2 while the launch runs whatever the
+ * stores' flavour - 75 MB +0.8 %, 133 MB +0.1 %, inside the runs' ranges - and cfg5's 1 GiB frame LOSES 6.5 % with it: a launch that
+ * writes more than RT_WIDE_MAX_BYTES, twice the L2, takes the 16-byte stores plain (+0.2 .. +0.3 % at 75 MB, 133 MB and 1 GiB). */
+#define RT_WIDE_STORES 1u            /* the launch takes the 16-byte stores */
+#define RT_WIDE_THROUGH_SKY 2u       /* ... write-through for the sky runs */
+#define RT_WIDE_THROUGH_TRACED 4u    /* ... and for the traced blocks */
+#ifndef RT_WIDE_MAX_BYTES
+#define RT_WIDE_MAX_BYTES (64ull << 20)
+#endif
+static inline uint32_t rt_wide_stores_of(bool strict, bool rgb24, bool scatter, uint32_t w, uint64_t out_address, uint32_t n_frames, uint64_t frame_stride_words,
+                                         uint64_t out_bytes) {
+  if (strict || rgb24 || scatter || (w & 3u) != 0u || (out_address & 15u) != 0u) return 0u;
+  if (n_frames > 1u && (frame_stride_words & 3u) != 0u) return 0u;
+  if (out_bytes > RT_WIDE_MAX_BYTES) return RT_WIDE_STORES;
+  return RT_WIDE_STORES | RT_WIDE_THROUGH_SKY | RT_WIDE_THROUGH_TRACED;
 }
 /* WHICH kernel instantiation a launch runs, decided once per launch on the host: the LDS size, the scratch figure held against free
  * memory and the launch itself all take this value, and each build of rt_kernel.hip maps it to a kernel's address in ONE table
@@ -137,6 +162,9 @@ struct rt_launch {
   uint32_t compact;                  // RT_FLAG_COMPACT (with rgb24): block b of the launch is stored whole at out + b * block bytes (a compact band for a collective)
   uint32_t scatter;                  // rt_render_scatter_device: frame f goes to out_frames[f] (possibly another GPU's memory,
                                      // peer-mapped), its rows in FRAME order; `out` and frame_stride are unused
+  uint32_t wide_stores;              // RT_WIDE_* (rt_wide_stores_of above), or 0: one 4-byte store per pixel.  The product trace kernels' epilogue reads it from
+                                     // the kernarg segment at its one use (rt_cold_args).  (It lies in what was padding in front of the pointers below: no other
+                                     // field has moved and the record has kept its size - the strict kernels' device code is unchanged.)
   uint32_t *out_frames[RT_MAX_SCATTER];
   // Launch table of the product kernel (rt_scene.hip: dispatch_order): workgroup b of the flat grid renders the tile described by
   // entry b = {tile_x | rows_valid << 11 | first frame row << 15, first row in the output band}; the table build (rt_tables_gpu.hip) lists the tiles
@@ -196,6 +224,8 @@ struct rt_launch {
   uint32_t no_second_node;           // RT_NO_SECOND_NODE (and RT_NO_FIRST_BOUNCE): the kernel ignores the table's second-node bits (rt_block.h: rt_second_node_bits)
 #endif
 };
+static_assert(offsetof(rt_launch, wide_stores) == offsetof(rt_launch, scatter) + 4u && offsetof(rt_launch, out_frames) == offsetof(rt_launch, scatter) + 8u,
+              "rt_launch: wide_stores fills the four bytes of padding behind scatter");
 
 // Boundary test of the samplers (product kernels): a sampler coordinate x = u * frequency is "on a boundary" when it lies within
 // RT_FLAG_T1 * (the scene's largest frequency) of an integer: 1e-9 for the reference's checker (5000 per unit u, main.js:129), three

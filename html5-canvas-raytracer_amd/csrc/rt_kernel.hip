@@ -56,6 +56,7 @@
 
 #include "rt_device.h"
 #include "rt_block.h"      // the launch table's words (RT_CAND_MASK, RT_CELL_SHIFT)
+#include "rt_wide.h"       // which lane stores which four pixels (the product kernels' 16-byte frame stores)
 
 #ifndef RT_STRICT
 #define RT_STRICT 0
@@ -82,6 +83,22 @@ namespace {
 #include "rt_kernel_entry.h"     // rt_pixel_of, rt_entry_*, rt_cold_args, rt_mark_append
 #include "rt_kernel_tables.h"    // rt_load_*, rt_mtl_*, rt_tex_desc, frame, park
 #include "rt_kernel_trace.h"     // trace_pixel
+
+#if !RT_STRICT
+// The 16-byte frame stores of the product kernels (rt_wide.h says which lane stores what; rt_device.h: rt_wide_stores_of which launches
+// take them).  `through`: write-through (sc1) - the line leaves L2 with the store instead of staying dirty until the end-of-kernel
+// release writes the frame back while no SIMD has work.  A 16-byte sc1 store costs what a plain one does; a 4-byte one is a fabric
+// write of its own, which is why the store's flavour comes with its shape.  (The asm ends in s_nop 1: the instruction behind it may
+// not overwrite the data registers before the store has read them.)
+typedef uint32_t __attribute__((ext_vector_type(4))) rt_px4;
+__device__ __forceinline__ void rt_store16(uint32_t *p, rt_px4 v, bool through) {
+  if (through) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
+  else *(rt_px4 *)p = v;
+}
+// the value lane + N of this lane's 16-lane row holds (DPP row_shl:N)
+template <int N>
+__device__ __forceinline__ uint32_t rt_row_down(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x100 + N, 0xf, 0xf, true); }
+#endif
 
 // W1: one-wave workgroups (rt_pixel_of), for the reflection-only variants.  A workgroup's waves are placed together: a 4-wave
 // workgroup starts when its CU has room for all four, and where the waves of a launch differ in length freed slots wait for their
@@ -292,14 +309,23 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
   uint32_t tid2 = threadIdx.x;
   asm volatile("" : "+v"(tid2));                       // opaque: recompute the pixel instead of keeping it live (see rt_pixel_of)
   const rt_pixel P1 = rt_pixel_of<SS2, W1>(L, tid2);
+#if !RT_STRICT
+  const uint32_t wide = rt_cold_args()->wide_stores;   // RT_WIDE_* (the 16-byte stores below) ...
+  // ... used here with the launch-record fields every arm of the epilogue asks for first - scatter, rgb24, the width, `out` and the frame
+  // stride - so that all their loads go out beside the entry's and its one wait covers them (rt_head_batch says why): the parent's
+  // epilogue stood through four dependent scalar waits on its way to its stores.  (Loaded behind the trace: none is held across it.)
+  asm volatile("" :: "s"(wide), "s"(L.scatter), "s"(L.rgb24), "s"(L.w), "s"(L.out), "s"(L.frame_stride));
+#endif
   const uint32_t frame_i = blockIdx.z;
   const bool valid = P1.valid;
   const uint32_t r8 = to_byte(rgb[0]), g8 = to_byte(rgb[1]), b8 = to_byte(rgb[2]);
   // scatter: every frame of the batch has its own destination (the frame buffer of the rank that owns it, peer-mapped
   // over xGMI) and rows go to their place in the FRAME, so nothing is left to exchange or to de-interleave; a tile row
   // is whole 128-byte lines written by one workgroup, which is what a remote store wants
+#if RT_STRICT
   uint32_t *__restrict__ out = L.scatter ? L.out_frames[frame_i] : L.out + (size_t)frame_i * L.frame_stride;
   const uint32_t orow = L.scatter ? P1.frow : P1.lrow;
+#endif
   uint32_t rgbw;                                       // this lane's pixel as 0x00BBGGRR
   if (!SS2) rgbw = r8 | (g8 << 8) | (b8 << 16);
   else {
@@ -316,6 +342,51 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
   const uint32_t n_run = 1u;
 #else
   const uint32_t n_run = P1.sky ? P1.run : 1u;
+#endif
+#if defined(RT_ABLATE_STORE) && !RT_STRICT
+  // timing experiment only (profiles/ab_build.sh <name> "-DRT_ABLATE_STORE" product, or "-DRT_ABLATE_STORE=2"): what a launch costs
+  // WITHOUT its RGBA8 frame stores (2: without the sky runs' stores only).  The pixel is computed to its last instruction (the empty asm
+  // uses it), and the stores stand behind a scalar test of a launch-record value that no launch has (grid z is below 65536) and the
+  // compiler cannot know: none executes, none is removed.  No Makefile target defines it.  (Not tied to RT_TESTING, like
+  // RT_ABLATE_QAMP: the test build's trace kernels run 23x the product's time, and a ceiling is priced on the product's kernels.)
+  asm volatile("" :: "v"(rgbw));
+  const bool store_off = ((RT_ABLATE_STORE + 0) == 2 ? P1.sky : true) && rt_cold_args()->n_frames != ~0u;
+#endif
+#if !RT_STRICT
+  // 16 bytes per storing lane (rt_wide.h), where the host found every group of four pixels whole and aligned (rt_device.h:
+  // rt_wide_stores_of) - such a launch is RGBA8 into the call's band, so this arm asks for neither rgb24 nor scatter.  The flags come
+  // from the kernarg segment (rt_cold_args: no scalar register is held across the trace), read above beside the entry's load, whose
+  // wait covers them and the arm's three launch-record fields.  Every other launch: the arms below, as they were.
+  if (wide != 0u) {
+    const uint32_t lane2 = tid2 & 63u, wave2 = rt_wave_of<W1>(tid2), pix = rgbw | 0xff000000u;
+    const uint32_t px0 = P1.px & ~(RT_TILE_W - 1u);                                // the entry's first pixel: a block starts at a multiple of 32
+    uint32_t *const band = L.out + (size_t)frame_i * L.frame_stride + (size_t)(P1.lrow - P1.trow) * L.w;     // ... and its first row in the call's output band
+#if defined(RT_ABLATE_STORE)
+    if (store_off) {} else
+#endif
+    if (P1.sky) {
+      // a sky run: block t of the run is ONE instruction of wave t % 4 - eight whole 128-byte lines
+      const rt_wide_piece wp = rt_wide_sky(lane2);
+      const rt_px4 v = {pix, pix, pix, pix};
+      for (uint32_t t = wave2; t < n_run; t += 4u) {
+        const uint32_t px = px0 + t * RT_TILE_W + wp.col;
+        if (wp.row < P1.rows_valid && px < L.w) rt_store16(band + (size_t)wp.row * L.w + px, v, (wide & RT_WIDE_THROUGH_SKY) != 0u);
+      }
+    } else {
+      // a traced block: the wave's piece of a row is 8 pixels = two stores; a group's first lane collects the other three
+      // pixels from its own 16-lane row
+      const rt_wide_piece wp = rt_wide_traced(SS2, wave2, lane2);
+      const rt_px4 v = {pix, rt_row_down<SS2 ? 4 : 1>(pix), rt_row_down<SS2 ? 8 : 2>(pix), rt_row_down<SS2 ? 12 : 3>(pix)};
+      const uint32_t px = px0 + wp.col;
+      if (wp.stores && wp.row < P1.rows_valid && px < L.w) rt_store16(band + (size_t)wp.row * L.w + px, v, (wide & RT_WIDE_THROUGH_TRACED) != 0u);
+    }
+  } else
+#endif
+  {
+#if !RT_STRICT
+  // (the product build asks for the destination here, behind the arm above, which has its own and never reads `scatter`)
+  uint32_t *__restrict__ out = L.scatter ? L.out_frames[frame_i] : L.out + (size_t)frame_i * L.frame_stride;
+  const uint32_t orow = L.scatter ? P1.frow : P1.lrow;
 #endif
   if (!W1 && !L.rgb24 && L.scatter && !SS2) {          // workgroup-uniform (the host launches the four-wave variant for scatter stores)
     // Peer stores want whole lines: a wave's 8x8 block is eight 32-byte pieces, one per row, and memory on the far side
@@ -341,6 +412,9 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
     }
   } else if (!L.rgb24) {                               // wave-uniform
     uint32_t pxq = P1.px;
+#if defined(RT_ABLATE_STORE) && !RT_STRICT
+    if (store_off) {} else
+#endif
     for (uint32_t t = 0; t < n_run; t++, pxq += RT_TILE_W) {
 #if RT_STRICT
       const bool validq = valid;
@@ -373,6 +447,7 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
       if (L.compact) out[(size_t)rt_entry_index<W1>() * (RT_TILE_W * 3u / 4u * (SS2 ? 2u : RT_TILE_H)) + P1.trow * (RT_TILE_W * 3u / 4u) + ((rt_wave_of<W1>(tid2) * 8u) >> 2) * 3u + j] = word;
       else out[((P1.lrow * L.w + x0) >> 2) * 3u + j] = word;
     }
+  }
   }
 
 #if defined(RT_WAVE_LOG) && !RT_STRICT

@@ -239,7 +239,8 @@ int render_supersampled(rt_scene_dev *s, uint32_t k, uint32_t w, uint32_t h, con
 // The test build's switches of a colour launch, read at ONE place.  The product build reads no environment variable: every switch is off.
 struct test_switches {
   bool no_grid, no_bounce; unsigned lds_pad; long count_wait_us;                 // once per process (A/B runs)
-  bool no_fixup, mark_all, exact_all, mark_stripes, no_uniform, no_cells, no_first_bounce, no_second_node;      // per call: tests set these between calls
+  bool no_fixup, mark_all, exact_all, mark_stripes, no_uniform, no_cells, no_first_bounce, no_second_node, no_wide;      // per call: tests set these between calls
+  int wide_form;                                                                 // (RT_WIDE_FORM; 0: not set)
   double flag_scale;                                                             // (RT_FLAG_SCALE; 1: not set)
   bool uncached_marks;                   // a switch that changes what is marked or re-traced is on - nothing is cached then
 };
@@ -255,6 +256,9 @@ test_switches read_test_switches() {
   t.no_cells = RT_TEST_ENV("RT_NO_CHECKER_CELLS") != nullptr;                   // the table's checker cells are ignored (rt_kernel.hip: trace_pixel, one_cell)
   t.no_first_bounce = RT_TEST_ENV("RT_NO_FIRST_BOUNCE") != nullptr;             // the table's first-bounce sets are ignored (rt_kernel_trace.h: the node after the primary)
   t.no_second_node = RT_TEST_ENV("RT_NO_SECOND_NODE") != nullptr;               // the table's second-node bits are ignored (rt_kernel_trace.h: the first-bounce walk)
+  t.no_wide = RT_TEST_ENV("RT_NO_WIDE_STORES") != nullptr;                      // every launch keeps one 4-byte store per pixel (rt_kernel.hip, A10)
+  // RT_WIDE_FORM (A/B runs): 1 - the 16-byte stores plain, 2 - write-through everywhere (the product's form), 3 - write-through for the sky runs only
+  t.wide_form = RT_TEST_ENV("RT_WIDE_FORM") ? atoi(RT_TEST_ENV("RT_WIDE_FORM")) : 0;
   const char *fs = RT_TEST_ENV("RT_FLAG_SCALE");                                // a wider boundary band, to exercise the second launch
   t.flag_scale = fs ? atof(fs) : 1.0;
   t.uncached_marks = fs || t.mark_all || t.exact_all || t.no_fixup;
@@ -503,6 +507,10 @@ int product_launch(const colour_call &c, rt_launch &L, marks_guard &temp_marks, 
     o.strict_rendered = true;
     return strict_launch(c, S, false);
   }
+  // how the trace stores the frame (rt_device.h: rt_wide_stores_of): 16 bytes per lane, write-through, where the launch's shape allows it
+  const uint64_t out_bytes = (uint64_t)c.tiles->n_tiles * c.tiles->tile_rows * c.w * 4u * c.n_frames;
+  L.wide_stores = c.t.no_wide ? 0u : rt_wide_stores_of(false, L.rgb24 != 0u, L.scatter != 0u, c.w, (uint64_t)(uintptr_t)L.out, c.n_frames, L.frame_stride, c.t.wide_form ? 0u : out_bytes);
+  if (L.wide_stores && c.t.wide_form) L.wide_stores = RT_WIDE_STORES | (c.t.wide_form == 2 ? RT_WIDE_THROUGH_SKY | RT_WIDE_THROUGH_TRACED : (c.t.wide_form == 3 ? RT_WIDE_THROUGH_SKY : 0u));
   const rt_trace_variant v = rt_trace_variant_of(false, false, s->refract, c.count, c.ss2, L.cull_in_lds != 0u, L.scatter != 0u, L.four_waves != 0u);
   if (int rc = guard_kernel_scratch(c.D, c.stream, v, (uint64_t)L.grid_x * c.n_frames * (RT_WG_THREADS / 64u), "the trace kernel")) return rc;
 #ifdef RT_WAVE_LOG
