@@ -10,6 +10,7 @@
 //   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick, and the host lists that go
 //                  through device buffers in chunks (rt_trace_rays, rt_occlusion and their binned forms, rt_shade_rays), rt_trace_rays_wavefront
 //   rt_nodes_api.hip  the wavefront form's device entry points: one level of nodes, the next level's ray list, the fold (rt_nodes.hip)
+//   rt_views_api.hip  views: validation, the panorama's tables, the host probe, the generator's launch (rt_views.hip), the traces of a whole view
 // Which kernel a launch runs is one value (rt_device.h: rt_trace_variant), worked out once per launch; the two builds of rt_kernel.hip map
 // it to a kernel (rt_kernel_trace_fast / rt_kernel_trace_strict), and the declarations below are all the host sees of them.
 #ifndef RT_API_INTERNAL_H
@@ -335,6 +336,9 @@ int fold_launch(uint32_t n, const rt_node *d_nodes, const int32_t *d_links, cons
 // descriptor, the padding between two textures).  `a` is a blob rt_scene_validate has accepted, `b` any `bytes` bytes.
 struct texel_edit { uint32_t texture, first_row, rows; };
 int texel_edits(const uint8_t *a, const uint8_t *b, size_t bytes, std::vector<texel_edit> *out);
+// rt_frame.hip: rt_render's resident scene of `device` for a blob (scene_for: the resident one, edited where the blob differs only in
+// what an edit reaches, else a fresh upload).  Under G.mu.
+int resident_scene(int device, const void *blob, size_t bytes, rt_scene_dev **out);
 // rt_frame.hip: RCCL's communicators are destroyed (rt_shutdown)
 void release_rccl();
 }  // namespace rt_api

@@ -244,6 +244,8 @@ int ensure_frame(int device, size_t bytes) {
 }
 }  // namespace
 
+int rt_api::resident_scene(int device, const void *blob, size_t bytes, rt_scene_dev **out) { return scene_for(device, blob, bytes, out); }
+
 void rt_api::release_rccl() {
   if (G.comms_ready) { for (size_t g = 0; g < G.dev.size(); g++) if (G.comms[g]) NCCL.destroy(G.comms[g]); G.comms_ready = false; }
 }

@@ -1,0 +1,194 @@
+// rt_views_api.hip — views (include/rt_hip.h: rt_view): the host logic (validation, the panorama's tables, the host probe), the
+// generator's launch (rt_views.hip) and the two traces of a whole view.  A view is traced in bands of whole rows: each band is
+// generated into the caller's workspace and handed to the launch of a caller's ray list (rt_launch.hip: trace_rays_launch) with its
+// base, so ray i = y * w + x keeps pix = i and no trace kernel knows that the list was made here.  The generator reads nothing of a
+// scene: rt_view_rays_device waits for no edit and takes no part in rt_scene_sync.h; the trace launch behind it waits as it always does.
+#include "rt_api_internal.h"
+#include "rt_views.h"
+
+static_assert(RT_VIEWS_REFERENCE == RT_VIEW_REFERENCE && RT_VIEWS_PINHOLE == RT_VIEW_PINHOLE && RT_VIEWS_ORTHO == RT_VIEW_ORTHO &&
+              RT_VIEWS_EQUIRECT == RT_VIEW_EQUIRECT, "rt_views.h restates the models of include/rt_hip.h");
+
+namespace {
+// rt_trace_view's chunks: whole rows of at most this many rays, as rt_trace_rays' chunks
+constexpr uint64_t RT_VIEW_CHUNK_RAYS = 1ull << 18;
+
+bool finite3(const double *a) { return std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]); }
+
+bool view_size_ok(uint32_t w, uint32_t h) { return w != 0 && h != 0 && (uint64_t)w * h < (1ull << 31); }
+
+int view_check(const rt_view *v, uint32_t w, uint32_t h, const char *what) {
+  if (!v) return fail(RT_ERR_INVALID, "%s: NULL view", what);
+  if (v->model > RT_VIEW_EQUIRECT || v->reserved != 0) return fail(RT_ERR_INVALID, "%s: unknown model %u or reserved %u not 0", what, v->model, v->reserved);
+  if (!view_size_ok(w, h)) return fail(RT_ERR_INVALID, "%s: view size %ux%u: w and h must be at least 1 and w * h below 2^31", what, w, h);
+  if (!finite3(v->origin) || !finite3(v->axis_x) || !finite3(v->axis_y) || !finite3(v->axis_z))
+    return fail(RT_ERR_INVALID, "%s: a non-finite origin or axis component", what);
+  if ((v->model == RT_VIEW_REFERENCE || v->model == RT_VIEW_PINHOLE) && !(v->fov_deg > 0.0 && v->fov_deg < 180.0))
+    return fail(RT_ERR_INVALID, "%s: fov_deg %g not in (0, 180)", what, v->fov_deg);
+  if (v->model == RT_VIEW_ORTHO && !(std::isfinite(v->scale) && v->scale > 0.0)) return fail(RT_ERR_INVALID, "%s: scale %g not finite and above 0", what, v->scale);
+  if (v->model == RT_VIEW_EQUIRECT && (!v->lon || !v->lat || (((uintptr_t)v->lon | (uintptr_t)v->lat) & 15u)))
+    return fail(RT_ERR_INVALID, "%s: NULL or misaligned panorama tables (16 bytes)", what);
+  return RT_OK;
+}
+
+int view_rows_check(uint32_t h, uint32_t first_row, uint32_t rows, const char *what) {
+  if ((uint64_t)first_row + rows > h) return fail(RT_ERR_INVALID, "%s: rows %u..%llu leave the view's %u", what, first_row, (unsigned long long)first_row + rows, h);
+  return RT_OK;
+}
+
+// what rays_check asks of a list's depth and outputs (rt_launch.hip), for a list the library makes itself
+int view_outputs_check(uint32_t segs, const rt_ray_outputs *out, const char *what) {
+  if (!out) return fail(RT_ERR_INVALID, "%s: NULL outputs", what);
+  if (segs > RT_MAX_SEGS) return fail(RT_ERR_INVALID, "%s: segs %u not in 0..%u (0 = the scene's depth)", what, segs, RT_MAX_SEGS);
+  if (!out->rgb && !out->rgba && !out->hits) return fail(RT_ERR_INVALID, "%s: every output is NULL", what);
+  if (((uintptr_t)out->rgb & 7u) || ((uintptr_t)out->rgba & 3u) || ((uintptr_t)out->hits & 7u))
+    return fail(RT_ERR_INVALID, "%s: misaligned output (rgb and hits need 8 bytes, rgba 4)", what);
+  return RT_OK;
+}
+
+// a checked view at one frame size, as the generator takes it
+rt_view_params view_params(const rt_view &v, uint32_t w, uint32_t h) {
+  rt_view_params P;
+  memset(&P, 0, sizeof P);
+  P.model = v.model; P.w = w; P.h = h;
+  P.proj_w = (double)w / 2.0; P.proj_h = (double)h / 2.0;
+  if (v.model == RT_VIEW_REFERENCE || v.model == RT_VIEW_PINHOLE) P.proj_d = rt_view_proj_d(v.fov_deg, P.proj_w);
+  P.scale = v.scale;
+  memcpy(P.o, v.origin, sizeof P.o); memcpy(P.ax, v.axis_x, sizeof P.ax); memcpy(P.ay, v.axis_y, sizeof P.ay); memcpy(P.az, v.axis_z, sizeof P.az);
+  if (v.model == RT_VIEW_EQUIRECT) { P.lon = v.lon; P.lat = v.lat; }
+  return P;
+}
+
+int view_rays_launch(const rt_view_params &P, uint32_t first_row, uint32_t rows, double *d_rays, hipStream_t stream) {
+  const int err = rt_launch_view_rays(&P, first_row, rows, d_rays, (void *)stream);
+  if (err != 0) return fail(RT_ERR_DEVICE, "view generator launch: %s", hipGetErrorString((hipError_t)err));
+  return RT_OK;
+}
+
+// The view's rows in bands of at most band_rows: generated into d_work, traced with base = first_row * w into the outputs' records
+// from there on.  One stream: a band's generation comes behind the trace that read the workspace before it.
+int trace_view_bands(rt_scene_dev *s, const rt_view_params &P, uint32_t row0, uint32_t row_end, uint32_t band_rows, uint32_t segs, const rt_ray_outputs &out,
+                     uint32_t out_row0, double *d_work, hipStream_t stream) {
+  for (uint32_t y = row0; y < row_end; y += band_rows) {
+    const uint32_t m = row_end - y < band_rows ? row_end - y : band_rows;
+    if (int rc = view_rays_launch(P, y, m, d_work, stream)) return rc;
+    const size_t at = (size_t)(y - out_row0) * P.w;       // of the band's first record in the outputs
+    const rt_ray_outputs band = {out.rgb ? out.rgb + 3u * at : nullptr, out.rgba ? out.rgba + 4u * at : nullptr, out.hits ? out.hits + at : nullptr};
+    if (int rc = trace_rays_launch(s, m * P.w, y * P.w, d_work, nullptr, segs, band, stream, nullptr)) return rc;
+  }
+  return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_view_validate(const rt_view *v, uint32_t w, uint32_t h) { return view_check(v, w, h, "rt_view_validate"); }
+
+extern "C" int rt_view_equirect_tables(uint32_t w, uint32_t h, double *lon, double *lat) {
+  if (!lon || !lat || w == 0 || h == 0) return fail(RT_ERR_INVALID, "rt_view_equirect_tables: a NULL table, w == 0 or h == 0");
+  for (uint32_t x = 0; x < w; x++) { const double a = rt_view_lon(x, w); lon[2u * (size_t)x] = sin(a); lon[2u * (size_t)x + 1u] = cos(a); }
+  for (uint32_t y = 0; y < h; y++) { const double a = rt_view_lat(y, h); lat[2u * (size_t)y] = sin(a); lat[2u * (size_t)y + 1u] = cos(a); }
+  return RT_OK;
+}
+
+extern "C" int rt_view_rays(const rt_view *v, uint32_t w, uint32_t h, uint32_t first_row, uint32_t rows, double *out) {
+  int rc = view_check(v, w, h, "rt_view_rays");
+  if (rc) return rc;
+  if (!out) return fail(RT_ERR_INVALID, "rt_view_rays: NULL output");
+  if ((rc = view_rows_check(h, first_row, rows, "rt_view_rays"))) return rc;
+  const rt_view_params P = view_params(*v, w, h);
+  rt_view_rays_host(&P, first_row, rows, out);
+  return RT_OK;
+}
+
+extern "C" int rt_view_rays_device(int device, const rt_view *v, uint32_t w, uint32_t h, uint32_t first_row, uint32_t rows, double *d_rays,
+                                   void *hip_stream) {
+  int rc = view_check(v, w, h, "rt_view_rays_device");
+  if (rc) return rc;
+  if (!d_rays || ((uintptr_t)d_rays & 15u)) return fail(RT_ERR_INVALID, "rt_view_rays_device: NULL or misaligned ray list (16 bytes)");
+  if ((rc = view_rows_check(h, first_row, rows, "rt_view_rays_device"))) return rc;
+  if (rows == 0) return RT_OK;
+  hipStream_t stream = nullptr;
+  if ((rc = device_stream(device, hip_stream, &stream))) return rc;
+  return view_rays_launch(view_params(*v, w, h), first_row, rows, d_rays, stream);
+}
+
+extern "C" size_t rt_view_work_bytes(uint32_t w, uint32_t h) {
+  // the whole view in one band: at 3840 x 2160 bands of 2^16, 2^18 and 2^20 rays cost default14 10.7, 3.8 and 1.7 ms against 0.91 ms
+  // for the whole view (docs/EVIDENCE.md, "Views")
+  return view_size_ok(w, h) ? (size_t)w * h * 48u : 0;
+}
+
+extern "C" int rt_scene_trace_view_device(rt_scene_dev *s, const rt_view *v, uint32_t w, uint32_t h, uint32_t segs, const rt_ray_outputs *d_out,
+                                          void *d_work, size_t work_bytes, void *hip_stream, rt_stats *stats) {
+  const char *what = "rt_scene_trace_view_device";
+  if (!s) return fail(RT_ERR_STATE, "%s: NULL scene handle", what);
+  int rc = view_check(v, w, h, what);
+  if (rc) return rc;
+  if ((rc = view_outputs_check(segs, d_out, what))) return rc;
+  if (!d_work || ((uintptr_t)d_work & 15u)) return fail(RT_ERR_INVALID, "%s: NULL or misaligned workspace (16 bytes)", what);
+  if (work_bytes < (size_t)w * 48u) return fail(RT_ERR_INVALID, "%s: work_bytes %llu below one row of rays, %llu", what, (unsigned long long)work_bytes, (unsigned long long)w * 48u);
+  hipStream_t stream = nullptr;
+  if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
+  const uint64_t fit = work_bytes / ((uint64_t)w * 48u);
+  const uint32_t band_rows = fit < h ? (uint32_t)fit : h;
+  stats_clock clock;
+  if ((rc = clock.start(stats, stream))) return rc;
+  if ((rc = trace_view_bands(s, view_params(*v, w, h), 0u, h, band_rows, segs, *d_out, 0u, (double *)d_work, stream))) return rc;
+  return clock.finish(stats, (uint64_t)w * h);
+}
+
+extern "C" int rt_trace_view(const void *blob, size_t bytes, const rt_view *v, uint32_t w, uint32_t h, uint32_t segs, const rt_ray_outputs *ho,
+                             rt_stats *stats) {
+  const char *what = "rt_trace_view";
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  if ((rc = view_check(v, w, h, what))) return rc;
+  if ((rc = view_outputs_check(segs, ho, what))) return rc;
+  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
+  std::lock_guard<std::mutex> lk(G.mu);
+  stats_clock clock;
+  rt_scene_dev *s = nullptr;
+  if ((rc = resident_scene(0, blob, bytes, &s))) return rc;
+  if ((rc = ensure_device(0))) return rc;
+  hipStream_t stream = G.dev[0].stream;
+  // chunks of whole rows of at most RT_VIEW_CHUNK_RAYS rays; a longer row is its own chunk
+  uint64_t chunk_rows = RT_VIEW_CHUNK_RAYS / w;
+  if (chunk_rows < 1u) chunk_rows = 1u;
+  if (chunk_rows > h) chunk_rows = h;
+  const size_t chunk = (size_t)chunk_rows * w;
+  device_mem d_rays, d_rgb, d_rgba, d_hits, d_lon, d_lat;      // of one chunk; the panorama's tables (released on every way out)
+  HIP_TRY(hipMalloc(&d_rays.h, chunk * 48u));
+  if (ho->rgb) HIP_TRY(hipMalloc(&d_rgb.h, chunk * 24u));
+  if (ho->rgba) HIP_TRY(hipMalloc(&d_rgba.h, chunk * 4u));
+  if (ho->hits) HIP_TRY(hipMalloc(&d_hits.h, chunk * sizeof(rt_hit)));
+  rt_view_params P = view_params(*v, w, h);
+  if (v->model == RT_VIEW_EQUIRECT) {
+    HIP_TRY(hipMalloc(&d_lon.h, (size_t)w * 16u));
+    HIP_TRY(hipMalloc(&d_lat.h, (size_t)h * 16u));
+    HIP_TRY(hipMemcpyAsync(d_lon.h, v->lon, (size_t)w * 16u, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_lat.h, v->lat, (size_t)h * 16u, hipMemcpyHostToDevice, stream));
+    P.lon = (const double *)d_lon.h; P.lat = (const double *)d_lat.h;
+  }
+  const rt_ray_outputs dout = {(double *)d_rgb.h, (uint8_t *)d_rgba.h, (rt_hit *)d_hits.h};
+  double kernel_ms = 0.0;
+  for (uint32_t y = 0; y < h; y += (uint32_t)chunk_rows) {
+    const uint32_t m = h - y < chunk_rows ? h - y : (uint32_t)chunk_rows;
+    const size_t at = (size_t)y * w, n = (size_t)m * w;
+    stats_clock step;
+    rt_stats st;
+    if ((rc = step.start(stats, stream))) return rc;
+    if ((rc = trace_view_bands(s, P, y, y + m, m, segs, dout, y, (double *)d_rays.h, stream))) return rc;
+    if ((rc = step.finish(stats ? &st : nullptr, n))) return rc;
+    if (stats) kernel_ms += st.kernel_ms;
+    if (ho->rgb) HIP_TRY(hipMemcpyAsync(ho->rgb + 3u * at, d_rgb.h, n * 24u, hipMemcpyDeviceToHost, stream));
+    if (ho->rgba) HIP_TRY(hipMemcpyAsync(ho->rgba + 4u * at, d_rgba.h, n * 4u, hipMemcpyDeviceToHost, stream));
+    if (ho->hits) HIP_TRY(hipMemcpyAsync(ho->hits + at, d_hits.h, n * sizeof(rt_hit), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = kernel_ms;
+    stats->pixels = (uint64_t)w * h;
+    stats->total_ms = clock.host_ms();
+  }
+  return RT_OK;
+}

@@ -153,6 +153,62 @@ function traceRays(sceneObj, rays, opts) {
   return r;
 }
 
+// Views: a camera's rays generated on the GPU (include/rt_hip.h: rt_view).  traceRays renders any projection, but its list is built
+// here and crosses the link at 48 bytes per ray; a view is the list's description - a model, an origin, a basis - and the library
+// generates the rays on the device in front of the same trace.  The constructors take the axes as given: image x runs along axisX,
+// image y (upwards) along axisY, the view looks along axisZ (lookAt's axisX, main.js:95, points to the viewer's LEFT).
+//   views.reference(origin, axisX, axisY, axisZ, fovDeg)  the reference's own per-component rays (main.js:186-193): the strict frame's
+//   views.pinhole(origin, axisX, axisY, axisZ, fovDeg)    a true pinhole for any basis
+//   views.ortho(origin, axisX, axisY, axisZ, scale)       parallel rays along axisZ, `scale` world units per pixel
+//   views.equirect(origin, axisX, axisY, axisZ, w, h)     a w x h panorama; its tables (sines and cosines per column and per row) are
+//                                                         filled through the addon, for that size
+//   views.cubeFaces(eye)         six pinholes of 90 degrees for square frames, +x -x +y -y +z -z; axisX = axisZ x axisY, up = +y for the
+//                                side faces, +z for +y and -z for -y (rt_host.cube_views states each basis)
+//   views.stereo(view, separation)   [left, right]: origins moved by -/+ separation / 2 along unit(axisX)
+//   views.bytes(view)            the 136 bytes of the rt_view record (table pointers zero): what Python's rt_host.view(...) holds
+const VIEW_REFERENCE = 0, VIEW_PINHOLE = 1, VIEW_ORTHO = 2, VIEW_EQUIRECT = 3, VIEW_BYTES = 136;
+function makeView(model, origin, axisX, axisY, axisZ, fovDeg, scale) {
+  const v3 = (a) => [Number(a[0]), Number(a[1]), Number(a[2])];
+  return {model, origin: v3(origin), axisX: v3(axisX), axisY: v3(axisY), axisZ: v3(axisZ), fovDeg: fovDeg === undefined ? 60 : fovDeg,
+    scale: scale === undefined ? 1 : scale, lon: null, lat: null};
+}
+function viewBytes(view) {
+  const buf = new Uint8Array(VIEW_BYTES), d = new DataView(buf.buffer);
+  d.setUint32(0, view.model, true);
+  [view.origin, view.axisX, view.axisY, view.axisZ].forEach((a, i) => { for (let c = 0; c < 3; c++) d.setFloat64(8 + 24 * i + 8 * c, a[c], true); });
+  d.setFloat64(104, view.fovDeg, true);
+  d.setFloat64(112, view.scale, true);
+  return buf;
+}
+const views = {
+  REFERENCE: VIEW_REFERENCE, PINHOLE: VIEW_PINHOLE, ORTHO: VIEW_ORTHO, EQUIRECT: VIEW_EQUIRECT,
+  reference: (origin, axisX, axisY, axisZ, fovDeg) => makeView(VIEW_REFERENCE, origin, axisX, axisY, axisZ, fovDeg),
+  pinhole: (origin, axisX, axisY, axisZ, fovDeg) => makeView(VIEW_PINHOLE, origin, axisX, axisY, axisZ, fovDeg),
+  ortho: (origin, axisX, axisY, axisZ, scale) => makeView(VIEW_ORTHO, origin, axisX, axisY, axisZ, undefined, scale),
+  equirect: (origin, axisX, axisY, axisZ, w, h) => Object.assign(makeView(VIEW_EQUIRECT, origin, axisX, axisY, axisZ), native().equirectTables(w, h)),
+  cubeFaces: (eye) => [[[0, 0, 1], [0, 1, 0], [1, 0, 0]], [[0, 0, -1], [0, 1, 0], [-1, 0, 0]], [[1, 0, 0], [0, 0, 1], [0, 1, 0]],
+    [[1, 0, 0], [0, 0, -1], [0, -1, 0]], [[-1, 0, 0], [0, 1, 0], [0, 0, 1]], [[1, 0, 0], [0, 1, 0], [0, 0, -1]]]
+    .map(([ax, ay, az]) => makeView(VIEW_PINHOLE, eye, ax, ay, az, 90)),
+  stereo: (view, separation) => {
+    const u = normal3D(view.axisX), half = separation / 2;
+    return [-1, 1].map((s) => Object.assign({}, view, {origin: view.origin.map((o, c) => (s < 0 ? o - u[c] * half : o + u[c] * half))}));
+  },
+  bytes: viewBytes,
+};
+
+// intersectWorld for every ray of `view` at w x h, in frame order (ray y w + x): traceRays' result shape.  opts: segs, and which
+// outputs to compute - rgba (default true) the Uint8ClampedArray that is a w x h ImageData.data, rgb Float64Array 3 per ray, hits.
+// The scene's own camera plays no part.
+function traceView(sceneObj, view, w, h, opts) {
+  if (!view || !Number.isInteger(view.model)) throw new TypeError('traceView: view must come from views.reference / pinhole / ortho / equirect');
+  if (!inited) init(opts && opts.maxDevices);
+  const o = opts || {};
+  const r = native().traceView(new Uint8Array(flattenScene(sceneObj)), viewBytes(view), view.lon || null, view.lat || null, w, h, o.segs || 0,
+    !!o.rgb, o.rgba !== false, !!o.hits);
+  if (r.hits) for (const hit of r.hits) if (hit) hit.object = sceneObj.objects[hit.index];
+  return r;
+}
+
 // One level of intersectWorld (main.js:216-336 WITHOUT its two recursive calls) for a list of rays: {nodes: ArrayBuffer of 200-byte
 // rt_node records (include/rt_hip.h), count, node(i)}.  opts: pix, path (Uint32Array per ray: the stars sampler's; default i and 1),
 // bin (the GPU orders the list first - the same nodes).  node(i) reads record i: {hit: pick's record or null, sample, diffuse,
@@ -238,4 +294,4 @@ function buildId() { return native().buildId(); }
 
 function shutdown() { if (addon) addon.shutdown(); inited = false; }
 
-module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, shadeRays, primaryRays, normal3D, occlusion, lightSegments, init, shutdown, buildId, flattenScene, scenes, native}, scene);
+module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, traceView, views, shadeRays, primaryRays, normal3D, occlusion, lightSegments, init, shutdown, buildId, flattenScene, scenes, native}, scene);

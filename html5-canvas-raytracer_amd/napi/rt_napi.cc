@@ -17,6 +17,9 @@
 //           bin: rt_trace_rays_binned, the list ordered on the GPU first - the same results; two more booleans, wavefront and
 //           orderLevels: rt_trace_rays_wavefront, the same rgb and rgba level by level, plus levelCounts)
 //           shadeRays(blob, rays, pix: Uint32Array | null, path: Uint32Array | null, bin) -> {nodes: ArrayBuffer of rt_node records, count}
+//           traceView(blob, view: Uint8Array (the 136 bytes of rt_view, table pointers ignored), lon: Float64Array | null, lat: Float64Array | null,
+//           w, h, segs, wantRgb, wantRgba, wantHits) -> traceRays' result for the view's w x h rays, generated on the GPU (rt_trace_view)
+//           equirectTables(w, h) -> {lon: Float64Array (2 w), lat: Float64Array (2 h)} (rt_view_equirect_tables)
 //           (these, and renderAdaptive, are not enumerable: the enumerable surface is the frame API of the first revision)
 // Every failure of the library becomes a thrown JS Error carrying rt_last_error().
 //
@@ -552,6 +555,111 @@ napi_value TraceRays(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// equirectTables(w, h): the panorama's tables of a w x h view (rt_view_equirect_tables)
+napi_value EquirectTables(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  uint32_t w = 0, h = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2 || napi_get_value_uint32(env, argv[0], &w) != napi_ok ||
+      napi_get_value_uint32(env, argv[1], &h) != napi_ok || w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 31)) {
+    napi_throw_type_error(env, nullptr, "equirectTables(w, h): a view size with w * h below 2^31");
+    return nullptr;
+  }
+  napi_value ab_lon, ab_lat, res, v;
+  void *lon = nullptr, *lat = nullptr;
+  NAPI_TRY(napi_create_arraybuffer(env, (size_t)w * 16u, &lon, &ab_lon));
+  NAPI_TRY(napi_create_arraybuffer(env, (size_t)h * 16u, &lat, &ab_lat));
+  const int rc = rt_view_equirect_tables(w, h, (double *)lon, (double *)lat);
+  if (rc != RT_OK) return throw_rt(env, "rt_view_equirect_tables", rc);
+  napi_create_object(env, &res);
+  napi_create_typedarray(env, napi_float64_array, 2u * (size_t)w, ab_lon, 0, &v); napi_set_named_property(env, res, "lon", v);
+  napi_create_typedarray(env, napi_float64_array, 2u * (size_t)h, ab_lat, 0, &v); napi_set_named_property(env, res, "lat", v);
+  return res;
+}
+
+// traceView(blob, view, lon, lat, w, h, segs, wantRgb, wantRgba, wantHits): rt_trace_view.  `view` is the bytes of an rt_view whose table
+// pointers are ignored: an EQUIRECT view's tables come as the two Float64Arrays.
+napi_value TraceView(napi_env env, napi_callback_info info) {
+  size_t argc = 10;
+  napi_value argv[10];
+  bool is_ta = false, is_view = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 6 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
+      napi_is_typedarray(env, argv[1], &is_view) != napi_ok || !is_view) {
+    napi_throw_type_error(env, nullptr, "traceView(blob: Uint8Array, view: Uint8Array, lon, lat, w, h[, segs, wantRgb, wantRgba, wantHits])");
+    return nullptr;
+  }
+  napi_typedarray_type bt, vt; napi_value ab; size_t off, blob_len = 0, view_len = 0;
+  void *blob_data = nullptr, *view_data = nullptr;
+  napi_get_typedarray_info(env, argv[0], &bt, &blob_len, &blob_data, &ab, &off);
+  napi_get_typedarray_info(env, argv[1], &vt, &view_len, &view_data, &ab, &off);
+  uint32_t w = 0, h = 0, segs = 0;
+  if ((bt != napi_uint8_array && bt != napi_uint8_clamped_array) || vt != napi_uint8_array || view_len != sizeof(rt_view) ||
+      napi_get_value_uint32(env, argv[4], &w) != napi_ok || napi_get_value_uint32(env, argv[5], &h) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "traceView: the blob must be a Uint8Array, the view the 136 bytes of an rt_view, w and h non-negative integers");
+    return nullptr;
+  }
+  rt_view view;
+  memcpy(&view, view_data, sizeof view);
+  view.lon = view.lat = nullptr;
+  size_t table_len[2] = {0, 0};
+  void *table_data[2] = {nullptr, nullptr};
+  for (int i = 0; i < 2; i++) {
+    bool is_table = false;
+    if (napi_is_typedarray(env, argv[2 + i], &is_table) == napi_ok && is_table) {
+      napi_typedarray_type tt;
+      napi_get_typedarray_info(env, argv[2 + i], &tt, &table_len[i], &table_data[i], &ab, &off);
+      if (tt != napi_float64_array) { table_len[i] = 0; table_data[i] = nullptr; }
+    }
+  }
+  if (view.model == RT_VIEW_EQUIRECT && (table_len[0] != 2u * (size_t)w || table_len[1] != 2u * (size_t)h)) {
+    napi_throw_type_error(env, nullptr, "traceView: an equirect view needs lon and lat, Float64Arrays of 2 w and 2 h numbers");
+    return nullptr;
+  }
+  const bool sized = w != 0 && h != 0 && (uint64_t)w * h < (1ull << 31);       // (anything else the library refuses: no buffer is sized from it)
+  bool want[3] = {false, true, false};
+  if (argc >= 7) napi_get_value_uint32(env, argv[6], &segs);
+  for (size_t i = 0; i < 3 && 7 + i < argc; i++) napi_get_value_bool(env, argv[7 + i], &want[i]);
+  const size_t n = sized ? (size_t)w * h : 0;
+  // the library wants the blob 8-byte and the tables 16-byte aligned: one aligned copy holds all three
+  const size_t blob_room = (blob_len + 15) & ~(size_t)15, lon_room = table_len[0] * 8u, lat_room = table_len[1] * 8u;
+  uint8_t *mem = (uint8_t *)aligned_alloc(16, blob_room + lon_room + lat_room + 16u);
+  napi_value ab_rgb = nullptr, ab_rgba = nullptr, res, v;
+  void *p_rgb = nullptr, *p_rgba = nullptr;
+  rt_hit *hits = (want[2] && n) ? (rt_hit *)malloc(n * sizeof(rt_hit)) : nullptr;
+  if (!mem || (want[2] && n && !hits) || (want[0] && napi_create_arraybuffer(env, n * 24u, &p_rgb, &ab_rgb) != napi_ok) ||
+      (want[1] && napi_create_arraybuffer(env, n * 4u, &p_rgba, &ab_rgba) != napi_ok)) {
+    free(mem); free(hits);
+    napi_throw_error(env, nullptr, "traceView: out of memory");
+    return nullptr;
+  }
+  memcpy(mem, blob_data, blob_len);
+  if (view.model == RT_VIEW_EQUIRECT) {
+    memcpy(mem + blob_room, table_data[0], lon_room);
+    memcpy(mem + blob_room + lon_room, table_data[1], lat_room);
+    view.lon = (const double *)(mem + blob_room);
+    view.lat = (const double *)(mem + blob_room + lon_room);
+  }
+  const rt_ray_outputs out = {(double *)p_rgb, (uint8_t *)p_rgba, hits};
+  rt_stats st;
+  const int rc = rt_trace_view(mem, blob_len, &view, w, h, segs, &out, &st);
+  free(mem);
+  if (rc != RT_OK) { free(hits); return throw_rt(env, "rt_trace_view", rc); }
+  napi_create_object(env, &res);
+  if (want[0]) napi_create_typedarray(env, napi_float64_array, 3 * n, ab_rgb, 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "rgb", v);
+  if (want[1]) napi_create_typedarray(env, napi_uint8_clamped_array, 4 * n, ab_rgba, 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "rgba", v);
+  if (want[2]) {
+    napi_create_array_with_length(env, n, &v);
+    for (size_t i = 0; i < n; i++) napi_set_element(env, v, (uint32_t)i, hit_object(env, hits[i]));
+    free(hits);
+  } else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "hits", v);
+  napi_value ms;
+  napi_create_double(env, st.kernel_ms, &ms); napi_set_named_property(env, res, "kernel_ms", ms);
+  return res;
+}
+
 // occlusion(blob, rays: Float64Array (6 per ray), length: Float64Array | null, intensity: Float64Array | null, skip: Int32Array | null,
 //           wantBlocker, bin) -> {intensity: Float64Array, blocker: Int32Array | null, kernel_ms}  (rt_occlusion / rt_occlusion_binned)
 napi_value Occlusion(napi_env env, napi_callback_info info) {
@@ -691,6 +799,8 @@ napi_value Module(napi_env env, napi_value exports) {
       {"traceRays", nullptr, TraceRays, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"occlusion", nullptr, Occlusion, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"shadeRays", nullptr, ShadeRays, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"traceView", nullptr, TraceView, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"equirectTables", nullptr, EquirectTables, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

@@ -200,6 +200,16 @@ class RtOcclusionOutputs(C.Structure):
     _fields_ = [("intensity", C.c_void_p), ("blocker", C.c_void_p)]
 
 
+RT_VIEW_REFERENCE, RT_VIEW_PINHOLE, RT_VIEW_ORTHO, RT_VIEW_EQUIRECT = 0, 1, 2, 3
+
+
+class RtView(C.Structure):
+    """A camera model (include/rt_hip.h rt_view, 136 bytes): model, origin, three axes, fov_deg (the perspective models), scale (ORTHO),
+    and the panorama's two tables (EQUIRECT: host memory for the host forms, device memory for the Renderer's)."""
+    _fields_ = [("model", C.c_uint32), ("reserved", C.c_uint32), ("origin", C.c_double * 3), ("axis_x", C.c_double * 3), ("axis_y", C.c_double * 3),
+                ("axis_z", C.c_double * 3), ("fov_deg", C.c_double), ("scale", C.c_double), ("lon", C.c_void_p), ("lat", C.c_void_p)]
+
+
 # every symbol include/rt_hip.h declares: (restype, argtypes)
 ABI = {
     "rt_init": (C.c_int, [C.c_int]),
@@ -279,6 +289,14 @@ ABI = {
     "rt_scene_fold_nodes_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_trace_rays_wavefront": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(RtRayOutputs), C.POINTER(RtStats),
                                           C.POINTER(C.c_uint64)]),
+    "rt_view_validate": (C.c_int, [C.POINTER(RtView), C.c_uint32, C.c_uint32]),
+    "rt_view_equirect_tables": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_view_rays": (C.c_int, [C.POINTER(RtView), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "rt_view_rays_device": (C.c_int, [C.c_int, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_view_work_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_scene_trace_view_device": (C.c_int, [C.c_void_p, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RtRayOutputs), C.c_void_p,
+                                             C.c_size_t, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_trace_view": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RtRayOutputs), C.POINTER(RtStats)]),
 }
 
 RT_MAX_SEGS = 16
@@ -523,6 +541,26 @@ class Renderer:
         rc = self.lib.rt_scene_trace_rays_ordered_device(self.handle, n, C.c_void_p(rays_ptr or 0), C.c_void_p(order_ptr or 0), segs, C.byref(out),
                                                          C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
         _check(self.lib, rc, "rt_scene_trace_rays_ordered_device")
+        return st
+
+    def view_rays(self, view, w, h, rays_ptr, first_row=0, rows=None, stream=None):
+        """Rows [first_row, first_row + rows) (default: to the last) of `view`'s w x h primary rays into rays_ptr (DEVICE, 16-byte
+        aligned, rows * w records of six float64), generated on the GPU: the bits of rt_host.view_rays.  Asynchronous; reads nothing of
+        the scene.  An EQUIRECT view's tables are DEVICE pointers here."""
+        rows = h - first_row if rows is None else rows
+        rc = self.lib.rt_view_rays_device(self.device, C.byref(view), w, h, first_row, rows, C.c_void_p(rays_ptr or 0), C.c_void_p(stream or 0))
+        _check(self.lib, rc, "rt_view_rays_device")
+
+    def trace_view(self, view, w, h, rgb_ptr, rgba_ptr, hits_ptr, work_ptr, work_bytes, segs=0, stream=None, want_stats=False):
+        """intersectWorld for every ray of `view` at w x h, into DEVICE buffers in frame order (0 / None = not wanted; rgba is the w x h
+        RGBA8 frame): the rays are generated on the GPU band by band into work_ptr (DEVICE, 16-byte aligned, work_bytes >= 48 w;
+        view_work_bytes(w, h) is the size the library prefers) and traced as trace_rays traces them, ray y w + x with pix = y w + x.
+        The scene's own camera plays no part.  An EQUIRECT view's tables are DEVICE pointers here."""
+        out = RtRayOutputs(rgb_ptr or None, rgba_ptr or None, hits_ptr or None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_trace_view_device(self.handle, C.byref(view), w, h, segs, C.byref(out), C.c_void_p(work_ptr or 0), work_bytes,
+                                                 C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_trace_view_device")
         return st
 
     def occlusion(self, n, rays_ptr, length_ptr, intensity_ptr, skip_ptr, out_intensity_ptr, out_blocker_ptr, order_ptr=0, stream=None, want_stats=False):
@@ -805,6 +843,139 @@ def trace_rays(scene, rays, segs=0, want=("rgb",), lib=None, order="list", metho
         return out
     call, what = (lib.rt_trace_rays, "rt_trace_rays") if order == "list" else (lib.rt_trace_rays_binned, "rt_trace_rays_binned")
     _check(lib, call(buf, len(blob), n, C.c_void_p(aligned.ctypes.data), segs, C.byref(bufs), None), what)
+    if records is not None:
+        out["hits"] = [_hit_dict(r) for r in records[:n]]
+    return out
+
+
+# --------------------------------------------------------------------------- views: a camera's rays generated on the GPU
+def _aligned_f64(n):
+    """n float64 on a 16-byte boundary."""
+    import numpy as np
+    a = np.empty(n + 2, np.float64)
+    return a[(a.ctypes.data >> 3) & 1:][:n]
+
+
+def view(model, origin, axis_x, axis_y, axis_z, fov_deg=60, scale=1.0, tables=None):
+    """-> RtView.  model: RT_VIEW_REFERENCE (the reference's own per-component rays, main.js:186-193: a pinhole only while the axes
+    are the world's), RT_VIEW_PINHOLE (a true pinhole for any basis), RT_VIEW_ORTHO (parallel rays along axis_z, `scale` world units per
+    pixel) or RT_VIEW_EQUIRECT (a panorama; tables = equirect_tables(w, h) for the host forms, or a pair of DEVICE pointers for the
+    Renderer's).  The axes are used as given: image x runs along axis_x, image y (upwards) along axis_y, the view looks along axis_z."""
+    v = RtView()
+    v.model, v.reserved = model, 0
+    v.origin[:] = [float(x) for x in origin]
+    v.axis_x[:] = [float(x) for x in axis_x]
+    v.axis_y[:] = [float(x) for x in axis_y]
+    v.axis_z[:] = [float(x) for x in axis_z]
+    v.fov_deg, v.scale = float(fov_deg), float(scale)
+    if tables is not None:
+        lon, lat = tables
+        if isinstance(lon, numbers.Integral):
+            v.lon, v.lat = lon or None, lat or None
+        else:
+            v.lon, v.lat = lon.ctypes.data, lat.ctypes.data
+            v._tables = (lon, lat)                       # (kept alive with the view)
+    return v
+
+
+def _copy_view(v):
+    c = RtView.from_buffer_copy(bytes(v))
+    if hasattr(v, "_tables"):
+        c._tables = v._tables
+    return c
+
+
+def look_at_view(model, org, tgt, up, fov_deg=60, scale=1.0, tables=None):
+    """view() with the basis of the reference's lookAt (main.js:92-100): axis_z = unit(tgt - org), axis_x = unit(cross(up, tgt - org)),
+    axis_y = unit(cross(tgt - org, cross(up, tgt - org))).  Note that this axis_x points to the LEFT of the viewer (the reference's
+    pictures are drawn that way round); negate it for an image whose x runs to the right."""
+    import numpy as np
+
+    def cross(a, b):
+        return np.array([a[1] * b[2] - b[1] * a[2], a[2] * b[0] - b[2] * a[0], a[0] * b[1] - b[0] * a[1]])
+    org, tgt, up = (np.array(x, np.float64) for x in (org, tgt, up))
+    z = tgt - org
+    x = cross(up, z)
+    y = cross(z, x)
+    return view(model, org, normal3d(x), normal3d(y), normal3d(z), fov_deg, scale, tables)
+
+
+def cube_views(eye):
+    """Six RT_VIEW_PINHOLE views with fov_deg = 90 from `eye`, for square frames (w == h): the faces of a cube map in the order
+    +x -x +y -y +z -z.  Image x runs along axis_x (to the viewer's right), image y upwards along axis_y:
+        face   axis_z (forward)   axis_y (up)   axis_x (right = forward x up)
+        +x     ( 1, 0, 0)         (0, 1, 0)     ( 0, 0, 1)
+        -x     (-1, 0, 0)         (0, 1, 0)     ( 0, 0,-1)
+        +y     ( 0, 1, 0)         (0, 0, 1)     ( 1, 0, 0)
+        -y     ( 0,-1, 0)         (0, 0,-1)     ( 1, 0, 0)
+        +z     ( 0, 0, 1)         (0, 1, 0)     (-1, 0, 0)
+        -z     ( 0, 0,-1)         (0, 1, 0)     ( 1, 0, 0)"""
+    faces = [((0, 0, 1), (0, 1, 0), (1, 0, 0)), ((0, 0, -1), (0, 1, 0), (-1, 0, 0)), ((1, 0, 0), (0, 0, 1), (0, 1, 0)),
+             ((1, 0, 0), (0, 0, -1), (0, -1, 0)), ((-1, 0, 0), (0, 1, 0), (0, 0, 1)), ((1, 0, 0), (0, 1, 0), (0, 0, -1))]
+    return [view(RT_VIEW_PINHOLE, eye, ax, ay, az, fov_deg=90) for ax, ay, az in faces]
+
+
+def stereo_views(v, separation):
+    """-> (left, right): two copies of the view whose origins are moved by -/+ separation / 2 along the unit axis_x:
+    origin[c] -/+ u[c] * (separation / 2.0) with u = normal3d(axis_x).  (With lookAt's basis, whose axis_x points left, the first is
+    the viewer's right eye.)"""
+    u = normal3d(list(v.axis_x))
+    half = float(separation) / 2.0
+    left, right = _copy_view(v), _copy_view(v)
+    for c in range(3):
+        left.origin[c] = v.origin[c] - float(u[c]) * half
+        right.origin[c] = v.origin[c] + float(u[c]) * half
+    return left, right
+
+
+def equirect_tables(w, h, lib=None):
+    """-> (lon, lat): the panorama's tables for a w x h view (rt_view_equirect_tables): float64 arrays of 2 w and 2 h entries on 16-byte
+    boundaries, {sin, cos} of the longitude 2 pi (x + 0.5) / w - pi per column and of the latitude pi / 2 - pi (y + 0.5) / h per row."""
+    lib = lib or load_library()
+    lon, lat = _aligned_f64(2 * w), _aligned_f64(2 * h)
+    _check(lib, lib.rt_view_equirect_tables(w, h, C.c_void_p(lon.ctypes.data), C.c_void_p(lat.ctypes.data)), "rt_view_equirect_tables")
+    return lon, lat
+
+
+def view_work_bytes(w, h, lib=None):
+    """Bytes of device workspace Renderer.trace_view prefers for a w x h view (host arithmetic; 0 for a size it refuses).  48 w - one
+    row - is the least it accepts."""
+    return int((lib or load_library()).rt_view_work_bytes(w, h))
+
+
+def view_rays(v, w, h, first_row=0, rows=None, lib=None):
+    """The host probe (rt_view_rays): rows [first_row, first_row + rows) (default: to the last) of the view's w x h primary rays as an
+    (rows * w, 6) float64 array {org, dir} in row order - what the GPU generates, bit for bit.  No GPU."""
+    import numpy as np
+    lib = lib or load_library()
+    rows = h - first_row if rows is None else rows
+    out = np.empty((max(rows, 0) * w, 6), np.float64)
+    _check(lib, lib.rt_view_rays(C.byref(v), w, h, first_row, rows, C.c_void_p(out.ctypes.data)), "rt_view_rays")
+    return out
+
+
+def trace_view(scene, v, w, h, segs=0, want=("rgba",), lib=None):
+    """trace_view(scene, view, w, h) -> the dict of trace_rays for the view's w x h rays in frame order (ray y w + x; "rgba" (w h, 4)
+    uint8 is the frame), on GPU 0 with rt_render's resident scene.  The rays are generated on the GPU: none crosses the link (an
+    EQUIRECT view's tables, host memory here, are uploaded once)."""
+    import numpy as np
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    want = set(want)
+    if not want or want - {"rgb", "rgba", "hits"}:
+        raise ValueError("want names some of 'hits', 'rgb', 'rgba'")
+    n = w * h
+    out = {}
+    if "rgb" in want:
+        out["rgb"] = np.empty((n, 3), np.float64)
+    if "rgba" in want:
+        out["rgba"] = np.empty((n, 4), np.uint8)
+    records = (RtHit * max(n, 1))() if "hits" in want else None
+    bufs = RtRayOutputs(out["rgb"].ctypes.data if "rgb" in out else None, out["rgba"].ctypes.data if "rgba" in out else None,
+                        C.addressof(records) if records is not None else None)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    _check(lib, lib.rt_trace_view(buf, len(blob), C.byref(v), w, h, segs, C.byref(bufs), None), "rt_trace_view")
     if records is not None:
         out["hits"] = [_hit_dict(r) for r in records[:n]]
     return out

@@ -713,6 +713,77 @@ int rt_scene_fold_nodes_device(rt_scene_dev *scene, uint64_t n, const rt_node *d
 int rt_trace_rays_wavefront(const void *scene_blob, size_t blob_bytes, uint64_t n, const double *rays, uint32_t segs, int order_levels,
                             const rt_ray_outputs *host_out, rt_stats *stats, uint64_t *level_counts);
 
+/* Views: a camera's rays generated on the GPU.  The ray-list calls above render any projection, but the list has to be built on the
+ * host and crosses the link at 48 bytes per ray (a 3840 x 2160 view: 398 MB per frame from a moving eye).  A view is the list's
+ * description instead - a model, an origin, a basis - and the library generates the list on the device, band by band, in front of
+ * the same rt_trace_rays launch.  No trace kernel knows about it.
+ *
+ * Pixel (x, y) of a w x h view, with X = ((double)x - w / 2.0) + 0.5 and Y = (h / 2.0 - (double)y) - 0.5 (main.js:186), o = origin,
+ * ax, ay, az = the axes, per component c, every operation in binary64 without FMA contraction, in the order written:
+ *   RT_VIEW_REFERENCE  org = o; main.js:186-193 operation for operation (quirk q1: dist is indexed by COMPONENT): with d = (X, Y, proj_d),
+ *                      target[c] = ((o[c] + ax[c] * d[c]) + ay[c] * d[c]) + az[c] * d[c], dir[c] = target[c] - o[c].  A pinhole only
+ *                      while the axes are the world's; the strict frame's own rays.
+ *   RT_VIEW_PINHOLE    org = o; dir[c] = (ax[c] * X + ay[c] * Y) + az[c] * proj_d.  A true pinhole for any basis.
+ *   RT_VIEW_ORTHO      org[c] = (o[c] + ax[c] * (X * scale)) + ay[c] * (Y * scale); dir = az.  `scale` is world units per pixel.
+ *   RT_VIEW_EQUIRECT   org = o; with {sl, cl} = lon[2x], lon[2x + 1] and {sa, ca} = lat[2y], lat[2y + 1]: l0 = ca * sl, l1 = sa,
+ *                      l2 = ca * cl, dir[c] = (ax[c] * l0 + ay[c] * l1) + az[c] * l2.
+ * and dir then goes through the reference's normal3D (multiplied by 1 / |dir|, a zero vector left as it is).  proj_d is
+ * (w / 2.0) / tan((fov_deg * M_PI / 180.0) / 2.0), the host's tan, as for a frame.  No transcendental function runs on the device: the
+ * panorama's tables hold per column the sine and cosine of lon_x = 2.0 * M_PI * (x + 0.5) / w - M_PI and per row those of
+ * lat_y = M_PI / 2.0 - M_PI * (y + 0.5) / h, made once per frame size (rt_view_equirect_tables, or the caller's own).  With axes
+ * (1,0,0), (0,1,0), (0,0,-1) the centre of the panorama looks along -z. */
+enum { RT_VIEW_REFERENCE = 0, RT_VIEW_PINHOLE = 1, RT_VIEW_ORTHO = 2, RT_VIEW_EQUIRECT = 3 };
+typedef struct rt_view {
+  uint32_t model, reserved;                 /* reserved = 0 */
+  double origin[3], axis_x[3], axis_y[3], axis_z[3];
+  double fov_deg;                            /* REFERENCE, PINHOLE: 0 < fov_deg < 180 */
+  double scale;                              /* ORTHO: finite, > 0 */
+  const double *lon, *lat;                   /* EQUIRECT: 2 w and 2 h doubles {sin, cos}, 16-byte aligned; else ignored */
+} rt_view;
+
+/* Host logic, no GPU, no rt_init.  RT_ERR_INVALID: NULL; an unknown model or reserved != 0; w == 0, h == 0 or w * h >= 2^31 (in 64
+ * bits); a non-finite origin or axis component; fov_deg outside (0, 180) or NaN for the two perspective models; scale not finite or
+ * <= 0 for ORTHO; NULL or misaligned (16 bytes) tables for EQUIRECT.  A zero axis is valid: the arithmetic stays finite for it. */
+int rt_view_validate(const rt_view *v, uint32_t w, uint32_t h);
+
+/* Host logic: the panorama's tables for a w x h view, lon_2w[2x], lon_2w[2x + 1] = sin, cos of lon_x and lat_2h[2y], lat_2h[2y + 1] =
+ * sin, cos of lat_y (the host's libm).  RT_ERR_INVALID: a NULL pointer, w == 0 or h == 0. */
+int rt_view_equirect_tables(uint32_t w, uint32_t h, double *lon_2w, double *lat_2h);
+
+/* Host logic: rows [first_row, first_row + rows) of the view into out (rows * w records of six doubles, row order; the tables in HOST
+ * memory).  The restatement the device is held to, bit for bit.  RT_ERR_INVALID: what rt_view_validate refuses, a NULL out,
+ * first_row + rows > h; rows == 0 is RT_OK and writes nothing. */
+int rt_view_rays(const rt_view *v, uint32_t w, uint32_t h, uint32_t first_row, uint32_t rows, double *out);
+
+/* The same rows into d_rays (DEVICE memory, 16-byte aligned, rows * w * 6 doubles), asynchronous on `hip_stream` (NULL = the
+ * library's stream of `device`); for EQUIRECT lon and lat are DEVICE pointers.  It needs no scene and waits for no edit.
+ * RT_ERR_INVALID as rt_view_rays, and for a NULL or misaligned d_rays, before a device is touched. */
+int rt_view_rays_device(int device, const rt_view *v, uint32_t w, uint32_t h, uint32_t first_row, uint32_t rows,
+                        double *d_rays, void *hip_stream);
+
+/* Host arithmetic: the workspace rt_scene_trace_view_device prefers for a w x h view: 48 w h bytes, the whole view in one band (smaller
+ * bands measured slower, docs/EVIDENCE.md "Views"; a caller short of memory hands in fewer rows and gets the same bytes).  0 for w == 0, h == 0 or w * h >= 2^31. */
+size_t rt_view_work_bytes(uint32_t w, uint32_t h);
+
+/* intersectWorld for every ray of the view, outputs in frame order: ray i = y * w + x.  rgba is the w x h frame in ImageData.data's
+ * layout; rgb and hits as for rt_scene_trace_rays_device, and so are segs, every-output-NULL, output alignment, the scratch
+ * reservation, stats (kernel_ms covers generation and trace of all bands) and the thread rules.  The view is processed in bands of
+ * whole rows: each band is generated into d_work (DEVICE memory, 16-byte aligned, work_bytes >= 48 w: one row is the smallest band)
+ * and traced by the rt_trace_rays launch with its base, so ray i keeps pix = i - the stars of a REFERENCE view with the scene's camera
+ * and fov are the RT_FLAG_STRICT_FP frame's, and so is every byte - and no result depends on the band size.  The scene's own camera,
+ * fov_deg, supersample, launch tables and RT_FLAG_* play no part; its current spheres, lights and stars seed do.  For EQUIRECT lon
+ * and lat are DEVICE pointers.  RT_ERR_STATE: a NULL scene; RT_ERR_INVALID: what rt_view_validate refuses, segs > RT_MAX_SEGS, NULL
+ * d_out or every output NULL, misaligned outputs, a NULL or misaligned d_work, work_bytes below one row. */
+int rt_scene_trace_view_device(rt_scene_dev *scene, const rt_view *v, uint32_t w, uint32_t h, uint32_t segs,
+                               const rt_ray_outputs *d_out, void *d_work, size_t work_bytes, void *hip_stream, rt_stats *stats);
+
+/* Host form: rt_render's resident scene (a blob that differs from the resident one only in what an edit reaches is not uploaded
+ * again, as for rt_trace_rays), outputs in HOST memory, synchronous, on GPU 0, in chunks of whole rows of at most 2^18 rays (a single
+ * row longer than that is its own chunk).  No ray crosses the link; for EQUIRECT lon and lat are HOST memory and the call uploads
+ * them once, (w + h) * 16 bytes. */
+int rt_trace_view(const void *scene_blob, size_t blob_bytes, const rt_view *v, uint32_t w, uint32_t h, uint32_t segs,
+                  const rt_ray_outputs *host_out, rt_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
