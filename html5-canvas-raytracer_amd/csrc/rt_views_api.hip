@@ -3,9 +3,13 @@
 // generated into the caller's workspace and handed to the launch of a caller's ray list (rt_launch.hip: trace_rays_launch) with its
 // base, so ray i = y * w + x keeps pix = i and no trace kernel knows that the list was made here.  The generator reads nothing of a
 // scene: rt_view_rays_device waits for no edit and takes no part in rt_scene_sync.h; the trace launch behind it waits as it always does.
+// Sampled views (rt_view_sample, rt_view_lens; rt_view_samples.h / .hip) run the same band loop with n generate-and-trace steps per
+// band, an accumulator and a resolve: the second half of this file.
 #include "rt_api_internal.h"
 #include "rt_views.h"
+#include "rt_view_samples.h"
 
+static_assert(sizeof(rt_view_sample) == 32 && sizeof(rt_view_lens) == 16 && sizeof(rt_view_sample_params) == 48, "a sample travels as 32 bytes, with its lens as 48");
 static_assert(RT_VIEWS_REFERENCE == RT_VIEW_REFERENCE && RT_VIEWS_PINHOLE == RT_VIEW_PINHOLE && RT_VIEWS_ORTHO == RT_VIEW_ORTHO &&
               RT_VIEWS_EQUIRECT == RT_VIEW_EQUIRECT, "rt_views.h restates the models of include/rt_hip.h");
 
@@ -76,6 +80,71 @@ int trace_view_bands(rt_scene_dev *s, const rt_view_params &P, uint32_t row0, ui
     const rt_ray_outputs band = {out.rgb ? out.rgb + 3u * at : nullptr, out.rgba ? out.rgba + 4u * at : nullptr, out.hits ? out.hits + at : nullptr};
     if (int rc = trace_rays_launch(s, m * P.w, y * P.w, d_work, nullptr, segs, band, stream, nullptr)) return rc;
   }
+  return RT_OK;
+}
+
+// ---- sampled views: sub-pixel offsets and a thin lens (rt_view_samples.h), averaged on the GPU
+constexpr uint32_t RT_VIEW_SAMPLE_BAND_BYTES = 96u;      // per pixel of a band: rays 48, one sample's rgb 24, the accumulator 24
+
+int view_samples_check(const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens, uint32_t n, const rt_view_sample *samples, const char *what) {
+  if (int rc = view_check(v, w, h, what)) return rc;
+  if (n < 1u || n > RT_VIEW_SAMPLES_MAX) return fail(RT_ERR_INVALID, "%s: %u samples not in 1..%u", what, n, RT_VIEW_SAMPLES_MAX);
+  if ((uint64_t)n * w * h > (1ull << 32)) return fail(RT_ERR_INVALID, "%s: %u samples of a %ux%u view: n * w * h above 2^32", what, n, w, h);
+  if (!samples) return fail(RT_ERR_INVALID, "%s: NULL samples", what);
+  for (uint32_t s = 0; s < n; s++)
+    if (!std::isfinite(samples[s].dx) || !std::isfinite(samples[s].dy) || !std::isfinite(samples[s].lu) || !std::isfinite(samples[s].lv))
+      return fail(RT_ERR_INVALID, "%s: sample %u has a non-finite component", what, s);
+  if (lens) {
+    if (!(std::isfinite(lens->radius) && lens->radius >= 0.0)) return fail(RT_ERR_INVALID, "%s: lens radius %g negative or not finite", what, lens->radius);
+    if (lens->radius > 0.0 && v->model != RT_VIEW_PINHOLE) return fail(RT_ERR_INVALID, "%s: a lens is for RT_VIEW_PINHOLE only (model %u)", what, v->model);
+    if (lens->radius > 0.0 && !(std::isfinite(lens->focus) && lens->focus > 0.0)) return fail(RT_ERR_INVALID, "%s: lens focus %g not finite and above 0", what, lens->focus);
+  }
+  return RT_OK;
+}
+
+rt_view_sample_params sample_params(const rt_view_sample &s, const rt_view_lens *lens) {
+  const bool on = lens && lens->radius > 0.0;
+  return rt_view_sample_params{s.dx, s.dy, s.lu, s.lv, on ? lens->radius : 0.0, on ? lens->focus : 0.0};
+}
+
+// the view with the panorama's tables of sample `table` (one table per sample back to back: 2 w and 2 h doubles each)
+rt_view_params view_params_of_table(rt_view_params P, uint32_t table) {
+  if (P.model == RT_VIEWS_EQUIRECT) { P.lon += 2u * (size_t)P.w * table; P.lat += 2u * (size_t)P.h * table; }
+  return P;
+}
+
+#define VIEW_LAUNCH(call, name) do { const int err_ = (call); if (err_ != 0) return fail(RT_ERR_DEVICE, name " launch: %s", hipGetErrorString((hipError_t)err_)); } while (0)
+
+// The view's rows in bands of at most band_rows, n samples per pixel.  d_work holds, for band_rows * w pixels, the rays (48 bytes each),
+// one sample's rgb (24) and the accumulator (24).  Per band and per sample in order: generate, trace with base = s * w * h + y * w
+// (sample 0 straight into the accumulator, the others into the rgb slab), accumulate; the last sample's addition is the resolve's.
+// One stream: every launch comes behind the one that wrote what it reads.
+int trace_view_sample_bands(rt_scene_dev *s, const rt_view_params &P, const rt_view_lens *lens, uint32_t n, const rt_view_sample *samples, uint32_t row0,
+                            uint32_t row_end, uint32_t band_rows, uint32_t segs, const rt_ray_outputs &out, uint32_t out_row0, void *d_work,
+                            hipStream_t stream) {
+  const size_t band = (size_t)band_rows * P.w;
+  double *rays = (double *)d_work, *slab = rays + 6u * band, *acc = slab + 3u * band;
+  for (uint32_t y = row0; y < row_end; y += band_rows) {
+    const uint32_t m = row_end - y < band_rows ? row_end - y : band_rows, pixels = m * P.w;
+    for (uint32_t k = 0; k < n; k++) {
+      const rt_view_params Pk = view_params_of_table(P, k);
+      const rt_view_sample_params S = sample_params(samples[k], lens);
+      VIEW_LAUNCH(rt_launch_view_sample_rays(&Pk, &S, y, m, rays, (void *)stream), "view sample generator");
+      const rt_ray_outputs into = {k == 0 ? acc : slab, nullptr, nullptr};
+      const uint32_t base = (uint32_t)((uint64_t)k * P.w * P.h + (uint64_t)y * P.w);           // (n * w * h <= 2^32: base + pixels - 1 < 2^32)
+      if (int rc = trace_rays_launch(s, pixels, base, rays, nullptr, segs, into, stream, nullptr)) return rc;
+      if (k != 0 && k + 1u != n) VIEW_LAUNCH(rt_launch_view_accumulate(acc, slab, pixels, (void *)stream), "view accumulate");
+    }
+    const size_t at = (size_t)(y - out_row0) * P.w;       // of the band's first pixel in the outputs
+    VIEW_LAUNCH(rt_launch_view_resolve(acc, n > 1u ? slab : nullptr, n, pixels, out.rgb ? out.rgb + 3u * at : nullptr, out.rgba ? out.rgba + 4u * at : nullptr,
+                                       (void *)stream), "view resolve");
+  }
+  return RT_OK;
+}
+
+int view_sample_outputs_check(uint32_t segs, const rt_ray_outputs *out, const char *what) {
+  if (int rc = view_outputs_check(segs, out, what)) return rc;
+  if (out->hits) return fail(RT_ERR_INVALID, "%s: hits must be NULL (a mean of hit records means nothing)", what);
   return RT_OK;
 }
 }  // namespace
@@ -182,6 +251,149 @@ extern "C" int rt_trace_view(const void *blob, size_t bytes, const rt_view *v, u
     if (ho->rgb) HIP_TRY(hipMemcpyAsync(ho->rgb + 3u * at, d_rgb.h, n * 24u, hipMemcpyDeviceToHost, stream));
     if (ho->rgba) HIP_TRY(hipMemcpyAsync(ho->rgba + 4u * at, d_rgba.h, n * 4u, hipMemcpyDeviceToHost, stream));
     if (ho->hits) HIP_TRY(hipMemcpyAsync(ho->hits + at, d_hits.h, n * sizeof(rt_hit), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = kernel_ms;
+    stats->pixels = (uint64_t)w * h;
+    stats->total_ms = clock.host_ms();
+  }
+  return RT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- sampled views
+extern "C" int rt_view_samples_validate(const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens, uint32_t n, const rt_view_sample *samples) {
+  return view_samples_check(v, w, h, lens, n, samples, "rt_view_samples_validate");
+}
+
+extern "C" int rt_view_samples_grid(uint32_t k, rt_view_sample *out) {
+  if (k < 1u || k > 32u || !out) return fail(RT_ERR_INVALID, "rt_view_samples_grid: k %u not in 1..32, or a NULL output", k);
+  for (uint32_t j = 0; j < k; j++)
+    for (uint32_t i = 0; i < k; i++) {
+      rt_view_sample &s = out[(size_t)j * k + i];
+      s.dx = ((double)i + 0.5) / (double)k - 0.5;
+      s.dy = ((double)j + 0.5) / (double)k - 0.5;
+      // Shirley's concentric map of (a, b) = (2 dx, 2 dy) in [-1, 1]^2 onto the unit disk
+      const double a = 2.0 * s.dx, b = 2.0 * s.dy;
+      double r, phi;
+      if (a == 0.0 && b == 0.0) { r = 0.0; phi = 0.0; }
+      else if (fabs(a) > fabs(b)) { r = a; phi = (M_PI / 4.0) * (b / a); }
+      else { r = b; phi = M_PI / 2.0 - (M_PI / 4.0) * (a / b); }
+      s.lu = r * cos(phi); s.lv = r * sin(phi);
+    }
+  return RT_OK;
+}
+
+extern "C" int rt_view_equirect_sample_tables(uint32_t w, uint32_t h, uint32_t n, const rt_view_sample *samples, double *lon, double *lat) {
+  if (!lon || !lat || !samples || w == 0 || h == 0 || n == 0) return fail(RT_ERR_INVALID, "rt_view_equirect_sample_tables: a NULL pointer, w == 0, h == 0 or n == 0");
+  for (uint32_t s = 0; s < n; s++) {
+    double *lo = lon + 2u * (size_t)w * s, *la = lat + 2u * (size_t)h * s;
+    for (uint32_t x = 0; x < w; x++) { const double a = rt_view_sample_lon(x, w, samples[s].dx); lo[2u * (size_t)x] = sin(a); lo[2u * (size_t)x + 1u] = cos(a); }
+    for (uint32_t y = 0; y < h; y++) { const double a = rt_view_sample_lat(y, h, samples[s].dy); la[2u * (size_t)y] = sin(a); la[2u * (size_t)y + 1u] = cos(a); }
+  }
+  return RT_OK;
+}
+
+extern "C" int rt_view_sample_rays(const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens, const rt_view_sample *sample, uint32_t table,
+                                   uint32_t first_row, uint32_t rows, double *out) {
+  const char *what = "rt_view_sample_rays";
+  int rc = view_samples_check(v, w, h, lens, 1u, sample, what);
+  if (rc) return rc;
+  if (!out) return fail(RT_ERR_INVALID, "%s: NULL output", what);
+  if ((rc = view_rows_check(h, first_row, rows, what))) return rc;
+  const rt_view_params P = view_params_of_table(view_params(*v, w, h), table);
+  const rt_view_sample_params S = sample_params(*sample, lens);
+  rt_view_sample_rays_host(&P, &S, first_row, rows, out);
+  return RT_OK;
+}
+
+extern "C" int rt_view_sample_rays_device(int device, const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens, const rt_view_sample *sample,
+                                          uint32_t table, uint32_t first_row, uint32_t rows, double *d_rays, void *hip_stream) {
+  const char *what = "rt_view_sample_rays_device";
+  int rc = view_samples_check(v, w, h, lens, 1u, sample, what);
+  if (rc) return rc;
+  if (!d_rays || ((uintptr_t)d_rays & 15u)) return fail(RT_ERR_INVALID, "%s: NULL or misaligned ray list (16 bytes)", what);
+  if ((rc = view_rows_check(h, first_row, rows, what))) return rc;
+  if (rows == 0) return RT_OK;
+  hipStream_t stream = nullptr;
+  if ((rc = device_stream(device, hip_stream, &stream))) return rc;
+  const rt_view_params P = view_params_of_table(view_params(*v, w, h), table);
+  const rt_view_sample_params S = sample_params(*sample, lens);
+  VIEW_LAUNCH(rt_launch_view_sample_rays(&P, &S, first_row, rows, d_rays, (void *)stream), "view sample generator");
+  return RT_OK;
+}
+
+extern "C" size_t rt_view_samples_work_bytes(uint32_t w, uint32_t h) {
+  // the whole view in one band, as rt_view_work_bytes and for its reason: a band costs n trace launches, and small launches are dear
+  return view_size_ok(w, h) ? (size_t)w * h * RT_VIEW_SAMPLE_BAND_BYTES : 0;
+}
+
+extern "C" int rt_scene_trace_view_samples_device(rt_scene_dev *s, const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens, uint32_t n,
+                                                  const rt_view_sample *samples, uint32_t segs, const rt_ray_outputs *d_out, void *d_work, size_t work_bytes,
+                                                  void *hip_stream, rt_stats *stats) {
+  const char *what = "rt_scene_trace_view_samples_device";
+  if (!s) return fail(RT_ERR_STATE, "%s: NULL scene handle", what);
+  int rc = view_samples_check(v, w, h, lens, n, samples, what);
+  if (rc) return rc;
+  if ((rc = view_sample_outputs_check(segs, d_out, what))) return rc;
+  if (!d_work || ((uintptr_t)d_work & 15u)) return fail(RT_ERR_INVALID, "%s: NULL or misaligned workspace (16 bytes)", what);
+  const uint64_t row_bytes = (uint64_t)w * RT_VIEW_SAMPLE_BAND_BYTES;
+  if (work_bytes < row_bytes) return fail(RT_ERR_INVALID, "%s: work_bytes %llu below one row of a band, %llu", what, (unsigned long long)work_bytes, (unsigned long long)row_bytes);
+  hipStream_t stream = nullptr;
+  if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
+  const uint64_t fit = work_bytes / row_bytes;
+  const uint32_t band_rows = fit < h ? (uint32_t)fit : h;
+  stats_clock clock;
+  if ((rc = clock.start(stats, stream))) return rc;
+  if ((rc = trace_view_sample_bands(s, view_params(*v, w, h), lens, n, samples, 0u, h, band_rows, segs, *d_out, 0u, d_work, stream))) return rc;
+  return clock.finish(stats, (uint64_t)w * h);
+}
+
+extern "C" int rt_trace_view_samples(const void *blob, size_t bytes, const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens, uint32_t n,
+                                     const rt_view_sample *samples, uint32_t segs, const rt_ray_outputs *ho, rt_stats *stats) {
+  const char *what = "rt_trace_view_samples";
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  if ((rc = view_samples_check(v, w, h, lens, n, samples, what))) return rc;
+  if ((rc = view_sample_outputs_check(segs, ho, what))) return rc;
+  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
+  std::lock_guard<std::mutex> lk(G.mu);
+  stats_clock clock;
+  rt_scene_dev *s = nullptr;
+  if ((rc = resident_scene(0, blob, bytes, &s))) return rc;
+  if ((rc = ensure_device(0))) return rc;
+  hipStream_t stream = G.dev[0].stream;
+  // chunks of whole rows of at most RT_VIEW_CHUNK_RAYS pixels; a longer row is its own chunk
+  uint64_t chunk_rows = RT_VIEW_CHUNK_RAYS / w;
+  if (chunk_rows < 1u) chunk_rows = 1u;
+  if (chunk_rows > h) chunk_rows = h;
+  const size_t chunk = (size_t)chunk_rows * w;
+  device_mem d_work, d_rgb, d_rgba, d_lon, d_lat;      // of one chunk; the panorama's tables of all samples (released on every way out)
+  HIP_TRY(hipMalloc(&d_work.h, chunk * RT_VIEW_SAMPLE_BAND_BYTES));
+  if (ho->rgb) HIP_TRY(hipMalloc(&d_rgb.h, chunk * 24u));
+  if (ho->rgba) HIP_TRY(hipMalloc(&d_rgba.h, chunk * 4u));
+  rt_view_params P = view_params(*v, w, h);
+  if (v->model == RT_VIEW_EQUIRECT) {
+    HIP_TRY(hipMalloc(&d_lon.h, (size_t)w * 16u * n));
+    HIP_TRY(hipMalloc(&d_lat.h, (size_t)h * 16u * n));
+    HIP_TRY(hipMemcpyAsync(d_lon.h, v->lon, (size_t)w * 16u * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_lat.h, v->lat, (size_t)h * 16u * n, hipMemcpyHostToDevice, stream));
+    P.lon = (const double *)d_lon.h; P.lat = (const double *)d_lat.h;
+  }
+  const rt_ray_outputs dout = {(double *)d_rgb.h, (uint8_t *)d_rgba.h, nullptr};
+  double kernel_ms = 0.0;
+  for (uint32_t y = 0; y < h; y += (uint32_t)chunk_rows) {
+    const uint32_t m = h - y < chunk_rows ? h - y : (uint32_t)chunk_rows;
+    const size_t at = (size_t)y * w, px = (size_t)m * w;
+    stats_clock step;
+    rt_stats st;
+    if ((rc = step.start(stats, stream))) return rc;
+    if ((rc = trace_view_sample_bands(s, P, lens, n, samples, y, y + m, m, segs, dout, y, d_work.h, stream))) return rc;
+    if ((rc = step.finish(stats ? &st : nullptr, px))) return rc;
+    if (stats) kernel_ms += st.kernel_ms;
+    if (ho->rgb) HIP_TRY(hipMemcpyAsync(ho->rgb + 3u * at, d_rgb.h, px * 24u, hipMemcpyDeviceToHost, stream));
+    if (ho->rgba) HIP_TRY(hipMemcpyAsync(ho->rgba + 4u * at, d_rgba.h, px * 4u, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
   }
   if (stats) {

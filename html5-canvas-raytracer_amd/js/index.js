@@ -194,15 +194,42 @@ const views = {
     return [-1, 1].map((s) => Object.assign({}, view, {origin: view.origin.map((o, c) => (s < 0 ? o - u[c] * half : o + u[c] * half))}));
   },
   bytes: viewBytes,
+  // sampled views (include/rt_hip.h: rt_view_sample, rt_view_lens)
+  //   views.sampleGrid(k)         the k x k pattern, k in 1..32, through the library (rt_view_samples_grid): [{dx, dy, lu, lv}], sub-pixel
+  //                               offsets in pixels (dy downwards) and their concentric map onto the unit disk - one pattern for
+  //                               antialiasing and the lens
+  //   views.lens(radius, focus)   a thin lens for a pinhole view, focused on the plane `focus` away along axisZ
+  sampleGrid: (k) => {
+    const a = native().viewSamplesGrid(k);
+    return Array.from({length: a.length / 4}, (_, i) => ({dx: a[4 * i], dy: a[4 * i + 1], lu: a[4 * i + 2], lv: a[4 * i + 3]}));
+  },
+  lens: (radius, focus) => ({radius: Number(radius), focus: Number(focus)}),
 };
+
+function packSamples(samples) {
+  if (samples instanceof Float64Array) return samples;
+  const a = new Float64Array(4 * samples.length);
+  samples.forEach((s, i) => { a[4 * i] = s.dx || 0; a[4 * i + 1] = s.dy || 0; a[4 * i + 2] = s.lu || 0; a[4 * i + 3] = s.lv || 0; });
+  return a;
+}
 
 // intersectWorld for every ray of `view` at w x h, in frame order (ray y w + x): traceRays' result shape.  opts: segs, and which
 // outputs to compute - rgba (default true) the Uint8ClampedArray that is a w x h ImageData.data, rgb Float64Array 3 per ray, hits.
 // The scene's own camera plays no part.
+// opts.samples (views.sampleGrid(k), or the caller's own [{dx, dy, lu, lv}]) and / or opts.lens (views.lens, pinhole views): one trace
+// per sample, averaged on the GPU in binary64 (rt_trace_view_samples) - rgb is the mean, rgba the mean through the store rule; no hits.
+// A lens without samples takes the one zero sample: the pinhole itself.
 function traceView(sceneObj, view, w, h, opts) {
   if (!view || !Number.isInteger(view.model)) throw new TypeError('traceView: view must come from views.reference / pinhole / ortho / equirect');
   if (!inited) init(opts && opts.maxDevices);
   const o = opts || {};
+  if (o.samples || o.lens) {
+    if (o.hits) throw new TypeError('traceView: a sampled view returns no hits (a mean of hit records means nothing)');
+    const samples = packSamples(o.samples || [{dx: 0, dy: 0, lu: 0, lv: 0}]);
+    const t = view.model === VIEW_EQUIRECT ? native().equirectSampleTables(w, h, samples) : {lon: null, lat: null};
+    return native().traceViewSamples(new Uint8Array(flattenScene(sceneObj)), viewBytes(view), t.lon, t.lat, w, h, samples,
+      o.lens ? new Float64Array([o.lens.radius, o.lens.focus]) : null, o.segs || 0, !!o.rgb, o.rgba !== false);
+  }
   const r = native().traceView(new Uint8Array(flattenScene(sceneObj)), viewBytes(view), view.lon || null, view.lat || null, w, h, o.segs || 0,
     !!o.rgb, o.rgba !== false, !!o.hits);
   if (r.hits) for (const hit of r.hits) if (hit) hit.object = sceneObj.objects[hit.index];

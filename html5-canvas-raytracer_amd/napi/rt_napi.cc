@@ -20,6 +20,10 @@
 //           traceView(blob, view: Uint8Array (the 136 bytes of rt_view, table pointers ignored), lon: Float64Array | null, lat: Float64Array | null,
 //           w, h, segs, wantRgb, wantRgba, wantHits) -> traceRays' result for the view's w x h rays, generated on the GPU (rt_trace_view)
 //           equirectTables(w, h) -> {lon: Float64Array (2 w), lat: Float64Array (2 h)} (rt_view_equirect_tables)
+//           viewSamplesGrid(k) -> Float64Array (dx, dy, lu, lv per sample: rt_view_samples_grid)
+//           equirectSampleTables(w, h, samples) -> {lon, lat}: one table per sample (rt_view_equirect_sample_tables)
+//           traceViewSamples(blob, view, lon, lat, w, h, samples: Float64Array (4 per sample), lens: Float64Array (radius, focus) | null, segs,
+//           wantRgb, wantRgba) -> {rgb, rgba, hits: null, kernel_ms}: the mean of one trace per sample (rt_trace_view_samples)
 //           (these, and renderAdaptive, are not enumerable: the enumerable surface is the frame API of the first revision)
 // Every failure of the library becomes a thrown JS Error carrying rt_last_error().
 //
@@ -660,6 +664,138 @@ napi_value TraceView(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// a Float64Array argument -> its numbers (nullptr / 0 for anything else)
+const double *f64_array(napi_env env, napi_value v, size_t *len) {
+  bool is_ta = false;
+  *len = 0;
+  if (napi_is_typedarray(env, v, &is_ta) != napi_ok || !is_ta) return nullptr;
+  napi_typedarray_type t; napi_value ab; size_t off; void *data = nullptr;
+  napi_get_typedarray_info(env, v, &t, len, &data, &ab, &off);
+  if (t != napi_float64_array) { *len = 0; return nullptr; }
+  return (const double *)data;
+}
+
+// viewSamplesGrid(k): the k x k pattern (rt_view_samples_grid) as a Float64Array of 4 k k numbers: dx, dy, lu, lv per sample
+napi_value ViewSamplesGrid(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  uint32_t k = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 1 || napi_get_value_uint32(env, argv[0], &k) != napi_ok || k < 1 || k > 32) {
+    napi_throw_type_error(env, nullptr, "viewSamplesGrid(k): k in 1..32");
+    return nullptr;
+  }
+  napi_value ab, v;
+  void *data = nullptr;
+  NAPI_TRY(napi_create_arraybuffer(env, (size_t)k * k * sizeof(rt_view_sample), &data, &ab));
+  const int rc = rt_view_samples_grid(k, (rt_view_sample *)data);
+  if (rc != RT_OK) return throw_rt(env, "rt_view_samples_grid", rc);
+  NAPI_TRY(napi_create_typedarray(env, napi_float64_array, 4u * (size_t)k * k, ab, 0, &v));
+  return v;
+}
+
+// equirectSampleTables(w, h, samples: Float64Array (4 per sample)) -> {lon: Float64Array (n 2 w), lat: Float64Array (n 2 h)}: one table
+// per sample back to back (rt_view_equirect_sample_tables)
+napi_value EquirectSampleTables(napi_env env, napi_callback_info info) {
+  size_t argc = 3, len = 0;
+  napi_value argv[3];
+  uint32_t w = 0, h = 0;
+  const double *samples = nullptr;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 3 || napi_get_value_uint32(env, argv[0], &w) != napi_ok ||
+      napi_get_value_uint32(env, argv[1], &h) != napi_ok || w == 0 || h == 0 || (uint64_t)w * h >= (1ull << 31) ||
+      !(samples = f64_array(env, argv[2], &len)) || len == 0 || len % 4u != 0 || len / 4u > 1024u) {
+    napi_throw_type_error(env, nullptr, "equirectSampleTables(w, h, samples): a view size with w * h below 2^31, a Float64Array of 4 numbers per sample, 1..1024 samples");
+    return nullptr;
+  }
+  const uint32_t n = (uint32_t)(len / 4u);
+  napi_value ab_lon, ab_lat, res, v;
+  void *lon = nullptr, *lat = nullptr;
+  NAPI_TRY(napi_create_arraybuffer(env, (size_t)w * 16u * n, &lon, &ab_lon));
+  NAPI_TRY(napi_create_arraybuffer(env, (size_t)h * 16u * n, &lat, &ab_lat));
+  const int rc = rt_view_equirect_sample_tables(w, h, n, (const rt_view_sample *)samples, (double *)lon, (double *)lat);
+  if (rc != RT_OK) return throw_rt(env, "rt_view_equirect_sample_tables", rc);
+  napi_create_object(env, &res);
+  napi_create_typedarray(env, napi_float64_array, 2u * (size_t)w * n, ab_lon, 0, &v); napi_set_named_property(env, res, "lon", v);
+  napi_create_typedarray(env, napi_float64_array, 2u * (size_t)h * n, ab_lat, 0, &v); napi_set_named_property(env, res, "lat", v);
+  return res;
+}
+
+// traceViewSamples(blob, view, lon, lat, w, h, samples: Float64Array (4 per sample), lens: Float64Array (radius, focus) | null, segs, wantRgb,
+// wantRgba): rt_trace_view_samples.  `view` as for traceView; an EQUIRECT view's tables are equirectSampleTables' for the same samples.
+napi_value TraceViewSamples(napi_env env, napi_callback_info info) {
+  size_t argc = 11;
+  napi_value argv[11];
+  bool is_ta = false, is_view = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 8 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
+      napi_is_typedarray(env, argv[1], &is_view) != napi_ok || !is_view) {
+    napi_throw_type_error(env, nullptr, "traceViewSamples(blob: Uint8Array, view: Uint8Array, lon, lat, w, h, samples, lens[, segs, wantRgb, wantRgba])");
+    return nullptr;
+  }
+  napi_typedarray_type bt, vt; napi_value ab; size_t off, blob_len = 0, view_len = 0;
+  void *blob_data = nullptr, *view_data = nullptr;
+  napi_get_typedarray_info(env, argv[0], &bt, &blob_len, &blob_data, &ab, &off);
+  napi_get_typedarray_info(env, argv[1], &vt, &view_len, &view_data, &ab, &off);
+  uint32_t w = 0, h = 0, segs = 0;
+  size_t table_len[2] = {0, 0}, samples_len = 0, lens_len = 0;
+  const double *table_data[2] = {f64_array(env, argv[2], &table_len[0]), f64_array(env, argv[3], &table_len[1])};
+  const double *samples = f64_array(env, argv[6], &samples_len), *lens_data = f64_array(env, argv[7], &lens_len);
+  if ((bt != napi_uint8_array && bt != napi_uint8_clamped_array) || vt != napi_uint8_array || view_len != sizeof(rt_view) ||
+      napi_get_value_uint32(env, argv[4], &w) != napi_ok || napi_get_value_uint32(env, argv[5], &h) != napi_ok || !samples || samples_len == 0 ||
+      samples_len % 4u != 0 || samples_len / 4u > 1024u || (lens_data && lens_len != 2)) {
+    napi_throw_type_error(env, nullptr, "traceViewSamples: the blob must be a Uint8Array, the view the 136 bytes of an rt_view, w and h non-negative integers, "
+                                        "samples a Float64Array of 4 numbers per sample (1..1024 samples), lens null or a Float64Array of 2");
+    return nullptr;
+  }
+  const uint32_t n_samples = (uint32_t)(samples_len / 4u);
+  rt_view view;
+  memcpy(&view, view_data, sizeof view);
+  view.lon = view.lat = nullptr;
+  if (view.model == RT_VIEW_EQUIRECT && (table_len[0] != 2u * (size_t)w * n_samples || table_len[1] != 2u * (size_t)h * n_samples)) {
+    napi_throw_type_error(env, nullptr, "traceViewSamples: an equirect view needs lon and lat, Float64Arrays of n 2 w and n 2 h numbers");
+    return nullptr;
+  }
+  const bool sized = w != 0 && h != 0 && (uint64_t)w * h < (1ull << 31);       // (anything else the library refuses: no buffer is sized from it)
+  bool want[2] = {false, true};
+  if (argc >= 9) napi_get_value_uint32(env, argv[8], &segs);
+  for (size_t i = 0; i < 2 && 9 + i < argc; i++) napi_get_value_bool(env, argv[9 + i], &want[i]);
+  const size_t n = sized ? (size_t)w * h : 0;
+  // the library wants the blob 8-byte and the tables 16-byte aligned: one aligned copy holds all three
+  const bool tables = view.model == RT_VIEW_EQUIRECT;
+  const size_t blob_room = (blob_len + 15) & ~(size_t)15, lon_room = tables ? table_len[0] * 8u : 0, lat_room = tables ? table_len[1] * 8u : 0;
+  uint8_t *mem = (uint8_t *)aligned_alloc(16, blob_room + lon_room + lat_room + 16u);
+  napi_value ab_rgb = nullptr, ab_rgba = nullptr, res, v;
+  void *p_rgb = nullptr, *p_rgba = nullptr;
+  if (!mem || (want[0] && napi_create_arraybuffer(env, n * 24u, &p_rgb, &ab_rgb) != napi_ok) ||
+      (want[1] && napi_create_arraybuffer(env, n * 4u, &p_rgba, &ab_rgba) != napi_ok)) {
+    free(mem);
+    napi_throw_error(env, nullptr, "traceViewSamples: out of memory");
+    return nullptr;
+  }
+  memcpy(mem, blob_data, blob_len);
+  if (tables) {
+    memcpy(mem + blob_room, table_data[0], lon_room);
+    memcpy(mem + blob_room + lon_room, table_data[1], lat_room);
+    view.lon = (const double *)(mem + blob_room);
+    view.lat = (const double *)(mem + blob_room + lon_room);
+  }
+  rt_view_lens lens = {0.0, 0.0};
+  if (lens_data) { lens.radius = lens_data[0]; lens.focus = lens_data[1]; }
+  const rt_ray_outputs out = {(double *)p_rgb, (uint8_t *)p_rgba, nullptr};
+  rt_stats st;
+  const int rc = rt_trace_view_samples(mem, blob_len, &view, w, h, lens_data ? &lens : nullptr, n_samples, (const rt_view_sample *)samples, segs, &out, &st);
+  free(mem);
+  if (rc != RT_OK) return throw_rt(env, "rt_trace_view_samples", rc);
+  napi_create_object(env, &res);
+  if (want[0]) napi_create_typedarray(env, napi_float64_array, 3 * n, ab_rgb, 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "rgb", v);
+  if (want[1]) napi_create_typedarray(env, napi_uint8_clamped_array, 4 * n, ab_rgba, 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "rgba", v);
+  napi_get_null(env, &v);
+  napi_set_named_property(env, res, "hits", v);
+  napi_value ms;
+  napi_create_double(env, st.kernel_ms, &ms); napi_set_named_property(env, res, "kernel_ms", ms);
+  return res;
+}
+
 // occlusion(blob, rays: Float64Array (6 per ray), length: Float64Array | null, intensity: Float64Array | null, skip: Int32Array | null,
 //           wantBlocker, bin) -> {intensity: Float64Array, blocker: Int32Array | null, kernel_ms}  (rt_occlusion / rt_occlusion_binned)
 napi_value Occlusion(napi_env env, napi_callback_info info) {
@@ -801,6 +937,9 @@ napi_value Module(napi_env env, napi_value exports) {
       {"shadeRays", nullptr, ShadeRays, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"traceView", nullptr, TraceView, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"equirectTables", nullptr, EquirectTables, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"viewSamplesGrid", nullptr, ViewSamplesGrid, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"equirectSampleTables", nullptr, EquirectSampleTables, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"traceViewSamples", nullptr, TraceViewSamples, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

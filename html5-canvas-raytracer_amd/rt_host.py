@@ -210,6 +210,17 @@ class RtView(C.Structure):
                 ("axis_z", C.c_double * 3), ("fov_deg", C.c_double), ("scale", C.c_double), ("lon", C.c_void_p), ("lat", C.c_void_p)]
 
 
+class RtViewSample(C.Structure):
+    """One sample of a sampled view (include/rt_hip.h rt_view_sample, 32 bytes): the sub-pixel offset (dx, dy) in pixels, dy downwards,
+    and the lens point (lu, lv) on the unit disk."""
+    _fields_ = [("dx", C.c_double), ("dy", C.c_double), ("lu", C.c_double), ("lv", C.c_double)]
+
+
+class RtViewLens(C.Structure):
+    """A thin lens for RT_VIEW_PINHOLE (include/rt_hip.h rt_view_lens): its radius and the distance of the plane of focus along axis_z."""
+    _fields_ = [("radius", C.c_double), ("focus", C.c_double)]
+
+
 # every symbol include/rt_hip.h declares: (restype, argtypes)
 ABI = {
     "rt_init": (C.c_int, [C.c_int]),
@@ -297,6 +308,18 @@ ABI = {
     "rt_scene_trace_view_device": (C.c_int, [C.c_void_p, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RtRayOutputs), C.c_void_p,
                                              C.c_size_t, C.c_void_p, C.POINTER(RtStats)]),
     "rt_trace_view": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RtRayOutputs), C.POINTER(RtStats)]),
+    "rt_view_samples_validate": (C.c_int, [C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtViewLens), C.c_uint32, C.c_void_p]),
+    "rt_view_samples_grid": (C.c_int, [C.c_uint32, C.c_void_p]),
+    "rt_view_equirect_sample_tables": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_view_sample_rays": (C.c_int, [C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtViewLens), C.POINTER(RtViewSample), C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.c_void_p]),
+    "rt_view_sample_rays_device": (C.c_int, [C.c_int, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtViewLens), C.POINTER(RtViewSample), C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_view_samples_work_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_scene_trace_view_samples_device": (C.c_int, [C.c_void_p, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtViewLens), C.c_uint32, C.c_void_p,
+                                                     C.c_uint32, C.POINTER(RtRayOutputs), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_trace_view_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtViewLens), C.c_uint32, C.c_void_p,
+                                        C.c_uint32, C.POINTER(RtRayOutputs), C.POINTER(RtStats)]),
 }
 
 RT_MAX_SEGS = 16
@@ -561,6 +584,31 @@ class Renderer:
         rc = self.lib.rt_scene_trace_view_device(self.handle, C.byref(view), w, h, segs, C.byref(out), C.c_void_p(work_ptr or 0), work_bytes,
                                                  C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
         _check(self.lib, rc, "rt_scene_trace_view_device")
+        return st
+
+    def view_sample_rays(self, view, w, h, sample, rays_ptr, lens=None, table=0, first_row=0, rows=None, stream=None):
+        """view_rays for ONE sample (an RtViewSample: sub-pixel offset and lens point) and an optional lens: the bits of
+        rt_host.view_sample_rays.  `table` is the index of the panorama table to read (EQUIRECT: DEVICE tables of several samples back to
+        back, equirect_sample_tables' layout).  Asynchronous; reads nothing of the scene."""
+        rows = h - first_row if rows is None else rows
+        rc = self.lib.rt_view_sample_rays_device(self.device, C.byref(view), w, h, C.byref(lens) if lens is not None else None, C.byref(sample), table,
+                                                 first_row, rows, C.c_void_p(rays_ptr or 0), C.c_void_p(stream or 0))
+        _check(self.lib, rc, "rt_view_sample_rays_device")
+
+    def trace_view_samples(self, view, w, h, samples, lens, rgb_ptr, rgba_ptr, work_ptr, work_bytes, segs=0, stream=None, want_stats=False):
+        """The mean of n = len(samples) traces of `view` at w x h, one per sample (view_samples_grid(k), or the caller's own pattern),
+        into DEVICE buffers in frame order (0 / None = not wanted): rgb the binary64 mean acc / n of the samples added in order, rgba
+        that mean through the store rule.  lens: None or lens(radius, focus) (PINHOLE only).  Rays, one sample's rgb and the accumulator
+        of a band live in work_ptr (DEVICE, 16-byte aligned, work_bytes >= 96 w; view_samples_work_bytes(w, h) is the size the library
+        prefers).  Sample s draws its stars with pix = s w h + y w + x.  An EQUIRECT view's tables are DEVICE pointers to one table per
+        sample (equirect_sample_tables)."""
+        arr, n = _samples_array(samples)
+        out = RtRayOutputs(rgb_ptr or None, rgba_ptr or None, None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_trace_view_samples_device(self.handle, C.byref(view), w, h, C.byref(lens) if lens is not None else None, n, arr, segs,
+                                                         C.byref(out), C.c_void_p(work_ptr or 0), work_bytes, C.c_void_p(stream or 0),
+                                                         C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_trace_view_samples_device")
         return st
 
     def occlusion(self, n, rays_ptr, length_ptr, intensity_ptr, skip_ptr, out_intensity_ptr, out_blocker_ptr, order_ptr=0, stream=None, want_stats=False):
@@ -978,6 +1026,92 @@ def trace_view(scene, v, w, h, segs=0, want=("rgba",), lib=None):
     _check(lib, lib.rt_trace_view(buf, len(blob), C.byref(v), w, h, segs, C.byref(bufs), None), "rt_trace_view")
     if records is not None:
         out["hits"] = [_hit_dict(r) for r in records[:n]]
+    return out
+
+
+# --------------------------------------------------------------------------- sampled views: sub-pixel offsets and a thin lens
+def _samples_array(samples):
+    """-> (a ctypes array of RtViewSample or None, n), from a list of RtViewSample or of (dx, dy, lu, lv) tuples."""
+    samples = list(samples) if samples is not None else []
+    n = len(samples)
+    if n == 0:
+        return None, 0
+    arr = (RtViewSample * n)()
+    for i, s in enumerate(samples):
+        arr[i] = s if isinstance(s, RtViewSample) else RtViewSample(*(float(c) for c in s))
+    return arr, n
+
+
+def view_sample(dx=0.0, dy=0.0, lu=0.0, lv=0.0):
+    """-> RtViewSample: a sub-pixel offset in pixels (dy downwards) and a lens point on the unit disk."""
+    return RtViewSample(float(dx), float(dy), float(lu), float(lv))
+
+
+def lens(radius, focus):
+    """-> RtViewLens: a thin lens of `radius` (along axis_x / axis_y) focused on the plane `focus` away along axis_z (PINHOLE views)."""
+    return RtViewLens(float(radius), float(focus))
+
+
+def view_samples_grid(k, lib=None):
+    """-> the k x k grid pattern (rt_view_samples_grid), k in 1..32: a list of k k RtViewSample, sample j k + i with
+    dx = (i + 0.5) / k - 0.5, dy = (j + 0.5) / k - 0.5 and (lu, lv) the concentric map of (2 dx, 2 dy) onto the unit disk."""
+    lib = lib or load_library()
+    arr = (RtViewSample * max(k * k, 1))()
+    _check(lib, lib.rt_view_samples_grid(k, arr), "rt_view_samples_grid")
+    return list(arr)
+
+
+def equirect_sample_tables(w, h, samples, lib=None):
+    """-> (lon, lat): the panorama's tables of len(samples) samples, one table per sample back to back (rt_view_equirect_sample_tables):
+    float64 arrays of n 2 w and n 2 h entries on 16-byte boundaries."""
+    lib = lib or load_library()
+    arr, n = _samples_array(samples)
+    lon, lat = _aligned_f64(2 * w * n), _aligned_f64(2 * h * n)
+    _check(lib, lib.rt_view_equirect_sample_tables(w, h, n, arr, C.c_void_p(lon.ctypes.data), C.c_void_p(lat.ctypes.data)), "rt_view_equirect_sample_tables")
+    return lon, lat
+
+
+def view_samples_work_bytes(w, h, lib=None):
+    """Bytes of device workspace Renderer.trace_view_samples prefers for a w x h view (host arithmetic; 0 for a size it refuses).
+    96 w - one row - is the least it accepts."""
+    return int((lib or load_library()).rt_view_samples_work_bytes(w, h))
+
+
+def view_sample_rays(v, w, h, sample, lens=None, table=0, first_row=0, rows=None, lib=None):
+    """The host probe for ONE sample (rt_view_sample_rays): rows [first_row, first_row + rows) of the sample's rays as an
+    (rows * w, 6) float64 array - what the GPU generates, bit for bit.  `table`: which of an EQUIRECT view's tables to read.  No GPU."""
+    import numpy as np
+    lib = lib or load_library()
+    rows = h - first_row if rows is None else rows
+    out = np.empty((max(rows, 0) * w, 6), np.float64)
+    s = sample if isinstance(sample, RtViewSample) else RtViewSample(*(float(c) for c in sample))
+    _check(lib, lib.rt_view_sample_rays(C.byref(v), w, h, C.byref(lens) if lens is not None else None, C.byref(s), table, first_row, rows,
+                                        C.c_void_p(out.ctypes.data)), "rt_view_sample_rays")
+    return out
+
+
+def trace_view_samples(scene, v, w, h, samples, lens=None, segs=0, want=("rgba",), lib=None):
+    """trace_view_samples(scene, view, w, h, samples) -> {"rgb": (w h, 3) float64, "rgba": (w h, 4) uint8} (the keys named in `want`):
+    the mean of len(samples) traces of the view, one per sample, averaged on GPU 0 with rt_render's resident scene
+    (rt_trace_view_samples).  An EQUIRECT view's tables are equirect_sample_tables(w, h, samples)."""
+    import numpy as np
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    want = set(want)
+    if not want or want - {"rgb", "rgba"}:
+        raise ValueError("want names some of 'rgb', 'rgba'")
+    arr, n = _samples_array(samples)
+    px = w * h
+    out = {}
+    if "rgb" in want:
+        out["rgb"] = np.empty((px, 3), np.float64)
+    if "rgba" in want:
+        out["rgba"] = np.empty((px, 4), np.uint8)
+    bufs = RtRayOutputs(out["rgb"].ctypes.data if "rgb" in out else None, out["rgba"].ctypes.data if "rgba" in out else None, None)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    _check(lib, lib.rt_trace_view_samples(buf, len(blob), C.byref(v), w, h, C.byref(lens) if lens is not None else None, n, arr, segs, C.byref(bufs), None),
+           "rt_trace_view_samples")
     return out
 
 

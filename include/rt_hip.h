@@ -784,6 +784,88 @@ int rt_scene_trace_view_device(rt_scene_dev *scene, const rt_view *v, uint32_t w
 int rt_trace_view(const void *scene_blob, size_t blob_bytes, const rt_view *v, uint32_t w, uint32_t h, uint32_t segs,
                   const rt_ray_outputs *host_out, rt_stats *stats);
 
+/* Sampled views: n rays per pixel of a view - sub-pixel offsets for antialiasing, points of a thin lens for depth of field, in the
+ * caller's own pattern - generated, traced and averaged on the GPU.  Every pixel uses the same n samples (the accumulation-buffer form:
+ * each sample is a coherent view).  No trace kernel knows about it: a generator that takes a sample stands in front of the same
+ * rt_trace_rays launch, an accumulator in binary64 and a resolve with the reference's store rule behind it.
+ *
+ * Sample s of pixel (x, y) of a w x h view; every operation in binary64 without FMA contraction, in the order written; proj_w = w / 2.0,
+ * proj_h = h / 2.0 and proj_d as for a view:
+ *   X = (((double)x - proj_w) + 0.5) + dx,  Y = ((proj_h - (double)y) - 0.5) - dy.  Offsets are in pixels, positive dy is DOWN like y;
+ *   any finite value is valid, a pattern normally stays in [-0.5, 0.5].
+ *   RT_VIEW_REFERENCE, RT_VIEW_ORTHO   the view's expressions (above) with this X and Y.
+ *   RT_VIEW_PINHOLE    raw[c] = (ax[c] * X + ay[c] * Y) + az[c] * proj_d.  Without a lens (NULL or radius == 0): org = o, dir = raw, and
+ *                      lu, lv are not read.  With a lens: f = focus / proj_d, lx = lu * radius, ly = lv * radius,
+ *                      off[c] = ax[c] * lx + ay[c] * ly, org[c] = o[c] + off[c], dir[c] = raw[c] * f - off[c].  With orthonormal axes
+ *                      every sample of a pixel passes through o + raw * f, on the plane at distance `focus` along az.
+ *   RT_VIEW_EQUIRECT   no transcendental function runs on the device, as before: the offset lives in the tables.  lon and lat hold one
+ *                      table per sample back to back - sample s reads lon + 2 w s and lat + 2 h s - made by
+ *                      rt_view_equirect_sample_tables from the angles 2.0 * M_PI * ((x + 0.5) + dx) / w - M_PI and
+ *                      M_PI / 2.0 - M_PI * ((y + 0.5) + dy) / h.  dx and dy are not read by the generator.
+ * and dir then goes through the reference's normal3D, as for a view.  A lens with radius > 0 is RT_VIEW_PINHOLE only.  With dx = dy = 0
+ * and no lens every model's sample ray is the view's ray bit for bit (X and Y are never -0, so adding 0.0 changes nothing).
+ *
+ * A sampled trace of n samples (1 <= n <= 1024, (uint64)n * w * h <= 2^32): ray i = y * w + x of sample s is intersectWorld(segs, ...)
+ * exactly as rt_scene_trace_rays_device traces it, its stars drawn with pix = s * w * h + i - each sample draws its own sky, as each
+ * redraw of the reference does.  Per channel acc = rgb_0, then acc = acc + rgb_s for s = 1 .. n - 1 in that order, then
+ * mean = acc / (double)n, one correctly rounded division.  rgb receives mean; rgba receives 255 * mean through the store rule of
+ * main.js:195-198 with alpha 255.  NaN propagates by IEEE rules and stores as 0.  n = 1 with the zero sample and no lens gives
+ * rt_scene_trace_view_device's bytes in rgb and rgba. */
+typedef struct rt_view_sample { double dx, dy, lu, lv; } rt_view_sample;   /* 32 bytes: the sub-pixel offset, the lens point on the unit disk */
+typedef struct rt_view_lens   { double radius, focus; } rt_view_lens;      /* NULL or radius 0 = no lens */
+
+/* Host logic, no GPU, no rt_init.  RT_ERR_INVALID: everything rt_view_validate refuses; n outside 1..1024 or n * w * h > 2^32 (in 64
+ * bits); NULL samples or a non-finite sample component; radius negative or non-finite; radius > 0 with a model other than
+ * RT_VIEW_PINHOLE, or with focus not finite or <= 0. */
+int rt_view_samples_validate(const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens, uint32_t n, const rt_view_sample *samples);
+
+/* Host logic: the k x k grid pattern, k in 1..32, into out[k * k]: sample j * k + i (row j, column i) has dx = (i + 0.5) / k - 0.5,
+ * dy = (j + 0.5) / k - 0.5 and (lu, lv) = Shirley's concentric map of (a, b) = (2 dx, 2 dy) onto the unit disk (the host's libm): (0, 0)
+ * at the centre; |a| > |b|: r = a, phi = (M_PI / 4.0) * (b / a); else r = b, phi = M_PI / 2.0 - (M_PI / 4.0) * (a / b); lu = r * cos(phi),
+ * lv = r * sin(phi).  k = 1 gives the zero sample.  One pattern serves antialiasing and the lens.  RT_ERR_INVALID: k outside 1..32, NULL. */
+int rt_view_samples_grid(uint32_t k, rt_view_sample *out);
+
+/* Host logic: the panorama's tables of n samples, one table per sample back to back (lon: n * 2 w doubles, lat: n * 2 h doubles; the
+ * layout of rt_view_equirect_tables each, whose bits the zero sample's table has).  RT_ERR_INVALID: a NULL pointer, w, h or n == 0. */
+int rt_view_equirect_sample_tables(uint32_t w, uint32_t h, uint32_t n, const rt_view_sample *samples, double *lon, double *lat);
+
+/* Host logic: rt_view_rays for ONE sample - the restatement the device is held to, bit for bit.  `table` is the index of the panorama
+ * table to read (RT_VIEW_EQUIRECT: lon + 2 w table, lat + 2 h table, HOST memory; not read for the other models, pass 0).
+ * RT_ERR_INVALID: what rt_view_samples_validate refuses for n = 1, a NULL out, first_row + rows > h; rows == 0 writes nothing. */
+int rt_view_sample_rays(const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens, const rt_view_sample *sample, uint32_t table,
+                        uint32_t first_row, uint32_t rows, double *out);
+
+/* The same rows into d_rays (DEVICE memory, 16-byte aligned), asynchronous on `hip_stream` (NULL = the library's stream of `device`);
+ * for RT_VIEW_EQUIRECT the tables are DEVICE pointers.  `sample` and `lens` are HOST memory, read before the call returns.  It needs no
+ * scene and waits for no edit.  RT_ERR_INVALID as rt_view_sample_rays, and for a NULL or misaligned d_rays, before a device is touched. */
+int rt_view_sample_rays_device(int device, const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens, const rt_view_sample *sample,
+                               uint32_t table, uint32_t first_row, uint32_t rows, double *d_rays, void *hip_stream);
+
+/* Host arithmetic: the workspace rt_scene_trace_view_samples_device prefers: 96 w h bytes - per pixel of a band the rays (48), one
+ * sample's rgb (24) and the accumulator (24) -, the whole view in one band (docs/EVIDENCE.md "Sampled views").  0 where
+ * rt_view_work_bytes is 0. */
+size_t rt_view_samples_work_bytes(uint32_t w, uint32_t h);
+
+/* The sampled trace of the view into d_out->rgb and / or d_out->rgba (DEVICE memory, frame order, as rt_scene_trace_view_device);
+ * d_out->hits must be NULL: a mean of hit records means nothing.  `samples` (and `lens`) are HOST memory, read before the call returns:
+ * each sample's 32 bytes travel in the generator's kernel arguments.  The view is processed in bands of whole rows (d_work: DEVICE
+ * memory, 16-byte aligned, work_bytes >= 96 w: one row is the smallest band): per band and per sample in order the rays are generated
+ * and traced with base = s * w * h + y0 * w; sample 0 goes straight into the accumulator, later samples into the rgb slab and are then
+ * accumulated; the last sample's accumulation is fused with the resolve, which writes the band's pixels of the outputs and nothing else.
+ * No result depends on the band size.  Stream, stats (kernel_ms covers every launch, pixels = w h), thread, scratch-reservation and
+ * pending-edit rules are rt_scene_trace_view_device's; for RT_VIEW_EQUIRECT the tables are DEVICE pointers.  Before a device is
+ * touched: RT_ERR_STATE for a NULL scene; then RT_ERR_INVALID for what rt_view_samples_validate refuses; then for segs > RT_MAX_SEGS,
+ * NULL d_out, both rgb and rgba NULL, a non-NULL hits, misaligned outputs, a NULL or misaligned d_work, work_bytes below one row. */
+int rt_scene_trace_view_samples_device(rt_scene_dev *scene, const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens, uint32_t n,
+                                       const rt_view_sample *samples, uint32_t segs, const rt_ray_outputs *d_out, void *d_work,
+                                       size_t work_bytes, void *hip_stream, rt_stats *stats);
+
+/* Host form on rt_render's resident scene, as rt_trace_view: outputs in HOST memory, synchronous, on GPU 0, in chunks of whole rows of
+ * at most 2^18 pixels (every sample of a chunk is traced before the next chunk).  No ray crosses the link; for RT_VIEW_EQUIRECT the
+ * tables are HOST memory and the call uploads them once, (w + h) * 16 * n bytes. */
+int rt_trace_view_samples(const void *scene_blob, size_t blob_bytes, const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens,
+                          uint32_t n, const rt_view_sample *samples, uint32_t segs, const rt_ray_outputs *host_out, rt_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
