@@ -99,4 +99,61 @@ FD_FN double fd_asin(double x) {
   return hx > 0 ? t : -t;
 }
 
+// fdlibm's sin / cos for HOST-built tables (rt_ambient_cosine_dirs): k_sin.c and k_cos.c (FreeBSD msun's form of the latter) behind
+// the two- and three-term Cody-Waite reduction of e_rem_pio2.c's medium range, |x| < 2^19 * (pi / 2); beyond it, and for a non-finite x,
+// NaN - no caller here comes near.  No kernel calls these: the device runs no transcendental function.
+FD_FN double fd_k_sin(double x, double y) {
+  const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04, S4 = 2.75573137070700676789e-06,
+               S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+  if ((fd_hi(x) & 0x7fffffffu) < 0x3e400000u) return x;                 // |x| < 2^-27
+  const double z = x * x, v = z * x, r = S2 + z * (S3 + z * (S4 + z * (S5 + z * S6)));
+  return x - ((z * (0.5 * y - v * r) - y) - v * S1);
+}
+FD_FN double fd_k_cos(double x, double y) {
+  const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05, C4 = -2.75573143513906633035e-07,
+               C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+  if ((fd_hi(x) & 0x7fffffffu) < 0x3e400000u) return 1.0;
+  const double z = x * x, w = z * z, r = z * (C1 + z * (C2 + z * C3)) + (w * w) * (C4 + z * (C5 + z * C6));
+  const double hz = 0.5 * z, t = 1.0 - hz;
+  return t + (((1.0 - t) - hz) + (z * r - x * y));
+}
+// x = n * (pi / 2) + (y0 + y1), |y0 + y1| <= pi / 4 -> n & 3; -1 outside the medium range
+FD_FN int fd_rem_pio2(double x, double *y0, double *y1) {
+  const double invpio2 = 6.36619772367581382433e-01, pio2_1 = 1.57079632673412561417e+00, pio2_1t = 6.07710050650619224932e-11,
+               pio2_2 = 6.07710050630396597660e-11, pio2_2t = 2.02226624879595063154e-21, pio2_3 = 2.02226624871116645580e-21,
+               pio2_3t = 8.47842766036889956997e-32;
+  const uint32_t ix = fd_hi(x) & 0x7fffffffu;
+  if (ix <= 0x3fe921fbu) { *y0 = x; *y1 = 0.0; return 0; }              // |x| <= pi / 4
+  if (ix >= 0x413921fbu) return -1;                                     // |x| >= 2^19 * (pi / 2), Inf, NaN
+  const double t0 = x < 0.0 ? -x : x;
+  const int n = (int)(t0 * invpio2 + 0.5);
+  const double fn = (double)n;
+  double r = t0 - fn * pio2_1, w = fn * pio2_1t, a = r - w;
+  const int j = (int)(ix >> 20);
+  if (j - (int)((fd_hi(a) >> 20) & 0x7ffu) > 16) {                      // the second term: good to 118 bits
+    double t = r;
+    w = fn * pio2_2; r = t - w; w = fn * pio2_2t - ((t - r) - w); a = r - w;
+    if (j - (int)((fd_hi(a) >> 20) & 0x7ffu) > 49) {                    // the third: 151 bits, covers every case
+      t = r;
+      w = fn * pio2_3; r = t - w; w = fn * pio2_3t - ((t - r) - w); a = r - w;
+    }
+  }
+  const double b = (r - a) - w;
+  if (x < 0.0) { *y0 = -a; *y1 = -b; return (-n) & 3; }
+  *y0 = a; *y1 = b;
+  return n & 3;
+}
+FD_FN double fd_sin(double x) {
+  double a, b;
+  const int n = fd_rem_pio2(x, &a, &b);
+  if (n < 0) return x - x == 0.0 ? __builtin_nan("") : x - x;
+  return n == 0 ? fd_k_sin(a, b) : n == 1 ? fd_k_cos(a, b) : n == 2 ? -fd_k_sin(a, b) : -fd_k_cos(a, b);
+}
+FD_FN double fd_cos(double x) {
+  double a, b;
+  const int n = fd_rem_pio2(x, &a, &b);
+  if (n < 0) return x - x == 0.0 ? __builtin_nan("") : x - x;
+  return n == 0 ? fd_k_cos(a, b) : n == 1 ? -fd_k_sin(a, b) : n == 2 ? -fd_k_cos(a, b) : fd_k_sin(a, b);
+}
+
 #endif

@@ -315,10 +315,58 @@ function occlusion(sceneObj, rays, opts) {
   return native().occlusion(new Uint8Array(flattenScene(sceneObj)), rays, o.length || null, o.intensity || null, o.skip || null, !!o.blocker, !!o.bin);
 }
 
+// Ambient occlusion (include/rt_hip.h: struct rt_ambient): per receiver - a hit record, as traceRays / traceView return them with
+// {hits: true} - opts.samples shadow scans of length opts.radius over the hemisphere of its facing normal, the receiver's own sphere left
+// out, counted and averaged on the GPU.  Returns {open: Float64Array (the share of scans no opaque sphere ended; a miss: 1), intensity:
+// Float64Array (their mean intensity from 1.0; glass divides by albedo[4], so it can exceed 1; NaN for a miss), rgba: Uint8ClampedArray
+// (open as a grey pixel), kernel_ms} - each null unless asked for: opts.open (default true), opts.intensity, opts.rgba.
+//   ambientDirs(n)                 the library's cosine-weighted spiral: Float64Array, 3 per entry, local directions with z along the normal
+//   ambient(scene, hits, opts)     hits: an array of hit objects (null: a miss) or a Uint8Array of 80-byte rt_hit records.  opts: samples
+//                                  (default 16), radius (default Infinity: sky visibility), dirs (default ambientDirs(samples)), stride
+//                                  (default 1) and base (default 0): sample s of receiver i reads entry ((base + i) stride + s) % n_dirs
+//   ambientView(scene, view, w, h, opts)   the same for what the view sees, pixel y w + x being receiver y w + x; rays, hit records and
+//                                  scans stay on the GPU.  opts.rgba defaults to true and opts.open to false here.
+const HIT_BYTES = 80;
+function hitRecords(hits) {
+  if (hits instanceof Uint8Array) return hits;
+  const buf = new Uint8Array(HIT_BYTES * hits.length), d = new DataView(buf.buffer);
+  hits.forEach((h, i) => {
+    const at = HIT_BYTES * i;
+    if (!h) { d.setInt32(at, -1, true); d.setFloat64(at + 8, Infinity, true); return; }
+    d.setInt32(at, h.index, true); d.setInt32(at + 4, h.inside ? 1 : 0, true); d.setFloat64(at + 8, h.t, true);
+    for (let c = 0; c < 3; c++) { d.setFloat64(at + 16 + 8 * c, h.point[c], true); d.setFloat64(at + 40 + 8 * c, h.normal[c], true); }
+    d.setFloat64(at + 64, h.u, true); d.setFloat64(at + 72, h.v, true);
+  });
+  return buf;
+}
+function ambientDirs(n) { return native().ambientDirs(n); }
+function ambientOpts(o, who) {
+  const samples = o.samples === undefined ? 16 : o.samples, dirs = o.dirs || native().ambientDirs(samples);
+  if (!(dirs instanceof Float64Array) || dirs.length === 0 || dirs.length % 3 !== 0) throw new TypeError(who + ': dirs must be a Float64Array of 3 numbers per direction');
+  return [dirs, samples, o.stride === undefined ? 1 : o.stride, o.base || 0, o.radius === undefined ? Infinity : o.radius];
+}
+function ambient(sceneObj, hits, opts) {
+  if (!(hits instanceof Uint8Array ? hits.length > 0 && hits.length % HIT_BYTES === 0 : Array.isArray(hits) && hits.length > 0)) {
+    throw new TypeError('ambient: hits must be a non-empty array of hit objects or a Uint8Array of 80-byte records');
+  }
+  const o = opts || {};
+  const args = ambientOpts(o, 'ambient');
+  if (!inited) init(o.maxDevices);
+  return native().ambient(new Uint8Array(flattenScene(sceneObj)), hitRecords(hits), ...args, o.open !== false, !!o.intensity, !!o.rgba);
+}
+function ambientView(sceneObj, view, w, h, opts) {
+  if (!view || !Number.isInteger(view.model)) throw new TypeError('ambientView: view must come from views.reference / pinhole / ortho / equirect');
+  const o = opts || {};
+  const args = ambientOpts(o, 'ambientView');
+  if (!inited) init(o.maxDevices);
+  return native().ambientView(new Uint8Array(flattenScene(sceneObj)), viewBytes(view), view.lon || null, view.lat || null, w, h, ...args,
+    !!o.open, !!o.intensity, o.rgba !== false);
+}
+
 // `const build = '741'` (main.js:3) + this library's revision; every render's `.stats` also carries `.build` and `.report`, the
 // reference's end-of-frame string 'build #<id> (<elapsed>ms)' (main.js:204-205) for that render.
 function buildId() { return native().buildId(); }
 
 function shutdown() { if (addon) addon.shutdown(); inited = false; }
 
-module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, traceView, views, shadeRays, primaryRays, normal3D, occlusion, lightSegments, init, shutdown, buildId, flattenScene, scenes, native}, scene);
+module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, traceView, views, shadeRays, primaryRays, normal3D, occlusion, lightSegments, ambient, ambientView, ambientDirs, init, shutdown, buildId, flattenScene, scenes, native}, scene);

@@ -919,6 +919,171 @@ napi_value ShadeRays(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// ---- ambient occlusion (include/rt_hip.h: struct rt_ambient)
+// ambientDirs(n): the cosine-weighted spiral (rt_ambient_cosine_dirs) as a Float64Array of 3 n numbers
+napi_value AmbientDirs(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  uint32_t n = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 1 || napi_get_value_uint32(env, argv[0], &n) != napi_ok || n < 1 || n > 65536) {
+    napi_throw_type_error(env, nullptr, "ambientDirs(n): n in 1..65536");
+    return nullptr;
+  }
+  napi_value ab, v;
+  void *data = nullptr;
+  NAPI_TRY(napi_create_arraybuffer(env, (size_t)n * 24u, &data, &ab));
+  const int rc = rt_ambient_cosine_dirs(n, (double *)data);
+  if (rc != RT_OK) return throw_rt(env, "rt_ambient_cosine_dirs", rc);
+  NAPI_TRY(napi_create_typedarray(env, napi_float64_array, 3u * (size_t)n, ab, 0, &v));
+  return v;
+}
+
+// the tail both ambient calls share: [dirs: Float64Array (3 per entry), nSamples, stride, base, radius, wantOpen, wantIntensity, wantRgba] from
+// argv[at] on -> the description, the table, the wanted outputs; false (a TypeError is pending) where an argument is of the wrong kind
+bool ambient_args(napi_env env, size_t argc, napi_value *argv, size_t at, const char *who, struct rt_ambient *a, const double **dirs, bool want[3]) {
+  size_t len = 0;
+  double base = 0.0;
+  memset(a, 0, sizeof *a);
+  if (argc < at + 5 || !(*dirs = f64_array(env, argv[at], &len)) || len == 0 || len % 3u != 0 || len / 3u > 65536u ||
+      napi_get_value_uint32(env, argv[at + 1], &a->n_samples) != napi_ok || napi_get_value_uint32(env, argv[at + 2], &a->stride) != napi_ok ||
+      napi_get_value_double(env, argv[at + 3], &base) != napi_ok || !(base >= 0.0 && base <= 9007199254740992.0) ||
+      napi_get_value_double(env, argv[at + 4], &a->radius) != napi_ok) {
+    napi_throw_type_error(env, nullptr, who);
+    return false;
+  }
+  a->n_dirs = (uint32_t)(len / 3u);
+  a->base = (uint64_t)base;
+  want[0] = true; want[1] = false; want[2] = false;
+  for (size_t i = 0; i < 3 && at + 5 + i < argc; i++) napi_get_value_bool(env, argv[at + 5 + i], &want[i]);
+  return true;
+}
+
+// {open: Float64Array | null, intensity: Float64Array | null, rgba: Uint8ClampedArray | null, kernel_ms}
+napi_value ambient_result(napi_env env, size_t n, const bool want[3], napi_value ab[3], double kernel_ms) {
+  napi_value res, v;
+  napi_create_object(env, &res);
+  if (want[0]) napi_create_typedarray(env, napi_float64_array, n, ab[0], 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "open", v);
+  if (want[1]) napi_create_typedarray(env, napi_float64_array, n, ab[1], 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "intensity", v);
+  if (want[2]) napi_create_typedarray(env, napi_uint8_clamped_array, 4 * n, ab[2], 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "rgba", v);
+  napi_create_double(env, kernel_ms, &v); napi_set_named_property(env, res, "kernel_ms", v);
+  return res;
+}
+
+// ambient(blob, hits: Uint8Array (80 bytes per receiver: rt_hit), dirs, nSamples, stride, base, radius[, wantOpen, wantIntensity, wantRgba]): rt_ambient
+napi_value Ambient(napi_env env, napi_callback_info info) {
+  const char *who = "ambient(blob: Uint8Array, hits: Uint8Array (80 bytes per receiver), dirs: Float64Array (3 per entry), nSamples, stride, base, radius[, wantOpen, wantIntensity, wantRgba])";
+  size_t argc = 10;
+  napi_value argv[10];
+  bool is_ta = false, is_hits = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 7 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
+      napi_is_typedarray(env, argv[1], &is_hits) != napi_ok || !is_hits) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  napi_typedarray_type bt, ht; napi_value ab; size_t off, blob_len = 0, hits_len = 0;
+  void *blob_data = nullptr, *hits_data = nullptr;
+  napi_get_typedarray_info(env, argv[0], &bt, &blob_len, &blob_data, &ab, &off);
+  napi_get_typedarray_info(env, argv[1], &ht, &hits_len, &hits_data, &ab, &off);
+  if ((bt != napi_uint8_array && bt != napi_uint8_clamped_array) || ht != napi_uint8_array || hits_len == 0 || hits_len % sizeof(rt_hit) != 0) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  struct rt_ambient a;
+  const double *dirs = nullptr;
+  bool want[3];
+  if (!ambient_args(env, argc, argv, 2, who, &a, &dirs, want)) return nullptr;
+  const size_t n = hits_len / sizeof(rt_hit);
+  // the library wants the blob and the records 8-byte aligned: one aligned copy holds both
+  const size_t blob_room = (blob_len + 15) & ~(size_t)15;
+  uint8_t *mem = (uint8_t *)aligned_alloc(16, blob_room + ((hits_len + 15) & ~(size_t)15));
+  napi_value abs[3] = {nullptr, nullptr, nullptr};
+  void *p[3] = {nullptr, nullptr, nullptr};
+  const size_t each[3] = {8u, 8u, 4u};
+  bool ok = mem != nullptr;
+  for (int i = 0; i < 3 && ok; i++) if (want[i]) ok = napi_create_arraybuffer(env, n * each[i], &p[i], &abs[i]) == napi_ok;
+  if (!ok) {
+    free(mem);
+    napi_throw_error(env, nullptr, "ambient: out of memory");
+    return nullptr;
+  }
+  memcpy(mem, blob_data, blob_len);
+  memcpy(mem + blob_room, hits_data, hits_len);
+  const rt_ambient_outputs out = {(double *)p[0], (double *)p[1], (uint32_t *)p[2]};
+  rt_stats st;
+  const int rc = rt_ambient(mem, blob_len, &a, dirs, n, (const rt_hit *)(mem + blob_room), &out, &st);
+  free(mem);
+  if (rc != RT_OK) return throw_rt(env, "rt_ambient", rc);
+  return ambient_result(env, n, want, abs, st.kernel_ms);
+}
+
+// ambientView(blob, view, lon, lat, w, h, dirs, nSamples, stride, base, radius[, wantOpen, wantIntensity, wantRgba]): rt_ambient_view.  `view`,
+// lon and lat as for traceView.
+napi_value AmbientView(napi_env env, napi_callback_info info) {
+  const char *who = "ambientView(blob: Uint8Array, view: Uint8Array, lon, lat, w, h, dirs: Float64Array (3 per entry), nSamples, stride, base, radius[, wantOpen, wantIntensity, wantRgba])";
+  size_t argc = 14;
+  napi_value argv[14];
+  bool is_ta = false, is_view = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 11 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
+      napi_is_typedarray(env, argv[1], &is_view) != napi_ok || !is_view) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  napi_typedarray_type bt, vt; napi_value ab; size_t off, blob_len = 0, view_len = 0;
+  void *blob_data = nullptr, *view_data = nullptr;
+  napi_get_typedarray_info(env, argv[0], &bt, &blob_len, &blob_data, &ab, &off);
+  napi_get_typedarray_info(env, argv[1], &vt, &view_len, &view_data, &ab, &off);
+  uint32_t w = 0, h = 0;
+  if ((bt != napi_uint8_array && bt != napi_uint8_clamped_array) || vt != napi_uint8_array || view_len != sizeof(rt_view) ||
+      napi_get_value_uint32(env, argv[4], &w) != napi_ok || napi_get_value_uint32(env, argv[5], &h) != napi_ok) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  rt_view view;
+  memcpy(&view, view_data, sizeof view);
+  view.lon = view.lat = nullptr;
+  size_t table_len[2] = {0, 0};
+  const double *table_data[2] = {f64_array(env, argv[2], &table_len[0]), f64_array(env, argv[3], &table_len[1])};
+  if (view.model == RT_VIEW_EQUIRECT && (table_len[0] != 2u * (size_t)w || table_len[1] != 2u * (size_t)h)) {
+    napi_throw_type_error(env, nullptr, "ambientView: an equirect view needs lon and lat, Float64Arrays of 2 w and 2 h numbers");
+    return nullptr;
+  }
+  struct rt_ambient a;
+  const double *dirs = nullptr;
+  bool want[3];
+  if (!ambient_args(env, argc, argv, 6, who, &a, &dirs, want)) return nullptr;
+  if (argc < 12) { want[0] = false; want[2] = true; }                             // (a view's default output is the picture)
+  const bool sized = w != 0 && h != 0 && (uint64_t)w * h < (1ull << 31);       // (anything else the library refuses: no buffer is sized from it)
+  const size_t n = sized ? (size_t)w * h : 0;
+  const size_t blob_room = (blob_len + 15) & ~(size_t)15, lon_room = table_len[0] * 8u, lat_room = table_len[1] * 8u;
+  uint8_t *mem = (uint8_t *)aligned_alloc(16, blob_room + lon_room + lat_room + 16u);
+  napi_value abs[3] = {nullptr, nullptr, nullptr};
+  void *p[3] = {nullptr, nullptr, nullptr};
+  const size_t each[3] = {8u, 8u, 4u};
+  bool ok = mem != nullptr;
+  for (int i = 0; i < 3 && ok; i++) if (want[i]) ok = napi_create_arraybuffer(env, n * each[i], &p[i], &abs[i]) == napi_ok;
+  if (!ok) {
+    free(mem);
+    napi_throw_error(env, nullptr, "ambientView: out of memory");
+    return nullptr;
+  }
+  memcpy(mem, blob_data, blob_len);
+  if (view.model == RT_VIEW_EQUIRECT) {
+    memcpy(mem + blob_room, table_data[0], lon_room);
+    memcpy(mem + blob_room + lon_room, table_data[1], lat_room);
+    view.lon = (const double *)(mem + blob_room);
+    view.lat = (const double *)(mem + blob_room + lon_room);
+  }
+  const rt_ambient_outputs out = {(double *)p[0], (double *)p[1], (uint32_t *)p[2]};
+  rt_stats st;
+  const int rc = rt_ambient_view(mem, blob_len, &view, w, h, &a, dirs, &out, &st);
+  free(mem);
+  if (rc != RT_OK) return throw_rt(env, "rt_ambient_view", rc);
+  return ambient_result(env, n, want, abs, st.kernel_ms);
+}
+
 napi_value Module(napi_env env, napi_value exports) {
   const napi_property_descriptor props[] = {
       {"init", nullptr, Init, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
@@ -940,6 +1105,9 @@ napi_value Module(napi_env env, napi_value exports) {
       {"viewSamplesGrid", nullptr, ViewSamplesGrid, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"equirectSampleTables", nullptr, EquirectSampleTables, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"traceViewSamples", nullptr, TraceViewSamples, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ambientDirs", nullptr, AmbientDirs, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ambient", nullptr, Ambient, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"ambientView", nullptr, AmbientView, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

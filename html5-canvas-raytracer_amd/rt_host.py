@@ -221,6 +221,19 @@ class RtViewLens(C.Structure):
     _fields_ = [("radius", C.c_double), ("focus", C.c_double)]
 
 
+class RtAmbient(C.Structure):
+    """Ambient occlusion (include/rt_hip.h struct rt_ambient, 32 bytes): n_samples scans per receiver, the direction table's n_dirs
+    entries, the stride and base of the entry index e = ((base + i) * stride + s) % n_dirs, and the scans' length `radius`."""
+    _fields_ = [("n_samples", C.c_uint32), ("n_dirs", C.c_uint32), ("stride", C.c_uint32), ("reserved", C.c_uint32), ("base", C.c_uint64),
+                ("radius", C.c_double)]
+
+
+class RtAmbientOutputs(C.Structure):
+    """Outputs of ambient occlusion (include/rt_hip.h rt_ambient_outputs): float64 open, float64 intensity, uint32 rgba per receiver;
+    NULL = not wanted."""
+    _fields_ = [("open", C.c_void_p), ("intensity", C.c_void_p), ("rgba", C.c_void_p)]
+
+
 # every symbol include/rt_hip.h declares: (restype, argtypes)
 ABI = {
     "rt_init": (C.c_int, [C.c_int]),
@@ -320,11 +333,26 @@ ABI = {
                                                      C.c_uint32, C.POINTER(RtRayOutputs), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RtStats)]),
     "rt_trace_view_samples": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtViewLens), C.c_uint32, C.c_void_p,
                                         C.c_uint32, C.POINTER(RtRayOutputs), C.POINTER(RtStats)]),
+    "rt_ambient_validate": (C.c_int, [C.POINTER(RtAmbient), C.c_void_p]),
+    "rt_ambient_cosine_dirs": (C.c_int, [C.c_uint32, C.c_void_p]),
+    "rt_ambient_segments": (C.c_int, [C.POINTER(RtAmbient), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_ambient_segments_device": (C.c_int, [C.c_int, C.POINTER(RtAmbient), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "rt_scene_ambient_device": (C.c_int, [C.c_void_p, C.POINTER(RtAmbient), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtAmbientOutputs),
+                                          C.c_void_p, C.POINTER(RtStats)]),
+    "rt_ambient": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtAmbient), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(RtAmbientOutputs),
+                             C.POINTER(RtStats)]),
+    "rt_ambient_view_work_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_scene_ambient_view_device": (C.c_int, [C.c_void_p, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtAmbient), C.c_void_p,
+                                               C.POINTER(RtAmbientOutputs), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_ambient_view": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtAmbient), C.c_void_p,
+                                  C.POINTER(RtAmbientOutputs), C.POINTER(RtStats)]),
 }
 
 RT_MAX_SEGS = 16
 
-# include/rt_hip.h rt_node (200 bytes) as numpy fields, in the header's order; NODE_DTYPE (below) is the structured dtype
+# include/rt_hip.h rt_hit (80 bytes) and rt_node (200 bytes) as numpy fields, in the header's order; NODE_DTYPE (below) is the structured dtype
+HIT_FIELDS = [("object", "<i4"), ("inside", "<i4"), ("t", "<f8"), ("point", "<f8", (3,)), ("normal", "<f8", (3,)), ("u", "<f8"), ("v", "<f8")]
 NODE_FIELDS = [("object", "<i4"), ("inside", "<i4"), ("t", "<f8"), ("point", "<f8", (3,)), ("normal", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"),
                ("sample", "<f8", (3,)), ("diffuse", "<f8"), ("specular", "<f8"), ("ambient", "<f8"), ("reflect_weight", "<f8"),
                ("refract_weight", "<f8"), ("reflect_dir", "<f8", (3,)), ("refract_dir", "<f8", (3,)), ("children", "<u4"), ("reserved", "<u4")]
@@ -622,6 +650,43 @@ class Renderer:
         rc = self.lib.rt_scene_occlusion_device(self.handle, n, C.c_void_p(rays_ptr or 0), C.c_void_p(order_ptr or 0), C.byref(ins), C.byref(out),
                                                 C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
         _check(self.lib, rc, "rt_scene_occlusion_device")
+        return st
+
+    def ambient_segments(self, n, hits_ptr, dirs_ptr, n_dirs, sample, rays_ptr, skip_ptr=0, n_samples=None, stride=1, base=0, stream=None):
+        """The segments of sample `sample` of n receivers (HIT_DTYPE records, DEVICE, 8-byte aligned) into rays_ptr (DEVICE, 16-byte
+        aligned, n records of six float64) and skip_ptr (DEVICE, n int32; 0 = not wanted), generated on the GPU: the bits of
+        rt_host.ambient_segments.  dirs_ptr: n_dirs local directions (DEVICE, 3 float64 each).  What comes out goes into occlusion
+        (length = the radius, intensity = 1.0, skip), order_rays or trace_rays as it is.  Asynchronous; reads nothing of the scene."""
+        a = RtAmbient(sample + 1 if n_samples is None else n_samples, n_dirs, stride, 0, base, 1.0)
+        rc = self.lib.rt_ambient_segments_device(self.device, C.byref(a), C.c_void_p(dirs_ptr or 0), n, C.c_void_p(hits_ptr or 0), sample,
+                                                 C.c_void_p(rays_ptr or 0), C.c_void_p(skip_ptr or 0), C.c_void_p(stream or 0))
+        _check(self.lib, rc, "rt_ambient_segments_device")
+
+    def ambient(self, n, hits_ptr, dirs_ptr, n_dirs, n_samples, radius, open_ptr, intensity_ptr, rgba_ptr, stride=1, base=0, order_ptr=0, stream=None,
+                want_stats=False):
+        """Ambient occlusion of n receivers (HIT_DTYPE records, DEVICE) in one fused kernel: n_samples scans of length `radius` per
+        receiver over the hemisphere of its facing normal, along the directions of the table dirs_ptr (DEVICE, n_dirs entries) - per
+        receiver float64 open (the share of scans no opaque sphere ended), float64 intensity (their mean intensity, starting from 1.0)
+        and uint32 rgba (open as a grey RGBA8 pixel) into DEVICE buffers (0 / None = not wanted).  order_ptr as occlusion takes it."""
+        a = RtAmbient(n_samples, n_dirs, stride, 0, base, float(radius))
+        out = RtAmbientOutputs(open_ptr or None, intensity_ptr or None, rgba_ptr or None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_ambient_device(self.handle, C.byref(a), C.c_void_p(dirs_ptr or 0), n, C.c_void_p(hits_ptr or 0), C.c_void_p(order_ptr or 0),
+                                              C.byref(out), C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_ambient_device")
+        return st
+
+    def ambient_view(self, view, w, h, dirs_ptr, n_dirs, n_samples, radius, open_ptr, intensity_ptr, rgba_ptr, work_ptr, work_bytes, stride=1, base=0,
+                     stream=None, want_stats=False):
+        """ambient() for what `view` sees at w x h, pixel y w + x being receiver y w + x, into DEVICE buffers in frame order: rays, hit
+        records and scans stay on the GPU, band by band in work_ptr (DEVICE, 16-byte aligned, work_bytes >= 128 w;
+        ambient_view_work_bytes(w, h) is the size the library prefers).  An EQUIRECT view's tables are DEVICE pointers here."""
+        a = RtAmbient(n_samples, n_dirs, stride, 0, base, float(radius))
+        out = RtAmbientOutputs(open_ptr or None, intensity_ptr or None, rgba_ptr or None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_ambient_view_device(self.handle, C.byref(view), w, h, C.byref(a), C.c_void_p(dirs_ptr or 0), C.byref(out),
+                                                   C.c_void_p(work_ptr or 0), work_bytes, C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_ambient_view_device")
         return st
 
     def shade_rays(self, n, rays_ptr, nodes_ptr, order_ptr=0, pix_ptr=0, path_ptr=0, stream=None, want_stats=False):
@@ -1229,15 +1294,160 @@ def light_intensity_at(scene, points, facing, skip, lib=None, order="list"):
     return li
 
 
+# --------------------------------------------------------------------------- ambient occlusion (include/rt_hip.h: rt_ambient)
+def hit_records(points, normals, objects, inside=None):
+    """-> an (n,) HIT_DTYPE array: receivers for ambient() made by hand - `points` and `normals` (n, 3), `objects` n sphere indices in
+    blob order (the sphere the point lies on, left out of its scans; -1: a miss, not scanned), `inside` n flags (the normal is turned
+    round; None = all outside).  t, u and v are 0: ambient occlusion does not read them."""
+    import numpy as np
+    p = _points3(points, "points")
+    n = p.shape[0]
+    out = np.zeros(n, np.dtype(HIT_FIELDS))
+    out["point"] = p
+    out["normal"] = _points3(normals, "normals", n)
+    out["object"] = _skip_array(objects, n)
+    if inside is not None:
+        ins = np.asarray(inside)
+        if ins.shape != (n,):
+            raise ValueError("inside must be n flags")
+        out["inside"] = ins.astype(bool)
+    return out
+
+
+def _hits_array(hits):
+    """-> a contiguous HIT_DTYPE array from one, or from a list of hit dicts as trace_rays / trace_view return them (None: a miss)."""
+    import numpy as np
+    dt = np.dtype(HIT_FIELDS)
+    if isinstance(hits, np.ndarray):
+        if hits.dtype != dt or hits.ndim != 1:
+            raise ValueError("hits must be an (n,) array of HIT_DTYPE")
+        return np.ascontiguousarray(hits)
+    out = np.zeros(len(hits), dt)
+    for i, r in enumerate(hits):
+        if r is None:
+            out[i]["object"], out[i]["t"] = -1, float("inf")
+        else:
+            out[i] = (r["object"], int(r["inside"]), r["t"], r["point"], r["normal"], r["u"], r["v"])
+    return out
+
+
+def view_hit_records(scene, v, w, h, lib=None):
+    """-> the (w h,) HIT_DTYPE array of trace_view's "hits" output as the library wrote it: the receivers of ambient_view."""
+    import numpy as np
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    out = np.zeros(w * h, np.dtype(HIT_FIELDS))
+    bufs = RtRayOutputs(None, None, out.ctypes.data)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    _check(lib, lib.rt_trace_view(buf, len(blob), C.byref(v), w, h, 0, C.byref(bufs), None), "rt_trace_view")
+    return out
+
+
+def ambient_dirs(n, lib=None):
+    """-> (n, 3) float64: the cosine-weighted spiral of rt_ambient_cosine_dirs, local directions with z along the facing normal: entry k
+    is {r cos(phi), r sin(phi), sqrt(1 - u)} with u = (k + 0.5) / n, phi = k pi (3 - sqrt(5)), r = sqrt(u) (fdlibm's cos and sin: the same
+    bits on every host)."""
+    import numpy as np
+    lib = lib or load_library()
+    out = np.empty((max(n, 0), 3), np.float64)
+    _check(lib, lib.rt_ambient_cosine_dirs(n, C.c_void_p(out.ctypes.data)), "rt_ambient_cosine_dirs")
+    return out
+
+
+def _ambient_args(n_samples, radius, dirs, stride, base, lib):
+    import numpy as np
+    if dirs is None:
+        dirs = ambient_dirs(n_samples, lib)
+    dirs = np.ascontiguousarray(dirs, np.float64)
+    if dirs.ndim != 2 or dirs.shape[1] != 3:
+        raise ValueError("dirs must be an (n_dirs, 3) array: local directions, z along the facing normal")
+    return RtAmbient(n_samples, dirs.shape[0], stride, 0, base, float(radius)), dirs
+
+
+def ambient_segments(hits, sample, n_samples, dirs=None, stride=1, base=0, lib=None):
+    """The host probe (rt_ambient_segments): -> (rays (n, 6) float64, skip (n,) int32), the segments sample `sample` of the receivers
+    `hits` scans - what the GPU generates, bit for bit.  dirs: None = ambient_dirs(n_samples).  No GPU."""
+    import numpy as np
+    lib = lib or load_library()
+    h = _hits_array(hits)
+    a, dirs = _ambient_args(n_samples, 1.0, dirs, stride, base, lib)
+    rays, skip = np.empty((len(h), 6), np.float64), np.empty(len(h), np.int32)
+    _check(lib, lib.rt_ambient_segments(C.byref(a), C.c_void_p(dirs.ctypes.data), len(h), C.c_void_p(h.ctypes.data), sample, C.c_void_p(rays.ctypes.data),
+                                        C.c_void_p(skip.ctypes.data)), "rt_ambient_segments")
+    return rays, skip
+
+
+def _ambient_outputs(n, want):
+    import numpy as np
+    want = set(want)
+    if not want or want - {"open", "intensity", "rgba"}:
+        raise ValueError("want names some of 'open', 'intensity', 'rgba'")
+    out = {}
+    if "open" in want:
+        out["open"] = np.empty(n, np.float64)
+    if "intensity" in want:
+        out["intensity"] = np.empty(n, np.float64)
+    if "rgba" in want:
+        out["rgba"] = np.empty((n, 4), np.uint8)
+    return out, RtAmbientOutputs(*[out[k].ctypes.data if k in out else None for k in ("open", "intensity", "rgba")])
+
+
+def ambient(scene, hits, n_samples, radius, dirs=None, stride=1, want=("open",), order="list", base=0, lib=None):
+    """ambient(scene, hits, n_samples, radius) -> {"open": (n,) float64, "intensity": (n,) float64, "rgba": (n, 4) uint8} (the keys named
+    in `want`): ambient occlusion of the receivers `hits` (a HIT_DTYPE array - view_hit_records, hit_records - or a list of hit dicts) on
+    GPU 0 with rt_render's resident scene.  Per receiver n_samples shadow scans of length `radius` (float("inf"): sky visibility) leave the
+    point along directions of the hemisphere around its facing normal, the receiver's own sphere left out: open is the share of scans
+    no opaque sphere ended (a miss: 1.0), intensity their mean intensity starting from 1.0 (glass DIVIDES by albedo[4], quirk q2: it can
+    exceed 1; NaN for a miss), rgba open as a grey pixel.  dirs: (n_dirs, 3) local directions, None = ambient_dirs(n_samples); sample s of
+    receiver i uses entry ((base + i) stride + s) % n_dirs - stride 0: the same directions everywhere.  order: "list" (the only one:
+    receivers that come from a view are neighbours already)."""
+    if order != "list":
+        raise ValueError("order is 'list'")
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    h = _hits_array(hits)
+    if len(h) == 0:
+        raise ValueError("hits must not be empty")
+    a, dirs = _ambient_args(n_samples, radius, dirs, stride, base, lib)
+    out, bufs = _ambient_outputs(len(h), want)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    _check(lib, lib.rt_ambient(buf, len(blob), C.byref(a), C.c_void_p(dirs.ctypes.data), len(h), C.c_void_p(h.ctypes.data), C.byref(bufs), None), "rt_ambient")
+    return out
+
+
+def ambient_view_work_bytes(w, h, lib=None):
+    """Bytes of device workspace Renderer.ambient_view prefers for a w x h view (host arithmetic; 0 for a size it refuses).  128 w - one
+    row - is the least it accepts."""
+    return int((lib or load_library()).rt_ambient_view_work_bytes(w, h))
+
+
+def ambient_view(scene, v, w, h, n_samples, radius, dirs=None, stride=1, want=("rgba",), base=0, lib=None):
+    """ambient() of what the view sees at w x h, in frame order ("rgba" (w h, 4) uint8 is the grey frame): the view's rays, their hit
+    records and the scans are made on the GPU (rt_ambient_view) - only the direction table goes up and the results come back."""
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    a, dirs = _ambient_args(n_samples, radius, dirs, stride, base, lib)
+    out, bufs = _ambient_outputs(w * h, want)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    _check(lib, lib.rt_ambient_view(buf, len(blob), C.byref(v), w, h, C.byref(a), C.c_void_p(dirs.ctypes.data), C.byref(bufs), None), "rt_ambient_view")
+    return out
+
+
 # --------------------------------------------------------------------------- wavefront ray lists (include/rt_hip.h: rt_node)
 def _node_dtype():
     import numpy as np
     return np.dtype(NODE_FIELDS)
 
 
-def __getattr__(name):                                   # NODE_DTYPE: built on first use, so that importing this module does not need numpy
+def __getattr__(name):                                   # NODE_DTYPE, HIT_DTYPE: built on first use, so that importing this module does not need numpy
     if name == "NODE_DTYPE":
         return _node_dtype()
+    if name == "HIT_DTYPE":
+        import numpy as np
+        return np.dtype(HIT_FIELDS)
     raise AttributeError(name)
 
 

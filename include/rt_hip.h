@@ -13,7 +13,7 @@
  * of the calling thread's last call.
  *
  * Threads: rt_init, rt_shutdown and rt_render serialise on an internal lock.  The device entry points
- * (rt_scene_upload, rt_render_tiles_device, rt_render_batch_device, rt_scene_trace_rays_device, rt_scene_order_rays_device, rt_scene_occlusion_device, rt_scene_shade_rays_device, rt_scene_spawn_rays_device, rt_scene_fold_nodes_device, rt_deinterleave_*) may be called from several
+ * (rt_scene_upload, rt_render_tiles_device, rt_render_batch_device, rt_scene_trace_rays_device, rt_scene_order_rays_device, rt_scene_occlusion_device, rt_scene_ambient_device, rt_scene_ambient_view_device, rt_scene_shade_rays_device, rt_scene_spawn_rays_device, rt_scene_fold_nodes_device, rt_deinterleave_*) may be called from several
  * threads at once; work on one HIP stream is ordered by the stream.  Launches with RT_FLAG_COUNT share one counter
  * buffer per device: one at a time per device.
  *
@@ -865,6 +865,117 @@ int rt_scene_trace_view_samples_device(rt_scene_dev *scene, const rt_view *v, ui
  * tables are HOST memory and the call uploads them once, (w + h) * 16 * n bytes. */
 int rt_trace_view_samples(const void *scene_blob, size_t blob_bytes, const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens,
                           uint32_t n, const rt_view_sample *samples, uint32_t segs, const rt_ray_outputs *host_out, rt_stats *stats);
+
+/* Ambient occlusion (sky visibility): n_samples shadow scans per RECEIVER over the hemisphere of its facing normal, counted and
+ * averaged on the GPU.  A receiver is an rt_hit record - what `hits` of rt_scene_trace_rays_device / rt_scene_trace_view_device holds,
+ * already in device memory - and a scan is rt_scene_occlusion_device's, bit for bit.  A fused kernel builds each segment in registers
+ * (no segment exists in memory) and stores 8 to 20 bytes per receiver; a generator kernel writes the segments of one sample as a ray
+ * list for callers who want to scan, order or trace them themselves (colour bleeding).  Whether the fused kernel is faster than those
+ * parts is a matter of measurement: docs/EVIDENCE.md, "Ambient occlusion".
+ *
+ * Receiver i with record H and sample s; every operation in binary64 without FMA contraction, in the order written:
+ *   l = H.inside ? -H.normal : H.normal              hit.l of main.js:445, the normal on the ray's side
+ *   org = H.point;  skip = H.object                  the receiver is left out, as main.js:294 leaves hit_i out - which is also what
+ *                                                    keeps a skybox from occluding everything seen from inside it
+ *   the frame around l (Duff et al. 2017, branch-free):
+ *     sg = copysign(1.0, l2);  a = -1.0 / (sg + l2);  b = (l0 * l1) * a
+ *     t  = {1.0 + (sg * (l0 * l0)) * a,  sg * b,  -sg * l0}
+ *     bt = {b,  sg + (l1 * l1) * a,  -l1}
+ *   e = (((uint64)base + (uint64)i) * (uint64)stride + (uint64)s) % (uint64)n_dirs      unsigned 64-bit, wrapping at 2^64
+ *   d = dirs[e]                                      a LOCAL direction {d0, d1, d2}, d2 along l; used as given
+ *   dir[c] = (t[c] * d0 + bt[c] * d1) + l[c] * d2,   then the reference's normal3D (times 1 / |dir|, a zero vector left as it is)
+ * stride == 0 gives every receiver the same n_samples directions (entries 0 .. n_samples - 1); stride >= 1 walks the table, so
+ * neighbours use different directions (a table of whole n_samples-point sets with stride = n_samples gives each receiver one set;
+ * n_samples consecutive entries of ONE long spiral all lie at nearly the same elevation).  A receiver is NOT SCANNED if it is a miss (object < 0) or has a non-finite word in point or
+ * normal: its segment is six NaNs and its skip -1, which rt_scene_occlusion_device answers with intensity NaN and blocker -1.
+ *
+ * The n_samples segments of a receiver are scanned with length `radius` (any value > 0, +Infinity included), starting intensity 1.0,
+ * the scene's CURRENT spheres and epsilon, in blob order, as rt_scene_occlusion_device scans them:
+ *   open       (double)count / (double)n_samples, count = the scans that ended with blocker -1.  A receiver that is not scanned: 1.0 -
+ *              a miss is open sky.
+ *   intensity  acc = li_0; acc = acc + li_s for s = 1 .. n_samples - 1 in that order; acc / (double)n_samples - the fold of a sampled
+ *              view.  A scan that crosses glass DIVIDES its intensity by albedo[4] (quirk q2), so intensity can exceed 1.  NaN for a
+ *              receiver that is not scanned.
+ *   rgba       `open` on all three channels through the store rule of main.js:195-198, alpha 255 - what rt_scene_set_texels_device takes. */
+struct rt_ambient {            /* 32 bytes.  A struct tag only, as POSIX has struct stat beside stat(): rt_ambient() is the host form */
+  uint32_t n_samples;          /* 1..1024 scans per receiver */
+  uint32_t n_dirs;             /* n_samples..65536 entries of the direction table, 3 doubles each */
+  uint32_t stride;             /* see e above */
+  uint32_t reserved;           /* 0 */
+  uint64_t base;               /* added to the receiver's index: a list processed in pieces passes each piece's first index */
+  double radius;               /* > 0; +Infinity: sky visibility */
+};
+typedef struct rt_ambient_outputs {   /* one entry per receiver; any may be NULL; all three NULL is RT_ERR_INVALID */
+  double   *open;
+  double   *intensity;
+  uint32_t *rgba;
+} rt_ambient_outputs;
+
+/* Host logic, no GPU, no rt_init.  RT_ERR_INVALID: a NULL pointer; n_samples outside 1..1024; n_dirs outside n_samples..65536;
+ * reserved != 0; radius not > 0 (a NaN radius included); a table entry with a non-finite component (`dirs`: HOST memory). */
+int rt_ambient_validate(const struct rt_ambient *a, const double *dirs);
+
+/* Host logic: a cosine-weighted spiral of n directions (1..65536) into out_3n.  Entry k: u = (k + 0.5) / n,
+ * phi = k * (M_PI * (3.0 - sqrt(5.0))), r = sqrt(u), {r * cos(phi), r * sin(phi), sqrt(1.0 - u)}, with fdlibm's cosine and sine
+ * (csrc/rt_fdlibm.h), so that the table's bits do not depend on the host's libm.  Every z is above 0.  No transcendental function runs
+ * on the device.  RT_ERR_INVALID: n outside 1..65536, NULL. */
+int rt_ambient_cosine_dirs(uint32_t n, double *out_3n);
+
+/* Host logic, the probe: the segments of sample `sample` of receivers 0 .. n - 1 (hits, dirs: HOST memory) into out_rays (n records
+ * {org[3], dir[3]}) and out_skip (n entries, or NULL) - the restatement the device is held to, bit for bit.  RT_ERR_INVALID: what
+ * rt_ambient_validate refuses, n outside 1..2^31 - 1, sample >= n_samples, NULL hits or out_rays. */
+int rt_ambient_segments(const struct rt_ambient *a, const double *dirs, uint64_t n, const rt_hit *hits, uint32_t sample, double *out_rays,
+                        int32_t *out_skip);
+
+/* The same from a kernel: d_dirs, d_hits (8-byte aligned), d_rays (16-byte aligned) and d_skip (4-byte aligned, or NULL) are DEVICE
+ * memory; asynchronous on `hip_stream` (NULL = the library's stream of `device`).  It needs no scene and waits for no edit.  The list
+ * goes into rt_scene_occlusion_device (length = radius, intensity = 1.0, skip = d_skip), rt_scene_order_rays_device or
+ * rt_scene_trace_rays_device as it is.  RT_ERR_INVALID as the probe (the table's entries are not looked at), and for a NULL or
+ * misaligned pointer, before a device is touched. */
+int rt_ambient_segments_device(int device, const struct rt_ambient *a, const double *d_dirs, uint64_t n, const rt_hit *d_hits,
+                               uint32_t sample, double *d_rays, int32_t *d_skip, void *hip_stream);
+
+/* The fused kernel: d_dirs, d_hits, d_order and the arrays d_out names are DEVICE memory (d_out itself is a host struct).  d_order is
+ * NULL or an order as rt_scene_trace_rays_ordered_device takes it: work-item j takes receiver i = d_order[j], an entry >= n is skipped,
+ * and receiver i reads record i, uses index i in e and writes index i - the buffers hold the bytes of the call without an order.
+ * Outputs are written for every receiver an entry names (every i < n without an order) and nowhere else; an output that is NULL is not
+ * touched.  A scan whose direction comes out non-finite is not traced (rt_scene_occlusion_device's rule: its intensity is NaN, it
+ * counts as open).  Asynchronous on `hip_stream` (NULL = the library's stream for the scene's device) unless `stats` is non-NULL (then
+ * it waits and fills kernel_ms, total_ms and pixels = n).  Waits by event for a pending rt_scene_set_objects like every other launch.
+ * One work-item per receiver; a lane whose scan has met its opaque sphere goes idle and a wave leaves the scan as soon as none of its
+ * 64 is live, so neighbours in the list should be neighbours in space.
+ * RT_ERR_INVALID, before a device is touched: what rt_ambient_validate refuses of `a`, n outside 1..2^31 - 1, a NULL or misaligned
+ * d_dirs or d_hits (8 bytes), a NULL d_out or all of its outputs NULL, a misaligned open or intensity (8 bytes), rgba or d_order
+ * (4 bytes); then RT_ERR_STATE: a NULL scene.  Thread rules as rt_render_tiles_device. */
+int rt_scene_ambient_device(rt_scene_dev *scene, const struct rt_ambient *a, const double *d_dirs, uint64_t n, const rt_hit *d_hits,
+                            const uint32_t *d_order, const rt_ambient_outputs *d_out, void *hip_stream, rt_stats *stats);
+
+/* Host form: rt_render's resident scene (as rt_occlusion), every array in HOST memory, the list's own order, synchronous, on GPU 0,
+ * any n >= 1.  The list is processed in chunks of 2^18 receivers and chunk c passes base + c * 2^18: the call gives the bytes of one
+ * launch over the whole list, and a caller who splits a list themselves passes base = the piece's first index for the same. */
+int rt_ambient(const void *scene_blob, size_t blob_bytes, const struct rt_ambient *a, const double *dirs, uint64_t n, const rt_hit *hits,
+               const rt_ambient_outputs *host_out, rt_stats *stats);
+
+/* Host arithmetic: the workspace rt_scene_ambient_view_device prefers for a w x h view: 128 w h bytes - per pixel of a band its ray
+ * (48) and its hit record (80) -, the whole view in one band.  0 where rt_view_work_bytes is 0. */
+size_t rt_ambient_view_work_bytes(uint32_t w, uint32_t h);
+
+/* Ambient occlusion of what a view sees: pixel i = y * w + x is receiver i, outputs in frame order (rgba is the w x h frame).  The view
+ * is processed in bands of whole rows (d_work: DEVICE memory, 16-byte aligned, work_bytes >= 128 w: one row is the smallest band): per
+ * band the view's rays, their hit records (the `hits` of rt_scene_trace_view_device) and the fused kernel with base + y0 * w.  No result
+ * depends on the band size.  d_dirs is DEVICE memory; for RT_VIEW_EQUIRECT the view's tables are DEVICE pointers.  Stream, stats
+ * (kernel_ms covers every launch, pixels = w h), thread and pending-edit rules are rt_scene_trace_view_device's.  RT_ERR_STATE: a NULL
+ * scene; RT_ERR_INVALID: what rt_view_validate and rt_ambient_validate (of `a`) refuse, a NULL or misaligned d_dirs, d_out as for
+ * rt_scene_ambient_device, a NULL or misaligned d_work, work_bytes below one row. */
+int rt_scene_ambient_view_device(rt_scene_dev *scene, const rt_view *v, uint32_t w, uint32_t h, const struct rt_ambient *a,
+                                 const double *d_dirs, const rt_ambient_outputs *d_out, void *d_work, size_t work_bytes, void *hip_stream,
+                                 rt_stats *stats);
+
+/* Host form on rt_render's resident scene, as rt_trace_view: `dirs` and the outputs in HOST memory, synchronous, on GPU 0, in chunks of
+ * whole rows of at most 2^18 pixels.  No ray and no hit record crosses the link: the table goes up once (24 n_dirs bytes), 8 to 20
+ * bytes per pixel come back. */
+int rt_ambient_view(const void *scene_blob, size_t blob_bytes, const rt_view *v, uint32_t w, uint32_t h, const struct rt_ambient *a,
+                    const double *dirs, const rt_ambient_outputs *host_out, rt_stats *stats);
 
 #ifdef __cplusplus
 }
