@@ -16,7 +16,7 @@ __device__ __forceinline__ double dot(const v3 a, const v3 b) { return a.x * b.x
 // the +-1 LSB tolerance exists for (tests/test_gpu_parity.py holds both kernels to it).
 #if RT_STRICT
 __device__ __forceinline__ double rt_sqrt(double x) { return sqrt(x); }
-__device__ __forceinline__ double rt_sqrt_nn(double x) { return sqrt(x); }
+template <bool FMIN = false> __device__ __forceinline__ double rt_sqrt_nn(double x) { return sqrt(x); }
 __device__ __forceinline__ double rt_rcp(double x) { return 1.0 / x; }
 __device__ __forceinline__ double rt_div(double a, double b) { return a / b; }
 __device__ __forceinline__ double rt_pow(double x, double e) { return pow(x, e); }
@@ -47,9 +47,34 @@ __device__ __forceinline__ double rt_sqrt(double x) {
   return (x > 0.0) ? g : x;                                           // +0 -> 0, NaN -> NaN, x < 0 -> x (callers never pass it)
 }
 // x >= 0 (or NaN): the +0 case is kept exact by clamping the estimate (rsq(0) = inf) instead of
-// selecting afterwards: 0 * 1e100 = 0 through every step below.
+// selecting afterwards: 0 * (a finite y) = 0 through every step below.
+// The clamp is an INTEGER minimum of the estimate's high word against 0x7fe00000 (the high word of 2^1023): one VALU instruction
+// with a 32-bit literal.  It used to be fmin(estimate, 1e100), whose 64-bit constant is two s_mov_b32 at each of the 22 inlined
+// sites, rebuilt at every shadow test that enters (the build has no MachineLICM).  Why every result a caller can see is the old one's:
+//   * For positive doubles the order of the values is the order of their high words as signed integers (then of the low words), so
+//     the minimum leaves every estimate below 2^1023 - every finite one but the last binade's - as it is, and so did the old clamp
+//     for an estimate <= 1e100.  The estimate is good to 2^-24 (measured, above): x >= 2^-664 = 1.31e-200 gives at most
+//     2^332 (1 + 2^-24) = 8.75e99 < 1e100, and x >= 1e-200 (1 + 2^-22) still gives less than 1e100.  For all those x neither
+//     clamp acts: bit for bit.  (In the band 1e-200 <= x < 1e-200 (1 + 2^-22), 2.4e-207 wide, the old clamp may have cut an estimate
+//     that overshot 1e100 by its own error and this one does not: both forms then return sqrt(x) to the bound above, not
+//     necessarily the same last bit.  Below 1e-200 the old clamp cut a correct estimate and returned a wrong root; this one does not.)
+//   * x = +0: rsq = +inf, high word 0x7ff00000 -> 0x7fe00000, y = 2^1023.  x y = 0, e = 1, y' = 1.5 * 2^1023 (finite),
+//     g = 0 y' = 0, fma(fma(-0, 0, 0), y' / 2, 0) = +0: as with 1e100.
+//   * x = -0 (no caller forms it: the discriminants are differences and fma results, +0 when exact): rsq = -inf, a negative high
+//     word, kept by the SIGNED minimum as fmin kept -inf: NaN both ways.
+//   * x = NaN: every step below has x as an operand: NaN, whatever y is.
+// FMIN (the general kernels, REFRACT): the old clamp.  There the integer form measured 0.5 % SLOWER (the reference's own scene, three runs of
+// three below the parent's: docs/EVIDENCE.md, first section) - those kernels are bound by their vector side, and the two s_mov_b32 stood in
+// the wait state between the v_rsq_f64 and its first use, where an s_nop stands now.
+template <bool FMIN = false>
 __device__ __forceinline__ double rt_sqrt_nn(double x) {
-  double y = __builtin_fmin(__builtin_amdgcn_rsq(x), 1e100);
+  double y;
+  if constexpr (FMIN) y = __builtin_fmin(__builtin_amdgcn_rsq(x), 1e100);
+  else {
+    const unsigned long long yb = __builtin_bit_cast(unsigned long long, __builtin_amdgcn_rsq(x));
+    const int32_t yh = (int32_t)(yb >> 32);
+    y = __builtin_bit_cast(double, ((unsigned long long)(uint32_t)(yh < 0x7fe00000 ? yh : 0x7fe00000) << 32) | (uint32_t)yb);
+  }
   const double e = __builtin_fma(-(x * y), y, 1.0);
   y = __builtin_fma(0.5 * y, e, y);
   const double g = x * y;
@@ -77,10 +102,12 @@ __device__ __attribute__((noinline)) double rt_pow_generic(double x, double e) {
 // Integer exponents (every specular_exponent of the reference scene, main.js:108-123) by square-and-multiply: <= 2*log2(n)
 // multiplies instead of OCML's ~150-instruction pow.  Every path multiplies in the same sequence - for bit i = 0, 1, ...: r *= b
 // where bit i is set, b *= b - with r = b standing for the first r = 1.0 * b (exact), so the result does not depend on the path.
-template <class EP>                                                  // (EP: where the material lies - const double * in any address space)
+// UNI (the uniform-material path): n comes from a scalar load - one exponent for the wave, known when the kernel is compiled - so the
+// walk below is entered without the ballot that finds that out and without the second form behind it.
+template <bool UNI = false, class EP>                                // (EP: where the material lies - const double * in any address space)
 __device__ __forceinline__ double rt_pow_spec(double x, int32_t n, EP e) {
-  const int32_t n0 = __builtin_amdgcn_readfirstlane(n);
-  if (__ballot(n != n0) == 0ull) {
+  const int32_t n0 = UNI ? n : __builtin_amdgcn_readfirstlane(n);
+  if (UNI || __ballot(n != n0) == 0ull) {
     // every lane here has the same exponent (a wave on one sphere: nearly all of them): walk its bits with scalar control
     if (n0 < 0) return rt_pow_generic(x, *e);
     // from set bit to set bit (the multiplies are unconditional: no select per bit)
@@ -134,7 +161,7 @@ __device__ __forceinline__ v3 unit(const v3 v, double *len_out) {
 // oracle/fdlibm_trig.h, which the CPU tests compare with Node's Math.atan2 / Math.asin bit for bit on 0.9 M vectors.
 #include "rt_fdlibm.h"
 // atan2(y, x) and asin(w) of one surface normal (the two halves of main.js:446-447 / :127-128)
-__device__ __forceinline__ void rt_atan2_asin(double y, double x, double w, double *at, double *as) { *at = fd_atan2(y, x); *as = fd_asin(w); }
+template <bool FMIN = false> __device__ __forceinline__ void rt_atan2_asin(double y, double x, double w, double *at, double *as) { *at = fd_atan2(y, x); *as = fd_asin(w); }
 #else
 __device__ __forceinline__ double rt_fma_k(double a, double b, double k) {     // a*b + k, k wave-uniform: v_fma_f64 v, v, v, s[..]
   double r;
@@ -162,6 +189,7 @@ __constant__ unsigned long long RT_TRIG_BITS[32] = {
     0x3fb3b13657b87036ull, 0x3f91c6c111dccb70ull, 0xbfb745d119378e4full, 0x3f96e89f0a0adacfull,
     0x3fbc71c717e1913cull, 0x3f9f1c72c668963full, 0xbfc2492492376b7dull, 0x3fa6db6db41ce4bdull,
     0x3fc99999999952ccull, 0x3fb333333336fd5bull, 0xbfd5555555555523ull, 0x3fc5555555555380ull};
+template <bool FMIN = false>                                         // (FMIN: rt_sqrt_nn's clamp, above)
 __device__ __forceinline__ void rt_atan2_asin(double y, double x, double w, double *at, double *as) {
   rt_trig_kptr K = (rt_trig_kptr)(const void *)RT_TRIG_BITS;
   asm volatile("" : "+s"(K));                        // opaque: the reads below stay scalar LOADS instead of being folded back into immediates
@@ -200,7 +228,7 @@ __device__ __forceinline__ void rt_atan2_asin(double y, double x, double w, doub
   *at = __builtin_copysign(a, y);                                    // NaN in, NaN out (every step above propagates it)
   // asin: x + x*r*P(r) below 1/2, pi/2 - 2*asin(sqrt((1-|x|)/2)) above
   pa = pa * r;
-  const double sq = big ? rt_sqrt_nn(t) : yw;
+  const double sq = big ? rt_sqrt_nn<FMIN>(t) : yw;
   const double ww = __builtin_fma(sq, pa, sq);                       // asin(sq)
   double b = big ? __builtin_fma(-2.0, ww, M_PI / 2.0) : ww;
   b = (yw > 1.0) ? __builtin_nan("") : b;                            // |w| > 1 by an ulp (a ray through the exact pole): NaN, as Math.asin gives

@@ -22,7 +22,7 @@
 // (the candidate root t_ of a ray that meets the sphere's line - DISC >= 0 -, and whether the ray starts inside: in_)
 // RT_ROOT(TCA, DISC): reads eps; declares thc_, t0_, t1_, in_ and t_ in the scope it stands in.
 #define RT_ROOT(TCA, DISC)                                                                    \
-        const double thc_ = rt_sqrt_nn(DISC);                                                 \
+        const double thc_ = rt_sqrt_nn<REFRACT>(DISC);                                                 \
         const double t0_ = (TCA) - thc_, t1_ = (TCA) + thc_;                                  \
         const bool in_ = (t0_ < eps);                                                         \
         const double t_ = in_ ? t1_ : t0_;
@@ -171,7 +171,7 @@ __device__ __forceinline__ int rt_lvl(int lv) { return lv; }
               RT_SDISC(G, tc_, disc_)                                                         \
               if (other_ && !(disc_ < 0.0) && !blocked) {                                     \
                 RT_PIN();                                                                     \
-                const double thc_ = rt_sqrt_nn(disc_);                                        \
+                const double thc_ = rt_sqrt_nn<REFRACT>(disc_);                                        \
                 RT_SROOTS(tc_, thc_, t0_, t1_)                                                \
                 const double t_ = (t0_ < eps) ? t1_ : t0_;                                    \
                 if ((t_ < llen) && !(t_ < eps)) {                                             \
@@ -192,7 +192,7 @@ __device__ __forceinline__ int rt_lvl(int lv) { return lv; }
               RT_SDISC(G, tc_, disc_)                                                       \
               if (((int)(J) != hi) && !(disc_ < 0.0)) {                                     \
                 RT_PIN();                                                                   \
-                const double thc_ = rt_sqrt_nn(disc_);                                      \
+                const double thc_ = rt_sqrt_nn<REFRACT>(disc_);                                      \
                 RT_SROOTS(tc_, thc_, t0_, t1_)                                              \
                 const double t_ = (t0_ < eps) ? t1_ : t0_;                                  \
                 if ((t_ < llen) && !(t_ < eps) && li != 0.0) {                              \
@@ -521,7 +521,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 #if RT_STRICT
         if (kind == RT_SAMPLER_TEXTURE) {
           double t_at, t_as;
-          rt_atan2_asin(-n.z, -n.x, -n.y, &t_at, &t_as);
+          rt_atan2_asin<REFRACT>(-n.z, -n.x, -n.y, &t_at, &t_as);
           const double u = RT_DIV_CONST(t_at, M_PI) / 2.0 + 0.5;   // main.js:446 (q6: two divisions)
           const double v = RT_DIV_CONST(t_as, M_PI / 2.0) / 2.0 + 0.5;  // main.js:447
           const rt_texture_desc td = rt_tex_desc<UNI>(tex, rt_mtl_texture(m));
@@ -534,7 +534,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
           if (xd != xd || yd != yd) col[0] = col[1] = col[2] = __builtin_nan("");   // texels[NaN] is undefined in JS
         } else if (kind == RT_SAMPLER_CHECKER) {
           double t_at, t_as;
-          rt_atan2_asin(-n.y, -n.x, -n.z, &t_at, &t_as);
+          rt_atan2_asin<REFRACT>(-n.y, -n.x, -n.z, &t_at, &t_as);
           const double u = RT_DIV_CONST(t_at, M_PI) / 2.0 + 0.5;   // main.js:127 (its own axes)
           const double v = RT_DIV_CONST(t_as, M_PI / 2.0) / 2.0 + 0.5;  // main.js:128
           const int c = to_int32_bit0(u * m.c[6]) ^ to_int32_bit0(v * m.c[7]);
@@ -548,14 +548,24 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
         // clear of the boundary test's band - parity in bit 28, rt_block.h: rt_column_cell.  The wave then agrees on nothing: no u, v)
         // (few-sphere kernels only: the many-sphere one-wave form has no scalar register left for it - tests/test_kernel_resources.py)
         [[maybe_unused]] const bool one_cell = UNI && !GRID && kind == RT_SAMPLER_CHECKER && (cand_host & (1u << 24)) != 0u;
+        // UNI: ONE decision tree on the scalar sampler kind, the commonest wave first - a floor block with its cell stated falls through to
+        // its colours; then plain colour; then the two samplers that need u, v, behind their one atan2 / asin pair.  Every arm is entered
+        // by a scalar compare and leaves for the lighting.  (As one chain of conditions shared with the general path every arm's outcome
+        // was a lane-mask flag set in one block and tested in the next: ~39 scalar instructions and six taken branches between the
+        // cell-stated wave's primary root and its light loop, ~22 now - the arms' exits still meet in one test; docs/EVIDENCE.md, first section.)
+        if (UNI && one_cell) {
+          // the cell's colour: three scalar operands, fetched through a scalar offset (nothing per lane)
+          const uint32_t c3 = (cand_host >> 28) & 1u ? 3u : 0u;
+          col[0] = m.c[c3]; col[1] = m.c[c3 + 1u]; col[2] = m.c[c3 + 2u];
+        } else if (UNI && kind != RT_SAMPLER_TEXTURE && kind != RT_SAMPLER_CHECKER) {      // (stars were turned away before the hit test)
+          col[0] = m.c[0]; col[1] = m.c[1]; col[2] = m.c[2];
+        } else {
         if constexpr (UNI) {
-          if (kind == RT_SAMPLER_TEXTURE || (kind == RT_SAMPLER_CHECKER && !one_cell)) {
-            const bool tx_ = (kind == RT_SAMPLER_TEXTURE);
-            rt_atan2_asin(tx_ ? -n.z : -n.y, -n.x, tx_ ? -n.y : -n.z, &t_at, &t_as);
-          }
+          const bool tx_ = (kind == RT_SAMPLER_TEXTURE);
+          rt_atan2_asin<REFRACT>(tx_ ? -n.z : -n.y, -n.x, tx_ ? -n.y : -n.z, &t_at, &t_as);
         }
         if (kind == RT_SAMPLER_TEXTURE) {
-          if constexpr (!UNI) rt_atan2_asin(-n.z, -n.x, -n.y, &t_at, &t_as);
+          if constexpr (!UNI) rt_atan2_asin<REFRACT>(-n.z, -n.x, -n.y, &t_at, &t_as);
           const double u = RT_DIV_CONST(t_at, M_PI) / 2.0 + 0.5;   // main.js:446 (q6: two divisions)
           const double v = RT_DIV_CONST(t_as, M_PI / 2.0) / 2.0 + 0.5;  // main.js:447
           const rt_texture_desc td = rt_tex_desc<UNI>(tex, rt_mtl_texture(m));
@@ -567,12 +577,8 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
           const uint32_t texel = *(const uint32_t *)(rt_cold_args()->texel_base + td.texels_offset + ((size_t)yi * td.width + xi) * 4u);
           col[0] = RT_DIV_CONST((double)(texel & 255u), 255.0); col[1] = RT_DIV_CONST((double)((texel >> 8) & 255u), 255.0);
           col[2] = RT_DIV_CONST((double)((texel >> 16) & 255u), 255.0);
-        } else if (UNI && one_cell) {
-          // the cell's colour: three scalar operands, fetched through a scalar offset (nothing per lane)
-          const uint32_t c3 = (cand_host >> 28) & 1u ? 3u : 0u;
-          col[0] = m.c[c3]; col[1] = m.c[c3 + 1u]; col[2] = m.c[c3 + 2u];
         } else if (kind == RT_SAMPLER_CHECKER) {
-          if constexpr (!UNI) rt_atan2_asin(-n.y, -n.x, -n.z, &t_at, &t_as);
+          if constexpr (!UNI) rt_atan2_asin<REFRACT>(-n.y, -n.x, -n.z, &t_at, &t_as);
           const double u = RT_DIV_CONST(t_at, M_PI) / 2.0 + 0.5;   // main.js:127 (its own axes)
           const double v = RT_DIV_CONST(t_as, M_PI / 2.0) / 2.0 + 0.5;  // main.js:128
           const double xu = u * m.c[6], xv = v * m.c[7];
@@ -605,6 +611,9 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
           c = (c >= m.c[6]) ? 0.0 : c * m.c[7];     // main.js:137-138
           col[0] = col[1] = col[2] = c;
         } else { col[0] = m.c[0]; col[1] = m.c[1]; col[2] = m.c[2]; }
+#if !RT_STRICT
+        }                                                               // (the third arm of the product build's tree above)
+#endif
 
         // general product kernel: the sampled colour waits in LDS (slots 10-12 of the lane's fold state) while the
         // lights are scanned: six registers fewer across the hottest loop, which is what lets this kernel fit
@@ -723,6 +732,9 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
             } else
 #endif
             if (!COUNT) {
+              // (UNI: pinned, so that the wave's scalar no_occluder test above stays a compare and a branch of its own instead of being folded,
+              // as a lane mask, into this per-lane test's exec mask)
+              if constexpr (UNI) RT_PIN();
               if (li != 0.0) {
                 uint32_t j = 0;
 #if !RT_STRICT
@@ -791,7 +803,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
                 spec_m = (const rt_mtl *)((const char *)mtl + off_);
               }
               const int32_t spec_n = spec_m->spec_n;
-              if (spd > 0.0) specular += rt_pow_spec(spd, spec_n, &spec_m->specular_exponent);
+              if (spd > 0.0) specular += rt_pow_spec<UNI>(spd, spec_n, &spec_m->specular_exponent);
 #else
               if (spd > 0.0) specular += rt_pow(spd, m.specular_exponent);
 #endif
