@@ -12,6 +12,7 @@
 //   rt_nodes_api.hip  the wavefront form's device entry points: one level of nodes, the next level's ray list, the fold (rt_nodes.hip)
 //   rt_views_api.hip  views: validation, the panorama's tables, the host probe, the generator's launch (rt_views.hip), the traces of a whole view
 //   rt_ambient_api.hip  ambient occlusion: validation, the cosine table, the host probe, the launches of rt_ambient.hip, the host forms
+//   rt_lighting_api.hip  sampled lights: validation, the offset table, the host probe, the launch of rt_lighting.hip, the host forms
 // Which kernel a launch runs is one value (rt_device.h: rt_trace_variant), worked out once per launch; the two builds of rt_kernel.hip map
 // it to a kernel (rt_kernel_trace_fast / rt_kernel_trace_strict), and the declarations below are all the host sees of them.
 #ifndef RT_API_INTERNAL_H

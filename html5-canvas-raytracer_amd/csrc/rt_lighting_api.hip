@@ -1,0 +1,300 @@
+// rt_lighting_api.hip — sampled lights (include/rt_hip.h: rt_lighting): the host logic (validation, the offset table, the host probe),
+// the launch of rt_lighting.hip's kernel, and the host forms: a list of receivers through device buffers in chunks, and a whole view
+// whose rays, hit records and scans never leave the device.  The kernel reads the scene's current spheres, epsilon, lights and light
+// intensity; the last two are the host copies every launch carries by value, taken under launch_mu with the sphere block
+// (rt_scene_set_lights and rt_scene_set_light_intensity write them under it).  The band loop of a view is a second one beside
+// rt_ambient_api.hip's: that one's launches stay exactly as they are.
+#include "rt_api_internal.h"
+#include "rt_lighting.h"
+
+static_assert(sizeof(struct rt_lighting) == 32 && sizeof(rt_hit) == 80, "a lighting description travels as 32 bytes, a receiver is 80");
+
+namespace {
+int lighting_check(const struct rt_lighting *a, const char *what) {
+  if (!a) return fail(RT_ERR_INVALID, "%s: NULL lighting description", what);
+  if (a->n_samples < 1u || a->n_samples > RT_LIGHTING_MAX_SAMPLES) return fail(RT_ERR_INVALID, "%s: n_samples %u not in 1..%u", what, a->n_samples, RT_LIGHTING_MAX_SAMPLES);
+  if (a->n_offs < a->n_samples || a->n_offs > RT_LIGHTING_MAX_OFFS)
+    return fail(RT_ERR_INVALID, "%s: n_offs %u not in n_samples..%u", what, a->n_offs, RT_LIGHTING_MAX_OFFS);
+  if (a->reserved != 0u) return fail(RT_ERR_INVALID, "%s: reserved %u not 0", what, a->reserved);
+  if (!std::isfinite(a->light_radius) || a->light_radius < 0.0) return fail(RT_ERR_INVALID, "%s: light_radius %g not finite and >= 0", what, a->light_radius);
+  return RT_OK;
+}
+
+// ... and a table in HOST memory
+int lighting_table_check(const struct rt_lighting *a, const double *offs, const char *what) {
+  if (int rc = lighting_check(a, what)) return rc;
+  if (!offs) return fail(RT_ERR_INVALID, "%s: NULL offset table", what);
+  for (uint32_t e = 0; e < a->n_offs; e++)
+    if (!std::isfinite(offs[3u * (size_t)e]) || !std::isfinite(offs[3u * (size_t)e + 1u]) || !std::isfinite(offs[3u * (size_t)e + 2u]))
+      return fail(RT_ERR_INVALID, "%s: offset %u has a non-finite component", what, e);
+  return RT_OK;
+}
+
+int lighting_count_check(uint64_t n, const char *what) {
+  return (n == 0 || n >= (1ull << 31)) ? fail(RT_ERR_INVALID, "%s: n %llu not in 1..2^31 - 1", what, (unsigned long long)n) : RT_OK;
+}
+
+int lighting_outputs_check(const rt_lighting_outputs *out, const char *what) {
+  if (!out) return fail(RT_ERR_INVALID, "%s: NULL outputs", what);
+  if (!out->diffuse && !out->intensity && !out->lit && !out->rgba) return fail(RT_ERR_INVALID, "%s: every output is NULL", what);
+  if (((uintptr_t)out->diffuse & 7u) || ((uintptr_t)out->intensity & 7u) || ((uintptr_t)out->lit & 7u) || ((uintptr_t)out->rgba & 3u))
+    return fail(RT_ERR_INVALID, "%s: misaligned output (diffuse, intensity and lit need 8 bytes, rgba 4)", what);
+  return RT_OK;
+}
+
+// a device table: NULL only where it is not read
+int lighting_offs_check(const struct rt_lighting &a, const double *d_offs, const char *what) {
+  if ((!d_offs && a.light_radius != 0.0) || ((uintptr_t)d_offs & 7u)) return fail(RT_ERR_INVALID, "%s: NULL or misaligned offset table (8 bytes)", what);
+  return RT_OK;
+}
+
+rt_lighting_launch launch_of(const struct rt_lighting &a, const double *offs, uint32_t n, const rt_hit *hits) {
+  rt_lighting_launch L;
+  memset(&L, 0, sizeof L);
+  L.hits = hits; L.offs = offs; L.n = n;
+  L.base = a.base; L.light_radius = a.light_radius;
+  L.n_samples = a.n_samples; L.n_offs = a.n_offs; L.stride = a.stride;
+  return L;
+}
+
+// the fused kernel for receivers [0, n) of d_hits with the description's base as given
+int lighting_launch(rt_scene_dev *s, const struct rt_lighting &a, const double *d_offs, uint32_t n, const rt_hit *d_hits, const uint32_t *d_order,
+                    const rt_lighting_outputs &out, hipStream_t stream, rt_stats *stats) {
+  stats_clock clock;
+  rt_lighting_launch L = launch_of(a, d_offs, n, d_hits);
+  {
+    std::lock_guard<std::mutex> lk(s->launch_mu);
+    if (int rc = enter_launch(s, stream)) return rc;
+    L.objects = (const rt_sphere *)(obj_block(s) + s->o_objs);   // this generation's spheres, in blob order
+    L.light_intensity = s->hd.light_intensity;                   // (rt_scene_set_light_intensity, rt_scene_set_lights: this launch's)
+    memcpy(L.lights, s->lights, sizeof L.lights);
+  }
+  L.epsilon = s->hd.epsilon;
+  L.n_objects = s->hd.n_objects; L.n_lights = s->hd.n_lights;
+  L.order = d_order;
+  L.diffuse = out.diffuse; L.intensity = out.intensity; L.lit = out.lit; L.rgba = out.rgba;
+  if (int rc = clock.start(stats, stream)) return rc;
+  const int err = rt_launch_lighting(&L, (void *)stream);
+  if (err != 0) return fail(RT_ERR_DEVICE, "lighting kernel launch: %s", hipGetErrorString((hipError_t)err));
+  return clock.finish(stats, n);
+}
+
+constexpr uint32_t RT_LIGHTING_VIEW_BAND_BYTES = 128u;    // per pixel of a band: the ray 48, its hit record 80
+
+bool lighting_view_size_ok(uint32_t w, uint32_t h) { return w != 0 && h != 0 && (uint64_t)w * h < (1ull << 31); }
+
+// The view's rows [row0, row_end) in bands of at most band_rows: per band the rays (rt_views.hip), their hit records (rt_hits.hip) and the
+// fused kernel with base = a.base + y * w, so that pixel i = y * w + x is receiver i whatever the band.  The outputs' first record is
+// pixel out_row0 * w.  One stream: every launch comes behind the one that wrote what it reads.  (The view was checked by the caller.)
+int lighting_view_bands(rt_scene_dev *s, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting &a, const double *d_offs, uint32_t row0,
+                        uint32_t row_end, uint32_t band_rows, const rt_lighting_outputs &out, uint32_t out_row0, void *d_work, hipStream_t stream) {
+  double *rays = (double *)d_work;
+  rt_hit *hits = (rt_hit *)(rays + 6u * ((size_t)band_rows * w));
+  for (uint32_t y = row0; y < row_end; y += band_rows) {
+    const uint32_t m = row_end - y < band_rows ? row_end - y : band_rows;
+    if (int rc = rt_view_rays_device(s->device, v, w, h, y, m, rays, (void *)stream)) return rc;
+    const rt_ray_outputs into = {nullptr, nullptr, hits};
+    if (int rc = trace_rays_launch(s, m * w, y * w, rays, nullptr, 1u, into, stream, nullptr)) return rc;
+    struct rt_lighting ab = a;
+    ab.base = a.base + (uint64_t)y * w;
+    const size_t at = (size_t)(y - out_row0) * w;
+    const rt_lighting_outputs band = {out.diffuse ? out.diffuse + at : nullptr, out.intensity ? out.intensity + at : nullptr, out.lit ? out.lit + at : nullptr,
+                                      out.rgba ? out.rgba + at : nullptr};
+    if (int rc = lighting_launch(s, ab, d_offs, m * w, hits, nullptr, band, stream, nullptr)) return rc;
+  }
+  return RT_OK;
+}
+
+// the outputs of one chunk in device memory, and their way back
+struct chunk_outputs {
+  device_mem diffuse, intensity, lit, rgba;
+  int alloc(const rt_lighting_outputs &ho, size_t chunk) {
+    if (ho.diffuse) HIP_TRY(hipMalloc(&diffuse.h, chunk * 8u));
+    if (ho.intensity) HIP_TRY(hipMalloc(&intensity.h, chunk * 8u));
+    if (ho.lit) HIP_TRY(hipMalloc(&lit.h, chunk * 8u));
+    if (ho.rgba) HIP_TRY(hipMalloc(&rgba.h, chunk * 4u));
+    return RT_OK;
+  }
+  rt_lighting_outputs dev() const { return rt_lighting_outputs{(double *)diffuse.h, (double *)intensity.h, (double *)lit.h, (uint32_t *)rgba.h}; }
+  int copy_back(const rt_lighting_outputs &ho, size_t at, size_t n, hipStream_t stream) {
+    if (ho.diffuse) HIP_TRY(hipMemcpyAsync(ho.diffuse + at, diffuse.h, n * 8u, hipMemcpyDeviceToHost, stream));
+    if (ho.intensity) HIP_TRY(hipMemcpyAsync(ho.intensity + at, intensity.h, n * 8u, hipMemcpyDeviceToHost, stream));
+    if (ho.lit) HIP_TRY(hipMemcpyAsync(ho.lit + at, lit.h, n * 8u, hipMemcpyDeviceToHost, stream));
+    if (ho.rgba) HIP_TRY(hipMemcpyAsync(ho.rgba + at, rgba.h, n * 4u, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return RT_OK;
+  }
+};
+
+// the table of a host form in device memory: not allocated where it is not read
+int upload_offs(const struct rt_lighting &a, const double *offs, device_mem *d_offs, hipStream_t stream) {
+  if (a.light_radius == 0.0) return RT_OK;
+  HIP_TRY(hipMalloc(&d_offs->h, (size_t)a.n_offs * 24u));
+  HIP_TRY(hipMemcpyAsync(d_offs->h, offs, (size_t)a.n_offs * 24u, hipMemcpyHostToDevice, stream));
+  return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_lighting_validate(const struct rt_lighting *a, const double *offs) { return lighting_table_check(a, offs, "rt_lighting_validate"); }
+
+extern "C" int rt_lighting_sphere_offsets(uint32_t n, double *out_3n) {
+  if (n < 1u || n > RT_LIGHTING_MAX_OFFS || !out_3n) return fail(RT_ERR_INVALID, "rt_lighting_sphere_offsets: n %u not in 1..%u, or a NULL output", n, RT_LIGHTING_MAX_OFFS);
+  rt_lighting_sphere_offsets_host(n, out_3n);
+  return RT_OK;
+}
+
+extern "C" int rt_lighting_segments(const struct rt_lighting *a, const double *offs, uint32_t n_lights, const double *lights_xyz, uint64_t n, const rt_hit *hits,
+                                    uint32_t sample, uint32_t light, double *out_rays, double *out_length, double *out_mag, double *out_dot, int32_t *out_skip) {
+  const char *what = "rt_lighting_segments";
+  int rc = lighting_table_check(a, offs, what);
+  if (rc) return rc;
+  if (n_lights < 1u || n_lights > RT_MAX_LIGHTS || !lights_xyz) return fail(RT_ERR_INVALID, "%s: n_lights %u not in 1..%u, or NULL lights", what, n_lights, RT_MAX_LIGHTS);
+  if ((rc = lighting_count_check(n, what))) return rc;
+  if (sample >= a->n_samples) return fail(RT_ERR_INVALID, "%s: sample %u not below n_samples %u", what, sample, a->n_samples);
+  if (light >= n_lights) return fail(RT_ERR_INVALID, "%s: light %u not below n_lights %u", what, light, n_lights);
+  if (!hits || !out_rays) return fail(RT_ERR_INVALID, "%s: NULL hit records or ray output", what);
+  rt_lighting_launch L = launch_of(*a, offs, (uint32_t)n, hits);
+  L.n_lights = n_lights;
+  memcpy(L.lights, lights_xyz, (size_t)n_lights * 24u);
+  rt_lighting_segments_host(&L, sample, light, out_rays, out_length, out_mag, out_dot, out_skip);
+  return RT_OK;
+}
+
+// (the arguments first: they are judged without a scene, and before a device is touched)
+extern "C" int rt_scene_lighting_device(rt_scene_dev *s, const struct rt_lighting *a, const double *d_offs, uint64_t n, const rt_hit *d_hits,
+                                        const uint32_t *d_order, const rt_lighting_outputs *d_out, void *hip_stream, rt_stats *stats) {
+  const char *what = "rt_scene_lighting_device";
+  int rc = lighting_check(a, what);
+  if (rc) return rc;
+  if ((rc = lighting_count_check(n, what))) return rc;
+  if ((rc = lighting_offs_check(*a, d_offs, what))) return rc;
+  if (!d_hits || ((uintptr_t)d_hits & 7u)) return fail(RT_ERR_INVALID, "%s: NULL or misaligned hit records (8 bytes)", what);
+  if ((rc = lighting_outputs_check(d_out, what))) return rc;
+  if ((uintptr_t)d_order & 3u) return fail(RT_ERR_INVALID, "%s: misaligned order (4 bytes)", what);
+  if (!s) return fail(RT_ERR_STATE, "%s: NULL scene handle", what);
+  hipStream_t stream = nullptr;
+  if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
+  return lighting_launch(s, *a, d_offs, (uint32_t)n, d_hits, d_order, *d_out, stream, stats);
+}
+
+extern "C" int rt_lighting(const void *blob, size_t bytes, const struct rt_lighting *a, const double *offs, uint64_t n, const rt_hit *hits,
+                           const rt_lighting_outputs *ho, rt_stats *stats) {
+  const char *what = "rt_lighting";
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  if ((rc = lighting_table_check(a, offs, what))) return rc;
+  if (n == 0) return fail(RT_ERR_INVALID, "%s: n is 0", what);
+  if (!hits) return fail(RT_ERR_INVALID, "%s: NULL hit records", what);
+  if ((rc = lighting_outputs_check(ho, what))) return rc;
+  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
+  std::lock_guard<std::mutex> lk(G.mu);
+  stats_clock clock;
+  rt_scene_dev *s = nullptr;
+  if ((rc = resident_scene(0, blob, bytes, &s))) return rc;
+  if ((rc = ensure_device(0))) return rc;
+  hipStream_t stream = G.dev[0].stream;
+  const size_t chunk = n < RT_LIGHTING_CHUNK ? (size_t)n : (size_t)RT_LIGHTING_CHUNK;
+  device_mem d_hits, d_offs;         // of one chunk; the table (released on every way out)
+  chunk_outputs d_out;
+  HIP_TRY(hipMalloc(&d_hits.h, chunk * sizeof(rt_hit)));
+  if ((rc = upload_offs(*a, offs, &d_offs, stream))) return rc;
+  if ((rc = d_out.alloc(*ho, chunk))) return rc;
+  double kernel_ms = 0.0;
+  for (uint64_t at = 0; at < n; at += RT_LIGHTING_CHUNK) {
+    const size_t m = n - at < RT_LIGHTING_CHUNK ? (size_t)(n - at) : (size_t)RT_LIGHTING_CHUNK;
+    HIP_TRY(hipMemcpyAsync(d_hits.h, hits + at, m * sizeof(rt_hit), hipMemcpyHostToDevice, stream));
+    struct rt_lighting ac = *a;
+    ac.base = a->base + at;          // receiver `at + i` of the list is receiver i of this chunk
+    rt_stats st;
+    if ((rc = lighting_launch(s, ac, (const double *)d_offs.h, (uint32_t)m, (const rt_hit *)d_hits.h, nullptr, d_out.dev(), stream, stats ? &st : nullptr))) return rc;
+    if (stats) kernel_ms += st.kernel_ms;
+    if ((rc = d_out.copy_back(*ho, (size_t)at, m, stream))) return rc;
+  }
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = kernel_ms;
+    stats->pixels = n;
+    stats->total_ms = clock.host_ms();
+  }
+  return RT_OK;
+}
+
+extern "C" size_t rt_lighting_view_work_bytes(uint32_t w, uint32_t h) {
+  // the whole view in one band, as rt_ambient_view_work_bytes
+  return lighting_view_size_ok(w, h) ? (size_t)w * h * RT_LIGHTING_VIEW_BAND_BYTES : 0;
+}
+
+extern "C" int rt_scene_lighting_view_device(rt_scene_dev *s, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting *a, const double *d_offs,
+                                             const rt_lighting_outputs *d_out, void *d_work, size_t work_bytes, void *hip_stream, rt_stats *stats) {
+  const char *what = "rt_scene_lighting_view_device";
+  if (!s) return fail(RT_ERR_STATE, "%s: NULL scene handle", what);
+  int rc = rt_view_validate(v, w, h);
+  if (rc) return rc;
+  if ((rc = lighting_check(a, what))) return rc;
+  if ((rc = lighting_offs_check(*a, d_offs, what))) return rc;
+  if ((rc = lighting_outputs_check(d_out, what))) return rc;
+  if (!d_work || ((uintptr_t)d_work & 15u)) return fail(RT_ERR_INVALID, "%s: NULL or misaligned workspace (16 bytes)", what);
+  const uint64_t row_bytes = (uint64_t)w * RT_LIGHTING_VIEW_BAND_BYTES;
+  if (work_bytes < row_bytes) return fail(RT_ERR_INVALID, "%s: work_bytes %llu below one row of a band, %llu", what, (unsigned long long)work_bytes, (unsigned long long)row_bytes);
+  hipStream_t stream = nullptr;
+  if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
+  const uint64_t fit = work_bytes / row_bytes;
+  const uint32_t band_rows = fit < h ? (uint32_t)fit : h;
+  stats_clock clock;
+  if ((rc = clock.start(stats, stream))) return rc;
+  if ((rc = lighting_view_bands(s, v, w, h, *a, d_offs, 0u, h, band_rows, *d_out, 0u, d_work, stream))) return rc;
+  return clock.finish(stats, (uint64_t)w * h);
+}
+
+extern "C" int rt_lighting_view(const void *blob, size_t bytes, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting *a, const double *offs,
+                                const rt_lighting_outputs *ho, rt_stats *stats) {
+  const char *what = "rt_lighting_view";
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  if ((rc = rt_view_validate(v, w, h))) return rc;
+  if ((rc = lighting_table_check(a, offs, what))) return rc;
+  if ((rc = lighting_outputs_check(ho, what))) return rc;
+  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
+  std::lock_guard<std::mutex> lk(G.mu);
+  stats_clock clock;
+  rt_scene_dev *s = nullptr;
+  if ((rc = resident_scene(0, blob, bytes, &s))) return rc;
+  if ((rc = ensure_device(0))) return rc;
+  hipStream_t stream = G.dev[0].stream;
+  // chunks of whole rows of at most RT_LIGHTING_CHUNK pixels; a longer row is its own chunk
+  uint64_t chunk_rows = RT_LIGHTING_CHUNK / w;
+  if (chunk_rows < 1u) chunk_rows = 1u;
+  if (chunk_rows > h) chunk_rows = h;
+  const size_t chunk = (size_t)chunk_rows * w;
+  device_mem d_work, d_offs, d_lon, d_lat;      // of one chunk; the table; the panorama's tables (released on every way out)
+  chunk_outputs d_out;
+  HIP_TRY(hipMalloc(&d_work.h, chunk * RT_LIGHTING_VIEW_BAND_BYTES));
+  if ((rc = upload_offs(*a, offs, &d_offs, stream))) return rc;
+  if ((rc = d_out.alloc(*ho, chunk))) return rc;
+  rt_view dv = *v;
+  if (v->model == RT_VIEW_EQUIRECT) {
+    HIP_TRY(hipMalloc(&d_lon.h, (size_t)w * 16u));
+    HIP_TRY(hipMalloc(&d_lat.h, (size_t)h * 16u));
+    HIP_TRY(hipMemcpyAsync(d_lon.h, v->lon, (size_t)w * 16u, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d_lat.h, v->lat, (size_t)h * 16u, hipMemcpyHostToDevice, stream));
+    dv.lon = (const double *)d_lon.h; dv.lat = (const double *)d_lat.h;
+  }
+  double kernel_ms = 0.0;
+  for (uint32_t y = 0; y < h; y += (uint32_t)chunk_rows) {
+    const uint32_t m = h - y < chunk_rows ? h - y : (uint32_t)chunk_rows;
+    stats_clock step;
+    rt_stats st;
+    if ((rc = step.start(stats, stream))) return rc;
+    if ((rc = lighting_view_bands(s, &dv, w, h, *a, (const double *)d_offs.h, y, y + m, m, d_out.dev(), y, d_work.h, stream))) return rc;
+    if ((rc = step.finish(stats ? &st : nullptr, (uint64_t)m * w))) return rc;
+    if (stats) kernel_ms += st.kernel_ms;
+    if ((rc = d_out.copy_back(*ho, (size_t)y * w, (size_t)m * w, stream))) return rc;
+  }
+  if (stats) {
+    memset(stats, 0, sizeof *stats);
+    stats->kernel_ms = kernel_ms;
+    stats->pixels = (uint64_t)w * h;
+    stats->total_ms = clock.host_ms();
+  }
+  return RT_OK;
+}

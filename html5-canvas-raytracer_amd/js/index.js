@@ -363,10 +363,48 @@ function ambientView(sceneObj, view, w, h, opts) {
     !!o.open, !!o.intensity, o.rgba !== false);
 }
 
+// Sampled lights (include/rt_hip.h: struct rt_lighting): how much light arrives at each receiver - the reference's light loop
+// (main.js:283-306) opts.samples times, every light displaced by opts.lightRadius times an entry of opts.offsets, averaged on the GPU.
+// With the defaults (one sample, lightRadius 0) it is the reference's own loop.  Returns {diffuse: Float64Array (the mean raw diffuse
+// sum), intensity: Float64Array (the mean intensity left after the last light, quirk q2), lit: Float64Array (the share of (sample, light)
+// pairs that arrived), rgba: Uint8ClampedArray (min(1, diffuse) as a grey pixel), kernel_ms} - each null unless named in opts.want.
+//   lightingOffsets(n)             the library's spiral over the unit sphere: Float64Array, 3 per entry
+//   lighting(scene, hits, opts)    hits as for ambient.  opts: samples (default 1), lightRadius (default 0), offsets (default
+//                                  lightingOffsets(samples)), stride (default 1), base (default 0), want (default ['diffuse'])
+//   lightingView(scene, view, w, h, opts)   the same for what the view sees; want defaults to ['rgba']
+const LIGHTING_OUTPUTS = ['diffuse', 'intensity', 'lit', 'rgba'];
+function lightingOffsets(n) { return native().lightingOffsets(n); }
+function lightingOpts(o, who, wantDefault) {
+  const samples = o.samples === undefined ? 1 : o.samples, offs = o.offsets || native().lightingOffsets(samples);
+  if (!(offs instanceof Float64Array) || offs.length === 0 || offs.length % 3 !== 0) throw new TypeError(who + ': offsets must be a Float64Array of 3 numbers per entry');
+  const want = o.want === undefined ? wantDefault : o.want;
+  if (!Array.isArray(want) || want.length === 0 || !want.every((k) => LIGHTING_OUTPUTS.includes(k))) {
+    throw new TypeError(who + ": want names some of 'diffuse', 'intensity', 'lit', 'rgba'");
+  }
+  return [offs, samples, o.stride === undefined ? 1 : o.stride, o.base || 0, o.lightRadius === undefined ? 0 : o.lightRadius,
+    ...LIGHTING_OUTPUTS.map((k) => want.includes(k))];
+}
+function lighting(sceneObj, hits, opts) {
+  if (!(hits instanceof Uint8Array ? hits.length > 0 && hits.length % HIT_BYTES === 0 : Array.isArray(hits) && hits.length > 0)) {
+    throw new TypeError('lighting: hits must be a non-empty array of hit objects or a Uint8Array of 80-byte records');
+  }
+  const o = opts || {};
+  const args = lightingOpts(o, 'lighting', ['diffuse']);
+  if (!inited) init(o.maxDevices);
+  return native().lighting(new Uint8Array(flattenScene(sceneObj)), hitRecords(hits), ...args);
+}
+function lightingView(sceneObj, view, w, h, opts) {
+  if (!view || !Number.isInteger(view.model)) throw new TypeError('lightingView: view must come from views.reference / pinhole / ortho / equirect');
+  const o = opts || {};
+  const args = lightingOpts(o, 'lightingView', ['rgba']);
+  if (!inited) init(o.maxDevices);
+  return native().lightingView(new Uint8Array(flattenScene(sceneObj)), viewBytes(view), view.lon || null, view.lat || null, w, h, ...args);
+}
+
 // `const build = '741'` (main.js:3) + this library's revision; every render's `.stats` also carries `.build` and `.report`, the
 // reference's end-of-frame string 'build #<id> (<elapsed>ms)' (main.js:204-205) for that render.
 function buildId() { return native().buildId(); }
 
 function shutdown() { if (addon) addon.shutdown(); inited = false; }
 
-module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, traceView, views, shadeRays, primaryRays, normal3D, occlusion, lightSegments, ambient, ambientView, ambientDirs, init, shutdown, buildId, flattenScene, scenes, native}, scene);
+module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, traceView, views, shadeRays, primaryRays, normal3D, occlusion, lightSegments, ambient, ambientView, ambientDirs, lighting, lightingView, lightingOffsets, init, shutdown, buildId, flattenScene, scenes, native}, scene);

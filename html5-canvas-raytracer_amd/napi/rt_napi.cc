@@ -1084,6 +1084,172 @@ napi_value AmbientView(napi_env env, napi_callback_info info) {
   return ambient_result(env, n, want, abs, st.kernel_ms);
 }
 
+// ---- sampled lights (include/rt_hip.h: struct rt_lighting)
+// lightingOffsets(n): the spiral over the unit sphere (rt_lighting_sphere_offsets) as a Float64Array of 3 n numbers
+napi_value LightingOffsets(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  uint32_t n = 0;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 1 || napi_get_value_uint32(env, argv[0], &n) != napi_ok || n < 1 || n > 65536) {
+    napi_throw_type_error(env, nullptr, "lightingOffsets(n): n in 1..65536");
+    return nullptr;
+  }
+  napi_value ab, v;
+  void *data = nullptr;
+  NAPI_TRY(napi_create_arraybuffer(env, (size_t)n * 24u, &data, &ab));
+  const int rc = rt_lighting_sphere_offsets(n, (double *)data);
+  if (rc != RT_OK) return throw_rt(env, "rt_lighting_sphere_offsets", rc);
+  NAPI_TRY(napi_create_typedarray(env, napi_float64_array, 3u * (size_t)n, ab, 0, &v));
+  return v;
+}
+
+// the tail both lighting calls share: [offs: Float64Array (3 per entry), nSamples, stride, base, lightRadius, wantDiffuse, wantIntensity, wantLit,
+// wantRgba] from argv[at] on -> the description, the table, the wanted outputs; false (a TypeError is pending) where an argument is of the wrong kind
+bool lighting_args(napi_env env, size_t argc, napi_value *argv, size_t at, const char *who, struct rt_lighting *a, const double **offs, bool want[4]) {
+  size_t len = 0;
+  double base = 0.0;
+  memset(a, 0, sizeof *a);
+  if (argc < at + 5 || !(*offs = f64_array(env, argv[at], &len)) || len == 0 || len % 3u != 0 || len / 3u > 65536u ||
+      napi_get_value_uint32(env, argv[at + 1], &a->n_samples) != napi_ok || napi_get_value_uint32(env, argv[at + 2], &a->stride) != napi_ok ||
+      napi_get_value_double(env, argv[at + 3], &base) != napi_ok || !(base >= 0.0 && base <= 9007199254740992.0) ||
+      napi_get_value_double(env, argv[at + 4], &a->light_radius) != napi_ok) {
+    napi_throw_type_error(env, nullptr, who);
+    return false;
+  }
+  a->n_offs = (uint32_t)(len / 3u);
+  a->base = (uint64_t)base;
+  want[0] = true; want[1] = false; want[2] = false; want[3] = false;
+  for (size_t i = 0; i < 4 && at + 5 + i < argc; i++) napi_get_value_bool(env, argv[at + 5 + i], &want[i]);
+  return true;
+}
+
+// {diffuse, intensity, lit: Float64Array | null, rgba: Uint8ClampedArray | null, kernel_ms}
+napi_value lighting_result(napi_env env, size_t n, const bool want[4], napi_value ab[4], double kernel_ms) {
+  static const char *const names[4] = {"diffuse", "intensity", "lit", "rgba"};
+  napi_value res, v;
+  napi_create_object(env, &res);
+  for (int i = 0; i < 4; i++) {
+    if (!want[i]) napi_get_null(env, &v);
+    else if (i < 3) napi_create_typedarray(env, napi_float64_array, n, ab[i], 0, &v);
+    else napi_create_typedarray(env, napi_uint8_clamped_array, 4 * n, ab[i], 0, &v);
+    napi_set_named_property(env, res, names[i], v);
+  }
+  napi_create_double(env, kernel_ms, &v); napi_set_named_property(env, res, "kernel_ms", v);
+  return res;
+}
+
+// lighting(blob, hits: Uint8Array (80 bytes per receiver: rt_hit), offs, nSamples, stride, base, lightRadius[, wantDiffuse, wantIntensity, wantLit, wantRgba]): rt_lighting
+napi_value Lighting(napi_env env, napi_callback_info info) {
+  const char *who = "lighting(blob: Uint8Array, hits: Uint8Array (80 bytes per receiver), offs: Float64Array (3 per entry), nSamples, stride, base, lightRadius[, wantDiffuse, wantIntensity, wantLit, wantRgba])";
+  size_t argc = 11;
+  napi_value argv[11];
+  bool is_ta = false, is_hits = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 7 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
+      napi_is_typedarray(env, argv[1], &is_hits) != napi_ok || !is_hits) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  napi_typedarray_type bt, ht; napi_value ab; size_t off, blob_len = 0, hits_len = 0;
+  void *blob_data = nullptr, *hits_data = nullptr;
+  napi_get_typedarray_info(env, argv[0], &bt, &blob_len, &blob_data, &ab, &off);
+  napi_get_typedarray_info(env, argv[1], &ht, &hits_len, &hits_data, &ab, &off);
+  if ((bt != napi_uint8_array && bt != napi_uint8_clamped_array) || ht != napi_uint8_array || hits_len == 0 || hits_len % sizeof(rt_hit) != 0) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  struct rt_lighting a;
+  const double *offs = nullptr;
+  bool want[4];
+  if (!lighting_args(env, argc, argv, 2, who, &a, &offs, want)) return nullptr;
+  const size_t n = hits_len / sizeof(rt_hit);
+  // the library wants the blob and the records 8-byte aligned: one aligned copy holds both
+  const size_t blob_room = (blob_len + 15) & ~(size_t)15;
+  uint8_t *mem = (uint8_t *)aligned_alloc(16, blob_room + ((hits_len + 15) & ~(size_t)15));
+  napi_value abs[4] = {nullptr, nullptr, nullptr, nullptr};
+  void *p[4] = {nullptr, nullptr, nullptr, nullptr};
+  const size_t each[4] = {8u, 8u, 8u, 4u};
+  bool ok = mem != nullptr;
+  for (int i = 0; i < 4 && ok; i++) if (want[i]) ok = napi_create_arraybuffer(env, n * each[i], &p[i], &abs[i]) == napi_ok;
+  if (!ok) {
+    free(mem);
+    napi_throw_error(env, nullptr, "lighting: out of memory");
+    return nullptr;
+  }
+  memcpy(mem, blob_data, blob_len);
+  memcpy(mem + blob_room, hits_data, hits_len);
+  const rt_lighting_outputs out = {(double *)p[0], (double *)p[1], (double *)p[2], (uint32_t *)p[3]};
+  rt_stats st;
+  const int rc = rt_lighting(mem, blob_len, &a, offs, n, (const rt_hit *)(mem + blob_room), &out, &st);
+  free(mem);
+  if (rc != RT_OK) return throw_rt(env, "rt_lighting", rc);
+  return lighting_result(env, n, want, abs, st.kernel_ms);
+}
+
+// lightingView(blob, view, lon, lat, w, h, offs, nSamples, stride, base, lightRadius[, wantDiffuse, wantIntensity, wantLit, wantRgba]): rt_lighting_view.
+// `view`, lon and lat as for traceView.
+napi_value LightingView(napi_env env, napi_callback_info info) {
+  const char *who = "lightingView(blob: Uint8Array, view: Uint8Array, lon, lat, w, h, offs: Float64Array (3 per entry), nSamples, stride, base, lightRadius[, wantDiffuse, wantIntensity, wantLit, wantRgba])";
+  size_t argc = 15;
+  napi_value argv[15];
+  bool is_ta = false, is_view = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 11 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
+      napi_is_typedarray(env, argv[1], &is_view) != napi_ok || !is_view) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  napi_typedarray_type bt, vt; napi_value ab; size_t off, blob_len = 0, view_len = 0;
+  void *blob_data = nullptr, *view_data = nullptr;
+  napi_get_typedarray_info(env, argv[0], &bt, &blob_len, &blob_data, &ab, &off);
+  napi_get_typedarray_info(env, argv[1], &vt, &view_len, &view_data, &ab, &off);
+  uint32_t w = 0, h = 0;
+  if ((bt != napi_uint8_array && bt != napi_uint8_clamped_array) || vt != napi_uint8_array || view_len != sizeof(rt_view) ||
+      napi_get_value_uint32(env, argv[4], &w) != napi_ok || napi_get_value_uint32(env, argv[5], &h) != napi_ok) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  rt_view view;
+  memcpy(&view, view_data, sizeof view);
+  view.lon = view.lat = nullptr;
+  size_t table_len[2] = {0, 0};
+  const double *table_data[2] = {f64_array(env, argv[2], &table_len[0]), f64_array(env, argv[3], &table_len[1])};
+  if (view.model == RT_VIEW_EQUIRECT && (table_len[0] != 2u * (size_t)w || table_len[1] != 2u * (size_t)h)) {
+    napi_throw_type_error(env, nullptr, "lightingView: an equirect view needs lon and lat, Float64Arrays of 2 w and 2 h numbers");
+    return nullptr;
+  }
+  struct rt_lighting a;
+  const double *offs = nullptr;
+  bool want[4];
+  if (!lighting_args(env, argc, argv, 6, who, &a, &offs, want)) return nullptr;
+  if (argc < 12) { want[0] = false; want[3] = true; }                             // (a view's default output is the picture)
+  const bool sized = w != 0 && h != 0 && (uint64_t)w * h < (1ull << 31);       // (anything else the library refuses: no buffer is sized from it)
+  const size_t n = sized ? (size_t)w * h : 0;
+  const size_t blob_room = (blob_len + 15) & ~(size_t)15, lon_room = table_len[0] * 8u, lat_room = table_len[1] * 8u;
+  uint8_t *mem = (uint8_t *)aligned_alloc(16, blob_room + lon_room + lat_room + 16u);
+  napi_value abs[4] = {nullptr, nullptr, nullptr, nullptr};
+  void *p[4] = {nullptr, nullptr, nullptr, nullptr};
+  const size_t each[4] = {8u, 8u, 8u, 4u};
+  bool ok = mem != nullptr;
+  for (int i = 0; i < 4 && ok; i++) if (want[i]) ok = napi_create_arraybuffer(env, n * each[i], &p[i], &abs[i]) == napi_ok;
+  if (!ok) {
+    free(mem);
+    napi_throw_error(env, nullptr, "lightingView: out of memory");
+    return nullptr;
+  }
+  memcpy(mem, blob_data, blob_len);
+  if (view.model == RT_VIEW_EQUIRECT) {
+    memcpy(mem + blob_room, table_data[0], lon_room);
+    memcpy(mem + blob_room + lon_room, table_data[1], lat_room);
+    view.lon = (const double *)(mem + blob_room);
+    view.lat = (const double *)(mem + blob_room + lon_room);
+  }
+  const rt_lighting_outputs out = {(double *)p[0], (double *)p[1], (double *)p[2], (uint32_t *)p[3]};
+  rt_stats st;
+  const int rc = rt_lighting_view(mem, blob_len, &view, w, h, &a, offs, &out, &st);
+  free(mem);
+  if (rc != RT_OK) return throw_rt(env, "rt_lighting_view", rc);
+  return lighting_result(env, n, want, abs, st.kernel_ms);
+}
+
 napi_value Module(napi_env env, napi_value exports) {
   const napi_property_descriptor props[] = {
       {"init", nullptr, Init, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
@@ -1108,6 +1274,9 @@ napi_value Module(napi_env env, napi_value exports) {
       {"ambientDirs", nullptr, AmbientDirs, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ambient", nullptr, Ambient, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ambientView", nullptr, AmbientView, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"lightingOffsets", nullptr, LightingOffsets, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"lighting", nullptr, Lighting, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"lightingView", nullptr, LightingView, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   return exports;

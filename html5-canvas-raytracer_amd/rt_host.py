@@ -234,6 +234,19 @@ class RtAmbientOutputs(C.Structure):
     _fields_ = [("open", C.c_void_p), ("intensity", C.c_void_p), ("rgba", C.c_void_p)]
 
 
+class RtLighting(C.Structure):
+    """Sampled lights (include/rt_hip.h struct rt_lighting, 32 bytes): n_samples runs of the light loop per receiver, the offset table's
+    n_offs entries, the stride and base of the entry index e = ((base + i) * stride + s) % n_offs, and the lights' radius."""
+    _fields_ = [("n_samples", C.c_uint32), ("n_offs", C.c_uint32), ("stride", C.c_uint32), ("reserved", C.c_uint32), ("base", C.c_uint64),
+                ("light_radius", C.c_double)]
+
+
+class RtLightingOutputs(C.Structure):
+    """Outputs of sampled lights (include/rt_hip.h rt_lighting_outputs): float64 diffuse, float64 intensity, float64 lit, uint32 rgba per
+    receiver; NULL = not wanted."""
+    _fields_ = [("diffuse", C.c_void_p), ("intensity", C.c_void_p), ("lit", C.c_void_p), ("rgba", C.c_void_p)]
+
+
 # every symbol include/rt_hip.h declares: (restype, argtypes)
 ABI = {
     "rt_init": (C.c_int, [C.c_int]),
@@ -347,6 +360,19 @@ ABI = {
                                                C.POINTER(RtAmbientOutputs), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RtStats)]),
     "rt_ambient_view": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtAmbient), C.c_void_p,
                                   C.POINTER(RtAmbientOutputs), C.POINTER(RtStats)]),
+    "rt_lighting_validate": (C.c_int, [C.POINTER(RtLighting), C.c_void_p]),
+    "rt_lighting_sphere_offsets": (C.c_int, [C.c_uint32, C.c_void_p]),
+    "rt_lighting_segments": (C.c_int, [C.POINTER(RtLighting), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_scene_lighting_device": (C.c_int, [C.c_void_p, C.POINTER(RtLighting), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtLightingOutputs),
+                                           C.c_void_p, C.POINTER(RtStats)]),
+    "rt_lighting": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtLighting), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(RtLightingOutputs),
+                              C.POINTER(RtStats)]),
+    "rt_lighting_view_work_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_scene_lighting_view_device": (C.c_int, [C.c_void_p, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtLighting), C.c_void_p,
+                                                C.POINTER(RtLightingOutputs), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_lighting_view": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtLighting), C.c_void_p,
+                                   C.POINTER(RtLightingOutputs), C.POINTER(RtStats)]),
 }
 
 RT_MAX_SEGS = 16
@@ -687,6 +713,35 @@ class Renderer:
         rc = self.lib.rt_scene_ambient_view_device(self.handle, C.byref(view), w, h, C.byref(a), C.c_void_p(dirs_ptr or 0), C.byref(out),
                                                    C.c_void_p(work_ptr or 0), work_bytes, C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
         _check(self.lib, rc, "rt_scene_ambient_view_device")
+        return st
+
+    def lighting(self, n, hits_ptr, offs_ptr, n_offs, n_samples, light_radius, diffuse_ptr, intensity_ptr, lit_ptr, rgba_ptr, stride=1, base=0, order_ptr=0,
+                 stream=None, want_stats=False):
+        """The reference's light loop (main.js:283-306) for n receivers (HIT_DTYPE records, DEVICE) in one fused kernel, n_samples times
+        with every light displaced by an entry of the table offs_ptr (DEVICE, n_offs entries of 3 float64; 0 where light_radius is 0)
+        times light_radius, with the scene's CURRENT lights and light intensity - per receiver float64 diffuse (the mean raw diffuse sum),
+        float64 intensity (the mean intensity left after the last light), float64 lit (the share of (sample, light) pairs that
+        contributed) and uint32 rgba (min(1, diffuse) as a grey RGBA8 pixel) into DEVICE buffers (0 / None = not wanted).  order_ptr as
+        occlusion takes it."""
+        a = RtLighting(n_samples, n_offs, stride, 0, base, float(light_radius))
+        out = RtLightingOutputs(diffuse_ptr or None, intensity_ptr or None, lit_ptr or None, rgba_ptr or None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_lighting_device(self.handle, C.byref(a), C.c_void_p(offs_ptr or 0), n, C.c_void_p(hits_ptr or 0), C.c_void_p(order_ptr or 0),
+                                               C.byref(out), C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_lighting_device")
+        return st
+
+    def lighting_view(self, view, w, h, offs_ptr, n_offs, n_samples, light_radius, diffuse_ptr, intensity_ptr, lit_ptr, rgba_ptr, work_ptr, work_bytes,
+                      stride=1, base=0, stream=None, want_stats=False):
+        """lighting() for what `view` sees at w x h, pixel y w + x being receiver y w + x, into DEVICE buffers in frame order: rays, hit
+        records and scans stay on the GPU, band by band in work_ptr (DEVICE, 16-byte aligned, work_bytes >= 128 w;
+        lighting_view_work_bytes(w, h) is the size the library prefers).  An EQUIRECT view's tables are DEVICE pointers here."""
+        a = RtLighting(n_samples, n_offs, stride, 0, base, float(light_radius))
+        out = RtLightingOutputs(diffuse_ptr or None, intensity_ptr or None, lit_ptr or None, rgba_ptr or None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_lighting_view_device(self.handle, C.byref(view), w, h, C.byref(a), C.c_void_p(offs_ptr or 0), C.byref(out),
+                                                    C.c_void_p(work_ptr or 0), work_bytes, C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_lighting_view_device")
         return st
 
     def shade_rays(self, n, rays_ptr, nodes_ptr, order_ptr=0, pix_ptr=0, path_ptr=0, stream=None, want_stats=False):
@@ -1433,6 +1488,105 @@ def ambient_view(scene, v, w, h, n_samples, radius, dirs=None, stride=1, want=("
     _init_once(lib)
     buf = C.create_string_buffer(blob, len(blob))
     _check(lib, lib.rt_ambient_view(buf, len(blob), C.byref(v), w, h, C.byref(a), C.c_void_p(dirs.ctypes.data), C.byref(bufs), None), "rt_ambient_view")
+    return out
+
+
+# --------------------------------------------------------------------------- sampled lights (include/rt_hip.h: rt_lighting)
+LIGHTING_OUTPUTS = ("diffuse", "intensity", "lit", "rgba")
+
+
+def lighting_offsets(n, lib=None):
+    """-> (n, 3) float64: rt_lighting_sphere_offsets' spiral of n points on the unit sphere: entry k is {r cos(phi), r sin(phi), z} with
+    z = 1 - (2 k + 1) / n, r = sqrt(1 - z z), phi = k pi (3 - sqrt(5)) (fdlibm's cos and sin: the same bits on every host).  Consecutive
+    entries lie on a ring: use whole sets (stride = n_samples over a table of sets), not neighbours of one long spiral."""
+    import numpy as np
+    lib = lib or load_library()
+    out = np.empty((max(n, 0), 3), np.float64)
+    _check(lib, lib.rt_lighting_sphere_offsets(n, C.c_void_p(out.ctypes.data)), "rt_lighting_sphere_offsets")
+    return out
+
+
+def _lighting_args(n_samples, light_radius, offs, stride, base, lib):
+    import numpy as np
+    if offs is None:
+        offs = lighting_offsets(n_samples, lib)
+    offs = np.ascontiguousarray(offs, np.float64)
+    if offs.ndim != 2 or offs.shape[1] != 3:
+        raise ValueError("offs must be an (n_offs, 3) array: offsets of a light, in units of light_radius")
+    return RtLighting(n_samples, offs.shape[0], stride, 0, base, float(light_radius)), offs
+
+
+def lighting_segments(scene_or_lights, hits, sample, light, n_samples, light_radius, offs=None, stride=1, base=0, lib=None):
+    """The host probe (rt_lighting_segments): the segments of (`sample`, `light`) of the receivers `hits` towards light `light` of a
+    scene dict (or of an (n_lights, 3) array of positions), displaced by light_radius times the sample's table entry - what the GPU
+    builds in registers, bit for bit.  -> a dict in light_segments' layout: "rays" (n, 6) {point, shadow_vec}, "length" (light_len),
+    "light_mag", "shadow_dot" (against hit.l, the normal on the ray's side), "mask" (not shadow_dot <= 0, and scanned: the loop goes on
+    to the scan) and "skip" (n,) int32 (hit_i; -1 for a receiver that is not scanned, whose other entries are NaN).  offs: None =
+    lighting_offsets(n_samples).  No GPU."""
+    import numpy as np
+    lib = lib or load_library()
+    h = _hits_array(hits)
+    xyz = np.array(light_positions(scene_or_lights["lights"] if isinstance(scene_or_lights, dict) else scene_or_lights), np.float64).reshape(-1, 3)
+    a, offs = _lighting_args(n_samples, light_radius, offs, stride, base, lib)
+    n = len(h)
+    rays, skip = np.empty((n, 6), np.float64), np.empty(n, np.int32)
+    length, mag, dot = np.empty(n, np.float64), np.empty(n, np.float64), np.empty(n, np.float64)
+    _check(lib, lib.rt_lighting_segments(C.byref(a), C.c_void_p(offs.ctypes.data), len(xyz), C.c_void_p(xyz.ctypes.data), n, C.c_void_p(h.ctypes.data), sample,
+                                         light, C.c_void_p(rays.ctypes.data), C.c_void_p(length.ctypes.data), C.c_void_p(mag.ctypes.data),
+                                         C.c_void_p(dot.ctypes.data), C.c_void_p(skip.ctypes.data)), "rt_lighting_segments")
+    with np.errstate(invalid="ignore"):
+        mask = ~(dot <= 0.0) & (skip >= 0)
+    return {"rays": rays, "length": length, "light_mag": mag, "shadow_dot": dot, "mask": mask, "skip": skip}
+
+
+def _lighting_outputs(n, want):
+    import numpy as np
+    want = set(want)
+    if not want or want - set(LIGHTING_OUTPUTS):
+        raise ValueError("want names some of 'diffuse', 'intensity', 'lit', 'rgba'")
+    out = {k: (np.empty((n, 4), np.uint8) if k == "rgba" else np.empty(n, np.float64)) for k in LIGHTING_OUTPUTS if k in want}
+    return out, RtLightingOutputs(*[out[k].ctypes.data if k in out else None for k in LIGHTING_OUTPUTS])
+
+
+def lighting(scene, hits, n_samples=1, light_radius=0.0, offs=None, stride=1, want=("diffuse",), base=0, lib=None):
+    """lighting(scene, hits) -> {"diffuse", "intensity", "lit": (n,) float64, "rgba": (n, 4) uint8} (the keys named in `want`): how much
+    light arrives at the receivers `hits` (a HIT_DTYPE array - view_hit_records, hit_records - or a list of hit dicts), by the
+    reference's light loop (main.js:283-306) on GPU 0 with rt_render's resident scene.  With the defaults it is the reference's own loop:
+    intensity is light_intensity_at's number, min(1, diffuse) * albedo[1] the reference's diffuse_intensity.  With n_samples > 1 and a
+    light_radius the loop runs n_samples times, every light displaced by light_radius times an entry of `offs` ((n_offs, 3); None =
+    lighting_offsets(n_samples); sample s of receiver i uses entry ((base + i) stride + s) % n_offs for every light), and the results are
+    averaged: soft shadows.  diffuse is the raw sum (li * shadow_dot / light_mag over the lights that arrive), lit the share of (sample,
+    light) pairs that arrived, rgba min(1, diffuse) as a grey pixel.  A receiver that is not scanned (a miss, a non-finite record): NaN,
+    NaN, 0.0, opaque black."""
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    h = _hits_array(hits)
+    if len(h) == 0:
+        raise ValueError("hits must not be empty")
+    a, offs = _lighting_args(n_samples, light_radius, offs, stride, base, lib)
+    out, bufs = _lighting_outputs(len(h), want)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    _check(lib, lib.rt_lighting(buf, len(blob), C.byref(a), C.c_void_p(offs.ctypes.data), len(h), C.c_void_p(h.ctypes.data), C.byref(bufs), None), "rt_lighting")
+    return out
+
+
+def lighting_view_work_bytes(w, h, lib=None):
+    """Bytes of device workspace Renderer.lighting_view prefers for a w x h view (host arithmetic; 0 for a size it refuses).  128 w - one
+    row - is the least it accepts."""
+    return int((lib or load_library()).rt_lighting_view_work_bytes(w, h))
+
+
+def lighting_view(scene, v, w, h, n_samples=1, light_radius=0.0, offs=None, stride=1, want=("rgba",), base=0, lib=None):
+    """lighting() of what the view sees at w x h, in frame order ("rgba" (w h, 4) uint8 is the grey frame): the view's rays, their hit
+    records and the light loops are made on the GPU (rt_lighting_view) - only the offset table goes up and the results come back."""
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    a, offs = _lighting_args(n_samples, light_radius, offs, stride, base, lib)
+    out, bufs = _lighting_outputs(w * h, want)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    _check(lib, lib.rt_lighting_view(buf, len(blob), C.byref(v), w, h, C.byref(a), C.c_void_p(offs.ctypes.data), C.byref(bufs), None), "rt_lighting_view")
     return out
 
 

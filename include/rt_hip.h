@@ -977,6 +977,104 @@ int rt_scene_ambient_view_device(rt_scene_dev *scene, const rt_view *v, uint32_t
 int rt_ambient_view(const void *scene_blob, size_t blob_bytes, const rt_view *v, uint32_t w, uint32_t h, const struct rt_ambient *a,
                     const double *dirs, const rt_ambient_outputs *host_out, rt_stats *stats);
 
+/* Sampled lights ("how much light arrives here"): the reference's light loop (main.js:283-306, and :316 for the picture) per RECEIVER,
+ * n_samples times, every light displaced by a table entry times light_radius in each sample, averaged on the GPU.  A receiver is an
+ * rt_hit record as for rt_ambient; a scan is rt_scene_occlusion_device's, bit for bit, and the intensity is carried from light to
+ * light (quirk q2).  With light_radius 0 and one sample it is the reference's own loop: `intensity` is what the hosts'
+ * light_intensity_at returns, min(1, diffuse) * albedo[1] the reference's diffuse_intensity.  One fused kernel; no segment exists in
+ * memory.  What it was measured at: docs/EVIDENCE.md, "Sampled lights".
+ *
+ * Receiver i with record H, sample s; every operation in binary64 without FMA contraction, in the order written:
+ *   l = H.inside ? -H.normal : H.normal;  p = H.point;  skip = H.object          (as rt_ambient; no frame is built)
+ *   NOT SCANNED: H.object < 0, or a non-finite word in point or normal
+ *   e = (((uint64)base + (uint64)i) * (uint64)stride + (uint64)s) % (uint64)n_offs     unsigned 64-bit, wrapping at 2^64
+ *   o = offs[e]                                       three doubles, used as given; the SAME entry for every light of the sample
+ *   li = the scene's current light_intensity;  diffuse = 0;  contributed = 0
+ *   for k = 0 .. n_lights - 1, the scene's current lights in blob order:
+ *     pos = light_radius == 0 ? light_k : { light_k[c] + light_radius * o[c] }         (at radius 0 the table is not read)
+ *     sv = pos - p;  mag = (sv0 * sv0 + sv1 * sv1) + sv2 * sv2;  len = sqrt(mag);  if (len != 0) sv = sv * (1 / len)
+ *     sd = (sv0 * l0 + sv1 * l1) + sv2 * l2;  if (sd <= 0) continue                    (a NaN sd goes on, as in the reference)
+ *     the scan of rt_scene_occlusion_device over the segment {p, sv}: length len, starting intensity li, sphere `skip` left out,
+ *       the scene's current spheres in blob order and its epsilon -> li.  A segment with a non-finite word is not scanned: li = NaN.
+ *     if (li == 0) continue
+ *     diffuse = diffuse + (li * sd) / mag;  contributed++
+ * (A light that is blocked leaves li 0 for the lights after it, whose scans still run, as the reference's do: a glass sphere then
+ * divides 0 by its albedo[4], which is -0 for a negative and NaN for a NaN albedo[4], and rt_scene_validate admits both.)
+ * Per receiver, over the samples (the fold of a sampled view: acc = x_0; acc = acc + x_s in order; acc / (double)n_samples):
+ *   diffuse    the fold of the per-sample diffuse, raw: before min(1, .) and albedo[1]
+ *   intensity  the fold of li after the last light
+ *   lit        (double)contributed / (double)(n_samples * n_lights), all samples' count; 0.0 for a scene without lights
+ *   rgba       jsmin(1, diffuse) on three channels through the store rule of main.js:195-198 (a NaN stores 0), alpha 255
+ * A receiver that is not scanned: diffuse and intensity NaN, lit 0.0, rgba 0xff000000.  A scene without lights: diffuse 0.0 and
+ * intensity the scene's light_intensity.
+ * stride == 0 gives every receiver the same n_samples entries (0 .. n_samples - 1); stride >= 1 walks the table.  Consecutive entries
+ * of rt_lighting_sphere_offsets lie on a ring, so a table of whole well-spread sets with stride = n_samples is the way to use it. */
+struct rt_lighting {           /* 32 bytes.  A struct tag only, as struct rt_ambient: rt_lighting() is the host form */
+  uint32_t n_samples;          /* 1..1024 runs of the light loop per receiver */
+  uint32_t n_offs;             /* n_samples..65536 entries of the offset table, 3 doubles each */
+  uint32_t stride;             /* see e above */
+  uint32_t reserved;           /* 0 */
+  uint64_t base;               /* added to the receiver's index: a list processed in pieces passes each piece's first index */
+  double light_radius;         /* finite, >= 0; 0: point lights, the table is not read */
+};
+typedef struct rt_lighting_outputs {  /* one entry per receiver; any may be NULL; all four NULL is RT_ERR_INVALID */
+  double   *diffuse;
+  double   *intensity;
+  double   *lit;
+  uint32_t *rgba;
+} rt_lighting_outputs;
+
+/* Host logic, no GPU, no rt_init.  RT_ERR_INVALID: a NULL pointer; n_samples outside 1..1024; n_offs outside n_samples..65536;
+ * reserved != 0; light_radius negative or not finite; a table entry with a non-finite component (`offs`: HOST memory). */
+int rt_lighting_validate(const struct rt_lighting *a, const double *offs);
+
+/* Host logic: n points (1..65536) on the unit sphere into out_3n, a spiral from pole to pole.  Entry k: z = 1 - (2 k + 1) / n,
+ * r = sqrt(1 - z * z), phi = k * (M_PI * (3.0 - sqrt(5.0))), {r * cos(phi), r * sin(phi), z}, with fdlibm's cosine and sine
+ * (csrc/rt_fdlibm.h): the same bits on every host.  Consecutive entries lie on a ring of nearly one z: give each receiver a whole
+ * set (stride = n_samples over a table of sets), not n_samples neighbours of one long spiral.  RT_ERR_INVALID: n outside 1..65536, NULL. */
+int rt_lighting_sphere_offsets(uint32_t n, double *out_3n);
+
+/* Host logic, the probe: the segment of (`sample`, `light`) of receivers 0 .. n - 1 towards light `light` of lights_xyz (n_lights
+ * positions, three doubles each; hits, offs: HOST memory) - out_rays n records {p[3], sv[3]} as rt_scene_occlusion_device takes
+ * them, out_length len, out_mag mag, out_dot sd, out_skip the sphere left out; any but out_rays may be NULL.  A receiver that is not
+ * scanned gives six NaNs, NaN length, mag and dot, and skip -1.  The restatement the device is held to, bit for bit.
+ * RT_ERR_INVALID: what rt_lighting_validate refuses, n_lights outside 1..16, NULL lights_xyz, n outside 1..2^31 - 1,
+ * sample >= n_samples, light >= n_lights, NULL hits or out_rays. */
+int rt_lighting_segments(const struct rt_lighting *a, const double *offs, uint32_t n_lights, const double *lights_xyz, uint64_t n,
+                         const rt_hit *hits, uint32_t sample, uint32_t light, double *out_rays, double *out_length, double *out_mag,
+                         double *out_dot, int32_t *out_skip);
+
+/* The fused kernel: d_offs, d_hits, d_order and the arrays d_out names are DEVICE memory (d_out itself is a host struct).  d_order,
+ * the stream, stats (pixels = n), pending edits, threads and alignment are rt_scene_ambient_device's.  The lights and light_intensity
+ * are the scene's current ones at the call (rt_scene_set_lights, rt_scene_set_light_intensity before it are seen); it waits by event
+ * for a pending rt_scene_set_objects.  d_offs may be NULL where light_radius is 0.  One work-item per receiver; a lane that does not
+ * face the light or whose scan has met its opaque sphere goes idle, and a wave leaves the scan as soon as none of its 64 is live.
+ * RT_ERR_INVALID, before a device is touched: what rt_lighting_validate refuses of `a`, n outside 1..2^31 - 1, a NULL (light_radius
+ * != 0) or misaligned d_offs, a NULL or misaligned d_hits (8 bytes), a NULL d_out or all of its outputs NULL, a misaligned diffuse,
+ * intensity or lit (8 bytes), rgba or d_order (4 bytes); then RT_ERR_STATE: a NULL scene. */
+int rt_scene_lighting_device(rt_scene_dev *scene, const struct rt_lighting *a, const double *d_offs, uint64_t n, const rt_hit *d_hits,
+                             const uint32_t *d_order, const rt_lighting_outputs *d_out, void *hip_stream, rt_stats *stats);
+
+/* Host form, as rt_ambient: rt_render's resident scene, every array in HOST memory, synchronous, on GPU 0, any n >= 1, in chunks of
+ * 2^18 receivers; chunk c passes base + c * 2^18: the bytes of one launch over the whole list. */
+int rt_lighting(const void *scene_blob, size_t blob_bytes, const struct rt_lighting *a, const double *offs, uint64_t n,
+                const rt_hit *hits, const rt_lighting_outputs *host_out, rt_stats *stats);
+
+/* Host arithmetic: the workspace rt_scene_lighting_view_device prefers for a w x h view, 128 w h bytes (rt_ambient_view_work_bytes). */
+size_t rt_lighting_view_work_bytes(uint32_t w, uint32_t h);
+
+/* Sampled lights on what a view sees: pixel i = y * w + x is receiver i, outputs in frame order.  Bands of whole rows in d_work
+ * (DEVICE, 16-byte aligned, work_bytes >= 128 w): per band the view's rays, their hit records and the fused kernel with
+ * base + y0 * w.  No result depends on the band size.  Everything else as rt_scene_ambient_view_device. */
+int rt_scene_lighting_view_device(rt_scene_dev *scene, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting *a,
+                                  const double *d_offs, const rt_lighting_outputs *d_out, void *d_work, size_t work_bytes,
+                                  void *hip_stream, rt_stats *stats);
+
+/* Host form on rt_render's resident scene, as rt_ambient_view: `offs` and the outputs in HOST memory, chunks of whole rows of at
+ * most 2^18 pixels.  The table goes up once (24 n_offs bytes), 8 to 28 bytes per pixel come back. */
+int rt_lighting_view(const void *scene_blob, size_t blob_bytes, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting *a,
+                     const double *offs, const rt_lighting_outputs *host_out, rt_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
