@@ -8,11 +8,12 @@
 //   rt_launch.hip  the launches: colour (the launch record, then the strict launch or the product launch and rt_retrace), supersampling,
 //                  compact bands, adaptive supersampling (rt_adaptive.hip), primary hits and picking, ray lists, occlusion queries
 //   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick, and the host lists that go
-//                  through device buffers in chunks (rt_trace_rays, rt_occlusion and their binned forms, rt_shade_rays), rt_trace_rays_wavefront
+//                  through device buffers in chunks (rt_trace_rays, rt_occlusion and their binned forms, rt_shade_rays, rt_relight_rays), rt_trace_rays_wavefront / rt_trace_rays_soft
 //   rt_nodes_api.hip  the wavefront form's device entry points: one level of nodes, the next level's ray list, the fold (rt_nodes.hip)
 //   rt_views_api.hip  views: validation, the panorama's tables, the host probe, the generator's launch (rt_views.hip), the traces of a whole view
 //   rt_ambient_api.hip  ambient occlusion: validation, the cosine table, the host probe, the launches of rt_ambient.hip, the host forms
 //   rt_lighting_api.hip  sampled lights: validation, the offset table, the host probe, the launch of rt_lighting.hip, the host forms
+//   rt_relight_api.hip  relit nodes: the argument check, the launch of rt_relight.hip and its device entry point (the host forms are rt_frame.hip's)
 // Which kernel a launch runs is one value (rt_device.h: rt_trace_variant), worked out once per launch; the two builds of rt_kernel.hip map
 // it to a kernel (rt_kernel_trace_fast / rt_kernel_trace_strict), and the declarations below are all the host sees of them.
 #ifndef RT_API_INTERNAL_H
@@ -331,6 +332,16 @@ int shade_launch(rt_scene_dev *s, uint32_t n, uint32_t base, const double *d_ray
 int spawn_launch(uint32_t n, uint32_t base, const rt_node *d_nodes, const uint32_t *d_pix, const uint32_t *d_path, double *d_child_rays, uint32_t *d_child_pix,
                  uint32_t *d_child_path, int32_t *d_links, uint32_t *d_count, void *d_work, hipStream_t stream);
 int fold_launch(uint32_t n, const rt_node *d_nodes, const int32_t *d_links, const double *d_child_rgb, double *d_rgb, uint8_t *d_rgba, hipStream_t stream);
+
+// rt_lighting_api.hip: the checks of a lighting description whose table is DEVICE memory (NULL only at light_radius 0), and the table of a
+// host form going up (nothing is allocated at light_radius 0)
+int lighting_device_check(const struct rt_lighting *a, const double *d_offs, const char *what);
+int lighting_upload_offs(const struct rt_lighting &a, const double *offs, device_mem *d_offs, hipStream_t stream);
+// rt_relight_api.hip: the relight of a level's nodes (device pointers; a.base as given): argument check and launch
+int relight_check(const struct rt_lighting *a, const double *d_offs, uint64_t n, const double *rays, const uint32_t *order, const uint32_t *pix,
+                  const rt_node *nodes, const char *what);
+int relight_launch(rt_scene_dev *s, const struct rt_lighting &a, const double *d_offs, uint32_t n, const double *d_rays, const uint32_t *d_order,
+                   const uint32_t *d_pix, rt_node *d_nodes, hipStream_t stream, rt_stats *stats);
 
 // rt_frame.hip: what scene_for does with a blob that differs from the resident one: per texture whose texels differ the smallest row
 // range that covers the differences, in texture order.  -1: the blobs differ in something no edit of a resident scene reaches (anything

@@ -1,5 +1,6 @@
 // rt_frame.hip — rt_render(width, height, scene) and its kin (rt_render_progressive, rt_render_hits, rt_pick; rt_trace_rays, rt_occlusion
-// and their binned forms and rt_shade_rays, which share one chunked list call; rt_trace_rays_wavefront): the resident scene
+// and their binned forms, rt_shade_rays and rt_relight_rays, which share one chunked list call; rt_trace_rays_wavefront and
+// rt_trace_rays_soft, which share one level loop): the resident scene
 // per device (scene_for), the one-GPU plans (banded copy-out, stores straight into a pinned frame) and the single-process multi-GPU
 // frame (interleaved row tiles stored straight into GPU 0's frame over xGMI; fallback: RGB24 bands + one RCCL gather + de-interleave).
 
@@ -461,6 +462,36 @@ extern "C" int rt_shade_rays(const void *blob, size_t bytes, uint64_t n, const d
                            });
 }
 
+// rt_shade_rays followed by the relight of each chunk (rt_relight.hip): the table goes up with the first chunk, and a chunk's base is
+// added to the description's where no pix travels, so a list gives the bytes of one launch however it is cut
+extern "C" int rt_relight_rays(const void *blob, size_t bytes, const struct rt_lighting *a, const double *offs, uint64_t n, const double *rays,
+                               const uint32_t *pix, const uint32_t *path, int binned, rt_node *nodes, rt_stats *stats) {
+  const char *what = "rt_relight_rays";
+  int rc = rt_scene_validate(blob, bytes);
+  if (rc) return rc;
+  if ((rc = rt_lighting_validate(a, offs))) return rc;
+  if ((rc = shade_check(n, rays, nullptr, pix, path, nodes, what))) return rc;
+  const list_row rows[4] = {{rays, 6u * sizeof(double), false}, {pix, sizeof(uint32_t), false}, {path, sizeof(uint32_t), false}, {nodes, sizeof(rt_node), true}};
+  device_mem d_offs;                                     // (released behind the call, whose every chunk has been waited for)
+  bool table_up = false;
+  return chunked_list_call(blob, bytes, n, rows, 4, binned != 0, stats,
+                           [&](rt_scene_dev *s, uint32_t m, uint32_t base, void *const *d, const uint32_t *d_order, hipStream_t stream, rt_stats *st) {
+                             if (!table_up) {
+                               if (int e = lighting_upload_offs(*a, offs, &d_offs, stream)) return e;
+                               table_up = true;
+                             }
+                             const uint32_t *d_pix = (const uint32_t *)d[1];
+                             if (int e = shade_launch(s, m, base, (const double *)d[0], d_order, d_pix, (const uint32_t *)d[2], (rt_node *)d[3], stream, st)) return e;
+                             struct rt_lighting ac = *a;
+                             if (!d_pix) ac.base = a->base + base;         // node i of this chunk is node base + i of the list
+                             rt_stats relit;
+                             if (int e = relight_launch(s, ac, (const double *)d_offs.h, m, (const double *)d[0], d_order, d_pix, (rt_node *)d[3], stream, st ? &relit : nullptr))
+                               return e;
+                             if (st) st->kernel_ms += relit.kernel_ms;
+                             return (int)RT_OK;
+                           });
+}
+
 // rt_trace_rays through the wavefront form (include/rt_hip.h: rt_trace_rays_wavefront): per chunk of the list, level after level is
 // shaded (rt_nodes.hip) and its children spawned - a level's buffers are sized from the count read back after the spawn that made it -
 // down to the call's depth or an empty level, then the levels are folded back up and level 1's colours copied out.  A chunk keeps the
@@ -484,10 +515,13 @@ struct device_pool {
   }
 };
 struct wave_level { rt_node *nodes; int32_t *links; uint32_t count; };
+// rt_trace_rays_soft's step behind the shade of every level below `levels` (rt_relight.hip); d_offs: the table, in device memory
+struct relight_step { const struct rt_lighting *a; const double *d_offs; uint32_t levels; };
 
-// rays [base, base + m) of the list.  *overflow: the chunk's trees hold more than RT_WAVEFRONT_NODES nodes (and m > 1): nothing was written
+// rays [base, base + m) of the list.  *overflow: the chunk's trees hold more than RT_WAVEFRONT_NODES nodes (and m > 1): nothing was written.
+// relight: NULL, or the step that follows a level's shade; without it the launches are rt_trace_rays_wavefront's, one for one
 int wavefront_chunk(rt_scene_dev *s, hipStream_t stream, const double *rays, uint64_t base, uint32_t m, uint32_t segs, bool order_levels,
-                    const rt_ray_outputs *ho, bool timed, double *kernel_ms, uint64_t *level_counts, bool *overflow) {
+                    const relight_step *relight, const rt_ray_outputs *ho, bool timed, double *kernel_ms, uint64_t *level_counts, bool *overflow) {
   device_pool mem;
   std::vector<wave_level> levels;
   int rc;
@@ -526,6 +560,13 @@ int wavefront_chunk(rt_scene_dev *s, hipStream_t stream, const double *rays, uin
     if ((rc = shade_launch(s, c, pix_base, (const double *)d_rays, (const uint32_t *)d_order, (const uint32_t *)d_pix, (const uint32_t *)d_path, L.nodes, stream,
                            nullptr)))
       return rc;
+    if (relight && lv < relight->levels) {
+      // pix is the root ray's index at every level: it travels in d_pix below the first, where the chunk's base stands in for it
+      struct rt_lighting ac = *relight->a;
+      if (lv == 0u) ac.base = relight->a->base + base;
+      if ((rc = relight_launch(s, ac, relight->d_offs, c, (const double *)d_rays, (const uint32_t *)d_order, (const uint32_t *)d_pix, L.nodes, stream, nullptr)))
+        return rc;
+    }
     uint32_t next = 0u;
     if (lv + 1u < segs) {
       HIP_TRY(mem.get((void **)&levels.back().links, (size_t)c * 2u * sizeof(int32_t)));
@@ -569,11 +610,13 @@ int wavefront_chunk(rt_scene_dev *s, hipStream_t stream, const double *rays, uin
 }
 }  // namespace
 
-extern "C" int rt_trace_rays_wavefront(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, int order_levels,
-                                       const rt_ray_outputs *ho, rt_stats *stats, uint64_t *level_counts) {
-  const char *what = "rt_trace_rays_wavefront";
+namespace {
+// the wavefront loop over a list in host memory; a: NULL, or the lights of rt_trace_rays_soft for the first `levels` levels
+int wavefront_to_host(const void *blob, size_t bytes, const struct rt_lighting *a, const double *offs, uint32_t levels, uint64_t n, const double *rays,
+                      uint32_t segs, int order_levels, const rt_ray_outputs *ho, rt_stats *stats, uint64_t *level_counts, const char *what) {
   int rc = rt_scene_validate(blob, bytes);
   if (rc) return rc;
+  if (a && (rc = rt_lighting_validate(a, offs))) return rc;
   if ((rc = rays_check(n, rays, segs, ho, what))) return rc;
   if (ho->hits) return fail(RT_ERR_INVALID, "%s: no hit records (level 1 of rt_scene_shade_rays_device holds them)", what);
   if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
@@ -584,6 +627,13 @@ extern "C" int rt_trace_rays_wavefront(const void *blob, size_t bytes, uint64_t 
   if ((rc = ensure_device(0))) return rc;
   device_state &D = G.dev[0];
   const uint32_t depth = segs ? segs : s->hd.segs;
+  device_mem d_offs;                                     // the table goes up once per call
+  relight_step step = {a, nullptr, levels};
+  const bool relit = a && levels != 0u && depth != 0u;
+  if (relit) {
+    if ((rc = lighting_upload_offs(*a, offs, &d_offs, D.stream))) return rc;
+    step.d_offs = (const double *)d_offs.h;
+  }
   if (level_counts) memset(level_counts, 0, RT_MAX_SEGS * sizeof(uint64_t));
   double kernel_ms = 0.0;
   uint32_t chunk = n < RT_RAY_CHUNK ? (uint32_t)n : RT_RAY_CHUNK;
@@ -600,7 +650,7 @@ extern "C" int rt_trace_rays_wavefront(const void *blob, size_t bytes, uint64_t 
   for (uint64_t base = 0; depth != 0u && base < n;) {
     const uint32_t m = n - base < chunk ? (uint32_t)(n - base) : chunk;
     bool overflow = false;
-    if ((rc = wavefront_chunk(s, D.stream, rays, base, m, depth, order_levels != 0, ho, stats != nullptr, &kernel_ms, level_counts, &overflow))) return rc;
+    if ((rc = wavefront_chunk(s, D.stream, rays, base, m, depth, order_levels != 0, relit ? &step : nullptr, ho, stats != nullptr, &kernel_ms, level_counts, &overflow))) return rc;
     if (overflow) { chunk = m / 2u; continue; }            // (m > 1; a chunk of one ray always fits)
     base += m;
   }
@@ -611,6 +661,19 @@ extern "C" int rt_trace_rays_wavefront(const void *blob, size_t bytes, uint64_t 
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
   return RT_OK;
+}
+}  // namespace
+
+extern "C" int rt_trace_rays_wavefront(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, int order_levels,
+                                       const rt_ray_outputs *ho, rt_stats *stats, uint64_t *level_counts) {
+  return wavefront_to_host(blob, bytes, nullptr, nullptr, 0u, n, rays, segs, order_levels, ho, stats, level_counts, "rt_trace_rays_wavefront");
+}
+
+// rt_trace_rays_wavefront with the nodes of the first `levels` levels relit (rt_relight.hip) between their shade and their spawn
+extern "C" int rt_trace_rays_soft(const void *blob, size_t bytes, const struct rt_lighting *a, const double *offs, uint32_t levels, uint64_t n,
+                                  const double *rays, uint32_t segs, int order_levels, const rt_ray_outputs *ho, rt_stats *stats, uint64_t *level_counts) {
+  if (!a) return fail(RT_ERR_INVALID, "rt_trace_rays_soft: NULL lighting description");
+  return wavefront_to_host(blob, bytes, a, offs, levels, n, rays, segs, order_levels, ho, stats, level_counts, "rt_trace_rays_soft");
 }
 
 // The shadow scan for a list of segments in host memory (`binned`: rt_occlusion_binned)

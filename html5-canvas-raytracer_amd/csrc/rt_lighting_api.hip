@@ -135,6 +135,15 @@ int upload_offs(const struct rt_lighting &a, const double *offs, device_mem *d_o
 }
 }  // namespace
 
+// what the relit nodes (rt_relight_api.hip, rt_frame.hip) share with this unit: the checks of a description with a device table, and the upload
+namespace rt_api {
+int lighting_device_check(const struct rt_lighting *a, const double *d_offs, const char *what) {
+  if (int rc = lighting_check(a, what)) return rc;
+  return lighting_offs_check(*a, d_offs, what);
+}
+int lighting_upload_offs(const struct rt_lighting &a, const double *offs, device_mem *d_offs, hipStream_t stream) { return upload_offs(a, offs, d_offs, stream); }
+}  // namespace rt_api
+
 extern "C" int rt_lighting_validate(const struct rt_lighting *a, const double *offs) { return lighting_table_check(a, offs, "rt_lighting_validate"); }
 
 extern "C" int rt_lighting_sphere_offsets(uint32_t n, double *out_3n) {

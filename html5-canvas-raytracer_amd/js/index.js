@@ -141,6 +141,22 @@ function tanHalf(projA) { return Math.tan(projA / 2); }
 // them (rt_trace_rays_binned) - the same results, sooner for a list that is not coherent (scattered probes, collected secondary rays).
 // opts.wavefront: level by level through shade, spawn and fold (rt_trace_rays_wavefront) instead of the one recursive kernel - the same
 // bytes in rgb and rgba, no hits, plus levelCounts (the rays shaded per level); opts.orderLevels bins every level after the first.
+// opts.soft: {samples, lightRadius, offsets, stride, levels, base} - the wavefront form with lights that have a size (rt_trace_rays_soft):
+// the diffuse and specular terms of the nodes of the first `levels` levels (default 1: what the rays hit; the scene's depth: every
+// bounce) are means over `samples` runs of the light loop, every light displaced by lightRadius times an entry of offsets (default
+// lightingOffsets(samples) with stride 0: every ray the same entries; with offsets, stride defaults to 1 and ray i walks the table from
+// (base + i) * stride; relightRays' stride defaults to 1 either way).  No hits, no bin.
+function softOf(o, who, walks) {
+  const s = o.soft;
+  if (s === null || typeof s !== 'object' || !Number.isInteger(s.samples) || s.samples < 1 || typeof s.lightRadius !== 'number' ||
+      (s.offsets != null && !(s.offsets instanceof Float64Array && s.offsets.length > 0 && s.offsets.length % 3 === 0)) ||
+      (s.stride != null && !(Number.isInteger(s.stride) && s.stride >= 0)) || (s.levels != null && !(Number.isInteger(s.levels) && s.levels >= 0)) ||
+      (s.base != null && !(Number.isInteger(s.base) && s.base >= 0))) {
+    throw new TypeError(who + ': soft is {samples: integer >= 1, lightRadius: number[, offsets: Float64Array of 3 numbers per entry, stride, levels, base]}');
+  }
+  const offs = s.offsets || native().lightingOffsets(s.samples);
+  return {levels: s.levels == null ? 1 : s.levels, tail: [offs, s.samples, s.stride != null ? s.stride : (s.offsets || walks ? 1 : 0), s.base || 0, s.lightRadius]};
+}
 function traceRays(sceneObj, rays, opts) {
   if (!(rays instanceof Float64Array) || rays.length === 0 || rays.length % 6 !== 0) {
     throw new TypeError('traceRays: rays must be a non-empty Float64Array of 6 numbers per ray');
@@ -148,7 +164,10 @@ function traceRays(sceneObj, rays, opts) {
   if (!inited) init(opts && opts.maxDevices);
   const o = opts || {};
   if (o.wavefront && (o.hits || o.bin)) throw new TypeError('traceRays: {wavefront: true} returns no hits and takes no {bin: true} (orderLevels bins the later levels)');
-  const r = native().traceRays(new Uint8Array(flattenScene(sceneObj)), rays, o.segs || 0, o.rgb !== false, !!o.rgba, !!o.hits, !!o.bin, !!o.wavefront, !!o.orderLevels);
+  if (o.soft !== undefined && (o.hits || o.bin)) throw new TypeError('traceRays: {soft} returns no hits and takes no {bin: true}');
+  const soft = o.soft !== undefined ? softOf(o, 'traceRays') : null;
+  const args = [new Uint8Array(flattenScene(sceneObj)), rays, o.segs || 0, o.rgb !== false, !!o.rgba, !!o.hits, !!o.bin, !!o.wavefront, !!o.orderLevels];
+  const r = soft ? native().traceRays(...args, soft.levels, ...soft.tail) : native().traceRays(...args);
   if (r.hits) for (const h of r.hits) if (h) h.object = sceneObj.objects[h.index];
   return r;
 }
@@ -250,16 +269,21 @@ function nodeAt(buf, i, sceneObj) {
   return {hit, sample: v3(80), diffuse: f(104), specular: f(112), ambient: f(120), reflectWeight: f(128), refractWeight: f(136),
     reflectDir: v3(144), refractDir: v3(168), children: d.getUint32(192, true)};
 }
-function shadeRays(sceneObj, rays, opts) {
+// relightRays(scene, rays, opts): shadeRays' result with soft lights (rt_relight_rays) - opts as shadeRays takes them, and samples,
+// lightRadius, offsets, stride, base as traceRays' opts.soft names them; sample s of ray i uses entry ((base + pix_i) stride + s) % n_offs.
+function shadeRays(sceneObj, rays, opts) { return shadeOrRelight('shadeRays', sceneObj, rays, opts, false); }
+function relightRays(sceneObj, rays, opts) { return shadeOrRelight('relightRays', sceneObj, rays, opts, true); }
+function shadeOrRelight(who, sceneObj, rays, opts, relight) {
   if (!(rays instanceof Float64Array) || rays.length === 0 || rays.length % 6 !== 0) {
-    throw new TypeError('shadeRays: rays must be a non-empty Float64Array of 6 numbers per ray');
+    throw new TypeError(who + ': rays must be a non-empty Float64Array of 6 numbers per ray');
   }
   const o = opts || {}, n = rays.length / 6;
   for (const name of ['pix', 'path']) {
-    if (o[name] != null && !(o[name] instanceof Uint32Array && o[name].length === n)) throw new TypeError('shadeRays: ' + name + ' must be a Uint32Array of one element per ray');
+    if (o[name] != null && !(o[name] instanceof Uint32Array && o[name].length === n)) throw new TypeError(who + ': ' + name + ' must be a Uint32Array of one element per ray');
   }
+  const tail = relight ? softOf({soft: {samples: o.samples, lightRadius: o.lightRadius, offsets: o.offsets, stride: o.stride, base: o.base}}, who, true).tail : [];
   if (!inited) init(o.maxDevices);
-  const r = native().shadeRays(new Uint8Array(flattenScene(sceneObj)), rays, o.pix || null, o.path || null, !!o.bin);
+  const r = (relight ? native().relightRays : native().shadeRays)(new Uint8Array(flattenScene(sceneObj)), rays, o.pix || null, o.path || null, !!o.bin, ...tail);
   r.node = (i) => {
     if (!Number.isInteger(i) || i < 0 || i >= r.count) throw new RangeError('node index out of range');
     return nodeAt(r.nodes, i, sceneObj);
@@ -407,4 +431,4 @@ function buildId() { return native().buildId(); }
 
 function shutdown() { if (addon) addon.shutdown(); inited = false; }
 
-module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, traceView, views, shadeRays, primaryRays, normal3D, occlusion, lightSegments, ambient, ambientView, ambientDirs, lighting, lightingView, lightingOffsets, init, shutdown, buildId, flattenScene, scenes, native}, scene);
+module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, traceView, views, shadeRays, relightRays, primaryRays, normal3D, occlusion, lightSegments, ambient, ambientView, ambientDirs, lighting, lightingView, lightingOffsets, init, shutdown, buildId, flattenScene, scenes, native}, scene);

@@ -15,8 +15,10 @@
 //           traceRays(blob, rays: Float64Array (6 per ray), segs, wantRgb, wantRgba, wantHits, bin) -> {rgb: Float64Array | null,
 //           rgba: Uint8ClampedArray | null, hits: Array of pick's records (null = a miss) | null}: intersectWorld per ray (rt_trace_rays;
 //           bin: rt_trace_rays_binned, the list ordered on the GPU first - the same results; two more booleans, wavefront and
-//           orderLevels: rt_trace_rays_wavefront, the same rgb and rgba level by level, plus levelCounts)
+//           orderLevels: rt_trace_rays_wavefront, the same rgb and rgba level by level, plus levelCounts; six more, levels and lighting's tail
+//           offs, nSamples, stride, base, lightRadius: rt_trace_rays_soft, the wavefront form with the first `levels` levels' nodes relit)
 //           shadeRays(blob, rays, pix: Uint32Array | null, path: Uint32Array | null, bin) -> {nodes: ArrayBuffer of rt_node records, count}
+//           relightRays(blob, rays, pix, path, bin, offs, nSamples, stride, base, lightRadius) -> the same, with soft lights (rt_relight_rays)
 //           traceView(blob, view: Uint8Array (the 136 bytes of rt_view, table pointers ignored), lon: Float64Array | null, lat: Float64Array | null,
 //           w, h, segs, wantRgb, wantRgba, wantHits) -> traceRays' result for the view's w x h rays, generated on the GPU (rt_trace_view)
 //           equirectTables(w, h) -> {lon: Float64Array (2 w), lat: Float64Array (2 h)} (rt_view_equirect_tables)
@@ -485,13 +487,16 @@ napi_value Pick(napi_env env, napi_callback_info info) {
   return hit_object(env, r);
 }
 
+// (defined with the sampled lights below; traceRays' soft tail and relightRays take the same five arguments)
+bool lighting_args(napi_env env, size_t argc, napi_value *argv, size_t at, const char *who, struct rt_lighting *a, const double **offs, bool want[4]);
+
 napi_value TraceRays(napi_env env, napi_callback_info info) {
-  size_t argc = 9;
-  napi_value argv[9];
+  size_t argc = 15;
+  napi_value argv[15];
   bool is_ta = false, is_rays = false;
   if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
       napi_is_typedarray(env, argv[1], &is_rays) != napi_ok || !is_rays) {
-    napi_throw_type_error(env, nullptr, "traceRays(blob: Uint8Array, rays: Float64Array[, segs, wantRgb, wantRgba, wantHits, bin])");
+    napi_throw_type_error(env, nullptr, "traceRays(blob: Uint8Array, rays: Float64Array[, segs, wantRgb, wantRgba, wantHits, bin, wavefront, orderLevels, levels, offs, nSamples, stride, base, lightRadius])");
     return nullptr;
   }
   napi_typedarray_type bt, rt; napi_value ab; size_t off, blob_len = 0, ray_len = 0;
@@ -511,6 +516,26 @@ napi_value TraceRays(napi_env env, napi_callback_info info) {
   bool wavefront = false, order_levels = false;         // rt_trace_rays_wavefront: level by level through shade, spawn and fold - the same bytes
   if (argc >= 8) napi_get_value_bool(env, argv[7], &wavefront);
   if (argc >= 9) napi_get_value_bool(env, argv[8], &order_levels);
+  // soft lights (rt_trace_rays_soft): levels, then the tail lighting takes - offs: Float64Array (3 per entry), nSamples, stride, base, lightRadius
+  bool soft = false;
+  uint32_t levels = 0;
+  struct rt_lighting la;
+  const double *offs = nullptr;
+  if (argc > 9) {
+    napi_valuetype vt;
+    napi_typeof(env, argv[9], &vt);
+    soft = vt != napi_undefined && vt != napi_null;
+  }
+  if (soft) {
+    const char *who = "traceRays: soft lights are levels, offs: Float64Array (3 per entry), nSamples, stride, base, lightRadius";
+    bool unused[4];
+    if (napi_get_value_uint32(env, argv[9], &levels) != napi_ok) {
+      napi_throw_type_error(env, nullptr, who);
+      return nullptr;
+    }
+    if (!lighting_args(env, argc, argv, 10, who, &la, &offs, unused)) return nullptr;
+    wavefront = true;                                   // (the wavefront loop with a relight behind the shade of the first `levels` levels)
+  }
   if (wavefront && (want[2] || bin)) {
     napi_throw_type_error(env, nullptr, "traceRays: the wavefront form returns no hit records and takes the first level in the list's order");
     return nullptr;
@@ -533,10 +558,11 @@ napi_value TraceRays(napi_env env, napi_callback_info info) {
   const rt_ray_outputs out = {(double *)p_rgb, (uint8_t *)p_rgba, hits};
   rt_stats st;
   uint64_t level_counts[RT_MAX_SEGS] = {0};
-  const int rc = wavefront ? rt_trace_rays_wavefront(mem, blob_len, n, (const double *)(mem + blob_room), segs, order_levels ? 1 : 0, &out, &st, level_counts)
-                           : (bin ? rt_trace_rays_binned : rt_trace_rays)(mem, blob_len, n, (const double *)(mem + blob_room), segs, &out, &st);
+  const int rc = soft ? rt_trace_rays_soft(mem, blob_len, &la, offs, levels, n, (const double *)(mem + blob_room), segs, order_levels ? 1 : 0, &out, &st, level_counts)
+                 : wavefront ? rt_trace_rays_wavefront(mem, blob_len, n, (const double *)(mem + blob_room), segs, order_levels ? 1 : 0, &out, &st, level_counts)
+                             : (bin ? rt_trace_rays_binned : rt_trace_rays)(mem, blob_len, n, (const double *)(mem + blob_room), segs, &out, &st);
   free(mem);
-  if (rc != RT_OK) { free(hits); return throw_rt(env, wavefront ? "rt_trace_rays_wavefront" : bin ? "rt_trace_rays_binned" : "rt_trace_rays", rc); }
+  if (rc != RT_OK) { free(hits); return throw_rt(env, soft ? "rt_trace_rays_soft" : wavefront ? "rt_trace_rays_wavefront" : bin ? "rt_trace_rays_binned" : "rt_trace_rays", rc); }
   napi_create_object(env, &res);
   if (wavefront) {                                      // the rays shaded per level
     napi_value lc, c;
@@ -864,9 +890,11 @@ napi_value Occlusion(napi_env env, napi_callback_info info) {
 
 // shadeRays(blob, rays: Float64Array (6 per ray), pix: Uint32Array | null, path: Uint32Array | null, bin) -> {nodes: ArrayBuffer (200 bytes
 //           per ray: rt_node), count, kernel_ms}  (rt_shade_rays: one level of intersectWorld)
-napi_value ShadeRays(napi_env env, napi_callback_info info) {
-  size_t argc = 5;
-  napi_value argv[5];
+// relightRays(blob, rays, pix, path, bin, offs: Float64Array (3 per entry), nSamples, stride, base, lightRadius) -> the same, the nodes' diffuse
+//           and specular terms averaged over nSamples displaced copies of the lights (rt_relight_rays)
+napi_value shade_or_relight(napi_env env, napi_callback_info info, bool relight) {
+  size_t argc = 10;
+  napi_value argv[10];
   bool is_ta = false, is_rays = false;
   if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
       napi_is_typedarray(env, argv[1], &is_rays) != napi_ok || !is_rays) {
@@ -896,6 +924,12 @@ napi_value ShadeRays(napi_env env, napi_callback_info info) {
   }
   bool bin = false;
   if (argc >= 5) napi_get_value_bool(env, argv[4], &bin);
+  struct rt_lighting la;
+  const double *offs = nullptr;
+  bool unused[4];
+  if (relight && !lighting_args(env, argc, argv, 5, "relightRays(blob: Uint8Array, rays: Float64Array, pix, path, bin, offs: Float64Array (3 per entry), nSamples, stride, base, lightRadius)",
+                                &la, &offs, unused))
+    return nullptr;
   const size_t blob_room = (blob_len + 15) & ~(size_t)15;
   uint8_t *mem = (uint8_t *)aligned_alloc(16, blob_room + ((n * 48u + 15) & ~(size_t)15));
   napi_value ab_nodes = nullptr, res, v;
@@ -908,16 +942,21 @@ napi_value ShadeRays(napi_env env, napi_callback_info info) {
   memcpy(mem, blob_data, blob_len);
   memcpy(mem + blob_room, ray_data, n * 48u);
   rt_stats st;
-  const int rc = rt_shade_rays(mem, blob_len, n, (const double *)(mem + blob_room), (const uint32_t *)in_data[0], (const uint32_t *)in_data[1], bin ? 1 : 0,
-                               (rt_node *)p_nodes, &st);
+  const int rc = relight ? rt_relight_rays(mem, blob_len, &la, offs, n, (const double *)(mem + blob_room), (const uint32_t *)in_data[0], (const uint32_t *)in_data[1],
+                                           bin ? 1 : 0, (rt_node *)p_nodes, &st)
+                         : rt_shade_rays(mem, blob_len, n, (const double *)(mem + blob_room), (const uint32_t *)in_data[0], (const uint32_t *)in_data[1], bin ? 1 : 0,
+                                         (rt_node *)p_nodes, &st);
   free(mem);
-  if (rc != RT_OK) return throw_rt(env, "rt_shade_rays", rc);
+  if (rc != RT_OK) return throw_rt(env, relight ? "rt_relight_rays" : "rt_shade_rays", rc);
   napi_create_object(env, &res);
   napi_set_named_property(env, res, "nodes", ab_nodes);
   napi_create_double(env, (double)n, &v); napi_set_named_property(env, res, "count", v);
   napi_create_double(env, st.kernel_ms, &v); napi_set_named_property(env, res, "kernel_ms", v);
   return res;
 }
+
+napi_value ShadeRays(napi_env env, napi_callback_info info) { return shade_or_relight(env, info, false); }
+napi_value RelightRays(napi_env env, napi_callback_info info) { return shade_or_relight(env, info, true); }
 
 // ---- ambient occlusion (include/rt_hip.h: struct rt_ambient)
 // ambientDirs(n): the cosine-weighted spiral (rt_ambient_cosine_dirs) as a Float64Array of 3 n numbers
@@ -1266,6 +1305,7 @@ napi_value Module(napi_env env, napi_value exports) {
       {"traceRays", nullptr, TraceRays, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"occlusion", nullptr, Occlusion, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"shadeRays", nullptr, ShadeRays, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"relightRays", nullptr, RelightRays, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"traceView", nullptr, TraceView, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"equirectTables", nullptr, EquirectTables, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"viewSamplesGrid", nullptr, ViewSamplesGrid, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -373,6 +373,12 @@ ABI = {
                                                 C.POINTER(RtLightingOutputs), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RtStats)]),
     "rt_lighting_view": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtLighting), C.c_void_p,
                                    C.POINTER(RtLightingOutputs), C.POINTER(RtStats)]),
+    "rt_scene_relight_nodes_device": (C.c_int, [C.c_void_p, C.POINTER(RtLighting), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.POINTER(RtStats)]),
+    "rt_relight_rays": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtLighting), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                  C.c_void_p, C.POINTER(RtStats)]),
+    "rt_trace_rays_soft": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtLighting), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int,
+                                     C.POINTER(RtRayOutputs), C.POINTER(RtStats), C.POINTER(C.c_uint64)]),
 }
 
 RT_MAX_SEGS = 16
@@ -753,6 +759,21 @@ class Renderer:
                                                  C.c_void_p(path_ptr or 0), C.c_void_p(nodes_ptr or 0), C.c_void_p(stream or 0),
                                                  C.byref(st) if st is not None else None)
         _check(self.lib, rc, "rt_scene_shade_rays_device")
+        return st
+
+    def relight_nodes(self, n, rays_ptr, nodes_ptr, offs_ptr, n_offs, n_samples, light_radius, stride=1, base=0, order_ptr=0, pix_ptr=0, stream=None,
+                      want_stats=False):
+        """Soft lights for n shaded nodes (DEVICE, what shade_rays wrote for the n rays at rays_ptr): the node's diffuse and specular terms
+        computed again n_samples times with every light displaced by light_radius times an entry of the table offs_ptr (DEVICE, n_offs
+        entries of 3 float64; 0 where light_radius is 0), clamped and weighted per sample, and their means written back into the node
+        (bytes 104..119; nothing else).  Sample s of node i uses entry ((base + pix_i) stride + s) % n_offs, pix_i = pix_ptr[i] (n uint32,
+        DEVICE) or i.  order_ptr as shade_rays takes it.  With the scene's CURRENT lights, light intensity and spheres."""
+        a = RtLighting(n_samples, n_offs, stride, 0, base, float(light_radius))
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_relight_nodes_device(self.handle, C.byref(a), C.c_void_p(offs_ptr or 0), n, C.c_void_p(rays_ptr or 0), C.c_void_p(order_ptr or 0),
+                                                    C.c_void_p(pix_ptr or 0), C.c_void_p(nodes_ptr or 0), C.c_void_p(stream or 0),
+                                                    C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_relight_nodes_device")
         return st
 
     def spawn_rays(self, n, nodes_ptr, child_rays_ptr, links_ptr, count_ptr, work_ptr, work_bytes, pix_ptr=0, path_ptr=0, child_pix_ptr=0,
@@ -1641,6 +1662,91 @@ def shade_rays(scene, rays, pix=None, path=None, order="list", lib=None):
                            C.c_void_p(extra["path"].ctypes.data if "path" in extra else 0), 1 if order == "binned" else 0, C.c_void_p(nodes.ctypes.data), None)
     _check(lib, rc, "rt_shade_rays")
     return nodes
+
+
+def _ray_list(rays):
+    """-> (n, the rays as n * 6 contiguous float64 on a 16-byte boundary)"""
+    import numpy as np
+    rays = np.asarray(rays)
+    if rays.dtype.kind not in "fiu" or rays.ndim != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
+        raise ValueError("rays must be a non-empty (n, 6) array: org[3], dir[3] per row")
+    aligned = _aligned_f64(rays.shape[0] * 6)
+    aligned[:] = rays.reshape(-1)
+    return rays.shape[0], aligned
+
+
+def relight_rays(scene, rays, n_samples, light_radius, offs=None, stride=1, pix=None, path=None, order="list", base=0, lib=None):
+    """relight_rays(scene, rays, n_samples, light_radius) -> structured array (NODE_DTYPE): shade_rays' nodes with soft lights - diffuse
+    and specular are the means over n_samples runs of the light loop, every light displaced by light_radius times an entry of `offs`
+    ((n_offs, 3); None = lighting_offsets(n_samples)) and each run's terms clamped and weighted as the reference does (main.js:316-317);
+    every other byte of a node is shade_rays'.  Sample s of ray i uses entry ((base + pix_i) stride + s) % n_offs for every light, pix_i =
+    pix[i], or i: a list cut in pieces gives the whole list's nodes when each piece passes its rays' indices as pix (they are the stars
+    sampler's pix too).  path and order as shade_rays takes them."""
+    import numpy as np
+    if order not in ("list", "binned"):
+        raise ValueError("order is 'list' or 'binned'")
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    n, aligned = _ray_list(rays)
+    a, offs = _lighting_args(n_samples, light_radius, offs, stride, base, lib)
+    extra = {}
+    for name, v in (("pix", pix), ("path", path)):
+        if v is not None:
+            v = np.asarray(v)
+            if v.dtype.kind not in "iu" or v.shape != (n,) or (v.size and (int(v.min()) < 0 or int(v.max()) >= 2 ** 32)):
+                raise ValueError("%s must be n integers in [0, 2^32)" % name)
+            extra[name] = np.ascontiguousarray(v.astype(np.uint32))
+    nodes = np.zeros(n, _node_dtype())
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    rc = lib.rt_relight_rays(buf, len(blob), C.byref(a), C.c_void_p(offs.ctypes.data), n, C.c_void_p(aligned.ctypes.data),
+                             C.c_void_p(extra["pix"].ctypes.data if "pix" in extra else 0), C.c_void_p(extra["path"].ctypes.data if "path" in extra else 0),
+                             1 if order == "binned" else 0, C.c_void_p(nodes.ctypes.data), None)
+    _check(lib, rc, "rt_relight_rays")
+    return nodes
+
+
+def trace_rays_soft(scene, rays, n_samples, light_radius, offs=None, stride=1, levels=1, segs=0, order_levels=False, want=("rgba",), base=0, lib=None):
+    """trace_rays_soft(scene, rays, n_samples, light_radius) -> {"rgb": (n, 3) float64, "rgba": (n, 4) uint8, "level_counts": uint64[16]}
+    (the keys named in `want`): trace_rays(method="wavefront") with the nodes of the first `levels` levels relit as relight_rays relights
+    them - the reference's picture, colours, highlights, reflections and glass, with lights that have a size.  levels 1 softens what the
+    rays themselves hit, levels >= the depth every bounce; levels 0 is the wavefront trace itself.  pix_i is the index of the ROOT ray
+    at every level.  offs None = lighting_offsets(n_samples) with stride 0 (every ray the same n_samples entries)."""
+    import numpy as np
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    want = set(want)
+    if not (want - {"level_counts"}) or want - {"rgb", "rgba", "level_counts"}:
+        raise ValueError("want names some of 'level_counts', 'rgb', 'rgba'")
+    if levels < 0 or levels >= 2 ** 32:
+        raise ValueError("levels is a count of levels, 0 .. 2^32 - 1")
+    n, aligned = _ray_list(rays)
+    if offs is None:
+        stride = 0
+    a, offs = _lighting_args(n_samples, light_radius, offs, stride, base, lib)
+    out = {}
+    if "rgb" in want:
+        out["rgb"] = np.empty((n, 3), np.float64)
+    if "rgba" in want:
+        out["rgba"] = np.empty((n, 4), np.uint8)
+    bufs = RtRayOutputs(out["rgb"].ctypes.data if "rgb" in out else None, out["rgba"].ctypes.data if "rgba" in out else None, None)
+    counts = np.zeros(RT_MAX_SEGS, np.uint64)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    rc = lib.rt_trace_rays_soft(buf, len(blob), C.byref(a), C.c_void_p(offs.ctypes.data), levels, n, C.c_void_p(aligned.ctypes.data), segs,
+                                1 if order_levels else 0, C.byref(bufs), None, counts.ctypes.data_as(C.POINTER(C.c_uint64)))
+    _check(lib, rc, "rt_trace_rays_soft")
+    if "level_counts" in want:
+        out["level_counts"] = counts
+    return out
+
+
+def trace_view_soft(scene, v, w, h, n_samples, light_radius, offs=None, stride=1, levels=1, segs=0, order_levels=False, want=("rgba",), lib=None):
+    """trace_rays_soft of what the view sees at w x h, in frame order ("rgba" (w h, 4) uint8 is the frame).  The rays are made on the HOST
+    (view_rays, the generator's restatement) and cross the link at 48 bytes each: a form that keeps a view's rays on the device is not
+    built."""
+    return trace_rays_soft(scene, view_rays(v, w, h, lib=lib), n_samples, light_radius, offs=offs, stride=stride, levels=levels, segs=segs,
+                           order_levels=order_levels, want=want, lib=lib)
 
 
 def _jsmin(a, b):

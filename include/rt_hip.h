@@ -1075,6 +1075,52 @@ int rt_scene_lighting_view_device(rt_scene_dev *scene, const rt_view *v, uint32_
 int rt_lighting_view(const void *scene_blob, size_t blob_bytes, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting *a,
                      const double *offs, const rt_lighting_outputs *host_out, rt_stats *stats);
 
+/* Relit nodes: soft shadows in the picture.  rt_lighting returns the diffuse sum alone; a wavefront node (rt_node) holds BOTH numbers the
+ * lights decide, diffuse and specular, and rt_scene_fold_nodes_device turns nodes into the picture.  This call computes the two again
+ * over n_samples displaced copies of the lights and writes their mean back into the node: shade, relight, spawn and fold then draw the
+ * reference's picture - colours, highlights, reflections, glass - with lights that have a size.  What it was measured at:
+ * docs/EVIDENCE.md, "Relit nodes".
+ *
+ * Node i of ray i (d_rays: the list rt_scene_shade_rays_device shaded it from; d is its direction), with the parameters of a struct
+ * rt_lighting; every operation in binary64 without FMA contraction, the strict arithmetic of rt_scene_shade_rays_device:
+ *   shading = hit.object >= 0 && (albedo[1] > 0 || albedo[2] > 0) of the hit sphere;  l = hit.inside ? -hit.normal : hit.normal
+ *   e = (((uint64)base + (uint64)pix_i) * (uint64)stride + (uint64)s) % (uint64)n_offs    pix_i = d_pix[i], or i where d_pix is NULL
+ *   o = offs[e]                             the SAME entry for every light of the sample; at light_radius 0 the table is not read
+ *   per sample s: the light loop of rt_scene_shade_rays_device (main.js:283-315) with light k standing at
+ *     light_radius == 0 ? light_k : { light_k[c] + light_radius * o[c] }
+ *   - ONE intensity carried from light to light, no scan for a light once it is 0 (the shade kernel's rule, where rt_lighting scans
+ *   on: they differ for a negative or NaN albedo[4] only), the specular term with the strict build's pow - and then
+ *     diffuse_s = min(1, diffuse) * albedo[1],  specular_s = min(1, specular) * albedo[2]            (main.js:316-317, PER SAMPLE)
+ *   over the samples, the fold of a sampled view, once per term: acc = x_0; acc = acc + x_s in order; acc / (double)n_samples
+ * The two means are stored at bytes 104 and 112 of the node; no other byte is written.  A miss and a node that is not shading get 0.0
+ * and 0.0, which is what the shade wrote.  The terms are clamped per sample: a relit node is the mean of the nodes
+ * rt_scene_shade_rays_device writes for the same ray in n_samples scenes whose lights were moved on the host - the accumulation of n
+ * point-light pictures' light terms - and with n_samples 1 and light_radius 0 it is the shaded node itself.
+ *
+ * d_offs, d_rays, d_order, d_pix and d_nodes are DEVICE memory.  d_order works as for rt_scene_shade_rays_device (an entry >= n is
+ * skipped, nothing is written for it).  Stream, stats (pixels = n), thread and pending-edit rules are rt_scene_lighting_device's: the
+ * spheres, epsilon, lights and light_intensity are the scene's current ones at the call.  One work-item per node, no scratch memory.
+ * RT_ERR_INVALID, before a device is touched: what rt_lighting_validate refuses of `a`, n outside 1..2^31 - 1, a NULL or misaligned
+ * d_rays (16 bytes) or d_nodes (8 bytes), a NULL (light_radius != 0) or misaligned d_offs (8 bytes), a misaligned d_order or d_pix
+ * (4 bytes); then RT_ERR_STATE: a NULL scene. */
+int rt_scene_relight_nodes_device(rt_scene_dev *scene, const struct rt_lighting *a, const double *d_offs, uint64_t n, const double *d_rays,
+                                  const uint32_t *d_order, const uint32_t *d_pix, rt_node *d_nodes, void *hip_stream, rt_stats *stats);
+
+/* Host form: rt_shade_rays followed by the relight of each chunk of 2^18 rays; `offs` (HOST memory, n_offs entries, what
+ * rt_lighting_validate accepts) goes up once.  Ray i keeps pix = i without `pix` (chunk c passes base + c * 2^18), so a list gives the
+ * bytes of one launch however it is cut.  Everything else as rt_shade_rays. */
+int rt_relight_rays(const void *scene_blob, size_t blob_bytes, const struct rt_lighting *a, const double *offs, uint64_t n,
+                    const double *rays, const uint32_t *pix, const uint32_t *path, int binned, rt_node *host_nodes, rt_stats *stats);
+
+/* Host form: rt_trace_rays_wavefront's loop with a relight behind the shade of every level lv < levels (level 0 holds the primary hits).
+ * levels 0 gives rt_trace_rays_wavefront itself, launch for launch; levels >= the depth relights every bounce.  pix_i is the ROOT ray's
+ * index in the list at every level (it travels with the children as the stars sampler's pix does), so the nodes of one tree share their
+ * root's table entries and no result depends on how the list is chunked.  The table goes up once per call.  RT_ERR_INVALID: what
+ * rt_lighting_validate and rt_trace_rays_wavefront refuse. */
+int rt_trace_rays_soft(const void *scene_blob, size_t blob_bytes, const struct rt_lighting *a, const double *offs, uint32_t levels,
+                       uint64_t n, const double *rays, uint32_t segs, int order_levels, const rt_ray_outputs *host_out, rt_stats *stats,
+                       uint64_t *level_counts);
+
 #ifdef __cplusplus
 }
 #endif
