@@ -14,6 +14,7 @@
 //   rt_ambient_api.hip  ambient occlusion: validation, the cosine table, the host probe, the launches of rt_ambient.hip, the host forms
 //   rt_lighting_api.hip  sampled lights: validation, the offset table, the host probe, the launch of rt_lighting.hip, the host forms
 //   rt_relight_api.hip  relit nodes: the argument check, the launch of rt_relight.hip and its device entry point (the host forms are rt_frame.hip's)
+//   rt_soft_api.hip  the soft trace in one launch: the argument check, the launch of rt_soft.hip, its device entry points (a list, a view) and host forms
 // Which kernel a launch runs is one value (rt_device.h: rt_trace_variant), worked out once per launch; the two builds of rt_kernel.hip map
 // it to a kernel (rt_kernel_trace_fast / rt_kernel_trace_strict), and the declarations below are all the host sees of them.
 #ifndef RT_API_INTERNAL_H
@@ -285,6 +286,9 @@ struct rt_scene_dev {
   bool unit_weights;             // every albedo and colour in [0, 1] (RT_MARK_WEIGHT)
   double flag_tol;               // RT_FLAG_T1 x the largest sampler frequency of the scene (texture width / height, checker frequencies): rt_device.h
 };
+
+// elements per chunk of the host lists that go through device buffers (rt_frame.hip, rt_soft_api.hip)
+#define RT_RAY_CHUNK (1u << 18)
 
 namespace rt_api {
 constexpr size_t RT_KNOWN_WORDS = 256;

@@ -372,7 +372,6 @@ extern "C" int rt_pick(const void *blob, size_t bytes, uint32_t w, uint32_t h, u
 // gets no buffer.  Per chunk: the inputs are copied in, `binned`: the chunk is ordered on the GPU (rt_rays_order.hip; the order buffer
 // and the workspace are the call's, like its other device memory), `launch` runs it, the outputs are copied back, and the stream is
 // drained.  Synchronous; kernel_ms is the sum over the chunks, the orderings included.
-#define RT_RAY_CHUNK (1u << 18)
 namespace {
 struct list_row { const void *host; size_t each; bool out; };       // one array of the list: element size, and which way it is copied
 constexpr int RT_LIST_ROWS = 6;

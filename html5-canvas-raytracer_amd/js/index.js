@@ -146,16 +146,18 @@ function tanHalf(projA) { return Math.tan(projA / 2); }
 // bounce) are means over `samples` runs of the light loop, every light displaced by lightRadius times an entry of offsets (default
 // lightingOffsets(samples) with stride 0: every ray the same entries; with offsets, stride defaults to 1 and ray i walks the table from
 // (base + i) * stride; relightRays' stride defaults to 1 either way).  No hits, no bin.
+// opts.soft.method: 'wavefront' (the default) or 'recursive' - the same picture from one launch per chunk of 2^18 rays, a per-lane stack
+// in place of the nodes in device memory (rt_trace_rays_soft_recursive): the same bytes, no levelCounts, and {bin: true} is allowed.
 function softOf(o, who, walks) {
   const s = o.soft;
   if (s === null || typeof s !== 'object' || !Number.isInteger(s.samples) || s.samples < 1 || typeof s.lightRadius !== 'number' ||
       (s.offsets != null && !(s.offsets instanceof Float64Array && s.offsets.length > 0 && s.offsets.length % 3 === 0)) ||
       (s.stride != null && !(Number.isInteger(s.stride) && s.stride >= 0)) || (s.levels != null && !(Number.isInteger(s.levels) && s.levels >= 0)) ||
-      (s.base != null && !(Number.isInteger(s.base) && s.base >= 0))) {
-    throw new TypeError(who + ': soft is {samples: integer >= 1, lightRadius: number[, offsets: Float64Array of 3 numbers per entry, stride, levels, base]}');
+      (s.base != null && !(Number.isInteger(s.base) && s.base >= 0)) || (s.method != null && s.method !== 'wavefront' && s.method !== 'recursive')) {
+    throw new TypeError(who + ": soft is {samples: integer >= 1, lightRadius: number[, offsets: Float64Array of 3 numbers per entry, stride, levels, base, method: 'wavefront' | 'recursive']}");
   }
   const offs = s.offsets || native().lightingOffsets(s.samples);
-  return {levels: s.levels == null ? 1 : s.levels, tail: [offs, s.samples, s.stride != null ? s.stride : (s.offsets || walks ? 1 : 0), s.base || 0, s.lightRadius]};
+  return {recursive: s.method === 'recursive', levels: s.levels == null ? 1 : s.levels, tail: [offs, s.samples, s.stride != null ? s.stride : (s.offsets || walks ? 1 : 0), s.base || 0, s.lightRadius]};
 }
 function traceRays(sceneObj, rays, opts) {
   if (!(rays instanceof Float64Array) || rays.length === 0 || rays.length % 6 !== 0) {
@@ -164,10 +166,11 @@ function traceRays(sceneObj, rays, opts) {
   if (!inited) init(opts && opts.maxDevices);
   const o = opts || {};
   if (o.wavefront && (o.hits || o.bin)) throw new TypeError('traceRays: {wavefront: true} returns no hits and takes no {bin: true} (orderLevels bins the later levels)');
-  if (o.soft !== undefined && (o.hits || o.bin)) throw new TypeError('traceRays: {soft} returns no hits and takes no {bin: true}');
   const soft = o.soft !== undefined ? softOf(o, 'traceRays') : null;
+  if (soft && (o.hits || (o.bin && !soft.recursive))) throw new TypeError("traceRays: {soft} returns no hits and takes {bin: true} with method 'recursive' only");
+  if (soft && soft.recursive && (o.wavefront || o.orderLevels)) throw new TypeError("traceRays: {soft: {method: 'recursive'}} is not the wavefront form");
   const args = [new Uint8Array(flattenScene(sceneObj)), rays, o.segs || 0, o.rgb !== false, !!o.rgba, !!o.hits, !!o.bin, !!o.wavefront, !!o.orderLevels];
-  const r = soft ? native().traceRays(...args, soft.levels, ...soft.tail) : native().traceRays(...args);
+  const r = soft ? native().traceRays(...args, soft.levels, ...soft.tail, soft.recursive) : native().traceRays(...args);
   if (r.hits) for (const h of r.hits) if (h) h.object = sceneObj.objects[h.index];
   return r;
 }
@@ -238,10 +241,13 @@ function packSamples(samples) {
 // opts.samples (views.sampleGrid(k), or the caller's own [{dx, dy, lu, lv}]) and / or opts.lens (views.lens, pinhole views): one trace
 // per sample, averaged on the GPU in binary64 (rt_trace_view_samples) - rgb is the mean, rgba the mean through the store rule; no hits.
 // A lens without samples takes the one zero sample: the pinhole itself.
+// opts.soft: {samples, lightRadius, offsets, stride, levels} as traceRays takes them - the soft trace of the view, its rays generated on
+// the device and each chunk of rows one launch (rt_trace_view_soft); no hits, no samples or lens.
 function traceView(sceneObj, view, w, h, opts) {
   if (!view || !Number.isInteger(view.model)) throw new TypeError('traceView: view must come from views.reference / pinhole / ortho / equirect');
   if (!inited) init(opts && opts.maxDevices);
   const o = opts || {};
+  if (o.soft !== undefined && (o.hits || o.samples || o.lens)) throw new TypeError('traceView: {soft} returns no hits and takes no samples or lens');
   if (o.samples || o.lens) {
     if (o.hits) throw new TypeError('traceView: a sampled view returns no hits (a mean of hit records means nothing)');
     const samples = packSamples(o.samples || [{dx: 0, dy: 0, lu: 0, lv: 0}]);
@@ -249,8 +255,9 @@ function traceView(sceneObj, view, w, h, opts) {
     return native().traceViewSamples(new Uint8Array(flattenScene(sceneObj)), viewBytes(view), t.lon, t.lat, w, h, samples,
       o.lens ? new Float64Array([o.lens.radius, o.lens.focus]) : null, o.segs || 0, !!o.rgb, o.rgba !== false);
   }
+  const soft = o.soft !== undefined ? softOf({soft: Object.assign({}, o.soft, {base: 0, method: undefined})}, 'traceView') : null;
   const r = native().traceView(new Uint8Array(flattenScene(sceneObj)), viewBytes(view), view.lon || null, view.lat || null, w, h, o.segs || 0,
-    !!o.rgb, o.rgba !== false, !!o.hits);
+    !!o.rgb, o.rgba !== false, !!o.hits, ...(soft ? [soft.levels, ...soft.tail] : []));
   if (r.hits) for (const hit of r.hits) if (hit) hit.object = sceneObj.objects[hit.index];
   return r;
 }

@@ -16,11 +16,13 @@
 //           rgba: Uint8ClampedArray | null, hits: Array of pick's records (null = a miss) | null}: intersectWorld per ray (rt_trace_rays;
 //           bin: rt_trace_rays_binned, the list ordered on the GPU first - the same results; two more booleans, wavefront and
 //           orderLevels: rt_trace_rays_wavefront, the same rgb and rgba level by level, plus levelCounts; six more, levels and lighting's tail
-//           offs, nSamples, stride, base, lightRadius: rt_trace_rays_soft, the wavefront form with the first `levels` levels' nodes relit)
+//           offs, nSamples, stride, base, lightRadius: rt_trace_rays_soft, the wavefront form with the first `levels` levels' nodes relit;
+//           one more boolean, recursive: rt_trace_rays_soft_recursive, the same bytes from one launch per chunk)
 //           shadeRays(blob, rays, pix: Uint32Array | null, path: Uint32Array | null, bin) -> {nodes: ArrayBuffer of rt_node records, count}
 //           relightRays(blob, rays, pix, path, bin, offs, nSamples, stride, base, lightRadius) -> the same, with soft lights (rt_relight_rays)
 //           traceView(blob, view: Uint8Array (the 136 bytes of rt_view, table pointers ignored), lon: Float64Array | null, lat: Float64Array | null,
-//           w, h, segs, wantRgb, wantRgba, wantHits) -> traceRays' result for the view's w x h rays, generated on the GPU (rt_trace_view)
+//           w, h, segs, wantRgb, wantRgba, wantHits) -> traceRays' result for the view's w x h rays, generated on the GPU (rt_trace_view;
+//           six more, levels and lighting's tail: rt_trace_view_soft, the soft trace of the view in one launch per chunk of rows, no hits)
 //           equirectTables(w, h) -> {lon: Float64Array (2 w), lat: Float64Array (2 h)} (rt_view_equirect_tables)
 //           viewSamplesGrid(k) -> Float64Array (dx, dy, lu, lv per sample: rt_view_samples_grid)
 //           equirectSampleTables(w, h, samples) -> {lon, lat}: one table per sample (rt_view_equirect_sample_tables)
@@ -491,12 +493,12 @@ napi_value Pick(napi_env env, napi_callback_info info) {
 bool lighting_args(napi_env env, size_t argc, napi_value *argv, size_t at, const char *who, struct rt_lighting *a, const double **offs, bool want[4]);
 
 napi_value TraceRays(napi_env env, napi_callback_info info) {
-  size_t argc = 15;
-  napi_value argv[15];
+  size_t argc = 16;
+  napi_value argv[16];
   bool is_ta = false, is_rays = false;
   if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
       napi_is_typedarray(env, argv[1], &is_rays) != napi_ok || !is_rays) {
-    napi_throw_type_error(env, nullptr, "traceRays(blob: Uint8Array, rays: Float64Array[, segs, wantRgb, wantRgba, wantHits, bin, wavefront, orderLevels, levels, offs, nSamples, stride, base, lightRadius])");
+    napi_throw_type_error(env, nullptr, "traceRays(blob: Uint8Array, rays: Float64Array[, segs, wantRgb, wantRgba, wantHits, bin, wavefront, orderLevels, levels, offs, nSamples, stride, base, lightRadius, recursive])");
     return nullptr;
   }
   napi_typedarray_type bt, rt; napi_value ab; size_t off, blob_len = 0, ray_len = 0;
@@ -517,7 +519,8 @@ napi_value TraceRays(napi_env env, napi_callback_info info) {
   if (argc >= 8) napi_get_value_bool(env, argv[7], &wavefront);
   if (argc >= 9) napi_get_value_bool(env, argv[8], &order_levels);
   // soft lights (rt_trace_rays_soft): levels, then the tail lighting takes - offs: Float64Array (3 per entry), nSamples, stride, base, lightRadius
-  bool soft = false;
+  // ... and `recursive`: the soft trace in one launch per chunk (rt_trace_rays_soft_recursive) instead of the wavefront loop - the same bytes
+  bool soft = false, recursive = false;
   uint32_t levels = 0;
   struct rt_lighting la;
   const double *offs = nullptr;
@@ -534,7 +537,12 @@ napi_value TraceRays(napi_env env, napi_callback_info info) {
       return nullptr;
     }
     if (!lighting_args(env, argc, argv, 10, who, &la, &offs, unused)) return nullptr;
-    wavefront = true;                                   // (the wavefront loop with a relight behind the shade of the first `levels` levels)
+    if (argc > 15) napi_get_value_bool(env, argv[15], &recursive);
+    wavefront = !recursive;                             // (the wavefront loop with a relight behind the shade of the first `levels` levels)
+    if (recursive && (want[2] || order_levels)) {
+      napi_throw_type_error(env, nullptr, "traceRays: the recursive soft trace returns no hit records and has no levels to order");
+      return nullptr;
+    }
   }
   if (wavefront && (want[2] || bin)) {
     napi_throw_type_error(env, nullptr, "traceRays: the wavefront form returns no hit records and takes the first level in the list's order");
@@ -558,11 +566,12 @@ napi_value TraceRays(napi_env env, napi_callback_info info) {
   const rt_ray_outputs out = {(double *)p_rgb, (uint8_t *)p_rgba, hits};
   rt_stats st;
   uint64_t level_counts[RT_MAX_SEGS] = {0};
-  const int rc = soft ? rt_trace_rays_soft(mem, blob_len, &la, offs, levels, n, (const double *)(mem + blob_room), segs, order_levels ? 1 : 0, &out, &st, level_counts)
+  const int rc = recursive ? rt_trace_rays_soft_recursive(mem, blob_len, &la, offs, levels, n, (const double *)(mem + blob_room), segs, bin ? 1 : 0, &out, &st)
+                 : soft ? rt_trace_rays_soft(mem, blob_len, &la, offs, levels, n, (const double *)(mem + blob_room), segs, order_levels ? 1 : 0, &out, &st, level_counts)
                  : wavefront ? rt_trace_rays_wavefront(mem, blob_len, n, (const double *)(mem + blob_room), segs, order_levels ? 1 : 0, &out, &st, level_counts)
                              : (bin ? rt_trace_rays_binned : rt_trace_rays)(mem, blob_len, n, (const double *)(mem + blob_room), segs, &out, &st);
   free(mem);
-  if (rc != RT_OK) { free(hits); return throw_rt(env, soft ? "rt_trace_rays_soft" : wavefront ? "rt_trace_rays_wavefront" : bin ? "rt_trace_rays_binned" : "rt_trace_rays", rc); }
+  if (rc != RT_OK) { free(hits); return throw_rt(env, recursive ? "rt_trace_rays_soft_recursive" : soft ? "rt_trace_rays_soft" : wavefront ? "rt_trace_rays_wavefront" : bin ? "rt_trace_rays_binned" : "rt_trace_rays", rc); }
   napi_create_object(env, &res);
   if (wavefront) {                                      // the rays shaded per level
     napi_value lc, c;
@@ -608,10 +617,11 @@ napi_value EquirectTables(napi_env env, napi_callback_info info) {
 }
 
 // traceView(blob, view, lon, lat, w, h, segs, wantRgb, wantRgba, wantHits): rt_trace_view.  `view` is the bytes of an rt_view whose table
-// pointers are ignored: an EQUIRECT view's tables come as the two Float64Arrays.
+// pointers are ignored: an EQUIRECT view's tables come as the two Float64Arrays.  With levels and traceRays' soft tail behind them (offs,
+// nSamples, stride, base, lightRadius): rt_trace_view_soft, the soft trace of the view generated on the device; no hits.
 napi_value TraceView(napi_env env, napi_callback_info info) {
-  size_t argc = 10;
-  napi_value argv[10];
+  size_t argc = 16;
+  napi_value argv[16];
   bool is_ta = false, is_view = false;
   if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 6 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
       napi_is_typedarray(env, argv[1], &is_view) != napi_ok || !is_view) {
@@ -649,6 +659,24 @@ napi_value TraceView(napi_env env, napi_callback_info info) {
   bool want[3] = {false, true, false};
   if (argc >= 7) napi_get_value_uint32(env, argv[6], &segs);
   for (size_t i = 0; i < 3 && 7 + i < argc; i++) napi_get_value_bool(env, argv[7 + i], &want[i]);
+  bool soft = false;
+  uint32_t levels = 0;
+  struct rt_lighting la;
+  const double *offs = nullptr;
+  if (argc > 10) {
+    napi_valuetype lt;
+    napi_typeof(env, argv[10], &lt);
+    soft = lt != napi_undefined && lt != napi_null;
+  }
+  if (soft) {
+    const char *who = "traceView: soft lights are levels, offs: Float64Array (3 per entry), nSamples, stride, base, lightRadius; no hits";
+    bool unused[4];
+    if (napi_get_value_uint32(env, argv[10], &levels) != napi_ok || want[2]) {
+      napi_throw_type_error(env, nullptr, who);
+      return nullptr;
+    }
+    if (!lighting_args(env, argc, argv, 11, who, &la, &offs, unused)) return nullptr;
+  }
   const size_t n = sized ? (size_t)w * h : 0;
   // the library wants the blob 8-byte and the tables 16-byte aligned: one aligned copy holds all three
   const size_t blob_room = (blob_len + 15) & ~(size_t)15, lon_room = table_len[0] * 8u, lat_room = table_len[1] * 8u;
@@ -671,9 +699,9 @@ napi_value TraceView(napi_env env, napi_callback_info info) {
   }
   const rt_ray_outputs out = {(double *)p_rgb, (uint8_t *)p_rgba, hits};
   rt_stats st;
-  const int rc = rt_trace_view(mem, blob_len, &view, w, h, segs, &out, &st);
+  const int rc = soft ? rt_trace_view_soft(mem, blob_len, &view, w, h, &la, offs, levels, segs, &out, &st) : rt_trace_view(mem, blob_len, &view, w, h, segs, &out, &st);
   free(mem);
-  if (rc != RT_OK) { free(hits); return throw_rt(env, "rt_trace_view", rc); }
+  if (rc != RT_OK) { free(hits); return throw_rt(env, soft ? "rt_trace_view_soft" : "rt_trace_view", rc); }
   napi_create_object(env, &res);
   if (want[0]) napi_create_typedarray(env, napi_float64_array, 3 * n, ab_rgb, 0, &v); else napi_get_null(env, &v);
   napi_set_named_property(env, res, "rgb", v);

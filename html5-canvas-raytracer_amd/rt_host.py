@@ -379,6 +379,15 @@ ABI = {
                                   C.c_void_p, C.POINTER(RtStats)]),
     "rt_trace_rays_soft": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtLighting), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int,
                                      C.POINTER(RtRayOutputs), C.POINTER(RtStats), C.POINTER(C.c_uint64)]),
+    "rt_scene_trace_rays_soft_device": (C.c_int, [C.c_void_p, C.POINTER(RtLighting), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                  C.c_uint32, C.POINTER(RtRayOutputs), C.c_void_p, C.POINTER(RtStats)]),
+    "rt_soft_view_work_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_scene_trace_view_soft_device": (C.c_int, [C.c_void_p, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtLighting), C.c_void_p, C.c_uint32,
+                                                  C.c_uint32, C.POINTER(RtRayOutputs), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_trace_rays_soft_recursive": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtLighting), C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32,
+                                               C.c_int, C.POINTER(RtRayOutputs), C.POINTER(RtStats)]),
+    "rt_trace_view_soft": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtLighting), C.c_void_p, C.c_uint32,
+                                     C.c_uint32, C.POINTER(RtRayOutputs), C.POINTER(RtStats)]),
 }
 
 RT_MAX_SEGS = 16
@@ -774,6 +783,37 @@ class Renderer:
                                                     C.c_void_p(pix_ptr or 0), C.c_void_p(nodes_ptr or 0), C.c_void_p(stream or 0),
                                                     C.byref(st) if st is not None else None)
         _check(self.lib, rc, "rt_scene_relight_nodes_device")
+        return st
+
+    def trace_rays_soft(self, n, rays_ptr, rgb_ptr, rgba_ptr, offs_ptr, n_offs, n_samples, light_radius, stride=1, base=0, levels=1, segs=0, order_ptr=0,
+                        pix_base=0, stream=None, want_stats=False):
+        """The soft trace in ONE launch: intersectWorld for n rays in DEVICE memory, walked depth-first over a per-lane stack, with the
+        light terms of the nodes at tree levels below `levels` sampled as relight_nodes samples them - rt_host.trace_rays_soft's rgb
+        (3 float64 per ray) and rgba into DEVICE buffers (0 / None = not wanted), bit for bit, without nodes in device memory and without
+        a host wait.  Sample s of every node of ray i uses entry ((base + pix_base + i) stride + s) % n_offs of the table offs_ptr (DEVICE;
+        0 where light_radius is 0); pix_base is the index of the list's first ray in the caller's whole list (the stars sampler's pix is
+        pix_base + i too), so a list traced in pieces gives the bytes of one call.  order_ptr as trace_rays_ordered takes it.  With the
+        scene's CURRENT lights, light intensity and spheres."""
+        a = RtLighting(n_samples, n_offs, stride, 0, base, float(light_radius))
+        out = RtRayOutputs(rgb_ptr or None, rgba_ptr or None, None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_trace_rays_soft_device(self.handle, C.byref(a), C.c_void_p(offs_ptr or 0), levels, n, C.c_void_p(rays_ptr or 0),
+                                                      C.c_void_p(order_ptr or 0), pix_base, segs, C.byref(out), C.c_void_p(stream or 0),
+                                                      C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_trace_rays_soft_device")
+        return st
+
+    def trace_view_soft(self, view, w, h, rgb_ptr, rgba_ptr, offs_ptr, n_offs, n_samples, light_radius, work_ptr, work_bytes, stride=1, base=0, levels=1,
+                        segs=0, stream=None, want_stats=False):
+        """trace_rays_soft() for what `view` sees at w x h, pixel y w + x being ray y w + x, into DEVICE buffers in frame order: the rays
+        are generated on the GPU band by band in work_ptr (DEVICE, 16-byte aligned, work_bytes >= 48 w; soft_view_work_bytes(w, h) is the
+        size the library prefers) and each band is one launch.  An EQUIRECT view's tables are DEVICE pointers here."""
+        a = RtLighting(n_samples, n_offs, stride, 0, base, float(light_radius))
+        out = RtRayOutputs(rgb_ptr or None, rgba_ptr or None, None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_trace_view_soft_device(self.handle, C.byref(view), w, h, C.byref(a), C.c_void_p(offs_ptr or 0), levels, segs, C.byref(out),
+                                                      C.c_void_p(work_ptr or 0), work_bytes, C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_trace_view_soft_device")
         return st
 
     def spawn_rays(self, n, nodes_ptr, child_rays_ptr, links_ptr, count_ptr, work_ptr, work_bytes, pix_ptr=0, path_ptr=0, child_pix_ptr=0,
@@ -1706,33 +1746,62 @@ def relight_rays(scene, rays, n_samples, light_radius, offs=None, stride=1, pix=
     return nodes
 
 
-def trace_rays_soft(scene, rays, n_samples, light_radius, offs=None, stride=1, levels=1, segs=0, order_levels=False, want=("rgba",), base=0, lib=None):
-    """trace_rays_soft(scene, rays, n_samples, light_radius) -> {"rgb": (n, 3) float64, "rgba": (n, 4) uint8, "level_counts": uint64[16]}
-    (the keys named in `want`): trace_rays(method="wavefront") with the nodes of the first `levels` levels relit as relight_rays relights
-    them - the reference's picture, colours, highlights, reflections and glass, with lights that have a size.  levels 1 softens what the
-    rays themselves hit, levels >= the depth every bounce; levels 0 is the wavefront trace itself.  pix_i is the index of the ROOT ray
-    at every level.  offs None = lighting_offsets(n_samples) with stride 0 (every ray the same n_samples entries)."""
+def soft_view_work_bytes(w, h, lib=None):
+    """Bytes of device workspace Renderer.trace_view_soft prefers for a w x h view (host arithmetic; 0 for a size it refuses).  48 w - one
+    row - is the least it accepts."""
+    return int((lib or load_library()).rt_soft_view_work_bytes(w, h))
+
+
+def _soft_outputs(n, want, counts_allowed):
     import numpy as np
-    lib = lib or load_library()
-    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
     want = set(want)
-    if not (want - {"level_counts"}) or want - {"rgb", "rgba", "level_counts"}:
-        raise ValueError("want names some of 'level_counts', 'rgb', 'rgba'")
-    if levels < 0 or levels >= 2 ** 32:
-        raise ValueError("levels is a count of levels, 0 .. 2^32 - 1")
-    n, aligned = _ray_list(rays)
-    if offs is None:
-        stride = 0
-    a, offs = _lighting_args(n_samples, light_radius, offs, stride, base, lib)
+    allowed = {"rgb", "rgba"} | ({"level_counts"} if counts_allowed else set())
+    if not (want - {"level_counts"}) or want - allowed:
+        raise ValueError("want names some of %s" % ", ".join(repr(k) for k in sorted(allowed)))
     out = {}
     if "rgb" in want:
         out["rgb"] = np.empty((n, 3), np.float64)
     if "rgba" in want:
         out["rgba"] = np.empty((n, 4), np.uint8)
-    bufs = RtRayOutputs(out["rgb"].ctypes.data if "rgb" in out else None, out["rgba"].ctypes.data if "rgba" in out else None, None)
-    counts = np.zeros(RT_MAX_SEGS, np.uint64)
+    return want, out, RtRayOutputs(out["rgb"].ctypes.data if "rgb" in out else None, out["rgba"].ctypes.data if "rgba" in out else None, None)
+
+
+def trace_rays_soft(scene, rays, n_samples, light_radius, offs=None, stride=1, levels=1, segs=0, order_levels=False, want=("rgba",), base=0, lib=None,
+                    method="wavefront", order="list"):
+    """trace_rays_soft(scene, rays, n_samples, light_radius) -> {"rgb": (n, 3) float64, "rgba": (n, 4) uint8, "level_counts": uint64[16]}
+    (the keys named in `want`): trace_rays(method="wavefront") with the nodes of the first `levels` levels relit as relight_rays relights
+    them - the reference's picture, colours, highlights, reflections and glass, with lights that have a size.  levels 1 softens what the
+    rays themselves hit, levels >= the depth every bounce; levels 0 is the wavefront trace itself.  pix_i is the index of the ROOT ray
+    at every level.  offs None = lighting_offsets(n_samples) with stride 0 (every ray the same n_samples entries).
+    method: "wavefront" (the default: the level-by-level loop, rt_trace_rays_soft) or "recursive" (rt_trace_rays_soft_recursive: one
+    launch per chunk of 2^18 rays, a per-lane stack instead of nodes in device memory - the same bytes; no "level_counts", no
+    order_levels).  order, for the recursive method: "list", or "binned" (the GPU orders each chunk first - the same bytes)."""
+    import numpy as np
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    if method not in ("wavefront", "recursive"):
+        raise ValueError("method is 'wavefront' or 'recursive'")
+    if order not in ("list", "binned"):
+        raise ValueError("order is 'list' or 'binned'")
+    if method == "wavefront" and order != "list":
+        raise ValueError("order is the recursive method's (the wavefront method has order_levels)")
+    if method == "recursive" and order_levels:
+        raise ValueError("order_levels is the wavefront method's (the recursive method has order)")
+    if levels < 0 or levels >= 2 ** 32:
+        raise ValueError("levels is a count of levels, 0 .. 2^32 - 1")
+    n, aligned = _ray_list(rays)
+    want, out, bufs = _soft_outputs(n, want, method == "wavefront")
+    if offs is None:
+        stride = 0
+    a, offs = _lighting_args(n_samples, light_radius, offs, stride, base, lib)
     _init_once(lib)
     buf = C.create_string_buffer(blob, len(blob))
+    if method == "recursive":
+        rc = lib.rt_trace_rays_soft_recursive(buf, len(blob), C.byref(a), C.c_void_p(offs.ctypes.data), levels, n, C.c_void_p(aligned.ctypes.data), segs,
+                                              1 if order == "binned" else 0, C.byref(bufs), None)
+        _check(lib, rc, "rt_trace_rays_soft_recursive")
+        return out
+    counts = np.zeros(RT_MAX_SEGS, np.uint64)
     rc = lib.rt_trace_rays_soft(buf, len(blob), C.byref(a), C.c_void_p(offs.ctypes.data), levels, n, C.c_void_p(aligned.ctypes.data), segs,
                                 1 if order_levels else 0, C.byref(bufs), None, counts.ctypes.data_as(C.POINTER(C.c_uint64)))
     _check(lib, rc, "rt_trace_rays_soft")
@@ -1741,12 +1810,32 @@ def trace_rays_soft(scene, rays, n_samples, light_radius, offs=None, stride=1, l
     return out
 
 
-def trace_view_soft(scene, v, w, h, n_samples, light_radius, offs=None, stride=1, levels=1, segs=0, order_levels=False, want=("rgba",), lib=None):
-    """trace_rays_soft of what the view sees at w x h, in frame order ("rgba" (w h, 4) uint8 is the frame).  The rays are made on the HOST
-    (view_rays, the generator's restatement) and cross the link at 48 bytes each: a form that keeps a view's rays on the device is not
-    built."""
-    return trace_rays_soft(scene, view_rays(v, w, h, lib=lib), n_samples, light_radius, offs=offs, stride=stride, levels=levels, segs=segs,
-                           order_levels=order_levels, want=want, lib=lib)
+def trace_view_soft(scene, v, w, h, n_samples, light_radius, offs=None, stride=1, levels=1, segs=0, order_levels=False, want=("rgba",), lib=None,
+                    method="wavefront"):
+    """trace_rays_soft of what the view sees at w x h, in frame order ("rgba" (w h, 4) uint8 is the frame).
+    method "wavefront" (the default): the rays are made on the HOST (view_rays, the generator's restatement), cross the link at 48 bytes
+    each and go through the wavefront loop.  method "recursive": the view's rays are generated on the GPU and traced there, one launch
+    per chunk of whole rows (rt_trace_view_soft) - only the offset table goes up and the frame comes back; the same bytes."""
+    if method not in ("wavefront", "recursive"):
+        raise ValueError("method is 'wavefront' or 'recursive'")
+    if method == "wavefront":
+        return trace_rays_soft(scene, view_rays(v, w, h, lib=lib), n_samples, light_radius, offs=offs, stride=stride, levels=levels, segs=segs,
+                               order_levels=order_levels, want=want, lib=lib)
+    if order_levels:
+        raise ValueError("order_levels is the wavefront method's")
+    if levels < 0 or levels >= 2 ** 32:
+        raise ValueError("levels is a count of levels, 0 .. 2^32 - 1")
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    want, out, bufs = _soft_outputs(max(int(w) * int(h), 0), want, False)
+    if offs is None:
+        stride = 0
+    a, offs = _lighting_args(n_samples, light_radius, offs, stride, 0, lib)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    rc = lib.rt_trace_view_soft(buf, len(blob), C.byref(v), w, h, C.byref(a), C.c_void_p(offs.ctypes.data), levels, segs, C.byref(bufs), None)
+    _check(lib, rc, "rt_trace_view_soft")
+    return out
 
 
 def _jsmin(a, b):

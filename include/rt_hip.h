@@ -1121,6 +1121,67 @@ int rt_trace_rays_soft(const void *scene_blob, size_t blob_bytes, const struct r
                        uint64_t n, const double *rays, uint32_t segs, int order_levels, const rt_ray_outputs *host_out, rt_stats *stats,
                        uint64_t *level_counts);
 
+/* Soft trace in one launch: rt_trace_rays_soft's picture from a recursive kernel.  The wavefront loop above allocates device memory,
+ * writes 200-byte nodes to HBM and waits on the host for the child count, per chunk and per level; this call is one launch per list
+ * with no node in HBM and no host wait.  What it was measured at: docs/EVIDENCE.md, "Soft trace in one launch".
+ *
+ * Ray i (record i of d_rays; pix = pix_base + i) is intersectWorld(segs, objects, org, dir), walked depth-first over a per-lane stack.
+ * Every operation is in binary64 without FMA contraction, and every step is one the calls above define:
+ *   a node at tree level lv (root = 0, lv < segs)   what rt_scene_shade_rays_device computes for the ray: the closest hit in blob order,
+ *     the sample (the stars sampler with pix and with path 1 at the root, 2 path for the reflect child, 2 path + 1 for the refract
+ *     child), the material's weights and the two directions.  A ray with a non-finite word is a miss whose sample is NaN x 3.
+ *   its light terms at lv < levels    rt_scene_relight_nodes_device's: n_samples passes of the light loop, sample s displacing every
+ *     light by light_radius * offs[e], e = (((uint64)base + pix_base + i) * stride + s) % n_offs with the ROOT ray's i; clamped and
+ *     weighted per sample; acc = x_0; acc = acc + x_s; acc / (double)n_samples; 0.0 and 0.0 for a node that is not shading
+ *   its light terms at lv >= levels   rt_scene_shade_rays_device's own: one pass, the lights where they stand, no division
+ *   children    as rt_scene_shade_rays_device marks them, reflect before refract; below the last level (lv + 1 == segs) none is visited
+ *   its colour  rt_scene_fold_nodes_device's: rgb*diffuse + rgb*specular + re + rf in that order, re and rf 0.0 where a child was not
+ *     visited (and added all the same), then max(rgb*albedo[0], min(1, .)); a miss returns its sample
+ * So rgb and rgba are rt_trace_rays_soft's for the same list, bit for bit; with levels 0, or with n_samples 1 and light_radius 0,
+ * they are rt_scene_trace_rays_device's.  segs 0 is the scene's depth; at depth 0 every finite ray gives 0, 0, 0.
+ * d_out: rgb (3 doubles per ray) and / or rgba (the store rule of main.js:195-198, alpha 255) at index i; hits must be NULL (the
+ * recursive rt_scene_trace_rays_device holds those).  d_order as for rt_scene_trace_rays_ordered_device, or NULL: work-item j takes ray
+ * d_order[j], an entry >= n is skipped and nothing is written for it; no result depends on it.  pix_base: a list processed in pieces
+ * passes each piece's first index, and gets the bytes of one call.
+ * d_offs, d_rays, d_order and the arrays d_out names are DEVICE memory.  Stream, stats (pixels = n), thread and pending-edit rules are
+ * rt_scene_relight_nodes_device's: the spheres, epsilon, lights, light_intensity and stars seed are the scene's current ones at the
+ * call.  One work-item per ray, 256 per workgroup; the stack (14 doubles per frame, at most 15 frames) lives in scratch memory, less
+ * per lane than rt_scene_trace_rays_device reserves; RT_ERR_NOMEM where the device cannot hold that reservation.
+ * RT_ERR_INVALID, before a device is touched: what rt_lighting_validate refuses of `a`, a NULL (light_radius != 0) or misaligned
+ * d_offs (8 bytes), n outside 1..2^31 - 1, pix_base + n > 2^31, a NULL or misaligned d_rays (16 bytes), a misaligned d_order
+ * (4 bytes), a NULL d_out, segs > RT_MAX_SEGS, a non-NULL hits, rgb and rgba both NULL, a misaligned rgb (8 bytes) or rgba (4 bytes);
+ * then RT_ERR_STATE: a NULL scene. */
+int rt_scene_trace_rays_soft_device(rt_scene_dev *scene, const struct rt_lighting *a, const double *d_offs, uint32_t levels, uint64_t n,
+                                    const double *d_rays, const uint32_t *d_order, uint32_t pix_base, uint32_t segs,
+                                    const rt_ray_outputs *d_out, void *hip_stream, rt_stats *stats);
+
+/* Host arithmetic: the workspace rt_scene_trace_view_soft_device prefers for a w x h view, 48 w h bytes - the whole view in one band.
+ * 0 where rt_view_work_bytes is 0. */
+size_t rt_soft_view_work_bytes(uint32_t w, uint32_t h);
+
+/* The soft trace of what a view sees, device-resident: pixel i = y * w + x is ray i, outputs in frame order.  Bands of whole rows in
+ * d_work (DEVICE, 16-byte aligned, work_bytes >= 48 w): per band the view's rays (rt_view_rays_device) and one launch of the kernel
+ * above with pix_base = y0 * w.  No result depends on the band size.  A panorama's tables are DEVICE memory, as for
+ * rt_scene_trace_view_device.  RT_ERR_INVALID, before a device is touched: what rt_view_validate refuses, what
+ * rt_scene_trace_rays_soft_device refuses of a, d_offs, segs and d_out, a NULL or misaligned workspace or one below a row; then
+ * RT_ERR_STATE: a NULL scene. */
+int rt_scene_trace_view_soft_device(rt_scene_dev *scene, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting *a,
+                                    const double *d_offs, uint32_t levels, uint32_t segs, const rt_ray_outputs *d_out, void *d_work,
+                                    size_t work_bytes, void *hip_stream, rt_stats *stats);
+
+/* Host form of rt_scene_trace_rays_soft_device on rt_render's resident scene, as rt_trace_rays: `offs`, the rays and the outputs in
+ * HOST memory, synchronous, on GPU 0, in chunks of 2^18 rays; chunk c passes pix_base = c * 2^18: the bytes of one launch over the
+ * whole list.  The table goes up once.  binned != 0 orders each chunk on the GPU first (rt_trace_rays_binned), which changes no result. */
+int rt_trace_rays_soft_recursive(const void *scene_blob, size_t blob_bytes, const struct rt_lighting *a, const double *offs,
+                                 uint32_t levels, uint64_t n, const double *rays, uint32_t segs, int binned,
+                                 const rt_ray_outputs *host_out, rt_stats *stats);
+
+/* Host form of rt_scene_trace_view_soft_device, as rt_trace_view: the rays are generated on the GPU and never cross the link; `offs`,
+ * a panorama's tables and the outputs in HOST memory, chunks of whole rows of at most 2^18 pixels.  The table goes up once (24 n_offs
+ * bytes); 4 to 28 bytes per pixel come back. */
+int rt_trace_view_soft(const void *scene_blob, size_t blob_bytes, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting *a,
+                       const double *offs, uint32_t levels, uint32_t segs, const rt_ray_outputs *host_out, rt_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
