@@ -244,6 +244,42 @@ __device__ __forceinline__ v3 reflect(const v3 v, const v3 n) {
 // Math.min(1, x) / Math.max(a, x) as used at main.js:316-317, :333-335 (NaN in x propagates)
 __device__ __forceinline__ double min1(double x) { return (x > 1.0) ? 1.0 : x; }
 __device__ __forceinline__ double maxa(double a, double x) { return (x < a) ? a : x; }
+// The same clamps as ONE instruction each, for the product build's frame kernels where the caller has established what the select
+// forms exist for.  min1 / maxa are a compare, two v_cndmask_b32 and a wait state; v_min_f64 / v_max_f64 are one issue - but they are
+// IEEE minNum / maxNum: of a NaN and a number they return the NUMBER, where Math.min(1, NaN) is NaN (and NaN is byte 0).  They are
+// written as inline asm because __builtin_fmin / __builtin_fmax put a canonicalising v_max_f64 x, x in front of every operand the compiler
+// cannot prove canonical (a value read from LDS, an asm result).  None is needed: every operand here is the result of this kernel's own
+// FP64 arithmetic or a finite constant, hence canonical, and with the IEEE mode bit of a compute kernel the instruction quiets a
+// signalling NaN itself.  Equal bytes, operand by operand:
+//   * rt_min1_nn(x): x is NOT NaN (the caller's test).  Then (x > 1) ? 1 : x and minNum(x, 1) are the same value, x's own zero included.
+//   * rt_max_nn(a, x): x is NOT NaN; a MAY be (colour inf x albedo 0).  (x < a) ? a : x takes x when a is NaN, and so does maxNum.
+//     For a == x of different signs of zero the select takes x and v_max_f64 may take +0: the value is 0 either way, and a channel's
+//     only readers are to_byte - 255 * (+-0) clamped against 0, byte 0 - and the parent's fold, fma(S, x, O), whose sum with O != 0 does not
+//     see the sign and with O == +-0 is a zero that goes the same two ways.  No reader divides by it or takes its sign.
+//   * rt_min_nn / rt_max_nn in the fold (F = max(LO, min(HI, O + S x))): operands are sums, products and fma results of this kernel (canonical); a NaN
+//     among them is swallowed as __builtin_fmin / __builtin_fmax swallowed it - the same minNum / maxNum, less the canonicalisation.
+// Not for ITEM, COUNT or RT_STRICT instantiations: rt_trace_rays hands rgb to its caller as DOUBLES (the sign of a zero is visible there),
+// rt_retrace and the strict kernels are the reference's own operation sequence, and the counting kernel is held to the strict one.
+__device__ __forceinline__ double rt_min_nn(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ double rt_max_nn(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ double rt_min1_nn(double x) { double r; asm("v_min_f64 %0, %1, 1.0" : "=v"(r) : "v"(x)); return r; }
+__device__ __forceinline__ double rt_max1_nn(double x) { double r; asm("v_max_f64 %0, %1, 1.0" : "=v"(r) : "v"(x)); return r; }
+#if !RT_STRICT
+// unit() for a caller that reads the vector only where the length it returns is non-zero (the reflection ray: `go_r = rlen != 0`): the
+// length as unit() gives it, the vector WITHOUT unit()'s four selects by m > 0 (eight v_cndmask_b32 and a compare).
+//   * m > 0: the selected arm, bit for bit.
+//   * m == 0 (the zero vector): the length is 0 - the caller does not descend, and nobody reads the vector (NaN here: 0 x rsq(0)).
+//   * m NaN (a NaN component): the length is NaN, which IS "non-zero" - the lane descends, here with a direction of three NaNs where unit()
+//     returned v with its NaN among finite components.  Either ray has tca = d.L NaN at every sphere (a sum with a NaN term), hence a NaN
+//     root that is never `closer_`: it meets nothing in either form, and a miss - the miss colour, or the flat enclosing sphere, whose colour
+//     is a constant or a hash of the pixel's index (rt_scene.hip: enclosing_flat) - does not read d.
+__device__ __forceinline__ v3 unit_go(const v3 v, double *len_out) {
+  const double m = dot(v, v);
+  const double s = rt_rsqrt_pos(m);
+  *len_out = (m > 0.0) ? m * s : m;
+  return mk(v.x * s, v.y * s, v.z * s);
+}
+#endif
 
 // Counter-based stand-in for Math.random() in the stars sampler (main.js:135-139): lowbias32 twice over the sample's
 // index in the frame and the node's position in the ray tree (root 1, reflect child 2p, refract child 2p+1), with the

@@ -208,7 +208,7 @@ __device__ __forceinline__ int rt_lvl(int lv) { return lv; }
 // The call then shades the wave on the uniform-material path - the one anchored test without closest-hit selects, the candidate's
 // record in scalar registers, the sampler, the light loop's material tests and the specular exponent decided on the scalar unit, no
 // LDS access, no fold state, no node loop - if, wave-uniformly, the material spawns no ray at this depth, its sampler is colour,
-// checker or texture, EVERY lane's primary ray meets the candidate, and no lane's sampler coordinate lies in the boundary test's
+// checker or texture, EVERY lane's primary ray meets the candidate from outside it, and no lane's sampler coordinate lies in the boundary test's
 // prefilter band (derived, not measured: ~6 x 2^-20 per sample x 64 samples = ~4e-4 of the waves; the general path marks such samples); otherwise it returns false before it has stored or marked
 // anything and the caller runs the general path (UNI = false), unchanged.  The per-lane arithmetic is this function's own: the same
 // statements in the same order, with the general path's bookkeeping compiled out (if constexpr).  Returns true when rgb is set.
@@ -238,6 +238,10 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 #else
   constexpr bool FOLD_FORWARD = true;       // the recursion is folded on the way down (see the descend step)
 #endif
+  // The reflection-only product frame kernels issue their clamps as one instruction each, restore no sign on the reflection's normal and select
+  // nothing in its normalisation (rt_kernel_math.h: rt_min_nn ..., unit_go, with the argument for equal bytes; docs/EVIDENCE.md, "Vector diet").
+  // Not the REFRACT kernels (bound by their parked stack, not examined), nor ITEM / COUNT / the strict build (rt_kernel_math.h says why).
+  constexpr bool LEAN = !RT_STRICT && !REFRACT && !COUNT && !ITEM;
   [[maybe_unused]] frame<REFRACT> stack[FOLD_FORWARD ? 1 : RT_MAX_SEGS];
   // product general kernel: nodes with BOTH a reflection and a refraction child are parked here while their
   // reflection subtree is traced (everything else needs no stack)
@@ -280,14 +284,18 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
           typename rt_mtl_src<true>::type &mu = *rt_mtl_at<true>(mtl, i);
           if ((mu.albedo[3] > 0.0 && segs_left > 1) || rt_mtl_kind(mu) == RT_SAMPLER_STARS) return false;
           RT_ANCHORED_DISC(g0)
-          RT_ROOT(tca_, disc_)
-          const bool met_ = !(disc_ < 0.0) && (t_ < ht) && !(t_ < eps);
+          const double t0_ = tca_ - rt_sqrt_nn<REFRACT>(disc_);          // (RT_ROOT's near root)
+          // ... and so does a lane that starts INSIDE the candidate (RT_ROOT's in_ = t0_ < eps, whose root would be the far one): the test is
+          // on the near root alone - no far root, no select - and the path takes l = n below, with nothing per lane.  (Today the launch
+          // table names no sphere the camera is inside of - rt_block.h, rt_ball.everywhere - so no wave leaves for this reason; the path's
+          // correctness does not rest on that property of the table.)
+          const bool met_ = !(disc_ < 0.0) && (t0_ < ht) && !(t0_ < eps);
           if (__ballot(!met_) != 0ull) return false;
 #if defined(RT_TESTING) && defined(RT_ABLATE_UNIFORM)   /* counting experiment only (profiles/ab_build.sh): what the launch issues WITHOUT the shading of these waves */
           rgb[0] = rgb[1] = rgb[2] = 0.0;
           return true;
 #endif
-          ht = t_; hcode = (int)(2u * i) + (in_ ? 1 : 0);
+          ht = t0_; hcode = (int)(2u * i);
         } else
         if (cand_host != 0u) {                        // count << 16 | second << 8 | first (loop indices, ascending)
           { const uint32_t i = cand_host & 255u; const rt_geom g0 = rt_load_geom32(ga, i); RT_ANCHORED(i, g0) }
@@ -491,11 +499,8 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
         const v3 n = mk((h.x - m.origin[0]) * inv_r, (h.y - m.origin[1]) * inv_r, (h.z - m.origin[2]) * inv_r);
 #endif
         v3 l;                                                           // hit.l, quirk q5
-        // (UNI: a camera outside the candidate - no lane inside - takes n as it is, decided once for the wave: the same values, no selects)
-        // (Belt and braces: today the launch table names no sphere the camera is inside of - rt_block.h, rt_ball.everywhere - so under UNI no
-        // lane is ever inside and the scalar branch is always taken; the per-lane form stays so that this path's correctness does not
-        // rest on that property of the table.)
-        if (UNI && __ballot(inside) == 0ull) l = n;
+        // (UNI: no lane is inside the candidate - a wave with one left before its hit test's ballot, above - so l is n)
+        if constexpr (UNI) l = n;
         else l = inside ? mk(-n.x, -n.y, -n.z) : n;
         const double a0 = m.albedo[0], a1 = m.albedo[1], a2 = m.albedo[2], a3 = m.albedo[3];
         const double a4 = REFRACT ? m.albedo[4] : 0.0;
@@ -626,6 +631,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
         // ---- A7 lights and shadow scan ----
         // A7 lighting and shadows
         double diffuse = 0.0, specular = 0.0;
+        [[maybe_unused]] double draw = 0.0, sraw = 0.0;                // (UNI: the light loop's sums before their clamps, for the leaf's NaN test)
 #if defined(RT_TESTING) && defined(RT_ABLATE_LIGHT)
         if (false) {
 #else
@@ -809,8 +815,15 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 #endif
             }
           }
+          if constexpr (UNI) {
+            // one-instruction clamps (a NaN sum comes out as 1 here: the wave's leaf below tests the raw sums and takes the select forms then)
+            draw = diffuse; sraw = specular;
+            diffuse = rt_min1_nn(diffuse) * a1;
+            specular = rt_min1_nn(specular) * a2;
+          } else {
           diffuse = min1(diffuse) * a1;
           specular = min1(specular) * a2;
+          }
 #ifdef RT_TESTING
           probe_li = li;
 #endif
@@ -827,6 +840,12 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 #endif
         v3 r = mk(0, 0, 0); double rlen = 0.0;
         // (with segs_left == 1 the child returns [0,0,0] at main.js:221 whatever its direction: skip it)
+#if !RT_STRICT
+        // LEAN: the mirror image in l instead of nq = +-l - d - 2 (d.nq) nq holds nq as a product of two, and negation is exact in every
+        // product, sum and fma on the way: the same bits for nq and -nq, without the three v_xor and six v_cndmask_b32 that restore the sign
+        // (the REFRACT kernels keep nq: the refraction reads its sign).  unit_go: the lanes that read r are those with rlen != 0 (go_r, below).
+        if constexpr (LEAN) { if (!UNI && a3 > 0.0 && segs_left > 1) r = unit_go(reflect(d, l), &rlen); } else
+#endif
         if (!UNI && a3 > 0.0 && segs_left > 1) r = unit(reflect(d, nq), &rlen);     // (UNI: decided against, for the wave, before the hit test)
         // A5 refraction direction
         v3 f = mk(0, 0, 0); double flen = 0.0;
@@ -862,6 +881,29 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 #endif
         if (!go_r && !go_f) {
           // children are absent or return [0,0,0] (segs == 0, main.js:221): x + 0*a == x
+          if constexpr (UNI) {
+            // The wave's eight clamps as one instruction each (rt_kernel_math.h: rt_min1_nn, rt_max_nn) if NO lane holds a NaN in a
+            // clamped quantity: the light loop's two sums and the three channel sums, all five added into one number that is NaN if
+            // any of them is (an inf - inf false alarm only takes the exact arm).  The ambient term col * a0 may be NaN in either arm.
+            double x[3];
+#pragma unroll
+            for (int c = 0; c < 3; c++) x[c] = col[c] * diffuse + col[c] * specular;
+            const double poison = (((draw + sraw) + x[0]) + x[1]) + x[2];
+            if (__ballot(poison != poison) == 0ull) {
+#pragma unroll
+              for (int c = 0; c < 3; c++) ret[c] = rt_max_nn(col[c] * a0, rt_min1_nn(x[c]));
+            } else {
+              // a NaN in the wave: the statements of the general path, from the raw sums (zero, and no product with a1 or a2, where the light loop did not run)
+#if defined(RT_TESTING) && defined(RT_ABLATE_LIGHT)
+              const bool lit = false;
+#else
+              const bool lit = (a1 > 0.0 || a2 > 0.0);
+#endif
+              const double d2 = lit ? min1(draw) * a1 : 0.0, s2 = lit ? min1(sraw) * a2 : 0.0;
+#pragma unroll
+              for (int c = 0; c < 3; c++) ret[c] = maxa(col[c] * a0, min1(col[c] * d2 + col[c] * s2));
+            }
+          } else
 #pragma unroll
           for (int c = 0; c < 3; c++) ret[c] = maxa(col[c] * a0, min1(col[c] * diffuse + col[c] * specular));
         } else if constexpr (FOLD_FORWARD) {
@@ -898,16 +940,25 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
             if (!map_valid) {
               acc[0] = coef;
 #pragma unroll
-              for (int c = 0; c < 3; c++) { acc[(1 + c) * T] = D[c]; acc[(4 + c) * T] = A[c]; acc[(7 + c) * T] = __builtin_fmax(A[c], 1.0); }
+              for (int c = 0; c < 3; c++) { acc[(1 + c) * T] = D[c]; acc[(4 + c) * T] = A[c]; acc[(7 + c) * T] = LEAN ? rt_max1_nn(A[c]) : __builtin_fmax(A[c], 1.0); }
             } else {
               const double S = acc[0];
 #pragma unroll
               for (int c = 0; c < 3; c++) {
                 const double O = acc[(1 + c) * T], LO = acc[(4 + c) * T], HI = acc[(7 + c) * T];
+                if constexpr (LEAN) {
+                  // (the same minNum / maxNum without a canonicalising v_max_f64 x, x in front of each value read from LDS: they are this
+                  // kernel's own results - rt_kernel_math.h)
+                  const double l2 = __builtin_fma(S, A[c], O), h2 = __builtin_fma(S, rt_max1_nn(A[c]), O);
+                  acc[(1 + c) * T] = __builtin_fma(S, D[c], O);
+                  acc[(4 + c) * T] = rt_max_nn(LO, rt_min_nn(HI, l2));
+                  acc[(7 + c) * T] = rt_max_nn(LO, rt_min_nn(HI, h2));
+                } else {
                 const double l2 = __builtin_fma(S, A[c], O), h2 = __builtin_fma(S, __builtin_fmax(A[c], 1.0), O);
                 acc[(1 + c) * T] = __builtin_fma(S, D[c], O);
                 acc[(4 + c) * T] = __builtin_fmax(LO, __builtin_fmin(HI, l2));
                 acc[(7 + c) * T] = __builtin_fmax(LO, __builtin_fmin(HI, h2));
+                }
               }
               acc[0] = S * coef;
             }
@@ -940,7 +991,10 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
         if (map_valid) {
           const double S = acc[0];
 #pragma unroll
-          for (int c = 0; c < 3; c++) ret[c] = __builtin_fmax(acc[(4 + c) * T], __builtin_fmin(acc[(7 + c) * T], __builtin_fma(S, ret[c], acc[(1 + c) * T])));
+          for (int c = 0; c < 3; c++) {
+            if constexpr (LEAN) ret[c] = rt_max_nn(acc[(4 + c) * T], rt_min_nn(acc[(7 + c) * T], __builtin_fma(S, ret[c], acc[(1 + c) * T])));
+            else ret[c] = __builtin_fmax(acc[(4 + c) * T], __builtin_fmin(acc[(7 + c) * T], __builtin_fma(S, ret[c], acc[(1 + c) * T])));
+          }
         }
         bool resumed = false;
         if constexpr (REFRACT) {
