@@ -128,7 +128,7 @@ struct rt_launch {
   const rt_sphere *objects;          // n_objects records of 192 B (materials; staged into LDS per workgroup)
   const rt_geom *geom;               // n_objects compact geometry records for the scalar-loaded loops
   const rt_geom *geom_cam;           // anchored at the camera: {o - cam, |o - cam|^2 - r2} per sphere
-  const void *lds_image;             // [materials (n_objects x rt_mtl) | 16 texture descriptors | cull rectangles if cull_in_lds]: the workgroup's LDS image
+  const void *lds_image;             // [materials (n_objects x rt_mtl) | 16 texture descriptors | cull rectangles if cull_in_lds]: the workgroup's LDS image (the few-sphere one-wave kernels stage the materials alone)
   const rt_geom *cull;               // per sphere {x_lo, x_hi, y_lo, y_hi}: bounds of X/D, Y/D of the pixels whose line meets it
   const void *shadow_grid;           // per-light shadow grids (rt_tables.cpp: build_shadow_grid), or NULL when the scene is small
   const void *bounce_table;          // per (sphere a ray starts on, direction cell): bit set of the spheres it can meet, or NULL

@@ -24,7 +24,8 @@
 //     intersection loops issue no vector memory and no LDS instruction;
 //   * the per-hit, per-lane data (material + sampler parameters of the sphere that lane hit, texture
 //     descriptors), the primary-ray cull rectangles and the 10-double state of the stackless recursion
-//     fold live in LDS; the LDS image is one contiguous block in HBM, loaded behind the ray generation;
+//     fold live in LDS; the LDS image is one contiguous block in HBM, loaded behind the ray generation (the few-sphere one-wave
+//     kernels stage its materials alone and read descriptors and rectangles where they lie: six waves per SIMD, MTL_ONLY below);
 //   * one-wave product kernels: a wave whose launch-table entry names ONE primary candidate and whose 64 rays all meet it (a floor
 //     block) has ONE material record: it is read with scalar loads from the image in HBM and the wave shades on the uniform-material
 //     path (trace_pixel, UNI) - no staging, no LDS access, no closest-hit selects, no node loop; the same statements otherwise;
@@ -74,6 +75,17 @@
 #define RT_WAVES_PER_EU 2
 #endif
 
+// ... by instantiation, in ONE place.  The few-sphere one-wave kernels: 6 (80 VGPRs; with their 6 400 bytes of LDS, 24 workgroups
+// per CU).  Measured on the headline by padding LDS (docs/EVIDENCE.md, "Six waves per SIMD"): 3 waves -27 %, 4 waves -11.5 %, 5 the
+// parent, 6 waves +5 % spill-free (the compiler's own 6-wave build, 12 spilled registers: +3.4 % with the LDS budget, -1.6 % without).
+// The reflection-only shadow-grid variants are held at 5 (96 VGPRs), the general kernel and the few-sphere four-wave forms are left
+// free: they fit 96 on their own, and forcing the general kernel to 5 waves spills into its loops (-9 %).
+constexpr unsigned rt_waves_per_eu(bool refract, bool grid, bool w1) {
+  return (w1 && !grid && !refract) ? (RT_WAVES_PER_EU > 6 ? RT_WAVES_PER_EU : 6)
+       : (refract || !grid)        ? RT_WAVES_PER_EU
+                                   : (RT_WAVES_PER_EU > 5 ? RT_WAVES_PER_EU : 5);
+}
+
 #define RT_INF __builtin_inf()
 
 namespace {
@@ -109,10 +121,8 @@ __device__ __forceinline__ uint32_t rt_row_down(uint32_t x) { return (uint32_t)_
 // form it was +0.5 %).  The general kernel keeps four waves (its 13-double fold state and image would leave a CU 16 one-wave
 // workgroups), and so does the peer-store path (whole 128-byte lines across the workgroup's waves).  profiles/r04_ab_log.md section 8.
 template <bool REFRACT, bool COUNT, bool SS2, bool GRID, bool W1 = false>
-// Register budget: the reflection-only kernel fits 96 VGPRs = 5 waves per SIMD on its own (measured: 4 waves cost 11 %,
-// more than 5 gain nothing); its shadow-grid variant is held there; the general kernel is left free (forcing it to 5
-// waves spills into its loops: -9 %).
-__global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ? RT_WAVES_PER_EU : (RT_WAVES_PER_EU > 5 ? RT_WAVES_PER_EU : 5))) rt_trace(const rt_launch L) {
+// Register budget: rt_waves_per_eu above.
+__global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, rt_waves_per_eu(REFRACT, GRID, W1)) rt_trace(const rt_launch L) {
   static_assert(!W1 || (!REFRACT && !COUNT && !RT_STRICT), "one-wave workgroups: the reflection-only product variants");
   [[maybe_unused]] constexpr uint32_t WG_WAVES = W1 ? 1u : RT_WG_THREADS / 64u;
   constexpr uint32_t KT = W1 ? 64u : RT_WG_THREADS;            // work-items of this workgroup
@@ -134,7 +144,12 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
   const uint32_t tex_words = 16u * 2u;               // RT_MAX_TEXTURES descriptors of 16 B
   const bool cull_lds_on = (!RT_STRICT && !COUNT) ? !GRID : (L.cull_in_lds != 0u);      // (see trace_pixel)
   const uint32_t cull_words = cull_lds_on ? L.n_objects * 4u : 0u;     // per-sphere screen rectangles of the primary-ray cull (few spheres)
-  const uint32_t image_words = mtl_words + tex_words + cull_words;
+  // The few-sphere one-wave kernels stage the MATERIALS alone (the image's first mtl_words): 8 spheres and the fold state are then
+  // 6 400 bytes, so that 24 one-wave workgroups - six waves per SIMD - fit a CU's 160 KiB, where the whole image (6 912 bytes) admits 22
+  // or 23.  Their texture descriptors are read where they lie in HBM (a textured hit's one 16-byte load, as in the many-sphere forms)
+  // and the cull's rectangles from L.cull at their one use (trace_pixel: only a block whose entry names no candidate runs the cull).
+  constexpr bool MTL_ONLY = W1 && !GRID;
+  const uint32_t image_words = MTL_ONLY ? mtl_words : mtl_words + tex_words + cull_words;
   // The reflection-only many-sphere variants read materials and texture descriptors WHERE THEY ARE (HBM / L2 / L1: a 32-bit offset from
   // a uniform base) instead of staging 10 KB of them per workgroup: LDS is then the fold state alone, 20 KB instead of 30 - a
   // workgroup's LDS stays allocated until its slowest wave ends, and with 30 KB (five per CU) the dear two thirds of a launch kept
@@ -171,7 +186,7 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
   constexpr bool UNI_OK = W1 && !REFRACT && !COUNT && !RT_STRICT && !(GRID && SS2);
   if constexpr (!UNI_OK) stage_issue(tid);
   const rt_mtl *mtl = IMAGE_IN_LDS ? (const rt_mtl *)lds_raw : (const rt_mtl *)L.lds_image;
-  const rt_texture_desc *tex = IMAGE_IN_LDS ? (const rt_texture_desc *)(lds_raw + mtl_words) : (const rt_texture_desc *)((const double *)L.lds_image + mtl_words);
+  const rt_texture_desc *tex = (IMAGE_IN_LDS && !MTL_ONLY) ? (const rt_texture_desc *)(lds_raw + mtl_words) : (const rt_texture_desc *)((const double *)L.lds_image + mtl_words);
   const rt_geom *cull_lds = (const rt_geom *)(lds_raw + mtl_words + tex_words);
   double *acc = lds_raw + lds_words + tid;   // fold state: 10 (general kernel: 13) x RT_WG_THREADS doubles, lane-major
   // Many spheres: the primary-ray cull's rectangle of sphere `lane` (the wave's first 64 spheres) comes straight from HBM / L2,
@@ -277,6 +292,7 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
                                                                          cull_lds, cull0, lane, 0.0, 0.0, 0.0, 0.0, o, ray, rgb, cnt, is_probe, P0.cand | (cell << 24));
       if (!uni_done) {
         uint32_t tid4 = threadIdx.x;
+        if constexpr (MTL_ONLY) tid4 = rt_lane_again(); else
         asm volatile("" : "+v"(tid4));                 // opaque: no address is kept in registers across the attempt
         stage_issue(tid4);
         stage_finish(tid4);
@@ -307,6 +323,7 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, ((REFRACT || !GRID) ?
 
   // ---- A10 RGBA8 store ----
   uint32_t tid2 = threadIdx.x;
+  if constexpr (W1 && !GRID) tid2 = rt_lane_again(); else
   asm volatile("" : "+v"(tid2));                       // opaque: recompute the pixel instead of keeping it live (see rt_pixel_of)
   const rt_pixel P1 = rt_pixel_of<SS2, W1>(L, tid2);
 #if !RT_STRICT

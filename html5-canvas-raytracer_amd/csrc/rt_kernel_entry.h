@@ -22,6 +22,16 @@ __device__ __forceinline__ uint32_t rt_entry_index() { return W1 ? (((blockIdx.x
 template <bool W1>
 __device__ __forceinline__ uint32_t rt_wave_of(uint32_t tid) { return W1 ? ((blockIdx.x >> 3) & 3u) : tid >> 6; }
 
+// The few-sphere one-wave kernels ask for the work-item id AGAIN where it is needed behind the primary test (a marked sample, the stars'
+// pixel index, the epilogue) WITHOUT keeping even the id's own register live across the trace: a one-wave workgroup's work-item id IS its
+// lane id, and v_mbcnt rebuilds that exactly under any exec mask (one of the 80 VGPRs that six waves per SIMD allow).  volatile: not merged
+// with an earlier one.  Every other kernel keeps its opaque copy of threadIdx.x at those places.
+__device__ __forceinline__ uint32_t rt_lane_again() {
+  uint32_t x;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(x));
+  return x;
+}
+
 #if RT_STRICT
 template <bool SS2, bool W1 = false>
 __device__ __forceinline__ rt_pixel rt_pixel_of(const rt_launch &L, uint32_t tid) {

@@ -142,6 +142,7 @@ __device__ __forceinline__ int rt_lvl(int lv) { return lv; }
             const bool bv = (zf && (FV) == 0.0 && (XV) == 0.0) || (__builtin_fabs((XV) - __builtin_rint(XV)) >= tol);    \
             if (!(bu & bv)) {                                                                                     /* NaN: marked */ \
               uint32_t t3 = threadIdx.x;                                                                          \
+              if constexpr (W1 && !GRID) t3 = rt_lane_again(); else                                               \
               asm volatile("" : "+v"(t3));                                                                        \
               rt_mark_append<SS2>(rt_pixel_of<SS2, W1>(L, t3));                                                        \
             }                                                                                                     \
@@ -232,7 +233,8 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
   const uint32_t enc = L.enclosing;                      // device index of the enclosing sphere (== NLOOP), or ~0u
   // where the primary-ray cull's rectangles are: the product kernels know at compile time (the host launches the many-sphere
   // variant exactly for the scenes whose LDS image leaves them out), the strict and counting kernels ask the launch record
-  const bool cull_lds_on = (!RT_STRICT && !COUNT) ? !GRID : (L.cull_in_lds != 0u);
+  // (the few-sphere one-wave kernels stage their materials alone - rt_kernel.hip, MTL_ONLY - and read the rectangles from L.cull here)
+  const bool cull_lds_on = (!RT_STRICT && !COUNT) ? (!GRID && !W1) : (L.cull_in_lds != 0u);
 #if RT_STRICT
   constexpr bool FOLD_FORWARD = false;
 #else
@@ -256,6 +258,10 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
   uint32_t segs_left = L.segs;
 #endif
   double ret[3] = {0.0, 0.0, 0.0};
+  // The few-sphere one-wave kernels (80 VGPRs, six waves per SIMD): a lane whose chain has ended parks its colour in its OWN fold-state
+  // slots O[0..2] - dead from then on: the lane evaluates no further node - and reads it back behind the node loop, so that the three
+  // doubles are not held in registers while the wave's other lanes go on through light loops.  A store and a load: the same bits.
+  constexpr bool PARK_RET = FOLD_FORWARD && W1 && !GRID && !REFRACT && !COUNT && !ITEM && !UNI;
 
   // ---- A2 / A3 candidates: the primary ray's here, a bounced ray's at the top of its node ----
   // A3: closest hit.  The winner is kept as (ht, hcode) with hcode = 2*index + inside, so a candidate costs one
@@ -313,7 +319,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
           } else if (cull_lds_on) {
             const rt_geom __attribute__((address_space(3))) *g = (const rt_geom __attribute__((address_space(3))) *)cull_lds + jj;
             c0 = g->ox; c1 = g->oy; c2 = g->oz; c3 = g->r2;
-          } else if (base != 0u) {
+          } else if (base != 0u || (W1 && !GRID)) {
             const rt_geom __attribute__((address_space(1))) *g = (const rt_geom __attribute__((address_space(1))) *)L.cull + jj;
             c0 = g->ox; c1 = g->oy; c2 = g->oz; c3 = g->r2;
           }
@@ -354,6 +360,8 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 
   if (segs_left != 0) {
     for (;;) {
+      // (every turn sets its own `ret`: nothing of it is carried from one turn into the next, or the parked colour would be held all the same)
+      if constexpr (PARK_RET) ret[0] = ret[1] = ret[2] = 0.0;
       // ---------------- evaluate one intersectWorld node (segs_left > 0 here) ----------------
       if (COUNT) cnt[0]++;
       if (!UNI && !searched) {                           // reflection / refraction rays: any origin, generic form
@@ -502,7 +510,9 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
         // (UNI: no lane is inside the candidate - a wave with one left before its hit test's ballot, above - so l is n)
         if constexpr (UNI) l = n;
         else l = inside ? mk(-n.x, -n.y, -n.z) : n;
-        const double a0 = m.albedo[0], a1 = m.albedo[1], a2 = m.albedo[2], a3 = m.albedo[3];
+        double a0 = m.albedo[0];                                        // (a0, a3: PARK_RET reads them again behind the lighting, below)
+        const double a1 = m.albedo[1], a2 = m.albedo[2];
+        double a3 = m.albedo[3];
         const double a4 = REFRACT ? m.albedo[4] : 0.0;
 #if !RT_STRICT && !defined(RT_ABLATE_QAMP)     /* (RT_ABLATE_QAMP: timing experiment, profiles/ab_build.sh) */
         // Q of this hit (see above): for a bounced ray's hit, and for a primary hit that will spawn a ray (ht is at hand here)
@@ -603,6 +613,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
           if constexpr (!ITEM) {
             f = blockIdx.z;                          // the frame of the batch
             uint32_t t3 = threadIdx.x;
+            if constexpr (W1 && !GRID) t3 = rt_lane_again(); else
             asm volatile("" : "+v"(t3));
             const rt_pixel P = rt_pixel_of<SS2, W1>(L, t3);
             sx = SS2 ? 2u * P.px + (P.sub & 1u) : P.px; sy = SS2 ? 2u * P.frow + (P.sub >> 1) : P.frow;
@@ -829,6 +840,16 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 #endif
         }
 
+        // (the few-sphere one-wave kernels) The ambient and the reflection coefficient are not needed by the lighting: they are read AGAIN
+        // here, the same two LDS words through an index the compiler cannot match with the first read, so that four registers less are
+        // held across the shadow scans.  A reload: the same bits.
+        if constexpr (PARK_RET) {
+          uint32_t hi2 = (uint32_t)hi;
+          asm volatile("" : "+v"(hi2));
+          const rt_mtl &m2 = *rt_mtl_at<false>(mtl, hi2);
+          a0 = m2.albedo[0]; a3 = m2.albedo[3];
+        }
+
         // ---- A4 / A5 directions ----
         // A4 reflection direction.  (Computed AFTER the lighting: in program order the reference does it before, but it
         // is pure, and placed here neither r nor f — nor n, which is l with its sign restored — occupies registers
@@ -1029,7 +1050,17 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
             resumed = true;
           }
         }
-        if (!resumed) break;
+        if (!resumed) {
+          if constexpr (PARK_RET) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) acc[(1 + c) * T] = ret[c];
+            // (the lane leaves HERE, through a test the compiler cannot decide: as the loop's plain exit the stores would move behind the
+            // loop, and the colour would wait for them in registers)
+            uint32_t fin = 1u;
+            asm volatile("" : "+v"(fin));
+            if (fin != 0u) break;
+          } else break;
+        }
       } else {
         // ---------------- return `ret` to the parents (post-order fold, main.js:268-278, :326-336) ----------------
         bool resumed = false;
@@ -1060,6 +1091,10 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
         }
         if (!resumed) break;
       }
+    }
+    if constexpr (PARK_RET) {
+#pragma unroll
+      for (int c = 0; c < 3; c++) ret[c] = acc[(1 + c) * 64u];
     }
   }
   rgb[0] = ret[0]; rgb[1] = ret[1]; rgb[2] = ret[2];

@@ -287,10 +287,12 @@ int launched(int err) { return err != 0 ? fail(RT_ERR_DEVICE, "kernel launch: %s
 
 // Dynamic LDS of a variant's workgroup: the scene's LDS image and the fold state (10 doubles per lane, the general kernel 13; the strict
 // kernels one slot, the scatter store's tile).  The reflection-only many-sphere variants keep only the fold state in LDS (rt_kernel.hip:
-// IMAGE_IN_LDS); one-wave workgroups have 64 lanes.
+// IMAGE_IN_LDS); one-wave workgroups have 64 lanes, and the few-sphere ones stage the image's materials alone (rt_kernel.hip: MTL_ONLY):
+// 8 spheres are 1 280 + 5 120 = 6 400 bytes, 24 workgroups in a CU's 160 KiB (DESIGN section 4 has the count per scene size).
 unsigned lds_for(const rt_scene_dev *s, rt_trace_variant v, unsigned lds_pad) {
   if (v.strict) return s->lds_bytes + lds_pad + RT_WG_THREADS * 8u;
   const unsigned fold = (v.refract ? 13u : 10u) * (v.one_wave ? 64u : RT_WG_THREADS) * 8u;
+  if (v.one_wave && !v.grid) return s->hd.n_objects * (unsigned)sizeof(rt_mtl) + lds_pad + fold;
   return ((v.grid && !v.refract) ? 0u : s->lds_bytes) + lds_pad + fold;
 }
 
@@ -607,6 +609,27 @@ int render_batch_impl(rt_scene_dev *s, uint32_t w, uint32_t h, const rt_tiles *t
   return RT_OK;
 }
 }  // namespace
+
+// How many workgroups of its trace kernel a CU holds at once for a colour launch of this resident scene, by the runtime's own count
+// (hipOccupancyMaxActiveBlocksPerMultiprocessor: the kernel's registers and the launch's dynamic LDS), and that LDS size.  The variant
+// and the LDS size are worked out as product_launch does: `four_waves` - the first frame from a moved camera (rt_launch::four_waves).
+// Nothing is launched.  (tests/test_gpu_occupancy.py: six waves per SIMD are 24 one-wave workgroups.)
+extern "C" int rt_scene_trace_occupancy(rt_scene_dev *s, int four_waves, int *out_workgroups_per_cu, uint32_t *out_lds_bytes) {
+  if (!s || !out_workgroups_per_cu) return fail(RT_ERR_INVALID, "rt_scene_trace_occupancy: NULL argument");
+  if (int rc = ensure_device(s->device)) return rc;
+  HIP_TRY(hipSetDevice(G.dev[s->device].hip_id));
+  const uint32_t ss = s->hd.supersample;
+  if (ss > 2u) return fail(RT_ERR_UNSUPPORTED, "rt_scene_trace_occupancy: supersample %u renders on the sample grid", ss);
+  const rt_trace_variant v = rt_trace_variant_of(strict_scene(s), false, s->refract, false, ss == 2u, s->cull_in_lds, false, four_waves != 0);
+  const void *f = (v.strict ? rt_kernel_trace_strict : rt_kernel_trace_fast)(v);
+  if (!f) return fail(RT_ERR_DEVICE, "rt_scene_trace_occupancy: no kernel for the variant");
+  const unsigned lds = lds_for(s, v, 0u);
+  int n = 0;
+  HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, v.one_wave ? 64 : (int)RT_WG_THREADS, lds));
+  *out_workgroups_per_cu = n;
+  if (out_lds_bytes) *out_lds_bytes = lds;
+  return RT_OK;
+}
 
 // ------------------------------------------------------------------------------------ adaptive supersampling (rt_adaptive.hip)
 // k x k samples only where the frame has edges (include/rt_hip.h: rt_render_adaptive_device).  Three launches follow each other on the

@@ -265,6 +265,7 @@ ABI = {
     "rt_scene_free": (None, [C.c_void_p]),
     "rt_scene_set_camera": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "rt_scene_set_stars_seed": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_scene_trace_occupancy": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "rt_scene_set_objects": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rt_scene_set_lights": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_void_p]),
     "rt_scene_set_light_intensity": (C.c_int, [C.c_void_p, C.c_double]),
@@ -460,6 +461,13 @@ class Renderer:
         if not (isinstance(seed, int) and not isinstance(seed, bool) and 0 <= seed < 2 ** 32):
             raise ValueError("stars seed must be an integer in [0, 2^32)")
         _check(self.lib, self.lib.rt_scene_set_stars_seed(self.handle, seed), "rt_scene_set_stars_seed")
+
+    def trace_occupancy(self, four_waves=False):
+        """(workgroups of the scene's trace kernel that one compute unit holds at once, dynamic LDS bytes per workgroup) for a colour launch
+        of the resident scene, by the HIP runtime's occupancy count; `four_waves`: the first frame from a moved camera.  Launches nothing."""
+        n, lds = C.c_int(), C.c_uint32()
+        _check(self.lib, self.lib.rt_scene_trace_occupancy(self.handle, 1 if four_waves else 0, C.byref(n), C.byref(lds)), "rt_scene_trace_occupancy")
+        return n.value, lds.value
 
     def set_objects(self, objects, first=0, stream=None):
         """Replace spheres [first, first + len(objects)) of the resident scene (scene-dict objects, or their packed records from

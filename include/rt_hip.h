@@ -238,6 +238,12 @@ int rt_scene_set_camera(rt_scene_dev *scene, const double origin[3], const doubl
  * rt_scene_set_camera.  Any value is valid. */
 int rt_scene_set_stars_seed(rt_scene_dev *scene, uint32_t seed);
 
+/* How many workgroups of its trace kernel one compute unit holds at once for a colour launch of this resident scene, by the HIP
+ * runtime's count for the kernel's registers and the launch's dynamic LDS (nothing is launched).  four_waves != 0: the first frame
+ * from a moved camera, which runs four-wave workgroups.  out_lds_bytes (may be NULL): the launch's dynamic LDS per workgroup.
+ * RT_ERR_UNSUPPORTED for supersample 3 / 4 (rendered on the sample grid). */
+int rt_scene_trace_occupancy(rt_scene_dev *scene, int four_waves, int *out_workgroups_per_cu, uint32_t *out_lds_bytes);
+
 /* Replace the sphere records [first, first + count) of a resident scene, in blob order (the reference's objects are plain arrays a
  * page may change between redraws, main.js:180-201): every field of a record may change - origin, r2, material, sampler, texture
  * index; n_objects, lights, textures, camera and seed stay.  Blob order stays the semantics (closest hit: strict <, the first wins).
