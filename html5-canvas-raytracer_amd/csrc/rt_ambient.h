@@ -13,7 +13,6 @@
 #define RT_AMBIENT_WG 256u              // receivers per workgroup
 #define RT_AMBIENT_MAX_SAMPLES 1024u
 #define RT_AMBIENT_MAX_DIRS 65536u
-#define RT_AMBIENT_CHUNK (1ull << 18)   // receivers per chunk of the host forms
 
 // what a receiver's hit record gives every one of its samples: the origin, the facing normal with its frame, the sphere left out
 struct amb_receiver {

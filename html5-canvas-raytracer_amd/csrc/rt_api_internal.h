@@ -2,19 +2,25 @@
 // scene (rt_scene_dev) and the few functions that cross units.  Not part of the ABI.
 //   rt_scene_sync.h  the stream ordering of a resident scene's launches, moves and texel edits (rules R1-R6) and the events, side stream
 //                  and pinned rings it owns for it: header-only, HIP's API and nothing of the project
+//   rt_chunked.h   how a host form pushes its work through one set of device buffers in chunks (lists: elements, views: whole rows): the
+//                  driver, the device buffers of a call, the clocks of a call that reports rt_stats: header-only, HIP's API, rt_stats, the error codes
 //   rt_api.hip     lifetime, errors, device state, the scratch guard and the per-variant scratch figures, the host-logic probes, memory helpers, IPC
 //   rt_scene.hip   upload and moves of a resident scene (the generation pipeline), its texel edits (rt_texels.hip), its launch decisions and launch
 //                  tables, and the launch prologue (enter_launch)
 //   rt_launch.hip  the launches: colour (the launch record, then the strict launch or the product launch and rt_retrace), supersampling,
 //                  compact bands, adaptive supersampling (rt_adaptive.hip), primary hits and picking, ray lists, occlusion queries
-//   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, rt_render_hits / rt_pick, and the host lists that go
-//                  through device buffers in chunks (rt_trace_rays, rt_occlusion and their binned forms, rt_shade_rays, rt_relight_rays), rt_trace_rays_wavefront / rt_trace_rays_soft
+//   rt_frame.hip   rt_render and its one-GPU and multi-GPU plans, RCCL, de-interleave, the prologue and epilogue of every host form (host_call),
+//                  rt_render_hits / rt_pick, and the host lists that go through device buffers in chunks (rt_trace_rays, rt_occlusion and
+//                  their binned forms, rt_shade_rays, rt_relight_rays), rt_trace_rays_wavefront / rt_trace_rays_soft
 //   rt_nodes_api.hip  the wavefront form's device entry points: one level of nodes, the next level's ray list, the fold (rt_nodes.hip)
-//   rt_views_api.hip  views: validation, the panorama's tables, the host probe, the generator's launch (rt_views.hip), the traces of a whole view
+//   rt_views_api.hip  views: validation, the panorama's tables, the host probe, the generator's launch (rt_views.hip), the traces of a whole view,
+//                  and what every unit that traces a view shares: the size test, the workspace check, the upload of the panorama's tables
 //   rt_ambient_api.hip  ambient occlusion: validation, the cosine table, the host probe, the launches of rt_ambient.hip, the host forms
 //   rt_lighting_api.hip  sampled lights: validation, the offset table, the host probe, the launch of rt_lighting.hip, the host forms
 //   rt_relight_api.hip  relit nodes: the argument check, the launch of rt_relight.hip and its device entry point (the host forms are rt_frame.hip's)
 //   rt_soft_api.hip  the soft trace in one launch: the argument check, the launch of rt_soft.hip, its device entry points (a list, a view) and host forms
+// A host form is its argument checks, host_call::begin, rows for the chunk driver (chunked_list_call, chunked_view_call below) and a
+// step of launches; the band loop of a view is for_bands.
 // Which kernel a launch runs is one value (rt_device.h: rt_trace_variant), worked out once per launch; the two builds of rt_kernel.hip map
 // it to a kernel (rt_kernel_trace_fast / rt_kernel_trace_strict), and the declarations below are all the host sees of them.
 #ifndef RT_API_INTERNAL_H
@@ -46,6 +52,7 @@
 #include "rt_texels.h"
 #include "rt_adaptive.h"
 #include "rt_scene_sync.h"
+#include "rt_chunked.h"
 
 // per build of rt_kernel.hip (product, strict): the variant's kernel (NULL: not this build's) and its launch
 extern "C" const void *rt_kernel_trace_fast(rt_trace_variant);
@@ -66,13 +73,6 @@ extern thread_local char g_err[512];
 #else
 #define RT_TEST_ENV(name) ((const char *)nullptr)
 #endif
-
-int fail(int code, const char *fmt, ...);
-#define HIP_TRY(expr)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail(RT_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_));     \
-  } while (0)
 
 struct device_state {
   int hip_id = -1;
@@ -132,50 +132,6 @@ struct launch_geom { uint32_t tiles_x, rows_per_wg, rb_per_tile; double proj_w, 
 launch_geom launch_geometry(double fov_deg, uint32_t w, uint32_t h, uint32_t ss, uint32_t tile_rows);
 
 using device_mem = owned<void *, hipFree>;   // (rt_scene_sync.h; pinned_mem: hipHostFree)
-
-// GPU time between start() and stop() on a stream; the events are released on every way out
-struct event_timer {
-  hipEvent_t a = nullptr, b = nullptr;
-  event_timer() = default;
-  event_timer(const event_timer &) = delete;
-  ~event_timer() { release(); }
-  void release() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); a = b = nullptr; }
-  hipError_t start(hipStream_t stream) {
-    hipError_t e = hipEventCreate(&a);
-    if (e == hipSuccess) e = hipEventCreate(&b);
-    if (e == hipSuccess) e = hipEventRecord(a, stream);
-    return e;
-  }
-  hipError_t stop(hipStream_t stream) { return hipEventRecord(b, stream); }
-  hipError_t elapsed(float *ms) const { return hipEventElapsedTime(ms, a, b); }
-};
-
-// The clock of a call that may report rt_stats: host time from its construction, GPU time on `stream` between start() and finish().
-// Without `stats` (most calls) it creates no event and waits for nothing.
-struct stats_clock {
-  const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
-  event_timer timer;
-  hipStream_t stream = nullptr;
-  double host_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); }
-  int start(const rt_stats *stats, hipStream_t on) {
-    stream = on;
-    if (stats) HIP_TRY(timer.start(stream));
-    return RT_OK;
-  }
-  // waits for the stream; *stats = {kernel_ms, pixels, total_ms}, every other field zero
-  int finish(rt_stats *stats, uint64_t pixels) {
-    if (!stats) return RT_OK;
-    HIP_TRY(timer.stop(stream));
-    HIP_TRY(hipEventSynchronize(timer.b));
-    float ms = 0.f;
-    HIP_TRY(timer.elapsed(&ms));
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = ms;
-    stats->pixels = pixels;
-    stats->total_ms = host_ms();
-    return RT_OK;
-  }
-};
 
 }  // namespace rt_api
 
@@ -287,7 +243,7 @@ struct rt_scene_dev {
   double flag_tol;               // RT_FLAG_T1 x the largest sampler frequency of the scene (texture width / height, checker frequencies): rt_device.h
 };
 
-// elements per chunk of the host lists that go through device buffers (rt_frame.hip, rt_soft_api.hip)
+// units per chunk of every host form that goes through device buffers (rt_chunked.h): elements of a list, pixels of a view's whole rows
 #define RT_RAY_CHUNK (1u << 18)
 
 namespace rt_api {
@@ -337,6 +293,8 @@ int spawn_launch(uint32_t n, uint32_t base, const rt_node *d_nodes, const uint32
                  uint32_t *d_child_path, int32_t *d_links, uint32_t *d_count, void *d_work, hipStream_t stream);
 int fold_launch(uint32_t n, const rt_node *d_nodes, const int32_t *d_links, const double *d_child_rgb, double *d_rgb, uint8_t *d_rgba, hipStream_t stream);
 
+// rt_ambient_api.hip: the number of receivers of a device list (ambient occlusion, sampled lights)
+int receiver_count_check(uint64_t n, const char *what);
 // rt_lighting_api.hip: the checks of a lighting description whose table is DEVICE memory (NULL only at light_radius 0), and the table of a
 // host form going up (nothing is allocated at light_radius 0)
 int lighting_device_check(const struct rt_lighting *a, const double *d_offs, const char *what);
@@ -353,11 +311,101 @@ int relight_launch(rt_scene_dev *s, const struct rt_lighting &a, const double *d
 // descriptor, the padding between two textures).  `a` is a blob rt_scene_validate has accepted, `b` any `bytes` bytes.
 struct texel_edit { uint32_t texture, first_row, rows; };
 int texel_edits(const uint8_t *a, const uint8_t *b, size_t bytes, std::vector<texel_edit> *out);
-// rt_frame.hip: rt_render's resident scene of `device` for a blob (scene_for: the resident one, edited where the blob differs only in
-// what an edit reaches, else a fresh upload).  Under G.mu.
-int resident_scene(int device, const void *blob, size_t bytes, rt_scene_dev **out);
 // rt_frame.hip: RCCL's communicators are destroyed (rt_shutdown)
 void release_rccl();
+
+// rt_frame.hip: the prologue and epilogue of a host form, behind its argument checks.  begin: rt_init has run, G.mu is held until the
+// call object goes, the clock runs, the blob is device 0's resident scene `s` (scene_for: rt_render's resident one, edited where the
+// blob differs only in what an edit reaches, else a fresh upload), and device 0 is current with its stream `stream`.
+// end: *stats (if any) = {kernel_ms, pixels, total_ms since begin}, every other field zero.
+struct host_call {
+  std::unique_lock<std::mutex> lock;
+  std::chrono::steady_clock::time_point t_begin;
+  rt_scene_dev *s = nullptr;
+  hipStream_t stream = nullptr;
+  int begin(const void *blob, size_t bytes);
+  void end(rt_stats *stats, double kernel_ms, uint64_t pixels) const;
+};
+
+// launches on `stream` between the two events of a clock: *st (if any) = {their GPU time, pixels, the host's time}
+template <typename Launches> int timed(hipStream_t stream, rt_stats *st, uint64_t pixels, Launches launches) {
+  stats_clock clock;
+  if (int rc = clock.start(st, stream)) return rc;
+  if (int rc = launches()) return rc;
+  return clock.finish(st, pixels);
+}
+
+// A binned chunk (rt_rays_order.hip): the two SCRATCH rows of a call over n elements - the chunk's order and the ordering's workspace;
+// none when not binned - and the step: the timed ordering of m rays into d_order (NULL: not binned), then launch(d_order, st), whose
+// GPU time the ordering's is added to.
+inline void order_rows(bool binned, uint64_t n, chunk_row out[2]) {
+  out[0] = row_scratch(binned ? sizeof(uint32_t) : 0u);
+  out[1] = row_scratch(0u, binned ? rt_rays_order_work_bytes(units_per_chunk(n, RT_RAY_CHUNK)) : 0u);
+}
+template <typename Launch>
+int ordered_step(uint32_t m, const double *d_rays, void *d_order, void *d_work, hipStream_t stream, rt_stats *st, Launch launch) {
+  double order_ms = 0.0;
+  if (d_order) {
+    stats_clock clock;
+    if (int rc = clock.start(st, stream)) return rc;
+    if (int rc = order_rays_launch(m, d_rays, (uint32_t *)d_order, d_work, stream)) return rc;
+    if (int rc = clock.finish(st, m)) return rc;
+    if (st) order_ms = st->kernel_ms;
+  }
+  if (int rc = launch((const uint32_t *)d_order, st)) return rc;
+  if (st) st->kernel_ms += order_ms;
+  return RT_OK;
+}
+
+// A list's host form: the chunk driver with unit = element, so element i of the list keeps pix = i (the chunk's base travels to the
+// launch).  `list`: the list's arrays, first the one a binned call orders (the ray records).  launch(m, base, d_rows, d_order, st):
+// elements [base, base + m), in the list's order (d_order NULL) or in that of m entries; kernel_ms is the sum over the chunks, the
+// orderings included.  Behind call.begin; ends the call.
+template <typename Launch>
+int chunked_list_call(const host_call &call, uint64_t n, const chunk_row *list, int n_rows, bool binned, rt_stats *stats, Launch launch) {
+  chunk_row rows[RT_CHUNK_ROWS];
+  if (n_rows + 2 > RT_CHUNK_ROWS) return fail(RT_ERR_INVALID, "a list call has at most %d arrays", RT_CHUNK_ROWS - 2);
+  for (int i = 0; i < n_rows; i++) rows[i] = list[i];
+  order_rows(binned, n, rows + n_rows);
+  double kernel_ms = 0.0;
+  const int rc = chunked_call(call.stream, n, RT_RAY_CHUNK, rows, n_rows + 2, stats ? &kernel_ms : nullptr,
+                              [&](uint64_t base, uint64_t m, void *const *d, rt_stats *st) {
+                                return ordered_step((uint32_t)m, (const double *)d[0], d[n_rows], d[n_rows + 1], call.stream, st,
+                                                    [&](const uint32_t *d_order, rt_stats *st2) { return launch((uint32_t)m, base, d, d_order, st2); });
+                              });
+  if (rc) return rc;
+  call.end(stats, kernel_ms, n);
+  return RT_OK;
+}
+
+// ---- views (rt_views_api.hip), for every unit that traces one: the size a view may have; the workspace of a device entry point, which
+// holds whole rows of pixel_bytes per pixel (`noun`: what a row is one of, in the entry point's own words) -> *band_rows, the rows of a
+// band; the panorama's tables of a host form going up (n_tables of them back to back; nothing for another model) -> *dv, the view with
+// device pointers, whose memory is `mem`'s; and the first half of a band of receivers: the rays of rows [y, y + m) into d_rays and their
+// hit records into d_hits
+bool view_size_ok(uint32_t w, uint32_t h);
+int view_work_check(const void *d_work, size_t work_bytes, uint32_t w, uint32_t h, uint32_t pixel_bytes, const char *noun, const char *what, uint32_t *band_rows);
+int view_upload_tables(const rt_view &v, uint32_t w, uint32_t h, uint32_t n_tables, hipStream_t stream, device_bufs<2> *mem, rt_view *dv);
+int view_band_hits(rt_scene_dev *s, const rt_view *v, uint32_t w, uint32_t h, uint32_t y, uint32_t m, double *d_rays, rt_hit *d_hits, hipStream_t stream);
+// rows [row0, row_end) in bands of at most band_rows: fn(y, m) -> an error code
+template <typename Band> int for_bands(uint32_t row0, uint32_t row_end, uint32_t band_rows, Band fn) {
+  for (uint32_t y = row0; y < row_end; y += band_rows)
+    if (int rc = fn(y, row_end - y < band_rows ? row_end - y : band_rows)) return rc;
+  return RT_OK;
+}
+// A view's host form: the chunk driver with unit = one row of w pixels (a row's `each`: w x its bytes per pixel).  bands(y, m, d_rows):
+// the launches of rows [y, y + m), timed as one stretch.  Behind call.begin; ends the call.
+template <typename Bands>
+int chunked_view_call(const host_call &call, uint32_t w, uint32_t h, const chunk_row *rows, int n_rows, rt_stats *stats, Bands bands) {
+  double kernel_ms = 0.0;
+  const int rc = chunked_call(call.stream, h, rows_per_chunk(RT_RAY_CHUNK, w, h), rows, n_rows, stats ? &kernel_ms : nullptr,
+                              [&](uint64_t y, uint64_t m, void *const *d, rt_stats *st) {
+                                return timed(call.stream, st, m * w, [&] { return bands((uint32_t)y, (uint32_t)m, d); });
+                              });
+  if (rc) return rc;
+  call.end(stats, kernel_ms, (uint64_t)w * h);
+  return RT_OK;
+}
 }  // namespace rt_api
 
 #endif

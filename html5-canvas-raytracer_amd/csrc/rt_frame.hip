@@ -1,7 +1,7 @@
 // rt_frame.hip — rt_render(width, height, scene) and its kin (rt_render_progressive, rt_render_hits, rt_pick; rt_trace_rays, rt_occlusion
-// and their binned forms, rt_shade_rays and rt_relight_rays, which share one chunked list call; rt_trace_rays_wavefront and
-// rt_trace_rays_soft, which share one level loop): the resident scene
-// per device (scene_for), the one-GPU plans (banded copy-out, stores straight into a pinned frame) and the single-process multi-GPU
+// and their binned forms, rt_shade_rays and rt_relight_rays, which are rows and a step for the chunked list call of rt_api_internal.h;
+// rt_trace_rays_wavefront and rt_trace_rays_soft, which share one level loop): the resident scene
+// per device (scene_for), the prologue and epilogue of every host form (host_call), the one-GPU plans (banded copy-out, stores straight into a pinned frame) and the single-process multi-GPU
 // frame (interleaved row tiles stored straight into GPU 0's frame over xGMI; fallback: RGB24 bands + one RCCL gather + de-interleave).
 
 #include "rt_api_internal.h"
@@ -245,19 +245,31 @@ int ensure_frame(int device, size_t bytes) {
 }
 }  // namespace
 
-int rt_api::resident_scene(int device, const void *blob, size_t bytes, rt_scene_dev **out) { return scene_for(device, blob, bytes, out); }
-
 void rt_api::release_rccl() {
   if (G.comms_ready) { for (size_t g = 0; g < G.dev.size(); g++) if (G.comms[g]) NCCL.destroy(G.comms[g]); G.comms_ready = false; }
 }
 
+// ------------------------------------------------------------------------------------ a host form's prologue and epilogue
+int rt_api::host_call::begin(const void *blob, size_t bytes) {
+  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
+  lock = std::unique_lock<std::mutex>(G.mu);
+  t_begin = std::chrono::steady_clock::now();
+  if (int rc = scene_for(0, blob, bytes, &s)) return rc;
+  if (int rc = ensure_device(0)) return rc;
+  stream = G.dev[0].stream;
+  return RT_OK;
+}
+
+void rt_api::host_call::end(rt_stats *stats, double kernel_ms, uint64_t pixels) const {
+  if (!stats) return;
+  memset(stats, 0, sizeof *stats);
+  stats->kernel_ms = kernel_ms;
+  stats->pixels = pixels;
+  stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+}
+
 // ------------------------------------------------------------------------------------ render(width,height,scene)
 namespace {
-// device buffers of one call, released on every way out
-template <int N> struct device_bufs {
-  void *p[N] = {};
-  ~device_bufs() { for (void *q : p) if (q) (void)hipFree(q); }
-};
 int render_to_host(const void *blob, size_t bytes, uint32_t w, uint32_t h, uint8_t *out_rgba, uint32_t flags, rt_stats *stats,
                    uint32_t want_bands, rt_band_callback on_band, void *user);
 int g_last_plan = 0;      // how the last rt_render put its frame together: 0 one GPU (banded copy-out), 1 peer stores, 2 ncclGather (or its emulation), 3 one GPU storing into the pinned frame
@@ -295,13 +307,8 @@ extern "C" int rt_render_hits(const void *blob, size_t bytes, uint32_t w, uint32
   if (rc) return rc;
   const uint32_t k = ((const rt_scene_header *)blob)->supersample;
   if ((rc = hits_frame_check(w, h, k, "rt_render_hits"))) return rc;
-  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
-  std::lock_guard<std::mutex> lk(G.mu);
-  const auto t_begin = std::chrono::steady_clock::now();
-  rt_scene_dev *s = nullptr;
-  if ((rc = scene_for(0, blob, bytes, &s))) return rc;
-  if ((rc = ensure_device(0))) return rc;
-  device_state &D = G.dev[0];
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
   const size_t samples = (size_t)k * w * k * h;
   device_bufs<3> mem;
   const size_t each[3] = {sizeof(int32_t), sizeof(double), 3u * sizeof(float)};
@@ -310,13 +317,10 @@ extern "C" int rt_render_hits(const void *blob, size_t bytes, uint32_t w, uint32
   const rt_hit_buffers db = {(int32_t *)mem.p[0], (double *)mem.p[1], (float *)mem.p[2]};
   const rt_tiles whole = {h, 0u, 1u, 1u};
   rt_stats st;
-  if ((rc = rt_render_hits_device(s, w, h, &whole, &db, D.stream, &st))) return rc;
-  for (int i = 0; i < 3; i++) if (host[i]) HIP_TRY(hipMemcpyAsync(host[i], mem.p[i], samples * each[i], hipMemcpyDeviceToHost, D.stream));
-  HIP_TRY(hipStreamSynchronize(D.stream));
-  if (stats) {
-    *stats = st;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
+  if ((rc = rt_render_hits_device(call.s, w, h, &whole, &db, call.stream, &st))) return rc;
+  for (int i = 0; i < 3; i++) if (host[i]) HIP_TRY(hipMemcpyAsync(host[i], mem.p[i], samples * each[i], hipMemcpyDeviceToHost, call.stream));
+  HIP_TRY(hipStreamSynchronize(call.stream));
+  call.end(stats, st.kernel_ms, st.pixels);
   return RT_OK;
 }
 
@@ -328,30 +332,22 @@ extern "C" int rt_render_adaptive(const void *blob, size_t bytes, uint32_t w, ui
   if (rc) return rc;
   const size_t work_bytes = rt_adaptive_work_bytes(w, h);
   if (!work_bytes) return fail(RT_ERR_INVALID, "rt_render_adaptive: frame size %ux%u not in 1..32768", w, h);
-  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
-  std::lock_guard<std::mutex> lk(G.mu);
-  const auto t_begin = std::chrono::steady_clock::now();
-  rt_scene_dev *s = nullptr;
-  if ((rc = scene_for(0, blob, bytes, &s))) return rc;
-  if ((rc = ensure_device(0))) return rc;
-  device_state &D = G.dev[0];
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
   const size_t pixels = (size_t)w * h;
   device_bufs<3> mem;                                  // the frame, the workspace, the mask
   HIP_TRY(hipMalloc(&mem.p[0], pixels * 4u));
   HIP_TRY(hipMalloc(&mem.p[1], work_bytes));
   if (out_mask) HIP_TRY(hipMalloc(&mem.p[2], pixels));
   rt_stats st;
-  if ((rc = rt_render_adaptive_device(s, w, h, k, threshold, mem.p[0], (uint8_t *)mem.p[2], mem.p[1], work_bytes, D.stream, flags, &st))) return rc;
+  if ((rc = rt_render_adaptive_device(call.s, w, h, k, threshold, mem.p[0], (uint8_t *)mem.p[2], mem.p[1], work_bytes, call.stream, flags, &st))) return rc;
   uint32_t n_refined = 0;
-  HIP_TRY(hipMemcpyAsync(out_rgba, mem.p[0], pixels * 4u, hipMemcpyDeviceToHost, D.stream));
-  HIP_TRY(hipMemcpyAsync(&n_refined, mem.p[1], sizeof n_refined, hipMemcpyDeviceToHost, D.stream));
-  if (out_mask) HIP_TRY(hipMemcpyAsync(out_mask, mem.p[2], pixels, hipMemcpyDeviceToHost, D.stream));
-  HIP_TRY(hipStreamSynchronize(D.stream));
+  HIP_TRY(hipMemcpyAsync(out_rgba, mem.p[0], pixels * 4u, hipMemcpyDeviceToHost, call.stream));
+  HIP_TRY(hipMemcpyAsync(&n_refined, mem.p[1], sizeof n_refined, hipMemcpyDeviceToHost, call.stream));
+  if (out_mask) HIP_TRY(hipMemcpyAsync(out_mask, mem.p[2], pixels, hipMemcpyDeviceToHost, call.stream));
+  HIP_TRY(hipStreamSynchronize(call.stream));
   if (refined) *refined = n_refined;
-  if (stats) {
-    *stats = st;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
+  call.end(stats, st.kernel_ms, st.pixels);
   return RT_OK;
 }
 
@@ -367,75 +363,27 @@ extern "C" int rt_pick(const void *blob, size_t bytes, uint32_t w, uint32_t h, u
 }
 
 // A list in host memory - rays (rt_trace_rays) or segments (rt_occlusion) - goes through rt_render's resident scene in chunks of
-// RT_RAY_CHUNK elements and one set of device buffers, so the device memory of a call does not grow with n (element i of the list keeps
-// pix = i: the chunk's base travels to the launch).  `rows`: the list's arrays, the ray records first; a row without a host pointer
-// gets no buffer.  Per chunk: the inputs are copied in, `binned`: the chunk is ordered on the GPU (rt_rays_order.hip; the order buffer
-// and the workspace are the call's, like its other device memory), `launch` runs it, the outputs are copied back, and the stream is
-// drained.  Synchronous; kernel_ms is the sum over the chunks, the orderings included.
+// RT_RAY_CHUNK elements and one set of device buffers (rt_api_internal.h: chunked_list_call).  A row without a host pointer gets no
+// buffer.  `binned`: each chunk is ordered on the GPU first (rt_rays_order.hip).  Synchronous.
 namespace {
-struct list_row { const void *host; size_t each; bool out; };       // one array of the list: element size, and which way it is copied
-constexpr int RT_LIST_ROWS = 6;
-// launch(scene, m, base, d, d_order, stream, st): elements [base, base + m), whose arrays are the device buffers d[row] (NULL: none),
-// in the list's order (d_order NULL) or in that of m entries
-template <typename Launch>
-int chunked_list_call(const void *blob, size_t bytes, uint64_t n, const list_row *rows, int n_rows, bool binned, rt_stats *stats, Launch launch) {
-  if (n_rows > RT_LIST_ROWS) return fail(RT_ERR_INVALID, "a list call has at most %d arrays", RT_LIST_ROWS);
-  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
-  std::lock_guard<std::mutex> lk(G.mu);
-  const auto t_begin = std::chrono::steady_clock::now();
-  rt_scene_dev *s = nullptr;
-  int rc = scene_for(0, blob, bytes, &s);
-  if (rc) return rc;
-  if ((rc = ensure_device(0))) return rc;
-  device_state &D = G.dev[0];
-  const size_t chunk = n < RT_RAY_CHUNK ? (size_t)n : RT_RAY_CHUNK;
-  device_bufs<RT_LIST_ROWS + 2> mem;                     // the rows, then the chunk's order and the ordering's workspace
-  void **d_order = &mem.p[RT_LIST_ROWS], **d_work = &mem.p[RT_LIST_ROWS + 1];
-  for (int i = 0; i < n_rows; i++) if (rows[i].host) HIP_TRY(hipMalloc(&mem.p[i], chunk * rows[i].each));
-  if (binned) {
-    HIP_TRY(hipMalloc(d_order, chunk * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(d_work, rt_rays_order_work_bytes(chunk)));
-  }
-  double kernel_ms = 0.0;
-  for (uint64_t base = 0; base < n; base += chunk) {
-    const size_t m = n - base < chunk ? (size_t)(n - base) : chunk;
-    for (int i = 0; i < n_rows; i++)
-      if (rows[i].host && !rows[i].out) HIP_TRY(hipMemcpyAsync(mem.p[i], (const uint8_t *)rows[i].host + base * rows[i].each, m * rows[i].each, hipMemcpyHostToDevice, D.stream));
-    rt_stats st;
-    if (binned) {
-      stats_clock step;
-      if ((rc = step.start(stats, D.stream))) return rc;
-      if ((rc = order_rays_launch((uint32_t)m, (const double *)mem.p[0], (uint32_t *)*d_order, *d_work, D.stream))) return rc;
-      if ((rc = step.finish(stats ? &st : nullptr, m))) return rc;
-      if (stats) kernel_ms += st.kernel_ms;
-    }
-    if ((rc = launch(s, (uint32_t)m, (uint32_t)base, mem.p, (const uint32_t *)*d_order, D.stream, stats ? &st : nullptr))) return rc;
-    if (stats) kernel_ms += st.kernel_ms;
-    for (int i = 0; i < n_rows; i++)
-      if (rows[i].host && rows[i].out) HIP_TRY(hipMemcpyAsync((uint8_t *)rows[i].host + base * rows[i].each, mem.p[i], m * rows[i].each, hipMemcpyDeviceToHost, D.stream));
-    HIP_TRY(hipStreamSynchronize(D.stream));
-  }
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = kernel_ms;
-    stats->pixels = n;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
-  return RT_OK;
-}
-
 // intersectWorld for a list of rays in host memory (`binned`: rt_trace_rays_binned)
 int trace_rays_to_host(const void *blob, size_t bytes, uint64_t n, const double *rays, uint32_t segs, const rt_ray_outputs *ho, rt_stats *stats,
                        bool binned, const char *what) {
   int rc = rt_scene_validate(blob, bytes);
   if (rc) return rc;
   if ((rc = rays_check(n, rays, segs, ho, what))) return rc;
-  const list_row rows[4] = {{rays, 6u * sizeof(double), false}, {ho->rgb, 3u * sizeof(double), true}, {ho->rgba, 4u, true}, {ho->hits, sizeof(rt_hit), true}};
-  return chunked_list_call(blob, bytes, n, rows, 4, binned, stats,
-                           [segs](rt_scene_dev *s, uint32_t m, uint32_t base, void *const *d, const uint32_t *d_order, hipStream_t stream, rt_stats *st) {
-                             const rt_ray_outputs dout = {(double *)d[1], (uint8_t *)d[2], (rt_hit *)d[3]};
-                             return trace_rays_launch(s, m, base, (const double *)d[0], d_order, segs, dout, stream, st);
-                           });
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
+  const chunk_row rows[4] = {row_in(rays, 6u * sizeof(double)), row_out(ho->rgb, 3u * sizeof(double)), row_out(ho->rgba, 4u), row_out(ho->hits, sizeof(rt_hit))};
+  return chunked_list_call(call, n, rows, 4, binned, stats, [&](uint32_t m, uint64_t base, void *const *d, const uint32_t *d_order, rt_stats *st) {
+    const rt_ray_outputs dout = {(double *)d[1], (uint8_t *)d[2], (rt_hit *)d[3]};
+    return trace_rays_launch(call.s, m, (uint32_t)base, (const double *)d[0], d_order, segs, dout, call.stream, st);
+  });
+}
+
+// the arrays of a list of rays that is shaded into nodes
+void shade_rows(const double *rays, const uint32_t *pix, const uint32_t *path, rt_node *nodes, chunk_row rows[4]) {
+  rows[0] = row_in(rays, 6u * sizeof(double)); rows[1] = row_in(pix, sizeof(uint32_t)); rows[2] = row_in(path, sizeof(uint32_t)); rows[3] = row_out(nodes, sizeof(rt_node));
 }
 }  // namespace
 
@@ -454,15 +402,17 @@ extern "C" int rt_shade_rays(const void *blob, size_t bytes, uint64_t n, const d
   int rc = rt_scene_validate(blob, bytes);
   if (rc) return rc;
   if ((rc = shade_check(n, rays, nullptr, pix, path, nodes, "rt_shade_rays"))) return rc;
-  const list_row rows[4] = {{rays, 6u * sizeof(double), false}, {pix, sizeof(uint32_t), false}, {path, sizeof(uint32_t), false}, {nodes, sizeof(rt_node), true}};
-  return chunked_list_call(blob, bytes, n, rows, 4, binned != 0, stats,
-                           [](rt_scene_dev *s, uint32_t m, uint32_t base, void *const *d, const uint32_t *d_order, hipStream_t stream, rt_stats *st) {
-                             return shade_launch(s, m, base, (const double *)d[0], d_order, (const uint32_t *)d[1], (const uint32_t *)d[2], (rt_node *)d[3], stream, st);
-                           });
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
+  chunk_row rows[4];
+  shade_rows(rays, pix, path, nodes, rows);
+  return chunked_list_call(call, n, rows, 4, binned != 0, stats, [&](uint32_t m, uint64_t base, void *const *d, const uint32_t *d_order, rt_stats *st) {
+    return shade_launch(call.s, m, (uint32_t)base, (const double *)d[0], d_order, (const uint32_t *)d[1], (const uint32_t *)d[2], (rt_node *)d[3], call.stream, st);
+  });
 }
 
-// rt_shade_rays followed by the relight of each chunk (rt_relight.hip): the table goes up with the first chunk, and a chunk's base is
-// added to the description's where no pix travels, so a list gives the bytes of one launch however it is cut
+// rt_shade_rays followed by the relight of each chunk (rt_relight.hip): the table goes up once, and a chunk's base is added to the
+// description's where no pix travels, so a list gives the bytes of one launch however it is cut
 extern "C" int rt_relight_rays(const void *blob, size_t bytes, const struct rt_lighting *a, const double *offs, uint64_t n, const double *rays,
                                const uint32_t *pix, const uint32_t *path, int binned, rt_node *nodes, rt_stats *stats) {
   const char *what = "rt_relight_rays";
@@ -470,25 +420,22 @@ extern "C" int rt_relight_rays(const void *blob, size_t bytes, const struct rt_l
   if (rc) return rc;
   if ((rc = rt_lighting_validate(a, offs))) return rc;
   if ((rc = shade_check(n, rays, nullptr, pix, path, nodes, what))) return rc;
-  const list_row rows[4] = {{rays, 6u * sizeof(double), false}, {pix, sizeof(uint32_t), false}, {path, sizeof(uint32_t), false}, {nodes, sizeof(rt_node), true}};
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
   device_mem d_offs;                                     // (released behind the call, whose every chunk has been waited for)
-  bool table_up = false;
-  return chunked_list_call(blob, bytes, n, rows, 4, binned != 0, stats,
-                           [&](rt_scene_dev *s, uint32_t m, uint32_t base, void *const *d, const uint32_t *d_order, hipStream_t stream, rt_stats *st) {
-                             if (!table_up) {
-                               if (int e = lighting_upload_offs(*a, offs, &d_offs, stream)) return e;
-                               table_up = true;
-                             }
-                             const uint32_t *d_pix = (const uint32_t *)d[1];
-                             if (int e = shade_launch(s, m, base, (const double *)d[0], d_order, d_pix, (const uint32_t *)d[2], (rt_node *)d[3], stream, st)) return e;
-                             struct rt_lighting ac = *a;
-                             if (!d_pix) ac.base = a->base + base;         // node i of this chunk is node base + i of the list
-                             rt_stats relit;
-                             if (int e = relight_launch(s, ac, (const double *)d_offs.h, m, (const double *)d[0], d_order, d_pix, (rt_node *)d[3], stream, st ? &relit : nullptr))
-                               return e;
-                             if (st) st->kernel_ms += relit.kernel_ms;
-                             return (int)RT_OK;
-                           });
+  if ((rc = lighting_upload_offs(*a, offs, &d_offs, call.stream))) return rc;
+  chunk_row rows[4];
+  shade_rows(rays, pix, path, nodes, rows);
+  return chunked_list_call(call, n, rows, 4, binned != 0, stats, [&](uint32_t m, uint64_t base, void *const *d, const uint32_t *d_order, rt_stats *st) {
+    const uint32_t *d_pix = (const uint32_t *)d[1];
+    if (int e = shade_launch(call.s, m, (uint32_t)base, (const double *)d[0], d_order, d_pix, (const uint32_t *)d[2], (rt_node *)d[3], call.stream, st)) return e;
+    struct rt_lighting ac = *a;
+    if (!d_pix) ac.base = a->base + base;                // node i of this chunk is node base + i of the list
+    rt_stats relit;
+    if (int e = relight_launch(call.s, ac, (const double *)d_offs.h, m, (const double *)d[0], d_order, d_pix, (rt_node *)d[3], call.stream, st ? &relit : nullptr)) return e;
+    if (st) st->kernel_ms += relit.kernel_ms;
+    return (int)RT_OK;
+  });
 }
 
 // rt_trace_rays through the wavefront form (include/rt_hip.h: rt_trace_rays_wavefront): per chunk of the list, level after level is
@@ -618,19 +565,14 @@ int wavefront_to_host(const void *blob, size_t bytes, const struct rt_lighting *
   if (a && (rc = rt_lighting_validate(a, offs))) return rc;
   if ((rc = rays_check(n, rays, segs, ho, what))) return rc;
   if (ho->hits) return fail(RT_ERR_INVALID, "%s: no hit records (level 1 of rt_scene_shade_rays_device holds them)", what);
-  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
-  std::lock_guard<std::mutex> lk(G.mu);
-  const auto t_begin = std::chrono::steady_clock::now();
-  rt_scene_dev *s = nullptr;
-  if ((rc = scene_for(0, blob, bytes, &s))) return rc;
-  if ((rc = ensure_device(0))) return rc;
-  device_state &D = G.dev[0];
-  const uint32_t depth = segs ? segs : s->hd.segs;
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
+  const uint32_t depth = segs ? segs : call.s->hd.segs;
   device_mem d_offs;                                     // the table goes up once per call
   relight_step step = {a, nullptr, levels};
   const bool relit = a && levels != 0u && depth != 0u;
   if (relit) {
-    if ((rc = lighting_upload_offs(*a, offs, &d_offs, D.stream))) return rc;
+    if ((rc = lighting_upload_offs(*a, offs, &d_offs, call.stream))) return rc;
     step.d_offs = (const double *)d_offs.h;
   }
   if (level_counts) memset(level_counts, 0, RT_MAX_SEGS * sizeof(uint64_t));
@@ -649,16 +591,11 @@ int wavefront_to_host(const void *blob, size_t bytes, const struct rt_lighting *
   for (uint64_t base = 0; depth != 0u && base < n;) {
     const uint32_t m = n - base < chunk ? (uint32_t)(n - base) : chunk;
     bool overflow = false;
-    if ((rc = wavefront_chunk(s, D.stream, rays, base, m, depth, order_levels != 0, relit ? &step : nullptr, ho, stats != nullptr, &kernel_ms, level_counts, &overflow))) return rc;
+    if ((rc = wavefront_chunk(call.s, call.stream, rays, base, m, depth, order_levels != 0, relit ? &step : nullptr, ho, stats != nullptr, &kernel_ms, level_counts, &overflow))) return rc;
     if (overflow) { chunk = m / 2u; continue; }            // (m > 1; a chunk of one ray always fits)
     base += m;
   }
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = kernel_ms;
-    stats->pixels = n;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
+  call.end(stats, kernel_ms, n);
   return RT_OK;
 }
 }  // namespace
@@ -682,14 +619,15 @@ int occlusion_to_host(const void *blob, size_t bytes, uint64_t n, const double *
   int rc = rt_scene_validate(blob, bytes);
   if (rc) return rc;
   if ((rc = occlusion_check(n, rays, hi, ho, what))) return rc;
-  const list_row rows[6] = {{rays, 6u * sizeof(double), false}, {hi ? hi->length : nullptr, sizeof(double), false}, {hi ? hi->intensity : nullptr, sizeof(double), false},
-                            {hi ? hi->skip : nullptr, sizeof(int32_t), false}, {ho->intensity, sizeof(double), true}, {ho->blocker, sizeof(int32_t), true}};
-  return chunked_list_call(blob, bytes, n, rows, 6, binned, stats,
-                           [](rt_scene_dev *s, uint32_t m, uint32_t, void *const *d, const uint32_t *d_order, hipStream_t stream, rt_stats *st) {
-                             const rt_occlusion_inputs din = {(const double *)d[1], (const double *)d[2], (const int32_t *)d[3]};
-                             const rt_occlusion_outputs dout = {(double *)d[4], (int32_t *)d[5]};
-                             return occlusion_launch(s, m, (const double *)d[0], d_order, din, dout, stream, st);
-                           });
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
+  const chunk_row rows[6] = {row_in(rays, 6u * sizeof(double)), row_in(hi ? hi->length : nullptr, sizeof(double)), row_in(hi ? hi->intensity : nullptr, sizeof(double)),
+                             row_in(hi ? hi->skip : nullptr, sizeof(int32_t)), row_out(ho->intensity, sizeof(double)), row_out(ho->blocker, sizeof(int32_t))};
+  return chunked_list_call(call, n, rows, 6, binned, stats, [&](uint32_t m, uint64_t, void *const *d, const uint32_t *d_order, rt_stats *st) {
+    const rt_occlusion_inputs din = {(const double *)d[1], (const double *)d[2], (const int32_t *)d[3]};
+    const rt_occlusion_outputs dout = {(double *)d[4], (int32_t *)d[5]};
+    return occlusion_launch(call.s, m, (const double *)d[0], d_order, din, dout, call.stream, st);
+  });
 }
 }  // namespace
 

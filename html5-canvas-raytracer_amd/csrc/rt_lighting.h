@@ -12,7 +12,6 @@
 #define RT_LIGHTING_WG 256u              // receivers per workgroup
 #define RT_LIGHTING_MAX_SAMPLES 1024u
 #define RT_LIGHTING_MAX_OFFS 65536u
-#define RT_LIGHTING_CHUNK (1ull << 18)   // receivers per chunk of the host forms
 
 // what a receiver's hit record gives every one of its segments: amb_receiver without its frame, which no light reads
 struct lgt_receiver {

@@ -2,8 +2,8 @@
 // the launch of rt_lighting.hip's kernel, and the host forms: a list of receivers through device buffers in chunks, and a whole view
 // whose rays, hit records and scans never leave the device.  The kernel reads the scene's current spheres, epsilon, lights and light
 // intensity; the last two are the host copies every launch carries by value, taken under launch_mu with the sphere block
-// (rt_scene_set_lights and rt_scene_set_light_intensity write them under it).  The band loop of a view is a second one beside
-// rt_ambient_api.hip's: that one's launches stay exactly as they are.
+// (rt_scene_set_lights and rt_scene_set_light_intensity write them under it).  The chunk driver, the prologue and the band loop are
+// the ones every host form shares (rt_api_internal.h); a band's first half - rays, hit records - is rt_views_api.hip's view_band_hits.
 #include "rt_api_internal.h"
 #include "rt_lighting.h"
 
@@ -28,10 +28,6 @@ int lighting_table_check(const struct rt_lighting *a, const double *offs, const 
     if (!std::isfinite(offs[3u * (size_t)e]) || !std::isfinite(offs[3u * (size_t)e + 1u]) || !std::isfinite(offs[3u * (size_t)e + 2u]))
       return fail(RT_ERR_INVALID, "%s: offset %u has a non-finite component", what, e);
   return RT_OK;
-}
-
-int lighting_count_check(uint64_t n, const char *what) {
-  return (n == 0 || n >= (1ull << 31)) ? fail(RT_ERR_INVALID, "%s: n %llu not in 1..2^31 - 1", what, (unsigned long long)n) : RT_OK;
 }
 
 int lighting_outputs_check(const rt_lighting_outputs *out, const char *what) {
@@ -81,8 +77,6 @@ int lighting_launch(rt_scene_dev *s, const struct rt_lighting &a, const double *
 
 constexpr uint32_t RT_LIGHTING_VIEW_BAND_BYTES = 128u;    // per pixel of a band: the ray 48, its hit record 80
 
-bool lighting_view_size_ok(uint32_t w, uint32_t h) { return w != 0 && h != 0 && (uint64_t)w * h < (1ull << 31); }
-
 // The view's rows [row0, row_end) in bands of at most band_rows: per band the rays (rt_views.hip), their hit records (rt_hits.hip) and the
 // fused kernel with base = a.base + y * w, so that pixel i = y * w + x is receiver i whatever the band.  The outputs' first record is
 // pixel out_row0 * w.  One stream: every launch comes behind the one that wrote what it reads.  (The view was checked by the caller.)
@@ -90,41 +84,22 @@ int lighting_view_bands(rt_scene_dev *s, const rt_view *v, uint32_t w, uint32_t 
                         uint32_t row_end, uint32_t band_rows, const rt_lighting_outputs &out, uint32_t out_row0, void *d_work, hipStream_t stream) {
   double *rays = (double *)d_work;
   rt_hit *hits = (rt_hit *)(rays + 6u * ((size_t)band_rows * w));
-  for (uint32_t y = row0; y < row_end; y += band_rows) {
-    const uint32_t m = row_end - y < band_rows ? row_end - y : band_rows;
-    if (int rc = rt_view_rays_device(s->device, v, w, h, y, m, rays, (void *)stream)) return rc;
-    const rt_ray_outputs into = {nullptr, nullptr, hits};
-    if (int rc = trace_rays_launch(s, m * w, y * w, rays, nullptr, 1u, into, stream, nullptr)) return rc;
+  return for_bands(row0, row_end, band_rows, [&](uint32_t y, uint32_t m) {
+    if (int rc = view_band_hits(s, v, w, h, y, m, rays, hits, stream)) return rc;
     struct rt_lighting ab = a;
     ab.base = a.base + (uint64_t)y * w;
     const size_t at = (size_t)(y - out_row0) * w;
     const rt_lighting_outputs band = {out.diffuse ? out.diffuse + at : nullptr, out.intensity ? out.intensity + at : nullptr, out.lit ? out.lit + at : nullptr,
                                       out.rgba ? out.rgba + at : nullptr};
-    if (int rc = lighting_launch(s, ab, d_offs, m * w, hits, nullptr, band, stream, nullptr)) return rc;
-  }
-  return RT_OK;
+    return lighting_launch(s, ab, d_offs, m * w, hits, nullptr, band, stream, nullptr);
+  });
 }
 
-// the outputs of one chunk in device memory, and their way back
-struct chunk_outputs {
-  device_mem diffuse, intensity, lit, rgba;
-  int alloc(const rt_lighting_outputs &ho, size_t chunk) {
-    if (ho.diffuse) HIP_TRY(hipMalloc(&diffuse.h, chunk * 8u));
-    if (ho.intensity) HIP_TRY(hipMalloc(&intensity.h, chunk * 8u));
-    if (ho.lit) HIP_TRY(hipMalloc(&lit.h, chunk * 8u));
-    if (ho.rgba) HIP_TRY(hipMalloc(&rgba.h, chunk * 4u));
-    return RT_OK;
-  }
-  rt_lighting_outputs dev() const { return rt_lighting_outputs{(double *)diffuse.h, (double *)intensity.h, (double *)lit.h, (uint32_t *)rgba.h}; }
-  int copy_back(const rt_lighting_outputs &ho, size_t at, size_t n, hipStream_t stream) {
-    if (ho.diffuse) HIP_TRY(hipMemcpyAsync(ho.diffuse + at, diffuse.h, n * 8u, hipMemcpyDeviceToHost, stream));
-    if (ho.intensity) HIP_TRY(hipMemcpyAsync(ho.intensity + at, intensity.h, n * 8u, hipMemcpyDeviceToHost, stream));
-    if (ho.lit) HIP_TRY(hipMemcpyAsync(ho.lit + at, lit.h, n * 8u, hipMemcpyDeviceToHost, stream));
-    if (ho.rgba) HIP_TRY(hipMemcpyAsync(ho.rgba + at, rgba.h, n * 4u, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return RT_OK;
-  }
-};
+// the outputs of a host form as the rows of a chunked call: `each` records per unit (a list: 1, a view: w), and a chunk's on the device
+void output_rows(const rt_lighting_outputs &ho, size_t each, chunk_row *rows) {
+  rows[0] = row_out(ho.diffuse, each * 8u); rows[1] = row_out(ho.intensity, each * 8u); rows[2] = row_out(ho.lit, each * 8u); rows[3] = row_out(ho.rgba, each * 4u);
+}
+rt_lighting_outputs device_outputs(void *const *d) { return rt_lighting_outputs{(double *)d[0], (double *)d[1], (double *)d[2], (uint32_t *)d[3]}; }
 
 // the table of a host form in device memory: not allocated where it is not read
 int upload_offs(const struct rt_lighting &a, const double *offs, device_mem *d_offs, hipStream_t stream) {
@@ -158,7 +133,7 @@ extern "C" int rt_lighting_segments(const struct rt_lighting *a, const double *o
   int rc = lighting_table_check(a, offs, what);
   if (rc) return rc;
   if (n_lights < 1u || n_lights > RT_MAX_LIGHTS || !lights_xyz) return fail(RT_ERR_INVALID, "%s: n_lights %u not in 1..%u, or NULL lights", what, n_lights, RT_MAX_LIGHTS);
-  if ((rc = lighting_count_check(n, what))) return rc;
+  if ((rc = receiver_count_check(n, what))) return rc;
   if (sample >= a->n_samples) return fail(RT_ERR_INVALID, "%s: sample %u not below n_samples %u", what, sample, a->n_samples);
   if (light >= n_lights) return fail(RT_ERR_INVALID, "%s: light %u not below n_lights %u", what, light, n_lights);
   if (!hits || !out_rays) return fail(RT_ERR_INVALID, "%s: NULL hit records or ray output", what);
@@ -175,7 +150,7 @@ extern "C" int rt_scene_lighting_device(rt_scene_dev *s, const struct rt_lightin
   const char *what = "rt_scene_lighting_device";
   int rc = lighting_check(a, what);
   if (rc) return rc;
-  if ((rc = lighting_count_check(n, what))) return rc;
+  if ((rc = receiver_count_check(n, what))) return rc;
   if ((rc = lighting_offs_check(*a, d_offs, what))) return rc;
   if (!d_hits || ((uintptr_t)d_hits & 7u)) return fail(RT_ERR_INVALID, "%s: NULL or misaligned hit records (8 bytes)", what);
   if ((rc = lighting_outputs_check(d_out, what))) return rc;
@@ -195,42 +170,22 @@ extern "C" int rt_lighting(const void *blob, size_t bytes, const struct rt_light
   if (n == 0) return fail(RT_ERR_INVALID, "%s: n is 0", what);
   if (!hits) return fail(RT_ERR_INVALID, "%s: NULL hit records", what);
   if ((rc = lighting_outputs_check(ho, what))) return rc;
-  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
-  std::lock_guard<std::mutex> lk(G.mu);
-  stats_clock clock;
-  rt_scene_dev *s = nullptr;
-  if ((rc = resident_scene(0, blob, bytes, &s))) return rc;
-  if ((rc = ensure_device(0))) return rc;
-  hipStream_t stream = G.dev[0].stream;
-  const size_t chunk = n < RT_LIGHTING_CHUNK ? (size_t)n : (size_t)RT_LIGHTING_CHUNK;
-  device_mem d_hits, d_offs;         // of one chunk; the table (released on every way out)
-  chunk_outputs d_out;
-  HIP_TRY(hipMalloc(&d_hits.h, chunk * sizeof(rt_hit)));
-  if ((rc = upload_offs(*a, offs, &d_offs, stream))) return rc;
-  if ((rc = d_out.alloc(*ho, chunk))) return rc;
-  double kernel_ms = 0.0;
-  for (uint64_t at = 0; at < n; at += RT_LIGHTING_CHUNK) {
-    const size_t m = n - at < RT_LIGHTING_CHUNK ? (size_t)(n - at) : (size_t)RT_LIGHTING_CHUNK;
-    HIP_TRY(hipMemcpyAsync(d_hits.h, hits + at, m * sizeof(rt_hit), hipMemcpyHostToDevice, stream));
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
+  device_mem d_offs;                 // the table (released behind the call, whose every chunk has been waited for)
+  if ((rc = upload_offs(*a, offs, &d_offs, call.stream))) return rc;
+  chunk_row rows[5] = {row_in(hits, sizeof(rt_hit))};
+  output_rows(*ho, 1u, rows + 1);
+  return chunked_list_call(call, n, rows, 5, false, stats, [&](uint32_t m, uint64_t at, void *const *d, const uint32_t *, rt_stats *st) {
     struct rt_lighting ac = *a;
     ac.base = a->base + at;          // receiver `at + i` of the list is receiver i of this chunk
-    rt_stats st;
-    if ((rc = lighting_launch(s, ac, (const double *)d_offs.h, (uint32_t)m, (const rt_hit *)d_hits.h, nullptr, d_out.dev(), stream, stats ? &st : nullptr))) return rc;
-    if (stats) kernel_ms += st.kernel_ms;
-    if ((rc = d_out.copy_back(*ho, (size_t)at, m, stream))) return rc;
-  }
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = kernel_ms;
-    stats->pixels = n;
-    stats->total_ms = clock.host_ms();
-  }
-  return RT_OK;
+    return lighting_launch(call.s, ac, (const double *)d_offs.h, m, (const rt_hit *)d[0], nullptr, device_outputs(d + 1), call.stream, st);
+  });
 }
 
 extern "C" size_t rt_lighting_view_work_bytes(uint32_t w, uint32_t h) {
   // the whole view in one band, as rt_ambient_view_work_bytes
-  return lighting_view_size_ok(w, h) ? (size_t)w * h * RT_LIGHTING_VIEW_BAND_BYTES : 0;
+  return view_size_ok(w, h) ? (size_t)w * h * RT_LIGHTING_VIEW_BAND_BYTES : 0;
 }
 
 extern "C" int rt_scene_lighting_view_device(rt_scene_dev *s, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting *a, const double *d_offs,
@@ -242,17 +197,11 @@ extern "C" int rt_scene_lighting_view_device(rt_scene_dev *s, const rt_view *v, 
   if ((rc = lighting_check(a, what))) return rc;
   if ((rc = lighting_offs_check(*a, d_offs, what))) return rc;
   if ((rc = lighting_outputs_check(d_out, what))) return rc;
-  if (!d_work || ((uintptr_t)d_work & 15u)) return fail(RT_ERR_INVALID, "%s: NULL or misaligned workspace (16 bytes)", what);
-  const uint64_t row_bytes = (uint64_t)w * RT_LIGHTING_VIEW_BAND_BYTES;
-  if (work_bytes < row_bytes) return fail(RT_ERR_INVALID, "%s: work_bytes %llu below one row of a band, %llu", what, (unsigned long long)work_bytes, (unsigned long long)row_bytes);
+  uint32_t band_rows = 0;
+  if ((rc = view_work_check(d_work, work_bytes, w, h, RT_LIGHTING_VIEW_BAND_BYTES, "a band", what, &band_rows))) return rc;
   hipStream_t stream = nullptr;
   if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
-  const uint64_t fit = work_bytes / row_bytes;
-  const uint32_t band_rows = fit < h ? (uint32_t)fit : h;
-  stats_clock clock;
-  if ((rc = clock.start(stats, stream))) return rc;
-  if ((rc = lighting_view_bands(s, v, w, h, *a, d_offs, 0u, h, band_rows, *d_out, 0u, d_work, stream))) return rc;
-  return clock.finish(stats, (uint64_t)w * h);
+  return timed(stream, stats, (uint64_t)w * h, [&] { return lighting_view_bands(s, v, w, h, *a, d_offs, 0u, h, band_rows, *d_out, 0u, d_work, stream); });
 }
 
 extern "C" int rt_lighting_view(const void *blob, size_t bytes, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting *a, const double *offs,
@@ -263,47 +212,16 @@ extern "C" int rt_lighting_view(const void *blob, size_t bytes, const rt_view *v
   if ((rc = rt_view_validate(v, w, h))) return rc;
   if ((rc = lighting_table_check(a, offs, what))) return rc;
   if ((rc = lighting_outputs_check(ho, what))) return rc;
-  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
-  std::lock_guard<std::mutex> lk(G.mu);
-  stats_clock clock;
-  rt_scene_dev *s = nullptr;
-  if ((rc = resident_scene(0, blob, bytes, &s))) return rc;
-  if ((rc = ensure_device(0))) return rc;
-  hipStream_t stream = G.dev[0].stream;
-  // chunks of whole rows of at most RT_LIGHTING_CHUNK pixels; a longer row is its own chunk
-  uint64_t chunk_rows = RT_LIGHTING_CHUNK / w;
-  if (chunk_rows < 1u) chunk_rows = 1u;
-  if (chunk_rows > h) chunk_rows = h;
-  const size_t chunk = (size_t)chunk_rows * w;
-  device_mem d_work, d_offs, d_lon, d_lat;      // of one chunk; the table; the panorama's tables (released on every way out)
-  chunk_outputs d_out;
-  HIP_TRY(hipMalloc(&d_work.h, chunk * RT_LIGHTING_VIEW_BAND_BYTES));
-  if ((rc = upload_offs(*a, offs, &d_offs, stream))) return rc;
-  if ((rc = d_out.alloc(*ho, chunk))) return rc;
-  rt_view dv = *v;
-  if (v->model == RT_VIEW_EQUIRECT) {
-    HIP_TRY(hipMalloc(&d_lon.h, (size_t)w * 16u));
-    HIP_TRY(hipMalloc(&d_lat.h, (size_t)h * 16u));
-    HIP_TRY(hipMemcpyAsync(d_lon.h, v->lon, (size_t)w * 16u, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_lat.h, v->lat, (size_t)h * 16u, hipMemcpyHostToDevice, stream));
-    dv.lon = (const double *)d_lon.h; dv.lat = (const double *)d_lat.h;
-  }
-  double kernel_ms = 0.0;
-  for (uint32_t y = 0; y < h; y += (uint32_t)chunk_rows) {
-    const uint32_t m = h - y < chunk_rows ? h - y : (uint32_t)chunk_rows;
-    stats_clock step;
-    rt_stats st;
-    if ((rc = step.start(stats, stream))) return rc;
-    if ((rc = lighting_view_bands(s, &dv, w, h, *a, (const double *)d_offs.h, y, y + m, m, d_out.dev(), y, d_work.h, stream))) return rc;
-    if ((rc = step.finish(stats ? &st : nullptr, (uint64_t)m * w))) return rc;
-    if (stats) kernel_ms += st.kernel_ms;
-    if ((rc = d_out.copy_back(*ho, (size_t)y * w, (size_t)m * w, stream))) return rc;
-  }
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = kernel_ms;
-    stats->pixels = (uint64_t)w * h;
-    stats->total_ms = clock.host_ms();
-  }
-  return RT_OK;
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
+  device_mem d_offs;                 // the table
+  device_bufs<2> tables;             // the panorama's
+  rt_view dv;
+  if ((rc = upload_offs(*a, offs, &d_offs, call.stream))) return rc;
+  if ((rc = view_upload_tables(*v, w, h, 1u, call.stream, &tables, &dv))) return rc;
+  chunk_row rows[5] = {row_scratch((size_t)w * RT_LIGHTING_VIEW_BAND_BYTES)};
+  output_rows(*ho, w, rows + 1);
+  return chunked_view_call(call, w, h, rows, 5, stats, [&](uint32_t y, uint32_t m, void *const *d) {
+    return lighting_view_bands(call.s, &dv, w, h, *a, (const double *)d_offs.h, y, y + m, m, device_outputs(d + 1), y, d[0], call.stream);
+  });
 }

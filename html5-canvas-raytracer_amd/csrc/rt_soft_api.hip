@@ -4,6 +4,7 @@
 // rt_nodes.hip's shade kernel and rt_relight.hip read - the scene's current spheres, epsilon, lights, light intensity, miss colour,
 // textures and stars seed, taken under launch_mu - so it comes behind the scene's preparation like every other launch.  It keeps a
 // stack in scratch memory: its figure goes through scratch_guard before the launch.
+// The host forms are rows and a step for the chunk drivers of rt_api_internal.h.
 // A view is traced in bands of whole rows as rt_views_api.hip's trace_view_bands does it: a band's rays are generated into the
 // workspace (rt_view_rays_device) and traced with pix_base = y * w, so pixel i = y * w + x is ray i whatever the band.
 #include "rt_api_internal.h"
@@ -88,20 +89,16 @@ int soft_launch(rt_scene_dev *s, const struct rt_lighting &a, const double *d_of
   return clock.finish(stats, n);
 }
 
-bool soft_view_size_ok(uint32_t w, uint32_t h) { return w != 0 && h != 0 && (uint64_t)w * h < (1ull << 31); }
-
 // The view's rows [row0, row_end) in bands of at most band_rows: generated into d_work and traced with pix_base = y * w into the outputs'
 // records from row out_row0 on.  One stream: a band's generation comes behind the trace that read the workspace before it.
 int soft_view_bands(rt_scene_dev *s, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting &a, const double *d_offs, uint32_t levels, uint32_t row0,
                     uint32_t row_end, uint32_t band_rows, uint32_t segs, const rt_ray_outputs &out, uint32_t out_row0, double *d_work, hipStream_t stream) {
-  for (uint32_t y = row0; y < row_end; y += band_rows) {
-    const uint32_t m = row_end - y < band_rows ? row_end - y : band_rows;
+  return for_bands(row0, row_end, band_rows, [&](uint32_t y, uint32_t m) {
     if (int rc = rt_view_rays_device(s->device, v, w, h, y, m, d_work, (void *)stream)) return rc;
     const size_t at = (size_t)(y - out_row0) * w;         // of the band's first record in the outputs
     const rt_ray_outputs band = {out.rgb ? out.rgb + 3u * at : nullptr, out.rgba ? out.rgba + 4u * at : nullptr, nullptr};
-    if (int rc = soft_launch(s, a, d_offs, levels, m * w, d_work, nullptr, y * w, segs, band, stream, nullptr)) return rc;
-  }
-  return RT_OK;
+    return soft_launch(s, a, d_offs, levels, m * w, d_work, nullptr, y * w, segs, band, stream, nullptr);
+  });
 }
 }  // namespace
 
@@ -122,7 +119,7 @@ extern "C" int rt_scene_trace_rays_soft_device(rt_scene_dev *s, const struct rt_
 
 extern "C" size_t rt_soft_view_work_bytes(uint32_t w, uint32_t h) {
   // the whole view in one band, as rt_view_work_bytes
-  return soft_view_size_ok(w, h) ? (size_t)w * h * 48u : 0;
+  return view_size_ok(w, h) ? (size_t)w * h * 48u : 0;
 }
 
 extern "C" int rt_scene_trace_view_soft_device(rt_scene_dev *s, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting *a, const double *d_offs,
@@ -133,23 +130,18 @@ extern "C" int rt_scene_trace_view_soft_device(rt_scene_dev *s, const rt_view *v
   if (rc) return rc;
   if ((rc = lighting_device_check(a, d_offs, what))) return rc;
   if ((rc = soft_outputs_check(segs, d_out, what))) return rc;
-  if (!d_work || ((uintptr_t)d_work & 15u)) return fail(RT_ERR_INVALID, "%s: NULL or misaligned workspace (16 bytes)", what);
-  const uint64_t row_bytes = (uint64_t)w * 48u;
-  if (work_bytes < row_bytes) return fail(RT_ERR_INVALID, "%s: work_bytes %llu below one row of rays, %llu", what, (unsigned long long)work_bytes, (unsigned long long)row_bytes);
+  uint32_t band_rows = 0;
+  if ((rc = view_work_check(d_work, work_bytes, w, h, 48u, "rays", what, &band_rows))) return rc;
   if (!s) return fail(RT_ERR_STATE, "%s: NULL scene handle", what);
   hipStream_t stream = nullptr;
   if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
-  const uint64_t fit = work_bytes / row_bytes;
-  const uint32_t band_rows = fit < h ? (uint32_t)fit : h;
-  stats_clock clock;
-  if ((rc = clock.start(stats, stream))) return rc;
-  if ((rc = soft_view_bands(s, v, w, h, *a, d_offs, levels, 0u, h, band_rows, segs, *d_out, 0u, (double *)d_work, stream))) return rc;
-  return clock.finish(stats, (uint64_t)w * h);
+  return timed(stream, stats, (uint64_t)w * h,
+               [&] { return soft_view_bands(s, v, w, h, *a, d_offs, levels, 0u, h, band_rows, segs, *d_out, 0u, (double *)d_work, stream); });
 }
 
-// Host form: the list goes through rt_render's resident scene in chunks of RT_RAY_CHUNK rays and one set of device buffers; chunk c is
-// traced with pix_base = c * RT_RAY_CHUNK, so ray i keeps pix = i and its table entries however the list is cut.  The table goes up
-// once.  `binned`: each chunk is ordered on the GPU first (rt_rays_order.hip), which changes which rays share a wave and no result.
+// Host form: the list goes through rt_render's resident scene in chunks of RT_RAY_CHUNK rays (chunked_list_call); chunk c is traced
+// with pix_base = c * RT_RAY_CHUNK, so ray i keeps pix = i and its table entries however the list is cut.  The table goes up once.
+// `binned`: each chunk is ordered on the GPU first (rt_rays_order.hip), which changes which rays share a wave and no result.
 extern "C" int rt_trace_rays_soft_recursive(const void *blob, size_t bytes, const struct rt_lighting *a, const double *offs, uint32_t levels, uint64_t n,
                                             const double *rays, uint32_t segs, int binned, const rt_ray_outputs *ho, rt_stats *stats) {
   const char *what = "rt_trace_rays_soft_recursive";
@@ -158,51 +150,15 @@ extern "C" int rt_trace_rays_soft_recursive(const void *blob, size_t bytes, cons
   if ((rc = rt_lighting_validate(a, offs))) return rc;
   if ((rc = soft_list_check(n, rays, nullptr, 0u, what))) return rc;
   if ((rc = soft_outputs_check(segs, ho, what))) return rc;
-  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
-  std::lock_guard<std::mutex> lk(G.mu);
-  stats_clock clock;
-  rt_scene_dev *s = nullptr;
-  if ((rc = resident_scene(0, blob, bytes, &s))) return rc;
-  if ((rc = ensure_device(0))) return rc;
-  hipStream_t stream = G.dev[0].stream;
-  const size_t chunk = n < RT_RAY_CHUNK ? (size_t)n : (size_t)RT_RAY_CHUNK;
-  device_mem d_rays, d_rgb, d_rgba, d_offs, d_order, d_work;      // of one chunk; the table (released on every way out)
-  HIP_TRY(hipMalloc(&d_rays.h, chunk * 48u));
-  if (ho->rgb) HIP_TRY(hipMalloc(&d_rgb.h, chunk * 24u));
-  if (ho->rgba) HIP_TRY(hipMalloc(&d_rgba.h, chunk * 4u));
-  if (binned) {
-    HIP_TRY(hipMalloc(&d_order.h, chunk * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&d_work.h, rt_rays_order_work_bytes(chunk)));
-  }
-  if ((rc = lighting_upload_offs(*a, offs, &d_offs, stream))) return rc;
-  const rt_ray_outputs dout = {(double *)d_rgb.h, (uint8_t *)d_rgba.h, nullptr};
-  double kernel_ms = 0.0;
-  for (uint64_t base = 0; base < n; base += chunk) {
-    const size_t m = n - base < chunk ? (size_t)(n - base) : chunk;
-    HIP_TRY(hipMemcpyAsync(d_rays.h, rays + 6u * base, m * 48u, hipMemcpyHostToDevice, stream));
-    rt_stats st;
-    if (binned) {
-      stats_clock step;
-      if ((rc = step.start(stats, stream))) return rc;
-      if ((rc = order_rays_launch((uint32_t)m, (const double *)d_rays.h, (uint32_t *)d_order.h, d_work.h, stream))) return rc;
-      if ((rc = step.finish(stats ? &st : nullptr, m))) return rc;
-      if (stats) kernel_ms += st.kernel_ms;
-    }
-    if ((rc = soft_launch(s, *a, (const double *)d_offs.h, levels, (uint32_t)m, (const double *)d_rays.h, (const uint32_t *)d_order.h, (uint32_t)base, segs, dout,
-                          stream, stats ? &st : nullptr)))
-      return rc;
-    if (stats) kernel_ms += st.kernel_ms;
-    if (ho->rgb) HIP_TRY(hipMemcpyAsync(ho->rgb + 3u * base, d_rgb.h, m * 24u, hipMemcpyDeviceToHost, stream));
-    if (ho->rgba) HIP_TRY(hipMemcpyAsync(ho->rgba + 4u * base, d_rgba.h, m * 4u, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = kernel_ms;
-    stats->pixels = n;
-    stats->total_ms = clock.host_ms();
-  }
-  return RT_OK;
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
+  device_mem d_offs;                 // the table (released behind the call, whose every chunk has been waited for)
+  if ((rc = lighting_upload_offs(*a, offs, &d_offs, call.stream))) return rc;
+  const chunk_row rows[3] = {row_in(rays, 48u), row_out(ho->rgb, 24u), row_out(ho->rgba, 4u)};
+  return chunked_list_call(call, n, rows, 3, binned != 0, stats, [&](uint32_t m, uint64_t base, void *const *d, const uint32_t *d_order, rt_stats *st) {
+    const rt_ray_outputs dout = {(double *)d[1], (uint8_t *)d[2], nullptr};
+    return soft_launch(call.s, *a, (const double *)d_offs.h, levels, m, (const double *)d[0], d_order, (uint32_t)base, segs, dout, call.stream, st);
+  });
 }
 
 // Host form on rt_render's resident scene, as rt_trace_view: chunks of whole rows of at most RT_RAY_CHUNK rays; a longer row is its own chunk
@@ -214,50 +170,16 @@ extern "C" int rt_trace_view_soft(const void *blob, size_t bytes, const rt_view 
   if ((rc = rt_view_validate(v, w, h))) return rc;
   if ((rc = rt_lighting_validate(a, offs))) return rc;
   if ((rc = soft_outputs_check(segs, ho, what))) return rc;
-  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
-  std::lock_guard<std::mutex> lk(G.mu);
-  stats_clock clock;
-  rt_scene_dev *s = nullptr;
-  if ((rc = resident_scene(0, blob, bytes, &s))) return rc;
-  if ((rc = ensure_device(0))) return rc;
-  hipStream_t stream = G.dev[0].stream;
-  uint64_t chunk_rows = RT_RAY_CHUNK / w;
-  if (chunk_rows < 1u) chunk_rows = 1u;
-  if (chunk_rows > h) chunk_rows = h;
-  const size_t chunk = (size_t)chunk_rows * w;
-  device_mem d_rays, d_rgb, d_rgba, d_offs, d_lon, d_lat;         // of one chunk; the table; the panorama's tables (released on every way out)
-  HIP_TRY(hipMalloc(&d_rays.h, chunk * 48u));
-  if (ho->rgb) HIP_TRY(hipMalloc(&d_rgb.h, chunk * 24u));
-  if (ho->rgba) HIP_TRY(hipMalloc(&d_rgba.h, chunk * 4u));
-  if ((rc = lighting_upload_offs(*a, offs, &d_offs, stream))) return rc;
-  rt_view dv = *v;
-  if (v->model == RT_VIEW_EQUIRECT) {
-    HIP_TRY(hipMalloc(&d_lon.h, (size_t)w * 16u));
-    HIP_TRY(hipMalloc(&d_lat.h, (size_t)h * 16u));
-    HIP_TRY(hipMemcpyAsync(d_lon.h, v->lon, (size_t)w * 16u, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_lat.h, v->lat, (size_t)h * 16u, hipMemcpyHostToDevice, stream));
-    dv.lon = (const double *)d_lon.h; dv.lat = (const double *)d_lat.h;
-  }
-  const rt_ray_outputs dout = {(double *)d_rgb.h, (uint8_t *)d_rgba.h, nullptr};
-  double kernel_ms = 0.0;
-  for (uint32_t y = 0; y < h; y += (uint32_t)chunk_rows) {
-    const uint32_t m = h - y < chunk_rows ? h - y : (uint32_t)chunk_rows;
-    const size_t at = (size_t)y * w, cnt = (size_t)m * w;
-    stats_clock step;
-    rt_stats st;
-    if ((rc = step.start(stats, stream))) return rc;
-    if ((rc = soft_view_bands(s, &dv, w, h, *a, (const double *)d_offs.h, levels, y, y + m, m, segs, dout, y, (double *)d_rays.h, stream))) return rc;
-    if ((rc = step.finish(stats ? &st : nullptr, cnt))) return rc;
-    if (stats) kernel_ms += st.kernel_ms;
-    if (ho->rgb) HIP_TRY(hipMemcpyAsync(ho->rgb + 3u * at, d_rgb.h, cnt * 24u, hipMemcpyDeviceToHost, stream));
-    if (ho->rgba) HIP_TRY(hipMemcpyAsync(ho->rgba + 4u * at, d_rgba.h, cnt * 4u, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = kernel_ms;
-    stats->pixels = (uint64_t)w * h;
-    stats->total_ms = clock.host_ms();
-  }
-  return RT_OK;
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
+  device_mem d_offs;                 // the table
+  device_bufs<2> tables;             // the panorama's
+  rt_view dv;
+  if ((rc = lighting_upload_offs(*a, offs, &d_offs, call.stream))) return rc;
+  if ((rc = view_upload_tables(*v, w, h, 1u, call.stream, &tables, &dv))) return rc;
+  const chunk_row rows[3] = {row_scratch((size_t)w * 48u), row_out(ho->rgb, (size_t)w * 24u), row_out(ho->rgba, (size_t)w * 4u)};
+  return chunked_view_call(call, w, h, rows, 3, stats, [&](uint32_t y, uint32_t m, void *const *d) {
+    const rt_ray_outputs dout = {(double *)d[1], (uint8_t *)d[2], nullptr};
+    return soft_view_bands(call.s, &dv, w, h, *a, (const double *)d_offs.h, levels, y, y + m, m, segs, dout, y, (double *)d[0], call.stream);
+  });
 }

@@ -4,7 +4,8 @@
 // base, so ray i = y * w + x keeps pix = i and no trace kernel knows that the list was made here.  The generator reads nothing of a
 // scene: rt_view_rays_device waits for no edit and takes no part in rt_scene_sync.h; the trace launch behind it waits as it always does.
 // Sampled views (rt_view_sample, rt_view_lens; rt_view_samples.h / .hip) run the same band loop with n generate-and-trace steps per
-// band, an accumulator and a resolve: the second half of this file.
+// band, an accumulator and a resolve: the second half of this file.  The host forms are rows and a step for chunked_view_call
+// (rt_api_internal.h): a chunk is whole rows of at most RT_RAY_CHUNK pixels, and the band workspace is the chunk's scratch.
 #include "rt_api_internal.h"
 #include "rt_views.h"
 #include "rt_view_samples.h"
@@ -13,13 +14,40 @@ static_assert(sizeof(rt_view_sample) == 32 && sizeof(rt_view_lens) == 16 && size
 static_assert(RT_VIEWS_REFERENCE == RT_VIEW_REFERENCE && RT_VIEWS_PINHOLE == RT_VIEW_PINHOLE && RT_VIEWS_ORTHO == RT_VIEW_ORTHO &&
               RT_VIEWS_EQUIRECT == RT_VIEW_EQUIRECT, "rt_views.h restates the models of include/rt_hip.h");
 
-namespace {
-// rt_trace_view's chunks: whole rows of at most this many rays, as rt_trace_rays' chunks
-constexpr uint64_t RT_VIEW_CHUNK_RAYS = 1ull << 18;
-
-bool finite3(const double *a) { return std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]); }
-
+// what every unit that traces a view shares (rt_api_internal.h)
+namespace rt_api {
 bool view_size_ok(uint32_t w, uint32_t h) { return w != 0 && h != 0 && (uint64_t)w * h < (1ull << 31); }
+
+int view_work_check(const void *d_work, size_t work_bytes, uint32_t w, uint32_t h, uint32_t pixel_bytes, const char *noun, const char *what, uint32_t *band_rows) {
+  if (!d_work || ((uintptr_t)d_work & 15u)) return fail(RT_ERR_INVALID, "%s: NULL or misaligned workspace (16 bytes)", what);
+  const uint64_t row_bytes = (uint64_t)w * pixel_bytes;
+  if (work_bytes < row_bytes) return fail(RT_ERR_INVALID, "%s: work_bytes %llu below one row of %s, %llu", what, (unsigned long long)work_bytes, noun, (unsigned long long)row_bytes);
+  const uint64_t fit = work_bytes / row_bytes;
+  *band_rows = fit < h ? (uint32_t)fit : h;
+  return RT_OK;
+}
+
+int view_upload_tables(const rt_view &v, uint32_t w, uint32_t h, uint32_t n_tables, hipStream_t stream, device_bufs<2> *mem, rt_view *dv) {
+  *dv = v;
+  if (v.model != RT_VIEW_EQUIRECT) return RT_OK;
+  const size_t lon_bytes = (size_t)w * 16u * n_tables, lat_bytes = (size_t)h * 16u * n_tables;
+  HIP_TRY(hipMalloc(&mem->p[0], lon_bytes));
+  HIP_TRY(hipMalloc(&mem->p[1], lat_bytes));
+  HIP_TRY(hipMemcpyAsync(mem->p[0], v.lon, lon_bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(mem->p[1], v.lat, lat_bytes, hipMemcpyHostToDevice, stream));
+  dv->lon = (const double *)mem->p[0]; dv->lat = (const double *)mem->p[1];
+  return RT_OK;
+}
+
+int view_band_hits(rt_scene_dev *s, const rt_view *v, uint32_t w, uint32_t h, uint32_t y, uint32_t m, double *d_rays, rt_hit *d_hits, hipStream_t stream) {
+  if (int rc = rt_view_rays_device(s->device, v, w, h, y, m, d_rays, (void *)stream)) return rc;
+  const rt_ray_outputs into = {nullptr, nullptr, d_hits};
+  return trace_rays_launch(s, m * w, y * w, d_rays, nullptr, 1u, into, stream, nullptr);
+}
+}  // namespace rt_api
+
+namespace {
+bool finite3(const double *a) { return std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]); }
 
 int view_check(const rt_view *v, uint32_t w, uint32_t h, const char *what) {
   if (!v) return fail(RT_ERR_INVALID, "%s: NULL view", what);
@@ -73,14 +101,12 @@ int view_rays_launch(const rt_view_params &P, uint32_t first_row, uint32_t rows,
 // from there on.  One stream: a band's generation comes behind the trace that read the workspace before it.
 int trace_view_bands(rt_scene_dev *s, const rt_view_params &P, uint32_t row0, uint32_t row_end, uint32_t band_rows, uint32_t segs, const rt_ray_outputs &out,
                      uint32_t out_row0, double *d_work, hipStream_t stream) {
-  for (uint32_t y = row0; y < row_end; y += band_rows) {
-    const uint32_t m = row_end - y < band_rows ? row_end - y : band_rows;
+  return for_bands(row0, row_end, band_rows, [&](uint32_t y, uint32_t m) {
     if (int rc = view_rays_launch(P, y, m, d_work, stream)) return rc;
     const size_t at = (size_t)(y - out_row0) * P.w;       // of the band's first record in the outputs
     const rt_ray_outputs band = {out.rgb ? out.rgb + 3u * at : nullptr, out.rgba ? out.rgba + 4u * at : nullptr, out.hits ? out.hits + at : nullptr};
-    if (int rc = trace_rays_launch(s, m * P.w, y * P.w, d_work, nullptr, segs, band, stream, nullptr)) return rc;
-  }
-  return RT_OK;
+    return trace_rays_launch(s, m * P.w, y * P.w, d_work, nullptr, segs, band, stream, nullptr);
+  });
 }
 
 // ---- sampled views: sub-pixel offsets and a thin lens (rt_view_samples.h), averaged on the GPU
@@ -124,8 +150,8 @@ int trace_view_sample_bands(rt_scene_dev *s, const rt_view_params &P, const rt_v
                             hipStream_t stream) {
   const size_t band = (size_t)band_rows * P.w;
   double *rays = (double *)d_work, *slab = rays + 6u * band, *acc = slab + 3u * band;
-  for (uint32_t y = row0; y < row_end; y += band_rows) {
-    const uint32_t m = row_end - y < band_rows ? row_end - y : band_rows, pixels = m * P.w;
+  return for_bands(row0, row_end, band_rows, [&](uint32_t y, uint32_t m) {
+    const uint32_t pixels = m * P.w;
     for (uint32_t k = 0; k < n; k++) {
       const rt_view_params Pk = view_params_of_table(P, k);
       const rt_view_sample_params S = sample_params(samples[k], lens);
@@ -138,8 +164,8 @@ int trace_view_sample_bands(rt_scene_dev *s, const rt_view_params &P, const rt_v
     const size_t at = (size_t)(y - out_row0) * P.w;       // of the band's first pixel in the outputs
     VIEW_LAUNCH(rt_launch_view_resolve(acc, n > 1u ? slab : nullptr, n, pixels, out.rgb ? out.rgb + 3u * at : nullptr, out.rgba ? out.rgba + 4u * at : nullptr,
                                        (void *)stream), "view resolve");
-  }
-  return RT_OK;
+    return (int)RT_OK;
+  });
 }
 
 int view_sample_outputs_check(uint32_t segs, const rt_ray_outputs *out, const char *what) {
@@ -193,16 +219,11 @@ extern "C" int rt_scene_trace_view_device(rt_scene_dev *s, const rt_view *v, uin
   int rc = view_check(v, w, h, what);
   if (rc) return rc;
   if ((rc = view_outputs_check(segs, d_out, what))) return rc;
-  if (!d_work || ((uintptr_t)d_work & 15u)) return fail(RT_ERR_INVALID, "%s: NULL or misaligned workspace (16 bytes)", what);
-  if (work_bytes < (size_t)w * 48u) return fail(RT_ERR_INVALID, "%s: work_bytes %llu below one row of rays, %llu", what, (unsigned long long)work_bytes, (unsigned long long)w * 48u);
+  uint32_t band_rows = 0;
+  if ((rc = view_work_check(d_work, work_bytes, w, h, 48u, "rays", what, &band_rows))) return rc;
   hipStream_t stream = nullptr;
   if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
-  const uint64_t fit = work_bytes / ((uint64_t)w * 48u);
-  const uint32_t band_rows = fit < h ? (uint32_t)fit : h;
-  stats_clock clock;
-  if ((rc = clock.start(stats, stream))) return rc;
-  if ((rc = trace_view_bands(s, view_params(*v, w, h), 0u, h, band_rows, segs, *d_out, 0u, (double *)d_work, stream))) return rc;
-  return clock.finish(stats, (uint64_t)w * h);
+  return timed(stream, stats, (uint64_t)w * h, [&] { return trace_view_bands(s, view_params(*v, w, h), 0u, h, band_rows, segs, *d_out, 0u, (double *)d_work, stream); });
 }
 
 extern "C" int rt_trace_view(const void *blob, size_t bytes, const rt_view *v, uint32_t w, uint32_t h, uint32_t segs, const rt_ray_outputs *ho,
@@ -212,54 +233,17 @@ extern "C" int rt_trace_view(const void *blob, size_t bytes, const rt_view *v, u
   if (rc) return rc;
   if ((rc = view_check(v, w, h, what))) return rc;
   if ((rc = view_outputs_check(segs, ho, what))) return rc;
-  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
-  std::lock_guard<std::mutex> lk(G.mu);
-  stats_clock clock;
-  rt_scene_dev *s = nullptr;
-  if ((rc = resident_scene(0, blob, bytes, &s))) return rc;
-  if ((rc = ensure_device(0))) return rc;
-  hipStream_t stream = G.dev[0].stream;
-  // chunks of whole rows of at most RT_VIEW_CHUNK_RAYS rays; a longer row is its own chunk
-  uint64_t chunk_rows = RT_VIEW_CHUNK_RAYS / w;
-  if (chunk_rows < 1u) chunk_rows = 1u;
-  if (chunk_rows > h) chunk_rows = h;
-  const size_t chunk = (size_t)chunk_rows * w;
-  device_mem d_rays, d_rgb, d_rgba, d_hits, d_lon, d_lat;      // of one chunk; the panorama's tables (released on every way out)
-  HIP_TRY(hipMalloc(&d_rays.h, chunk * 48u));
-  if (ho->rgb) HIP_TRY(hipMalloc(&d_rgb.h, chunk * 24u));
-  if (ho->rgba) HIP_TRY(hipMalloc(&d_rgba.h, chunk * 4u));
-  if (ho->hits) HIP_TRY(hipMalloc(&d_hits.h, chunk * sizeof(rt_hit)));
-  rt_view_params P = view_params(*v, w, h);
-  if (v->model == RT_VIEW_EQUIRECT) {
-    HIP_TRY(hipMalloc(&d_lon.h, (size_t)w * 16u));
-    HIP_TRY(hipMalloc(&d_lat.h, (size_t)h * 16u));
-    HIP_TRY(hipMemcpyAsync(d_lon.h, v->lon, (size_t)w * 16u, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_lat.h, v->lat, (size_t)h * 16u, hipMemcpyHostToDevice, stream));
-    P.lon = (const double *)d_lon.h; P.lat = (const double *)d_lat.h;
-  }
-  const rt_ray_outputs dout = {(double *)d_rgb.h, (uint8_t *)d_rgba.h, (rt_hit *)d_hits.h};
-  double kernel_ms = 0.0;
-  for (uint32_t y = 0; y < h; y += (uint32_t)chunk_rows) {
-    const uint32_t m = h - y < chunk_rows ? h - y : (uint32_t)chunk_rows;
-    const size_t at = (size_t)y * w, n = (size_t)m * w;
-    stats_clock step;
-    rt_stats st;
-    if ((rc = step.start(stats, stream))) return rc;
-    if ((rc = trace_view_bands(s, P, y, y + m, m, segs, dout, y, (double *)d_rays.h, stream))) return rc;
-    if ((rc = step.finish(stats ? &st : nullptr, n))) return rc;
-    if (stats) kernel_ms += st.kernel_ms;
-    if (ho->rgb) HIP_TRY(hipMemcpyAsync(ho->rgb + 3u * at, d_rgb.h, n * 24u, hipMemcpyDeviceToHost, stream));
-    if (ho->rgba) HIP_TRY(hipMemcpyAsync(ho->rgba + 4u * at, d_rgba.h, n * 4u, hipMemcpyDeviceToHost, stream));
-    if (ho->hits) HIP_TRY(hipMemcpyAsync(ho->hits + at, d_hits.h, n * sizeof(rt_hit), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = kernel_ms;
-    stats->pixels = (uint64_t)w * h;
-    stats->total_ms = clock.host_ms();
-  }
-  return RT_OK;
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
+  device_bufs<2> tables;
+  rt_view dv;
+  if ((rc = view_upload_tables(*v, w, h, 1u, call.stream, &tables, &dv))) return rc;
+  const rt_view_params P = view_params(dv, w, h);
+  const chunk_row rows[4] = {row_scratch((size_t)w * 48u), row_out(ho->rgb, (size_t)w * 24u), row_out(ho->rgba, (size_t)w * 4u), row_out(ho->hits, (size_t)w * sizeof(rt_hit))};
+  return chunked_view_call(call, w, h, rows, 4, stats, [&](uint32_t y, uint32_t m, void *const *d) {
+    const rt_ray_outputs dout = {(double *)d[1], (uint8_t *)d[2], (rt_hit *)d[3]};
+    return trace_view_bands(call.s, P, y, y + m, m, segs, dout, y, (double *)d[0], call.stream);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- sampled views
@@ -337,17 +321,12 @@ extern "C" int rt_scene_trace_view_samples_device(rt_scene_dev *s, const rt_view
   int rc = view_samples_check(v, w, h, lens, n, samples, what);
   if (rc) return rc;
   if ((rc = view_sample_outputs_check(segs, d_out, what))) return rc;
-  if (!d_work || ((uintptr_t)d_work & 15u)) return fail(RT_ERR_INVALID, "%s: NULL or misaligned workspace (16 bytes)", what);
-  const uint64_t row_bytes = (uint64_t)w * RT_VIEW_SAMPLE_BAND_BYTES;
-  if (work_bytes < row_bytes) return fail(RT_ERR_INVALID, "%s: work_bytes %llu below one row of a band, %llu", what, (unsigned long long)work_bytes, (unsigned long long)row_bytes);
+  uint32_t band_rows = 0;
+  if ((rc = view_work_check(d_work, work_bytes, w, h, RT_VIEW_SAMPLE_BAND_BYTES, "a band", what, &band_rows))) return rc;
   hipStream_t stream = nullptr;
   if ((rc = scene_stream(s, hip_stream, &stream))) return rc;
-  const uint64_t fit = work_bytes / row_bytes;
-  const uint32_t band_rows = fit < h ? (uint32_t)fit : h;
-  stats_clock clock;
-  if ((rc = clock.start(stats, stream))) return rc;
-  if ((rc = trace_view_sample_bands(s, view_params(*v, w, h), lens, n, samples, 0u, h, band_rows, segs, *d_out, 0u, d_work, stream))) return rc;
-  return clock.finish(stats, (uint64_t)w * h);
+  return timed(stream, stats, (uint64_t)w * h,
+               [&] { return trace_view_sample_bands(s, view_params(*v, w, h), lens, n, samples, 0u, h, band_rows, segs, *d_out, 0u, d_work, stream); });
 }
 
 extern "C" int rt_trace_view_samples(const void *blob, size_t bytes, const rt_view *v, uint32_t w, uint32_t h, const rt_view_lens *lens, uint32_t n,
@@ -357,50 +336,15 @@ extern "C" int rt_trace_view_samples(const void *blob, size_t bytes, const rt_vi
   if (rc) return rc;
   if ((rc = view_samples_check(v, w, h, lens, n, samples, what))) return rc;
   if ((rc = view_sample_outputs_check(segs, ho, what))) return rc;
-  if (!G.inited) return fail(RT_ERR_STATE, "rt_init has not been called");
-  std::lock_guard<std::mutex> lk(G.mu);
-  stats_clock clock;
-  rt_scene_dev *s = nullptr;
-  if ((rc = resident_scene(0, blob, bytes, &s))) return rc;
-  if ((rc = ensure_device(0))) return rc;
-  hipStream_t stream = G.dev[0].stream;
-  // chunks of whole rows of at most RT_VIEW_CHUNK_RAYS pixels; a longer row is its own chunk
-  uint64_t chunk_rows = RT_VIEW_CHUNK_RAYS / w;
-  if (chunk_rows < 1u) chunk_rows = 1u;
-  if (chunk_rows > h) chunk_rows = h;
-  const size_t chunk = (size_t)chunk_rows * w;
-  device_mem d_work, d_rgb, d_rgba, d_lon, d_lat;      // of one chunk; the panorama's tables of all samples (released on every way out)
-  HIP_TRY(hipMalloc(&d_work.h, chunk * RT_VIEW_SAMPLE_BAND_BYTES));
-  if (ho->rgb) HIP_TRY(hipMalloc(&d_rgb.h, chunk * 24u));
-  if (ho->rgba) HIP_TRY(hipMalloc(&d_rgba.h, chunk * 4u));
-  rt_view_params P = view_params(*v, w, h);
-  if (v->model == RT_VIEW_EQUIRECT) {
-    HIP_TRY(hipMalloc(&d_lon.h, (size_t)w * 16u * n));
-    HIP_TRY(hipMalloc(&d_lat.h, (size_t)h * 16u * n));
-    HIP_TRY(hipMemcpyAsync(d_lon.h, v->lon, (size_t)w * 16u * n, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_lat.h, v->lat, (size_t)h * 16u * n, hipMemcpyHostToDevice, stream));
-    P.lon = (const double *)d_lon.h; P.lat = (const double *)d_lat.h;
-  }
-  const rt_ray_outputs dout = {(double *)d_rgb.h, (uint8_t *)d_rgba.h, nullptr};
-  double kernel_ms = 0.0;
-  for (uint32_t y = 0; y < h; y += (uint32_t)chunk_rows) {
-    const uint32_t m = h - y < chunk_rows ? h - y : (uint32_t)chunk_rows;
-    const size_t at = (size_t)y * w, px = (size_t)m * w;
-    stats_clock step;
-    rt_stats st;
-    if ((rc = step.start(stats, stream))) return rc;
-    if ((rc = trace_view_sample_bands(s, P, lens, n, samples, y, y + m, m, segs, dout, y, d_work.h, stream))) return rc;
-    if ((rc = step.finish(stats ? &st : nullptr, px))) return rc;
-    if (stats) kernel_ms += st.kernel_ms;
-    if (ho->rgb) HIP_TRY(hipMemcpyAsync(ho->rgb + 3u * at, d_rgb.h, px * 24u, hipMemcpyDeviceToHost, stream));
-    if (ho->rgba) HIP_TRY(hipMemcpyAsync(ho->rgba + 4u * at, d_rgba.h, px * 4u, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
-  if (stats) {
-    memset(stats, 0, sizeof *stats);
-    stats->kernel_ms = kernel_ms;
-    stats->pixels = (uint64_t)w * h;
-    stats->total_ms = clock.host_ms();
-  }
-  return RT_OK;
+  host_call call;
+  if ((rc = call.begin(blob, bytes))) return rc;
+  device_bufs<2> tables;                               // the panorama's tables of all samples
+  rt_view dv;
+  if ((rc = view_upload_tables(*v, w, h, n, call.stream, &tables, &dv))) return rc;
+  const rt_view_params P = view_params(dv, w, h);
+  const chunk_row rows[3] = {row_scratch((size_t)w * RT_VIEW_SAMPLE_BAND_BYTES), row_out(ho->rgb, (size_t)w * 24u), row_out(ho->rgba, (size_t)w * 4u)};
+  return chunked_view_call(call, w, h, rows, 3, stats, [&](uint32_t y, uint32_t m, void *const *d) {
+    const rt_ray_outputs dout = {(double *)d[1], (uint8_t *)d[2], nullptr};
+    return trace_view_sample_bands(call.s, P, lens, n, samples, y, y + m, m, segs, dout, y, d[0], call.stream);
+  });
 }
