@@ -204,6 +204,22 @@ __device__ __forceinline__ int rt_lvl(int lv) { return lv; }
               }                                                                             \
             }
 
+// ---- the end of a lane's chain (the six-wave kernels) -------------------------------------------------------------------------------
+// RT_CHAIN_END(): reads and writes ret; reads SIX_WAVES, map_valid, acc.  The chain of one-child nodes ends at this node with colour `ret`:
+// the accumulated map is applied HERE, in the branch that made the colour (the other kernels apply it behind the node's body, where the
+// ending and the descending lanes' paths have met), and the lane leaves the loop by a plain `break`.  `ret` is then a value of that branch
+// alone: it meets no other path, nothing of it is zeroed per turn, and no test of an opaque constant stands at the exit.  A block that
+// always leaves is no part of the loop: in the code object the whole chain end - the leaf's three channel sums, the application - stands
+// BEHIND the node loop and runs once per wave, for all its lanes together, on what each lane held when it left.
+#define RT_CHAIN_END()                                                                                                          \
+        if constexpr (SIX_WAVES) {                                                                                              \
+          if (map_valid) {                                                                                                      \
+            const double S_ = acc[0];                                                                                           \
+            _Pragma("unroll")                                                                                                   \
+            for (int c = 0; c < 3; c++) ret[c] = rt_max_nn(acc[(4 + c) * 64u], rt_min_nn(acc[(7 + c) * 64u], __builtin_fma(S_, ret[c], acc[(1 + c) * 64u])));   \
+          }                                                                                                                     \
+        }
+
 // One intersectWorld call tree for one sample.  UNI (product reflection-only one-wave-workgroup kernels only): the caller has found the
 // wave's launch-table entry to name exactly ONE primary candidate, cand_host & 255, and hands over `mtl` / `tex` as the image in HBM.
 // The call then shades the wave on the uniform-material path - the one anchored test without closest-hit selects, the candidate's
@@ -258,10 +274,18 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
   uint32_t segs_left = L.segs;
 #endif
   double ret[3] = {0.0, 0.0, 0.0};
-  // The few-sphere one-wave kernels (80 VGPRs, six waves per SIMD): a lane whose chain has ended parks its colour in its OWN fold-state
-  // slots O[0..2] - dead from then on: the lane evaluates no further node - and reads it back behind the node loop, so that the three
-  // doubles are not held in registers while the wave's other lanes go on through light loops.  A store and a load: the same bits.
-  constexpr bool PARK_RET = FOLD_FORWARD && W1 && !GRID && !REFRACT && !COUNT && !ITEM && !UNI;
+  // The few-sphere one-wave kernels (80 VGPRs, six waves per SIMD), general path: a lane's chain ends in the branch that made its colour
+  // (RT_CHAIN_END), and the ambient and reflection coefficients are read a second time behind the lighting (below).  (The colour used to be
+  // parked in the lane's fold-state slots O[0..2] and read back behind the loop, with `ret` zeroed at every turn's top and an exit through
+  // an opaque test that kept the stores inside the loop; with the chain end in its branch the registers fit without: docs/EVIDENCE.md.)
+  constexpr bool SIX_WAVES = FOLD_FORWARD && W1 && !GRID && !REFRACT && !COUNT && !ITEM && !UNI;
+  // The few-sphere reflection-only product kernels: every node has at most one child, so every lane still in the node loop is at the same node
+  // in every turn of it, and which node that is - the primary ray's, the first bounce's, a later one - is a COUNT of the loop's turns in a
+  // scalar register.  (As booleans carried from turn to turn the same facts were lane masks: an exec-mask save, test and restore at every
+  // use, and every value derived from them - the shadow scan's pair mask - a vector register tested per lane.)  In these kernels the
+  // count is rt_lvl(level), and `map_valid` is "not the primary node".
+  constexpr bool WAVE_NODE = LEAN && !GRID && !UNI;
+  [[maybe_unused]] uint32_t turn = 0u;
 
   // ---- A2 / A3 candidates: the primary ray's here, a bounced ray's at the top of its node ----
   // A3: closest hit.  The winner is kept as (ht, hcode) with hcode = 2*index + inside, so a candidate costs one
@@ -346,6 +370,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
   bool searched = true;                // the primary ray's candidates were found above (culled; camera-anchored in the product kernel)
   // (few-sphere reflection-only product kernels) wave-uniform like `searched`: the node being evaluated is the one AFTER the primary - in these kernels
   // every node has at most one child, so every lane still in the loop is at the same level in every turn of it
+  // (WAVE_NODE: both, and map_valid, are set from the turn's number at the loop's head; carried from turn to turn they are lane masks)
   [[maybe_unused]] bool first_bounce = false;
 #if !RT_STRICT
   // A wave none of whose primary rays met a sphere of the loops, in a scene whose enclosing sphere is flat AND constant in colour
@@ -360,8 +385,13 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 
   if (segs_left != 0) {
     for (;;) {
-      // (every turn sets its own `ret`: nothing of it is carried from one turn into the next, or the parked colour would be held all the same)
-      if constexpr (PARK_RET) ret[0] = ret[1] = ret[2] = 0.0;
+      // (WAVE_NODE) which node this turn evaluates: 0 the primary ray's, 1 the first bounce's, ...; counted at the turn's top, where every
+      // lane in the loop passes, so that it stays a scalar
+      [[maybe_unused]] const uint32_t node_no = turn;
+      if constexpr (WAVE_NODE) {
+        turn++;
+        searched = (node_no == 0u); first_bounce = (node_no == 1u); map_valid = (node_no != 0u);
+      }
       // ---------------- evaluate one intersectWorld node (segs_left > 0 here) ----------------
       if (COUNT) cnt[0]++;
       if (!UNI && !searched) {                           // reflection / refraction rays: any origin, generic form
@@ -459,8 +489,10 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
         }
       }
       [[maybe_unused]] const bool primary_node = UNI || searched;       // wave-uniform: this node is the primary ray's
+      if constexpr (!WAVE_NODE) {                                       // (WAVE_NODE: the three are set from the turn's number, above)
       first_bounce = searched;                                          // ... and the next one, if any, the first bounce's
       searched = false;
+      }
       // ---- the enclosing sphere ----
       // The enclosing sphere (every other sphere, light and the camera strictly inside it: a skybox) is
       // kept LAST in the device tables and outside the loops above: it can only be the closest hit of a
@@ -481,7 +513,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
       const bool inside = (hcode & 1) != 0;
       bool descend = false;
 #if defined(RT_TESTING) && defined(RT_ABLATE_SHADE)
-      if (true) { ret[0] = ht; ret[1] = (double)hcode; ret[2] = 0.0; } else
+      if (true) { ret[0] = ht; ret[1] = (double)hcode; ret[2] = 0.0; RT_CHAIN_END() } else
 #endif
       if (!UNI && hcode < 0) {                        // main.js:231 (with a flat sky of constant colour: that sky's pixel term, see rt_launch.hip bind_kernel)
         // (product build: read where it is used, from the kernarg segment: six scalar registers less across the whole loop)
@@ -494,6 +526,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
           q[17] = (double)segs_left; q[19] = p.x; q[20] = p.y; q[21] = p.z; q[23] = 1.0;
         }
 #endif
+        RT_CHAIN_END()
       } else {
         typename rt_mtl_src<UNI>::type &m = *rt_mtl_at<UNI>(mtl, (uint32_t)hi);      // per-lane index, a 32-bit offset (LDS; the many-sphere variant: HBM / L2); UNI: the wave's one record, scalar loads
         // A2 ext part for the closest hit only (main.js:440-447; pure, so deferring it is exact)
@@ -510,13 +543,14 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
         // (UNI: no lane is inside the candidate - a wave with one left before its hit test's ballot, above - so l is n)
         if constexpr (UNI) l = n;
         else l = inside ? mk(-n.x, -n.y, -n.z) : n;
-        double a0 = m.albedo[0];                                        // (a0, a3: PARK_RET reads them again behind the lighting, below)
+        double a0 = m.albedo[0];                                        // (a0, a3: SIX_WAVES reads them again behind the lighting, below)
         const double a1 = m.albedo[1], a2 = m.albedo[2];
         double a3 = m.albedo[3];
         const double a4 = REFRACT ? m.albedo[4] : 0.0;
 #if !RT_STRICT && !defined(RT_ABLATE_QAMP)     /* (RT_ABLATE_QAMP: timing experiment, profiles/ab_build.sh) */
         // Q of this hit (see above): for a bounced ray's hit, and for a primary hit that will spawn a ray (ht is at hand here)
-        if (!UNI && (rt_lvl(level) != 0 || ((a3 > 0.0 || a4 > 0.0) && segs_left > 1))) {      // (UNI: a primary hit that spawns nothing)
+        // (WAVE_NODE: rt_lvl(level) is the turn's number - a scalar test, and no test at all below the primary)
+        if (!UNI && ((WAVE_NODE ? node_no != 0u : rt_lvl(level) != 0) || ((a3 > 0.0 || a4 > 0.0) && segs_left > 1))) {      // (UNI: a primary hit that spawns nothing)
           const float ir_ = (float)inv_r;
           const float q_ = RT_Q_OF(RT_Q_GET(level), (float)ht, ir_, __builtin_fabsf((float)dot(d, n)), rt_r_get(level));
           level = rt_q_put(level, q_);
@@ -757,6 +791,10 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 #if !RT_STRICT
                 // a non-empty set still skips the PAIRS of the scan neither sphere of which is in it (a loop over just the named
                 // spheres would cost the kernel its 96th register)
+                // (WAVE_NODE: primary_node is a scalar compare, so mk - the entry's word, a shift and an OR - lives in a scalar register and a pair
+                // is decided by a scalar bit test and a branch of its own; elsewhere primary_node is a lane mask, mk a vector register selected
+                // under it, and every pair tests it per lane.  At a bounced node mk is ~0 and the scalar test still runs: a second copy of the
+                // scan without it spilled ten scalar registers in the six-wave kernels and measured slower - docs/EVIDENCE.md)
                 [[maybe_unused]] uint32_t mk = ~0u;
                 if constexpr (!GRID) { if (primary_node && k < 2u) mk = (smask >> (16u * k)) | 0xffff0000u; }
                 if constexpr (!GRID) {
@@ -765,6 +803,8 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 #endif
                 for (; j + 2 <= NS; j += 2) {
 #if !RT_STRICT
+                  // (WAVE_NODE: mk is a scalar, and the same test is a shift, an AND and a branch on the scalar unit - bits 30 and 31 of mk are set)
+                  if constexpr (WAVE_NODE) { if (((mk >> (j < 30u ? j : 30u)) & 3u) == 0u) continue; } else
                   if (!GRID && j < 31u && ((mk >> j) & 3u) == 0u) continue;       // (sets name 16 spheres; the upper half of mk is all ones: beyond bit 30 every pair is scanned)
 #endif
                   const rt_geom_pair gp = rt_load_geom_pair32(gl, glo + j);
@@ -843,7 +883,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
         // (the few-sphere one-wave kernels) The ambient and the reflection coefficient are not needed by the lighting: they are read AGAIN
         // here, the same two LDS words through an index the compiler cannot match with the first read, so that four registers less are
         // held across the shadow scans.  A reload: the same bits.
-        if constexpr (PARK_RET) {
+        if constexpr (SIX_WAVES) {
           uint32_t hi2 = (uint32_t)hi;
           asm volatile("" : "+v"(hi2));
           const rt_mtl &m2 = *rt_mtl_at<false>(mtl, hi2);
@@ -924,9 +964,11 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 #pragma unroll
               for (int c = 0; c < 3; c++) ret[c] = maxa(col[c] * a0, min1(col[c] * d2 + col[c] * s2));
             }
-          } else
+          } else {
 #pragma unroll
           for (int c = 0; c < 3; c++) ret[c] = maxa(col[c] * a0, min1(col[c] * diffuse + col[c] * specular));
+          RT_CHAIN_END()
+          }
         } else if constexpr (FOLD_FORWARD) {
           // Each level maps its child's colour x through  f(x) = max(amb, min(1, (ds [+ other child]) + a*x))
           // (main.js:326-336), a non-decreasing clamped-affine map, and compositions of such maps are again
@@ -983,7 +1025,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
               }
               acc[0] = S * coef;
             }
-            map_valid = true;
+            if constexpr (!WAVE_NODE) map_valid = true;                 // (WAVE_NODE: "not the primary node", set at the turn's top)
             p = h; d = via_f ? f : r; tree_path = 2u * tree_path + (via_f ? 1u : 0u);
           }
           level++; segs_left--;
@@ -1006,7 +1048,9 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
       }
       if (descend) continue;
 
-      if constexpr (FOLD_FORWARD) {
+      // (SIX_WAVES: the lane's colour is folded - RT_CHAIN_END, in the branch that ended its chain; it leaves)
+      if constexpr (SIX_WAVES) break;
+      else if constexpr (FOLD_FORWARD) {
         // a chain of one-child nodes ended with colour `ret`: apply the accumulated map once
         const uint32_t T = W1 ? 64u : RT_WG_THREADS;
         if (map_valid) {
@@ -1050,17 +1094,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
             resumed = true;
           }
         }
-        if (!resumed) {
-          if constexpr (PARK_RET) {
-#pragma unroll
-            for (int c = 0; c < 3; c++) acc[(1 + c) * T] = ret[c];
-            // (the lane leaves HERE, through a test the compiler cannot decide: as the loop's plain exit the stores would move behind the
-            // loop, and the colour would wait for them in registers)
-            uint32_t fin = 1u;
-            asm volatile("" : "+v"(fin));
-            if (fin != 0u) break;
-          } else break;
-        }
+        if (!resumed) break;
       } else {
         // ---------------- return `ret` to the parents (post-order fold, main.js:268-278, :326-336) ----------------
         bool resumed = false;
@@ -1092,10 +1126,6 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
         if (!resumed) break;
       }
     }
-    if constexpr (PARK_RET) {
-#pragma unroll
-      for (int c = 0; c < 3; c++) ret[c] = acc[(1 + c) * 64u];
-    }
   }
   rgb[0] = ret[0]; rgb[1] = ret[1]; rgb[2] = ret[2];
   return true;
@@ -1113,3 +1143,4 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 #undef RT_SROOTS
 #undef RT_SHADOW
 #undef RT_SHADOW_U
+#undef RT_CHAIN_END
