@@ -394,6 +394,41 @@ function ambientView(sceneObj, view, w, h, opts) {
     !!o.open, !!o.intensity, o.rgba !== false);
 }
 
+// Gathered light (include/rt_hip.h: struct rt_gather): what colour arrives at each receiver from the rest of the scene - opts.samples rays
+// over the hemisphere of its facing normal along the directions ambient uses, each traced as traceRays traces any ray (depth opts.segs,
+// 0 = the scene's; no sphere left out), averaged on the GPU in one launch.  With the default cosine-weighted table rgb is irradiance / pi.
+// Returns {rgb: Float64Array (3 per receiver; NaN for a miss), rgba: Uint8ClampedArray (the mean as a pixel), kernel_ms} - each null
+// unless named in opts.want.
+//   gather(scene, hits, opts)      hits as for ambient.  opts: samples (default 16), dirs (default ambientDirs(samples)), stride (default 1),
+//                                  segs (default 0), base and pixBase (default 0), pixStride (default: the number of receivers; the stars
+//                                  sampler's pix of sample s of receiver i is pixBase + s pixStride + i), want (default ['rgb'])
+//   gatherView(scene, view, w, h, opts)   the same for what the view sees; pixStride defaults to w h, want to ['rgba']
+const GATHER_OUTPUTS = ['rgb', 'rgba'];
+function gatherOpts(o, who, n, wantDefault) {
+  const samples = o.samples === undefined ? 16 : o.samples, dirs = o.dirs || native().ambientDirs(samples);
+  if (!(dirs instanceof Float64Array) || dirs.length === 0 || dirs.length % 3 !== 0) throw new TypeError(who + ': dirs must be a Float64Array of 3 numbers per direction');
+  const want = o.want === undefined ? wantDefault : o.want;
+  if (!Array.isArray(want) || want.length === 0 || !want.every((k) => GATHER_OUTPUTS.includes(k))) throw new TypeError(who + ": want names some of 'rgb', 'rgba'");
+  return [dirs, samples, o.stride === undefined ? 1 : o.stride, o.segs || 0, o.base || 0, o.pixBase || 0, o.pixStride === undefined ? n : o.pixStride,
+    ...GATHER_OUTPUTS.map((k) => want.includes(k))];
+}
+function gather(sceneObj, hits, opts) {
+  if (!(hits instanceof Uint8Array ? hits.length > 0 && hits.length % HIT_BYTES === 0 : Array.isArray(hits) && hits.length > 0)) {
+    throw new TypeError('gather: hits must be a non-empty array of hit objects or a Uint8Array of 80-byte records');
+  }
+  const o = opts || {};
+  const args = gatherOpts(o, 'gather', hits instanceof Uint8Array ? hits.length / HIT_BYTES : hits.length, ['rgb']);
+  if (!inited) init(o.maxDevices);
+  return native().gather(new Uint8Array(flattenScene(sceneObj)), hitRecords(hits), ...args);
+}
+function gatherView(sceneObj, view, w, h, opts) {
+  if (!view || !Number.isInteger(view.model)) throw new TypeError('gatherView: view must come from views.reference / pinhole / ortho / equirect');
+  const o = opts || {};
+  const args = gatherOpts(o, 'gatherView', w * h, ['rgba']);
+  if (!inited) init(o.maxDevices);
+  return native().gatherView(new Uint8Array(flattenScene(sceneObj)), viewBytes(view), view.lon || null, view.lat || null, w, h, ...args);
+}
+
 // Sampled lights (include/rt_hip.h: struct rt_lighting): how much light arrives at each receiver - the reference's light loop
 // (main.js:283-306) opts.samples times, every light displaced by opts.lightRadius times an entry of opts.offsets, averaged on the GPU.
 // With the defaults (one sample, lightRadius 0) it is the reference's own loop.  Returns {diffuse: Float64Array (the mean raw diffuse
@@ -438,4 +473,4 @@ function buildId() { return native().buildId(); }
 
 function shutdown() { if (addon) addon.shutdown(); inited = false; }
 
-module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, traceView, views, shadeRays, relightRays, primaryRays, normal3D, occlusion, lightSegments, ambient, ambientView, ambientDirs, lighting, lightingView, lightingOffsets, init, shutdown, buildId, flattenScene, scenes, native}, scene);
+module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, traceView, views, shadeRays, relightRays, primaryRays, normal3D, occlusion, lightSegments, ambient, ambientView, ambientDirs, gather, gatherView, lighting, lightingView, lightingOffsets, init, shutdown, buildId, flattenScene, scenes, native}, scene);

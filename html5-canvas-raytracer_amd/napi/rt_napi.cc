@@ -1151,6 +1151,107 @@ napi_value AmbientView(napi_env env, napi_callback_info info) {
   return ambient_result(env, n, want, abs, st.kernel_ms);
 }
 
+// ---- gathered light (include/rt_hip.h: struct rt_gather)
+// gather(blob, hits: Uint8Array (80 bytes per receiver), dirs, nSamples, stride, segs, base, pixBase, pixStride, wantRgb, wantRgba): rt_gather
+// gatherView(blob, view, lon, lat, w, h, dirs, nSamples, stride, segs, base, pixBase, pixStride, wantRgb, wantRgba): rt_gather_view; `view`, lon
+// and lat as for traceView.  -> {rgb: Float64Array (3 per receiver) | null, rgba: Uint8ClampedArray | null, kernel_ms}
+napi_value gather_call(napi_env env, napi_callback_info info, bool of_view) {
+  const char *who = of_view ? "gatherView(blob: Uint8Array, view: Uint8Array, lon, lat, w, h, dirs: Float64Array (3 per entry), nSamples, stride, segs, base, pixBase, pixStride, wantRgb, wantRgba)"
+                            : "gather(blob: Uint8Array, hits: Uint8Array (80 bytes per receiver), dirs: Float64Array (3 per entry), nSamples, stride, segs, base, pixBase, pixStride, wantRgb, wantRgba)";
+  const size_t at = of_view ? 6 : 2;                   // of dirs
+  size_t argc = 15;
+  napi_value argv[15];
+  bool is_ta = false, is_second = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < at + 9 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
+      napi_is_typedarray(env, argv[1], &is_second) != napi_ok || !is_second) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  napi_typedarray_type bt, st2; napi_value ab; size_t off, blob_len = 0, second_len = 0;
+  void *blob_data = nullptr, *second_data = nullptr;
+  napi_get_typedarray_info(env, argv[0], &bt, &blob_len, &blob_data, &ab, &off);
+  napi_get_typedarray_info(env, argv[1], &st2, &second_len, &second_data, &ab, &off);
+  uint32_t w = 0, h = 0;
+  if ((bt != napi_uint8_array && bt != napi_uint8_clamped_array) || st2 != napi_uint8_array ||
+      (of_view ? second_len != sizeof(rt_view) || napi_get_value_uint32(env, argv[4], &w) != napi_ok || napi_get_value_uint32(env, argv[5], &h) != napi_ok
+               : second_len == 0 || second_len % sizeof(rt_hit) != 0)) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  rt_view view;
+  size_t table_len[2] = {0, 0};
+  const double *table_data[2] = {nullptr, nullptr};
+  if (of_view) {
+    memcpy(&view, second_data, sizeof view);
+    view.lon = view.lat = nullptr;
+    table_data[0] = f64_array(env, argv[2], &table_len[0]); table_data[1] = f64_array(env, argv[3], &table_len[1]);
+    if (view.model == RT_VIEW_EQUIRECT && (table_len[0] != 2u * (size_t)w || table_len[1] != 2u * (size_t)h)) {
+      napi_throw_type_error(env, nullptr, "gatherView: an equirect view needs lon and lat, Float64Arrays of 2 w and 2 h numbers");
+      return nullptr;
+    }
+  }
+  struct rt_gather a;
+  memset(&a, 0, sizeof a);
+  size_t len = 0;
+  double base = 0.0;
+  const double *dirs = f64_array(env, argv[at], &len);
+  bool want[2] = {false, false};
+  if (!dirs || len == 0 || len % 3u != 0 || len / 3u > 65536u || napi_get_value_uint32(env, argv[at + 1], &a.n_samples) != napi_ok ||
+      napi_get_value_uint32(env, argv[at + 2], &a.stride) != napi_ok || napi_get_value_uint32(env, argv[at + 3], &a.segs) != napi_ok ||
+      napi_get_value_double(env, argv[at + 4], &base) != napi_ok || !(base >= 0.0 && base <= 9007199254740992.0) ||
+      napi_get_value_uint32(env, argv[at + 5], &a.pix_base) != napi_ok || napi_get_value_uint32(env, argv[at + 6], &a.pix_stride) != napi_ok ||
+      napi_get_value_bool(env, argv[at + 7], &want[0]) != napi_ok || napi_get_value_bool(env, argv[at + 8], &want[1]) != napi_ok) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  a.n_dirs = (uint32_t)(len / 3u);
+  a.base = (uint64_t)base;
+  const bool sized = !of_view || (w != 0 && h != 0 && (uint64_t)w * h < (1ull << 31));   // (anything else the library refuses: no buffer is sized from it)
+  const size_t n = of_view ? (sized ? (size_t)w * h : 0) : second_len / sizeof(rt_hit);
+  // the library wants the blob, the records and the tables 8-byte aligned: one aligned copy holds them
+  const size_t blob_room = (blob_len + 15) & ~(size_t)15, lon_room = table_len[0] * 8u, lat_room = table_len[1] * 8u;
+  const size_t rest = of_view ? lon_room + lat_room + 16u : ((second_len + 15) & ~(size_t)15);
+  uint8_t *mem = (uint8_t *)aligned_alloc(16, blob_room + rest);
+  napi_value abs[2] = {nullptr, nullptr};
+  void *p[2] = {nullptr, nullptr};
+  const size_t each[2] = {24u, 4u};
+  bool ok = mem != nullptr;
+  for (int i = 0; i < 2 && ok; i++) if (want[i]) ok = napi_create_arraybuffer(env, n * each[i], &p[i], &abs[i]) == napi_ok;
+  if (!ok) {
+    free(mem);
+    napi_throw_error(env, nullptr, "gather: out of memory");
+    return nullptr;
+  }
+  memcpy(mem, blob_data, blob_len);
+  const rt_gather_outputs out = {(double *)p[0], (uint32_t *)p[1]};
+  rt_stats st;
+  int rc;
+  if (of_view) {
+    if (view.model == RT_VIEW_EQUIRECT) {
+      memcpy(mem + blob_room, table_data[0], lon_room);
+      memcpy(mem + blob_room + lon_room, table_data[1], lat_room);
+      view.lon = (const double *)(mem + blob_room);
+      view.lat = (const double *)(mem + blob_room + lon_room);
+    }
+    rc = rt_gather_view(mem, blob_len, &view, w, h, &a, dirs, &out, &st);
+  } else {
+    memcpy(mem + blob_room, second_data, second_len);
+    rc = rt_gather(mem, blob_len, &a, dirs, n, (const rt_hit *)(mem + blob_room), &out, &st);
+  }
+  free(mem);
+  if (rc != RT_OK) return throw_rt(env, of_view ? "rt_gather_view" : "rt_gather", rc);
+  napi_value res, v;
+  napi_create_object(env, &res);
+  if (want[0]) napi_create_typedarray(env, napi_float64_array, 3 * n, abs[0], 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "rgb", v);
+  if (want[1]) napi_create_typedarray(env, napi_uint8_clamped_array, 4 * n, abs[1], 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "rgba", v);
+  napi_create_double(env, st.kernel_ms, &v); napi_set_named_property(env, res, "kernel_ms", v);
+  return res;
+}
+napi_value Gather(napi_env env, napi_callback_info info) { return gather_call(env, info, false); }
+napi_value GatherView(napi_env env, napi_callback_info info) { return gather_call(env, info, true); }
+
 // ---- sampled lights (include/rt_hip.h: struct rt_lighting)
 // lightingOffsets(n): the spiral over the unit sphere (rt_lighting_sphere_offsets) as a Float64Array of 3 n numbers
 napi_value LightingOffsets(napi_env env, napi_callback_info info) {
@@ -1342,6 +1443,8 @@ napi_value Module(napi_env env, napi_value exports) {
       {"ambientDirs", nullptr, AmbientDirs, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ambient", nullptr, Ambient, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ambientView", nullptr, AmbientView, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"gather", nullptr, Gather, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"gatherView", nullptr, GatherView, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lightingOffsets", nullptr, LightingOffsets, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lighting", nullptr, Lighting, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lightingView", nullptr, LightingView, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -247,6 +247,19 @@ class RtLightingOutputs(C.Structure):
     _fields_ = [("diffuse", C.c_void_p), ("intensity", C.c_void_p), ("lit", C.c_void_p), ("rgba", C.c_void_p)]
 
 
+class RtGather(C.Structure):
+    """Gathered light (include/rt_hip.h struct rt_gather, 32 bytes): n_samples rays per receiver, the direction table's n_dirs entries,
+    the stride and base of the entry index e = ((base + i) * stride + s) % n_dirs, the depth `segs` of every gathered ray (0: the scene's)
+    and the stars sampler's pix = pix_base + s * pix_stride + i."""
+    _fields_ = [("n_samples", C.c_uint32), ("n_dirs", C.c_uint32), ("stride", C.c_uint32), ("segs", C.c_uint32), ("base", C.c_uint64),
+                ("pix_base", C.c_uint32), ("pix_stride", C.c_uint32)]
+
+
+class RtGatherOutputs(C.Structure):
+    """Outputs of gathered light (include/rt_hip.h rt_gather_outputs): 3 float64 rgb, uint32 rgba per receiver; NULL = not wanted."""
+    _fields_ = [("rgb", C.c_void_p), ("rgba", C.c_void_p)]
+
+
 # every symbol include/rt_hip.h declares: (restype, argtypes)
 ABI = {
     "rt_init": (C.c_int, [C.c_int]),
@@ -389,6 +402,16 @@ ABI = {
                                                C.c_int, C.POINTER(RtRayOutputs), C.POINTER(RtStats)]),
     "rt_trace_view_soft": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtLighting), C.c_void_p, C.c_uint32,
                                      C.c_uint32, C.POINTER(RtRayOutputs), C.POINTER(RtStats)]),
+    "rt_gather_validate": (C.c_int, [C.POINTER(RtGather), C.c_void_p]),
+    "rt_scene_gather_device": (C.c_int, [C.c_void_p, C.POINTER(RtGather), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtGatherOutputs),
+                                         C.c_void_p, C.POINTER(RtStats)]),
+    "rt_gather": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtGather), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(RtGatherOutputs),
+                            C.POINTER(RtStats)]),
+    "rt_gather_view_work_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rt_scene_gather_view_device": (C.c_int, [C.c_void_p, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtGather), C.c_void_p,
+                                              C.POINTER(RtGatherOutputs), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RtStats)]),
+    "rt_gather_view": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtGather), C.c_void_p,
+                                 C.POINTER(RtGatherOutputs), C.POINTER(RtStats)]),
 }
 
 RT_MAX_SEGS = 16
@@ -822,6 +845,36 @@ class Renderer:
         rc = self.lib.rt_scene_trace_view_soft_device(self.handle, C.byref(view), w, h, C.byref(a), C.c_void_p(offs_ptr or 0), levels, segs, C.byref(out),
                                                       C.c_void_p(work_ptr or 0), work_bytes, C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
         _check(self.lib, rc, "rt_scene_trace_view_soft_device")
+        return st
+
+    def gather(self, n, hits_ptr, dirs_ptr, n_dirs, n_samples, rgb_ptr, rgba_ptr, stride=1, segs=0, base=0, pix_base=0, pix_stride=None, order_ptr=0,
+               stream=None, want_stats=False):
+        """Gathered light of n receivers (HIT_DTYPE records, DEVICE) in ONE fused kernel: per receiver n_samples rays leave the point along
+        the directions ambient_segments defines (table dirs_ptr: DEVICE, n_dirs entries), each traced as trace_rays traces any ray (depth
+        `segs`, 0 = the scene's; no sphere left out) with the scene's CURRENT spheres, lights, textures and stars seed, and their mean
+        goes into rgb_ptr (3 float64 per receiver) and rgba_ptr (uint32, the store rule) - DEVICE buffers, 0 / None = not wanted.  No
+        segment and no per-sample colour exists in memory.  The stars sampler's pix of sample s of receiver i is
+        pix_base + s pix_stride + i (pix_stride None = n).  order_ptr as ambient takes it."""
+        a = RtGather(n_samples, n_dirs, stride, segs, base, pix_base, n if pix_stride is None else pix_stride)
+        out = RtGatherOutputs(rgb_ptr or None, rgba_ptr or None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_gather_device(self.handle, C.byref(a), C.c_void_p(dirs_ptr or 0), n, C.c_void_p(hits_ptr or 0), C.c_void_p(order_ptr or 0),
+                                             C.byref(out), C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_gather_device")
+        return st
+
+    def gather_view(self, view, w, h, dirs_ptr, n_dirs, n_samples, rgb_ptr, rgba_ptr, work_ptr, work_bytes, stride=1, segs=0, base=0, pix_base=0,
+                    pix_stride=None, stream=None, want_stats=False):
+        """gather() for what `view` sees at w x h, pixel y w + x being receiver y w + x, into DEVICE buffers in frame order: rays, hit
+        records and the gathered rays stay on the GPU, band by band in work_ptr (DEVICE, 16-byte aligned, work_bytes >= 128 w;
+        gather_view_work_bytes(w, h) is the size the library prefers).  pix_stride None = w h, the sampled view's pix = s w h + y w + x.
+        An EQUIRECT view's tables are DEVICE pointers here."""
+        a = RtGather(n_samples, n_dirs, stride, segs, base, pix_base, w * h if pix_stride is None else pix_stride)
+        out = RtGatherOutputs(rgb_ptr or None, rgba_ptr or None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_gather_view_device(self.handle, C.byref(view), w, h, C.byref(a), C.c_void_p(dirs_ptr or 0), C.byref(out),
+                                                  C.c_void_p(work_ptr or 0), work_bytes, C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_gather_view_device")
         return st
 
     def spawn_rays(self, n, nodes_ptr, child_rays_ptr, links_ptr, count_ptr, work_ptr, work_bytes, pix_ptr=0, path_ptr=0, child_pix_ptr=0,
@@ -1557,6 +1610,71 @@ def ambient_view(scene, v, w, h, n_samples, radius, dirs=None, stride=1, want=("
     _init_once(lib)
     buf = C.create_string_buffer(blob, len(blob))
     _check(lib, lib.rt_ambient_view(buf, len(blob), C.byref(v), w, h, C.byref(a), C.c_void_p(dirs.ctypes.data), C.byref(bufs), None), "rt_ambient_view")
+    return out
+
+
+# --------------------------------------------------------------------------- gathered light (include/rt_hip.h: rt_gather)
+def _gather_args(n, n_samples, dirs, stride, segs, base, pix_base, pix_stride, lib):
+    import numpy as np
+    if dirs is None:
+        dirs = ambient_dirs(n_samples, lib)
+    dirs = np.ascontiguousarray(dirs, np.float64)
+    if dirs.ndim != 2 or dirs.shape[1] != 3:
+        raise ValueError("dirs must be an (n_dirs, 3) array: local directions, z along the facing normal")
+    return RtGather(n_samples, dirs.shape[0], stride, segs, base, pix_base, n if pix_stride is None else pix_stride), dirs
+
+
+def _gather_outputs(n, want):
+    import numpy as np
+    want = set(want)
+    if not want or want - {"rgb", "rgba"}:
+        raise ValueError("want names some of 'rgb', 'rgba'")
+    out = {}
+    if "rgb" in want:
+        out["rgb"] = np.empty((n, 3), np.float64)
+    if "rgba" in want:
+        out["rgba"] = np.empty((n, 4), np.uint8)
+    return out, RtGatherOutputs(*[out[k].ctypes.data if k in out else None for k in ("rgb", "rgba")])
+
+
+def gather(scene, hits, n_samples, dirs=None, stride=1, segs=0, base=0, pix_base=0, pix_stride=None, want=("rgb",), lib=None):
+    """gather(scene, hits, n_samples) -> {"rgb": (n, 3) float64, "rgba": (n, 4) uint8} (the keys named in `want`): the light that arrives
+    at the receivers `hits` (a HIT_DTYPE array - view_hit_records, hit_records - or a list of hit dicts) from the rest of the scene, on
+    GPU 0 with rt_render's resident scene.  Per receiver n_samples rays leave the point along the directions ambient_segments defines
+    (dirs: (n_dirs, 3) local directions, None = ambient_dirs(n_samples), with which rgb is irradiance / pi; sample s of receiver i uses
+    entry ((base + i) stride + s) % n_dirs), each traced as trace_rays traces any ray - depth `segs` (0: the scene's), no sphere left out
+    - and rgb is their mean, rgba that mean as a pixel.  A miss or a NaN record gives NaN x 3 and 0, 0, 0, 255.  The stars sampler's pix of
+    sample s of receiver i is pix_base + s pix_stride + i; pix_stride None = len(hits)."""
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    h = _hits_array(hits)
+    if len(h) == 0:
+        raise ValueError("hits must not be empty")
+    a, dirs = _gather_args(len(h), n_samples, dirs, stride, segs, base, pix_base, pix_stride, lib)
+    out, bufs = _gather_outputs(len(h), want)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    _check(lib, lib.rt_gather(buf, len(blob), C.byref(a), C.c_void_p(dirs.ctypes.data), len(h), C.c_void_p(h.ctypes.data), C.byref(bufs), None), "rt_gather")
+    return out
+
+
+def gather_view_work_bytes(w, h, lib=None):
+    """Bytes of device workspace Renderer.gather_view prefers for a w x h view (host arithmetic; 0 for a size it refuses).  128 w - one
+    row - is the least it accepts."""
+    return int((lib or load_library()).rt_gather_view_work_bytes(w, h))
+
+
+def gather_view(scene, v, w, h, n_samples, dirs=None, stride=1, segs=0, base=0, pix_base=0, pix_stride=None, want=("rgba",), lib=None):
+    """gather() of what the view sees at w x h, in frame order ("rgba" (w h, 4) uint8 is the frame): the view's rays, their hit records
+    and the gathered rays are made on the GPU (rt_gather_view) - only the direction table goes up and the results come back.
+    pix_stride None = w h, the sampled view's pix = s w h + y w + x."""
+    lib = lib or load_library()
+    blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
+    a, dirs = _gather_args(w * h, n_samples, dirs, stride, segs, base, pix_base, pix_stride, lib)
+    out, bufs = _gather_outputs(w * h, want)
+    _init_once(lib)
+    buf = C.create_string_buffer(blob, len(blob))
+    _check(lib, lib.rt_gather_view(buf, len(blob), C.byref(v), w, h, C.byref(a), C.c_void_p(dirs.ctypes.data), C.byref(bufs), None), "rt_gather_view")
     return out
 
 

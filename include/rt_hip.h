@@ -13,7 +13,7 @@
  * of the calling thread's last call.
  *
  * Threads: rt_init, rt_shutdown and rt_render serialise on an internal lock.  The device entry points
- * (rt_scene_upload, rt_render_tiles_device, rt_render_batch_device, rt_scene_trace_rays_device, rt_scene_order_rays_device, rt_scene_occlusion_device, rt_scene_ambient_device, rt_scene_ambient_view_device, rt_scene_shade_rays_device, rt_scene_spawn_rays_device, rt_scene_fold_nodes_device, rt_deinterleave_*) may be called from several
+ * (rt_scene_upload, rt_render_tiles_device, rt_render_batch_device, rt_scene_trace_rays_device, rt_scene_order_rays_device, rt_scene_occlusion_device, rt_scene_ambient_device, rt_scene_ambient_view_device, rt_scene_gather_device, rt_scene_gather_view_device, rt_scene_shade_rays_device, rt_scene_spawn_rays_device, rt_scene_fold_nodes_device, rt_deinterleave_*) may be called from several
  * threads at once; work on one HIP stream is ordered by the stream.  Launches with RT_FLAG_COUNT share one counter
  * buffer per device: one at a time per device.
  *
@@ -876,7 +876,7 @@ int rt_trace_view_samples(const void *scene_blob, size_t blob_bytes, const rt_vi
  * averaged on the GPU.  A receiver is an rt_hit record - what `hits` of rt_scene_trace_rays_device / rt_scene_trace_view_device holds,
  * already in device memory - and a scan is rt_scene_occlusion_device's, bit for bit.  A fused kernel builds each segment in registers
  * (no segment exists in memory) and stores 8 to 20 bytes per receiver; a generator kernel writes the segments of one sample as a ray
- * list for callers who want to scan, order or trace them themselves (colour bleeding).  Whether the fused kernel is faster than those
+ * list for callers who want to scan, order or trace them themselves (their trace and fold in one launch: rt_gather, below).  Whether the fused kernel is faster than those
  * parts is a matter of measurement: docs/EVIDENCE.md, "Ambient occlusion".
  *
  * Receiver i with record H and sample s; every operation in binary64 without FMA contraction, in the order written:
@@ -1187,6 +1187,84 @@ int rt_trace_rays_soft_recursive(const void *scene_blob, size_t blob_bytes, cons
  * bytes); 4 to 28 bytes per pixel come back. */
 int rt_trace_view_soft(const void *scene_blob, size_t blob_bytes, const rt_view *v, uint32_t w, uint32_t h, const struct rt_lighting *a,
                        const double *offs, uint32_t levels, uint32_t segs, const rt_ray_outputs *host_out, rt_stats *stats);
+
+/* Gathered light ("what colour arrives here from the rest of the scene"): n_samples rays per RECEIVER over the hemisphere of its facing
+ * normal, each traced as rt_scene_trace_rays_device traces any ray, averaged on the GPU - colour bleeding, irradiance and light probes,
+ * sky light from a textured skybox, a final gather for baked textures.  What rt_ambient_segments_device makes one launch per sample and
+ * a 48-byte ray in HBM for, rt_scene_trace_rays_soft_device a second launch per sample, and a host a fold over 24 n n_samples bytes,
+ * is ONE launch here: no segment and no per-sample colour exists in memory.  What it was measured at: docs/EVIDENCE.md, "Gathered light".
+ *
+ * Receiver i with record H (an rt_hit, as for rt_ambient) and sample s; binary64 without FMA contraction, in the order written:
+ *   the ray     the segment rt_ambient_segments defines for (i, s), by rt_ambient's own source: org = H.point; the direction is
+ *               dirs[e], e = (((uint64)base + (uint64)i) * (uint64)stride + (uint64)s) % (uint64)n_dirs, turned into the frame of the
+ *               facing normal l and passed through normal3D.  NO sphere is left out (there is no skip): the scene's epsilon alone
+ *               keeps the receiver's own sphere from the start, as the reference's reflected rays rely on (main.js:270, 430).
+ *   c_s         intersectWorld(segs, objects, org, dir) over the scene's CURRENT spheres, lights (where they stand), light intensity,
+ *               epsilon, miss colour, textures and stars seed; the stars sampler with pix = pix_base + s * pix_stride + i and the path
+ *               from the root 1.  Bit for bit what rt_scene_trace_rays_soft_device(levels = 0, pix_base = pix_base + s * pix_stride)
+ *               returns for that segment list.  segs 0 is the scene's depth.
+ *   rgb         acc = c_0; acc = acc + c_s for s = 1 .. n_samples - 1 in that order; acc / (double)n_samples, per channel - the fold
+ *               of a sampled view.  With a cosine-weighted table (rt_ambient_cosine_dirs) rgb is irradiance / pi.
+ *   rgba        rgb through the store rule of main.js:195-198, alpha 255, packed as rt_ambient's rgba - what
+ *               rt_scene_set_texels_device takes.
+ * A receiver that is NOT SCANNED (a miss, or a non-finite word in point or normal) has six-NaN segments: rt_scene_trace_rays_device's
+ * rule for a ray that is not finite gives every c_s NaN x 3, so rgb is NaN x 3 and rgba 0, 0, 0, 255.  A sample whose direction comes
+ * out non-finite makes that receiver's mean NaN, by the same rule.  Neither is a special case of this call.
+ * One work-item per receiver: neighbours in the list should be neighbours in space (stride 0 then gives a wave one local direction per
+ * sample), and a list below a few thousand receivers under-fills the GPU. */
+struct rt_gather {             /* 32 bytes, no padding.  A struct tag only, as struct rt_ambient: rt_gather() is the host form */
+  uint32_t n_samples;          /* 1..1024 rays per receiver */
+  uint32_t n_dirs;             /* n_samples..65536 entries of the direction table, 3 doubles each */
+  uint32_t stride;             /* rt_ambient's: see e above */
+  uint32_t segs;               /* 1..RT_MAX_SEGS, 0 = the scene's depth: intersectWorld's first argument for every gathered ray */
+  uint64_t base;               /* added to the receiver's index in e */
+  uint32_t pix_base;           /* stars: pix of sample s of receiver i = pix_base + s * pix_stride + i */
+  uint32_t pix_stride;
+};
+typedef struct rt_gather_outputs {    /* rgb: 3 doubles per receiver; rgba: one word; either may be NULL; both NULL is RT_ERR_INVALID */
+  double   *rgb;
+  uint32_t *rgba;
+} rt_gather_outputs;
+
+/* Host logic, no GPU, no rt_init.  RT_ERR_INVALID: a NULL pointer; n_samples outside 1..1024; n_dirs outside n_samples..65536;
+ * segs > RT_MAX_SEGS; a table entry with a non-finite component (`dirs`: HOST memory). */
+int rt_gather_validate(const struct rt_gather *a, const double *dirs);
+
+/* The fused kernel: d_dirs, d_hits, d_order and the arrays d_out names are DEVICE memory (d_out itself is a host struct).  d_order as
+ * for rt_scene_ambient_device: work-item j takes receiver d_order[j], an entry >= n is skipped, receiver i reads record i, uses index
+ * i in e and in pix and writes index i.  Outputs are written for every receiver an entry names (every i < n without an order) and
+ * nowhere else; an output that is NULL is not touched.  Stream, stats (pixels = n), pending-edit (spheres, lights, texels) and thread
+ * rules are rt_scene_trace_rays_soft_device's.  The kernel keeps that call's stack in scratch memory, the same bytes per lane;
+ * RT_ERR_NOMEM where the device cannot hold the reservation.
+ * RT_ERR_INVALID, before a device is touched: what rt_gather_validate refuses of `a` (the table's entries are not looked at),
+ * n outside 1..2^31 - 1, pix_base + (n_samples - 1) * pix_stride + n > 2^31 (in 64 bits: the soft call's bound, for the last sample),
+ * a NULL or misaligned d_dirs or d_hits (8 bytes), a NULL d_out or both of its outputs NULL, a misaligned rgb (8 bytes), rgba or
+ * d_order (4 bytes); then RT_ERR_STATE: a NULL scene. */
+int rt_scene_gather_device(rt_scene_dev *scene, const struct rt_gather *a, const double *d_dirs, uint64_t n, const rt_hit *d_hits,
+                           const uint32_t *d_order, const rt_gather_outputs *d_out, void *hip_stream, rt_stats *stats);
+
+/* Host form, as rt_ambient: rt_render's resident scene, every array in HOST memory, the list's own order, synchronous, on GPU 0.  The
+ * list is processed in chunks of 2^18 receivers and chunk c adds c * 2^18 to both base and pix_base: the call gives the bytes of one
+ * launch over the whole list.  RT_ERR_INVALID as above, with `dirs` judged by rt_gather_validate. */
+int rt_gather(const void *scene_blob, size_t blob_bytes, const struct rt_gather *a, const double *dirs, uint64_t n, const rt_hit *hits,
+              const rt_gather_outputs *host_out, rt_stats *stats);
+
+/* Host arithmetic: the workspace rt_scene_gather_view_device prefers for a w x h view, 128 w h bytes (rt_ambient_view_work_bytes). */
+size_t rt_gather_view_work_bytes(uint32_t w, uint32_t h);
+
+/* Gathered light of what a view sees: pixel i = y * w + x is receiver i, outputs in frame order (rgba is the w x h frame).  Bands of
+ * whole rows as rt_scene_ambient_view_device (d_work: DEVICE memory, 16-byte aligned, work_bytes >= 128 w): per band the view's rays,
+ * their hit records and the fused kernel; a band that starts at row y0 adds y0 * w to base and pix_base.  No result depends on the
+ * band size.  The bound on pix is taken with n = w h.  Everything else as rt_scene_ambient_view_device and rt_scene_gather_device. */
+int rt_scene_gather_view_device(rt_scene_dev *scene, const rt_view *v, uint32_t w, uint32_t h, const struct rt_gather *a,
+                                const double *d_dirs, const rt_gather_outputs *d_out, void *d_work, size_t work_bytes, void *hip_stream,
+                                rt_stats *stats);
+
+/* Host form on rt_render's resident scene, as rt_ambient_view: `dirs` and the outputs in HOST memory, synchronous, on GPU 0, in chunks
+ * of whole rows of at most 2^18 pixels.  No ray and no hit record crosses the link: the table goes up once, 4 to 28 bytes per pixel
+ * come back. */
+int rt_gather_view(const void *scene_blob, size_t blob_bytes, const rt_view *v, uint32_t w, uint32_t h, const struct rt_gather *a,
+                   const double *dirs, const rt_gather_outputs *host_out, rt_stats *stats);
 
 #ifdef __cplusplus
 }
