@@ -19,6 +19,9 @@
 //   rt_lighting_api.hip  sampled lights: validation, the offset table, the host probe, the launch of rt_lighting.hip, the host forms
 //   rt_relight_api.hip  relit nodes: the argument check, the launch of rt_relight.hip and its device entry point (the host forms are rt_frame.hip's)
 //   rt_soft_api.hip  the soft trace in one launch: the argument check, the launch of rt_soft.hip, its device entry points (a list, a view) and host forms
+//   rt_gather_api.hip  gathered light: the argument checks, the launch of rt_gather.hip, its device entry points (a list, a view) and host forms
+//   rt_probe_api.hip  probes: the weights' checks, the launch of rt_probe.hip on rt_gather_api.hip's launch record, the device entry point, the
+//                  host form, the spherical-harmonics weights
 // A host form is its argument checks, host_call::begin, rows for the chunk driver (chunked_list_call, chunked_view_call below) and a
 // step of launches; the band loop of a view is for_bands.
 // Which kernel a launch runs is one value (rt_device.h: rt_trace_variant), worked out once per launch; the two builds of rt_kernel.hip map
@@ -405,6 +408,25 @@ int chunked_view_call(const host_call &call, uint32_t w, uint32_t h, const chunk
   if (rc) return rc;
   call.end(stats, kernel_ms, (uint64_t)w * h);
   return RT_OK;
+}
+}  // namespace rt_api
+
+struct rt_gather_launch;     // (rt_gather.h)
+
+namespace rt_api {
+// ---- gathered light (rt_gather_api.hip), for the probe call (rt_probe_api.hip), which takes the same description and whose kernel reads
+// the same launch record: the description's fields (and a table in HOST memory), the bound on n and pix, the record of one launch, and
+// receivers [at, at + m) of a list or a view as one launch's - both indices advance with the piece
+int gather_check(const struct rt_gather *a, const char *what);
+int gather_table_check(const struct rt_gather *a, const double *dirs, const char *what);
+int gather_count_check(const struct rt_gather &a, uint64_t n, const char *what);
+int gather_record(rt_scene_dev *s, const struct rt_gather &a, const double *d_dirs, uint32_t n, const rt_hit *d_hits, const uint32_t *d_order, double *rgb,
+                  uint32_t *rgba, hipStream_t stream, struct rt_gather_launch *out);
+inline struct rt_gather gather_piece_of(const struct rt_gather &a, uint64_t at) {
+  struct rt_gather p = a;
+  p.base = a.base + at;
+  p.pix_base = a.pix_base + (uint32_t)at;                          // (at + m <= n, and pix_base + ... + n <= 2^31 was checked)
+  return p;
 }
 }  // namespace rt_api
 

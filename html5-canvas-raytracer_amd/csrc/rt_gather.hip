@@ -19,7 +19,7 @@
 // the compiler hoists the loads out of the loop and the receiver is back in registers.  The stack is the walk's: the same bytes of
 // scratch per lane as rt_soft_trace (tests/test_gather_resources.py reads both).
 // One lane per receiver under-fills the GPU below a few thousand receivers (256 CUs x 4 SIMDs x 64 lanes = 65 536 lanes make ONE wave
-// per SIMD): a short probe list is latency-bound here, and a lanes-per-sample mapping for such lists is not built.
+// per SIMD): a short probe list is latency-bound here; the lanes-per-sample mapping for such lists is rt_probe_kernel (rt_probe.hip).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stddef.h>

@@ -12,7 +12,8 @@ static_assert(sizeof(struct rt_gather) == 32 && offsetof(struct rt_gather, base)
                   sizeof(rt_gather_outputs) == 16 && sizeof(rt_hit) == 80,
               "a gather description travels as 32 bytes without padding, a receiver is 80");
 
-namespace {
+// ---- what the probe call (rt_probe_api.hip) shares: declared in rt_api_internal.h
+namespace rt_api {
 // the shared fields as rt_ambient_validate judges them, and the depth
 int gather_check(const struct rt_gather *a, const char *what) {
   if (!a) return fail(RT_ERR_INVALID, "%s: NULL gather description", what);
@@ -42,6 +43,9 @@ int gather_count_check(const struct rt_gather &a, uint64_t n, const char *what) 
   return RT_OK;
 }
 
+}  // namespace rt_api
+
+namespace {
 int gather_outputs_check(const rt_gather_outputs *out, const char *what) {
   if (!out) return fail(RT_ERR_INVALID, "%s: NULL outputs", what);
   if (!out->rgb && !out->rgba) return fail(RT_ERR_INVALID, "%s: every output is NULL", what);
@@ -65,12 +69,14 @@ int gather_scratch(size_t *out) {
   return RT_OK;
 }
 
-// the fused kernel for receivers [0, n) of d_hits with the description's base and pix_base as given
-int gather_launch(rt_scene_dev *s, const struct rt_gather &a, const double *d_dirs, uint32_t n, const rt_hit *d_hits, const uint32_t *d_order,
-                  const rt_gather_outputs &out, hipStream_t stream, rt_stats *stats) {
-  stats_clock clock;
+}  // namespace
+
+// the launch record for receivers [0, n) of d_hits with the description's base and pix_base as given: the scene's state of THIS launch,
+// taken under launch_mu behind the scene's preparation (shared with rt_probe_api.hip, whose kernel reads the same record)
+int rt_api::gather_record(rt_scene_dev *s, const struct rt_gather &a, const double *d_dirs, uint32_t n, const rt_hit *d_hits, const uint32_t *d_order,
+                          double *rgb, uint32_t *rgba, hipStream_t stream, rt_gather_launch *out) {
   const rt_scene_header &hd = s->hd;
-  rt_gather_launch L;
+  rt_gather_launch &L = *out;
   memset(&L, 0, sizeof L);
   {
     std::lock_guard<std::mutex> lk(s->launch_mu);
@@ -86,12 +92,22 @@ int gather_launch(rt_scene_dev *s, const struct rt_gather &a, const double *d_di
   L.S.epsilon = hd.epsilon;
   L.S.n_objects = hd.n_objects; L.S.n_lights = hd.n_lights;
   L.S.n_samples = 1u;                                              // (the walk's own sample loop: not entered without its relit branch)
-  L.S.order = d_order; L.S.rgb = out.rgb; L.S.rgba = out.rgba; L.S.n = n;
+  L.S.order = d_order; L.S.rgb = rgb; L.S.rgba = rgba; L.S.n = n;
   L.S.segs = a.segs ? a.segs : hd.segs;                            // the CALL's depth
   if (L.S.segs > RT_MAX_SEGS) return fail(RT_ERR_INVALID, "the gather kernel: depth %u above %u", L.S.segs, RT_MAX_SEGS);   // (the stack's size)
   L.hits = d_hits; L.dirs = d_dirs;
   L.base = a.base; L.n_samples = a.n_samples; L.n_dirs = a.n_dirs; L.stride = a.stride;
   L.pix_base = a.pix_base; L.pix_stride = a.pix_stride;
+  return RT_OK;
+}
+
+namespace {
+// the fused kernel for receivers [0, n) of d_hits with the description's base and pix_base as given
+int gather_launch(rt_scene_dev *s, const struct rt_gather &a, const double *d_dirs, uint32_t n, const rt_hit *d_hits, const uint32_t *d_order,
+                  const rt_gather_outputs &out, hipStream_t stream, rt_stats *stats) {
+  stats_clock clock;
+  rt_gather_launch L;
+  if (int rc = gather_record(s, a, d_dirs, n, d_hits, d_order, out.rgb, out.rgba, stream, &L)) return rc;
   size_t per_lane = 0;
   if (int rc = gather_scratch(&per_lane)) return rc;
   const uint64_t n_wg = ((uint64_t)n + RT_GATHER_WG - 1u) / RT_GATHER_WG;
@@ -100,14 +116,6 @@ int gather_launch(rt_scene_dev *s, const struct rt_gather &a, const double *d_di
   const int err = rt_launch_gather(&L, (void *)stream);
   if (err != 0) return fail(RT_ERR_DEVICE, "gather kernel launch: %s", hipGetErrorString((hipError_t)err));
   return clock.finish(stats, n);
-}
-
-// receivers [at, at + m) of a list or a view as one launch's: both indices advance with the piece
-struct rt_gather piece_of(const struct rt_gather &a, uint64_t at) {
-  struct rt_gather p = a;
-  p.base = a.base + at;
-  p.pix_base = a.pix_base + (uint32_t)at;                          // (at + m <= n, and pix_base + ... + n <= 2^31 was checked)
-  return p;
 }
 
 constexpr uint32_t RT_GATHER_VIEW_BAND_BYTES = 128u;      // per pixel of a band: the ray 48, its hit record 80
@@ -122,7 +130,7 @@ int gather_view_bands(rt_scene_dev *s, const rt_view *v, uint32_t w, uint32_t h,
     if (int rc = view_band_hits(s, v, w, h, y, m, rays, hits, stream)) return rc;
     const size_t at = (size_t)(y - out_row0) * w;
     const rt_gather_outputs band = {out.rgb ? out.rgb + 3u * at : nullptr, out.rgba ? out.rgba + at : nullptr};
-    return gather_launch(s, piece_of(a, (uint64_t)y * w), d_dirs, m * w, hits, nullptr, band, stream, nullptr);
+    return gather_launch(s, gather_piece_of(a, (uint64_t)y * w), d_dirs, m * w, hits, nullptr, band, stream, nullptr);
   });
 }
 
@@ -169,7 +177,7 @@ extern "C" int rt_gather(const void *blob, size_t bytes, const struct rt_gather 
   const chunk_row rows[3] = {row_in(hits, sizeof(rt_hit)), row_out(ho->rgb, 24u), row_out(ho->rgba, 4u)};
   return chunked_list_call(call, n, rows, 3, false, stats, [&](uint32_t m, uint64_t at, void *const *d, const uint32_t *, rt_stats *st) {
     const rt_gather_outputs dout = {(double *)d[1], (uint32_t *)d[2]};
-    return gather_launch(call.s, piece_of(*a, at), (const double *)d_dirs.h, m, (const rt_hit *)d[0], nullptr, dout, call.stream, st);
+    return gather_launch(call.s, gather_piece_of(*a, at), (const double *)d_dirs.h, m, (const rt_hit *)d[0], nullptr, dout, call.stream, st);
   });
 }
 

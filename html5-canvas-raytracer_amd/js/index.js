@@ -403,23 +403,54 @@ function ambientView(sceneObj, view, w, h, opts) {
 //                                  segs (default 0), base and pixBase (default 0), pixStride (default: the number of receivers; the stars
 //                                  sampler's pix of sample s of receiver i is pixBase + s pixStride + i), want (default ['rgb'])
 //   gatherView(scene, view, w, h, opts)   the same for what the view sees; pixStride defaults to w h, want to ['rgba']
+//   gather(..., {mapping: 'samples'})   the same bytes from the probe call (rt_gather_probes): one workgroup per receiver, its samples on
+//                                  lanes - for SHORT lists (light probes); the default mapping 'receivers' is the call above.  With
+//                                  opts.weights (Float64Array, one row of 1..16 numbers per table entry) want may name 'coef':
+//                                  Float64Array, per receiver, weight k and channel the mean of weights[e_s][k] c_s, e_s being the entry
+//                                  sample s took its direction from
+//   sh9Weights(dirs)               nine real spherical-harmonics values per direction, in the header's order: a weight table
+//   probes(scene, points, opts)    light probes at points in free space ([x, y, z] each): gather with mapping 'samples', stride 0 and
+//                                  hand-made records (normal [0, 0, 1], object 0: table directions are world directions).  opts: samples
+//                                  (default 64), dirs (default lightingOffsets(samples): the whole sphere), weights, segs, pixBase, want
 const GATHER_OUTPUTS = ['rgb', 'rgba'];
-function gatherOpts(o, who, n, wantDefault) {
+function gatherOpts(o, who, n, wantDefault, outputs) {
+  const names = outputs || GATHER_OUTPUTS;
   const samples = o.samples === undefined ? 16 : o.samples, dirs = o.dirs || native().ambientDirs(samples);
   if (!(dirs instanceof Float64Array) || dirs.length === 0 || dirs.length % 3 !== 0) throw new TypeError(who + ': dirs must be a Float64Array of 3 numbers per direction');
   const want = o.want === undefined ? wantDefault : o.want;
-  if (!Array.isArray(want) || want.length === 0 || !want.every((k) => GATHER_OUTPUTS.includes(k))) throw new TypeError(who + ": want names some of 'rgb', 'rgba'");
+  if (!Array.isArray(want) || want.length === 0 || !want.every((k) => names.includes(k))) throw new TypeError(who + ': want names some of ' + names.map((k) => "'" + k + "'").join(', '));
   return [dirs, samples, o.stride === undefined ? 1 : o.stride, o.segs || 0, o.base || 0, o.pixBase || 0, o.pixStride === undefined ? n : o.pixStride,
-    ...GATHER_OUTPUTS.map((k) => want.includes(k))];
+    ...names.map((k) => want.includes(k))];
 }
 function gather(sceneObj, hits, opts) {
   if (!(hits instanceof Uint8Array ? hits.length > 0 && hits.length % HIT_BYTES === 0 : Array.isArray(hits) && hits.length > 0)) {
     throw new TypeError('gather: hits must be a non-empty array of hit objects or a Uint8Array of 80-byte records');
   }
-  const o = opts || {};
-  const args = gatherOpts(o, 'gather', hits instanceof Uint8Array ? hits.length / HIT_BYTES : hits.length, ['rgb']);
+  const o = opts || {}, n = hits instanceof Uint8Array ? hits.length / HIT_BYTES : hits.length;
+  const mapping = o.mapping === undefined ? 'receivers' : o.mapping;
+  if (mapping !== 'receivers' && mapping !== 'samples') throw new TypeError("gather: mapping is 'receivers' or 'samples'");
+  if (o.weights != null && mapping !== 'samples') throw new TypeError("gather: weights need mapping 'samples'");
+  if (mapping === 'receivers') {
+    const args = gatherOpts(o, 'gather', n, ['rgb']);
+    if (!inited) init(o.maxDevices);
+    return native().gather(new Uint8Array(flattenScene(sceneObj)), hitRecords(hits), ...args);
+  }
+  const w = o.weights == null ? null : o.weights;
+  const args = gatherOpts(o, 'gather', n, ['rgb'], w ? ['rgb', 'rgba', 'coef'] : GATHER_OUTPUTS), nDirs = args[0].length / 3;
+  if (w && !(w instanceof Float64Array && w.length > 0 && w.length % nDirs === 0 && w.length / nDirs <= 16)) {
+    throw new TypeError('gather: weights must be a Float64Array of 1..16 numbers per table entry');
+  }
+  if (w && !args[9]) throw new TypeError("gather: weights are given: want names 'coef'");
   if (!inited) init(o.maxDevices);
-  return native().gather(new Uint8Array(flattenScene(sceneObj)), hitRecords(hits), ...args);
+  return native().gatherProbes(new Uint8Array(flattenScene(sceneObj)), hitRecords(hits), args[0], w, w ? w.length / nDirs : 0, ...args.slice(1, 9), w ? args[9] : false);
+}
+function sh9Weights(dirs) { return native().sh9Weights(dirs); }
+function probes(sceneObj, points, opts) {
+  if (!Array.isArray(points) || points.length === 0 || !points.every((p) => p && p.length === 3)) throw new TypeError('probes: points must be a non-empty array of [x, y, z]');
+  const o = opts || {}, samples = o.samples === undefined ? 64 : o.samples;
+  const recs = points.map((p) => ({index: 0, inside: false, t: 0, point: p, normal: [0, 0, 1], u: 0, v: 0}));
+  return gather(sceneObj, recs, {samples, dirs: o.dirs || native().lightingOffsets(samples), weights: o.weights, segs: o.segs, pixBase: o.pixBase, stride: 0,
+    mapping: 'samples', want: o.want, maxDevices: o.maxDevices});
 }
 function gatherView(sceneObj, view, w, h, opts) {
   if (!view || !Number.isInteger(view.model)) throw new TypeError('gatherView: view must come from views.reference / pinhole / ortho / equirect');
@@ -473,4 +504,4 @@ function buildId() { return native().buildId(); }
 
 function shutdown() { if (addon) addon.shutdown(); inited = false; }
 
-module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, traceView, views, shadeRays, relightRays, primaryRays, normal3D, occlusion, lightSegments, ambient, ambientView, ambientDirs, gather, gatherView, lighting, lightingView, lightingOffsets, init, shutdown, buildId, flattenScene, scenes, native}, scene);
+module.exports = Object.assign({render, renderAsync, renderProgressive, renderHits, pick, traceRays, traceView, views, shadeRays, relightRays, primaryRays, normal3D, occlusion, lightSegments, ambient, ambientView, ambientDirs, gather, gatherView, sh9Weights, probes, lighting, lightingView, lightingOffsets, init, shutdown, buildId, flattenScene, scenes, native}, scene);

@@ -1252,6 +1252,97 @@ napi_value gather_call(napi_env env, napi_callback_info info, bool of_view) {
 napi_value Gather(napi_env env, napi_callback_info info) { return gather_call(env, info, false); }
 napi_value GatherView(napi_env env, napi_callback_info info) { return gather_call(env, info, true); }
 
+// ---- probes (include/rt_hip.h: rt_probe_outputs)
+// sh9Weights(dirs: Float64Array, 3 per direction): rt_probe_sh9_weights -> Float64Array, 9 per direction
+napi_value Sh9Weights(napi_env env, napi_callback_info info) {
+  size_t argc = 1, len = 0;
+  napi_value argv[1];
+  const double *dirs = nullptr;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 1 || !(dirs = f64_array(env, argv[0], &len)) || len == 0 || len % 3u != 0 ||
+      len / 3u > 65536u) {
+    napi_throw_type_error(env, nullptr, "sh9Weights(dirs: Float64Array of 3 numbers per direction, 1..65536 directions)");
+    return nullptr;
+  }
+  napi_value ab, v;
+  void *data = nullptr;
+  NAPI_TRY(napi_create_arraybuffer(env, len * 24u, &data, &ab));
+  const int rc = rt_probe_sh9_weights((uint32_t)(len / 3u), dirs, (double *)data);
+  if (rc != RT_OK) return throw_rt(env, "rt_probe_sh9_weights", rc);
+  NAPI_TRY(napi_create_typedarray(env, napi_float64_array, 3u * len, ab, 0, &v));
+  return v;
+}
+
+// gatherProbes(blob, hits: Uint8Array (80 bytes per receiver), dirs, weights: Float64Array (nWeights per entry) | null, nWeights, nSamples, stride,
+// segs, base, pixBase, pixStride, wantRgb, wantRgba, wantCoef): rt_gather_probes
+// -> {rgb: Float64Array | null, rgba: Uint8ClampedArray | null, coef: Float64Array (3 nWeights per receiver) | null, kernel_ms}
+napi_value GatherProbes(napi_env env, napi_callback_info info) {
+  const char *who = "gatherProbes(blob: Uint8Array, hits: Uint8Array (80 bytes per receiver), dirs: Float64Array (3 per entry), weights: Float64Array (nWeights per entry) | null, "
+                    "nWeights, nSamples, stride, segs, base, pixBase, pixStride, wantRgb, wantRgba, wantCoef)";
+  size_t argc = 14;
+  napi_value argv[14];
+  bool is_ta = false, is_second = false;
+  if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 14 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
+      napi_is_typedarray(env, argv[1], &is_second) != napi_ok || !is_second) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  napi_typedarray_type bt, st2; napi_value ab; size_t off, blob_len = 0, hits_len = 0;
+  void *blob_data = nullptr, *hits_data = nullptr;
+  napi_get_typedarray_info(env, argv[0], &bt, &blob_len, &blob_data, &ab, &off);
+  napi_get_typedarray_info(env, argv[1], &st2, &hits_len, &hits_data, &ab, &off);
+  struct rt_gather a;
+  memset(&a, 0, sizeof a);
+  size_t len = 0, wlen = 0;
+  double base = 0.0;
+  uint32_t n_weights = 0;
+  const double *dirs = f64_array(env, argv[2], &len);
+  const double *weights = f64_array(env, argv[3], &wlen);          // (null: no weights)
+  bool want[3] = {false, false, false};
+  if ((bt != napi_uint8_array && bt != napi_uint8_clamped_array) || st2 != napi_uint8_array || hits_len == 0 || hits_len % sizeof(rt_hit) != 0 || !dirs || len == 0 ||
+      len % 3u != 0 || len / 3u > 65536u || napi_get_value_uint32(env, argv[4], &n_weights) != napi_ok || n_weights > RT_PROBE_MAX_WEIGHTS ||
+      wlen != (len / 3u) * n_weights || napi_get_value_uint32(env, argv[5], &a.n_samples) != napi_ok || napi_get_value_uint32(env, argv[6], &a.stride) != napi_ok ||
+      napi_get_value_uint32(env, argv[7], &a.segs) != napi_ok || napi_get_value_double(env, argv[8], &base) != napi_ok ||
+      !(base >= 0.0 && base <= 9007199254740992.0) || napi_get_value_uint32(env, argv[9], &a.pix_base) != napi_ok ||
+      napi_get_value_uint32(env, argv[10], &a.pix_stride) != napi_ok || napi_get_value_bool(env, argv[11], &want[0]) != napi_ok ||
+      napi_get_value_bool(env, argv[12], &want[1]) != napi_ok || napi_get_value_bool(env, argv[13], &want[2]) != napi_ok) {
+    napi_throw_type_error(env, nullptr, who);
+    return nullptr;
+  }
+  a.n_dirs = (uint32_t)(len / 3u);
+  a.base = (uint64_t)base;
+  const size_t n = hits_len / sizeof(rt_hit);
+  // the library wants the blob and the records 8-byte aligned: one aligned copy holds them
+  const size_t blob_room = (blob_len + 15) & ~(size_t)15;
+  uint8_t *mem = (uint8_t *)aligned_alloc(16, blob_room + ((hits_len + 15) & ~(size_t)15));
+  napi_value abs[3] = {nullptr, nullptr, nullptr};
+  void *p[3] = {nullptr, nullptr, nullptr};
+  const size_t each[3] = {24u, 4u, 24u * (size_t)n_weights};
+  bool ok = mem != nullptr;
+  for (int i = 0; i < 3 && ok; i++) if (want[i]) ok = napi_create_arraybuffer(env, n * each[i], &p[i], &abs[i]) == napi_ok;
+  if (!ok) {
+    free(mem);
+    napi_throw_error(env, nullptr, "gatherProbes: out of memory");
+    return nullptr;
+  }
+  memcpy(mem, blob_data, blob_len);
+  memcpy(mem + blob_room, hits_data, hits_len);
+  const rt_probe_outputs out = {(double *)p[0], (uint32_t *)p[1], n_weights ? (double *)p[2] : nullptr};
+  rt_stats st;
+  const int rc = rt_gather_probes(mem, blob_len, &a, dirs, n_weights ? weights : nullptr, n_weights, n, (const rt_hit *)(mem + blob_room), &out, &st);
+  free(mem);
+  if (rc != RT_OK) return throw_rt(env, "rt_gather_probes", rc);
+  napi_value res, v;
+  napi_create_object(env, &res);
+  if (want[0]) napi_create_typedarray(env, napi_float64_array, 3 * n, abs[0], 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "rgb", v);
+  if (want[1]) napi_create_typedarray(env, napi_uint8_clamped_array, 4 * n, abs[1], 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "rgba", v);
+  if (want[2]) napi_create_typedarray(env, napi_float64_array, 3 * n * n_weights, abs[2], 0, &v); else napi_get_null(env, &v);
+  napi_set_named_property(env, res, "coef", v);
+  napi_create_double(env, st.kernel_ms, &v); napi_set_named_property(env, res, "kernel_ms", v);
+  return res;
+}
+
 // ---- sampled lights (include/rt_hip.h: struct rt_lighting)
 // lightingOffsets(n): the spiral over the unit sphere (rt_lighting_sphere_offsets) as a Float64Array of 3 n numbers
 napi_value LightingOffsets(napi_env env, napi_callback_info info) {
@@ -1445,6 +1536,8 @@ napi_value Module(napi_env env, napi_value exports) {
       {"ambientView", nullptr, AmbientView, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"gather", nullptr, Gather, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"gatherView", nullptr, GatherView, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"gatherProbes", nullptr, GatherProbes, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"sh9Weights", nullptr, Sh9Weights, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lightingOffsets", nullptr, LightingOffsets, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lighting", nullptr, Lighting, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"lightingView", nullptr, LightingView, nullptr, nullptr, nullptr, napi_default, nullptr},

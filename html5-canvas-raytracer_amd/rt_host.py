@@ -260,6 +260,12 @@ class RtGatherOutputs(C.Structure):
     _fields_ = [("rgb", C.c_void_p), ("rgba", C.c_void_p)]
 
 
+class RtProbeOutputs(C.Structure):
+    """Outputs of the probe call (include/rt_hip.h rt_probe_outputs): rgb and rgba as RtGatherOutputs, coef n x n_weights x 3 float64;
+    NULL = not wanted."""
+    _fields_ = [("rgb", C.c_void_p), ("rgba", C.c_void_p), ("coef", C.c_void_p)]
+
+
 # every symbol include/rt_hip.h declares: (restype, argtypes)
 ABI = {
     "rt_init": (C.c_int, [C.c_int]),
@@ -412,7 +418,15 @@ ABI = {
                                               C.POINTER(RtGatherOutputs), C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(RtStats)]),
     "rt_gather_view": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtView), C.c_uint32, C.c_uint32, C.POINTER(RtGather), C.c_void_p,
                                  C.POINTER(RtGatherOutputs), C.POINTER(RtStats)]),
+    "rt_probes_validate": (C.c_int, [C.POINTER(RtGather), C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rt_probe_sh9_weights": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rt_scene_gather_probes_device": (C.c_int, [C.c_void_p, C.POINTER(RtGather), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                C.POINTER(RtProbeOutputs), C.c_void_p, C.POINTER(RtStats)]),
+    "rt_gather_probes": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(RtGather), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
+                                   C.POINTER(RtProbeOutputs), C.POINTER(RtStats)]),
 }
+
+RT_PROBE_MAX_WEIGHTS = 16
 
 RT_MAX_SEGS = 16
 
@@ -861,6 +875,22 @@ class Renderer:
         rc = self.lib.rt_scene_gather_device(self.handle, C.byref(a), C.c_void_p(dirs_ptr or 0), n, C.c_void_p(hits_ptr or 0), C.c_void_p(order_ptr or 0),
                                              C.byref(out), C.c_void_p(stream or 0), C.byref(st) if st is not None else None)
         _check(self.lib, rc, "rt_scene_gather_device")
+        return st
+
+    def gather_probes(self, n, hits_ptr, dirs_ptr, n_dirs, n_samples, rgb_ptr, rgba_ptr, coef_ptr=0, weights_ptr=0, n_weights=0, stride=1, segs=0, base=0,
+                      pix_base=0, pix_stride=None, order_ptr=0, stream=None, want_stats=False):
+        """gather() for a SHORT list (light probes): one workgroup per receiver with its samples on lanes; rgb_ptr and rgba_ptr receive
+        gather's bytes.  With weights_ptr (DEVICE, n_dirs rows of n_weights float64, 1..16) coef_ptr (DEVICE, n x n_weights x 3 float64)
+        receives per receiver, weight k and channel the mean of w[e_s][k] c_s, e_s being the table entry sample s took its direction
+        from - with sh9_weights of a sphere table, the probe's nine spherical-harmonics coefficients up to the factor 4 pi.  Everything
+        else as gather()."""
+        a = RtGather(n_samples, n_dirs, stride, segs, base, pix_base, n if pix_stride is None else pix_stride)
+        out = RtProbeOutputs(rgb_ptr or None, rgba_ptr or None, coef_ptr or None)
+        st = RtStats() if want_stats else None
+        rc = self.lib.rt_scene_gather_probes_device(self.handle, C.byref(a), C.c_void_p(dirs_ptr or 0), C.c_void_p(weights_ptr or 0), n_weights, n,
+                                                    C.c_void_p(hits_ptr or 0), C.c_void_p(order_ptr or 0), C.byref(out), C.c_void_p(stream or 0),
+                                                    C.byref(st) if st is not None else None)
+        _check(self.lib, rc, "rt_scene_gather_probes_device")
         return st
 
     def gather_view(self, view, w, h, dirs_ptr, n_dirs, n_samples, rgb_ptr, rgba_ptr, work_ptr, work_bytes, stride=1, segs=0, base=0, pix_base=0,
@@ -1637,25 +1667,92 @@ def _gather_outputs(n, want):
     return out, RtGatherOutputs(*[out[k].ctypes.data if k in out else None for k in ("rgb", "rgba")])
 
 
-def gather(scene, hits, n_samples, dirs=None, stride=1, segs=0, base=0, pix_base=0, pix_stride=None, want=("rgb",), lib=None):
+def gather(scene, hits, n_samples, dirs=None, stride=1, segs=0, base=0, pix_base=0, pix_stride=None, want=("rgb",), lib=None, mapping="receivers",
+           weights=None):
     """gather(scene, hits, n_samples) -> {"rgb": (n, 3) float64, "rgba": (n, 4) uint8} (the keys named in `want`): the light that arrives
     at the receivers `hits` (a HIT_DTYPE array - view_hit_records, hit_records - or a list of hit dicts) from the rest of the scene, on
     GPU 0 with rt_render's resident scene.  Per receiver n_samples rays leave the point along the directions ambient_segments defines
     (dirs: (n_dirs, 3) local directions, None = ambient_dirs(n_samples), with which rgb is irradiance / pi; sample s of receiver i uses
     entry ((base + i) stride + s) % n_dirs), each traced as trace_rays traces any ray - depth `segs` (0: the scene's), no sphere left out
     - and rgb is their mean, rgba that mean as a pixel.  A miss or a NaN record gives NaN x 3 and 0, 0, 0, 255.  The stars sampler's pix of
-    sample s of receiver i is pix_base + s pix_stride + i; pix_stride None = len(hits)."""
+    sample s of receiver i is pix_base + s pix_stride + i; pix_stride None = len(hits).
+    mapping: "receivers" (one lane per receiver: rt_gather, for lists of thousands) or "samples" (one workgroup per receiver, its samples
+    on lanes: rt_gather_probes, for short lists - the same bytes; docs/EVIDENCE.md, "Probes", has the crossover).  weights: an
+    (n_dirs, n_weights) float64 table, n_weights 1..16, with mapping "samples" only; `want` may then name "coef": (n, n_weights, 3)
+    float64, the mean over the samples of weights[e_s][k] c_s (e_s: the entry sample s took its direction from)."""
+    if mapping not in ("receivers", "samples"):
+        raise ValueError("mapping is 'receivers' or 'samples'")
+    if weights is not None and mapping != "samples":
+        raise ValueError("weights need mapping='samples'")
     lib = lib or load_library()
     blob = scene if isinstance(scene, (bytes, bytearray)) else flatten_scene(scene)
     h = _hits_array(hits)
     if len(h) == 0:
         raise ValueError("hits must not be empty")
     a, dirs = _gather_args(len(h), n_samples, dirs, stride, segs, base, pix_base, pix_stride, lib)
-    out, bufs = _gather_outputs(len(h), want)
+    if mapping == "receivers":
+        out, bufs = _gather_outputs(len(h), want)
+        _init_once(lib)
+        buf = C.create_string_buffer(blob, len(blob))
+        _check(lib, lib.rt_gather(buf, len(blob), C.byref(a), C.c_void_p(dirs.ctypes.data), len(h), C.c_void_p(h.ctypes.data), C.byref(bufs), None), "rt_gather")
+        return out
+    import numpy as np
+    n_weights = 0
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, np.float64)
+        if weights.ndim != 2 or weights.shape[0] != dirs.shape[0]:
+            raise ValueError("weights must be an (n_dirs, n_weights) array: one row per table entry")
+        n_weights = weights.shape[1]
+    want = set(want)
+    if "coef" in want and weights is None:
+        raise ValueError("'coef' needs weights")
+    if weights is not None and "coef" not in want:
+        raise ValueError("weights are given: want names 'coef'")
+    out, plain = _gather_outputs(len(h), want - {"coef"}) if want - {"coef"} else ({}, RtGatherOutputs(None, None))
+    if "coef" in want:
+        out["coef"] = np.empty((len(h), n_weights, 3), np.float64)
+    bufs = RtProbeOutputs(plain.rgb, plain.rgba, out["coef"].ctypes.data if "coef" in out else None)
     _init_once(lib)
     buf = C.create_string_buffer(blob, len(blob))
-    _check(lib, lib.rt_gather(buf, len(blob), C.byref(a), C.c_void_p(dirs.ctypes.data), len(h), C.c_void_p(h.ctypes.data), C.byref(bufs), None), "rt_gather")
+    _check(lib, lib.rt_gather_probes(buf, len(blob), C.byref(a), C.c_void_p(dirs.ctypes.data), C.c_void_p(weights.ctypes.data if weights is not None else 0),
+                                     n_weights, len(h), C.c_void_p(h.ctypes.data), C.byref(bufs), None), "rt_gather_probes")
     return out
+
+
+def sh9_weights(dirs, lib=None):
+    """-> (n, 9) float64: rt_probe_sh9_weights, the nine real spherical harmonics of bands 0..2 at the directions `dirs` (n, 3), taken as
+    given, in the header's order: 1, y, z, x, xy, yz, xz, 3 z z - 1, x x - y y, each with its constant.  A weight table for gather().
+    No GPU."""
+    import numpy as np
+    lib = lib or load_library()
+    dirs = np.ascontiguousarray(dirs, np.float64)
+    if dirs.ndim != 2 or dirs.shape[1] != 3:
+        raise ValueError("dirs must be an (n, 3) array")
+    out = np.empty((dirs.shape[0], 9), np.float64)
+    _check(lib, lib.rt_probe_sh9_weights(dirs.shape[0], C.c_void_p(dirs.ctypes.data), C.c_void_p(out.ctypes.data)), "rt_probe_sh9_weights")
+    return out
+
+
+def probe_records(points):
+    """-> the hit records probes() gathers at: `points` (n, 3) in free space as receivers with normal (0, 0, 1) on object 0.  The frame
+    of that normal is the world's axes, so a table's directions are world directions."""
+    import numpy as np
+    p = _points3(points, "points")
+    normals = np.zeros_like(p)
+    normals[:, 2] = 1.0
+    return hit_records(p, normals, np.zeros(len(p), np.int32))
+
+
+def probes(scene, points, n_samples, dirs=None, weights=None, segs=0, pix_base=0, want=("rgb",), lib=None):
+    """Light probes at `points` (n, 3) in free space: gather(mapping="samples", stride=0) of probe_records(points) - every probe takes
+    the table's first n_samples directions, as world directions.  dirs: None = lighting_offsets(n_samples), the spiral over the whole
+    sphere.  weights as gather takes them: sh9_weights(dirs) with want=("coef",) gives each probe's nine spherical-harmonics
+    coefficients per channel, up to the factor 4 pi."""
+    lib = lib or load_library()
+    if dirs is None:
+        dirs = lighting_offsets(n_samples, lib)
+    return gather(scene, probe_records(points), n_samples, dirs=dirs, stride=0, segs=segs, pix_base=pix_base, want=want, lib=lib, mapping="samples",
+                  weights=weights)
 
 
 def gather_view_work_bytes(w, h, lib=None):

@@ -1211,7 +1211,8 @@ int rt_trace_view_soft(const void *scene_blob, size_t blob_bytes, const rt_view 
  * rule for a ray that is not finite gives every c_s NaN x 3, so rgb is NaN x 3 and rgba 0, 0, 0, 255.  A sample whose direction comes
  * out non-finite makes that receiver's mean NaN, by the same rule.  Neither is a special case of this call.
  * One work-item per receiver: neighbours in the list should be neighbours in space (stride 0 then gives a wave one local direction per
- * sample), and a list below a few thousand receivers under-fills the GPU. */
+ * sample), and a list below a few thousand receivers under-fills the GPU: for short lists - light probes - the same result, and its
+ * weighted sums, come from rt_scene_gather_probes_device below, which puts a receiver's samples on lanes. */
 struct rt_gather {             /* 32 bytes, no padding.  A struct tag only, as struct rt_ambient: rt_gather() is the host form */
   uint32_t n_samples;          /* 1..1024 rays per receiver */
   uint32_t n_dirs;             /* n_samples..65536 entries of the direction table, 3 doubles each */
@@ -1265,6 +1266,61 @@ int rt_scene_gather_view_device(rt_scene_dev *scene, const rt_view *v, uint32_t 
  * come back. */
 int rt_gather_view(const void *scene_blob, size_t blob_bytes, const rt_view *v, uint32_t w, uint32_t h, const struct rt_gather *a,
                    const double *dirs, const rt_gather_outputs *host_out, rt_stats *stats);
+
+/* Probes: gathered light for SHORT receiver lists, and its weighted sums.  The description is struct rt_gather, unchanged, and rgb and
+ * rgba are rt_scene_gather_device's, BYTE FOR BYTE: the same ray, the same c_s, the same fold in the same order.  What differs is the
+ * mapping - one workgroup per receiver, the receiver's samples on its lanes (up to 1024), the colours folded through LDS by one lane
+ * per chain in list order - and the third output:
+ *   coef        n x n_weights x 3 doubles.  With e_s the table entry sample s of receiver i took its direction from (e above: the SAME
+ *               entry; d_weights has one row of n_weights contiguous doubles per table entry, n_dirs rows), binary64 without FMA
+ *               contraction, in the order written:
+ *                 acc = w[e_0][k] * c_0[ch];  acc = acc + (w[e_s][k] * c_s[ch]) for s = 1 .. n_samples - 1 in that order;
+ *                 coef[i][k][ch] = acc / (double)n_samples.
+ *               With rt_probe_sh9_weights of the table and a table of uniform sphere directions, coef is the projection of the arriving
+ *               radiance on the nine real spherical harmonics of bands 0..2 up to the measure: the radiance coefficient is 4 pi * coef,
+ *               which is the caller's multiplication.  A receiver that is not scanned has NaN in every coefficient (the sign of a NaN
+ *               product is not stated).
+ * n_weights 0: d_weights and coef must both be NULL, and the call is the plain mean.
+ * Which call to choose (measured on one MI355X, default14, docs/EVIDENCE.md, "Probes"): this call below some 300 000 receivers - 120
+ * times faster at 64 receivers x 256 samples, 5 times at 65 536 receivers -, rt_scene_gather_device above: it overtakes between 262 144
+ * and 1 048 576 receivers at 64, 256 and 1024 samples alike.  Table directions are world directions where the receiver's normal is
+ * (0, 0, 1): the frame of that normal is the world's axes. */
+typedef struct rt_probe_outputs {     /* rgb, rgba: as rt_gather_outputs; coef: n x n_weights x 3 doubles; any may be NULL, not all */
+  double   *rgb;
+  uint32_t *rgba;
+  double   *coef;
+} rt_probe_outputs;
+
+#define RT_PROBE_MAX_WEIGHTS 16u
+
+/* Host logic, no GPU, no rt_init.  RT_ERR_INVALID: what rt_gather_validate refuses of `a` and `dirs`; n_weights > 16; n_weights > 0
+ * with NULL `weights`, or n_weights 0 with `weights` given; a weight (`weights`: HOST memory, n_dirs x n_weights) that is not finite. */
+int rt_probes_validate(const struct rt_gather *a, const double *dirs, const double *weights, uint32_t n_weights);
+
+/* Nine real spherical-harmonics values per direction, for `n` directions (x, y, z) = dirs[3 i .. 3 i + 2] taken AS GIVEN (not
+ * normalised), into out[9 i .. 9 i + 8].  Host arithmetic in binary64, only *, + and -, in exactly this order:
+ *   out[0] = 0.28209479177387814
+ *   out[1] = 0.4886025119029199 * y        out[2] = 0.4886025119029199 * z        out[3] = 0.4886025119029199 * x
+ *   out[4] = 1.0925484305920792 * (x * y)  out[5] = 1.0925484305920792 * (y * z)  out[6] = 1.0925484305920792 * (x * z)
+ *   out[7] = 0.31539156525252005 * ((3.0 * (z * z)) - 1.0)
+ *   out[8] = 0.5462742152960396 * ((x * x) - (y * y))
+ * RT_ERR_INVALID: a NULL pointer, n == 0 or n > 65536. */
+int rt_probe_sh9_weights(uint32_t n, const double *dirs, double *out);
+
+/* The probe kernel: d_dirs, d_weights, d_hits, d_order and the arrays d_out names are DEVICE memory (d_out itself is a host struct).
+ * d_order, the outputs written, stream, stats (pixels = n), pending-edit and thread rules and RT_ERR_NOMEM are
+ * rt_scene_gather_device's; one workgroup per entry of the list, 24 n_samples bytes of LDS each.
+ * RT_ERR_INVALID, before a device is touched: everything rt_scene_gather_device refuses (with every output NULL in place of both),
+ * n_weights > 16, d_weights and coef not both given or both absent, n_weights 0 with either given or > 0 with neither, a misaligned
+ * coef or d_weights (8 bytes); then RT_ERR_STATE: a NULL scene.  The weights in DEVICE memory are not looked at. */
+int rt_scene_gather_probes_device(rt_scene_dev *scene, const struct rt_gather *a, const double *d_dirs, const double *d_weights,
+                                  uint32_t n_weights, uint64_t n, const rt_hit *d_hits, const uint32_t *d_order,
+                                  const rt_probe_outputs *d_out, void *hip_stream, rt_stats *stats);
+
+/* Host form, as rt_gather: every array in HOST memory, chunks of 2^18 receivers with base and pix_base advanced; `dirs` and `weights`
+ * judged by rt_probes_validate. */
+int rt_gather_probes(const void *scene_blob, size_t blob_bytes, const struct rt_gather *a, const double *dirs, const double *weights,
+                     uint32_t n_weights, uint64_t n, const rt_hit *hits, const rt_probe_outputs *host_out, rt_stats *stats);
 
 #ifdef __cplusplus
 }
