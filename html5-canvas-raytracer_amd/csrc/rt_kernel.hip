@@ -216,6 +216,27 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, rt_waves_per_eu(REFRA
   // (peer stores, a moved camera's first frame, the general kernel) do not take the path.
   [[maybe_unused]] bool uni_try = false;
   [[maybe_unused]] uint32_t cell = 0u;
+  // The few-sphere one-wave kernels keep the wave's two decisions about its entry - a sky run; one candidate: try the path - as BITS of one
+  // scalar word, set in nested branches and tested where each is used (s_bitcmp; s_cbranch_scc).  As booleans carried across the ray generation
+  // they were lane masks: seven s_cselect_b64, two s_or_b64 and three branches through vcc in every wave (docs/EVIDENCE.md, "Scalar forms").
+  // (The many-sphere one-wave kernel keeps the booleans: its code object is not part of this change.)
+  constexpr bool WAVE_FLAGS = UNI_OK && !GRID;
+  [[maybe_unused]] uint32_t wf = 0u;                      // bit 0: try the uniform-material path; bit 1: a sky run
+  if constexpr (WAVE_FLAGS) {
+    cell = (P0.cell >> rt_wave_of<W1>(tid)) & 0x11u;     // this wave's column of the block: bit 0 - inside one checker cell, bit 4 - the cell's parity
+#ifdef RT_TESTING
+    if (L.no_cells) cell = 0u;                          // test build (RT_NO_CHECKER_CELLS): every wave works its checker out per sample
+#endif
+    if (P0.sky) wf = 2u;
+    else {
+      if ((P0.cand >> 16) == 1u) wf = 1u;
+#ifdef RT_TESTING
+      if (L.no_uniform) wf = 0u;                        // test build (RT_NO_UNIFORM_BLOCKS): every wave on the general path
+#endif
+      if ((wf & 1u) == 0u) stage_issue(tid);
+    }
+    asm volatile("" : "+s"(wf));                        // opaque: a word in a scalar register, not two conditions
+  } else
   if constexpr (UNI_OK) {
     uni_try = !P0.sky && (P0.cand >> 16) == 1u;
     if constexpr (!GRID) cell = (P0.cell >> rt_wave_of<W1>(tid)) & 0x11u;     // this wave's column of the block: bit 0 - inside one checker cell, bit 4 - the cell's parity
@@ -225,14 +246,19 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, rt_waves_per_eu(REFRA
 #endif
     if (!uni_try && !P0.sky) stage_issue(tid);
   }
+  // (tested at each use, through an opaque copy of the word: one condition shared by the uses would be carried between them as a lane mask again)
+  const auto wf_bit0 = [&]() __attribute__((always_inline)) { uint32_t w_ = wf; asm volatile("" : "+s"(w_)); return (w_ & 1u) != 0u; };
+#define RT_UNI_TRY() (WAVE_FLAGS ? wf_bit0() : uni_try)
   double rgb[3];
   uint32_t cnt[3] = {0u, 0u, 0u};
   // A workgroup the table build marked as showing no sphere (rt_block.h: the cone test, made once for the workgroup's
   // box) stores the background constant: no staging, no barrier, no ray, no cull.  (Staging loads issued above - the four-wave forms -
   // are simply never waited for.)  45 % of the headline's workgroups.
-  if (P0.sky) {
+  // (WAVE_FLAGS: a sky run's wave skips the trace here and takes the constant in the epilogue, where its entry is read again - as a value that
+  // meets the traced colour behind this block, the constant was copied into vector registers in front of it, by every wave)
+  if (!WAVE_FLAGS && P0.sky) {
     rgb[0] = L.sky_rgb[0]; rgb[1] = L.sky_rgb[1]; rgb[2] = L.sky_rgb[2];
-  } else {
+  } else if (!WAVE_FLAGS || (wf & 2u) == 0u) {
   const uint32_t px = P0.px, frow = P0.frow, sub = P0.sub;
   const uint32_t sx = SS2 ? 2u * px + (sub & 1u) : px;
   const uint32_t sy = SS2 ? 2u * frow + (sub >> 1) : frow;
@@ -287,7 +313,7 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, rt_waves_per_eu(REFRA
   // away (a horizon, a mirror, stars) has touched nothing yet: it stages now and takes the general path
   [[maybe_unused]] bool uni_done = false;
   if constexpr (UNI_OK) {
-    if (uni_try) {
+    if (RT_UNI_TRY()) {
       uni_done = trace_pixel<REFRACT, COUNT, GRID, SS2, false, W1, true>(L, (const rt_mtl *)L.lds_image, (const rt_texture_desc *)((const double *)L.lds_image + mtl_words), acc,
                                                                          cull_lds, cull0, lane, 0.0, 0.0, 0.0, 0.0, o, ray, rgb, cnt, is_probe, P0.cand | (cell << 24));
       if (!uni_done) {
@@ -306,7 +332,7 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, rt_waves_per_eu(REFRA
     }
   }
   if (!uni_done) {                                    // the general path: every wave that did not shade above
-    if (!UNI_OK || !uni_try) stage_finish(tid);
+    if (!UNI_OK || !RT_UNI_TRY()) stage_finish(tid);
     if constexpr (IMAGE_IN_LDS) __syncthreads();
 
     // this wave's pixel block in the units of d0/d1 (every lane holds the same four numbers)
@@ -316,10 +342,11 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, rt_waves_per_eu(REFRA
     // (a wave the uniform-material path turned away has an entry that names its candidate: it skips the cull, the only reader of the
     // block's rectangle - which is then not computed, so that d0 / d1 are not held in registers across that attempt)
     double blk_x0 = 0.0, blk_x1 = 0.0, blk_y0 = 0.0, blk_y1 = 0.0;
-    if (!UNI_OK || !uni_try) { blk_x0 = d0 - lx; blk_x1 = blk_x0 + bw; blk_y1 = d1 + ly; blk_y0 = blk_y1 - bh; }
+    if (!UNI_OK || !RT_UNI_TRY()) { blk_x0 = d0 - lx; blk_x1 = blk_x0 + bw; blk_y1 = d1 + ly; blk_y0 = blk_y1 - bh; }
     trace_pixel<REFRACT, COUNT, GRID, SS2, false, W1>(L, mtl, tex, acc, cull_lds, cull0, lane, blk_x0, blk_x1, blk_y0, blk_y1, o, ray, rgb, cnt, is_probe, P0.cand);
   }                                                    // if (!uni_done)
   }                                                    // else of if (P0.sky)
+#undef RT_UNI_TRY
 
   // ---- A10 RGBA8 store ----
   uint32_t tid2 = threadIdx.x;
@@ -335,6 +362,11 @@ __global__ void __launch_bounds__(W1 ? 64 : RT_WG_THREADS, rt_waves_per_eu(REFRA
 #endif
   const uint32_t frame_i = blockIdx.z;
   const bool valid = P1.valid;
+  // (WAVE_FLAGS: a sky run's colour is taken HERE - see the trace's head.  Until this line `rgb` is uninitialised in a sky run's wave, and set by
+  // one of the two paths in every other wave: that rests on P1.sky == P0.sky, which holds because P1 is P0's entry read again - same slot of the
+  // launch table, which no kernel writes while a launch that reads it runs - so the wave that skipped the trace is exactly the wave that stores
+  // the constant)
+  if constexpr (WAVE_FLAGS) { if (P1.sky) { rgb[0] = L.sky_rgb[0]; rgb[1] = L.sky_rgb[1]; rgb[2] = L.sky_rgb[2]; } }
   const uint32_t r8 = to_byte(rgb[0]), g8 = to_byte(rgb[1]), b8 = to_byte(rgb[2]);
   // scatter: every frame of the batch has its own destination (the frame buffer of the rank that owns it, peer-mapped
   // over xGMI) and rows go to their place in the FRAME, so nothing is left to exchange or to de-interleave; a tile row

@@ -100,37 +100,34 @@ __device__ __forceinline__ double rt_div_const(double a, double c, double rc) {
 __device__ __attribute__((noinline)) double rt_pow_generic(double x, double e) { return pow(x, e); }
 // x^e, x > 0, of a material whose exponent e (read through `e` only when it is needed) the host classified as n = rt_spec_n(e).
 // Integer exponents (every specular_exponent of the reference scene, main.js:108-123) by square-and-multiply: <= 2*log2(n)
-// multiplies instead of OCML's ~150-instruction pow.  Every path multiplies in the same sequence - for bit i = 0, 1, ...: r *= b
-// where bit i is set, b *= b - with r = b standing for the first r = 1.0 * b (exact), so the result does not depend on the path.
+// multiplies instead of OCML's ~150-instruction pow.  The multiply sequence is stated once, in rt_spec_walk.h - for bit i = 0, 1, ...:
+// r *= b where bit i is set, b *= b between bits, with r = b standing for the first r = 1.0 * b (exact) - and every path below walks it
+// in that order, so the result does not depend on the path.
 // UNI (the uniform-material path): n comes from a scalar load - one exponent for the wave, known when the kernel is compiled - so the
 // walk below is entered without the ballot that finds that out and without the second form behind it.
-template <bool UNI = false, class EP>                                // (EP: where the material lies - const double * in any address space)
+// LADDER (the six-wave kernels: the uniform-material path, and the uniform-exponent arm of their general path): the walk as a ladder of RT_SPEC_LADDER steps on the condition code
+// (rt_spec_walk.h: two tests and at most two multiplies per bit above the lowest set one, no inner loop: an exponent of 10 is 25 scalar
+// instructions where the gap form below is 31 - measured, 6 x 51 947 per headline launch: docs/EVIDENCE.md, "Scalar forms"); exponents of more
+// bits than the ladder has steps go on in its loop.
+#include "rt_spec_walk.h"
+#define RT_SPEC_LADDER 9                                             // steps above the lowest set bit: exponents below 1024 never reach the loop
+template <bool UNI = false, bool LADDER = false, class EP>           // (EP: where the material lies - const double * in any address space)
 __device__ __forceinline__ double rt_pow_spec(double x, int32_t n, EP e) {
+  const auto mul = [](double a, double b) __attribute__((always_inline)) { return a * b; };
   const int32_t n0 = UNI ? n : __builtin_amdgcn_readfirstlane(n);
   if (UNI || __ballot(n != n0) == 0ull) {
     // every lane here has the same exponent (a wave on one sphere: nearly all of them): walk its bits with scalar control
     if (n0 < 0) return rt_pow_generic(x, *e);
-    // from set bit to set bit (the multiplies are unconditional: no select per bit)
-    uint32_t k = (uint32_t)n0;
+    const uint32_t k = (uint32_t)n0;
     if (k == 0u) return 1.0;
-    double b = x;
-    uint32_t g = __builtin_ctz(k);
-    for (uint32_t i = 0; i < g; i++) b *= b;
-    double r = b;
-    for (k >>= g + 1u; k != 0u; k >>= g + 1u) {
-      g = __builtin_ctz(k);
-      for (uint32_t i = 0; i <= g; i++) b *= b;
-      r *= b;
-    }
-    return r;
+    if constexpr (LADDER) return rt_spec_walk_ladder<RT_SPEC_LADDER>(k, x, mul);
+    // from set bit to set bit (the multiplies are unconditional: no select per bit)
+    else return rt_spec_walk_gaps(k, x, mul);
   }
   // several exponents (silhouettes, bounce nodes on different spheres): per lane, for as many bits as the longest exponent among
   // the lanes has - the loop's exit is wave-uniform, so no lane leaves it on its own
   if (n < 0) return rt_pow_generic(x, *e);
-  double r = 1.0, b = x;
-  uint32_t k = (uint32_t)n;
-  do { if (k & 1u) r *= b; b *= b; k >>= 1; } while (__ballot(k != 0u) != 0ull);
-  return r;
+  return rt_spec_walk_lanes((uint32_t)n, x, mul, [](bool more) __attribute__((always_inline)) { return __ballot(more) != 0ull; });
 }
 // main.js:62-66 — v * (1/len), len = sqrt(v.v); the zero vector is returned unchanged
 __device__ __forceinline__ v3 unit(const v3 v, double *len_out) {

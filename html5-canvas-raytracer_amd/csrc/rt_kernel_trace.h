@@ -2,6 +2,8 @@
 // statement macros of its stages, each with the locals of trace_pixel it reads and writes.
 // A fragment: included once by rt_kernel.hip, inside its anonymous namespace, after the three other fragments.
 
+#include "rt_uniform_pred.h"     // rt_nonzero_bits: the integer form of `x != 0.0` on a scalar double (RT_OA4_NONZERO)
+
 // ---- closest hit (A2 / A3) -------------------------------------------------------------------------------------------------
 // main.js:420-439, as a "candidate root" test.  With thc >= 0 (or NaN) the reference's two-armed
 // root selection reduces to: cand = (t0 < eps) ? t1 : t0, and the sphere is hit at cand unless
@@ -187,7 +189,16 @@ __device__ __forceinline__ int rt_lvl(int lv) { return lv; }
 // is already blocked (li == 0) keeps testing, and whatever it hits leaves li at 0 (0 / albedo, or 0), exactly where the
 // reference's `break` (main.js:301) left it.  The loop is then wave-uniform: the exec-mask bookkeeping of a divergent loop
 // exit - about 10 scalar instructions per iteration, for every wave - is gone (measured: +4.6 % on the headline).
-// RT_SHADOW_U(J, G): reads hi, eps, llen, objs, sv (strict build: and h); reads and writes li.
+// RT_SHADOW_U(J, G): reads hi, eps, llen, objs, sv (strict build: and h), SIX_FORMS; reads and writes li.
+// (RT_OA4_NONZERO: the occluder's transparency is a scalar load - `x != 0.0` of a scalar is a vector compare into a lane mask and a branch through vcc; the
+// few-sphere one-wave kernels test the pattern instead, on the condition code: rt_uniform_pred.h, with the argument that it is the same for every pattern)
+// (the pattern passes through an opaque scalar copy: the compiler otherwise recognises the shift-and-test as `x != 0.0` and writes the vector compare again)
+__device__ __forceinline__ bool rt_nonzero_scalar(double x) {
+  unsigned long long b_ = __builtin_bit_cast(unsigned long long, x);
+  asm volatile("" : "+s"(b_));
+  return rt_nonzero_bits(b_);
+}
+#define RT_OA4_NONZERO(X) (SIX_FORMS ? rt_nonzero_scalar(X) : ((X) != 0.0))
 #define RT_SHADOW_U(J, G)                                                                     \
             {                                                                               \
               RT_SDISC(G, tc_, disc_)                                                       \
@@ -199,7 +210,7 @@ __device__ __forceinline__ int rt_lvl(int lv) { return lv; }
                 if ((t_ < llen) && !(t_ < eps) && li != 0.0) {                              \
                   RT_PIN();                                                                 \
                   const double oa4_ = objs[J].albedo[4];                                    \
-                  li = (oa4_ != 0.0) ? rt_div(li, oa4_) : 0.0;                              \
+                  li = RT_OA4_NONZERO(oa4_) ? rt_div(li, oa4_) : 0.0;                       \
                 }                                                                           \
               }                                                                             \
             }
@@ -260,6 +271,10 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
   // nothing in its normalisation (rt_kernel_math.h: rt_min_nn ..., unit_go, with the argument for equal bytes; docs/EVIDENCE.md, "Vector diet").
   // Not the REFRACT kernels (bound by their parked stack, not examined), nor ITEM / COUNT / the strict build (rt_kernel_math.h says why).
   constexpr bool LEAN = !RT_STRICT && !REFRACT && !COUNT && !ITEM;
+  // The six-wave kernels, both paths (UNI and the general path's WAVE_NODE form): the scalar forms that are theirs alone - the specular walk's
+  // ladder (rt_pow_spec), a light's occluder set by one 64-bit shift (occ, below), the pair test on the scalar mk in the uniform path's scan too,
+  // and RT_OA4_NONZERO (above).  The four-wave forms and every other kernel keep the parent's code (docs/EVIDENCE.md, "Scalar forms").
+  [[maybe_unused]] constexpr bool SIX_FORMS = LEAN && W1 && !GRID;
   [[maybe_unused]] frame<REFRACT> stack[FOLD_FORWARD ? 1 : RT_MAX_SEGS];
   // product general kernel: nodes with BOTH a reflection and a refraction child are parked here while their
   // reflection subtree is traced (everything else needs no stack)
@@ -686,6 +701,9 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
 #if !RT_STRICT
           [[maybe_unused]] uint32_t smask = ~0u;
           if constexpr (!COUNT) { if (primary_node) smask = rt_entry_shadow_masks<W1>(L); }
+          // (SIX_FORMS) the entry's word - all ones at a node below the primary - under 32 set bits: light k's set is then ONE 64-bit shift by 16 min(k, 2) - the
+          // set of light 0 or 1, or all ones from the third light on - in place of a test of k and a test of the set, combined as lane masks
+          [[maybe_unused]] const unsigned long long smask64 = 0xffffffff00000000ull | smask;
 #endif
           for (uint32_t k = 0; k < NL; k++) {
             double llen;
@@ -743,6 +761,12 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
             // Primary hits of a block whose table entry says that NO sphere can stand between the block's hit points and light k
             // (rt_block.h, shadow masks; most floor blocks): neither grid nor scan.
             bool no_occluder = false;
+            [[maybe_unused]] uint32_t occ = ~0u;                        // (SIX_FORMS) bits 0..15: the spheres that can shadow this block from light k (a bounced node, a third light: all ones)
+            if constexpr (SIX_FORMS) {
+              occ = (uint32_t)(smask64 >> (16u * (k < 2u ? k : 2u)));
+              if constexpr (UNI) asm volatile("" : "+s"(occ));          // (opaque on the uniform path alone: a word, not two conditions.  The general path's node count is a value of a loop that lanes leave one by one, which a build may regard as per-lane: no scalar constraint there)
+              no_occluder = (occ & 0xffffu) == 0u;
+            } else
             if constexpr (!COUNT) no_occluder = primary_node && k < 2u && ((smask >> (16u * k)) & 0xffffu) == 0u;
             if (no_occluder) {
             } else
@@ -796,6 +820,8 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
                 // under it, and every pair tests it per lane.  At a bounced node mk is ~0 and the scalar test still runs: a second copy of the
                 // scan without it spilled ten scalar registers in the six-wave kernels and measured slower - docs/EVIDENCE.md)
                 [[maybe_unused]] uint32_t mk = ~0u;
+                if constexpr (SIX_FORMS) mk = occ | 0xffff0000u;      // (the same word: k >= 2 and every node below the primary have all ones)
+                else
                 if constexpr (!GRID) { if (primary_node && k < 2u) mk = (smask >> (16u * k)) | 0xffff0000u; }
                 if constexpr (!GRID) {
                   if (NS >= 2u) { if (mk & 3u) { const rt_geom g0 = gp_first.a, g1 = gp_first.b; RT_SHADOW_U(0u, g0) RT_SHADOW_U(1u, g1) } j = 2u; }
@@ -804,7 +830,8 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
                 for (; j + 2 <= NS; j += 2) {
 #if !RT_STRICT
                   // (WAVE_NODE: mk is a scalar, and the same test is a shift, an AND and a branch on the scalar unit - bits 30 and 31 of mk are set)
-                  if constexpr (WAVE_NODE) { if (((mk >> (j < 30u ? j : 30u)) & 3u) == 0u) continue; } else
+                  // (the few-sphere uniform path: its mk is a scalar word as well - occ, above - and takes the same form)
+                  if constexpr (WAVE_NODE || (UNI && !GRID)) { if (((mk >> (j < 30u ? j : 30u)) & 3u) == 0u) continue; } else
                   if (!GRID && j < 31u && ((mk >> j) & 3u) == 0u) continue;       // (sets name 16 spheres; the upper half of mk is all ones: beyond bit 30 every pair is scanned)
 #endif
                   const rt_geom_pair gp = rt_load_geom_pair32(gl, glo + j);
@@ -860,7 +887,7 @@ __device__ __forceinline__ bool trace_pixel(const rt_launch &L, const rt_mtl *mt
                 spec_m = (const rt_mtl *)((const char *)mtl + off_);
               }
               const int32_t spec_n = spec_m->spec_n;
-              if (spd > 0.0) specular += rt_pow_spec<UNI>(spd, spec_n, &spec_m->specular_exponent);
+              if (spd > 0.0) specular += rt_pow_spec<UNI, SIX_FORMS>(spd, spec_n, &spec_m->specular_exponent);
 #else
               if (spd > 0.0) specular += rt_pow(spd, m.specular_exponent);
 #endif
